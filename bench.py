@@ -6,7 +6,7 @@ search + refine, soft-bit extraction, Viterbi, merge) over synthetic white noise
 
   python bench.py --gpus 1 --steps K --warmup W                     BASELINE.json configs[1]: 60 min stereo per GPU
   python bench.py --gpus N --steps K --warmup W                     N > 1 without a launcher: bench.py starts its N ranks itself
-                                                                    (re-executes under torch.distributed.run, 127.0.0.1 rendezvous)
+                                                                    (a child process under torch.distributed.run, 127.0.0.1 rendezvous)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W     (ranks from the launcher)
   ... bench.py --gpus N --config 8h                                 configs[3]: ONE 8 h stream over the N ranks (strong scaling)
   ... bench.py --gpus N --config clips                              configs[4]: 1024 clips of 30 s over the N ranks (replicas)
@@ -17,7 +17,16 @@ and max-reduces the per-second limiter maxima; `get` keeps the reference's 30-mi
 scores / refines / decodes the start frames inside its span, the ranks that share a chunk exchange one block of overlap, their
 score segments, the refined candidates and the raw soft bits, rank 0 merges the pattern records -> weak scaling.
 
-Rank 0 prints ONE JSON line.  At N = 1 (60min) it also carries:
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (the milliseconds of one timed step), the
+workload's description (config).  A plain run does nothing but that: set up, warm up, time --steps steps, print.
+
+  --dump-outputs DIR   after the timed steps, what the timed path returned in its LAST step as DIR/<name>.npy (float32 / float64, about
+                       24 MB: a fixed, seeded sample of the watermarked PCM + its per-channel statistics over ALL samples, the pattern list);
+                       the inputs are seeded, so two builds run with the same arguments can be compared output for output
+  --full               everything else as well (untimed extra passes and runs of their own): the per-kernel HIP events in the timed
+                       steps, the one-call step, the one-lane pass behind the roofline objects, and at N = 1 (60min) the legs below
+
+With --full the line at N = 1 (60min) also carries:
   roofline       the single DEVICE KERNEL with the largest stand-alone share of GPU time (what `rocprofv3 --kernel-trace --stats` of
                  the one-lane pass ranks first): algorithmic bytes per launch / its average launch duration when the chunks run
                  one after the other (awm_ctx_set_chunk_lanes (1), untimed extra pass), HBM traffic per launch from the PMC passes
@@ -174,6 +183,69 @@ def traffic_provenance():
 def quantise16(np, x):
     """what reading back the 16 bit WAV of `audiowmark test-gen-noise` gives (truncation towards zero, / 32768)"""
     return (np.clip(np.trunc(x.astype(np.float64) * 32768.0), -32768, 32767) / 32768.0).astype(np.float32)
+
+
+DUMP_SAMPLES = 1 << 21             # --dump-outputs: watermarked samples kept (the whole batch of a clip config shares them out)
+DUMP_SEED = 2718
+PATTERN_COLUMNS = ("time", "sync_index", "sync_quality", "block_type", "type", "decode_error", "speed")
+
+
+def sample_positions(np, n_values, k, seed=DUMP_SEED):
+    """k positions out of n_values, one drawn (seeded) from each of k equal strata: the whole stream is covered, the same in every run"""
+    if n_values <= k:
+        return np.arange(n_values, dtype=np.int64)
+    edges = (np.arange(k + 1, dtype=np.int64) * n_values) // k
+    rng = np.random.default_rng(seed)
+    return edges[:-1] + (rng.random(k) * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def channel_stats(torch, pcm):
+    """[sum, sum of squares, min, max] per channel over every sample of a [frames, channels] tensor, in float64 (slabs of rows)"""
+    ch = pcm.shape[1]
+    acc = torch.zeros((ch, 4), dtype=torch.float64, device=pcm.device)
+    acc[:, 2], acc[:, 3] = float("inf"), float("-inf")
+    for i in range(0, pcm.shape[0], 1 << 24):
+        s = pcm[i:i + (1 << 24)].double()
+        acc[:, 0] += s.sum(0)
+        acc[:, 1] += (s * s).sum(0)
+        acc[:, 2] = torch.minimum(acc[:, 2], s.amin(0))
+        acc[:, 3] = torch.maximum(acc[:, 3], s.amax(0))
+    return acc.cpu().numpy()
+
+
+def dump_outputs(d, torch, pcm, pats, clip_numbers=None):
+    """--dump-outputs DIR: what the timed path returned in its last step.  `pcm` is the watermarked stream ([frames, channels]) or
+    the list of watermarked clips, `pats` its pattern list or the list of the clips' pattern lists (clip_numbers: their --test-key).
+      watermarked_pcm_sample.npy            float32 [k] | [clips, k]: the watermarked PCM at fixed seeded positions
+      watermarked_pcm_sample_positions.npy  float64 [k]: those positions among the interleaved samples of the stream / of every clip
+      watermarked_pcm_stats.npy             float64 [channels, 4] | [clips, channels, 4]: sum, sum of squares, min, max of ALL samples
+      patterns.npy                          float64 [patterns, 7] (clips: a leading column with the clip's number): PATTERN_COLUMNS
+      patterns_bits.npy                     float32 [patterns, 128]: the decoded bits (-1 behind a shorter payload)
+    Some 24 MB in all."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    clips = clip_numbers is not None
+    streams = pcm if clips else [pcm]
+    per_stream = pats if clips else [pats]
+    pos = sample_positions(np, streams[0].numel(), max(1, DUMP_SAMPLES // len(streams)))
+    idx = torch.from_numpy(pos).to(streams[0].device)
+    sample = np.stack([s.reshape(-1)[idx].cpu().numpy() for s in streams])
+    stats = np.stack([channel_stats(torch, s) for s in streams])
+    rows, bits = [], []
+    for i, plist in enumerate(per_stream):
+        for p in plist or []:
+            rows.append(([float(clip_numbers[i])] if clips else []) + [float(p[c]) for c in PATTERN_COLUMNS])
+            b = np.full(128, -1, np.float32)
+            v = [(int(h, 16) >> s) & 1 for h in p["bits"] for s in (3, 2, 1, 0)]
+            b[:len(v)] = v
+            bits.append(b)
+    out = {"watermarked_pcm_sample": (sample if clips else sample[0]).astype(np.float32),
+           "watermarked_pcm_sample_positions": pos.astype(np.float64),
+           "watermarked_pcm_stats": stats if clips else stats[0],
+           "patterns": np.array(rows, np.float64).reshape(len(rows), len(PATTERN_COLUMNS) + clips),
+           "patterns_bits": np.array(bits, np.float32).reshape(len(bits), 128)}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def cpu_baseline_and_parity(torch, awm, ctx, sample_seconds):
@@ -451,18 +523,14 @@ def e2e_leg(torch, awm, ctx, x, resident_ms):
             fmt = ["--format", "raw", "--raw-rate", str(RATE), "--raw-channels", "2", "--raw-bits", "16"]
             # measured from a FRESH small interpreter: a child forked from this process (torch: several GB resident) would
             # report the parent's resident set as its own peak (ru_maxrss covers the moment between fork and exec)
-            helper = ("import os, sys, time, json\n"
+            helper = ("import os, sys, time, json, subprocess\n"
                       "def child(cmd):\n"
-                      "    t0 = time.perf_counter(); r, w = os.pipe(); pid = os.fork()\n"
-                      "    if pid == 0:\n"
-                      "        os.dup2(w, 1); os.dup2(os.open(os.devnull, os.O_WRONLY), 2); os.close(r); os.execv(cmd[0], cmd)\n"
-                      "    os.close(w); text = b''\n"
-                      "    while True:\n"
-                      "        b = os.read(r, 1 << 16)\n"
-                      "        if not b: break\n"
-                      "        text += b\n"
-                      "    _, status, ru = os.wait4(pid, 0)\n"
-                      "    return time.perf_counter() - t0, ru.ru_maxrss / 1024.0, os.waitstatus_to_exitcode(status), text.decode(errors='replace')\n"
+                      "    t0 = time.perf_counter()\n"
+                      "    p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL)\n"
+                      "    text = p.stdout.read(); p.stdout.close()\n"
+                      "    _, status, ru = os.wait4(p.pid, 0)\n"
+                      "    p.returncode = os.waitstatus_to_exitcode(status)\n"
+                      "    return time.perf_counter() - t0, ru.ru_maxrss / 1024.0, p.returncode, text.decode(errors='replace')\n"
                       "cmds = json.loads(sys.argv[1]); print(json.dumps([child(c) for c in cmds]))\n")
             # (the queue count this process asked the HIP runtime for is its own business: the command line picks its own)
             child_env = {k: v for k, v in os.environ.items() if k not in ("GPU_MAX_HW_QUEUES", "HSA_ENABLE_SDMA")}
@@ -536,11 +604,21 @@ def free_port():
         return s.getsockname()[1]
 
 
+def visible_gpus():
+    """the node's GPU count, asked in a fresh child process: the process that starts the ranks never initialises the GPU itself"""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                       stdout=subprocess.PIPE, text=True)
+    try:
+        return int(r.stdout.split()[-1])
+    except (IndexError, ValueError):
+        return 0
+
+
 def ensure_ranks(args, argv):
     """`--gpus N` is the number of ranks of the job.  Under a launcher (WORLD_SIZE set) the two must agree; without one and
-    N > 1 this process REPLACES itself by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same
-    arguments>` (one rank per GPU, rendezvous on 127.0.0.1), so that the plain command `python bench.py --gpus N` yields a line
-    with n_gpus == ranks_seen == N.  Fails loudly when the node has fewer than N GPUs."""
+    N > 1 this process starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>`
+    as a child (one rank per GPU, rendezvous on 127.0.0.1) and exits with its status, so that the plain command
+    `python bench.py --gpus N` yields a line with n_gpus == ranks_seen == N.  Fails loudly when the node has fewer than N GPUs."""
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:
         if int(env_world) != args.gpus:
@@ -549,15 +627,15 @@ def ensure_ranks(args, argv):
     if args.gpus <= 1:
         return
     if not args.rank_check_only and not args.same_device:
-        import torch
-        have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+        have = visible_gpus()
         if have < args.gpus:
             raise SystemExit(f"bench.py: --gpus {args.gpus} but this node has {have} visible GPU(s)")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + list(argv)
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd).returncode
+    raise SystemExit(rc if rc >= 0 else 128 - rc)
 
 
 def _shard_plan(args, sharded_path, pipe, dist, world, rate):
@@ -637,7 +715,14 @@ def main():
                          "protocol itself costs when no second GPU pays anything back; never a scaling number")
     ap.add_argument("--rank-check-only", action="store_true",
                     help="start the ranks (as --gpus N does), count them over gloo and stop: CPU test of the launch path")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-kernel HIP events in the timed steps, the one-call step, the one-lane "
+                         "pass (roofline objects), the clip batch's extra passes, and at N = 1 (60min) e2e, detect_speed_config, cpu_baseline + parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     ensure_ranks(args, sys.argv[1:])
     if args.rank_check_only:
         return rank_check(args)
@@ -684,7 +769,7 @@ def main():
 
         def make_clip(k):                                    # (the C call releases the GIL: the generator runs on all host cores)
             return quantise16(np, awm.binding.gen_noise(awm.test_key(k), 2 * n_clip)).reshape(n_clip, 2)
-        with ThreadPoolExecutor(max_workers=min(64, os.cpu_count() or 8)) as pool:
+        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 8)) as pool:
             clips = [torch.from_numpy(c).to(dev) for c in pool.map(make_clip, mine)]
         outs = [torch.empty_like(c) for c in clips]
         audio_seconds = args.clips * 30.0
@@ -747,9 +832,9 @@ def main():
     for _ in range(max(0, args.warmup - 1)):
         step()
     awm.lib.awm_prof_reset(ctx._h)
-    # per-kernel HIP events: two events per launch -- noise for the 60 min kernels, a sizeable cost for the ~40 small launches
-    # of a 30 s clip, so the clips mode is timed without them
-    awm.lib.awm_prof_enable(ctx._h, 0 if args.config == "clips" else 1)
+    # per-kernel HIP events (--full only): two events per launch -- noise for the 60 min kernels, a sizeable cost for the ~40 small
+    # launches of a 30 s clip, so the clips mode is timed without them
+    awm.lib.awm_prof_enable(ctx._h, 1 if args.full and args.config != "clips" else 0)
     sync()
     t0 = time.perf_counter()
     pats = None
@@ -772,6 +857,11 @@ def main():
         elapsed = float(tmax[0].item())
         matches_local = int(t[1].item())
         ranks_seen = int(t[2].item())
+    if args.dump_outputs and rank == 0:                      # (before any extra pass of --full reuses the buffers)
+        if args.config == "clips":
+            dump_outputs(args.dump_outputs, torch, outs, pats, clip_numbers=mine)
+        else:
+            dump_outputs(args.dump_outputs, torch, out, pats)
 
     # one stream over several ranks: what every rank held, worked on and sent in the LAST timed step, so that a scaling curve explains
     # itself (plan: awm_sharded_plan, pure host; bytes: counted by the transport)
@@ -784,7 +874,7 @@ def main():
     prof = read_prof(awm, ctx)
     two_calls_ms = None
     one_call_equal = None
-    if world == 1 and not args.sharded and args.config != "clips" and not args.one_call:
+    if args.full and world == 1 and not args.sharded and args.config != "clips" and not args.one_call:
         # the same step as ONE call (awm_add_get_watermark_d; untimed extra): what the add -> get hand-over per chunk is worth
         awm.lib.awm_prof_enable(ctx._h, 0)
         def two():
@@ -801,7 +891,7 @@ def main():
         if not one_call_equal:                               # (a bug to report -- in the line, which it must not cost)
             print("bench.py: awm_add_get_watermark_d and the two separate calls disagree", file=sys.stderr)
     serial, serial_steps = {}, 3
-    if args.config != "clips":
+    if args.full and args.config != "clips":
         # the same kernels one after the other (a single lane), outside the timed region: the duration a kernel has when it
         # owns the GPU -- the number a roofline is about, and what a rocprofv3 --kernel-trace of this pass shows
         awm.lib.awm_ctx_set_chunk_lanes(ctx._h, 1)
@@ -817,6 +907,10 @@ def main():
 
     if rank == 0:
         if args.config == "clips":
+            per_clip = elapsed / args.steps * 1e3 / max(1, len(clips))
+            cfg = {"workload": workload, "parallelism": f"{world} replica(s)", "clips_with_payload": matches_local,
+                   "clip_batch_config": {"ms_per_clip_add_and_get": round(per_clip, 4)}}
+        if args.config == "clips" and args.full:
             # measured, untimed: profiled launch scopes per clip (one extra pass with the per-kernel events on), the host cost of one
             # key's tables on one core, and the same batch with ONE key for all clips (what the per-clip keys add)
             awm.lib.awm_prof_reset(ctx._h)
@@ -853,15 +947,12 @@ def main():
                 ctx.get_watermark_batch(keys[0], outs)
             sync()
             one_key = (time.perf_counter() - t0) / 2
-            per_clip = elapsed / args.steps * 1e3 / max(1, len(clips))
-            cfg = {"workload": workload, "parallelism": f"{world} replica(s)", "clips_with_payload": matches_local,
-                   "clip_batch_config": {"ms_per_clip_add_and_get": round(per_clip, 4),
-                                         "ms_per_clip_with_one_key_for_all": round(one_key * 1e3 / max(1, len(clips)), 4),
-                                         "key_tables_ms_per_clip_amortised": round(per_clip - one_key * 1e3 / max(1, len(clips)), 4),
-                                         "key_tables_host_ms_per_key_on_one_core": round(t_tab * 1e3, 3), "host_cores": os.cpu_count(),
-                                         "profiled_launch_scopes_per_clip": round(scopes / max(1, len(clips)), 3),
-                                         "kernels_one_group_of_64_clips": one_group}}
-        else:
+            cfg["clip_batch_config"].update({"ms_per_clip_with_one_key_for_all": round(one_key * 1e3 / max(1, len(clips)), 4),
+                                             "key_tables_ms_per_clip_amortised": round(per_clip - one_key * 1e3 / max(1, len(clips)), 4),
+                                             "key_tables_host_ms_per_key_on_one_core": round(t_tab * 1e3, 3), "host_cores": os.cpu_count(),
+                                             "profiled_launch_scopes_per_clip": round(scopes / max(1, len(clips)), 3),
+                                             "kernels_one_group_of_64_clips": one_group})
+        if args.config != "clips":
             matches = sum(1 for p in (pats or []) if p["bits"] == PAYLOAD)
             cfg = {"workload": workload, "parallelism": (f"one stream sharded over {world} GPU(s)" if sharded_path else "1 GPU") +
                    (" -- DEBUG: all ranks on ONE device over gloo (--same-device), not a scaling measurement" if args.same_device else ""),
@@ -938,7 +1029,8 @@ def main():
             "roofline": roofline,
             "scopes_ms_per_step": scopes,
             "viterbi_form": dict(viterbi_form(awm) or {}, forced=args.viterbi_form != "auto"),
-            "traffic_source": traffic_provenance(),
+            "traffic_source": traffic_provenance() if args.full else None,
+            "full": args.full,
         }
         if serial:
             am = serial.get("add_mix_kernel")
@@ -955,7 +1047,7 @@ def main():
             res["kernels_ms_per_step_alone"] = {k: round(v[1] / serial_steps, 3) for k, v in serial.items()}
             # algorithmic GB/s (SURVEY.md 8d bytes / stand-alone time), same definition as roofline.achieved
             res["kernels_algorithmic_GBps"] = {k: round(v[3] / (v[1] * 1e-3) / 1e9, 1) for k, v in serial.items() if v[1] > 0}
-        if single_stream:
+        if single_stream and args.full:
             if not args.no_e2e:
                 try:
                     res["e2e"] = e2e_leg(torch, awm, ctx, x, elapsed / args.steps * 1e3)

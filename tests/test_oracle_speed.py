@@ -97,12 +97,14 @@ def test_select_and_smooth_helpers():
         assert _ref.speed_smooth_best(sp, qq, 1 - 1.00005, 20) == best
 
 
-@pytest.mark.skipif(not _ref.available(), reason="oracle/_ref not built")
 def test_patient_mode_matches_reference(golden, marked):
+    """against the reference's recorded answer (speed_v1.json) and, where oracle/_ref is built, against the reference itself"""
     C = golden["channels"]
     z = orc.resample_ratio(marked, C, 1 / 1.01)
     use, best, quality = orc.detect_speed(KEY, z, C, True)
-    assert use == golden["cases"]["1.01"]["detect_patient"] == _ref.detect_speed(KEY, z, C, True)
+    assert use == golden["cases"]["1.01"]["detect_patient"]
+    if _ref.available():
+        assert use == _ref.detect_speed(KEY, z, C, True)
 
 
 def test_short_and_silent_inputs():

@@ -17,7 +17,7 @@ cd /tmp && export TMPDIR=/tmp
 export GPU_MAX_HW_QUEUES=16
 # (--viterbi-form chain: what the untraced run picks on a box with cheap launches; under the tracer a launch costs several times more and
 # the probe would choose the one-launch kernel -- profiles/rNN must show the kernels the bench line's step runs)
-B="python $R/bench.py --no-e2e --no-cpu-baseline --no-detect-speed-config --viterbi-form ${VITERBI_FORM:-chain}"
+B="python $R/bench.py --full --no-e2e --no-cpu-baseline --no-detect-speed-config --viterbi-form ${VITERBI_FORM:-chain}"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/lanes -o s -- $B --steps 5 --warmup 3 > $OUT/lanes.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/one_lane -o s -- $B --steps 5 --warmup 3 --lanes 1 > $OUT/one_lane.log 2>&1
 pass () { rocprofv3 --pmc "$@" --output-format csv -d $OUT/pmc_$1 -o s -- $B --steps 2 --warmup 1 --lanes 1 > $OUT/pmc_$1.log 2>&1; }
