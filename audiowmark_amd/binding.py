@@ -121,6 +121,13 @@ lib.awm_add_get_watermark_d.argtypes = [_vp, _vp, C.c_char_p, _vp, _vp, C.c_size
 lib.awm_resample_frames.argtypes = [_vp, C.c_size_t, C.c_int, C.c_int]
 lib.awm_resample_frames.restype = C.c_size_t
 lib.awm_resample_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t]
+lib.awm_add_watermark_payloads_d.argtypes = [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_int]
+lib.awm_debug_set_add_payloads_fused.argtypes = [C.c_int]
+lib.awm_debug_set_add_payloads_fused.restype = None
+lib.awm_debug_add_payloads_fused_in_use.argtypes = []
+lib.awm_debug_add_payloads_fused_in_use.restype = C.c_int
+lib.awm_debug_add_payloads_tile.argtypes = []
+lib.awm_debug_add_payloads_tile.restype = C.c_int
 lib.awm_add_watermark_batch_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
 lib.awm_get_watermark_batch_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
 lib.awm_add_watermark_batch_keys_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
@@ -417,6 +424,39 @@ def _pcm_shape(pcm):
     return pcm.shape[0], pcm.shape[1]
 
 
+def check_payload_outputs(payloads, pcm, outs):
+    """argument check of Context.add_watermark_payloads, before the library is called (needs no GPU): one float32 output of the input's
+    shape and device per payload; returns outs as a list (or None)"""
+    import torch
+    if pcm.dtype != torch.float32 or not pcm.is_contiguous():
+        raise ValueError("add_watermark_payloads: pcm must be a contiguous float32 tensor")
+    for i, p in enumerate(payloads):
+        if not isinstance(p, str):
+            raise TypeError(f"add_watermark_payloads: payloads[{i}] must be a hex string")
+    if outs is None:
+        return None
+    outs = list(outs)
+    if len(outs) != len(payloads):
+        raise ValueError(f"add_watermark_payloads: {len(payloads)} payloads but {len(outs)} outputs")
+    for i, o in enumerate(outs):
+        if o.dtype != torch.float32 or o.shape != pcm.shape or o.device != pcm.device or not o.is_contiguous():
+            raise ValueError(f"add_watermark_payloads: outs[{i}] must be a contiguous float32 tensor of the input's shape and device")
+    return outs
+
+
+def set_add_payloads_fused(on):
+    """(tests, measurements) add_watermark_payloads: True (default) the fused kernel, False a loop over the single-payload path"""
+    lib.awm_debug_set_add_payloads_fused(int(on))
+
+
+def add_payloads_fused_in_use():
+    """1 if the last add_watermark_payloads ran the fused kernel"""
+    return lib.awm_debug_add_payloads_fused_in_use()
+
+
+ADD_PAYLOADS_TILE = lib.awm_debug_add_payloads_tile()     # outputs per pass of the fused kernel over the input
+
+
 class Context:
     """One awm_ctx: a GPU, its stream and workspaces.  Work is enqueued on torch's current stream
     of that device so that torch.cuda events/synchronisation bracket it."""
@@ -497,6 +537,23 @@ class Context:
         frames = (C.c_size_t * len(clips))(*[s[0] for s in shapes])
         _check(lib.awm_add_watermark_batch_d(self._h, key_bytes(key), payload_hex.encode(), len(clips), src, dst, frames, ch),
                "awm_add_watermark_batch_d")
+        return outs
+
+    def add_watermark_payloads(self, key, payloads, pcm, outs=None, sample_rate=44100):
+        """add_watermark of ONE resident input with many payloads and one key (awm_add_watermark_payloads_d): the input is read and
+        transformed once per tile of ADD_PAYLOADS_TILE outputs; returns the list of outputs, outs[p] == add_watermark(key, payloads[p], pcm)."""
+        import torch
+        payloads = list(payloads)
+        outs = check_payload_outputs(payloads, pcm, outs)
+        n, ch = _pcm_shape(pcm)
+        if outs is None:
+            outs = [torch.empty_like(pcm) for _ in payloads]
+        if not payloads:
+            return []
+        hexes = (C.c_char_p * len(payloads))(*[p.encode() for p in payloads])
+        dst = (C.c_void_p * len(payloads))(*[_dev_ptr(o) for o in outs])
+        _check(lib.awm_add_watermark_payloads_d(self._h, key_bytes(key), hexes, len(payloads), _dev_ptr(pcm), dst, n, ch, sample_rate),
+               "awm_add_watermark_payloads_d")
         return outs
 
     def add_watermark_batch_keys(self, keys, payload_hex, clips, outs=None):

@@ -59,6 +59,36 @@ hipError_t launch_add_mix_batch (hipStream_t st, const DevTables& t, const AddMi
                                  int frames_pad_start);
 int        add_mix_waves_per_simd();     // occupancy the stereo kernel is built for (sizes the spans: one round of resident waves)
 
+/* K2m: K2 for ONE input stream and several outputs, each with a frame_mod table of its own (one programme, one payload per recipient).
+ * A wave fetches, windows and transforms a frame once and computes both band factors (UP and DOWN) once; band selection, inverse
+ * transform, overlap-add, mix, stores and block maxima then run once per output.  Whole streams only (frame 0 is sample 0, no halos);
+ * every channel count takes it (stereo through the paired transforms, anything else one channel per wave like K2).  out[p] is bit for bit
+ * what launch_add_mix writes with frame_mod[p]: the same device functions and expressions in the same order. */
+constexpr int ADD_MULTI_TILE = 4;        // outputs per launch (their overlap-add carry lives in registers: DESIGN.md section 9)
+struct AddMixOut
+{
+  float        *out;
+  const int8_t *frame_mod;        // device, [2 * block_frames][81]
+  unsigned int *block_max;        // float bits, n_blocks of them, or nullptr
+};
+struct AddMixMultiArgs
+{
+  const float *pcm_in;
+  long long    n_frames;          // samples per channel
+  int          n_channels;
+  float        neg_delta_up;      // as in AddMixArgs
+  float        neg_delta_down;
+  long long    n_blocks;
+  int          limiter_block;
+  int          frames_per_span;
+  int          block_frames;
+  int          frames_pad_start;
+  int          n_out;             // 1 .. ADD_MULTI_TILE
+  AddMixOut    o[ADD_MULTI_TILE];
+};
+hipError_t launch_add_mix_multi (hipStream_t st, const DevTables& t, const AddMixMultiArgs& a);
+int        add_mix_multi_waves_per_simd();   // occupancy K2m is built for (sizes its spans)
+
 /* K3: limiter ramp, in place */
 hipError_t launch_limiter (hipStream_t st, float *data, long long n_frames, int n_channels, long long first_sample,
                            const float *block_max, long long first_block, long long n_blocks,

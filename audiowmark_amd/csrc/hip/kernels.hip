@@ -3,6 +3,7 @@
 //   K1 stft_full_kernel    FFTAnalyzer::run_fft / fft_range        (reference wmcommon.cc:91-141)
 //   K2 add_mix_kernel      run_fft + apply_frame_mod + c2r + 3-frame windowed overlap-add + mix
 //                          + per-second max|x|                     (reference wmadd.cc:61-84,215-250,297-317,564-565; limiter.cc:90-97)
+//   K2m add_mix_multi_kernel  K2 for one input and several payloads: the forward half once, the rest per output (reference wmadd.cc:86-162)
 //   K3 limiter_kernel      Limiter::process_block ramp             (reference limiter.cc:99-124)
 //   K4 sync_db_kernel      SyncFinder::sync_fft (STFT -> dB, 81 bands) (reference syncfinder.cc:560-605)
 //   K5 sync_scan_kernel    SyncFinder::sync_decode + bit_quality   (reference syncfinder.cc:80-153)
@@ -692,6 +693,486 @@ launch_add_mix_batch (hipStream_t st, const DevTables& t, const AddMixArgs *args
   const long long frame_number0 = 2LL * block_frames - frames_pad_start;         // reference wmadd.cc:293-294
   hipLaunchKernelGGL (add_mix_pair_batch_kernel, dim3 (unsigned ((max_spans + WAVES - 1) / WAVES), unsigned (n_clips)), dim3 (64 * WAVES), 0, st,
                       t, args_dev, frame_number0, block_frames);
+  return hipGetLastError();
+}
+
+/* ==========================================================================================
+ * K2m: fused add of ONE stream with several payloads (kernels.hh AddMixMultiArgs)
+ *
+ * What of K2 does not depend on the payload runs once per frame: the fetch, the window, the forward transform, the real split
+ * of the 81 bands and BOTH band factors (the frame_mod tables of two payloads differ only in UP <-> DOWN of data frames,
+ * reference wmadd.cc:86-162).  Per output follow the choice of D by its table, the inverse transform, the overlap-add, the mix,
+ * the stores and the block maxima -- every expression is K2's (frame_delta / frame_delta2 / add_mix_body), so output p is bit
+ * for bit what K2 writes with table p.  The outputs of a launch are unrolled: their overlap-add carry (8 floats per lane and
+ * stereo output) stays in registers.
+ * ========================================================================================== */
+
+// where output frame m lies: in the wave's span or not, and the limiter block boundary inside it / inside frame m - 1
+struct FramePlace
+{
+  bool own, own_prev;
+  int b0, bound, pb0, pbound;       // limiter block of the frame's first sample; samples of the frame before the next block begins
+};
+
+// stores + block maxima of one output: values 0 .. 13 of o are frame m, 14 and 15 the tail of frame m - 1 (add_mix_body's, for a whole stream)
+template<int CV> __device__ __forceinline__ void
+multi_emit (float *out, unsigned int *block_max, const float (&o)[CV][16], long long m, const FramePlace& fp,
+            long long n_frames, long long n_blocks, int C, int ch0, int lane)
+{
+  float max0 = 0.f, max1 = 0.f, pmax0 = 0.f, pmax1 = 0.f;
+  const bool whole_m = (m + 1) * 1024 <= n_frames;
+  if (fp.own && whole_m && fp.bound >= 1024)
+    {
+      const long long base = m * 1024;
+#pragma unroll
+      for (int j = 0; j < 7; j++)
+        {
+          const long long ls = base + 2 * (lane + 64 * j);
+          if (CV == 2)
+            *reinterpret_cast<float4 *> (out + ls * 2) = make_float4 (o[0][2 * j], o[CV - 1][2 * j], o[0][2 * j + 1], o[CV - 1][2 * j + 1]);
+          else
+            {
+              float *p = out + ls * C + ch0;
+              p[0] = o[0][2 * j];
+              p[C] = o[0][2 * j + 1];
+            }
+#pragma unroll
+          for (int c = 0; c < CV; c++)
+            max0 = fmaxf (max0, fmaxf (fabsf (o[c][2 * j]), fabsf (o[c][2 * j + 1])));
+        }
+    }
+  else if (fp.own)
+    {
+      const long long base = m * 1024;
+#pragma unroll
+      for (int j = 0; j < 7; j++)
+        {
+          const int x = 2 * (lane + 64 * j);
+          const long long ls = base + x;
+          if (CV == 2)
+            {
+              float *p = out + ls * 2;
+              if (ls + 1 < n_frames)
+                *reinterpret_cast<float4 *> (p) = make_float4 (o[0][2 * j], o[CV - 1][2 * j], o[0][2 * j + 1], o[CV - 1][2 * j + 1]);
+              else if (ls < n_frames)
+                *reinterpret_cast<float2 *> (p) = make_float2 (o[0][2 * j], o[CV - 1][2 * j]);
+            }
+          else
+            {
+              float *p = out + ls * C + ch0;
+              if (ls < n_frames)
+                p[0] = o[0][2 * j];
+              if (ls + 1 < n_frames)
+                p[C] = o[0][2 * j + 1];
+            }
+#pragma unroll
+          for (int c = 0; c < CV; c++)
+            {
+              const float v0 = ls < n_frames ? fabsf (o[c][2 * j]) : 0.f;
+              const float v1 = ls + 1 < n_frames ? fabsf (o[c][2 * j + 1]) : 0.f;
+              if (x < fp.bound) max0 = fmaxf (max0, v0); else max1 = fmaxf (max1, v0);
+              if (x + 1 < fp.bound) max0 = fmaxf (max0, v1); else max1 = fmaxf (max1, v1);
+            }
+        }
+    }
+  if (fp.own_prev && m * 1024 <= n_frames && fp.pbound >= 1024)
+    {
+      const long long ls = (m - 1) * 1024 + 896 + 2 * lane;
+      if (CV == 2)
+        *reinterpret_cast<float4 *> (out + ls * 2) = make_float4 (o[0][14], o[CV - 1][14], o[0][15], o[CV - 1][15]);
+      else
+        {
+          float *p = out + ls * C + ch0;
+          p[0] = o[0][14];
+          p[C] = o[0][15];
+        }
+#pragma unroll
+      for (int c = 0; c < CV; c++)
+        pmax0 = fmaxf (pmax0, fmaxf (fabsf (o[c][14]), fabsf (o[c][15])));
+    }
+  else if (fp.own_prev)
+    {
+      const int x = 896 + 2 * lane;
+      const long long ls = (m - 1) * 1024 + x;
+      if (CV == 2)
+        {
+          float *p = out + ls * 2;
+          if (ls + 1 < n_frames)
+            *reinterpret_cast<float4 *> (p) = make_float4 (o[0][14], o[CV - 1][14], o[0][15], o[CV - 1][15]);
+          else if (ls < n_frames)
+            *reinterpret_cast<float2 *> (p) = make_float2 (o[0][14], o[CV - 1][14]);
+        }
+      else
+        {
+          float *p = out + ls * C + ch0;
+          if (ls < n_frames)
+            p[0] = o[0][14];
+          if (ls + 1 < n_frames)
+            p[C] = o[0][15];
+        }
+#pragma unroll
+      for (int c = 0; c < CV; c++)
+        {
+          const float v0 = ls < n_frames ? fabsf (o[c][14]) : 0.f;
+          const float v1 = ls + 1 < n_frames ? fabsf (o[c][15]) : 0.f;
+          if (x < fp.pbound) pmax0 = fmaxf (pmax0, v0); else pmax1 = fmaxf (pmax1, v0);
+          if (x + 1 < fp.pbound) pmax0 = fmaxf (pmax0, v1); else pmax1 = fmaxf (pmax1, v1);
+        }
+    }
+  if (block_max)
+    {
+      // Limiter::block_max (reference limiter.cc:90-97), see add_mix_body
+      if (fp.own)
+        {
+          max0 = wave_max (max0);
+          max1 = wave_max (max1);
+          if (lane == 0)
+            {
+              const long long i0 = fp.b0, i1 = i0 + 1;
+              if (i0 < n_blocks && max0 > 0.f) atomicMax (block_max + i0, __float_as_uint (max0));
+              if (i1 < n_blocks && max1 > 0.f) atomicMax (block_max + i1, __float_as_uint (max1));
+            }
+        }
+      if (fp.own_prev)
+        {
+          pmax0 = wave_max (pmax0);
+          pmax1 = wave_max (pmax1);
+          if (lane == 0)
+            {
+              const long long i0 = fp.pb0, i1 = i0 + 1;
+              if (i0 < n_blocks && pmax0 > 0.f) atomicMax (block_max + i0, __float_as_uint (pmax0));
+              if (i1 < n_blocks && pmax1 > 0.f) atomicMax (block_max + i1, __float_as_uint (pmax1));
+            }
+        }
+    }
+}
+
+template<int CV> __device__ __forceinline__ void
+add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a)
+{
+  constexpr int PT = ADD_MULTI_TILE;
+  __shared__ float2 s_tw[512];
+  __shared__ float2 s_tw3[512];
+  __shared__ float  s_win[1024];
+  __shared__ float2 s_twb[NB];
+  __shared__ float2 s_x[WAVES][XBUF_ELEMS];
+  __shared__ float2 s_zd[WAVES][256];
+  __shared__ float2 s_syn[4][64];                          // the lanes' synthesis window pieces (the same in every wave)
+  const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane (threadIdx.x >> 6);
+  int lane = lane0;
+  load_shared_tables (t, s_tw, s_win, s_twb);
+  fft512_load_twiddles_inverse (t.tw512, s_tw3);
+  for (int i = lane; i < 256; i += 64)
+    s_zd[wave][i] = make_float2 (0.f, 0.f);
+  // synthesis window pieces a lane needs (see add_mix_body): head = samples 2 lane, 2 lane + 1 of a frame (slots W1, W2), tail = samples
+  // 896 + 2 lane (+ 1) (slots W1, W0).  In LDS, read per output: eight registers less across the outputs
+  if (wave == 0)
+    {
+      s_syn[0][lane] = reinterpret_cast<const float2 *> (t.synth + 1024)[lane];
+      s_syn[1][lane] = reinterpret_cast<const float2 *> (t.synth + 2048)[lane];
+      s_syn[2][lane] = reinterpret_cast<const float2 *> (t.synth + 1024 + 896)[lane];
+      s_syn[3][lane] = reinterpret_cast<const float2 *> (t.synth + 896)[lane];
+    }
+  __syncthreads();
+
+  const int C = a.n_channels;
+  const int n_cg = CV == 2 ? 1 : C;
+  const long long F = (a.n_frames + 1023) / 1024;
+  const int L = a.frames_per_span;
+  const long long n_spans = (F + L - 1) / L;
+  const long long item = (long long) blockIdx.x * WAVES + wave;
+  if (item >= n_spans * n_cg)
+    return;
+  const long long span = item / n_cg;
+  const int ch0 = int (item % n_cg);
+  const long long s = span * L, e = (s + L < F) ? s + L : F;
+  float2 *xbuf = s_x[wave], *zd = s_zd[wave];
+
+  // overlap-add carry: the watermark signal's per output, the input's once
+  float head2[PT][CV][2], tail_s1[PT][CV][2], tail_in[CV][2];
+#pragma unroll
+  for (int c = 0; c < CV; c++)
+    {
+      tail_in[c][0] = tail_in[c][1] = 0.f;
+#pragma unroll
+      for (int p = 0; p < PT; p++)
+        head2[p][c][0] = head2[p][c][1] = tail_s1[p][c][0] = tail_s1[p][c][1] = 0.f;
+    }
+
+  const int BS = a.limiter_block;
+  const long long total_rows = 2LL * a.block_frames;
+  const long long frame_number0 = total_rows - a.frames_pad_start;     // reference wmadd.cc:293-294
+  const float2 zero = make_float2 (0.f, 0.f);
+  auto zposb = [] (int k) { const int p = zpos (k); return p < 128 ? p + 128 : p - 128; };
+
+  for (long long m = s - 1; m <= e; m++)
+    {
+      // (the lane index opaque per frame: twiddle factors are re-read from LDS instead of living in registers for the span, see add_mix_body)
+      lane = lane0;
+      asm volatile ("" : "+v" (lane));
+      int avail = 0;
+      if (m >= 0 && m < F)
+        {
+          const long long left = a.n_frames - m * 1024;
+          avail = left < 1024 ? int (left) : 1024;
+        }
+      float in[CV][16];
+      float2 d_up[CV][2], d_down[CV][2];             // per pass of the bands: X (|X|^-delta - 1), X (|X|^+delta - 1)
+      int mod[2];                                    // frame_mod of every output for the lane's band: 2 bits each (bit 0 touched, bit 1 UP)
+      if (avail > 0)
+        {
+          const float *src = a.pcm_in + m * 1024 * C;
+          if constexpr (CV == 2)
+            fetch_stereo (src, 0, avail, lane, in[0], in[1]);
+          else
+            fetch_channel (src, 0, avail, C, ch0, lane, in[0]);
+          const long long row = (frame_number0 + m) % total_rows;      // reference wmadd.cc:326-344
+#pragma unroll
+          for (int pass = 0; pass < 2; pass++)
+            {
+              const int k = MIN_BAND + lane + 64 * pass;
+              mod[pass] = 0;
+#pragma unroll
+              for (int p = 0; p < PT; p++)
+                if (p < a.n_out && k <= 100)
+                  {
+                    const int v = a.o[p].frame_mod[row * NB + (k - MIN_BAND)];
+                    mod[pass] |= (v ? (v == 1 ? 3 : 1) : 0) << (2 * p);
+                  }
+            }
+          // the two exponents, kept on the scalar side (hoisted out of the frame loop they take vector registers)
+          const float e_up = __int_as_float (__builtin_amdgcn_readfirstlane (__float_as_int (0.5f * a.neg_delta_up)));
+          const float e_down = __int_as_float (__builtin_amdgcn_readfirstlane (__float_as_int (0.5f * a.neg_delta_down)));
+          float2 z[CV][8];
+#pragma unroll
+          for (int c = 0; c < CV; c++)
+            window_pack (in[c], s_win, lane, z[c]);
+          if constexpr (CV == 2)
+            {
+              // frame_delta2's forward half
+              fft512_forward2 (z[0], z[1], xbuf, s_tw, lane);
+              lds_st (&xbuf[0 * 64 + lane], z[0][0]);
+              lds_st (&xbuf[1 * 64 + lane], z[0][1]);
+              lds_st (&xbuf[6 * 64 + lane], z[0][6]);
+              lds_st (&xbuf[7 * 64 + lane], z[0][7]);
+              lds_st (&xbuf[2 * 64 + lane], z[1][0]);
+              lds_st (&xbuf[3 * 64 + lane], z[1][1]);
+              lds_st (&xbuf[4 * 64 + lane], z[1][6]);
+              lds_st (&xbuf[5 * 64 + lane], z[1][7]);
+              wave_sync_pinned();
+            }
+          else
+            {
+              // frame_delta's forward half
+              fft512_forward (z[0], xbuf, s_tw, lane);
+              xbuf[0 * 64 + lane] = z[0][0];
+              xbuf[1 * 64 + lane] = z[0][1];
+              xbuf[6 * 64 + lane] = z[0][6];
+              xbuf[7 * 64 + lane] = z[0][7];
+              wave_sync();
+            }
+#pragma unroll
+          for (int pass = 0; pass < 2; pass++)
+            {
+              const int k = MIN_BAND + lane + 64 * pass;
+#pragma unroll
+              for (int c = 0; c < CV; c++)
+                d_up[c][pass] = d_down[c][pass] = zero;
+              if (k <= 100)
+                {
+                  const float2 w = s_twb[k - MIN_BAND];
+#pragma unroll
+                  for (int c = 0; c < CV; c++)
+                    {
+                      float2 X;
+                      if (CV == 2 && c == 1)
+                        X = real_split (lds_ld (&xbuf[zposb (k)]), lds_ld (&xbuf[zposb (512 - k)]), w);
+                      else if (CV == 2)
+                        X = real_split (lds_ld (&xbuf[zpos (k)]), lds_ld (&xbuf[zpos (512 - k)]), w);
+                      else
+                        X = real_split (xbuf[zpos (k)], xbuf[zpos (512 - k)], w);
+                      // apply_frame_mod (reference wmadd.cc:61-84) for both signs, see frame_delta
+                      const float abs2 = X.x * X.x + X.y * X.y;
+                      if (abs2 > 1e-14f)
+                        {
+                          const float s_up = __builtin_amdgcn_exp2f (__builtin_amdgcn_logf (abs2) * e_up) - 1.0f;
+                          const float s_down = __builtin_amdgcn_exp2f (__builtin_amdgcn_logf (abs2) * e_down) - 1.0f;
+                          d_up[c][pass] = make_float2 (X.x * s_up, X.y * s_up);
+                          d_down[c][pass] = make_float2 (X.x * s_down, X.y * s_down);
+                        }
+                    }
+                }
+            }
+        }
+      else
+        {
+#pragma unroll
+          for (int c = 0; c < CV; c++)
+#pragma unroll
+            for (int j = 0; j < 16; j++)
+              in[c][j] = 0.f;
+        }
+
+      FramePlace fp;
+      fp.own = m >= s && m < e;
+      fp.own_prev = m - 1 >= s && m - 1 < e;
+      const long long gs_m = m * 1024;
+      const long long b0 = gs_m >= 0 ? gs_m / BS : 0;
+      const long long gs_p = gs_m - 1024;
+      const long long pb0 = gs_p >= 0 ? gs_p / BS : 0;
+      fp.b0 = int (b0);
+      fp.bound = int (std::min<long long> ((b0 + 1) * BS - gs_m, 2048));        // (only compared with offsets below 1024)
+      fp.pb0 = int (pb0);
+      fp.pbound = int (std::min<long long> ((pb0 + 1) * BS - gs_p, 2048));
+
+#pragma unroll
+      for (int p = 0; p < PT; p++)
+        if (p < a.n_out)
+          {
+            lane = lane0;
+            asm volatile ("" : "+v" (lane));
+            float2 d[CV][8];
+            if (avail > 0)
+              {
+                // the output's choice of D per band (frame_mod: 1 UP, 0 untouched, anything else DOWN), then frame_delta's / frame_delta2's inverse half
+                float2 D[CV][2], O[CV][2];
+#pragma unroll
+                for (int pass = 0; pass < 2; pass++)
+                  {
+                    // (the band's twiddle again from LDS: four registers less across the outputs; lanes without a band in this pass have D == 0)
+                    const int k = MIN_BAND + lane + 64 * pass;
+                    const float2 w = s_twb[k <= 100 ? k - MIN_BAND : 0];
+#pragma unroll
+                    for (int c = 0; c < CV; c++)
+                      {
+                      // (selects per component: a choice among three float2 becomes a table in scratch memory)
+                      const bool any = (mod[pass] >> (2 * p)) & 1, up = (mod[pass] >> (2 * p)) & 2;
+                      const float dx = up ? d_up[c][pass].x : d_down[c][pass].x, dy = up ? d_up[c][pass].y : d_down[c][pass].y;
+                      D[c][pass] = make_float2 (any ? dx : 0.f, any ? dy : 0.f);
+                      O[c][pass] = cmulc (D[c][pass], w);
+                      }
+                  }
+                if constexpr (CV == 2)
+                  {
+#pragma unroll
+                    for (int c = 0; c < 2; c++)
+                      {
+                        wave_sync_pinned();
+#pragma unroll
+                        for (int pass = 0; pass < 2; pass++)
+                          {
+                            const int k = MIN_BAND + lane + 64 * pass;
+                            if (k <= 100)
+                              {
+                                lds_st (&zd[zdpos (k)],       make_float2 (D[c][pass].x - O[c][pass].y, D[c][pass].y + O[c][pass].x));
+                                lds_st (&zd[zdpos (512 - k)], make_float2 (D[c][pass].x + O[c][pass].y, O[c][pass].x - D[c][pass].y));
+                              }
+                          }
+                        wave_sync_pinned();
+                        d[c][0] = lds_ld (&zd[0 * 64 + lane]);
+                        d[c][1] = lds_ld (&zd[1 * 64 + lane]);
+                        d[c][2] = zero; d[c][3] = zero; d[c][4] = zero; d[c][5] = zero;
+                        d[c][6] = lds_ld (&zd[2 * 64 + lane]);
+                        d[c][7] = lds_ld (&zd[3 * 64 + lane]);
+                      }
+                    wave_sync_pinned();
+                    fft512_inverse2 (d[0], d[CV - 1], xbuf, s_tw, s_tw3, lane);
+                  }
+                else
+                  {
+                    wave_sync();
+#pragma unroll
+                    for (int pass = 0; pass < 2; pass++)
+                      {
+                        const int k = MIN_BAND + lane + 64 * pass;
+                        if (k <= 100)
+                          {
+                            zd[zdpos (k)]       = make_float2 (D[0][pass].x - O[0][pass].y, D[0][pass].y + O[0][pass].x);
+                            zd[zdpos (512 - k)] = make_float2 (D[0][pass].x + O[0][pass].y, O[0][pass].x - D[0][pass].y);
+                          }
+                      }
+                    wave_sync();
+                    d[0][0] = zd[0 * 64 + lane];
+                    d[0][1] = zd[1 * 64 + lane];
+                    d[0][2] = zero; d[0][3] = zero; d[0][4] = zero; d[0][5] = zero;
+                    d[0][6] = zd[2 * 64 + lane];
+                    d[0][7] = zd[3 * 64 + lane];
+                    wave_sync();
+                    fft512_inverse (d[0], xbuf, s_tw, s_tw3, lane);
+                  }
+              }
+            else
+              {
+#pragma unroll
+                for (int c = 0; c < CV; c++)
+#pragma unroll
+                  for (int j = 0; j < 8; j++)
+                    d[c][j] = zero;
+              }
+
+            // output frame m = d[m-1] W2 + d[m] W1 + d[m+1] W0 + in[m]   (reference wmadd.cc:228-238, 564-565), as add_mix_body
+            const float2 w1_head = s_syn[0][lane], w2_head = s_syn[1][lane], w1_tail = s_syn[2][lane], w0_tail = s_syn[3][lane];
+            float o[CV][16];
+#pragma unroll
+            for (int c = 0; c < CV; c++)
+              {
+                const float s1x = __fadd_rn (head2[p][c][0], __fmul_rn (d[c][0].x, w1_head.x));
+                const float s1y = __fadd_rn (head2[p][c][1], __fmul_rn (d[c][0].y, w1_head.y));
+                o[c][0] = __fadd_rn (s1x, in[c][0]);
+                o[c][1] = __fadd_rn (s1y, in[c][1]);
+                head2[p][c][0] = __fmul_rn (d[c][0].x, w2_head.x);
+                head2[p][c][1] = __fmul_rn (d[c][0].y, w2_head.y);
+#pragma unroll
+                for (int j = 1; j < 7; j++)
+                  {
+                    o[c][2 * j]     = __fadd_rn (d[c][j].x, in[c][2 * j]);
+                    o[c][2 * j + 1] = __fadd_rn (d[c][j].y, in[c][2 * j + 1]);
+                  }
+                o[c][14] = __fadd_rn (__fadd_rn (tail_s1[p][c][0], __fmul_rn (d[c][7].x, w0_tail.x)), tail_in[c][0]);
+                o[c][15] = __fadd_rn (__fadd_rn (tail_s1[p][c][1], __fmul_rn (d[c][7].y, w0_tail.y)), tail_in[c][1]);
+                tail_s1[p][c][0] = __fmul_rn (d[c][7].x, w1_tail.x);
+                tail_s1[p][c][1] = __fmul_rn (d[c][7].y, w1_tail.y);
+              }
+            multi_emit<CV> (a.o[p].out, a.o[p].block_max, o, m, fp, a.n_frames, a.n_blocks, C, ch0, lane);
+          }
+#pragma unroll
+      for (int c = 0; c < CV; c++)
+        {
+          tail_in[c][0] = in[c][14];
+          tail_in[c][1] = in[c][15];
+        }
+    }
+}
+
+// mono (and 3+ channels, a channel per wave): 41 KB of LDS per workgroup, three workgroups per CU
+__global__ void __launch_bounds__ (64 * WAVES)
+add_mix_multi_kernel (DevTables t, AddMixMultiArgs a)
+{
+  add_mix_multi_body<1> (t, a);
+}
+// stereo: three waves per SIMD (at most 168 registers)
+__global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (3, 3)))
+add_mix_multi_pair_kernel (DevTables t, AddMixMultiArgs a)
+{
+  add_mix_multi_body<2> (t, a);
+}
+int add_mix_multi_waves_per_simd() { return 3; }
+
+hipError_t
+launch_add_mix_multi (hipStream_t st, const DevTables& t, const AddMixMultiArgs& a)
+{
+  if (a.n_frames <= 0 || a.n_out <= 0)
+    return hipSuccess;
+  if (a.n_out > ADD_MULTI_TILE || a.frames_per_span < 1 || a.n_channels < 1)
+    return hipErrorInvalidValue;
+  const long long F = (a.n_frames + 1023) / 1024;
+  const long long n_spans = (F + a.frames_per_span - 1) / a.frames_per_span;
+  const long long items = n_spans * (a.n_channels == 2 ? 1 : a.n_channels);
+  const unsigned grid = unsigned ((items + WAVES - 1) / WAVES);
+  if (a.n_channels == 2)
+    hipLaunchKernelGGL (add_mix_multi_pair_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a);
+  else
+    hipLaunchKernelGGL (add_mix_multi_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a);
   return hipGetLastError();
 }
 

@@ -57,7 +57,7 @@ check_ctx (awm_ctx *ctx)
   if (int rc__ = check_ctx (ctx)) return rc__
 
 int
-frames_per_span (awm_ctx *ctx, long long n_frames1024)
+frames_per_span (awm_ctx *ctx, long long n_frames1024, int waves_per_simd = 0)       // 0: the fused add kernel's (K2) own occupancy
 {
   // Every wave streams through L frames plus 2 halo frames.  All waves of one "round" (CUs x resident waves) start
   // and finish together, so pick the number of rounds k that minimises k * (L + 2) with L = ceil (F / (k * capacity)):
@@ -70,7 +70,7 @@ frames_per_span (awm_ctx *ctx, long long n_frames1024)
       if (hipGetDeviceProperties (&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0)
         cus = prop.multiProcessorCount;
     }
-  const int capacity = cus * 4 * awmk::add_mix_waves_per_simd();       // resident waves of the fused add kernel
+  const int capacity = cus * 4 * (waves_per_simd > 0 ? waves_per_simd : awmk::add_mix_waves_per_simd());       // resident waves of the fused add kernel
   long long best_l = 4, best_cost = -1;
   for (int k = 1; k <= 16; k++)
     {
@@ -1029,6 +1029,140 @@ awm_add_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_he
   if (sample_rate != Params::mark_sample_rate)
     return add_full_rate (ctx, pcm_in_d, out_d, n_frames, n_channels, fm->dev.as<int8_t>(), params().water_delta, !params().test_no_limiter, sample_rate);
   return add_full (ctx, pcm_in_d, out_d, n_frames, n_channels, fm->dev.as<int8_t>(), params().water_delta, !params().test_no_limiter);
+}
+
+/* One input, many payloads (include/awm_hip.h).  At 44.1 kHz the payloads go through K2m in tiles of ADD_MULTI_TILE outputs: a tile pass
+ * reads the input once and transforms every frame forward once, whatever the number of its outputs; block maxima and limiter ramp are
+ * per output.  Other sample rates (and the debug toggle) loop over the single-payload path. */
+static int g_add_payloads_fused = 1, g_add_payloads_fused_in_use = 0;
+extern "C" void awm_debug_set_add_payloads_fused (int on) { g_add_payloads_fused = on; }
+extern "C" int  awm_debug_add_payloads_fused_in_use (void) { return g_add_payloads_fused_in_use; }
+extern "C" int  awm_debug_add_payloads_tile (void) { return awmk::ADD_MULTI_TILE; }
+
+int
+awm_add_watermark_payloads_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
+                              const float *pcm_in_d, float *const *out_d, size_t n_frames, int n_channels, int sample_rate)
+{
+  AWM_ENTER (ctx);
+  g_add_payloads_fused_in_use = 0;
+  if (!n_payloads || !n_frames)
+    return 0;
+  if (!key || !payload_hex || !pcm_in_d || !out_d || n_channels < 1)
+    {
+      set_error ("awm_add_watermark_payloads_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  if (ctx->snr_on)
+    {
+      set_error ("awm_add_watermark_payloads_d: not available while the SNR meter is armed (awm_ctx_snr_begin)");
+      return AWM_ERR_ARG;
+    }
+  // everything is checked before anything is enqueued: the input is read for every output, so no output may overlap it or another one
+  const size_t n_values = n_frames * size_t (n_channels);
+  auto overlap = [n_values] (const float *a, const float *b) { return a < b + n_values && b < a + n_values; };
+  for (size_t p = 0; p < n_payloads; p++)
+    {
+      if (!payload_hex[p] || !out_d[p])
+        {
+          set_error (string_printf ("awm_add_watermark_payloads_d: null pointer at index %zu", p));
+          return AWM_ERR_ARG;
+        }
+      if (parse_payload (payload_hex[p]).empty())
+        {
+          set_error (string_printf ("awm_add_watermark_payloads_d: cannot parse payload '%s' at index %zu", payload_hex[p], p));
+          return AWM_ERR_ARG;
+        }
+      if (overlap (out_d[p], pcm_in_d))
+        {
+          set_error (string_printf ("awm_add_watermark_payloads_d: output %zu overlaps the input", p));
+          return AWM_ERR_ARG;
+        }
+      for (size_t q = 0; q < p; q++)
+        if (overlap (out_d[p], out_d[q]))
+          {
+            set_error (string_printf ("awm_add_watermark_payloads_d: outputs %zu and %zu overlap", q, p));
+            return AWM_ERR_ARG;
+          }
+    }
+  const Key k = capi_key (key);
+  const double water_delta = params().water_delta;
+  const int use_limiter = !params().test_no_limiter;
+  if (n_payloads == 1 || !g_add_payloads_fused || sample_rate != Params::mark_sample_rate)
+    {
+      for (size_t p = 0; p < n_payloads; p++)
+        {
+          FrameModTable *fm = ctx->get_frame_mod (k, payload_hex[p]);
+          if (!fm)
+            return AWM_ERR_ARG;
+          const int rc = sample_rate != Params::mark_sample_rate
+                       ? add_full_rate (ctx, pcm_in_d, out_d[p], n_frames, n_channels, fm->dev.as<int8_t>(), water_delta, use_limiter, sample_rate)
+                       : add_full (ctx, pcm_in_d, out_d[p], n_frames, n_channels, fm->dev.as<int8_t>(), water_delta, use_limiter);
+          if (rc)
+            return rc;
+        }
+      return 0;
+    }
+
+  hipStream_t st = ctx->stream;
+  const size_t n_blocks = n_frames / LIMITER_BLOCK + 2;
+  float *block_max = nullptr;
+  size_t tab_entries = 0;
+  if (use_limiter)
+    {
+      if (int rc = ctx->ws_block_max.reserve (n_payloads * n_blocks * sizeof (float))) return rc;
+      block_max = ctx->ws_block_max.as<float>();
+      unsigned int bits;
+      std::memcpy (&bits, &LIMITER_CEILING, sizeof (bits));
+      AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (block_max), bits, n_payloads * n_blocks));
+      tab_entries = awmk::limiter_tab_entries ((long long) n_frames, 0, LIMITER_BLOCK);
+      if (int rc = ctx->ws_limit_tab.reserve ((tab_entries + 1) * sizeof (float2))) return rc;
+    }
+  awmk::AddMixMultiArgs a {};
+  a.pcm_in = pcm_in_d;
+  a.n_frames = (long long) n_frames;
+  a.n_channels = n_channels;
+  a.neg_delta_up = float (-water_delta * 1);             // as add_mix_impl
+  a.neg_delta_down = float (-water_delta * -1);
+  a.n_blocks = (long long) n_blocks;
+  a.limiter_block = LIMITER_BLOCK;
+  a.block_frames = int (mark_block_frame_count());
+  a.frames_pad_start = int (Params::frames_pad_start);
+  a.frames_per_span = frames_per_span (ctx, (long long) (n_frames + 1023) / 1024, awmk::add_mix_multi_waves_per_simd());
+  // tile passes of nearly equal size (5 payloads: 3 + 2, not 4 + 1: a pass costs the input read and the forward transforms whatever it carries)
+  const size_t n_passes = (n_payloads + awmk::ADD_MULTI_TILE - 1) / awmk::ADD_MULTI_TILE;
+  size_t p0 = 0;
+  for (size_t pass = 0; pass < n_passes; pass++)
+    {
+      const size_t n = n_payloads / n_passes + (pass < n_payloads % n_passes ? 1 : 0);
+      // (the tables of a pass are looked up when it is launched: the cache holds far more than a tile, and drains the device before it drops one)
+      for (size_t i = 0; i < n; i++)
+        {
+          FrameModTable *fm = ctx->get_frame_mod (k, payload_hex[p0 + i]);
+          if (!fm)
+            return AWM_ERR_ARG;
+          a.o[i].out = out_d[p0 + i];
+          a.o[i].frame_mod = fm->dev.as<int8_t>();
+          a.o[i].block_max = use_limiter ? reinterpret_cast<unsigned int *> (block_max + (p0 + i) * n_blocks) : nullptr;
+        }
+      for (size_t i = n; i < size_t (awmk::ADD_MULTI_TILE); i++)
+        a.o[i] = awmk::AddMixOut {};
+      a.n_out = int (n);
+      {
+        ProfScope ps (ctx, PROF_ADD_MIX_MULTI, double (1 + n) * double (n_frames) * n_channels * 4.0, st);     // the input once, every output once
+        AWM_HIP_CHECK (awmk::launch_add_mix_multi (st, ctx->tabs, a));
+      }
+      if (use_limiter)
+        for (size_t i = 0; i < n; i++)
+          {
+            ProfScope ps (ctx, PROF_LIMITER, double (n_frames) * n_channels * 8.0, st);
+            // (the outputs share the ramp table: the passes run in stream order, each rebuilds the entries)
+            AWM_HIP_CHECK (awmk::launch_limiter (st, out_d[p0 + i], (long long) n_frames, n_channels, 0, block_max + (p0 + i) * n_blocks, 0, (long long) n_blocks,
+                                                 LIMITER_BLOCK, LIMITER_CEILING, ctx->ws_limit_tab.as<float2>(), tab_entries));
+          }
+      p0 += n;
+    }
+  g_add_payloads_fused_in_use = 1;
+  return 0;
 }
 
 /* add_watermark followed by get_watermark of its output ("watermark, then verify") as ONE call: the library owns the order of the two

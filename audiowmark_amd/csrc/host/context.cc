@@ -545,7 +545,8 @@ static const char *prof_names[awm::PROF_COUNT] = {
   "add_mix_kernel", "limiter_kernel", "sync_db_kernel(approx)", "sync_scan_kernel(approx)", "local_mean_kernel",
   "sync_db_kernel(refine)", "sync_scan_kernel(refine)", "sync_db_kernel(block)", "soft_bits_kernel", "viterbi_kernel",
   "stft_full_kernel",
-  "resample_kernel", "resample_var_kernel", "speed_mags_kernel", "speed_compare_kernel", "frame_mod_table_kernel"
+  "resample_kernel", "resample_var_kernel", "speed_mags_kernel", "speed_compare_kernel", "frame_mod_table_kernel",
+  "add_mix_multi_kernel"
 };
 
 extern "C" {

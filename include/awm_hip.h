@@ -223,6 +223,20 @@ int awm_get_watermark_batch_keys_d (awm_ctx *ctx, const uint8_t *keys, size_t n_
 int awm_add_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex,
                          const float *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
                          int sample_rate);
+/* add_watermark (wmadd.cc:448-618) of ONE input with n_payloads payloads and one key: out_d[p] receives what
+ * awm_add_watermark_d (ctx, key, payload_hex[p], pcm_in_d, out_d[p], ...) would write, bit for bit -- the same programme for many
+ * recipients, each copy with a payload of its own (what the reference prepares once and then marks per subscriber in its HLS mode,
+ * hls.cc).  The frame_mod tables of two payloads differ only in UP <-> DOWN of the data frames' bands (mark_data, wmadd.cc:86-162), so at
+ * 44100 Hz one kernel (K2m, hip/kernels.hip) reads, windows and transforms every frame once and computes both band factors once; the
+ * choice per band, the inverse transform, overlap-add, mix, block maxima and limiter run per output, ADD_MULTI_TILE (4) outputs per pass
+ * over the input.  Every channel count takes the fused kernel (stereo with both channels in a wave, anything else a channel per wave).
+ * Other sample rates loop over the single-payload path (the resampled add is not fused).  The context's parameters apply as for
+ * awm_add_watermark_d.  n_payloads == 0 or n_frames == 0: returns 0, writes nothing; n_payloads == 1: the single-payload path.
+ * AWM_ERR_ARG with nothing enqueued: a payload that does not parse (awm_last_error names its index), a NULL pointer, an output that
+ * overlaps the input or another output, a call while the SNR meter is armed (awm_ctx_snr_begin).
+ * Not offered in this form: the file level, the command line, the tile stream, sharding, a key per payload. */
+int awm_add_watermark_payloads_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
+                                  const float *pcm_in_d, float *const *out_d, size_t n_frames, int n_channels, int sample_rate);
 /* Streams at another sample rate.  The reference resamples them to 44.1 kHz with zita-resampler (hlen 16): the fixed-ratio
  * Resampler where it takes the two rates, else the VResampler with ratio new / old (ResamplerImpl::create,
  * resample.cc:233-270).  `get` decodes the resampled stream (WavChunkLoader, wavchunkloader.cc:70-71,200-216), `add` generates the
@@ -469,6 +483,9 @@ void awm_debug_set_add_batched (int on);   /* add of a batch of stereo clips: 2 
                                             * group's tables built while the previous group of 256 clips is watermarked | 0 four launches per clip on eight lanes; the
                                             * outputs are the same */
 void awm_debug_set_add_slab_mb (int mb);   /* add: 0 (default) one fused add over the stream, then the limiter | > 0: in slabs of that many MB (cache experiment) */
+void awm_debug_set_add_payloads_fused (int on);   /* awm_add_watermark_payloads_d: 1 (default) the fused kernel | 0 a loop over the single-payload path */
+int  awm_debug_add_payloads_fused_in_use (void);  /* 1 if the last awm_add_watermark_payloads_d ran the fused kernel */
+int  awm_debug_add_payloads_tile (void);          /* outputs per pass of the fused kernel over the input (ADD_MULTI_TILE) */
 void awm_debug_set_fft_pair (int on);      /* stereo add: both channels' transforms pipelined in one wave (default) | one after the other */
 void awm_debug_set_clip_poison (int on);    /* clip batches: the padded slices are filled with NaNs before the copies are written (the copy writes a clip and 2048
                                             * frames of zeros on either side, not the rest of the padding: a consumer that read further would change its result) */
