@@ -415,6 +415,16 @@ def _dev_ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _out_tensor(out, shape, dtype, device, what):
+    """the caller's output buffer of a call that would otherwise allocate one: contiguous, of the call's shape, type and device"""
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}")
+    return out
+
+
 def _pcm_shape(pcm):
     """(n_frames, n_channels) of an interleaved float32 CUDA tensor shaped [frames, channels] or [frames]."""
     import torch
@@ -486,28 +496,28 @@ class Context:
         _check(lib.awm_ctx_synchronize(self._h), "awm_ctx_synchronize")
 
     # RawConverter::from_raw / to_raw on the device
-    def pcm_decode(self, raw_bytes, bit_depth, encoding=0, big_endian=False):
+    def pcm_decode(self, raw_bytes, bit_depth, encoding=0, big_endian=False, out=None):
         import torch
         assert raw_bytes.dtype == torch.uint8 and raw_bytes.is_cuda and raw_bytes.is_contiguous()
         n = raw_bytes.numel() // (bit_depth // 8)
-        out = torch.empty(n, dtype=torch.float32, device=raw_bytes.device)
+        out = _out_tensor(out, (n,), torch.float32, raw_bytes.device, "pcm_decode")
         _check(lib.awm_pcm_decode_d(self._h, _dev_ptr(raw_bytes), n, bit_depth, encoding, int(big_endian), _dev_ptr(out)), "awm_pcm_decode_d")
         return out
 
-    def pcm_encode(self, samples, bit_depth, encoding=0, big_endian=False, direct16=True):
+    def pcm_encode(self, samples, bit_depth, encoding=0, big_endian=False, direct16=True, out=None):
         import torch
         assert samples.dtype == torch.float32 and samples.is_cuda and samples.is_contiguous()
         n = samples.numel()
-        out = torch.empty(n * (bit_depth // 8), dtype=torch.uint8, device=samples.device)
+        out = _out_tensor(out, (n * (bit_depth // 8),), torch.uint8, samples.device, "pcm_encode")
         _check(lib.awm_pcm_encode_d(self._h, _dev_ptr(samples), n, bit_depth, encoding, int(big_endian), int(direct16), _dev_ptr(out)),
                "awm_pcm_encode_d")
         return out
 
     # FFTAnalyzer::fft_range
-    def fft_range(self, pcm, start_index, frame_count, hop=1024):
+    def fft_range(self, pcm, start_index, frame_count, hop=1024, out=None):
         import torch
         n, ch = _pcm_shape(pcm)
-        out = torch.empty((frame_count, ch, 513, 2), dtype=torch.float32, device=pcm.device)
+        out = _out_tensor(out, (frame_count, ch, 513, 2), torch.float32, pcm.device, "fft_range")
         _check(lib.awm_stft_d(self._h, _dev_ptr(pcm), n, ch, start_index, hop, frame_count, _dev_ptr(out)), "awm_stft_d")
         return out
 
@@ -664,23 +674,30 @@ class Context:
         assert written == n
         return out
 
-    def resample(self, pcm, rate_in, rate_out):
+    def resample_frames(self, n_frames, rate_in, rate_out):
+        """frames `resample` delivers for n_frames at rate_in (0: the ratio is not supported)"""
+        return lib.awm_resample_frames(self._h, n_frames, rate_in, rate_out)
+
+    def resample(self, pcm, rate_in, rate_out, out=None):
         """The stream the reference's loader hands to the decoder for a file at rate_in (zita-resampler restated)."""
         import torch
         n, ch = _pcm_shape(pcm)
         m = lib.awm_resample_frames(self._h, n, rate_in, rate_out)
         if n and not m:
             raise AwmError("resampling %d -> %d Hz is not supported: %s" % (rate_in, rate_out, lib.awm_last_error().decode()))
-        out = torch.empty((m, ch), dtype=torch.float32, device=pcm.device)
+        out = _out_tensor(out, (m, ch), torch.float32, pcm.device, "resample")
         _check(lib.awm_resample_d(self._h, _dev_ptr(pcm), n, ch, rate_in, rate_out, _dev_ptr(out), m), "awm_resample_d")
         return out
 
-    def resample_ratio(self, pcm, ratio, rate=44100, max_in_seconds=-1.0):
+    def resample_ratio_frames(self, n_frames, n_channels, ratio, rate=44100, max_in_seconds=-1.0):
+        return lib.awm_resample_ratio_frames(n_frames, n_channels, rate, ratio, max_in_seconds)
+
+    def resample_ratio(self, pcm, ratio, rate=44100, max_in_seconds=-1.0, out=None):
         """resample_ratio_truncate (reference resample.cc:96-119): zita's VResampler, restated."""
         import torch
         n, ch = _pcm_shape(pcm)
         m = lib.awm_resample_ratio_frames(n, ch, rate, ratio, max_in_seconds)
-        out = torch.empty((m, ch), dtype=torch.float32, device=pcm.device)
+        out = _out_tensor(out, (m, ch), torch.float32, pcm.device, "resample_ratio")
         _check(lib.awm_resample_ratio_d(self._h, _dev_ptr(pcm), n, ch, rate, ratio, max_in_seconds, _dev_ptr(out), m),
                "awm_resample_ratio_d")
         return out
@@ -748,13 +765,18 @@ class Context:
                                    block_max.numel()), "awm_add_limit_d")
 
     # SyncFinder::sync_fft
-    def sync_fft(self, pcm, index, frame_count, want_frames=None, first=0, last=None):
+    def sync_fft(self, pcm, index, frame_count, want_frames=None, first=0, last=None, out=None):
+        """out: (db, have) buffers of the caller instead of fresh ones (every row is written: zeros for the frames that are skipped)"""
         import torch
         n, ch = _pcm_shape(pcm)
         if last is None:
             last = n * ch
-        db = torch.zeros((frame_count, N_BANDS), dtype=torch.float32, device=pcm.device)
-        have = torch.zeros(frame_count, dtype=torch.int8, device=pcm.device)
+        if out is None:
+            db = torch.zeros((frame_count, N_BANDS), dtype=torch.float32, device=pcm.device)
+            have = torch.zeros(frame_count, dtype=torch.int8, device=pcm.device)
+        else:
+            db = _out_tensor(out[0], (frame_count, N_BANDS), torch.float32, pcm.device, "sync_fft (db)")
+            have = _out_tensor(out[1], (frame_count,), torch.int8, pcm.device, "sync_fft (have)")
         want = None
         if want_frames is not None:
             want = np.ascontiguousarray(want_frames, np.int8)

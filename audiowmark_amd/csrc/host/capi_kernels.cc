@@ -267,6 +267,16 @@ awm_add_limit_d (awm_ctx *ctx, float *out_d, size_t n_frames, int n_channels, si
 static int g_add_slab_mb = 0;
 extern "C" void awm_debug_set_add_slab_mb (int mb) { g_add_slab_mb = mb < 0 ? 0 : mb; }
 
+/* `add` reads three frames of the input per frame of the output (the overlap-add of the neighbours' watermark signal): an output that
+ * overlaps the input anywhere is a race between workgroups.  The entry points that take both pointers from the caller refuse it before
+ * anything is enqueued. */
+static bool
+add_buffers_overlap (const float *in, const float *out, size_t n_values)
+{
+  const uintptr_t a = reinterpret_cast<uintptr_t> (in), b = reinterpret_cast<uintptr_t> (out), bytes = n_values * sizeof (float);
+  return a < b + bytes && b < a + bytes;
+}
+
 /* whole stream on one lane (stream + block maxima + limiter table of that lane; the context itself is lane 0) */
 static int
 add_full (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
@@ -744,6 +754,11 @@ awm_add_d (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames, i
       set_error ("awm_add_d: bad argument");
       return AWM_ERR_ARG;
     }
+  if (add_buffers_overlap (pcm_in_d, out_d, n_frames * size_t (n_channels)))
+    {
+      set_error ("awm_add_d: the output overlaps the input");
+      return AWM_ERR_ARG;
+    }
   const size_t table_bytes = 2 * mark_block_frame_count() * Params::n_bands;
   if (int rc = ctx->ws_misc.reserve (table_bytes)) return rc;
   AWM_HIP_CHECK (hipMemcpyAsync (ctx->ws_misc.ptr, frame_mod, table_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -1023,6 +1038,11 @@ awm_add_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_he
                      size_t n_frames, int n_channels, int sample_rate)
 {
   AWM_ENTER (ctx);
+  if (n_channels >= 1 && add_buffers_overlap (pcm_in_d, out_d, n_frames * size_t (n_channels)))
+    {
+      set_error ("awm_add_watermark_d: the output overlaps the input");
+      return AWM_ERR_ARG;
+    }
   FrameModTable *fm = ctx->get_frame_mod (capi_key (key), payload_hex ? payload_hex : "");
   if (!fm)
     return AWM_ERR_ARG;

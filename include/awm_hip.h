@@ -7,6 +7,10 @@
  * Conventions
  *   - plain C, pointers + sizes only.  Pointers suffixed _d are DEVICE pointers (HBM),
  *     everything else is host memory.
+ *   - device buffers need only the alignment of their element type (4 bytes for float32
+ *     PCM and tables, 1 byte for raw PCM bytes and flags): results are bit-identical at every
+ *     placement and nothing outside [pointer, pointer + size) is read or written
+ *     (tests/test_gpu_placement.py is that promise).
  *   - return 0 on success, negative on error; awm_last_error() gives the message
  *     (thread-local).  There is NO CPU fallback: without a usable gfx950 device every
  *     compute entry point fails with AWM_ERR_NO_DEVICE.
@@ -113,7 +117,9 @@ int awm_stft_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channel
  * awm_add_mix_d writes the un-limited mix to out_d and accumulates per-limiter-block maxima into
  * block_max_d[b] (b = global limiter block index - first_block, float32, pre-initialised by
  * awm_add_init_block_max_d); awm_add_limit_d applies the limiter ramp in place.  Between the two a
- * multi-GPU caller all-reduces (max) block_max_d.  awm_add_d = both, single GPU. */
+ * multi-GPU caller all-reduces (max) block_max_d.  awm_add_d = both, single GPU.
+ * Every output frame is computed from three input frames: out_d must not overlap pcm_in_d.  awm_add_d refuses an output that overlaps
+ * the input anywhere (AWM_ERR_ARG, nothing enqueued). */
 int awm_add_init_block_max_d (awm_ctx *ctx, float *block_max_d, size_t n_blocks);
 int awm_add_mix_d (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
                    const int8_t *frame_mod, double water_delta, size_t first_frame,
@@ -219,7 +225,8 @@ int awm_get_watermark_batch_keys_d (awm_ctx *ctx, const uint8_t *keys, size_t n_
                                     const size_t *n_frames, int n_channels, int n_threads, size_t max_out_per_clip,
                                     awm_pattern *out, int *n_out);
 
-/* add_watermark core (wmadd.cc:448-618) on resident PCM: out_d gets n_frames*C samples */
+/* add_watermark core (wmadd.cc:448-618) on resident PCM: out_d gets n_frames*C samples.  AWM_ERR_ARG with nothing enqueued if out_d
+ * overlaps pcm_in_d anywhere (every output frame is computed from three input frames: an overlap would be a race). */
 int awm_add_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex,
                          const float *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
                          int sample_rate);
