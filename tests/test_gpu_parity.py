@@ -1100,17 +1100,28 @@ def test_one_clean_gap_is_exact(gpu):
     assert max([abs(g["sync_quality"] - w["sync_quality"]) for g, w in zip(got, want)] + [0]) < QUALITY_TOL
 
 
-@pytest.mark.parametrize("minutes,limiter", [(61, True), (61, False), (95, True), (0.9, True)])
-def test_add_get_as_one_call_equals_the_two_calls(gpu, minutes, limiter):
+@pytest.mark.parametrize("minutes,limiter,material", [
+    pytest.param(61, True, "noise", id="61-True"), pytest.param(61, False, "noise", id="61-False"), pytest.param(95, True, "noise", id="95-True"),
+    pytest.param(0.9, True, "noise", id="0.9-True"), pytest.param(31, True, "ladder", id="31-True-ladder")])
+def test_add_get_as_one_call_equals_the_two_calls(gpu, minutes, limiter, material):
     """awm_add_get_watermark_d (add, then get of its output, one call: `get` starts a chunk behind the limiter pass that covers it, on
     other streams than the add): the PCM of awm_add_watermark_d bit for bit and the pattern list of awm_get_watermark_d on it, incl.
     quality and error values -- three chunks, four chunks (more chunks than a first round of lanes), a clip (one chunk: no hand-over),
     with and without the limiter; repeated, with the output buffer cleared in between (a chunk that started too early would read
-    zeros or unlimited samples and change the list)."""
+    zeros or unlimited samples and change the list).
+    "ladder": quiet noise with the rising peaks of tests/_limiter.py's ladder on both sides of every limiter block boundary (steep ramps,
+    block maxima on the boundaries), two chunks: the limiter runs as two passes, the second of which begins in the middle of the stream."""
     torch = gpu.torch
     n = int(minutes * 60 * 44100) + 333
     g = torch.Generator(device="cuda"); g.manual_seed(17)
     x = torch.rand((n, 2), generator=g, device="cuda") * 2 - 1
+    if material == "ladder":
+        assert len(gpu.awm.plan_chunks(n)) >= 2                # one limiter pass per chunk end
+        x *= 0.05
+        k = torch.arange(1, n // 44100 + 1, device="cuda")       # every boundary; the ladder starts again every 17 blocks
+        for side in (0, 1):
+            j = 2 * (k % 17) + side
+            x[k * 44100 - 1 + side, j % 2] = ((1.20 + 0.02 * j) * (1 - 2 * (j % 2))).float()
     full = lambda p: pkey(p) + (p["sync_quality"], p["decode_error"])
     gpu.awm.set_params(test_no_limiter=not limiter)
     try:
