@@ -162,6 +162,17 @@ lib.awm_add_stream_destroy.restype = None
 lib.awm_add_stream_input.argtypes = [_vp]
 lib.awm_add_stream_input.restype = C.c_void_p
 lib.awm_add_stream_push.argtypes = [_vp, C.c_size_t, C.c_int, _vp, _vp]
+lib.awm_add_mix_payloads_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_int, _vp, C.c_double, C.c_size_t, _vp, _vp, _vp,
+                                       C.c_size_t, C.c_size_t]
+lib.awm_add_stream_create_payloads_at.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(_vp)]
+lib.awm_add_stream_payloads.argtypes = [_vp]
+lib.awm_add_stream_payloads.restype = C.c_size_t
+lib.awm_add_stream_push_payloads.argtypes = [_vp, C.c_size_t, C.c_int, _vp, _vp]
+lib.awm_add_watermark_payloads_file.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_char_p, _vp, C.POINTER(RawFormat), C.POINTER(RawFormat)]
+lib.awm_add_stream_watermark_payloads_file.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_char_p, _vp, C.POINTER(RawFormat), C.POINTER(RawFormat),
+                                                       C.c_size_t]
+lib.awm_debug_set_payloads_file_tile.argtypes = [C.c_int]
+lib.awm_debug_set_payloads_file_tile.restype = None
 
 
 lib.awm_decode_chunks_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_size_t, _vp, _vp]
@@ -454,6 +465,54 @@ def check_payload_outputs(payloads, pcm, outs):
     return outs
 
 
+def check_payload_paths(payloads, in_path, out_paths):
+    """argument check of Context.add_watermark_payloads_file, before the library is called: one output path per payload (hex strings), no
+    two of them equal and none equal to the input; returns the output paths as a list of bytes"""
+    payloads = list(payloads)
+    for i, p in enumerate(payloads):
+        if not isinstance(p, str):
+            raise TypeError(f"add_watermark_payloads_file: payloads[{i}] must be a hex string")
+    if isinstance(out_paths, (str, bytes, os.PathLike)):
+        raise TypeError("add_watermark_payloads_file: out_paths must be a list of paths, one per payload")
+    outs = [os.fsencode(o) for o in out_paths]
+    if len(outs) != len(payloads):
+        raise ValueError(f"add_watermark_payloads_file: {len(payloads)} payloads but {len(outs)} output paths")
+    seen = {os.path.abspath(os.fsencode(in_path)): -1}
+    for i, o in enumerate(outs):
+        a = os.path.abspath(o)
+        if a in seen:
+            other = "the input path" if seen[a] < 0 else f"out_paths[{seen[a]}]"
+            raise ValueError(f"add_watermark_payloads_file: out_paths[{i}] equals {other}")
+        seen[a] = i
+    return outs
+
+
+def check_mix_payloads(pcm, outs, frame_mods, block_maxes):
+    """argument check of Context.add_mix_payloads, before the library is called: one output of the input's shape and one table per payload,
+    and either no block maxima or one array per payload"""
+    import torch
+    outs, frame_mods = list(outs), list(frame_mods)
+    if pcm.dtype != torch.float32 or not pcm.is_contiguous():
+        raise ValueError("add_mix_payloads: pcm must be a contiguous float32 tensor")
+    if len(outs) != len(frame_mods):
+        raise ValueError(f"add_mix_payloads: {len(frame_mods)} tables but {len(outs)} outputs")
+    for i, o in enumerate(outs):
+        if o.dtype != torch.float32 or o.shape != pcm.shape or o.device != pcm.device or not o.is_contiguous():
+            raise ValueError(f"add_mix_payloads: outs[{i}] must be a contiguous float32 tensor of the input's shape and device")
+    if block_maxes is not None:
+        block_maxes = list(block_maxes)
+        if len(block_maxes) != len(outs):
+            raise ValueError(f"add_mix_payloads: {len(outs)} outputs but {len(block_maxes)} arrays of block maxima")
+        if any(b.numel() != block_maxes[0].numel() for b in block_maxes):
+            raise ValueError("add_mix_payloads: the arrays of block maxima must have one length")
+    return outs, frame_mods, block_maxes
+
+
+def set_payloads_file_tile(frames1024):
+    """(tests, measurements) add_watermark_payloads_file: tile of the fused path in 1024-sample frames (>= 128); 0 (default): automatic"""
+    lib.awm_debug_set_payloads_file_tile(int(frames1024))
+
+
 def set_add_payloads_fused(on):
     """(tests, measurements) add_watermark_payloads: True (default) the fused kernel, False a loop over the single-payload path"""
     lib.awm_debug_set_add_payloads_fused(int(on))
@@ -618,6 +677,22 @@ class Context:
                                           C.byref(raw_in) if raw_in is not None else None,
                                           C.byref(raw_out) if raw_out is not None else None), "awm_add_watermark_file")
 
+    def add_watermark_payloads_file(self, key, payloads, in_path, out_paths, raw_in=None, raw_out=None, zero_frames=None):
+        """awm_add_watermark_payloads_file: ONE infile -> out_paths[p] with payloads[p]; every output is the file add_watermark_file writes
+        for that payload, the input is read, uploaded and decoded once (44.1 kHz)"""
+        payloads = list(payloads)
+        outs = check_payload_paths(payloads, in_path, out_paths)
+        hexes = (C.c_char_p * len(payloads))(*[p.encode() for p in payloads])
+        paths = (C.c_char_p * len(payloads))(*outs)
+        rin = C.byref(raw_in) if raw_in is not None else None
+        rout = C.byref(raw_out) if raw_out is not None else None
+        if zero_frames is not None:
+            _check(lib.awm_add_stream_watermark_payloads_file(self._h, key_bytes(key), hexes, len(payloads), os.fsencode(in_path), paths, rin, rout,
+                                                              zero_frames), "awm_add_stream_watermark_payloads_file")
+            return
+        _check(lib.awm_add_watermark_payloads_file(self._h, key_bytes(key), hexes, len(payloads), os.fsencode(in_path), paths, rin, rout),
+               "awm_add_watermark_payloads_file")
+
     def add_get_watermark_file(self, key, payload_hex, in_path, out_path, raw_in=None, raw_out=None):
         """awm_add_get_watermark_file: infile -> outfile, and the pattern list of `get` on what was written (never read back)"""
         return self._patterns(lib.awm_add_get_watermark_file, "awm_add_get_watermark_file", self._h, key_bytes(key), payload_hex.encode(),
@@ -673,6 +748,46 @@ class Context:
             lib.awm_add_stream_destroy(h)
         assert written == n
         return out
+
+    def add_watermark_payloads_tiles(self, key, payloads, pcm, tile_frames1024=128, zero_frames=0):
+        """awm_add_stream with P payloads: the tile loop over resident PCM for one input and many payloads; returns the list of
+        concatenated outputs, outs[p] == add_watermark_tiles(key, payloads[p], pcm, tile_frames1024, zero_frames) bit for bit."""
+        import torch
+        payloads = list(payloads)
+        check_payload_outputs(payloads, pcm, None)
+        n, ch = _pcm_shape(pcm)
+        P = len(payloads)
+        hexes = (C.c_char_p * P)(*[p.encode() for p in payloads])
+        h = C.c_void_p()
+        _check(lib.awm_add_stream_create_payloads_at(self._h, key_bytes(key), hexes, P, ch, tile_frames1024, zero_frames, C.byref(h)),
+               "awm_add_stream_create_payloads_at")
+        outs = [torch.empty_like(pcm) for _ in payloads]
+        tile = tile_frames1024 * 1024
+        done_p = (C.c_void_p * (3 * P))()
+        done_n = (C.c_size_t * 3)()
+        pos = written = 0
+        esz = pcm.element_size() * ch
+        try:
+            assert lib.awm_add_stream_payloads(h) == P
+            while True:
+                got = min(tile, n - pos)
+                last = pos + got >= n
+                slot = lib.awm_add_stream_input(h)
+                if got:
+                    _hip_memcpy_dtod(self, slot, pcm.data_ptr() + pos * esz, got * esz)
+                k = _check(lib.awm_add_stream_push_payloads(h, got, int(last), done_p, done_n), "awm_add_stream_push_payloads")
+                for i in range(k):
+                    for p in range(P):
+                        _hip_memcpy_dtod(self, outs[p].data_ptr() + written * esz, done_p[i * P + p], done_n[i] * esz)
+                    written += done_n[i]
+                pos += got
+                if last:
+                    break
+            self.synchronize()
+        finally:
+            lib.awm_add_stream_destroy(h)
+        assert written == n
+        return outs
 
     def resample_frames(self, n_frames, rate_in, rate_out):
         """frames `resample` delivers for n_frames at rate_in (0: the ratio is not supported)"""
@@ -755,6 +870,21 @@ class Context:
                                  _dev_ptr(halo_after) if halo_after is not None else None,
                                  _dev_ptr(block_max) if block_max is not None else None, first_block,
                                  block_max.numel() if block_max is not None else 0), "awm_add_mix_d")
+
+    def add_mix_payloads(self, pcm, outs, frame_mods, water_delta, first_frame, halo_before, halo_after, block_maxes, first_block=0):
+        """awm_add_mix_payloads_d: add_mix of one span for len(frame_mods) tables in fused passes; outs[p] / block_maxes[p] (None: no
+        limiter) receive what add_mix writes with frame_mods[p]"""
+        outs, frame_mods, block_maxes = check_mix_payloads(pcm, outs, frame_mods, block_maxes)
+        n, ch = _pcm_shape(pcm)
+        P = len(outs)
+        fms = [np.ascontiguousarray(fm, np.int8) for fm in frame_mods]
+        fm_p = (C.c_void_p * P)(*[_np(fm) for fm in fms])
+        out_p = (C.c_void_p * P)(*[_dev_ptr(o) for o in outs])
+        bm_p = (C.c_void_p * P)(*[_dev_ptr(b) for b in block_maxes]) if block_maxes is not None else None
+        _check(lib.awm_add_mix_payloads_d(self._h, _dev_ptr(pcm), out_p, P, n, ch, fm_p, water_delta, first_frame,
+                                          _dev_ptr(halo_before) if halo_before is not None else None,
+                                          _dev_ptr(halo_after) if halo_after is not None else None,
+                                          bm_p, first_block, block_maxes[0].numel() if block_maxes else 0), "awm_add_mix_payloads_d")
 
     def add_init_block_max(self, block_max):
         _check(lib.awm_add_init_block_max_d(self._h, _dev_ptr(block_max), block_max.numel()), "awm_add_init_block_max_d")

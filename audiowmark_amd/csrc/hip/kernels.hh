@@ -61,7 +61,7 @@ int        add_mix_waves_per_simd();     // occupancy the stereo kernel is built
 
 /* K2m: K2 for ONE input stream and several outputs, each with a frame_mod table of its own (one programme, one payload per recipient).
  * A wave fetches, windows and transforms a frame once and computes both band factors (UP and DOWN) once; band selection, inverse
- * transform, overlap-add, mix, stores and block maxima then run once per output.  Whole streams only (frame 0 is sample 0, no halos);
+ * transform, overlap-add, mix, stores and block maxima then run once per output.  This form: whole streams (frame 0 is sample 0, no halos; spans: AddMixSpan below);
  * every channel count takes it (stereo through the paired transforms, anything else one channel per wave like K2).  out[p] is bit for bit
  * what launch_add_mix writes with frame_mod[p]: the same device functions and expressions in the same order. */
 constexpr int ADD_MULTI_TILE = 4;        // outputs per launch (their overlap-add carry lives in registers: DESIGN.md section 9)
@@ -88,6 +88,19 @@ struct AddMixMultiArgs
 };
 hipError_t launch_add_mix_multi (hipStream_t st, const DevTables& t, const AddMixMultiArgs& a);
 int        add_mix_multi_waves_per_simd();   // occupancy K2m is built for (sizes its spans)
+/* K2m for a SPAN of a stream (the P-output form of AddMixArgs' span fields, with add_mix_body's meaning): local frame m is frame
+ * first_frame + m of the stream (table row, limiter block), frame -1 / frame ceil (n_frames / 1024) come from the halos (nullptr: zeros),
+ * block maxima are stored at index - first_block (o[p].block_max has n_blocks entries from there).  The halo frames are transformed once
+ * per launch like every other frame.  out[p] is bit for bit what launch_add_mix writes for the span with frame_mod[p]. */
+struct AddMixSpan
+{
+  long long    first_frame;       // global frame index of local frame 0
+  const float *halo_before;       // 1024*C samples or nullptr
+  const float *halo_after;        // 1024*C samples or nullptr
+  long long    first_block;
+};
+hipError_t launch_add_mix_multi_span (hipStream_t st, const DevTables& t, const AddMixMultiArgs& a, const AddMixSpan& sp);
+int        add_mix_multi_span_waves_per_simd();   // occupancy the span kernels are built for
 
 /* K3: limiter ramp, in place */
 hipError_t launch_limiter (hipStream_t st, float *data, long long n_frames, int n_channels, long long first_sample,

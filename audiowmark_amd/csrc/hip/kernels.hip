@@ -3,7 +3,8 @@
 //   K1 stft_full_kernel    FFTAnalyzer::run_fft / fft_range        (reference wmcommon.cc:91-141)
 //   K2 add_mix_kernel      run_fft + apply_frame_mod + c2r + 3-frame windowed overlap-add + mix
 //                          + per-second max|x|                     (reference wmadd.cc:61-84,215-250,297-317,564-565; limiter.cc:90-97)
-//   K2m add_mix_multi_kernel  K2 for one input and several payloads: the forward half once, the rest per output (reference wmadd.cc:86-162)
+//   K2m add_mix_multi_kernel  K2 for one input and several payloads: the forward half once, the rest per output (reference wmadd.cc:86-162);
+//                          add_mix_multi_span_kernel: the same for a span of a stream (halos, first_frame, first_block)
 //   K3 limiter_kernel      Limiter::process_block ramp             (reference limiter.cc:99-124)
 //   K4 sync_db_kernel      SyncFinder::sync_fft (STFT -> dB, 81 bands) (reference syncfinder.cc:560-605)
 //   K5 sync_scan_kernel    SyncFinder::sync_decode + bit_quality   (reference syncfinder.cc:80-153)
@@ -705,6 +706,10 @@ launch_add_mix_batch (hipStream_t st, const DevTables& t, const AddMixArgs *args
  * the stores and the block maxima -- every expression is K2's (frame_delta / frame_delta2 / add_mix_body), so output p is bit
  * for bit what K2 writes with table p.  The outputs of a launch are unrolled: their overlap-add carry (8 floats per lane and
  * stereo output) stays in registers.
+ *
+ * Two forms of one body: a whole stream (frame 0 is sample 0, no halos) and, SPAN = true, a span of a stream (kernels.hh AddMixSpan:
+ * first_frame, halos, first_block with add_mix_body's meaning) -- the halo frames go through the shared forward half like every other
+ * frame.  Everything the span form adds is behind `if constexpr (SPAN)`: the whole-stream kernels compile as they did without it.
  * ========================================================================================== */
 
 // where output frame m lies: in the wave's span or not, and the limiter block boundary inside it / inside frame m - 1
@@ -714,8 +719,9 @@ struct FramePlace
   int b0, bound, pb0, pbound;       // limiter block of the frame's first sample; samples of the frame before the next block begins
 };
 
-// stores + block maxima of one output: values 0 .. 13 of o are frame m, 14 and 15 the tail of frame m - 1 (add_mix_body's, for a whole stream)
-template<int CV> __device__ __forceinline__ void
+// stores + block maxima of one output: values 0 .. 13 of o are frame m, 14 and 15 the tail of frame m - 1 (add_mix_body's).  m and n_frames
+// are local to the launch; SPAN: fp.b0 / fp.pb0 are relative to the first block of the maxima and may lie in front of it (K2's range checks)
+template<int CV, bool SPAN = false> __device__ __forceinline__ void
 multi_emit (float *out, unsigned int *block_max, const float (&o)[CV][16], long long m, const FramePlace& fp,
             long long n_frames, long long n_blocks, int C, int ch0, int lane)
 {
@@ -829,8 +835,8 @@ multi_emit (float *out, unsigned int *block_max, const float (&o)[CV][16], long 
           if (lane == 0)
             {
               const long long i0 = fp.b0, i1 = i0 + 1;
-              if (i0 < n_blocks && max0 > 0.f) atomicMax (block_max + i0, __float_as_uint (max0));
-              if (i1 < n_blocks && max1 > 0.f) atomicMax (block_max + i1, __float_as_uint (max1));
+              if ((!SPAN || i0 >= 0) && i0 < n_blocks && max0 > 0.f) atomicMax (block_max + i0, __float_as_uint (max0));
+              if ((!SPAN || i1 >= 0) && i1 < n_blocks && max1 > 0.f) atomicMax (block_max + i1, __float_as_uint (max1));
             }
         }
       if (fp.own_prev)
@@ -840,15 +846,15 @@ multi_emit (float *out, unsigned int *block_max, const float (&o)[CV][16], long 
           if (lane == 0)
             {
               const long long i0 = fp.pb0, i1 = i0 + 1;
-              if (i0 < n_blocks && pmax0 > 0.f) atomicMax (block_max + i0, __float_as_uint (pmax0));
-              if (i1 < n_blocks && pmax1 > 0.f) atomicMax (block_max + i1, __float_as_uint (pmax1));
+              if ((!SPAN || i0 >= 0) && i0 < n_blocks && pmax0 > 0.f) atomicMax (block_max + i0, __float_as_uint (pmax0));
+              if ((!SPAN || i1 >= 0) && i1 < n_blocks && pmax1 > 0.f) atomicMax (block_max + i1, __float_as_uint (pmax1));
             }
         }
     }
 }
 
-template<int CV> __device__ __forceinline__ void
-add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a)
+template<int CV, bool SPAN = false> __device__ __forceinline__ void
+add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSpan& sp)
 {
   constexpr int PT = ADD_MULTI_TILE;
   __shared__ float2 s_tw[512];
@@ -916,17 +922,30 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a)
           const long long left = a.n_frames - m * 1024;
           avail = left < 1024 ? int (left) : 1024;
         }
+      // a span of a stream: frame -1 / frame F from the halos, as add_mix_body's frame_source
+      const float *halo = nullptr;
+      if constexpr (SPAN)
+        if (m < 0 || m >= F)
+          {
+            halo = m < 0 ? sp.halo_before : sp.halo_after;
+            avail = halo ? 1024 : 0;
+          }
       float in[CV][16];
       float2 d_up[CV][2], d_down[CV][2];             // per pass of the bands: X (|X|^-delta - 1), X (|X|^+delta - 1)
       int mod[2];                                    // frame_mod of every output for the lane's band: 2 bits each (bit 0 touched, bit 1 UP)
       if (avail > 0)
         {
           const float *src = a.pcm_in + m * 1024 * C;
+          if constexpr (SPAN)
+            if (halo)
+              src = halo;
           if constexpr (CV == 2)
             fetch_stereo (src, 0, avail, lane, in[0], in[1]);
           else
             fetch_channel (src, 0, avail, C, ch0, lane, in[0]);
-          const long long row = (frame_number0 + m) % total_rows;      // reference wmadd.cc:326-344
+          long long row = (frame_number0 + m) % total_rows;      // reference wmadd.cc:326-344
+          if constexpr (SPAN)
+            row = (frame_number0 + sp.first_frame + m) % total_rows;
 #pragma unroll
           for (int pass = 0; pass < 2; pass++)
             {
@@ -1016,7 +1035,9 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a)
       FramePlace fp;
       fp.own = m >= s && m < e;
       fp.own_prev = m - 1 >= s && m - 1 < e;
-      const long long gs_m = m * 1024;
+      long long gs_m = m * 1024;
+      if constexpr (SPAN)
+        gs_m = (sp.first_frame + m) * 1024;                                      // the frame's first sample in the whole stream
       const long long b0 = gs_m >= 0 ? gs_m / BS : 0;
       const long long gs_p = gs_m - 1024;
       const long long pb0 = gs_p >= 0 ? gs_p / BS : 0;
@@ -1024,6 +1045,11 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a)
       fp.bound = int (std::min<long long> ((b0 + 1) * BS - gs_m, 2048));        // (only compared with offsets below 1024)
       fp.pb0 = int (pb0);
       fp.pbound = int (std::min<long long> ((pb0 + 1) * BS - gs_p, 2048));
+      if constexpr (SPAN)
+        {
+          fp.b0 = int (b0 - sp.first_block);
+          fp.pb0 = int (pb0 - sp.first_block);
+        }
 
 #pragma unroll
       for (int p = 0; p < PT; p++)
@@ -1133,7 +1159,7 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a)
                 tail_s1[p][c][0] = __fmul_rn (d[c][7].x, w1_tail.x);
                 tail_s1[p][c][1] = __fmul_rn (d[c][7].y, w1_tail.y);
               }
-            multi_emit<CV> (a.o[p].out, a.o[p].block_max, o, m, fp, a.n_frames, a.n_blocks, C, ch0, lane);
+            multi_emit<CV, SPAN> (a.o[p].out, a.o[p].block_max, o, m, fp, a.n_frames, a.n_blocks, C, ch0, lane);
           }
 #pragma unroll
       for (int c = 0; c < CV; c++)
@@ -1148,18 +1174,30 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a)
 __global__ void __launch_bounds__ (64 * WAVES)
 add_mix_multi_kernel (DevTables t, AddMixMultiArgs a)
 {
-  add_mix_multi_body<1> (t, a);
+  add_mix_multi_body<1> (t, a, AddMixSpan {});
 }
 // stereo: three waves per SIMD (at most 168 registers)
 __global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (3, 3)))
 add_mix_multi_pair_kernel (DevTables t, AddMixMultiArgs a)
 {
-  add_mix_multi_body<2> (t, a);
+  add_mix_multi_body<2> (t, a, AddMixSpan {});
 }
 int add_mix_multi_waves_per_simd() { return 3; }
+// the span forms (AddMixSpan): instantiations of their own, the whole-stream kernels above compile as they did without them
+__global__ void __launch_bounds__ (64 * WAVES)
+add_mix_multi_span_kernel (DevTables t, AddMixMultiArgs a, AddMixSpan sp)
+{
+  add_mix_multi_body<1, true> (t, a, sp);
+}
+__global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (3, 3)))
+add_mix_multi_span_pair_kernel (DevTables t, AddMixMultiArgs a, AddMixSpan sp)
+{
+  add_mix_multi_body<2, true> (t, a, sp);
+}
+int add_mix_multi_span_waves_per_simd() { return 3; }
 
-hipError_t
-launch_add_mix_multi (hipStream_t st, const DevTables& t, const AddMixMultiArgs& a)
+static hipError_t
+launch_add_mix_multi_any (hipStream_t st, const DevTables& t, const AddMixMultiArgs& a, const AddMixSpan *sp)
 {
   if (a.n_frames <= 0 || a.n_out <= 0)
     return hipSuccess;
@@ -1169,11 +1207,23 @@ launch_add_mix_multi (hipStream_t st, const DevTables& t, const AddMixMultiArgs&
   const long long n_spans = (F + a.frames_per_span - 1) / a.frames_per_span;
   const long long items = n_spans * (a.n_channels == 2 ? 1 : a.n_channels);
   const unsigned grid = unsigned ((items + WAVES - 1) / WAVES);
-  if (a.n_channels == 2)
+  if (sp && a.n_channels == 2)
+    hipLaunchKernelGGL (add_mix_multi_span_pair_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, *sp);
+  else if (sp)
+    hipLaunchKernelGGL (add_mix_multi_span_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, *sp);
+  else if (a.n_channels == 2)
     hipLaunchKernelGGL (add_mix_multi_pair_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a);
   else
     hipLaunchKernelGGL (add_mix_multi_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a);
   return hipGetLastError();
+}
+hipError_t launch_add_mix_multi (hipStream_t st, const DevTables& t, const AddMixMultiArgs& a) { return launch_add_mix_multi_any (st, t, a, nullptr); }
+hipError_t
+launch_add_mix_multi_span (hipStream_t st, const DevTables& t, const AddMixMultiArgs& a, const AddMixSpan& sp)
+{
+  if (sp.first_frame < 0 || sp.first_block < 0)
+    return hipErrorInvalidValue;
+  return launch_add_mix_multi_any (st, t, a, &sp);
 }
 
 /* ==========================================================================================

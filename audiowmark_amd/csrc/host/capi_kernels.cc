@@ -5,6 +5,7 @@
 #include "wmspeed.hh"
 #include "utils.hh"
 #include "wmfile.hh"
+#include <sys/stat.h>
 #include <atomic>
 #include <future>
 #include <thread>
@@ -545,6 +546,11 @@ add_full_rate (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frame
   return 0;
 }
 
+static int g_add_payloads_fused = 1, g_add_payloads_fused_in_use = 0;        // (awm_debug_set_add_payloads_fused, below)
+static int add_mix_payloads_impl (awm_ctx *ctx, const float *pcm_in_d, float *const *out_d, size_t n_payloads, size_t n_frames, int n_channels,
+                                  const int8_t *const *frame_mod_dev, double water_delta, size_t first_frame, const float *halo_before_d,
+                                  const float *halo_after_d, float *const *block_max_d, size_t first_block, size_t n_blocks);
+
 /* ---- add as a tile loop (reference add_stream_watermark, wmadd.cc:520-589: the stream is processed frame by frame with
  * WatermarkSynth holding one frame back (wmadd.cc:220-222) and the Limiter holding up to two blocks back (limiter.cc:51-64)).
  * Here a TILE of frames is in flight instead of a frame; what is carried from tile to tile is the same state:
@@ -556,13 +562,16 @@ struct awm_add_stream
 {
   awm_ctx  *ctx = nullptr;
   int       C = 0;
+  size_t    P = 1;                    // payloads: every tile is mixed and limited once per payload, from one input
   size_t    tile = 0;                 // samples per channel in a full tile (multiple of 1024)
   bool      limiter = true;
   bool      finished = false;
   long long t = 0;                    // tiles pushed so far
   size_t    len[3] = { 0, 0, 0 };     // samples per channel in the input slots
-  DevBuffer table, in[3], mix[3], block_max;
-  size_t    n_blocks = 0;             // block maxima allocated (and initialised)
+  DevBuffer in[3], block_max;         // block_max: P arrays of n_blocks maxima each, payload p at p * n_blocks
+  std::vector<DevBuffer> table;       // [P] a private copy of each payload's frame_mod table
+  std::vector<DevBuffer> mix;         // [3][P] mix slot i of payload p at i * P + p
+  size_t    n_blocks = 0;             // block maxima allocated (and initialised) per payload
   // a stream that starts `zero_frames` samples into its frame / limiter block grid (add_stream_watermark's zero_frames, reference
   // wmadd.cc:501-526): whole frames of zeros are only counted (WatermarkGen::skip, Limiter::skip), the rest is a prefix of zeros
   size_t    skipped = 0;              // zero_frames rounded down to whole 1024-sample frames
@@ -580,14 +589,61 @@ add_stream_grow_blocks (awm_add_stream *s, size_t need)
   while (cap < need)
     cap *= 2;
   DevBuffer bigger;
-  if (int rc = bigger.reserve (cap * sizeof (float))) return rc;
-  if (s->n_blocks)
-    AWM_HIP_CHECK (hipMemcpyAsync (bigger.ptr, s->block_max.ptr, s->n_blocks * sizeof (float), hipMemcpyDeviceToDevice, ctx->stream));
-  if (int rc = awm_add_init_block_max_d (ctx, bigger.as<float>() + s->n_blocks, cap - s->n_blocks)) return rc;
+  if (int rc = bigger.reserve (s->P * cap * sizeof (float))) return rc;
+  for (size_t p = 0; p < s->P; p++)
+    {
+      if (s->n_blocks)
+        AWM_HIP_CHECK (hipMemcpyAsync (bigger.as<float>() + p * cap, s->block_max.as<float>() + p * s->n_blocks, s->n_blocks * sizeof (float),
+                                       hipMemcpyDeviceToDevice, ctx->stream));
+      if (int rc = awm_add_init_block_max_d (ctx, bigger.as<float>() + p * cap + s->n_blocks, cap - s->n_blocks)) return rc;
+    }
   AWM_HIP_CHECK (hipStreamSynchronize (ctx->stream));      // the old array may still be read by a queued kernel
   s->block_max.release();
   s->block_max = bigger;
   s->n_blocks = cap;
+  return 0;
+}
+
+static int
+add_stream_create (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int n_channels,
+                   size_t tile_frames1024, size_t zero_frames, awm_add_stream **out)
+{
+  auto s = std::make_unique<awm_add_stream>();
+  s->ctx = ctx;
+  s->C = n_channels;
+  s->P = n_payloads;
+  s->tile = tile_frames1024 * Params::frame_size;
+  s->limiter = !params().test_no_limiter;
+  s->prefix = zero_frames % Params::frame_size;
+  s->skipped = zero_frames - s->prefix;
+  s->first_block = s->skipped / LIMITER_BLOCK;
+  s->table.resize (n_payloads);
+  s->mix.resize (3 * n_payloads);
+  const size_t table_bytes = 2 * mark_block_frame_count() * Params::n_bands;
+  auto fail = [&] (int rc) { awm_add_stream_destroy (s.release()); return rc; };
+  for (size_t p = 0; p < n_payloads; p++)
+    {
+      FrameModTable *fm = ctx->get_frame_mod (capi_key (key), payload_hex[p]);
+      if (!fm)
+        return fail (AWM_ERR_ARG);
+      if (int rc = s->table[p].reserve (table_bytes)) return fail (rc);
+      // own copy of the table: the context's cache may evict its entry while the stream lives (or while the next table is made)
+      if (hipMemcpyAsync (s->table[p].ptr, fm->dev.ptr, table_bytes, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess
+          || hipStreamSynchronize (ctx->stream) != hipSuccess)
+        return fail (AWM_ERR_HIP);
+    }
+  // (one frame of room behind a tile: with a prefix the caller's tile lies `prefix` frames into the slot, what hangs over is
+  // carried to the next slot -- or, for the last tile, stays: the last tile may be up to prefix frames longer)
+  const size_t room = s->prefix ? Params::frame_size : 0;
+  for (int i = 0; i < 3; i++)
+    {
+      if (int rc = s->in[i].reserve ((s->tile + room) * s->C * sizeof (float))) return fail (rc);
+      for (size_t p = 0; p < n_payloads; p++)
+        if (int rc = s->mix[i * n_payloads + p].reserve ((s->tile + room) * s->C * sizeof (float))) return fail (rc);
+    }
+  if (s->prefix)
+    AWM_HIP_CHECK (hipMemsetAsync (s->in[0].ptr, 0, s->prefix * s->C * sizeof (float), ctx->stream));
+  *out = s.release();
   return 0;
 }
 
@@ -601,36 +657,9 @@ awm_add_stream_create_at (awm_ctx *ctx, const uint8_t key[16], const char *paylo
       set_error ("awm_add_stream_create: bad argument (a tile is at least 128 frames: the limiter looks one second ahead)");
       return AWM_ERR_ARG;
     }
-  FrameModTable *fm = ctx->get_frame_mod (capi_key (key), payload_hex ? payload_hex : "");
-  if (!fm)
-    return AWM_ERR_ARG;
-  auto s = std::make_unique<awm_add_stream>();
-  s->ctx = ctx;
-  s->C = n_channels;
-  s->tile = tile_frames1024 * Params::frame_size;
-  s->limiter = !params().test_no_limiter;
-  s->prefix = zero_frames % Params::frame_size;
-  s->skipped = zero_frames - s->prefix;
-  s->first_block = s->skipped / LIMITER_BLOCK;
-  const size_t table_bytes = 2 * mark_block_frame_count() * Params::n_bands;
-  auto fail = [&] (int rc) { awm_add_stream_destroy (s.release()); return rc; };
-  if (int rc = s->table.reserve (table_bytes)) return fail (rc);
-  // own copy of the table: the context's cache may evict its entry while the stream lives
-  if (hipMemcpyAsync (s->table.ptr, fm->dev.ptr, table_bytes, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess
-      || hipStreamSynchronize (ctx->stream) != hipSuccess)
-    return fail (AWM_ERR_HIP);
-  // (one frame of room behind a tile: with a prefix the caller's tile lies `prefix` frames into the slot, what hangs over is
-  // carried to the next slot -- or, for the last tile, stays: the last tile may be up to prefix frames longer)
-  const size_t room = s->prefix ? Params::frame_size : 0;
-  for (int i = 0; i < 3; i++)
-    {
-      if (int rc = s->in[i].reserve ((s->tile + room) * s->C * sizeof (float))) return fail (rc);
-      if (int rc = s->mix[i].reserve ((s->tile + room) * s->C * sizeof (float))) return fail (rc);
-    }
-  if (s->prefix)
-    AWM_HIP_CHECK (hipMemsetAsync (s->in[0].ptr, 0, s->prefix * s->C * sizeof (float), ctx->stream));
-  *out = s.release();
-  return 0;
+  if (!payload_hex)
+    payload_hex = "";
+  return add_stream_create (ctx, key, &payload_hex, 1, n_channels, tile_frames1024, zero_frames, out);
 }
 
 int
@@ -640,6 +669,42 @@ awm_add_stream_create (awm_ctx *ctx, const uint8_t key[16], const char *payload_
   return awm_add_stream_create_at (ctx, key, payload_hex, n_channels, tile_frames1024, 0, out);
 }
 
+/* the same object for P payloads (include/awm_hip.h): one input, P tables, P x 3 mix slots, P arrays of block maxima */
+int
+awm_add_stream_create_payloads_at (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int n_channels,
+                                   size_t tile_frames1024, size_t zero_frames, awm_add_stream **out)
+{
+  AWM_ENTER (ctx);
+  if (!out || !payload_hex || n_channels < 1 || tile_frames1024 < 128)
+    {
+      set_error ("awm_add_stream_create_payloads_at: bad argument (a tile is at least 128 frames: the limiter looks one second ahead)");
+      return AWM_ERR_ARG;
+    }
+  if (n_payloads < 1 || n_payloads > AWM_ADD_STREAM_MAX_PAYLOADS)
+    {
+      set_error (string_printf ("awm_add_stream_create_payloads_at: %zu payloads (1 .. %d are possible)", n_payloads, AWM_ADD_STREAM_MAX_PAYLOADS));
+      return AWM_ERR_ARG;
+    }
+  if (ctx->snr_on)
+    {
+      set_error ("awm_add_stream_create_payloads_at: not available while the SNR meter is armed (awm_ctx_snr_begin)");
+      return AWM_ERR_ARG;
+    }
+  for (size_t p = 0; p < n_payloads; p++)
+    if (!payload_hex[p] || parse_payload (payload_hex[p]).empty())
+      {
+        set_error (string_printf ("awm_add_stream_create_payloads_at: cannot parse payload '%s' at index %zu", payload_hex[p] ? payload_hex[p] : "(null)", p));
+        return AWM_ERR_ARG;
+      }
+  return add_stream_create (ctx, key, payload_hex, n_payloads, n_channels, tile_frames1024, zero_frames, out);
+}
+
+size_t
+awm_add_stream_payloads (const awm_add_stream *s)
+{
+  return s ? s->P : 0;
+}
+
 void
 awm_add_stream_destroy (awm_add_stream *s)
 {
@@ -647,13 +712,13 @@ awm_add_stream_destroy (awm_add_stream *s)
     return;
   (void) hipSetDevice (s->ctx->device);
   (void) hipStreamSynchronize (s->ctx->stream);
-  s->table.release();
   s->block_max.release();
+  for (DevBuffer& b : s->table)
+    b.release();
+  for (DevBuffer& b : s->mix)
+    b.release();
   for (int i = 0; i < 3; i++)
-    {
-      s->in[i].release();
-      s->mix[i].release();
-    }
+    s->in[i].release();
   delete s;
 }
 
@@ -663,28 +728,24 @@ awm_add_stream_input (awm_add_stream *s)
   return s && !s->finished ? s->in[s->t % 3].as<float>() + s->prefix * s->C : nullptr;
 }
 
-int
-awm_add_stream_push (awm_add_stream *s, size_t n_frames, int last, const float *out_d[3], size_t out_frames[3])
+/* one push for the P payloads of the object: out_d[i * P + p] = finished tile i of payload p */
+static int
+add_stream_push (awm_add_stream *s, size_t n_frames, int last, const float **out_d, size_t out_frames[3], const char *who)
 {
-  if (!s || !out_d || !out_frames)
-    {
-      set_error ("awm_add_stream_push: bad argument");
-      return AWM_ERR_ARG;
-    }
   awm_ctx *ctx = s->ctx;
-  AWM_ENTER (ctx);
   if (s->finished || n_frames > s->tile || (!last && n_frames != s->tile))
     {
-      set_error ("awm_add_stream_push: every tile but the last one must be full, nothing may follow the last one");
+      set_error (std::string (who) + ": every tile but the last one must be full, nothing may follow the last one");
       return AWM_ERR_ARG;
     }
   const int C = s->C;
-  const size_t N = Params::frame_size;
+  const size_t N = Params::frame_size, P = s->P;
   const long long t = s->t;
   int n_out = 0;
-  for (int i = 0; i < 3; i++)
+  for (size_t i = 0; i < 3; i++)
     {
-      out_d[i] = nullptr;
+      for (size_t p = 0; p < P; p++)
+        out_d[i * P + p] = nullptr;
       out_frames[i] = 0;
     }
   auto slot = [&] (long long k) { return int (k % 3); };
@@ -694,23 +755,38 @@ awm_add_stream_push (awm_add_stream *s, size_t n_frames, int last, const float *
       return 0;
     const float *before = k > 0 ? s->in[slot (k - 1)].as<float>() + (s->tile - N) * C : nullptr;
     const float *after = has_next ? s->in[slot (k + 1)].as<float>() : nullptr;
-    return add_mix_impl (ctx, s->in[slot (k)].as<float>(), s->mix[slot (k)].as<float>(), n, C, s->table.as<int8_t>(), params().water_delta,
-                         (s->skipped + size_t (k) * s->tile) / N, before, after, s->limiter ? s->block_max.as<float>() : nullptr,
-                         s->first_block, s->n_blocks);
+    if (P == 1)
+      return add_mix_impl (ctx, s->in[slot (k)].as<float>(), s->mix[slot (k)].as<float>(), n, C, s->table[0].as<int8_t>(), params().water_delta,
+                           (s->skipped + size_t (k) * s->tile) / N, before, after, s->limiter ? s->block_max.as<float>() : nullptr,
+                           s->first_block, s->n_blocks);
+    // the forward half of every frame (the halos included) once for the payloads of a pass
+    std::vector<float *> outs (P), maxima (P);
+    std::vector<const int8_t *> tables (P);
+    for (size_t p = 0; p < P; p++)
+      {
+        outs[p] = s->mix[slot (k) * P + p].as<float>();
+        maxima[p] = s->block_max.as<float>() + p * s->n_blocks;
+        tables[p] = s->table[p].as<int8_t>();
+      }
+    return add_mix_payloads_impl (ctx, s->in[slot (k)].as<float>(), outs.data(), P, n, C, tables.data(), params().water_delta,
+                                  (s->skipped + size_t (k) * s->tile) / N, before, after, s->limiter ? maxima.data() : nullptr,
+                                  s->first_block, s->n_blocks);
   };
   auto limit_tile = [&] (long long k) -> int {
     const size_t n = s->len[slot (k)];
     if (!n)
       return 0;
     if (s->limiter)
-      if (int rc = awm_add_limit_d (ctx, s->mix[slot (k)].as<float>(), n, C, s->skipped + size_t (k) * s->tile, s->block_max.as<float>(),
-                                    s->first_block, s->n_blocks))
-        return rc;
+      for (size_t p = 0; p < P; p++)
+        if (int rc = awm_add_limit_d (ctx, s->mix[slot (k) * P + p].as<float>(), n, C, s->skipped + size_t (k) * s->tile,
+                                      s->block_max.as<float>() + p * s->n_blocks, s->first_block, s->n_blocks))
+          return rc;
     // (the zeros in front of the caller's first sample are not part of the output: reference wmadd.cc:574-580)
     const size_t cut = k == 0 ? s->prefix : 0;
     if (n > cut)
       {
-        out_d[n_out] = s->mix[slot (k)].as<float>() + cut * C;
+        for (size_t p = 0; p < P; p++)
+          out_d[n_out * P + p] = s->mix[slot (k) * P + p].as<float>() + cut * C;
         out_frames[n_out++] = n - cut;
       }
     return 0;
@@ -742,6 +818,42 @@ awm_add_stream_push (awm_add_stream *s, size_t n_frames, int last, const float *
     }
   s->t++;
   return n_out;
+}
+
+int
+awm_add_stream_push (awm_add_stream *s, size_t n_frames, int last, const float *out_d[3], size_t out_frames[3])
+{
+  if (!s || !out_d || !out_frames)
+    {
+      set_error ("awm_add_stream_push: bad argument");
+      return AWM_ERR_ARG;
+    }
+  awm_ctx *ctx = s->ctx;
+  AWM_ENTER (ctx);
+  if (s->P != 1)
+    {
+      set_error (string_printf ("awm_add_stream_push: the object has %zu payloads (awm_add_stream_push_payloads)", s->P));
+      return AWM_ERR_ARG;
+    }
+  return add_stream_push (s, n_frames, last, out_d, out_frames, "awm_add_stream_push");
+}
+
+int
+awm_add_stream_push_payloads (awm_add_stream *s, size_t n_frames, int last, const float **out_d, size_t out_frames[3])
+{
+  if (!s || !out_d || !out_frames)
+    {
+      set_error ("awm_add_stream_push_payloads: bad argument");
+      return AWM_ERR_ARG;
+    }
+  awm_ctx *ctx = s->ctx;
+  AWM_ENTER (ctx);
+  if (ctx->snr_on && s->P > 1)
+    {
+      set_error ("awm_add_stream_push_payloads: not available while the SNR meter is armed (awm_ctx_snr_begin)");
+      return AWM_ERR_ARG;
+    }
+  return add_stream_push (s, n_frames, last, out_d, out_frames, "awm_add_stream_push_payloads");
 }
 
 int
@@ -1054,7 +1166,6 @@ awm_add_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_he
 /* One input, many payloads (include/awm_hip.h).  At 44.1 kHz the payloads go through K2m in tiles of ADD_MULTI_TILE outputs: a tile pass
  * reads the input once and transforms every frame forward once, whatever the number of its outputs; block maxima and limiter ramp are
  * per output.  Other sample rates (and the debug toggle) loop over the single-payload path. */
-static int g_add_payloads_fused = 1, g_add_payloads_fused_in_use = 0;
 extern "C" void awm_debug_set_add_payloads_fused (int on) { g_add_payloads_fused = on; }
 extern "C" int  awm_debug_add_payloads_fused_in_use (void) { return g_add_payloads_fused_in_use; }
 extern "C" int  awm_debug_add_payloads_tile (void) { return awmk::ADD_MULTI_TILE; }
@@ -1183,6 +1294,123 @@ awm_add_watermark_payloads_d (awm_ctx *ctx, const uint8_t key[16], const char *c
     }
   g_add_payloads_fused_in_use = 1;
   return 0;
+}
+
+/* The P-output twin of add_mix_impl: one span of a stream, a table (on the device), an output and -- with the limiter -- an array of block
+ * maxima per payload.  Passes of at most ADD_MULTI_TILE outputs through K2m's span form, balanced like the whole-stream entry; with the
+ * toggle off (or one payload) a loop over K2.  Nothing is checked here. */
+static int
+add_mix_payloads_impl (awm_ctx *ctx, const float *pcm_in_d, float *const *out_d, size_t n_payloads, size_t n_frames, int n_channels,
+                       const int8_t *const *frame_mod_dev, double water_delta, size_t first_frame, const float *halo_before_d,
+                       const float *halo_after_d, float *const *block_max_d, size_t first_block, size_t n_blocks)
+{
+  g_add_payloads_fused_in_use = 0;
+  if (n_payloads == 1 || !g_add_payloads_fused)
+    {
+      for (size_t p = 0; p < n_payloads; p++)
+        if (int rc = add_mix_impl (ctx, pcm_in_d, out_d[p], n_frames, n_channels, frame_mod_dev[p], water_delta, first_frame, halo_before_d,
+                                   halo_after_d, block_max_d ? block_max_d[p] : nullptr, first_block, n_blocks))
+          return rc;
+      return 0;
+    }
+  hipStream_t st = ctx->stream;
+  awmk::AddMixMultiArgs a {};
+  a.pcm_in = pcm_in_d;
+  a.n_frames = (long long) n_frames;
+  a.n_channels = n_channels;
+  a.neg_delta_up = float (-water_delta * 1);             // as add_mix_impl
+  a.neg_delta_down = float (-water_delta * -1);
+  a.n_blocks = (long long) n_blocks;
+  a.limiter_block = LIMITER_BLOCK;
+  a.block_frames = int (mark_block_frame_count());
+  a.frames_pad_start = int (Params::frames_pad_start);
+  a.frames_per_span = frames_per_span (ctx, (long long) (n_frames + 1023) / 1024, awmk::add_mix_multi_span_waves_per_simd());
+  awmk::AddMixSpan sp {};
+  sp.first_frame = (long long) first_frame;
+  sp.halo_before = halo_before_d;
+  sp.halo_after = halo_after_d;
+  sp.first_block = (long long) first_block;
+  const size_t n_passes = (n_payloads + awmk::ADD_MULTI_TILE - 1) / awmk::ADD_MULTI_TILE;
+  size_t p0 = 0;
+  for (size_t pass = 0; pass < n_passes; pass++)
+    {
+      const size_t n = n_payloads / n_passes + (pass < n_payloads % n_passes ? 1 : 0);
+      for (size_t i = 0; i < size_t (awmk::ADD_MULTI_TILE); i++)
+        {
+          a.o[i] = awmk::AddMixOut {};
+          if (i < n)
+            {
+              a.o[i].out = out_d[p0 + i];
+              a.o[i].frame_mod = frame_mod_dev[p0 + i];
+              a.o[i].block_max = block_max_d ? reinterpret_cast<unsigned int *> (block_max_d[p0 + i]) : nullptr;
+            }
+        }
+      a.n_out = int (n);
+      ProfScope ps (ctx, PROF_ADD_MIX_MULTI, double (1 + n) * double (n_frames) * n_channels * 4.0, st);     // the input once, every output once
+      AWM_HIP_CHECK (awmk::launch_add_mix_multi_span (st, ctx->tabs, a, sp));
+      p0 += n;
+    }
+  g_add_payloads_fused_in_use = 1;
+  return 0;
+}
+
+int
+awm_add_mix_payloads_d (awm_ctx *ctx, const float *pcm_in_d, float *const *out_d, size_t n_payloads, size_t n_frames, int n_channels,
+                        const int8_t *const *frame_mod, double water_delta, size_t first_frame, const float *halo_before_d,
+                        const float *halo_after_d, float *const *block_max_d, size_t first_block, size_t n_blocks)
+{
+  AWM_ENTER (ctx);
+  g_add_payloads_fused_in_use = 0;
+  if (!n_payloads || !pcm_in_d || !out_d || !frame_mod || n_channels < 1)
+    {
+      set_error (n_payloads ? "awm_add_mix_payloads_d: bad argument" : "awm_add_mix_payloads_d: no payloads");
+      return AWM_ERR_ARG;
+    }
+  if (ctx->snr_on && n_payloads > 1)
+    {
+      set_error ("awm_add_mix_payloads_d: not available while the SNR meter is armed (awm_ctx_snr_begin)");
+      return AWM_ERR_ARG;
+    }
+  // everything is checked before anything is enqueued: the input and the halos are read for every output
+  const size_t n_values = n_frames * size_t (n_channels), halo_values = size_t (Params::frame_size) * n_channels;
+  auto overlap = [] (const float *a, size_t na, const float *b, size_t nb) { return a && b && a < b + nb && b < a + na; };
+  for (size_t p = 0; p < n_payloads; p++)
+    {
+      if (!out_d[p] || !frame_mod[p] || (block_max_d && !block_max_d[p]))
+        {
+          set_error (string_printf ("awm_add_mix_payloads_d: null pointer at index %zu", p));
+          return AWM_ERR_ARG;
+        }
+      if (overlap (out_d[p], n_values, pcm_in_d, n_values))
+        {
+          set_error (string_printf ("awm_add_mix_payloads_d: output %zu overlaps the input", p));
+          return AWM_ERR_ARG;
+        }
+      if (overlap (out_d[p], n_values, halo_before_d, halo_values) || overlap (out_d[p], n_values, halo_after_d, halo_values))
+        {
+          set_error (string_printf ("awm_add_mix_payloads_d: output %zu overlaps a halo", p));
+          return AWM_ERR_ARG;
+        }
+      for (size_t q = 0; q < p; q++)
+        if (overlap (out_d[p], n_values, out_d[q], n_values))
+          {
+            set_error (string_printf ("awm_add_mix_payloads_d: outputs %zu and %zu overlap", q, p));
+            return AWM_ERR_ARG;
+          }
+    }
+  if (!n_frames)
+    return 0;
+  // the tables of all payloads side by side in the context's workspace
+  const size_t table_bytes = 2 * mark_block_frame_count() * Params::n_bands;
+  if (int rc = ctx->ws_misc.reserve (n_payloads * table_bytes)) return rc;
+  std::vector<const int8_t *> tables (n_payloads);
+  for (size_t p = 0; p < n_payloads; p++)
+    {
+      tables[p] = ctx->ws_misc.as<int8_t>() + p * table_bytes;
+      AWM_HIP_CHECK (hipMemcpyAsync (ctx->ws_misc.as<int8_t>() + p * table_bytes, frame_mod[p], table_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+  return add_mix_payloads_impl (ctx, pcm_in_d, out_d, n_payloads, n_frames, n_channels, tables.data(), water_delta, first_frame, halo_before_d,
+                                halo_after_d, block_max_d, first_block, n_blocks);
 }
 
 /* add_watermark followed by get_watermark of its output ("watermark, then verify") as ONE call: the library owns the order of the two
@@ -2041,6 +2269,76 @@ awm_add_stream_watermark_file (awm_ctx *ctx, const uint8_t key[16], const char *
     }
   file_fail_reset();
   return add_watermark_at (ctx, capi_key (key), in_path, out_path, payload_hex, zero_frames) ? file_fail_kind() : 0;
+}
+
+/* two paths that name the same file: equal strings, or both exist and are one inode */
+static bool
+same_file (const char *a, const char *b)
+{
+  if (!std::strcmp (a, b))
+    return true;
+  struct stat sa, sb;
+  return stat (a, &sa) == 0 && stat (b, &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+}
+
+int
+awm_add_stream_watermark_payloads_file (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
+                                        const char *in_path, const char *const *out_path,
+                                        const awm_raw_format *raw_in, const awm_raw_format *raw_out, size_t zero_frames)
+{
+  AWM_ENTER (ctx);
+  if (!n_payloads)
+    return 0;
+  if (!key || !payload_hex || !in_path || !out_path)
+    {
+      set_error ("awm_add_watermark_payloads_file: bad argument");
+      return AWM_ERR_ARG;
+    }
+  // everything is checked before a file is opened: creating an output truncates what is there
+  std::vector<std::string> outfiles, bits;
+  for (size_t p = 0; p < n_payloads; p++)
+    {
+      if (!payload_hex[p] || !out_path[p])
+        {
+          set_error (string_printf ("awm_add_watermark_payloads_file: null pointer at index %zu", p));
+          return AWM_ERR_ARG;
+        }
+      if (parse_payload (payload_hex[p]).empty())
+        {
+          set_error (string_printf ("awm_add_watermark_payloads_file: cannot parse payload '%s' at index %zu", payload_hex[p], p));
+          return AWM_ERR_ARG;
+        }
+      if (same_file (out_path[p], in_path))
+        {
+          set_error (string_printf ("awm_add_watermark_payloads_file: output path %zu is the input path", p));
+          return AWM_ERR_ARG;
+        }
+      for (size_t q = 0; q < p; q++)
+        if (same_file (out_path[p], out_path[q]))
+          {
+            set_error (string_printf ("awm_add_watermark_payloads_file: output paths %zu and %zu are equal", q, p));
+            return AWM_ERR_ARG;
+          }
+      outfiles.push_back (out_path[p]);
+      bits.push_back (payload_hex[p]);
+    }
+  FormatScope scope;
+  if (!FormatScope::apply (raw_in, params().input_format, StreamParams::raw_input_format)
+      || !FormatScope::apply (raw_out, params().output_format, StreamParams::raw_output_format))
+    {
+      set_error ("awm_add_watermark_payloads_file: unsupported raw format");
+      return AWM_ERR_ARG;
+    }
+  file_fail_reset();
+  return add_watermark_payloads_at (ctx, capi_key (key), in_path, outfiles, bits, zero_frames) ? file_fail_kind() : 0;
+}
+
+int
+awm_add_watermark_payloads_file (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
+                                 const char *in_path, const char *const *out_path,
+                                 const awm_raw_format *raw_in, const awm_raw_format *raw_out)
+{
+  return awm_add_stream_watermark_payloads_file (ctx, key, payload_hex, n_payloads, in_path, out_path, raw_in, raw_out, 0);
 }
 
 int

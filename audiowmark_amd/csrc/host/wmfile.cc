@@ -779,6 +779,38 @@ public:
 
 /* float32 PCM in HBM -> output stream: encode, copy and write tile by tile (mirror image of load_stream_to_device).
  * `OutputStage` is also what the tile loop of `add` uses for its finished tiles. */
+/* a ring of output tiles that belongs to a call instead of the context (the context's FileStaging holds ONE output ring: the outputs
+ * beyond the first of awm_add_watermark_payloads_file bring their own and give it back when the call ends) */
+struct OutRing
+{
+  PinnedBuffer host[OUT_RING];
+  DevBuffer    dev[OUT_RING];
+  hipEvent_t   encoded[OUT_RING] = {}, copied[OUT_RING] = {};
+  bool
+  ensure_events()
+  {
+    for (int i = 0; i < OUT_RING; i++)
+      for (hipEvent_t *e : { &encoded[i], &copied[i] })
+        if (!*e && hipEventCreateWithFlags (e, hipEventDisableTiming) != hipSuccess)
+          return false;
+    return true;
+  }
+  OutRing() = default;
+  OutRing (const OutRing&) = delete;
+  OutRing& operator= (const OutRing&) = delete;
+  ~OutRing()
+  {
+    for (int i = 0; i < OUT_RING; i++)
+      {
+        for (hipEvent_t e : { encoded[i], copied[i] })
+          if (e)
+            (void) hipEventDestroy (e);
+        host[i].release();
+        dev[i].release();
+      }
+  }
+};
+
 struct OutputStage
 {
   awm_ctx *ctx;
@@ -795,18 +827,18 @@ struct OutputStage
   std::unique_ptr<ChunkWriter> writer;
   size_t k = 0;
   bool ok = false;
-  OutputStage (awm_ctx *c, AudioOutputStream *o, size_t frames_per_chunk, size_t total_frames)
+  OutputStage (awm_ctx *c, AudioOutputStream *o, size_t frames_per_chunk, size_t total_frames, OutRing *own_ring = nullptr)
     : ctx (c), out (o), C (o->n_channels()), chunk_frames (frames_per_chunk)
   {
     raw = out->raw_access (fmt, direct16) && device_codec_supported (fmt);
     unit = raw ? size_t (C) * (fmt.bit_depth / 8) : size_t (C) * sizeof (float);
     copy = ctx->get_copy_stream();
     FileStaging& fs = ctx->file_staging;
-    ok = copy != nullptr && fs.ensure_events();
-    ev_encoded = fs.out_encoded;
-    ev_copied = fs.out_copied;
-    host = fs.out_host;
-    dev = fs.out_dev;
+    ok = copy != nullptr && (own_ring ? own_ring->ensure_events() : fs.ensure_events());
+    ev_encoded = own_ring ? own_ring->encoded : fs.out_encoded;
+    ev_copied = own_ring ? own_ring->copied : fs.out_copied;
+    host = own_ring ? own_ring->host : fs.out_host;
+    dev = own_ring ? own_ring->dev : fs.out_dev;
     for (int i = 0; i < SLOTS && ok; i++)
       ok = host[i].reserve (chunk_frames * unit) == 0 && (!raw || dev[i].reserve (chunk_frames * unit) == 0);
     if (fs.keep)
@@ -1097,6 +1129,115 @@ add_tiles (awm_ctx *ctx, const Key& key, AudioInputStream *in_stream, AudioOutpu
   return 0;
 }
 
+/* add_tiles for ONE input and P payloads (awm_add_watermark_payloads_file): the input side is add_tiles' -- one TileReader, one upload and
+ * one sample decode per tile --, the tile goes through an awm_add_stream with P payloads (the forward transforms once per pass of four
+ * outputs), and every payload has an output stage of its own: ring, copies, writer.  Output 0 uses the context's ring, the others a ring
+ * that belongs to this call. */
+int
+add_tiles_payloads (awm_ctx *ctx, const Key& key, AudioInputStream *in_stream, const std::vector<AudioOutputStream *>& out_streams,
+                    const std::vector<std::string>& payload_hex, size_t zero_frames, size_t tile_frames1024, size_t& n_frames)
+{
+  const size_t P = out_streams.size();
+  const size_t tile = tile_frames1024 * Params::frame_size;
+  const int C = in_stream->n_channels();
+  n_frames = 0;
+  std::vector<const char *> hexes;
+  for (const std::string& h : payload_hex)
+    hexes.push_back (h.c_str());
+  awm_add_stream *add = nullptr;
+  if (awm_add_stream_create_payloads_at (ctx, key.aes_key(), hexes.data(), P, C, tile_frames1024, zero_frames, &add))
+    {
+      error ("audiowmark: GPU watermarking failed: %s\n", awm_last_error());
+      return fail (AWM_ERR_HIP);
+    }
+  struct Guard { awm_add_stream *s; ~Guard() { awm_add_stream_destroy (s); } } guard { add };
+  RawFormat fmt;
+  const bool raw = in_stream->raw_access (fmt) && device_codec_supported (fmt);
+  const size_t unit = raw ? size_t (C) * (fmt.bit_depth / 8) : size_t (C) * sizeof (float);
+  TileReader rd (ctx, in_stream, raw, unit, tile, raw);
+  // (declared before the stages: a stage's destructor waits for the copies into its ring)
+  std::vector<std::unique_ptr<OutRing>> rings;
+  std::vector<std::unique_ptr<OutputStage>> stages;
+  bool ok_all = rd.ok;
+  for (size_t p = 0; p < P && ok_all; p++)
+    {
+      rings.push_back (nullptr);
+      if (p)
+        rings.back() = std::make_unique<OutRing>();
+      stages.push_back (std::make_unique<OutputStage> (ctx, out_streams[p], tile, rd.announced_frames(), rings.back().get()));
+      ok_all = stages.back()->ok;
+    }
+  if (!ok_all)
+    {
+      error ("audiowmark: out of memory for the staging buffers\n");
+      return fail (AWM_ERR_HIP);
+    }
+  bool eof = false;
+  std::vector<const float *> done (3 * P);
+  for (size_t k = 0; !eof; k++)
+    {
+      int b = 0;
+      size_t got = 0;
+      Error err = rd.next (b, got);                        // (read ahead by the I/O workers / the reader thread)
+      if (err)
+        {
+          error ("audiowmark: input stream read failed: %s\n", err.message());
+          return fail (AWM_ERR_IO);
+        }
+      eof = got < tile;
+      float *slot = awm_add_stream_input (add);
+      bool ok = true;
+      // (as add_tiles)
+      if (got && raw)
+        ok = (k < size_t (IN_RING) || hipStreamWaitEvent (rd.copy, rd.ev_used (b), 0) == hipSuccess)
+          && hipMemcpyAsync (rd.dev (b), rd.host (b), got * unit, hipMemcpyHostToDevice, rd.copy) == hipSuccess
+          && hipEventRecord (rd.ev_copied (b), rd.copy) == hipSuccess
+          && hipStreamWaitEvent (ctx->stream, rd.ev_copied (b), 0) == hipSuccess
+          && awm_pcm_decode_d (ctx, rd.dev (b), got * C, fmt.bit_depth, encoding_id (fmt.encoding), fmt.endian == RawFormat::BIG, slot) == 0
+          && hipEventRecord (rd.ev_used (b), ctx->stream) == hipSuccess;
+      else if (got)
+        ok = hipEventRecord (rd.ev_used (b), ctx->stream) == hipSuccess
+          && hipStreamWaitEvent (rd.copy, rd.ev_used (b), 0) == hipSuccess
+          && hipMemcpyAsync (slot, rd.host (b), got * unit, hipMemcpyHostToDevice, rd.copy) == hipSuccess
+          && hipEventRecord (rd.ev_copied (b), rd.copy) == hipSuccess
+          && hipStreamWaitEvent (ctx->stream, rd.ev_copied (b), 0) == hipSuccess;
+      if (ok && got)
+        rd.recycle (b, rd.ev_copied (b));
+      size_t done_frames[3];
+      int n_done = ok ? awm_add_stream_push_payloads (add, got, eof, done.data(), done_frames) : -1;
+      if (n_done < 0)
+        {
+          error ("audiowmark: GPU watermarking failed: %s\n", awm_last_error());
+          return fail (AWM_ERR_HIP);
+        }
+      for (int i = 0; i < n_done; i++)
+        for (size_t p = 0; p < P; p++)
+          // (with zero_frames the last tile carries what hung over the one before it: up to 1023 frames more than a ring slot takes)
+          for (size_t at = 0; at < done_frames[i]; at += tile)
+            if (!stages[p]->put (done[i * P + p] + at * C, std::min (tile, done_frames[i] - at)))
+              {
+                error ("audiowmark: GPU staging failed: %s\n", awm_last_error());
+                return fail (AWM_ERR_HIP);
+              }
+      n_frames += got;
+    }
+  if (hipStreamSynchronize (ctx->stream) != hipSuccess)
+    {
+      error ("audiowmark: GPU watermarking failed\n");
+      return fail (AWM_ERR_HIP);
+    }
+  for (size_t p = 0; p < P; p++)
+    {
+      Error err = stages[p]->finish();
+      if (err)
+        {
+          error ("audiowmark output write failed: %s\n", err.message());
+          return fail (AWM_ERR_IO);
+        }
+    }
+  return 0;
+}
+
 /* `add` at another sample rate: the WatermarkResampler path works on the whole stream in HBM (awm_add_watermark_d); the
  * host side is still bounded (chunked staging both ways) */
 int
@@ -1280,6 +1421,130 @@ add_watermark_at (awm_ctx *ctx, const Key& key, const std::string& infile, const
   if (params().output_format == Format::RAW)
     info_format ("Raw Output", StreamParams::raw_output_format);
   return add_stream_watermark (ctx, key, in_stream.get(), out_stream.get(), bits, zero_frames);
+}
+
+/* (debug hook) tile of add_watermark_payloads_at's fused path in 1024-sample frames; 0: the rule below */
+static std::atomic<int> g_payloads_file_tile { 0 };
+extern "C" void awm_debug_set_payloads_file_tile (int frames1024) { g_payloads_file_tile.store (frames1024 < 0 ? 0 : frames1024, std::memory_order_relaxed); }
+
+/* add_watermark_at of one input file for several payloads (awm_add_watermark_payloads_file, include/awm_hip.h): outfiles[p] is the file
+ * add_watermark_at writes with bits[p].  The arguments have been checked by the caller (payloads parse, paths differ). */
+int
+add_watermark_payloads_at (awm_ctx *ctx, const Key& key, const std::string& infile, const std::vector<std::string>& outfiles,
+                           const std::vector<std::string>& bits, size_t zero_frames)
+{
+  const size_t P = outfiles.size();
+  if (!P)
+    return 0;
+  auto loop = [&] () -> int {
+    for (size_t p = 0; p < P; p++)
+      if (int rc = add_watermark_at (ctx, key, infile, outfiles[p], bits[p], zero_frames))
+        return rc;
+    return 0;
+  };
+  if (P == 1 || P > size_t (AWM_ADD_STREAM_MAX_PAYLOADS) || params().snr)
+    return loop();
+  Error err;
+  auto in_stream = AudioInputStream::create (infile, err);
+  if (err)
+    {
+      error ("audiowmark: error opening %s: %s\n", infile.c_str(), err.message());
+      return fail (AWM_ERR_IO);
+    }
+  if (in_stream->sample_rate() != Params::mark_sample_rate)
+    {
+      // the resampled add is not fused: one pass over the file per payload
+      in_stream.reset();
+      return loop();
+    }
+  int out_bit_depth = in_stream->bit_depth();
+  Encoding out_encoding = in_stream->encoding();
+  if (in_stream->bit_depth() < 16)
+    {
+      out_bit_depth = 16;
+      out_encoding = Encoding::SIGNED;
+    }
+  std::vector<decltype (parse_payload (std::string()))> bitvecs;
+  for (const std::string& b : bits)
+    {
+      bitvecs.push_back (parse_payload (b));
+      if (bitvecs.back().empty())
+        return fail (AWM_ERR_ARG);
+    }
+  std::vector<std::unique_ptr<AudioOutputStream>> out_streams;
+  std::vector<AudioOutputStream *> outs;
+  std::vector<std::string> hexes;
+  const int C = in_stream->n_channels();
+  for (size_t p = 0; p < P; p++)
+    {
+      out_streams.push_back (AudioOutputStream::create (outfiles[p], C, in_stream->sample_rate(), out_bit_depth, out_encoding, in_stream->n_frames(), err));
+      if (err)
+        {
+          error ("audiowmark: error writing to %s: %s\n", outfiles[p].c_str(), err.message());
+          return fail (AWM_ERR_IO);
+        }
+      outs.push_back (out_streams.back().get());
+      hexes.push_back (bit_vec_to_str (bitvecs[p]));
+    }
+  auto info_head = [&] (size_t p) {
+    info ("Input:        %s\n", infile.c_str());
+    if (params().input_format == Format::RAW)
+      info_format ("Raw Input", StreamParams::raw_input_format);
+    info ("Output:       %s\n", outfiles[p].c_str());
+    if (params().output_format == Format::RAW)
+      info_format ("Raw Output", StreamParams::raw_output_format);
+    info ("Message:      %s\n", hexes[p].c_str());
+    info ("Strength:     %.6g\n\n", params().water_delta * 1000);
+    if (in_stream->n_frames() == AudioInputStream::N_FRAMES_UNKNOWN)
+      info ("Time:         unknown\n");
+    else
+      {
+        const size_t orig_seconds = in_stream->n_frames() / in_stream->sample_rate();
+        info ("Time:         %zd:%02zd\n", orig_seconds / 60, orig_seconds % 60);
+      }
+    info ("Sample Rate:  %d\n", in_stream->sample_rate());
+    info ("Channels:     %d\n", C);
+  };
+  /* the tile: as large as add_tiles' (4096 frames), but so that the P output rings together -- P x OUT_RING slots x tile x bytes per
+   * output frame -- stay within PINNED_CAP of page-locked memory; never below the 128 frames an awm_add_stream needs */
+  constexpr size_t PINNED_CAP = size_t (1) << 30, TILE_MAX = 4096, TILE_MIN = 128;
+  size_t tile_frames1024 = size_t (g_payloads_file_tile.load (std::memory_order_relaxed));
+  if (!tile_frames1024)
+    {
+      RawFormat ofmt;
+      bool direct16 = false;
+      const bool oraw = outs[0]->raw_access (ofmt, direct16) && device_codec_supported (ofmt);
+      const size_t ounit = oraw ? size_t (C) * (ofmt.bit_depth / 8) : size_t (C) * sizeof (float);
+      tile_frames1024 = PINNED_CAP / (P * size_t (OUT_RING) * Params::frame_size * ounit);
+      tile_frames1024 = std::min (TILE_MAX, std::max (TILE_MIN, tile_frames1024));
+    }
+  tile_frames1024 = std::max (TILE_MIN, tile_frames1024);
+  size_t n_frames = 0;
+  if (int rc = add_tiles_payloads (ctx, key, in_stream.get(), outs, hexes, zero_frames, tile_frames1024, n_frames))
+    return rc;
+  const bool short_input = in_stream->n_frames() != AudioInputStream::N_FRAMES_UNKNOWN && n_frames != in_stream->n_frames();
+  for (size_t p = 0; p < P; p++)
+    {
+      info_head (p);
+      info ("Data Blocks:  %d\n", count_data_blocks (n_frames, in_stream->sample_rate(), !params().test_no_limiter, zero_frames));
+      if (short_input)
+        {
+          auto msg = string_printf ("unexpected EOF; input frames (%zd) != output frames (%zd)", in_stream->n_frames() + zero_frames, n_frames + zero_frames);
+          if (params().strict)
+            {
+              error ("audiowmark: error: %s\n", msg.c_str());
+              return fail (AWM_ERR_IO);
+            }
+          warning ("audiowmark: warning: %s\n", msg.c_str());
+        }
+      err = out_streams[p]->close();
+      if (err)
+        {
+          error ("audiowmark: closing output stream failed: %s\n", err.message());
+          return fail (AWM_ERR_IO);
+        }
+    }
+  return 0;
 }
 
 /* add_watermark (key, infile, outfile, bits) followed by get_watermark (key, outfile) -- "watermark, then verify that the payload decodes"

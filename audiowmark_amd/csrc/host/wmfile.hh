@@ -14,6 +14,9 @@ int add_stream_watermark (awm_ctx *ctx, const Key& key, AudioInputStream *in_str
 int add_watermark (awm_ctx *ctx, const Key& key, const std::string& infile, const std::string& outfile, const std::string& bits);
 int add_watermark_at (awm_ctx *ctx, const Key& key, const std::string& infile, const std::string& outfile, const std::string& bits,
                       size_t zero_frames);
+// add_watermark_at of ONE input for several payloads: outfiles[p] is the file add_watermark_at writes with bits[p] (input read once at 44.1 kHz)
+int add_watermark_payloads_at (awm_ctx *ctx, const Key& key, const std::string& infile, const std::vector<std::string>& outfiles,
+                               const std::vector<std::string>& bits, size_t zero_frames);
 int get_watermark (awm_ctx *ctx, const std::vector<Key>& key_list, const std::string& infile, const std::string& orig_pattern);
 class ResultSet;
 int get_watermark_stream (awm_ctx *ctx, const std::vector<Key>& key_list, AudioInputStream *in_stream, bool print_speed, ResultSet& result_set,

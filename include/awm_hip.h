@@ -129,6 +129,18 @@ int awm_add_limit_d (awm_ctx *ctx, float *out_d, size_t n_frames, int n_channels
                      const float *block_max_d, size_t first_block, size_t n_blocks);
 int awm_add_d (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
                const int8_t *frame_mod, double water_delta, int use_limiter);
+/* awm_add_mix_d for ONE span and n_payloads tables: out_d[p] (and, with a limiter, block_max_d[p]) receive what awm_add_mix_d writes
+ * for the span with frame_mod[p], bit for bit.  The span is read, windowed and transformed forward once per pass of at most 4 outputs
+ * (K2m's span form, hip/kernels.hip; passes are balanced: 5 payloads run as 3 + 2) -- the halo frames too.  Same rules as awm_add_mix_d:
+ * the span starts on a frame boundary, every block_max_d[p] (n_blocks floats from block first_block) is pre-initialised with
+ * awm_add_init_block_max_d, the outputs are limited one by one with awm_add_limit_d.  frame_mod: n_payloads host tables.
+ * AWM_ERR_ARG with nothing enqueued: n_payloads == 0, a NULL pointer (block_max_d itself may be NULL: no limiter), an output that
+ * overlaps the input, a halo or another output; with more than one payload also a call while the SNR meter is armed.
+ * awm_debug_set_add_payloads_fused (0) makes it a loop over awm_add_mix_d. */
+int awm_add_mix_payloads_d (awm_ctx *ctx, const float *pcm_in_d, float *const *out_d, size_t n_payloads, size_t n_frames, int n_channels,
+                            const int8_t *const *frame_mod /* host, one per payload */, double water_delta, size_t first_frame,
+                            const float *halo_before_d, const float *halo_after_d,
+                            float *const *block_max_d /* NULL: no limiter; else n_payloads arrays */, size_t first_block, size_t n_blocks);
 
 /* add as a tile loop with bounded memory -- the reference's streaming add_stream_watermark (wmadd.cc:520-589) keeps one
  * frame (WatermarkSynth, wmadd.cc:173,220-222) and up to two limiter blocks (limiter.cc:51-64) of state; here the unit in
@@ -153,6 +165,22 @@ int    awm_add_stream_create_at (awm_ctx *ctx, const uint8_t key[16], const char
 void   awm_add_stream_destroy (awm_add_stream *s);
 float *awm_add_stream_input (awm_add_stream *s);
 int    awm_add_stream_push (awm_add_stream *s, size_t n_frames, int last, const float *out_d[3], size_t out_frames[3]);
+/* The tile loop for ONE input and n_payloads payloads (1 .. AWM_ADD_STREAM_MAX_PAYLOADS) with one key: the same object with three input
+ * slots as before, three mix slots, a table and an array of block maxima PER PAYLOAD.  awm_add_stream_input / awm_add_stream_destroy are
+ * unchanged; awm_add_stream_push_payloads pushes as awm_add_stream_push does (mix tile t - 1 once tile t is there -- one
+ * awm_add_mix_payloads_d-like pass over the tile and its halos for all payloads --, limit tile t - 2 per output, flush on last) and returns
+ * how many tiles became final: out_d has room for 3 * n_payloads pointers, out_d[i * n_payloads + p] is finished tile i of payload p,
+ * out_frames[i] its length for every payload.  zero_frames as in awm_add_stream_create_at.  The concatenated output p is bit-identical to
+ * an awm_add_stream with payload p.  HBM: (3 + 3 n_payloads) tiles.
+ * AWM_ERR_ARG: n_payloads == 0 or > AWM_ADD_STREAM_MAX_PAYLOADS, a payload that does not parse (awm_last_error names its index),
+ * awm_add_stream_push on an object with more than one payload, creating such an object -- or pushing to one with more than one payload --
+ * while the SNR meter is armed.  awm_add_stream_push_payloads on a one-payload object is awm_add_stream_push. */
+#define AWM_ADD_STREAM_MAX_PAYLOADS 64
+int    awm_add_stream_create_payloads_at (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
+                                          int n_channels, size_t tile_frames1024, size_t zero_frames, awm_add_stream **out);
+size_t awm_add_stream_payloads (const awm_add_stream *s);        /* 0 for NULL */
+int    awm_add_stream_push_payloads (awm_add_stream *s, size_t n_frames, int last,
+                                     const float **out_d /* [3][n_payloads] */, size_t out_frames[3]);
 
 /* I/O staging: RawConverter::from_raw / to_raw (rawconverter.cc:155-286) on the device, so that files cross PCIe in
  * their own sample format.  bit_depth 8/16/24/32 (integer) or 32/64 (float); encoding 0 signed, 1 unsigned, 2 float.
@@ -241,7 +269,8 @@ int awm_add_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payloa
  * awm_add_watermark_d.  n_payloads == 0 or n_frames == 0: returns 0, writes nothing; n_payloads == 1: the single-payload path.
  * AWM_ERR_ARG with nothing enqueued: a payload that does not parse (awm_last_error names its index), a NULL pointer, an output that
  * overlaps the input or another output, a call while the SNR meter is armed (awm_ctx_snr_begin).
- * Not offered in this form: the file level, the command line, the tile stream, sharding, a key per payload. */
+ * The same for a span of a stream: awm_add_mix_payloads_d; with bounded memory: awm_add_stream_create_payloads_at; for files:
+ * awm_add_watermark_payloads_file.  Not offered in this form: the command line, sharding, a key per payload. */
 int awm_add_watermark_payloads_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
                                   const float *pcm_in_d, float *const *out_d, size_t n_frames, int n_channels, int sample_rate);
 /* Streams at another sample rate.  The reference resamples them to 44.1 kHz with zita-resampler (hlen 16): the fixed-ratio
@@ -311,6 +340,23 @@ int awm_add_watermark_file (awm_ctx *ctx, const uint8_t key[16], const char *pay
  * zeros are materialised in HBM in front of the input (the resamplers see them, resample.cc:150-168). */
 int awm_add_stream_watermark_file (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, const char *in_path, const char *out_path,
                                    const awm_raw_format *raw_in, const awm_raw_format *raw_out, size_t zero_frames);
+/* awm_add_watermark_file / awm_add_stream_watermark_file of ONE input file with n_payloads payloads and one key: out_path[p] is byte for
+ * byte the file awm_add_stream_watermark_file (ctx, key, payload_hex[p], in_path, out_path[p], raw_in, raw_out, zero_frames) writes.  At
+ * 44.1 kHz the input is read, uploaded and sample-decoded once and pushed through an awm_add_stream with n_payloads payloads; every
+ * payload has an output stage of its own (a ring of page-locked tiles, a writer), so the files are written side by side.  Host memory
+ * stays bounded whatever the file length and n_payloads: the tile is the largest number of 1024-sample frames, at most 4096 and never
+ * below 128, for which the output rings together -- n_payloads rings x 4 slots x tile x bytes per output frame -- stay within 1 GiB of
+ * page-locked memory (stereo 16 bit: 4096 frames up to 16 payloads, 1024 frames at 64).  The additional rings belong to the call.
+ * Other sample rates, `snr` in the parameters, n_payloads == 1 and more than AWM_ADD_STREAM_MAX_PAYLOADS payloads: a loop over
+ * awm_add_stream_watermark_file.  n_payloads == 0: returns 0 and touches nothing.
+ * AWM_ERR_ARG before any file is opened or truncated: a NULL pointer, a payload that does not parse, two equal output paths, an output
+ * path equal to the input path.  Information lines appear once per output, in payload order. */
+int awm_add_watermark_payloads_file (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
+                                     const char *in_path, const char *const *out_path,
+                                     const awm_raw_format *raw_in, const awm_raw_format *raw_out);
+int awm_add_stream_watermark_payloads_file (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
+                                            const char *in_path, const char *const *out_path,
+                                            const awm_raw_format *raw_in, const awm_raw_format *raw_out, size_t zero_frames);
 int awm_get_watermark_file (awm_ctx *ctx, const uint8_t key[16], const char *in_path, const awm_raw_format *raw_in,
                             size_t max_out, awm_pattern *out);
 /* add_watermark (key, infile, outfile, bits) followed by get_watermark (key, outfile) ("watermark, then verify that the payload decodes":
@@ -490,8 +536,9 @@ void awm_debug_set_add_batched (int on);   /* add of a batch of stereo clips: 2 
                                             * group's tables built while the previous group of 256 clips is watermarked | 0 four launches per clip on eight lanes; the
                                             * outputs are the same */
 void awm_debug_set_add_slab_mb (int mb);   /* add: 0 (default) one fused add over the stream, then the limiter | > 0: in slabs of that many MB (cache experiment) */
-void awm_debug_set_add_payloads_fused (int on);   /* awm_add_watermark_payloads_d: 1 (default) the fused kernel | 0 a loop over the single-payload path */
-int  awm_debug_add_payloads_fused_in_use (void);  /* 1 if the last awm_add_watermark_payloads_d ran the fused kernel */
+void awm_debug_set_add_payloads_fused (int on);   /* awm_add_watermark_payloads_d, awm_add_mix_payloads_d: 1 (default) the fused kernel | 0 a loop over the single-payload path */
+int  awm_debug_add_payloads_fused_in_use (void);  /* 1 if the last awm_add_watermark_payloads_d / awm_add_mix_payloads_d (also inside a stream push) ran the fused kernel */
+void awm_debug_set_payloads_file_tile (int frames1024);   /* awm_add_watermark_payloads_file: tile of the fused path in 1024-sample frames (>= 128) | 0 (default) automatic */
 int  awm_debug_add_payloads_tile (void);          /* outputs per pass of the fused kernel over the input (ADD_MULTI_TILE) */
 void awm_debug_set_fft_pair (int on);      /* stereo add: both channels' transforms pipelined in one wave (default) | one after the other */
 void awm_debug_set_clip_poison (int on);    /* clip batches: the padded slices are filled with NaNs before the copies are written (the copy writes a clip and 2048
