@@ -35,6 +35,7 @@
 //                                                                 (effective clock under this kernel 2.3 GHz, GRBM_GUI_ACTIVE; an earlier
 //                                                                 "1.6 GHz" came from s_memtime, which counts a constant reference clock)
 #include "kernels.hh"
+#include <atomic>
 #include <type_traits>
 
 namespace awmk {
@@ -433,6 +434,11 @@ pack_scan_chains (const int *packed, int rows_per_bit, unsigned *out)
       }
 }
 
+int g_scan_generic = 0;          // (debug toggle: the generic K5 wherever the caller has no per-slice tables)
+extern "C" void awm_debug_set_scan_generic (int on) { g_scan_generic = on; }
+static std::atomic<int> g_scan_generic_launches { 0 };      // (counted on the fallback only: the streaming path pays nothing)
+extern "C" int awm_debug_scan_generic_launches() { return g_scan_generic_launches.load(); }
+
 hipError_t
 launch_sync_scan_window (hipStream_t st, const SyncScanArgs& a, int total_frames)
 {
@@ -440,10 +446,11 @@ launch_sync_scan_window (hipStream_t st, const SyncScanArgs& a, int total_frames
     return hipSuccess;
   if (a.row_stride != 1 || a.n_planes > 65535 || (a.band_stride & 63) || a.lane_count)
     return hipErrorInvalidValue;
-  if ((a.have && !a.have_is_run) || !a.table.chains || total_frames >= 0xffff || a.n_lanes + total_frames > 0x1000000 || a.table.rows_per_bit > 4096)
+  if ((g_scan_generic && !a.table.chains_slice_stride) || (a.have && !a.have_is_run) || !a.table.chains || total_frames >= 0xffff || a.n_lanes + total_frames > 0x1000000 || a.table.rows_per_bit > 4096)
     {
       if (a.table.chains_slice_stride)
         return hipErrorInvalidValue;                      // (per-slice key tables exist for this kernel only)
+      g_scan_generic_launches++;
       return launch_sync_scan (st, a);                    // arbitrary skipped frames: the generic kernel handles any `have`
     }
   const long long px = ((a.n_lanes + QUAD_TILE - 1) / QUAD_TILE + 7) / 8;

@@ -511,6 +511,8 @@ void awm_debug_set_k4s_ablate (int flags);     /* measurement only (tools/gpu_k4
 int  awm_debug_sync_db_sliding_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channels, const long long *base_d, size_t n_streams,
                                   int count, int ld, float *out_d);
 void awm_debug_set_soft_bits_generic (int on); /* K7: one thread per soft bit for every shape (the fallback kernel) | four bits per wave */
+void awm_debug_set_scan_generic (int on);      /* K5w: 1 the approximate search takes launch_sync_scan_window's fallback, the generic K5 (scores identical) | 0 (default) the streaming kernel */
+int  awm_debug_scan_generic_launches (void);   /* K5w: how often launch_sync_scan_window has taken that fallback in this process, by the switch or by its own conditions */
 void awm_debug_set_chunk_stagger (int mode); /* get: phase offset between the chunk lanes -- 0 all chunks start together | 1 chunk i + 1 behind chunk i's
                                              * dB kernel | 2 behind its scan | -1 (default) 1 for streams of up to `lanes` chunks, 2 for longer ones */
 void awm_debug_set_resample_phase (int on);  /* K10: 1 (default) the phase-per-thread kernel for stereo 48 <-> 44.1 kHz | 0 the generic kernel (outputs identical) */

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _oracle as orc
+from _scan import clip_padded as _clip_padded
 
 pytestmark = pytest.mark.gpu
 
@@ -933,15 +934,6 @@ def test_get_on_tiny_inputs(gpu, n):
         assert len(got) >= 1 and all(p["type"] == 1 for p in got)
         return
     assert [pkey(p) for p in got] == [pkey(p) for p in want]
-
-
-def _clip_padded(x):
-    ch = x.shape[1]
-    n = (2226 + 5) * 1024 * ch
-    vals = x.ravel()
-    last = min(n, vals.size)
-    pad_start = n + (n - last if last < n else 0)
-    return np.concatenate([np.zeros(pad_start, np.float32), vals[:last], np.zeros(n, np.float32)]).reshape(-1, ch)
 
 
 @pytest.mark.parametrize("kind", ["one_sample", "all_zero"])
