@@ -348,6 +348,7 @@ hipError_t launch_soft_prep (hipStream_t st, const SoftPrepArgs& a);
 hipError_t launch_viterbi (hipStream_t st, const float *const soft[3], const long long n_blocks[3], long long n_steps,
                            unsigned char *const decisions_ws[3], int *const bits_out[3], float *const error_out[3], unsigned int *sync_ws);
 size_t viterbi_workspace_bytes (long long coded_len, int rate, long long n_blocks);
+bool viterbi_steps_supported (long long n_steps);  // 15 <= n_steps and a plan of at most 64 rounds: everything else is refused on the host
 size_t viterbi_sync_bytes (long long n_blocks);
 /* microseconds per launch of a chain of empty dependent launches on the (idle) stream: decides, per process, between the chain of 16
  * launches and the one-launch kernel (viterbi.hip) */

@@ -136,8 +136,32 @@ ld_words (const unsigned int *p)
   return *reinterpret_cast<const uint4 *> (p);
 }
 
-/* workspace of one block: [metrics A][metrics B][decision words of all rounds] */
+/* workspace of one block: [metrics A][metrics B][decision words of all rounds][flag] */
 constexpr size_t V_METRIC_BYTES = V_STATES * sizeof (float);
+constexpr size_t V_FLAG_BYTES = 256;                       // (keeps the blocks 256-byte aligned)
+
+/* The block's flag (first word of the last V_FLAG_BYTES of its workspace): 1 = one of its soft bits is NaN, wherever it sits.  Such a
+ * block takes the checked path in every round, where a NaN sum fails every comparison exactly like in the reference (the state then
+ * counts as unreachable from the next step on); the plain path would carry NaN metrics along and report a NaN error value.  The first
+ * launch of a chain looks at the whole block once and leaves the answer here for the launches that follow; its own rounds all start
+ * before step V_ORDER and are checked whatever the input.  Infinite soft bits need no flag: their costs are +inf, never NaN, "<" and the
+ * chain of the smaller predecessor treat +inf like any other value, and the window test fails (inf - inf, x > inf), which repeats the
+ * step with both chains. */
+__device__ __forceinline__ unsigned int *
+block_flag (unsigned char *ws, size_t block_ws_bytes)
+{
+  return reinterpret_cast<unsigned int *> (ws + block_ws_bytes - V_FLAG_BYTES);
+}
+
+/* asked by a whole workgroup (it contains a barrier) */
+__device__ __forceinline__ bool
+block_has_nan (const float *coded, int coded_len)
+{
+  int nan = 0;
+  for (int i = threadIdx.x; i < coded_len; i += blockDim.x)
+    nan |= !(coded[i] == coded[i]);
+  return __syncthreads_or (nan) != 0;
+}
 
 struct RoundPlan           // host side description of one launch
 {
@@ -318,9 +342,8 @@ viterbi_round_kernel (ViterbiBatch b, int step0, int parity_in, size_t dec_offse
   float *m_out = reinterpret_cast<float *> (ws + (parity_in ? 0 : V_METRIC_BYTES));
   unsigned int *dec = reinterpret_cast<unsigned int *> (ws + 2 * V_METRIC_BYTES) + dec_offset;
   const float *coded = b.soft[t] + (size_t) blk * b.n_steps * rate;
-  // normalize_soft_bits turns ALL bits of a block into NaN or none (0 / 0 mean): such a block takes the checked path, where a
-  // NaN sum fails every comparison exactly like in the reference
-  const bool finite = coded[0] == coded[0];
+  // a block with a NaN among its soft bits takes the checked path (block_flag, written by the chain's first launch)
+  const bool finite = *block_flag (ws, b.block_ws_bytes) == 0;
   if (t == 0)
     {
       if (PLAIN && finite) viterbi_round<0, K, true> (coded, step0, m_in, m_out, dec, L);
@@ -426,7 +449,15 @@ viterbi_super_kernel (ViterbiBatch b, int step0, int parity_in, SuperOffsets so)
   float *m_out = reinterpret_cast<float *> (ws + (parity_in ? 0 : V_METRIC_BYTES));
   unsigned int *dec = reinterpret_cast<unsigned int *> (ws + 2 * V_METRIC_BYTES);
   const float *coded = b.soft[t] + (size_t) blk * b.n_steps * rate;
-  const bool finite = coded[0] == coded[0];              // (see viterbi_round_kernel)
+  // (see viterbi_round_kernel)  The launch that starts from the initial metrics is the chain's first: its three rounds are checked
+  // anyway (NPF = 3), and its family-0 workgroup leaves the flag for the launches behind it.
+  if (so.first && g == 0)
+    {
+      const bool has_nan = block_has_nan (coded, b.n_steps * rate);
+      if (lane == 0)
+        *block_flag (ws, b.block_ws_bytes) = has_nan;
+    }
+  const bool finite = so.first || *block_flag (ws, b.block_ws_bytes) == 0;
   if (t == 0)
     {
       if (finite) viterbi_super_round<0, NPF> (coded, step0, m_in, m_out, dec, so.off, g, lane, lds_a, lds_b, so.in_perm != 0, so.out_perm != 0, so.first != 0);
@@ -450,9 +481,17 @@ viterbi_init_kernel (ViterbiBatch b)
   int blk = blockIdx.y, t = 0;
   if (blk >= b.n[0]) { blk -= b.n[0]; t = 1; }
   if (t == 1 && blk >= b.n[1]) { blk -= b.n[1]; t = 2; }
-  float *m = reinterpret_cast<float *> (b.ws[t] + (size_t) blk * b.block_ws_bytes);
+  unsigned char *ws = b.ws[t] + (size_t) blk * b.block_ws_bytes;
+  float *m = reinterpret_cast<float *> (ws);
   const int i = blockIdx.x * 256 + threadIdx.x;
   m[i] = i == 0 ? 0.f : -1.f;                              // start state 0, everything else unreachable (convcode.cc:144-146)
+  if (blockIdx.x == 0)                                     // the chain's first launch: the block's flag for the rounds (block_flag)
+    {
+      const int rate = t == 2 ? 12 : 6;
+      const bool has_nan = block_has_nan (b.soft[t] + (size_t) blk * b.n_steps * rate, b.n_steps * rate);
+      if (threadIdx.x == 0)
+        *block_flag (ws, b.block_ws_bytes) = has_nan;
+    }
 }
 
 constexpr int MAX_ROUNDS = 64;
@@ -658,7 +697,8 @@ viterbi_persistent_decode (const ViterbiBatch& b, const TracePlan& plan, int n_s
   float *metric[2] = { reinterpret_cast<float *> (ws), reinterpret_cast<float *> (ws + V_METRIC_BYTES) };
   unsigned int *dec = reinterpret_cast<unsigned int *> (ws + 2 * V_METRIC_BYTES);
   const float *coded = b.soft[t] + (size_t) blk * b.n_steps * rate;
-  const bool finite = coded[0] == coded[0];              // (see viterbi_round_kernel)
+  // (see viterbi_round_kernel; here every workgroup looks at the whole block itself, once for all 143 steps: nothing to exchange)
+  const bool finite = !block_has_nan (coded, b.n_steps * rate);
   int parity = 0;
   unsigned int meetings = 0;
   if (n_super == 0)
@@ -738,7 +778,7 @@ viterbi_last_round_kernel (ViterbiBatch b, int step0, int parity_in, size_t dec_
   float *m_out = reinterpret_cast<float *> (ws + (parity_in ? 0 : V_METRIC_BYTES));
   unsigned int *dec = reinterpret_cast<unsigned int *> (ws + 2 * V_METRIC_BYTES) + dec_offset;
   const float *coded = b.soft[t] + (size_t) blk * b.n_steps * rate;
-  const bool finite = coded[0] == coded[0];              // (see viterbi_round_kernel)
+  const bool finite = *block_flag (ws, b.block_ws_bytes) == 0;       // (see viterbi_round_kernel)
   if (t == 0)
     {
       if (PLAIN && finite) viterbi_round<0, K, true, true> (coded, step0, m_in, m_out, dec, L);
@@ -838,8 +878,19 @@ viterbi_workspace_bytes (long long coded_len, int rate, long long n_blocks)
   size_t words = 0;
   for (const auto& r : rounds)
     words += size_t (V_STATES >> r.k) * dec_words (r.k);
-  const size_t per_block = (2 * V_METRIC_BYTES + words * sizeof (unsigned int) + 255) & ~size_t (255);
+  const size_t per_block = ((2 * V_METRIC_BYTES + words * sizeof (unsigned int) + 255) & ~size_t (255)) + V_FLAG_BYTES;
   return per_block * size_t (n_blocks);
+}
+
+/* the trellis lengths launch_viterbi has a plan for: at least the 15 termination steps, and at most MAX_ROUNDS rounds (every length
+ * from 15 on splits into rounds of 4 and at most three of 3) -- for the host to refuse the others before it sizes or launches anything */
+bool
+viterbi_steps_supported (long long n_steps)
+{
+  if (n_steps < V_ORDER || n_steps > 4 * MAX_ROUNDS)
+    return false;
+  const auto rounds = plan_rounds (int (n_steps));
+  return !rounds.empty() && rounds.size() <= size_t (MAX_ROUNDS);
 }
 
 int g_viterbi_super = 1;         // (debug toggle)

@@ -186,6 +186,7 @@ viterbi_decode_all (awm_ctx *ctx, const std::vector<std::vector<float>> soft[3],
                     std::vector<float> errors[3])
 {
   size_t n_steps = 0;
+  bool have_steps = false;
   for (int t = 0; t < 3; t++)
     {
       bits[t].assign (soft[t].size(), {});
@@ -193,16 +194,23 @@ viterbi_decode_all (awm_ctx *ctx, const std::vector<std::vector<float>> soft[3],
       const size_t rate = t == 2 ? 12 : 6;
       for (const auto& v : soft[t])
         {
-          if (v.size() % rate || (n_steps && v.size() / rate != n_steps))
+          if (v.size() % rate || (have_steps && v.size() / rate != n_steps))
             {
-              set_error ("viterbi_decode: ragged batch");
+              set_error ("viterbi_decode: ragged batch (a coded length that is no multiple of the rate, or blocks of different lengths)");
               return AWM_ERR_ARG;
             }
           n_steps = v.size() / rate;
+          have_steps = true;
         }
     }
-  if (!n_steps)
+  if (soft[0].empty() && soft[1].empty() && soft[2].empty())
     return 0;
+  // decided here, before any size is computed from n_steps - conv_order and before anything is copied or launched
+  if (!awmk::viterbi_steps_supported ((long long) std::min<size_t> (n_steps, 1u << 20)))
+    {
+      set_error ("viterbi_decode: " + std::to_string (n_steps) + " trellis steps per block; the decoder takes 15 (the termination alone) up to 256 (64 rounds of 4)");
+      return AWM_ERR_ARG;
+    }
   hipStream_t st = ctx->stream;
   const size_t n_out = n_steps - conv_order;
   const size_t max_batch = 512;            // decodes per launch and code type
@@ -256,7 +264,8 @@ viterbi_decode_all (awm_ctx *ctx, const std::vector<std::vector<float>> soft[3],
       }
       std::vector<int> hbits (bits_total);
       std::vector<float> herr (err_total);
-      AWM_HIP_CHECK (hipMemcpyAsync (hbits.data(), ctx->ws_viterbi_bits.ptr, hbits.size() * sizeof (int), hipMemcpyDeviceToHost, st));
+      if (!hbits.empty())                      // (15 steps: the termination alone, no payload bits)
+        AWM_HIP_CHECK (hipMemcpyAsync (hbits.data(), ctx->ws_viterbi_bits.ptr, hbits.size() * sizeof (int), hipMemcpyDeviceToHost, st));
       AWM_HIP_CHECK (hipMemcpyAsync (herr.data(), ctx->ws_viterbi_err.ptr, herr.size() * sizeof (float), hipMemcpyDeviceToHost, st));
       AWM_HIP_CHECK (stream_wait (st));
       if (int rc = viterbi_check_errors (ctx, herr.data(), herr.size()))

@@ -216,7 +216,9 @@ int awm_block_soft_bits_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm
                            int n_channels, const uint64_t *index, size_t n_blocks, float *out, int *ok);
 
 /* conv_decode_soft (convcode.cc:128-213) for a batch of equally typed blocks.
- * soft: [n][coded_len] normalised soft bits; bits_out: [n][coded_len/rate - 15]; error_out[n]. */
+ * soft: [n][coded_len] normalised soft bits; bits_out: [n][coded_len/rate - 15]; error_out[n].
+ * coded_len / rate = 15 ... 256 trellis steps (the termination alone up to 64 rounds of 4 steps); other lengths and a coded_len
+ * that is no multiple of the rate (6 for A and B blocks, 12 for AB) return AWM_ERR_ARG before anything is launched. */
 int awm_viterbi_decode (awm_ctx *ctx, int block_type, const float *soft, size_t coded_len, size_t n,
                         int *bits_out, float *error_out);
 
@@ -487,6 +489,7 @@ int    awm_speed_clip_candidates (const uint8_t key[16], const float *hashed_val
 /* A / B hooks for measurements (tools/gpu_variants.py): the previous formulation of two kernels stays selectable so that a change can be
  * timed against it in one process, on the same data, with the same clocks.  Results are bit-identical either way (tests).
  *   viterbi_super: 1 (default) three trellis rounds per launch with the metrics exchanged through LDS / 0 one round per launch
+ *                  (tests/test_gpu_viterbi_edges.py runs every input of its fixture in both forms)
  *   sliding3:      1 (default) refinement with three bins of one channel per lane / 0 two bins of both channels (stereo) */
 void awm_debug_set_viterbi_super (int on);
 void awm_debug_set_viterbi_persistent (int on); /* K8: 1 ONE launch per batch of decodes (8 resident workgroups per decode meeting at a counter in global
