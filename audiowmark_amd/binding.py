@@ -129,6 +129,10 @@ lib.awm_debug_add_payloads_fused_in_use.restype = C.c_int
 lib.awm_debug_add_payloads_tile.argtypes = []
 lib.awm_debug_add_payloads_tile.restype = C.c_int
 lib.awm_add_watermark_batch_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
+lib.awm_add_watermark_segments_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int]
+lib.awm_debug_add_segments_fused_in_use.argtypes = []
+lib.awm_debug_add_segments_fused_in_use.restype = C.c_int
+lib.awm_debug_payload_tables_d.argtypes = [_vp, _vp, _vp, C.c_size_t, _vp]
 lib.awm_get_watermark_batch_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
 lib.awm_add_watermark_batch_keys_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
 lib.awm_get_watermark_batch_keys_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
@@ -138,6 +142,7 @@ lib.awm_tab_bit_pos.argtypes = [_vp, _vp]
 lib.awm_tab_mix_entries.argtypes = [_vp, _vp]
 lib.awm_tab_bit_order.argtypes = [_vp, C.c_size_t, _vp]
 lib.awm_tab_frame_mod.argtypes = [_vp, C.c_char_p, _vp]
+lib.awm_tab_frame_mod_template.argtypes = [_vp, _vp]
 lib.awm_tab_sync_bits.argtypes = [_vp, C.c_int, _vp]
 lib.awm_tab_window.argtypes = [C.c_size_t, _vp]
 lib.awm_tab_synth_window.argtypes = [_vp]
@@ -361,6 +366,24 @@ def tab_frame_mod(key, payload_hex):
     out = np.zeros((2, BLOCK_FRAMES, N_BANDS), np.int8)
     _check(lib.awm_tab_frame_mod(key_bytes(key), payload_hex.encode(), _np(out)), "awm_tab_frame_mod")
     return out
+
+
+def frame_mod_template(key, block_frames=None):
+    """awm_tab_frame_mod_template: what of tab_frame_mod depends on the key alone, int16 [2 (A, B)][block frames][81]: 0 KEEP, 1 UP, 2 DOWN,
+    or 4 + 2 k + s -- UP if bit k of conv_encode(block type, payload) xor s, else DOWN.  block_frames: 510 + 858 * frames_per_bit as in
+    force (default: BLOCK_FRAMES, two frames per bit)."""
+    entries = _check(lib.awm_tab_frame_mod_template(key_bytes(key), None), "awm_tab_frame_mod_template")     # (the size in force: nothing written)
+    if block_frames is not None and 2 * block_frames * N_BANDS != entries:
+        raise ValueError("frame_mod_template: block_frames does not match the parameters in force")
+    out = np.zeros((2, entries // (2 * N_BANDS), N_BANDS), np.int16)
+    n = _check(lib.awm_tab_frame_mod_template(key_bytes(key), _np(out)), "awm_tab_frame_mod_template")
+    assert n == out.size
+    return out
+
+
+def add_segments_fused_in_use():
+    """1 if the last add_watermark_segments took the fused path (one launch per stage for the batch)"""
+    return lib.awm_debug_add_segments_fused_in_use()
 
 
 def tab_sync_bits(key, clip_mode=False):
@@ -607,6 +630,44 @@ class Context:
         _check(lib.awm_add_watermark_batch_d(self._h, key_bytes(key), payload_hex.encode(), len(clips), src, dst, frames, ch),
                "awm_add_watermark_batch_d")
         return outs
+
+    def add_watermark_segments(self, key, payloads, segments, zero_frames, outs=None):
+        """awm_add_watermark_segments_d: a batch of stream segments (resident, 44.1 kHz, one channel count) with one key, segment i with
+        payloads[i] and starting zero_frames[i] samples into its stream; outs[i] == add_watermark_tiles(key, payloads[i], segments[i],
+        zero_frames=zero_frames[i]) bit for bit.  Segments may be one tensor many times (one programme, many subscribers)."""
+        import torch
+        payloads, segments, zero_frames = list(payloads), list(segments), list(zero_frames)
+        if not (len(payloads) == len(segments) == len(zero_frames)):
+            raise ValueError("add_watermark_segments: payloads, segments and zero_frames must have one length")
+        if not segments:
+            return []
+        shapes = [_pcm_shape(s) for s in segments]
+        ch = shapes[0][1]
+        if any(s[1] != ch for s in shapes):
+            raise ValueError("add_watermark_segments: the segments must have one channel count")
+        if outs is None:
+            outs = [torch.empty_like(s) for s in segments]
+        elif len(outs) != len(segments) or any(o.shape != s.shape or o.dtype != s.dtype or not o.is_contiguous() for o, s in zip(outs, segments)):
+            raise ValueError("add_watermark_segments: outs must match the segments")
+        n = len(segments)
+        hexes = (C.c_char_p * n)(*[p.encode() for p in payloads])
+        zf = (C.c_size_t * n)(*[int(z) for z in zero_frames])
+        src = (C.c_void_p * n)(*[_dev_ptr(s) for s in segments])
+        dst = (C.c_void_p * n)(*[_dev_ptr(o) for o in outs])
+        frames = (C.c_size_t * n)(*[s[0] for s in shapes])
+        _check(lib.awm_add_watermark_segments_d(self._h, key_bytes(key), n, hexes, zf, src, dst, frames, ch), "awm_add_watermark_segments_d")
+        return outs
+
+    def payload_tables(self, key, payloads, block_frames=None):
+        """K16p alone (awm_debug_payload_tables_d): the frame_mod tables of the payloads, built on the device; == tab_frame_mod per payload"""
+        payloads = list(payloads)
+        hexes = (C.c_char_p * len(payloads))(*[p.encode() for p in payloads])
+        in_force = 510 + 858 * self.get_params().frames_per_bit          # (mark_block_frame_count: the library writes that many rows)
+        if block_frames is not None and block_frames != in_force:
+            raise ValueError("payload_tables: block_frames does not match the context's parameters")
+        out = np.zeros((len(payloads), 2, in_force, N_BANDS), np.int8)
+        _check(lib.awm_debug_payload_tables_d(self._h, key_bytes(key), hexes, len(payloads), _np(out)), "awm_debug_payload_tables_d")
+        return out
 
     def add_watermark_payloads(self, key, payloads, pcm, outs=None, sample_rate=44100):
         """add_watermark of ONE resident input with many payloads and one key (awm_add_watermark_payloads_d): the input is read and

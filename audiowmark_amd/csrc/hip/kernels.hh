@@ -106,11 +106,22 @@ int        add_mix_multi_span_waves_per_simd();   // occupancy the span kernels 
 hipError_t launch_limiter (hipStream_t st, float *data, long long n_frames, int n_channels, long long first_sample,
                            const float *block_max, long long first_block, long long n_blocks,
                            int limiter_block, float ceiling, float2 *scale_tab = nullptr, size_t scale_tab_entries = 0);
-/* K3 for a batch of clips (1 or 2 channels, data 16 byte aligned), every clip a stream that starts at sample 0 with its own block maxima
- * and a ramp table of limiter_tab_entries (n_frames, 0, limiter_block) entries: two launches for the batch */
-struct LimiterClip { float *data; long long n_frames; const float *block_max; long long n_blocks; float2 *tab; long long n_tab; };
+/* K3 for a batch of clips (1 or 2 channels, data 16 byte aligned), every clip a stream of its own with its own block maxima and a ramp
+ * table of limiter_tab_entries (n_frames, first_sample, limiter_block) entries: two launches for the batch.  first_sample / first_block
+ * have launch_limiter's meaning (data[0] is sample first_sample of the clip's stream, block_max[0] the maximum of limiter block
+ * first_block); 0 / 0: a stream that starts at sample 0.  max_tab: the largest n_tab among the clips (0: what max_frames gives for
+ * first_sample 0). */
+struct LimiterClip
+{
+  float *data; long long n_frames; const float *block_max; long long n_blocks; float2 *tab; long long n_tab;
+  long long first_sample, first_block;       // (a brace list that ends before them leaves both 0)
+};
+/* gather / scatter of a batch of interleaved STEREO segments in one launch (float2 pieces: src, dst + zeros and the counts are whole
+ * frames from 16-byte aligned bases): dst[0 .. zeros) = 0, dst[zeros .. zeros + n_values) = src[0 .. n_values).  n_values 0: nothing. */
+struct SegmentCopy { const float *src; float *dst; long long n_values, zeros; };
+hipError_t launch_segment_copy (hipStream_t st, const SegmentCopy *copies_dev, int n_copies, long long max_values);
 hipError_t launch_limiter_batch (hipStream_t st, const LimiterClip *clips_dev, int n_clips, long long max_frames, int n_channels, int limiter_block,
-                                 float ceiling);
+                                 float ceiling, long long max_tab = 0);
 /* entries launch_limiter needs in scale_tab for this span (one (scale_start, scale_step) pair per limiter block) */
 size_t     limiter_tab_entries (long long n_frames, long long first_sample, int limiter_block);
 hipError_t launch_fill_u32 (hipStream_t st, unsigned int *p, unsigned int v, size_t n);
@@ -373,6 +384,24 @@ struct KeyTableArgs
 size_t key_table_scratch_bytes();
 size_t key_table_bytes();
 hipError_t launch_frame_mod_tables (hipStream_t st, const KeyTableArgs& a);
+
+/* K16p (keytab.hip): the frame_mod tables of MANY PAYLOADS with one key, expanded from the key's template (host/wmcommon.cc
+ * build_frame_mod_template: int16 per (block type, frame, band): 0 / 1 / 2 as they are, 4 + 2 k + s = UP if coded bit k of the block type
+ * xor s, else DOWN) in one launch: blockIdx.y = payload.  coded: n_payloads x [2 (A, B)][n_code] bytes 0 / 1; tables: n_payloads tables
+ * of table_stride bytes each in K2's format, [2 * half_entries] int8 + padding.  table_stride is a multiple of 16 >= 2 * half_entries,
+ * and the template holds table_stride entries (zeros behind the last one): every load and store is a whole 16-byte piece. */
+struct PayloadTableArgs
+{
+  const short         *tmpl;
+  const unsigned char *coded;
+  signed char         *tables;
+  long long            table_stride;
+  int                  half_entries;     // block_frames * 81: where the B block begins
+  int                  n_code;
+  int                  n_payloads;       // <= 65535
+};
+size_t     payload_table_stride (size_t block_frames);       // bytes between the tables of two payloads
+hipError_t launch_payload_tables (hipStream_t st, const PayloadTableArgs& a);
 
 /* K16g: the tables `get` needs for a clip with a key of its own (CLIP mode; reference syncfinder.cc:30-77 init_up_down, wmget.cc:52-108
  * mix_decode's entries, wmcommon.hh randomize_bit_order), from the same draws and shuffles as K16, one workgroup per key -- what the

@@ -1342,7 +1342,9 @@ limiter_apply_kernel (float4 *data, long long n_vec, long long first_sample, con
   limiter_apply_run<C> (data, n_vec, first_sample, tab, tab_first_block, BS);
 }
 
-/* K3 for a batch of clips, every clip a stream of its own that starts at sample 0: blockIdx.y = clip */
+/* K3 for a batch of clips, every clip a stream of its own: blockIdx.y = clip.  data[0] is sample first_sample of the clip's stream and
+ * block_max[0] belongs to limiter block first_block (launch_limiter's meaning; 0 / 0: the stream starts at sample 0); the ramp table
+ * begins at the block of first_sample. */
 __global__ void
 limiter_table_batch_kernel (const LimiterClip *clips, int BS, float ceiling)
 {
@@ -1350,12 +1352,14 @@ limiter_table_batch_kernel (const LimiterClip *clips, int BS, float ceiling)
   const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= c.n_tab)
     return;
+  const long long b = c.first_sample / BS + k;
   auto M = [&] (long long bb) -> float {
-    if (bb < 0 || bb >= c.n_blocks)
+    const long long j = bb - c.first_block;
+    if (bb < 0 || j < 0 || j >= c.n_blocks)
       return ceiling;
-    return fmaxf (c.block_max[bb], ceiling);
+    return fmaxf (c.block_max[j], ceiling);
   };
-  const float m_last = M (k - 1), m_cur = M (k), m_next = M (k + 1);
+  const float m_last = M (b - 1), m_cur = M (b), m_next = M (b + 1);
   const float scale_start = __fdiv_rn (ceiling, fmaxf (m_last, m_cur));
   const float scale_end   = __fdiv_rn (ceiling, fmaxf (m_cur, m_next));
   c.tab[k] = make_float2 (scale_start, __fdiv_rn (__fsub_rn (scale_end, scale_start), float (BS)));
@@ -1366,25 +1370,28 @@ limiter_apply_batch_kernel (const LimiterClip *clips, int BS)
 {
   const LimiterClip c = clips[blockIdx.y];
   const long long n_values = c.n_frames * C, n_vec = n_values / 4;
+  const long long tab_first = c.first_sample / BS;
   if ((long long) blockIdx.x * LIMITER_RUN < n_vec)
-    limiter_apply_run<C> (reinterpret_cast<float4 *> (c.data), n_vec, 0, c.tab, 0, BS);
+    limiter_apply_run<C> (reinterpret_cast<float4 *> (c.data), n_vec, c.first_sample, c.tab, tab_first, BS);
   // the values behind the last whole float4 (stereo: an odd number of frames), with the same table entries and arithmetic
   if (blockIdx.x == 0 && 4 * n_vec + threadIdx.x < n_values)
     {
-      const long long v = 4 * n_vec + threadIdx.x, f = v / C, b = f / BS;
-      const float2 t = c.tab[b];
+      const long long v = 4 * n_vec + threadIdx.x, f = c.first_sample + v / C, b = f / BS;
+      const float2 t = c.tab[b - tab_first];
       c.data[v] = __fmul_rn (c.data[v], __fadd_rn (t.x, __fmul_rn (float (int (f - b * BS)), t.y)));
     }
 }
 
 hipError_t
-launch_limiter_batch (hipStream_t st, const LimiterClip *clips_dev, int n_clips, long long max_frames, int n_channels, int limiter_block, float ceiling)
+launch_limiter_batch (hipStream_t st, const LimiterClip *clips_dev, int n_clips, long long max_frames, int n_channels, int limiter_block, float ceiling,
+                      long long max_tab)
 {
   if (n_clips <= 0 || max_frames <= 0)
     return hipSuccess;
   if ((n_channels != 1 && n_channels != 2) || limiter_block < 4 * LIMITER_RUN)
     return hipErrorInvalidValue;
-  const long long max_tab = limiter_tab_entries (max_frames, 0, limiter_block);
+  if (max_tab <= 0)
+    max_tab = limiter_tab_entries (max_frames, 0, limiter_block);
   hipLaunchKernelGGL (limiter_table_batch_kernel, dim3 (unsigned ((max_tab + 255) / 256), unsigned (n_clips)), dim3 (256), 0, st, clips_dev, limiter_block, ceiling);
   const long long max_vec = std::max<long long> (1, max_frames * n_channels / 4);
   const dim3 grid (unsigned ((max_vec + LIMITER_RUN - 1) / LIMITER_RUN), unsigned (n_clips));
@@ -3908,6 +3915,47 @@ launch_clip_pad (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, lo
   auto *r = reinterpret_cast<unsigned long long *> (range);
   hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
   hipLaunchKernelGGL (clip_pad_kernel, dim3 (128, unsigned (n_clips)), dim3 (256), 0, st, src, dst, slice_values, margin_values, r);
+  return hipGetLastError();
+}
+
+/* kernels.hh launch_segment_copy: grid (runs, segments).  A segment that starts r samples into its first frame is 8 r bytes off the
+ * 16-byte grid of its staged slice, so the pieces are float2 (a stereo frame): always aligned on both sides, a wave moves 512 bytes per
+ * instruction.  A workgroup owns a run of SEG_RUN pieces, loads first. */
+constexpr int SEG_RUN = 2048;
+__global__ void __launch_bounds__ (256)
+segment_copy_kernel (const SegmentCopy *copies)
+{
+  const SegmentCopy c = copies[blockIdx.y];
+  const long long n_zero = c.zeros / 2, n_total = n_zero + c.n_values / 2;
+  const long long base = (long long) blockIdx.x * SEG_RUN;
+  if (c.n_values <= 0 || base >= n_total)
+    return;
+  const float2 *src = reinterpret_cast<const float2 *> (c.src);
+  float2 *dst = reinterpret_cast<float2 *> (c.dst);
+  constexpr int U = SEG_RUN / 256;
+  float2 v[U];
+#pragma unroll
+  for (int j = 0; j < U; j++)
+    {
+      const long long q = base + threadIdx.x + 256 * j;
+      v[j] = q >= n_zero && q < n_total ? src[q - n_zero] : make_float2 (0.f, 0.f);
+    }
+#pragma unroll
+  for (int j = 0; j < U; j++)
+    {
+      const long long q = base + threadIdx.x + 256 * j;
+      if (q < n_total)
+        dst[q] = v[j];
+    }
+}
+
+hipError_t
+launch_segment_copy (hipStream_t st, const SegmentCopy *copies_dev, int n_copies, long long max_values)
+{
+  if (n_copies <= 0 || max_values <= 0)
+    return hipSuccess;
+  const long long max_pieces = (max_values + 1) / 2;
+  hipLaunchKernelGGL (segment_copy_kernel, dim3 (unsigned ((max_pieces + SEG_RUN - 1) / SEG_RUN), unsigned (n_copies)), dim3 (256), 0, st, copies_dev);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // keytab.hip -- K16: the frame_mod table of `add` built ON THE DEVICE, one workgroup per key; K16g: the same draws and shuffles turned
-// into the tables `get` needs for a clip with a key of its own (clip_key_tables_tail below).
+// into the tables `get` needs for a clip with a key of its own (clip_key_tables_tail below); K16p: the tables of many PAYLOADS with one
+// key, expanded from the key's template (payload_table_kernel, at the end of the file).
 //
 // Replaces, for batches with one key per clip (awm_add_watermark_batch_keys_d), the host's build_frame_mod_table
 // (host/wmcommon.cc; reference wmadd.cc:86-162 "init_frame_mod_vec", wmcommon.cc:143-202 UpDownGen / BitPosGen / gen_mix_entries,
@@ -576,6 +577,88 @@ launch_frame_mod_tables (hipStream_t st, const KeyTableArgs& a)
   if (!a.round_keys || !a.sbox || !a.coded || !a.scratch || !a.tables || a.scratch_slots <= 0 || a.n_keys > a.scratch_slots)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL (frame_mod_table_kernel, dim3 ((unsigned) a.n_keys), dim3 (KT_WG), 0, st, a);
+  return hipGetLastError();
+}
+
+/* ==========================================================================================
+ * K16p: the tables of many payloads with ONE key (kernels.hh PayloadTableArgs)
+ *
+ * For one key the tables of two payloads differ only in UP <-> DOWN of the data bands (reference wmadd.cc:86-162): no AES, no shuffle --
+ * the key's template names, per band, the coded bit that decides it.  A workgroup keeps its payload's 2 x n_code coded bits in LDS and
+ * converts PT_PIECES x 256 pieces of 16 adjacent entries: two 16-byte loads of the template (the same for every payload: it stays in L2
+ * across the launch), 16 byte lookups in LDS, one 16-byte store.  Memory-bound on the store of the tables, which is the point.
+ * ========================================================================================== */
+constexpr int PT_WG = 256, PT_PIECES = 4;
+
+__global__ void __launch_bounds__ (PT_WG)
+payload_table_kernel (PayloadTableArgs a)
+{
+  extern __shared__ __attribute__ ((aligned (16))) unsigned char s_coded[];        // [2][n_code]
+  const unsigned char *coded = a.coded + size_t (blockIdx.y) * 2 * a.n_code;
+  for (int i = threadIdx.x; i < 2 * a.n_code; i += PT_WG)
+    s_coded[i] = coded[i] & 1;
+  __syncthreads();
+
+  const long long n_pieces = a.table_stride / 16;
+  const uint4 *tmpl = reinterpret_cast<const uint4 *> (a.tmpl);
+  uint4 *table = reinterpret_cast<uint4 *> (a.tables + size_t (blockIdx.y) * a.table_stride);
+  const long long piece0 = (long long) blockIdx.x * (PT_WG * PT_PIECES) + threadIdx.x;
+  uint4 lo[PT_PIECES], hi[PT_PIECES];
+#pragma unroll
+  for (int j = 0; j < PT_PIECES; j++)                      // all loads first
+    {
+      const long long q = piece0 + j * PT_WG;
+      lo[j] = hi[j] = make_uint4 (0, 0, 0, 0);
+      if (q < n_pieces)
+        {
+          lo[j] = tmpl[2 * q];
+          hi[j] = tmpl[2 * q + 1];
+        }
+    }
+#pragma unroll
+  for (int j = 0; j < PT_PIECES; j++)
+    {
+      const long long q = piece0 + j * PT_WG;
+      if (q >= n_pieces)
+        continue;
+      const long long e0 = q * 16;
+      const unsigned int w[8] = { lo[j].x, lo[j].y, lo[j].z, lo[j].w, hi[j].x, hi[j].y, hi[j].z, hi[j].w };
+      unsigned int o[4] = { 0, 0, 0, 0 };
+#pragma unroll
+      for (int i = 0; i < 16; i++)
+        {
+          const unsigned int v = (w[i >> 1] >> (16 * (i & 1))) & 0xffff;
+          unsigned int r = v;                              // KEEP 0 / UP 1 / DOWN 2 as they are
+          if (v >= 4)
+            {
+              const unsigned int k = (v - 4) >> 1, s = (v - 4) & 1;
+              const int ab = e0 + i >= a.half_entries;
+              r = k < (unsigned int) a.n_code ? 2 - (s_coded[ab * a.n_code + k] ^ s) : 0;     // bit ^ s: UP 1, else DOWN 2
+            }
+          o[i >> 2] |= (r & 0xff) << (8 * (i & 3));
+        }
+      table[q] = make_uint4 (o[0], o[1], o[2], o[3]);
+    }
+}
+
+size_t
+payload_table_stride (size_t block_frames)
+{
+  return (2 * block_frames * KT_NB + 15) / 16 * 16;
+}
+
+hipError_t
+launch_payload_tables (hipStream_t st, const PayloadTableArgs& a)
+{
+  if (a.n_payloads <= 0)
+    return hipSuccess;
+  if (!a.tmpl || !a.coded || !a.tables || a.n_payloads > 65535 || a.n_code <= 0 || a.half_entries <= 0 || (a.table_stride & 15)
+      || a.table_stride < 2LL * a.half_entries || (reinterpret_cast<uintptr_t> (a.tmpl) & 15) || (reinterpret_cast<uintptr_t> (a.tables) & 15))
+    return hipErrorInvalidValue;
+  const long long n_pieces = a.table_stride / 16;
+  const unsigned grid_x = unsigned ((n_pieces + PT_WG * PT_PIECES - 1) / (PT_WG * PT_PIECES));
+  const size_t lds = (size_t (2) * a.n_code + 15) / 16 * 16;
+  hipLaunchKernelGGL (payload_table_kernel, dim3 (grid_x, unsigned (a.n_payloads)), dim3 (PT_WG), lds, st, a);
   return hipGetLastError();
 }
 

@@ -1682,6 +1682,400 @@ awm_add_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], const char *payl
   return rc;
 }
 
+/* ---- a batch of stream SEGMENTS, each with its own offset and payload (include/awm_hip.h; reference hls.cc:244-279: a few seconds of
+ * audio with context on either side, watermarked on request for one subscriber by add_stream_watermark (key, in, out, bits, zero_frames)).
+ * The machine is the batched clip path above -- one launch per stage, blockIdx.y = segment --, with three things per segment: the table
+ * of its payload (K16p expands the key's template for all distinct payloads of a group in one launch: no table is built on the host), its
+ * place in the frame / watermark block grid (first_frame) and in the limiter's (first_sample, first_block).  A segment that begins
+ * r = zero_frames % 1024 samples into a frame is staged: "r zeros, then the segment" in an aligned slice of a workspace (one gather
+ * launch per batch), K2 and the limiter work there, one scatter launch brings the result home without the r samples.  The scatter is a
+ * launch of its own and not the limiter's apply pass writing to the caller's buffer: that pass moves float4 and the caller's buffer is
+ * 8 r bytes off the staged slice's 16-byte grid. ---- */
+static int g_add_segments_fused_in_use = 0;
+extern "C" int awm_debug_add_segments_fused_in_use (void) { return g_add_segments_fused_in_use; }
+
+/* one segment through the tile stream (what every segment of a call that cannot take the fused path goes through) */
+static int
+add_segment_stream (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, size_t zero_frames, const float *pcm_in_d, float *out_d,
+                    size_t n_frames, int C)
+{
+  constexpr size_t TILE1024 = 128;
+  awm_add_stream *s = nullptr;
+  if (int rc = add_stream_create (ctx, key, &payload_hex, 1, C, TILE1024, zero_frames, &s))
+    return rc;
+  struct Guard { awm_add_stream *s; ~Guard() { awm_add_stream_destroy (s); } } guard { s };      // (waits for the stream: the copies below are through)
+  const size_t tile = TILE1024 * Params::frame_size;
+  size_t pos = 0, written = 0;
+  for (;;)
+    {
+      const size_t got = std::min (tile, n_frames - pos);
+      const bool last = pos + got >= n_frames;
+      if (got)
+        AWM_HIP_CHECK (hipMemcpyAsync (awm_add_stream_input (s), pcm_in_d + pos * C, got * C * sizeof (float), hipMemcpyDeviceToDevice, ctx->stream));
+      const float *done[3];
+      size_t done_frames[3];
+      const int k = add_stream_push (s, got, last, done, done_frames, "awm_add_watermark_segments_d");
+      if (k < 0)
+        return k;
+      for (int i = 0; i < k; i++)
+        {
+          AWM_HIP_CHECK (hipMemcpyAsync (out_d + written * C, done[i], done_frames[i] * C * sizeof (float), hipMemcpyDeviceToDevice, ctx->stream));
+          written += done_frames[i];
+        }
+      pos += got;
+      if (last)
+        break;
+    }
+  return 0;
+}
+
+/* the fused path: segs = the segments with samples, ordered by payload; payload_of[i] = index of segment i's payload among the distinct
+ * ones; coded = their codes, [distinct][2 (A, B)][n_code] bytes */
+static int
+add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_t>& segs, const std::vector<size_t>& payload_of,
+                    const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames, const float *const *pcm_in_d,
+                    float *const *out_d, const size_t *n_frames)
+{
+  constexpr size_t PER_LAUNCH = 4096;                      // (blockIdx.y <= 65535; a launch of 4096 clips fills the device many times over)
+  constexpr size_t TABLE_GROUP = 1024;                     // distinct payloads whose tables exist at a time (~370 MB at the default geometry)
+  constexpr size_t STAGE_MAX_FLOATS = size_t (1) << 28;    // staged samples per batch and direction (1 GiB): a batch that would need more is split
+  const size_t FRAME = Params::frame_size, n = segs.size(), n_distinct = coded.size() / (2 * n_code);
+  const int use_limiter = !params().test_no_limiter;
+  const size_t block_frames = mark_block_frame_count();
+  const size_t table_stride = awmk::payload_table_stride (block_frames);
+  hipStream_t st = ctx->stream;
+
+  FrameModTemplate *tmpl = ctx->get_frame_mod_template (capi_key (key));
+  if (!tmpl)
+    return AWM_ERR_HIP;
+
+  // geometry of every segment and the batches: consecutive segments (in payload order) of one table group, at most PER_LAUNCH of them
+  struct Seg { size_t r, skipped, len, first_block, n_blocks, n_tab, max_off, tab_off, stage_off; };
+  struct Batch { size_t i0, i1, g0, g1, stage_floats, max_len, max_tab; };
+  std::vector<Seg> geo (n);
+  std::vector<Batch> batches;
+  size_t max_total = 0, tab_total = 0, stage_max = 0, n_staged = 0;
+  long long total_frames1024 = 0;
+  for (size_t i = 0; i < n; i++)
+    {
+      const size_t zf = zero_frames[segs[i]];
+      Seg& g = geo[i];
+      g.r = zf % FRAME;
+      g.skipped = zf - g.r;
+      g.len = g.r + n_frames[segs[i]];                     // the stream behind the whole frames of zeros: r zeros, then the segment
+      g.first_block = g.skipped / LIMITER_BLOCK;
+      g.n_blocks = (g.skipped + g.len) / LIMITER_BLOCK + 2 - g.first_block;
+      g.n_tab = awmk::limiter_tab_entries ((long long) g.len, (long long) g.skipped, LIMITER_BLOCK);
+      g.max_off = max_total;
+      g.tab_off = tab_total;
+      max_total += g.n_blocks;
+      tab_total += g.n_tab + 1;
+      total_frames1024 += (long long) ((g.len + FRAME - 1) / FRAME);
+      const size_t stage_floats = g.r ? (g.len * 2 + 3) / 4 * 4 : 0;
+      if (batches.empty() || i - batches.back().i0 >= PER_LAUNCH || payload_of[i] / TABLE_GROUP != payload_of[batches.back().i0] / TABLE_GROUP
+          || (batches.back().stage_floats && batches.back().stage_floats + stage_floats > STAGE_MAX_FLOATS))
+        batches.push_back ({ i, i, n_staged, n_staged, 0, 0, 0 });
+      Batch& b = batches.back();
+      g.stage_off = b.stage_floats;
+      b.stage_floats += stage_floats;
+      b.i1 = i + 1;
+      b.max_len = std::max (b.max_len, g.len);
+      b.max_tab = std::max (b.max_tab, g.n_tab);
+      if (g.r)
+        b.g1 = ++n_staged;
+      stage_max = std::max (stage_max, b.stage_floats);
+    }
+  const int L = frames_per_span (ctx, total_frames1024);
+
+  // one page-locked block, one upload: the segments' kernel arguments, the gather / scatter lists of the staged ones, the payloads' codes
+  const size_t off_lim = n * sizeof (awmk::AddMixArgs), off_gather = off_lim + n * sizeof (awmk::LimiterClip),
+               off_scatter = off_gather + n_staged * sizeof (awmk::SegmentCopy), off_coded = off_scatter + n_staged * sizeof (awmk::SegmentCopy),
+               arg_bytes = off_coded + coded.size();
+  if (int rc = ctx->ws_add_batch.reserve (arg_bytes)) return rc;
+  if (int rc = ctx->ws_keytab.reserve (std::min (n_distinct, TABLE_GROUP) * table_stride)) return rc;
+  if (use_limiter)
+    {
+      if (int rc = ctx->ws_block_max.reserve (max_total * sizeof (float))) return rc;
+      if (int rc = ctx->ws_limit_tab.reserve (tab_total * sizeof (float2))) return rc;
+    }
+  if (stage_max)
+    {
+      if (int rc = ctx->ws_seg_in.reserve (stage_max * sizeof (float))) return rc;
+      if (int rc = ctx->ws_seg_out.reserve (stage_max * sizeof (float))) return rc;
+    }
+  if (ctx->ev_add_batch)
+    AWM_HIP_CHECK (hipEventSynchronize (ctx->ev_add_batch));            // (an earlier batch's staging has been copied)
+  else
+    AWM_HIP_CHECK (hipEventCreateWithFlags (&ctx->ev_add_batch, hipEventDisableTiming));
+  if (int rc = ctx->pin_add_batch.reserve (arg_bytes)) return rc;
+  char *h = ctx->pin_add_batch.as<char>(), *d = ctx->ws_add_batch.as<char>();
+  auto *h_mix = reinterpret_cast<awmk::AddMixArgs *> (h);
+  auto *h_lim = reinterpret_cast<awmk::LimiterClip *> (h + off_lim);
+  auto *h_gather = reinterpret_cast<awmk::SegmentCopy *> (h + off_gather), *h_scatter = reinterpret_cast<awmk::SegmentCopy *> (h + off_scatter);
+  const auto *d_mix = reinterpret_cast<const awmk::AddMixArgs *> (d);
+  const auto *d_lim = reinterpret_cast<const awmk::LimiterClip *> (d + off_lim);
+  const auto *d_gather = reinterpret_cast<const awmk::SegmentCopy *> (d + off_gather), *d_scatter = reinterpret_cast<const awmk::SegmentCopy *> (d + off_scatter);
+  const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
+  std::memcpy (h + off_coded, coded.data(), coded.size());
+  float *block_max = ctx->ws_block_max.as<float>();
+  float2 *tabs = ctx->ws_limit_tab.as<float2>();
+  std::vector<long long> spans (n);
+  size_t staged = 0;
+  for (size_t i = 0; i < n; i++)
+    {
+      const Seg& g = geo[i];
+      const size_t s = segs[i];
+      const float *in = g.r ? ctx->ws_seg_in.as<float>() + g.stage_off : pcm_in_d[s];
+      float *out = g.r ? ctx->ws_seg_out.as<float>() + g.stage_off : out_d[s];
+      awmk::AddMixArgs a {};
+      a.pcm_in = in;
+      a.out = out;
+      a.n_frames = (long long) g.len;
+      a.n_channels = 2;
+      a.frame_mod = ctx->ws_keytab.as<int8_t>() + (payload_of[i] % TABLE_GROUP) * table_stride;
+      a.neg_delta_up = float (-params().water_delta * 1);
+      a.neg_delta_down = float (-params().water_delta * -1);
+      a.first_frame = (long long) (g.skipped / FRAME);
+      a.block_max = use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr;
+      a.first_block = (long long) g.first_block;
+      a.n_blocks = (long long) g.n_blocks;
+      a.limiter_block = LIMITER_BLOCK;
+      a.block_frames = int (block_frames);
+      a.frames_pad_start = int (Params::frames_pad_start);
+      a.frames_per_span = L;
+      h_mix[i] = a;
+      h_lim[i] = { out, (long long) g.len, block_max + g.max_off, (long long) g.n_blocks, tabs + g.tab_off, (long long) g.n_tab,
+                   (long long) g.skipped, (long long) g.first_block };
+      spans[i] = ((long long) ((g.len + FRAME - 1) / FRAME) + L - 1) / L;
+      if (g.r)
+        {
+          h_gather[staged] = { pcm_in_d[s], ctx->ws_seg_in.as<float>() + g.stage_off, (long long) (n_frames[s] * 2), (long long) (g.r * 2) };
+          h_scatter[staged] = { out + g.r * 2, out_d[s], (long long) (n_frames[s] * 2), 0 };
+          staged++;
+        }
+    }
+  AWM_HIP_CHECK (hipMemcpyAsync (d, h, arg_bytes, hipMemcpyHostToDevice, st));
+  AWM_HIP_CHECK (hipEventRecord (ctx->ev_add_batch, st));
+
+  size_t group_built = size_t (-1);
+  for (const Batch& b : batches)
+    {
+      const size_t group = payload_of[b.i0] / TABLE_GROUP, nb = b.i1 - b.i0;
+      if (group != group_built)
+        {
+          awmk::PayloadTableArgs pa {};
+          pa.tmpl = tmpl->dev.as<short>();
+          pa.coded = d_coded + group * TABLE_GROUP * 2 * n_code;
+          pa.tables = ctx->ws_keytab.as<signed char>();
+          pa.table_stride = (long long) table_stride;
+          pa.half_entries = int (block_frames * Params::n_bands);
+          pa.n_code = int (n_code);
+          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
+          ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (pa.n_payloads) * table_stride, st);          // the tables out, once
+          AWM_HIP_CHECK (awmk::launch_payload_tables (st, pa));
+          group_built = group;
+        }
+      long long max_spans = 0;
+      double values = 0;
+      for (size_t i = b.i0; i < b.i1; i++)
+        {
+          max_spans = std::max (max_spans, spans[i]);
+          values += double (geo[i].len) * 2;
+        }
+      if (b.g1 > b.g0)
+        AWM_HIP_CHECK (awmk::launch_segment_copy (st, d_gather + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
+      if (use_limiter)
+        {
+          unsigned int bits;
+          std::memcpy (&bits, &LIMITER_CEILING, sizeof (bits));
+          const size_t m0 = geo[b.i0].max_off, m1 = geo[b.i1 - 1].max_off + geo[b.i1 - 1].n_blocks;
+          AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (block_max + m0), bits, m1 - m0));
+        }
+      {
+        ProfScope ps (ctx, PROF_ADD_MIX, values * 8.0, st);                          // read + write every sample once
+        AWM_HIP_CHECK (awmk::launch_add_mix_batch (st, ctx->tabs, d_mix + b.i0, int (nb), max_spans, int (block_frames), int (Params::frames_pad_start)));
+      }
+      if (use_limiter)
+        {
+          ProfScope ps (ctx, PROF_LIMITER, values * 8.0, st);
+          AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_lim + b.i0, int (nb), (long long) b.max_len, 2, LIMITER_BLOCK, LIMITER_CEILING, (long long) b.max_tab));
+        }
+      if (b.g1 > b.g0)
+        AWM_HIP_CHECK (awmk::launch_segment_copy (st, d_scatter + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
+    }
+  return 0;
+}
+
+int
+awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                              const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels)
+{
+  AWM_ENTER (ctx);
+  g_add_segments_fused_in_use = 0;
+  if (!n_segments)
+    return 0;
+  if (!key || !payload_hex || !zero_frames || !pcm_in_d || !out_d || !n_frames || n_channels < 1)
+    {
+      set_error ("awm_add_watermark_segments_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  if (ctx->snr_on)
+    {
+      set_error ("awm_add_watermark_segments_d: not available while the SNR meter is armed (awm_ctx_snr_begin)");
+      return AWM_ERR_ARG;
+    }
+  // everything is checked before anything is enqueued
+  const size_t C = size_t (n_channels);
+  for (size_t i = 0; i < n_segments; i++)
+    if (!payload_hex[i] || (n_frames[i] && (!pcm_in_d[i] || !out_d[i])))
+      {
+        set_error (string_printf ("awm_add_watermark_segments_d: null pointer at index %zu", i));
+        return AWM_ERR_ARG;
+      }
+  // the distinct payloads in order of appearance: parse_payload + code_encode (A and B) is all the host does per payload
+  const size_t n_code = code_size (ConvBlockType::a, params().payload_size);
+  std::map<std::string, size_t> distinct;
+  std::vector<size_t> payload_index (n_segments);
+  std::vector<unsigned char> coded;
+  for (size_t i = 0; i < n_segments; i++)
+    {
+      auto it = distinct.find (payload_hex[i]);
+      if (it == distinct.end())
+        {
+          const std::vector<int> bits = parse_payload (payload_hex[i]);
+          if (bits.empty())
+            {
+              set_error (string_printf ("awm_add_watermark_segments_d: cannot parse payload '%s' at index %zu", payload_hex[i], i));
+              return AWM_ERR_ARG;
+            }
+          if (!n_frames[i])                                // (a segment without samples: its payload is checked, no table is made for it)
+            continue;
+          for (int ab = 0; ab < 2; ab++)
+            {
+              const std::vector<int> code = code_encode (ab ? ConvBlockType::b : ConvBlockType::a, bits);
+              if (code.size() != n_code)
+                {
+                  set_error ("conv code of unexpected size");
+                  return AWM_ERR_GENERIC;
+                }
+              for (int c : code)
+                coded.push_back ((unsigned char) (c & 1));
+            }
+          it = distinct.emplace (payload_hex[i], distinct.size()).first;
+        }
+      payload_index[i] = it->second;
+    }
+  // Inputs may alias each other (the same segment for many subscribers), an output may overlap nothing: one sweep over the buffers by
+  // address, with the furthest end of any buffer and of any output seen so far
+  {
+    struct Range { uintptr_t a, b; size_t seg; bool out; };
+    std::vector<Range> ranges;
+    for (size_t i = 0; i < n_segments; i++)
+      if (n_frames[i])
+        {
+          const uintptr_t bytes = n_frames[i] * C * sizeof (float);
+          ranges.push_back ({ reinterpret_cast<uintptr_t> (pcm_in_d[i]), reinterpret_cast<uintptr_t> (pcm_in_d[i]) + bytes, i, false });
+          ranges.push_back ({ reinterpret_cast<uintptr_t> (out_d[i]), reinterpret_cast<uintptr_t> (out_d[i]) + bytes, i, true });
+        }
+    std::sort (ranges.begin(), ranges.end(), [] (const Range& x, const Range& y) { return x.a < y.a; });
+    uintptr_t end_any = 0, end_out = 0;
+    size_t seg_any = 0, seg_out = 0;
+    for (const Range& r : ranges)
+      {
+        if (r.out ? r.a < end_any : r.a < end_out)
+          {
+            set_error (string_printf ("awm_add_watermark_segments_d: the output of segment %zu overlaps a buffer of segment %zu",
+                                      r.out ? r.seg : seg_out, r.out ? seg_any : r.seg));
+            return AWM_ERR_ARG;
+          }
+        if (r.b > end_any) { end_any = r.b; seg_any = r.seg; }
+        if (r.out && r.b > end_out) { end_out = r.b; seg_out = r.seg; }
+      }
+  }
+  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2;
+  for (size_t i = 0; i < n_segments && fused; i++)
+    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) & 15) || (reinterpret_cast<uintptr_t> (out_d[i]) & 15)))
+      fused = false;
+  if (!fused)
+    {
+      for (size_t i = 0; i < n_segments; i++)
+        if (n_frames[i])
+          if (int rc = add_segment_stream (ctx, key, payload_hex[i], zero_frames[i], pcm_in_d[i], out_d[i], n_frames[i], n_channels))
+            return rc;
+      return 0;
+    }
+  // the segments with samples, by payload: the segments of a group of payloads are neighbours
+  std::vector<size_t> segs;
+  for (size_t i = 0; i < n_segments; i++)
+    if (n_frames[i])
+      segs.push_back (i);
+  std::stable_sort (segs.begin(), segs.end(), [&] (size_t x, size_t y) { return payload_index[x] < payload_index[y]; });
+  std::vector<size_t> payload_of (segs.size());
+  for (size_t i = 0; i < segs.size(); i++)
+    payload_of[i] = payload_index[segs[i]];
+  g_add_segments_fused_in_use = 1;
+  if (segs.empty())
+    return 0;
+  return add_segments_fused (ctx, key, segs, payload_of, coded, n_code, zero_frames, pcm_in_d, out_d, n_frames);
+}
+
+/* K16p alone (measurements, tests): the tables of n_payloads payloads with one key built on the device and copied to the host,
+ * n_payloads x [2][block frames][81] bytes -- they must equal awm_tab_frame_mod payload by payload.  tables_out may be NULL: the launch
+ * alone, on the context's stream (for timing) */
+int
+awm_debug_payload_tables_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int8_t *tables_out)
+{
+  AWM_ENTER (ctx);
+  if (!key || !payload_hex || !n_payloads || n_payloads > 1024)
+    {
+      set_error ("awm_debug_payload_tables_d: bad argument (1 .. 1024 payloads)");
+      return AWM_ERR_ARG;
+    }
+  const size_t n_code = code_size (ConvBlockType::a, params().payload_size), block_frames = mark_block_frame_count();
+  const size_t table_stride = awmk::payload_table_stride (block_frames), table_bytes = 2 * block_frames * Params::n_bands;
+  std::vector<unsigned char> coded;
+  for (size_t p = 0; p < n_payloads; p++)
+    {
+      const std::vector<int> bits = parse_payload (payload_hex[p] ? payload_hex[p] : "");
+      if (bits.empty())
+        {
+          set_error (string_printf ("awm_debug_payload_tables_d: cannot parse the payload at index %zu", p));
+          return AWM_ERR_ARG;
+        }
+      for (int ab = 0; ab < 2; ab++)
+        for (int c : code_encode (ab ? ConvBlockType::b : ConvBlockType::a, bits))
+          coded.push_back ((unsigned char) (c & 1));
+    }
+  if (coded.size() != n_payloads * 2 * n_code)
+    {
+      set_error ("conv code of unexpected size");
+      return AWM_ERR_GENERIC;
+    }
+  FrameModTemplate *tmpl = ctx->get_frame_mod_template (capi_key (key));
+  if (!tmpl)
+    return AWM_ERR_HIP;
+  if (int rc = ctx->ws_keytab.reserve (n_payloads * table_stride)) return rc;
+  if (int rc = upload_sync (ctx->ws_keytab_aux, coded.data(), coded.size(), ctx->stream)) return rc;
+  awmk::PayloadTableArgs pa {};
+  pa.tmpl = tmpl->dev.as<short>();
+  pa.coded = ctx->ws_keytab_aux.as<unsigned char>();
+  pa.tables = ctx->ws_keytab.as<signed char>();
+  pa.table_stride = (long long) table_stride;
+  pa.half_entries = int (block_frames * Params::n_bands);
+  pa.n_code = int (n_code);
+  pa.n_payloads = int (n_payloads);
+  {
+    ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (n_payloads) * table_stride);
+    AWM_HIP_CHECK (awmk::launch_payload_tables (ctx->stream, pa));
+  }
+  if (tables_out)
+    {
+      AWM_HIP_CHECK (hipMemcpy2DAsync (tables_out, table_bytes, ctx->ws_keytab.ptr, table_stride, table_bytes, n_payloads, hipMemcpyDeviceToHost, ctx->stream));
+      AWM_HIP_CHECK (stream_wait (ctx->stream));
+    }
+  return 0;
+}
+
 /* the same with ONE KEY PER CLIP (BASELINE configs[4]: `--test-key k` per clip).  The frame_mod tables (361 KB per key; 2226 up / down
  * draws and three shuffles per key on the host: ~3 ms of one core) are built on host threads group by group while the device works on
  * the previous group, and live in one batch buffer instead of the context's per-key cache. */

@@ -92,6 +92,21 @@ awm_tab_frame_mod (const uint8_t key[16], const char *payload_hex, int8_t *out)
 }
 
 int
+awm_tab_frame_mod_template (const uint8_t key[16], int16_t *out)
+{
+  if (!key)
+    {
+      set_error ("awm_tab_frame_mod_template: bad argument");
+      return AWM_ERR_ARG;
+    }
+  if (!out)                                                // (the size alone: 2 * mark_block_frame_count() * n_bands entries)
+    return int (2 * mark_block_frame_count() * Params::n_bands);
+  const auto table = build_frame_mod_template (key_from_bytes (key));
+  std::memcpy (out, table.data(), table.size() * sizeof (int16_t));
+  return int (table.size());
+}
+
+int
 awm_tab_sync_bits (const uint8_t key[16], int clip_mode, int *out)
 {
   const auto t = build_sync_table (key_from_bytes (key), clip_mode != 0);

@@ -526,6 +526,39 @@ awm_ctx::get_frame_mod (const Key& key, const std::string& payload_hex)
   return frame_mod_tables.back().get();
 }
 
+FrameModTemplate *
+awm_ctx::get_frame_mod_template (const Key& key)
+{
+  std::lock_guard<std::mutex> lock (table_mutex);
+  std::vector<unsigned char> kb (key.aes_key(), key.aes_key() + Key::SIZE);
+  for (auto& t : frame_mod_templates)
+    if (t->key == kb && t->mix == params().mix && t->frames_per_bit == params().frames_per_bit)
+      {
+        t->last_use = ++table_clock;
+        return t.get();
+      }
+  auto table = build_frame_mod_template (key);
+  table.resize (awmk::payload_table_stride (mark_block_frame_count()), 0);      // K16p reads whole 16-entry pieces
+  auto t = std::make_unique<FrameModTemplate>();
+  t->key = kb;
+  t->mix = params().mix;
+  t->frames_per_bit = params().frames_per_bit;
+  t->last_use = ++table_clock;
+  if (upload (t->dev, table.data(), table.size() * sizeof (int16_t), stream))
+    return nullptr;
+  if (frame_mod_templates.size() >= MAX_CACHED_TABLES)
+    {
+      // as in get_frame_mod: a queued kernel may still read the victim
+      auto victim = std::min_element (frame_mod_templates.begin(), frame_mod_templates.end(),
+                                      [] (const auto& a, const auto& b) { return a->last_use < b->last_use; });
+      (void) hipDeviceSynchronize();
+      (*victim)->dev.release();
+      frame_mod_templates.erase (victim);
+    }
+  frame_mod_templates.push_back (std::move (t));
+  return frame_mod_templates.back().get();
+}
+
 void
 awm_ctx::prof_collect()
 {
@@ -546,7 +579,7 @@ static const char *prof_names[awm::PROF_COUNT] = {
   "sync_db_kernel(refine)", "sync_scan_kernel(refine)", "sync_db_kernel(block)", "soft_bits_kernel", "viterbi_kernel",
   "stft_full_kernel",
   "resample_kernel", "resample_var_kernel", "speed_mags_kernel", "speed_compare_kernel", "frame_mod_table_kernel",
-  "add_mix_multi_kernel"
+  "add_mix_multi_kernel", "payload_table_kernel"
 };
 
 extern "C" {
@@ -779,6 +812,8 @@ awm_ctx_trim (awm_ctx *ctx)
   awm::speed_workspace_free (ctx);
   ctx->ws_add_batch.release();
   ctx->pin_add_batch.release();
+  ctx->ws_seg_in.release();
+  ctx->ws_seg_out.release();
   ctx->ws_merge_soft.release();
   ctx->ws_rate_a.release();
   ctx->ws_rate_b.release();
@@ -800,10 +835,14 @@ awm_ctx_destroy (awm_ctx *ctx)
     release_key_tables (*kt);
   for (auto& t : ctx->frame_mod_tables)
     t->dev.release();
+  for (auto& t : ctx->frame_mod_templates)
+    t->dev.release();
   for (auto& t : ctx->resample_tables)
     t->ctab.release();
   awm::speed_workspace_free (ctx);
   ctx->ws_snr.release();
+  ctx->ws_seg_in.release();
+  ctx->ws_seg_out.release();
   ctx->ws_add_batch.release();
   ctx->pin_add_batch.release();
   if (ctx->ev_add_batch)

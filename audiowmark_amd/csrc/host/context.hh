@@ -204,13 +204,23 @@ struct FrameModTable
   DevBuffer   dev;                 // [2 * block frames][81] int8 (2226 frames with two frames per bit)
 };
 
+// what of the frame_mod tables depends on the key alone (wmcommon.hh build_frame_mod_template), for K16p: the tables of many payloads
+struct FrameModTemplate
+{
+  std::vector<unsigned char> key;
+  bool        mix = true;
+  int         frames_per_bit = 2;
+  unsigned long last_use = 0;
+  DevBuffer   dev;                 // int16, awmk::payload_table_stride (block frames) entries (zeros behind the last one)
+};
+
 } // namespace awm
 
 namespace awm {
 // per-kernel timing with HIP events on the context's stream (awm_prof_* in awm_hip.h)
 enum ProfId { PROF_ADD_MIX, PROF_LIMITER, PROF_SYNC_DB, PROF_SYNC_SCAN, PROF_LOCAL_MEAN, PROF_REFINE_DB, PROF_REFINE_SCAN,
               PROF_BLOCK_DB, PROF_SOFT_BITS, PROF_VITERBI, PROF_STFT,
-              PROF_RESAMPLE, PROF_RESAMPLE_VAR, PROF_SPEED_MAGS, PROF_SPEED_COMPARE, PROF_KEYTAB, PROF_ADD_MIX_MULTI, PROF_COUNT };
+              PROF_RESAMPLE, PROF_RESAMPLE_VAR, PROF_SPEED_MAGS, PROF_SPEED_COMPARE, PROF_KEYTAB, PROF_ADD_MIX_MULTI, PROF_PAYLOAD_TAB, PROF_COUNT };
 struct ProfPending { int id; hipEvent_t start, stop; };
 }
 
@@ -249,6 +259,7 @@ struct awm_ctx : awm::WorkLane
 
   std::vector<std::unique_ptr<awm::KeyTables>>     key_tables;
   std::vector<std::unique_ptr<awm::FrameModTable>> frame_mod_tables;
+  std::vector<std::unique_ptr<awm::FrameModTemplate>> frame_mod_templates;
   std::vector<std::unique_ptr<awm::ResampleTable>> resample_tables;
   awm::ResampleTable *get_resample_table (int rate_in, int rate_out);      // nullptr: ratio not supported by the fixed-ratio resampler
   awm::DevBuffer ws_rate_a, ws_rate_b, ws_rate_c;                          // resampled input / watermark signals of the other-rate add path
@@ -265,6 +276,7 @@ struct awm_ctx : awm::WorkLane
   awm::DevBuffer    ws_add_batch;        // batches of clips in one launch per stage (capi_kernels.cc add_clips_batched): the clips' kernel arguments,
   awm::PinnedBuffer pin_add_batch;       // their page-locked staging,
   hipEvent_t        ev_add_batch = nullptr;   // and "the staging has been copied" (the next batch may overwrite it)
+  awm::DevBuffer ws_seg_in, ws_seg_out;  // awm_add_watermark_segments_d: the staged slices ("r zeros, then the segment") of segments that begin inside a frame, and their results
   awm::DevBuffer ws_snr;                 // `add --snr`: { power of the watermark signal, power of the input } accumulated by every mix while snr_on
   bool           snr_on = false;
   int            chunk_lanes = awm::CHUNK_LANES;   // lanes the chunks of one stream may be spread over (awm_ctx_set_chunk_lanes)
@@ -286,6 +298,7 @@ struct awm_ctx : awm::WorkLane
 
   awm::KeyTables     *get_key_tables (const awm::Key& key);
   awm::FrameModTable *get_frame_mod (const awm::Key& key, const std::string& payload_hex);
+  awm::FrameModTemplate *get_frame_mod_template (const awm::Key& key);
 };
 
 #include "../../../include/awm_hip.h"

@@ -214,6 +214,77 @@ build_frame_mod_table (const Key& key, const std::vector<int>& payload_bits)
   return table;
 }
 
+std::vector<int16_t>
+build_frame_mod_template (const Key& key)
+{
+  enum : int16_t { KEEP = 0, UP = 1, DOWN = 2 };
+  const size_t n_block = mark_block_frame_count();
+  const int NB = Params::n_bands;
+  std::vector<int16_t> table (2 * n_block * NB, KEEP);
+
+  // build_frame_mod_table's walk, write for write: a sync band gets its value, a data band the name of the coded bit that decides it
+  BitPosGen bit_pos_gen (key);
+  auto set_bands = [&] (int16_t *row, int up_band, int down_band, int bit) {
+    row[up_band - Params::min_band]   = bit ? UP : DOWN;
+    row[down_band - Params::min_band] = bit ? DOWN : UP;
+  };
+  auto name_bands = [&] (int16_t *row, int up_band, int down_band, unsigned k) {
+    row[up_band - Params::min_band]   = int16_t (FRAME_MOD_TEMPLATE_DATA + 2 * k);
+    row[down_band - Params::min_band] = int16_t (FRAME_MOD_TEMPLATE_DATA + 2 * k + 1);
+  };
+  const int n_sync = int (mark_sync_frame_count()), n_data = mark_data_frame_count();
+  std::vector<UpDownArray> sync_up (n_sync), sync_down (n_sync);
+  {
+    UpDownGen sync_gen (key, Random::Stream::sync_up_down);
+    for (int f = 0; f < n_sync; f++)
+      sync_gen.get (f, sync_up[f], sync_down[f]);
+  }
+  std::vector<MixEntry> entries;
+  std::vector<UpDownArray> data_up, data_down;
+  if (params().mix)
+    entries = gen_mix_entries (key);
+  else
+    {
+      data_up.resize (n_data);
+      data_down.resize (n_data);
+      UpDownGen data_gen (key, Random::Stream::data_up_down);
+      for (int f = 0; f < n_data; f++)
+        data_gen.get (f, data_up[f], data_down[f]);
+    }
+  // fec[j] = code[order[j]] (apply_bit_order, encode)
+  const std::vector<unsigned> order = bit_order (key, code_size (ConvBlockType::a, params().payload_size));
+  for (int ab = 0; ab < 2; ab++)
+    {
+      int16_t *block = &table[ab * n_block * NB];
+      for (int f = 0; f < n_sync; f++)
+        {
+          const int bit = (f / Params::sync_frames_per_bit + ab) & 1;
+          int16_t *row = block + size_t (bit_pos_gen.sync_frame (f)) * NB;
+          for (size_t i = 0; i < sync_up[f].size(); i++)
+            set_bands (row, sync_up[f][i], sync_down[f][i], bit);
+        }
+      if (params().mix)
+        {
+          for (int f = 0; f < n_data; f++)
+            for (size_t j = 0; j < Params::bands_per_frame; j++)
+              {
+                const MixEntry& e = entries[f * Params::bands_per_frame + j];
+                name_bands (block + size_t (e.frame) * NB, e.up, e.down, order[f / params().frames_per_bit]);
+              }
+        }
+      else
+        {
+          for (int f = 0; f < n_data; f++)
+            {
+              int16_t *row = block + size_t (bit_pos_gen.data_frame (f)) * NB;
+              for (size_t i = 0; i < data_up[f].size(); i++)
+                name_bands (row, data_up[f][i], data_down[f][i], order[f / params().frames_per_bit]);
+            }
+        }
+    }
+  return table;
+}
+
 SyncTable
 build_sync_table (const Key& key, bool clip_mode)
 {

@@ -145,6 +145,13 @@ std::vector<float> gen_synth_window();                          // reference wma
 // (reference wmadd.cc:86-162 init_frame_mod_vec / mark_sync / mark_data)
 std::vector<int8_t> build_frame_mod_table (const Key& key, const std::vector<int>& payload_bits);
 
+// what of that table depends on the key alone: [2 (A,B)][mark_block_frame_count()][81] with 0 KEEP, 1 UP, 2 DOWN (the sync frames of the
+// block type) and 4 + 2 k + s for a data band governed by bit k of code_encode (block_type, bits) -- k BEFORE apply_bit_order, the bit
+// order is folded in; s = 0: UP when the bit is 1, DOWN otherwise; s = 1: the opposite.  The same walk as build_frame_mod_table (same
+// order of writes, last writer wins), so expanding it with a payload's code gives that payload's table byte for byte (K16p, hip/keytab.hip)
+constexpr int16_t FRAME_MOD_TEMPLATE_DATA = 4;
+std::vector<int16_t> build_frame_mod_template (const Key& key);
+
 // sync table (reference syncfinder.cc:30-77): for bit 0..5, rows sorted by frame:
 // frame (int32) and 30 up + 30 down band indices (band - 20, ascending).
 struct SyncTable

@@ -89,6 +89,12 @@ int awm_tab_mix_entries (const uint8_t key[16], int *frame_up_down /* [51480*3] 
 int awm_tab_bit_order (const uint8_t key[16], size_t n, unsigned *order);
 /* out[2][2226][81]: 0 KEEP / 1 UP / 2 DOWN for the A and the B block */
 int awm_tab_frame_mod (const uint8_t key[16], const char *payload_hex, int8_t *out);
+/* what of that table depends on the key alone, out[2][block frames][81] int16: 0 KEEP / 1 UP / 2 DOWN (the sync frames of the block
+ * type) or 4 + 2 k + s, a data band governed by bit k of conv_encode (block type, payload) -- k BEFORE the bit order, which is folded in;
+ * s = 0: UP when the bit is 1, DOWN otherwise; s = 1 the opposite.  The walk of wmadd.cc:86-162, write for write: expanded with a
+ * payload's A and B code it is awm_tab_frame_mod of that payload byte for byte (mix and frames_per_bit as in force).  Returns the
+ * number of entries; with out == NULL that number alone (nothing is written), so that a caller can size the buffer. */
+int awm_tab_frame_mod_template (const uint8_t key[16], int16_t *out);
 /* out rows: frame, up[30], down[30] (band-20, ascending); returns rows per bit (85 / 170) */
 int awm_tab_sync_bits (const uint8_t key[16], int clip_mode, int *out /* [6*rows*61] */);
 int awm_tab_window (size_t n, float *out);                    /* FFTAnalyzer::gen_normalized_window wmcommon.cc:68-89 */
@@ -241,6 +247,30 @@ typedef struct
  * watermark rate (44100 Hz) with n_channels channels; out_d[i] holds n_frames[i] * n_channels floats. */
 int awm_add_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, size_t n_clips, const float *const *pcm_in_d,
                                float *const *out_d, const size_t *n_frames, int n_channels);
+
+/* A batch of stream SEGMENTS with one key, each with its own offset and payload: what the reference's HLS mode does per request
+ * (hls.cc:244-279: a few seconds of audio with up to 3 x 1024 samples of context on either side, watermarked for one subscriber by
+ * add_stream_watermark (key, in, out, bits, start_pos - prev_size), hls.cc:279).  For every i, out_d[i] receives n_frames[i] * n_channels
+ * floats: bit for bit the concatenated output of an awm_add_stream_create_at (ctx, key, payload_hex[i], n_channels, ..., zero_frames[i])
+ * stream fed that segment.  44100 Hz only, as for the other batch entry points; the context's parameters apply as for awm_add_watermark_d
+ * (water_delta, mix, frames_per_bit, test_no_limiter).  Inputs may alias each other (the same segment for many subscribers).
+ * AWM_ERR_ARG with nothing enqueued: a NULL pointer (pcm_in_d[i] / out_d[i] may be NULL where n_frames[i] is 0), an output that overlaps
+ * an input or another output, a payload that does not parse (awm_last_error names its index), a call while the SNR meter is armed.
+ * n_segments == 0 returns 0; a segment with n_frames == 0 writes nothing.
+ * Stereo, 16-byte aligned pointers and n_segments >= 2 take the fused path: the batched clip machine (one launch per stage, blockIdx.y =
+ * segment; the number of launches does not depend on n_segments up to the 4096 segments a launch takes) with, per segment, its place in
+ * the frame and limiter grids (first_frame = zero_frames / 1024, limiter phase and block from zero_frames) and the table of its payload.
+ * No table is built on the host: K16p (hip/keytab.hip) expands the key's template (awm_tab_frame_mod_template, cached per context) with
+ * the payloads' codes, one launch per group of at most 1024 DISTINCT payloads; equal payload strings share a table; the host contributes
+ * parse_payload + conv_encode per distinct payload.  A segment with r = zero_frames % 1024 != 0 begins r samples into its first frame:
+ * such segments are staged -- one gather launch per batch writes "r zeros, then the segment" into aligned slices of a workspace, K2 and
+ * the limiter work there, one scatter launch brings the results home without the r samples (a batch stages at most 1 GiB per direction,
+ * more is split); segments with r = 0 are read from and written to the caller's buffers directly.  Everything else (other channel
+ * counts, a misaligned pointer, a single segment, awm_debug_set_add_batched (0)) goes segment by segment through the tile stream, with
+ * the same results.  Not offered in this form: the command line, the awm_multi_* / sharded forms, a key per segment. */
+int awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
+                                  const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
+                                  int n_channels);
 
 /* The batch entry points with ONE KEY PER CLIP (keys = n_clips * 16 bytes; BASELINE configs[4]: `--test-key k` for clip k).  The key
  * tables -- frame_mod for `add`; CLIP sync tables, mix table and bit order for `get` (wmcommon.cc:143-202, wmadd.cc:86-162,
@@ -543,6 +573,11 @@ void awm_debug_set_add_batched (int on);   /* add of a batch of stereo clips: 2 
 void awm_debug_set_add_slab_mb (int mb);   /* add: 0 (default) one fused add over the stream, then the limiter | > 0: in slabs of that many MB (cache experiment) */
 void awm_debug_set_add_payloads_fused (int on);   /* awm_add_watermark_payloads_d, awm_add_mix_payloads_d: 1 (default) the fused kernel | 0 a loop over the single-payload path */
 int  awm_debug_add_payloads_fused_in_use (void);  /* 1 if the last awm_add_watermark_payloads_d / awm_add_mix_payloads_d (also inside a stream push) ran the fused kernel */
+int  awm_debug_add_segments_fused_in_use (void);  /* 1 if the last awm_add_watermark_segments_d took the fused path (one launch per stage), 0: segment by segment */
+int  awm_debug_payload_tables_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int8_t *tables_out);
+                                             /* K16p alone: the frame_mod tables of 1 .. 1024 payloads with one key, expanded on the device from the key's template,
+                                              * n_payloads x 2 x block frames x 81 bytes to host memory (they equal awm_tab_frame_mod payload by payload);
+                                              * tables_out NULL: the launch alone, on the context's stream (timing) */
 void awm_debug_set_payloads_file_tile (int frames1024);   /* awm_add_watermark_payloads_file: tile of the fused path in 1024-sample frames (>= 128) | 0 (default) automatic */
 int  awm_debug_add_payloads_tile (void);          /* outputs per pass of the fused kernel over the input (ADD_MULTI_TILE) */
 void awm_debug_set_fft_pair (int on);      /* stereo add: both channels' transforms pipelined in one wave (default) | one after the other */
