@@ -63,7 +63,7 @@ int        add_mix_waves_per_simd();     // occupancy the stereo kernel is built
  * A wave fetches, windows and transforms a frame once and computes both band factors (UP and DOWN) once; band selection, inverse
  * transform, overlap-add, mix, stores and block maxima then run once per output.  This form: whole streams (frame 0 is sample 0, no halos; spans: AddMixSpan below);
  * every channel count takes it (stereo through the paired transforms, anything else one channel per wave like K2).  out[p] is bit for bit
- * what launch_add_mix writes with frame_mod[p]: the same device functions and expressions in the same order. */
+ * what launch_add_mix writes with frame_mod[p]: both kernels call the same device functions for every step after the band edit. */
 constexpr int ADD_MULTI_TILE = 4;        // outputs per launch (their overlap-add carry lives in registers: DESIGN.md section 9)
 struct AddMixOut
 {

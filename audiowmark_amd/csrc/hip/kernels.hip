@@ -187,10 +187,14 @@ zdpos (int k)
   return (kc < 2 ? kc : kc - 4) * 64 + ((k >> 3) & 7) + 8 * (k & 7);
 }
 
-// one frame-channel: windowed samples -> delta signal d (time domain, unnormalised c2r like FFTW)
+/* The pieces of a frame's way through the fused add, each written once: K2 (add_mix_body) and K2m (add_mix_multi_body, below) are both
+ * built from them, so K2m's outputs are K2's bit for bit by construction.  Device code is built with -ffp-contract=on: only equal
+ * expressions give equal bits, and the __fmul_rn / __fadd_rn calls and every wave_sync* below are where the reference's order and the
+ * exchange tile need them. */
+
+// forward half of a frame-channel: transform, then the rows with the watermark bands and their mirrors into the exchange tile
 __device__ __forceinline__ void
-frame_delta (float2 (&z)[8], const int8_t *mod_row, float nd_up, float nd_down,
-             float2 *xbuf, float2 *zd, const float2 *s_tw, const float2 *s_tw3, const float2 *s_twb, int lane)
+frame_forward (float2 (&z)[8], float2 *xbuf, const float2 *s_tw, int lane)
 {
   fft512_forward (z, xbuf, s_tw, lane);
   xbuf[0 * 64 + lane] = z[0];
@@ -198,6 +202,109 @@ frame_delta (float2 (&z)[8], const int8_t *mod_row, float nd_up, float nd_down,
   xbuf[6 * 64 + lane] = z[6];
   xbuf[7 * 64 + lane] = z[7];
   wave_sync();
+}
+
+// both channels of a stereo frame, the two transforms pipelined over the wave's one exchange tile (fft512_forward2): a in rows 0, 1, 6, 7
+// of the tile (zpos), b in the rows between (zposb)
+__device__ __forceinline__ void
+frame_forward2 (float2 (&za)[8], float2 (&zb)[8], float2 *xbuf, const float2 *s_tw, int lane)
+{
+  fft512_forward2 (za, zb, xbuf, s_tw, lane);
+  lds_st (&xbuf[0 * 64 + lane], za[0]);
+  lds_st (&xbuf[1 * 64 + lane], za[1]);
+  lds_st (&xbuf[6 * 64 + lane], za[6]);
+  lds_st (&xbuf[7 * 64 + lane], za[7]);
+  lds_st (&xbuf[2 * 64 + lane], zb[0]);
+  lds_st (&xbuf[3 * 64 + lane], zb[1]);
+  lds_st (&xbuf[4 * 64 + lane], zb[6]);
+  lds_st (&xbuf[5 * 64 + lane], zb[7]);
+  wave_sync_pinned();
+}
+
+__device__ __forceinline__ int
+zposb (int k)
+{
+  const int p = zpos (k);
+  return p < 128 ? p + 128 : p - 128;
+}
+
+/* band k of a frame-channel into the half-length spectrum of the c2r transform (zd): Zd[k] = D + i D conj(W^k), Zd[512-k] = conj(D) +
+ * i conj(D conj(W^k)); every other bin stays 0.  D: the edit of band k (0 where the row leaves the band alone), O = D conj (W^k) */
+template<bool PINNED = false> __device__ __forceinline__ void
+halfspec_store (float2 *zd, int k, float2 D, float2 O)
+{
+  const float2 lo = make_float2 (D.x - O.y, D.y + O.x), hi = make_float2 (D.x + O.y, O.x - D.y);
+  if constexpr (PINNED)
+    {
+      lds_st (&zd[zdpos (k)], lo);
+      lds_st (&zd[zdpos (512 - k)], hi);
+    }
+  else
+    {
+      zd[zdpos (k)] = lo;
+      zd[zdpos (512 - k)] = hi;
+    }
+}
+
+// inverse half of a frame-channel, once every lane has stored its bands: z = the delta signal d (time domain, unnormalised c2r like FFTW)
+__device__ __forceinline__ void
+frame_inverse (float2 (&z)[8], float2 *xbuf, float2 *zd, const float2 *s_tw, const float2 *s_tw3, int lane)
+{
+  wave_sync();
+  const float2 zero = make_float2 (0.f, 0.f);
+  z[0] = zd[0 * 64 + lane];
+  z[1] = zd[1 * 64 + lane];
+  z[2] = zero; z[3] = zero; z[4] = zero; z[5] = zero;
+  z[6] = zd[2 * 64 + lane];
+  z[7] = zd[3 * 64 + lane];
+  wave_sync();
+  fft512_inverse (z, xbuf, s_tw, s_tw3, lane);
+}
+
+// the same for both channels of a stereo frame, stores included: one after the other through the wave's zd, then the paired inverse transform
+__device__ __forceinline__ void
+frame_inverse2 (float2 (&za)[8], float2 (&zb)[8], const float2 (&Da)[2], const float2 (&Oa)[2], const float2 (&Db)[2], const float2 (&Ob)[2],
+                float2 *xbuf, float2 *zd, const float2 *s_tw, const float2 *s_tw3, int lane)
+{
+  const float2 zero = make_float2 (0.f, 0.f);
+  wave_sync_pinned();
+#pragma unroll
+  for (int pass = 0; pass < 2; pass++)
+    {
+      const int k = MIN_BAND + lane + 64 * pass;
+      if (k <= 100)
+        halfspec_store<true> (zd, k, Da[pass], Oa[pass]);
+    }
+  wave_sync_pinned();
+  za[0] = lds_ld (&zd[0 * 64 + lane]);
+  za[1] = lds_ld (&zd[1 * 64 + lane]);
+  za[2] = zero; za[3] = zero; za[4] = zero; za[5] = zero;
+  za[6] = lds_ld (&zd[2 * 64 + lane]);
+  za[7] = lds_ld (&zd[3 * 64 + lane]);
+  wave_sync_pinned();
+#pragma unroll
+  for (int pass = 0; pass < 2; pass++)
+    {
+      const int k = MIN_BAND + lane + 64 * pass;
+      if (k <= 100)
+        halfspec_store<true> (zd, k, Db[pass], Ob[pass]);
+    }
+  wave_sync_pinned();
+  zb[0] = lds_ld (&zd[0 * 64 + lane]);
+  zb[1] = lds_ld (&zd[1 * 64 + lane]);
+  zb[2] = zero; zb[3] = zero; zb[4] = zero; zb[5] = zero;
+  zb[6] = lds_ld (&zd[2 * 64 + lane]);
+  zb[7] = lds_ld (&zd[3 * 64 + lane]);
+  wave_sync_pinned();
+  fft512_inverse2 (za, zb, xbuf, s_tw, s_tw3, lane);
+}
+
+// one frame-channel of K2: windowed samples -> delta signal d.  Forward half, the band edit with the row's one exponent, inverse half
+__device__ __forceinline__ void
+frame_delta (float2 (&z)[8], const int8_t *mod_row, float nd_up, float nd_down,
+             float2 *xbuf, float2 *zd, const float2 *s_tw, const float2 *s_tw3, const float2 *s_twb, int lane)
+{
+  frame_forward (z, xbuf, s_tw, lane);
 #pragma unroll
   for (int pass = 0; pass < 2; pass++)
     {
@@ -222,41 +329,18 @@ frame_delta (float2 (&z)[8], const int8_t *mod_row, float nd_up, float nd_down,
                   D = make_float2 (X.x * s, X.y * s);
                 }
             }
-          // half-length spectrum of the c2r transform: Zd[k] = D + i D conj(W^k), Zd[512-k] = conj(D) + i conj(D conj(W^k))
-          const float2 O = cmulc (D, w);
-          zd[zdpos (k)]       = make_float2 (D.x - O.y, D.y + O.x);
-          zd[zdpos (512 - k)] = make_float2 (D.x + O.y, O.x - D.y);
+          halfspec_store (zd, k, D, cmulc (D, w));
         }
     }
-  wave_sync();
-  const float2 zero = make_float2 (0.f, 0.f);
-  z[0] = zd[0 * 64 + lane];
-  z[1] = zd[1 * 64 + lane];
-  z[2] = zero; z[3] = zero; z[4] = zero; z[5] = zero;
-  z[6] = zd[2 * 64 + lane];
-  z[7] = zd[3 * 64 + lane];
-  wave_sync();
-  fft512_inverse (z, xbuf, s_tw, s_tw3, lane);
+  frame_inverse (z, xbuf, zd, s_tw, s_tw3, lane);
 }
 
-// both channels of a stereo frame: the two transforms pipelined over the wave's one exchange tile (fft512_forward2 / fft512_inverse2);
-// the frame_mod row is the same for both, the band edit of a bin runs for both at once
+// both channels of a stereo frame of K2: the frame_mod row is the same for both, the band edit of a bin runs for both at once
 __device__ __forceinline__ void
 frame_delta2 (float2 (&za)[8], float2 (&zb)[8], const int8_t *mod_row, float nd_up, float nd_down,
               float2 *xbuf, float2 *zd, const float2 *s_tw, const float2 *s_tw3, const float2 *s_twb, int lane)
 {
-  fft512_forward2 (za, zb, xbuf, s_tw, lane);
-  // rows with the bands and their mirrors: a in rows 0, 1, 6, 7 of the tile (zpos), b in the rows between (zpos + 128 / - 128)
-  lds_st (&xbuf[0 * 64 + lane], za[0]);
-  lds_st (&xbuf[1 * 64 + lane], za[1]);
-  lds_st (&xbuf[6 * 64 + lane], za[6]);
-  lds_st (&xbuf[7 * 64 + lane], za[7]);
-  lds_st (&xbuf[2 * 64 + lane], zb[0]);
-  lds_st (&xbuf[3 * 64 + lane], zb[1]);
-  lds_st (&xbuf[4 * 64 + lane], zb[6]);
-  lds_st (&xbuf[5 * 64 + lane], zb[7]);
-  wave_sync_pinned();
-  auto zposb = [] (int k) { const int p = zpos (k); return p < 128 ? p + 128 : p - 128; };
+  frame_forward2 (za, zb, xbuf, s_tw, lane);
   float2 Da[2], Db[2], Oa[2], Ob[2];
 #pragma unroll
   for (int pass = 0; pass < 2; pass++)
@@ -289,43 +373,7 @@ frame_delta2 (float2 (&za)[8], float2 (&zb)[8], const int8_t *mod_row, float nd_
           Ob[pass] = cmulc (Db[pass], w);
         }
     }
-  wave_sync_pinned();
-  const float2 zero = make_float2 (0.f, 0.f);
-#pragma unroll
-  for (int pass = 0; pass < 2; pass++)
-    {
-      const int k = MIN_BAND + lane + 64 * pass;
-      if (k <= 100)
-        {
-          lds_st (&zd[zdpos (k)],       make_float2 (Da[pass].x - Oa[pass].y, Da[pass].y + Oa[pass].x));
-          lds_st (&zd[zdpos (512 - k)], make_float2 (Da[pass].x + Oa[pass].y, Oa[pass].x - Da[pass].y));
-        }
-    }
-  wave_sync_pinned();
-  za[0] = lds_ld (&zd[0 * 64 + lane]);
-  za[1] = lds_ld (&zd[1 * 64 + lane]);
-  za[2] = zero; za[3] = zero; za[4] = zero; za[5] = zero;
-  za[6] = lds_ld (&zd[2 * 64 + lane]);
-  za[7] = lds_ld (&zd[3 * 64 + lane]);
-  wave_sync_pinned();
-#pragma unroll
-  for (int pass = 0; pass < 2; pass++)
-    {
-      const int k = MIN_BAND + lane + 64 * pass;
-      if (k <= 100)
-        {
-          lds_st (&zd[zdpos (k)],       make_float2 (Db[pass].x - Ob[pass].y, Db[pass].y + Ob[pass].x));
-          lds_st (&zd[zdpos (512 - k)], make_float2 (Db[pass].x + Ob[pass].y, Ob[pass].x - Db[pass].y));
-        }
-    }
-  wave_sync_pinned();
-  zb[0] = lds_ld (&zd[0 * 64 + lane]);
-  zb[1] = lds_ld (&zd[1 * 64 + lane]);
-  zb[2] = zero; zb[3] = zero; zb[4] = zero; zb[5] = zero;
-  zb[6] = lds_ld (&zd[2 * 64 + lane]);
-  zb[7] = lds_ld (&zd[3 * 64 + lane]);
-  wave_sync_pinned();
-  fft512_inverse2 (za, zb, xbuf, s_tw, s_tw3, lane);
+  frame_inverse2 (za, zb, Da, Oa, Db, Ob, xbuf, zd, s_tw, s_tw3, lane);
 }
 
 __device__ __forceinline__ float
@@ -337,392 +385,69 @@ wave_max (float v)
   return v;
 }
 
-template<int CV, bool OPAQUE, bool PAIR = false> __device__ __forceinline__ void
-add_mix_body (const DevTables& t, const AddMixArgs& a, long long frame_number0, int block_frames)
-{
-  __shared__ float2 s_tw[512];
-  __shared__ float2 s_tw3[512];                            // twiddles of the inverse transform's last stage (awm_fft.hip.h)
-  __shared__ float  s_win[1024];
-  __shared__ float2 s_twb[NB];
-  __shared__ float2 s_x[WAVES][XBUF_ELEMS];
-  __shared__ float2 s_zd[WAVES][256];
-  // the wave index is wave-uniform: in a scalar register, the frame loop's counters, bounds tests and base addresses run on the
-  // scalar unit (the compiler cannot see that threadIdx.x >> 6 is the same for all lanes)
-  const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane (threadIdx.x >> 6);
-  int lane = lane0;
-  load_shared_tables (t, s_tw, s_win, s_twb);
-  fft512_load_twiddles_inverse (t.tw512, s_tw3);
-  for (int i = lane; i < 256; i += 64)
-    s_zd[wave][i] = make_float2 (0.f, 0.f);
-  __syncthreads();
-
-  const int C = a.n_channels;
-  const int n_cg = CV == 2 ? 1 : C;
-  const long long F = (a.n_frames + 1023) / 1024;
-  const int L = a.frames_per_span;
-  const long long n_spans = (F + L - 1) / L;
-  const long long item = (long long) blockIdx.x * WAVES + wave;
-  if (item >= n_spans * n_cg)
-    return;
-  const long long span = item / n_cg;
-  const int ch0 = int (item % n_cg);
-  const long long s = span * L, e = (s + L < F) ? s + L : F;
-  float2 *xbuf = s_x[wave], *zd = s_zd[wave];
-
-  // synthesis window pieces this lane needs (reference wmadd.cc:177-206): head = samples 2 lane, 2 lane + 1
-  // of a frame (slots W1, W2); tail = samples 896 + 2 lane (+1) (slots W1, W0).  In between W1 == 1, W0 == W2 == 0.
-  const float2 w1_head = reinterpret_cast<const float2 *> (t.synth + 1024)[lane];
-  const float2 w2_head = reinterpret_cast<const float2 *> (t.synth + 2048)[lane];
-  const float2 w1_tail = reinterpret_cast<const float2 *> (t.synth + 1024 + 896)[lane];
-  const float2 w0_tail = reinterpret_cast<const float2 *> (t.synth + 896)[lane];
-
-  float head2[CV][2], tail_s1[CV][2], tail_in[CV][2];
-#pragma unroll
-  for (int c = 0; c < CV; c++)
-    head2[c][0] = head2[c][1] = tail_s1[c][0] = tail_s1[c][1] = tail_in[c][0] = tail_in[c][1] = 0.f;
-
-  const int BS = a.limiter_block;
-  const long long total_rows = 2LL * block_frames;
-
-  // where frame m comes from (halo before / the span / halo after) and how much of it exists
-  auto frame_source = [&] (long long m, int& avail) -> const float * {
-    const float *src;
-    if (m < 0)
-      {
-        src = a.halo_before;
-        avail = src ? 1024 : 0;
-      }
-    else if (m >= F)
-      {
-        src = a.halo_after;
-        avail = src ? 1024 : 0;
-      }
-    else
-      {
-        src = a.pcm_in + m * 1024 * C;
-        const long long left = a.n_frames - m * 1024;
-        avail = left < 1024 ? int (left) : 1024;
-      }
-    return src;
-  };
-  for (long long m = s - 1; m <= e; m++)
-    {
-      if (OPAQUE)
-        {
-          // make the lane index opaque per frame: the ~60 lane-dependent twiddle factors are then re-read from LDS
-          // for every transform instead of being hoisted into registers for the whole span (occupancy over reuse)
-          lane = lane0;
-          asm volatile ("" : "+v" (lane));
-        }
-      int avail;
-      const float *src = frame_source (m, avail);
-      float in[CV][16];
-      float2 d[CV][8];
-      if (avail > 0)
-        {
-          if constexpr (CV == 2)
-            fetch_stereo (src, 0, avail, lane, in[0], in[1]);
-          else
-            fetch_channel (src, 0, avail, C, ch0, lane, in[0]);
-          const long long g = a.first_frame + m;                       // frame index in the whole stream
-          const long long row = (frame_number0 + g) % total_rows;      // reference wmadd.cc:326-344
-          const int8_t *mod_row = a.frame_mod + row * NB;
-          if constexpr (CV == 2 && PAIR)
-            {
-              window_pack (in[0], s_win, lane, d[0]);
-              window_pack (in[1], s_win, lane, d[1]);
-              frame_delta2 (d[0], d[1], mod_row, a.neg_delta_up, a.neg_delta_down, xbuf, zd, s_tw, s_tw3, s_twb, lane);
-            }
-          else
-            {
-#pragma unroll
-              for (int c = 0; c < CV; c++)
-                {
-                  window_pack (in[c], s_win, lane, d[c]);
-                  frame_delta (d[c], mod_row, a.neg_delta_up, a.neg_delta_down, xbuf, zd, s_tw, s_tw3, s_twb, lane);
-                }
-            }
-        }
-      else
-        {
-#pragma unroll
-          for (int c = 0; c < CV; c++)
-            {
-#pragma unroll
-              for (int j = 0; j < 16; j++)
-                in[c][j] = 0.f;
-#pragma unroll
-              for (int j = 0; j < 8; j++)
-                d[c][j] = make_float2 (0.f, 0.f);
-            }
-        }
-
-      if (a.delta_only)
-        {
-          // WatermarkGen::run alone: the mix below then adds 0 instead of the input
-#pragma unroll
-          for (int c = 0; c < CV; c++)
-#pragma unroll
-            for (int j = 0; j < 16; j++)
-              in[c][j] = 0.f;
-        }
-      const bool own = m >= s && m < e;
-      const bool own_prev = m - 1 >= s && m - 1 < e;
-      float max0 = 0.f, max1 = 0.f, pmax0 = 0.f, pmax1 = 0.f;
-      // limiter blocks touched by frame m / m - 1: offset inside the frame where the next block begins
-      const long long gs_m = (a.first_frame + m) * 1024;
-      const long long b0 = gs_m >= 0 ? gs_m / BS : 0;
-      const long long bound = (b0 + 1) * BS - gs_m;
-      const long long gs_p = gs_m - 1024;
-      const long long pb0 = gs_p >= 0 ? gs_p / BS : 0;
-      const long long pbound = (pb0 + 1) * BS - gs_p;
-
-      // output frame m = d[m-1] W2 + d[m] W1 + d[m+1] W0 + in[m]   (reference wmadd.cc:228-238, 564-565)
-      float o[CV][16];
-#pragma unroll
-      for (int c = 0; c < CV; c++)
-        {
-          // j = 0: head region, W1/W2 ramps
-          const float s1x = __fadd_rn (head2[c][0], __fmul_rn (d[c][0].x, w1_head.x));
-          const float s1y = __fadd_rn (head2[c][1], __fmul_rn (d[c][0].y, w1_head.y));
-          o[c][0] = __fadd_rn (s1x, in[c][0]);
-          o[c][1] = __fadd_rn (s1y, in[c][1]);
-          head2[c][0] = __fmul_rn (d[c][0].x, w2_head.x);
-          head2[c][1] = __fmul_rn (d[c][0].y, w2_head.y);
-#pragma unroll
-          for (int j = 1; j < 7; j++)
-            {
-              o[c][2 * j]     = __fadd_rn (d[c][j].x, in[c][2 * j]);
-              o[c][2 * j + 1] = __fadd_rn (d[c][j].y, in[c][2 * j + 1]);
-            }
-          // j = 7 of the PREVIOUS frame gets its W0 contribution now
-          o[c][14] = __fadd_rn (__fadd_rn (tail_s1[c][0], __fmul_rn (d[c][7].x, w0_tail.x)), tail_in[c][0]);
-          o[c][15] = __fadd_rn (__fadd_rn (tail_s1[c][1], __fmul_rn (d[c][7].y, w0_tail.y)), tail_in[c][1]);
-          tail_s1[c][0] = __fmul_rn (d[c][7].x, w1_tail.x);
-          tail_s1[c][1] = __fmul_rn (d[c][7].y, w1_tail.y);
-          tail_in[c][0] = in[c][14];
-          tail_in[c][1] = in[c][15];
-        }
-
-      // stores (bounded by the span's sample count) + maxima.  Common case (all but the last frame of the stream, and 42 of 43
-      // frames have no limiter block boundary inside): plain stores and ONE running maximum, no per-value bounds tests.
-      const bool whole_m = (m + 1) * 1024 <= a.n_frames;
-      if (own && whole_m && bound >= 1024)
-        {
-          const long long base = m * 1024;
-#pragma unroll
-          for (int j = 0; j < 7; j++)
-            {
-              const long long ls = base + 2 * (lane + 64 * j);
-              if (CV == 2)
-                *reinterpret_cast<float4 *> (a.out + ls * 2) = make_float4 (o[0][2 * j], o[CV - 1][2 * j], o[0][2 * j + 1], o[CV - 1][2 * j + 1]);
-              else
-                {
-                  float *p = a.out + ls * C + ch0;
-                  p[0] = o[0][2 * j];
-                  p[C] = o[0][2 * j + 1];
-                }
-#pragma unroll
-              for (int c = 0; c < CV; c++)
-                max0 = fmaxf (max0, fmaxf (fabsf (o[c][2 * j]), fabsf (o[c][2 * j + 1])));
-            }
-        }
-      else if (own)
-        {
-          const long long base = m * 1024;
-#pragma unroll
-          for (int j = 0; j < 7; j++)
-            {
-              const int x = 2 * (lane + 64 * j);
-              const long long ls = base + x;
-              if (CV == 2)
-                {
-                  float *p = a.out + ls * 2;
-                  if (ls + 1 < a.n_frames)
-                    *reinterpret_cast<float4 *> (p) = make_float4 (o[0][2 * j], o[CV - 1][2 * j], o[0][2 * j + 1], o[CV - 1][2 * j + 1]);
-                  else if (ls < a.n_frames)
-                    *reinterpret_cast<float2 *> (p) = make_float2 (o[0][2 * j], o[CV - 1][2 * j]);
-                }
-              else
-                {
-                  float *p = a.out + ls * C + ch0;
-                  if (ls < a.n_frames)
-                    p[0] = o[0][2 * j];
-                  if (ls + 1 < a.n_frames)
-                    p[C] = o[0][2 * j + 1];
-                }
-#pragma unroll
-              for (int c = 0; c < CV; c++)
-                {
-                  const float v0 = ls < a.n_frames ? fabsf (o[c][2 * j]) : 0.f;
-                  const float v1 = ls + 1 < a.n_frames ? fabsf (o[c][2 * j + 1]) : 0.f;
-                  if (x < bound) max0 = fmaxf (max0, v0); else max1 = fmaxf (max1, v0);
-                  if (x + 1 < bound) max0 = fmaxf (max0, v1); else max1 = fmaxf (max1, v1);
-                }
-            }
-        }
-      if (own_prev && m * 1024 <= a.n_frames && pbound >= 1024)
-        {
-          const long long ls = (m - 1) * 1024 + 896 + 2 * lane;
-          if (CV == 2)
-            *reinterpret_cast<float4 *> (a.out + ls * 2) = make_float4 (o[0][14], o[CV - 1][14], o[0][15], o[CV - 1][15]);
-          else
-            {
-              float *p = a.out + ls * C + ch0;
-              p[0] = o[0][14];
-              p[C] = o[0][15];
-            }
-#pragma unroll
-          for (int c = 0; c < CV; c++)
-            pmax0 = fmaxf (pmax0, fmaxf (fabsf (o[c][14]), fabsf (o[c][15])));
-        }
-      else if (own_prev)
-        {
-          const int x = 896 + 2 * lane;
-          const long long ls = (m - 1) * 1024 + x;
-          if (CV == 2)
-            {
-              float *p = a.out + ls * 2;
-              if (ls + 1 < a.n_frames)
-                *reinterpret_cast<float4 *> (p) = make_float4 (o[0][14], o[CV - 1][14], o[0][15], o[CV - 1][15]);
-              else if (ls < a.n_frames)
-                *reinterpret_cast<float2 *> (p) = make_float2 (o[0][14], o[CV - 1][14]);
-            }
-          else
-            {
-              float *p = a.out + ls * C + ch0;
-              if (ls < a.n_frames)
-                p[0] = o[0][14];
-              if (ls + 1 < a.n_frames)
-                p[C] = o[0][15];
-            }
-#pragma unroll
-          for (int c = 0; c < CV; c++)
-            {
-              const float v0 = ls < a.n_frames ? fabsf (o[c][14]) : 0.f;
-              const float v1 = ls + 1 < a.n_frames ? fabsf (o[c][15]) : 0.f;
-              if (x < pbound) pmax0 = fmaxf (pmax0, v0); else pmax1 = fmaxf (pmax1, v0);
-              if (x + 1 < pbound) pmax0 = fmaxf (pmax0, v1); else pmax1 = fmaxf (pmax1, v1);
-            }
-        }
-      if (a.block_max)
-        {
-          // Limiter::block_max (reference limiter.cc:90-97): max |x| per limiter block; non-negative
-          // floats order like their bit patterns, so an integer atomic max does it
-          if (own)
-            {
-              max0 = wave_max (max0);
-              max1 = wave_max (max1);
-              if (lane == 0)
-                {
-                  const long long i0 = b0 - a.first_block, i1 = i0 + 1;
-                  if (i0 >= 0 && i0 < a.n_blocks && max0 > 0.f) atomicMax (a.block_max + i0, __float_as_uint (max0));
-                  if (i1 >= 0 && i1 < a.n_blocks && max1 > 0.f) atomicMax (a.block_max + i1, __float_as_uint (max1));
-                }
-            }
-          if (own_prev)
-            {
-              pmax0 = wave_max (pmax0);
-              pmax1 = wave_max (pmax1);
-              if (lane == 0)
-                {
-                  const long long i0 = pb0 - a.first_block, i1 = i0 + 1;
-                  if (i0 >= 0 && i0 < a.n_blocks && pmax0 > 0.f) atomicMax (a.block_max + i0, __float_as_uint (pmax0));
-                  if (i1 >= 0 && i1 < a.n_blocks && pmax1 > 0.f) atomicMax (a.block_max + i1, __float_as_uint (pmax1));
-                }
-            }
-        }
-    }
-}
-
-template<int CV> __global__ void __launch_bounds__ (64 * WAVES)
-add_mix_kernel (DevTables t, AddMixArgs a, long long frame_number0, int block_frames)
-{
-  add_mix_body<CV, false> (t, a, frame_number0, block_frames);
-}
-// stereo: four waves per SIMD (122 registers, 39 KB of LDS per workgroup: four workgroups per CU)
-template<int CV> __global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
-add_mix_kernel_w4 (DevTables t, AddMixArgs a, long long frame_number0, int block_frames)
-{
-  add_mix_body<CV, true> (t, a, frame_number0, block_frames);
-}
-// the same with the two channels' transforms pipelined over the wave's one exchange tile (frame_delta2)
-__global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
-add_mix_pair_kernel (DevTables t, AddMixArgs a, long long frame_number0, int block_frames)
-{
-  add_mix_body<2, true, true> (t, a, frame_number0, block_frames);
-}
-/* a batch of clips in ONE launch (stereo): blockIdx.y = clip, its arguments from an array on the device (uniform: scalar loads); the grid's
- * x extent covers the clip with the most spans, the others' surplus workgroups return at once */
-__global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
-add_mix_pair_batch_kernel (DevTables t, const AddMixArgs *args, long long frame_number0, int block_frames)
-{
-  const AddMixArgs a = args[blockIdx.y];
-  add_mix_body<2, true, true> (t, a, frame_number0, block_frames);
-}
-int add_mix_waves_per_simd() { return 4; }
-int g_fft_pair = 1;              // (debug toggle: stereo add with frame_delta2)
-extern "C" void awm_debug_set_fft_pair (int on) { g_fft_pair = on; }
-
-hipError_t
-launch_add_mix (hipStream_t st, const DevTables& t, const AddMixArgs& a)
-{
-  if (a.n_frames <= 0)
-    return hipSuccess;
-  const long long F = (a.n_frames + 1023) / 1024;
-  const long long n_spans = (F + a.frames_per_span - 1) / a.frames_per_span;
-  const bool stereo = a.n_channels == 2;
-  const long long items = n_spans * (stereo ? 1 : a.n_channels);
-  const unsigned grid = unsigned ((items + WAVES - 1) / WAVES);
-  const int block_frames = a.block_frames;
-  const long long frame_number0 = 2LL * block_frames - a.frames_pad_start;       // reference wmadd.cc:293-294
-  // stereo: both channels in one wave, four waves per SIMD (122 registers; three waves + prefetch of the next frame: 3 - 5 % slower)
-  if (stereo && g_fft_pair)
-    hipLaunchKernelGGL (add_mix_pair_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
-  else if (stereo)
-    hipLaunchKernelGGL (add_mix_kernel_w4<2>, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
-  else
-    hipLaunchKernelGGL (add_mix_kernel<1>, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
-  return hipGetLastError();
-}
-
-hipError_t
-launch_add_mix_batch (hipStream_t st, const DevTables& t, const AddMixArgs *args_dev, int n_clips, long long max_spans, int block_frames, int frames_pad_start)
-{
-  if (n_clips <= 0 || max_spans <= 0)
-    return hipSuccess;
-  const long long frame_number0 = 2LL * block_frames - frames_pad_start;         // reference wmadd.cc:293-294
-  hipLaunchKernelGGL (add_mix_pair_batch_kernel, dim3 (unsigned ((max_spans + WAVES - 1) / WAVES), unsigned (n_clips)), dim3 (64 * WAVES), 0, st,
-                      t, args_dev, frame_number0, block_frames);
-  return hipGetLastError();
-}
-
-/* ==========================================================================================
- * K2m: fused add of ONE stream with several payloads (kernels.hh AddMixMultiArgs)
- *
- * What of K2 does not depend on the payload runs once per frame: the fetch, the window, the forward transform, the real split
- * of the 81 bands and BOTH band factors (the frame_mod tables of two payloads differ only in UP <-> DOWN of data frames,
- * reference wmadd.cc:86-162).  Per output follow the choice of D by its table, the inverse transform, the overlap-add, the mix,
- * the stores and the block maxima -- every expression is K2's (frame_delta / frame_delta2 / add_mix_body), so output p is bit
- * for bit what K2 writes with table p.  The outputs of a launch are unrolled: their overlap-add carry (8 floats per lane and
- * stereo output) stays in registers.
- *
- * Two forms of one body: a whole stream (frame 0 is sample 0, no halos) and, SPAN = true, a span of a stream (kernels.hh AddMixSpan:
- * first_frame, halos, first_block with add_mix_body's meaning) -- the halo frames go through the shared forward half like every other
- * frame.  Everything the span form adds is behind `if constexpr (SPAN)`: the whole-stream kernels compile as they did without it.
- * ========================================================================================== */
-
 // where output frame m lies: in the wave's span or not, and the limiter block boundary inside it / inside frame m - 1
 struct FramePlace
 {
   bool own, own_prev;
-  int b0, bound, pb0, pbound;       // limiter block of the frame's first sample; samples of the frame before the next block begins
+  int b0, bound, pb0, pbound;       // limiter block of the frame's first sample, relative to the first block of the maxima (may lie in front of
+                                    // it); samples of the frame before the next block begins
 };
 
-// stores + block maxima of one output: values 0 .. 13 of o are frame m, 14 and 15 the tail of frame m - 1 (add_mix_body's).  m and n_frames
-// are local to the launch; SPAN: fp.b0 / fp.pb0 are relative to the first block of the maxima and may lie in front of it (K2's range checks)
-template<int CV, bool SPAN = false> __device__ __forceinline__ void
-multi_emit (float *out, unsigned int *block_max, const float (&o)[CV][16], long long m, const FramePlace& fp,
+// gs_m: the frame's first sample in the whole stream
+__device__ __forceinline__ FramePlace
+frame_place (long long gs_m, int BS, long long first_block, bool own, bool own_prev)
+{
+  FramePlace fp;
+  fp.own = own;
+  fp.own_prev = own_prev;
+  const long long b0 = gs_m >= 0 ? gs_m / BS : 0;
+  const long long gs_p = gs_m - 1024;
+  const long long pb0 = gs_p >= 0 ? gs_p / BS : 0;
+  fp.b0 = int (b0 - first_block);
+  fp.bound = int (std::min<long long> ((b0 + 1) * BS - gs_m, 2048));        // (only compared with offsets below 1024)
+  fp.pb0 = int (pb0 - first_block);
+  fp.pbound = int (std::min<long long> ((pb0 + 1) * BS - gs_p, 2048));
+  return fp;
+}
+
+/* output frame m = d[m-1] W2 + d[m] W1 + d[m+1] W0 + in[m]   (reference wmadd.cc:228-238, 564-565), separately rounded products and sums in
+ * the reference's order.  Values 0 .. 13 of o are frame m, 14 and 15 the tail of frame m - 1, which gets its W0 contribution now.  head2 / tail_s1
+ * are the output's overlap-add carry; tail_in (the input under the previous frame's tail) is the caller's to update.  Window pieces of the
+ * lane (reference wmadd.cc:177-206): head = samples 2 lane, 2 lane + 1 of a frame (slots W1, W2); tail = samples 896 + 2 lane (+1) (slots
+ * W1, W0).  In between W1 == 1, W0 == W2 == 0. */
+template<int CV> __device__ __forceinline__ void
+overlap_add_mix (float (&o)[CV][16], const float2 (&d)[CV][8], const float (&in)[CV][16], float (&head2)[CV][2], float (&tail_s1)[CV][2],
+                 const float (&tail_in)[CV][2], float2 w1_head, float2 w2_head, float2 w1_tail, float2 w0_tail)
+{
+#pragma unroll
+  for (int c = 0; c < CV; c++)
+    {
+      // j = 0: head region, W1/W2 ramps
+      const float s1x = __fadd_rn (head2[c][0], __fmul_rn (d[c][0].x, w1_head.x));
+      const float s1y = __fadd_rn (head2[c][1], __fmul_rn (d[c][0].y, w1_head.y));
+      o[c][0] = __fadd_rn (s1x, in[c][0]);
+      o[c][1] = __fadd_rn (s1y, in[c][1]);
+      head2[c][0] = __fmul_rn (d[c][0].x, w2_head.x);
+      head2[c][1] = __fmul_rn (d[c][0].y, w2_head.y);
+#pragma unroll
+      for (int j = 1; j < 7; j++)
+        {
+          o[c][2 * j]     = __fadd_rn (d[c][j].x, in[c][2 * j]);
+          o[c][2 * j + 1] = __fadd_rn (d[c][j].y, in[c][2 * j + 1]);
+        }
+      // j = 7 of the PREVIOUS frame
+      o[c][14] = __fadd_rn (__fadd_rn (tail_s1[c][0], __fmul_rn (d[c][7].x, w0_tail.x)), tail_in[c][0]);
+      o[c][15] = __fadd_rn (__fadd_rn (tail_s1[c][1], __fmul_rn (d[c][7].y, w0_tail.y)), tail_in[c][1]);
+      tail_s1[c][0] = __fmul_rn (d[c][7].x, w1_tail.x);
+      tail_s1[c][1] = __fmul_rn (d[c][7].y, w1_tail.y);
+    }
+}
+
+/* stores (bounded by the launch's sample count) + block maxima of one output frame.  m and n_frames are local to the launch.  Common case
+ * (all but the last frame of the stream, and 42 of 43 frames have no limiter block boundary inside): plain stores and ONE running maximum, no
+ * per-value bounds tests.  RANGE: a block may lie in front of the array of maxima (a span with first_block > 0) and is dropped then. */
+template<int CV, bool RANGE> __device__ __forceinline__ void
+emit_frame (float *out, unsigned int *block_max, const float (&o)[CV][16], long long m, const FramePlace& fp,
             long long n_frames, long long n_blocks, int C, int ch0, int lane)
 {
   float max0 = 0.f, max1 = 0.f, pmax0 = 0.f, pmax1 = 0.f;
@@ -827,7 +552,8 @@ multi_emit (float *out, unsigned int *block_max, const float (&o)[CV][16], long 
     }
   if (block_max)
     {
-      // Limiter::block_max (reference limiter.cc:90-97), see add_mix_body
+      // Limiter::block_max (reference limiter.cc:90-97): max |x| per limiter block; non-negative
+      // floats order like their bit patterns, so an integer atomic max does it
       if (fp.own)
         {
           max0 = wave_max (max0);
@@ -835,8 +561,8 @@ multi_emit (float *out, unsigned int *block_max, const float (&o)[CV][16], long 
           if (lane == 0)
             {
               const long long i0 = fp.b0, i1 = i0 + 1;
-              if ((!SPAN || i0 >= 0) && i0 < n_blocks && max0 > 0.f) atomicMax (block_max + i0, __float_as_uint (max0));
-              if ((!SPAN || i1 >= 0) && i1 < n_blocks && max1 > 0.f) atomicMax (block_max + i1, __float_as_uint (max1));
+              if ((!RANGE || i0 >= 0) && i0 < n_blocks && max0 > 0.f) atomicMax (block_max + i0, __float_as_uint (max0));
+              if ((!RANGE || i1 >= 0) && i1 < n_blocks && max1 > 0.f) atomicMax (block_max + i1, __float_as_uint (max1));
             }
         }
       if (fp.own_prev)
@@ -846,12 +572,251 @@ multi_emit (float *out, unsigned int *block_max, const float (&o)[CV][16], long 
           if (lane == 0)
             {
               const long long i0 = fp.pb0, i1 = i0 + 1;
-              if ((!SPAN || i0 >= 0) && i0 < n_blocks && pmax0 > 0.f) atomicMax (block_max + i0, __float_as_uint (pmax0));
-              if ((!SPAN || i1 >= 0) && i1 < n_blocks && pmax1 > 0.f) atomicMax (block_max + i1, __float_as_uint (pmax1));
+              if ((!RANGE || i0 >= 0) && i0 < n_blocks && pmax0 > 0.f) atomicMax (block_max + i0, __float_as_uint (pmax0));
+              if ((!RANGE || i1 >= 0) && i1 < n_blocks && pmax1 > 0.f) atomicMax (block_max + i1, __float_as_uint (pmax1));
             }
         }
     }
 }
+
+// prologue of a workgroup: the transforms' tables into LDS, the wave's zd cleared (the bins between the bands stay 0 for good).  The caller's
+// __syncthreads() follows
+__device__ __forceinline__ void
+add_load_tables (const DevTables& t, float2 *s_tw, float2 *s_tw3, float *s_win, float2 *s_twb, float2 *zd, int lane)
+{
+  load_shared_tables (t, s_tw, s_win, s_twb);
+  fft512_load_twiddles_inverse (t.tw512, s_tw3);          // twiddles of the inverse transform's last stage (awm_fft.hip.h)
+  for (int i = lane; i < 256; i += 64)
+    zd[i] = make_float2 (0.f, 0.f);
+}
+
+// the wave's share of the launch: frames s .. e - 1 of the F frames, L to a span; CV == 2 both channels, otherwise channel ch0.  false: none
+template<int CV> __device__ __forceinline__ bool
+span_partition (long long n_frames, int C, int L, int wave, long long& F, long long& s, long long& e, int& ch0)
+{
+  const int n_cg = CV == 2 ? 1 : C;
+  F = (n_frames + 1023) / 1024;
+  const long long n_spans = (F + L - 1) / L;
+  const long long item = (long long) blockIdx.x * WAVES + wave;
+  if (item >= n_spans * n_cg)
+    return false;
+  const long long span = item / n_cg;
+  ch0 = int (item % n_cg);
+  s = span * L;
+  e = (s + L < F) ? s + L : F;
+  return true;
+}
+
+// where frame m comes from (halo before / the launch's samples / halo after) and how much of it exists.  Without HALO frames -1 and F are
+// silence.  The pointer is only good where avail > 0
+template<bool HALO> __device__ __forceinline__ const float *
+frame_source (const float *pcm_in, long long n_frames, int C, long long F, long long m, const float *halo_before, const float *halo_after, int& avail)
+{
+  if constexpr (HALO)
+    if (m < 0 || m >= F)
+      {
+        const float *src = m < 0 ? halo_before : halo_after;
+        avail = src ? 1024 : 0;
+        return src;
+      }
+  avail = 0;
+  if (HALO || (m >= 0 && m < F))
+    {
+      const long long left = n_frames - m * 1024;
+      avail = left < 1024 ? int (left) : 1024;
+    }
+  return pcm_in + m * 1024 * C;
+}
+
+template<int CV, bool OPAQUE, bool PAIR = false> __device__ __forceinline__ void
+add_mix_body (const DevTables& t, const AddMixArgs& a, long long frame_number0, int block_frames)
+{
+  __shared__ float2 s_tw[512];
+  __shared__ float2 s_tw3[512];
+  __shared__ float  s_win[1024];
+  __shared__ float2 s_twb[NB];
+  __shared__ float2 s_x[WAVES][XBUF_ELEMS];
+  __shared__ float2 s_zd[WAVES][256];
+  // the wave index is wave-uniform: in a scalar register, the frame loop's counters, bounds tests and base addresses run on the
+  // scalar unit (the compiler cannot see that threadIdx.x >> 6 is the same for all lanes)
+  const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane (threadIdx.x >> 6);
+  int lane = lane0;
+  add_load_tables (t, s_tw, s_tw3, s_win, s_twb, s_zd[wave], lane);
+  __syncthreads();
+
+  const int C = a.n_channels;
+  long long F, s, e;
+  int ch0;
+  if (!span_partition<CV> (a.n_frames, C, a.frames_per_span, wave, F, s, e, ch0))
+    return;
+  float2 *xbuf = s_x[wave], *zd = s_zd[wave];
+
+  // synthesis window pieces this lane needs (overlap_add_mix), in registers for the span
+  const float2 w1_head = reinterpret_cast<const float2 *> (t.synth + 1024)[lane];
+  const float2 w2_head = reinterpret_cast<const float2 *> (t.synth + 2048)[lane];
+  const float2 w1_tail = reinterpret_cast<const float2 *> (t.synth + 1024 + 896)[lane];
+  const float2 w0_tail = reinterpret_cast<const float2 *> (t.synth + 896)[lane];
+
+  float head2[CV][2], tail_s1[CV][2], tail_in[CV][2];
+#pragma unroll
+  for (int c = 0; c < CV; c++)
+    head2[c][0] = head2[c][1] = tail_s1[c][0] = tail_s1[c][1] = tail_in[c][0] = tail_in[c][1] = 0.f;
+
+  const int BS = a.limiter_block;
+  const long long total_rows = 2LL * block_frames;
+
+  for (long long m = s - 1; m <= e; m++)
+    {
+      if (OPAQUE)
+        {
+          // make the lane index opaque per frame: the ~60 lane-dependent twiddle factors are then re-read from LDS
+          // for every transform instead of being hoisted into registers for the whole span (occupancy over reuse)
+          lane = lane0;
+          asm volatile ("" : "+v" (lane));
+        }
+      int avail;
+      const float *src = frame_source<true> (a.pcm_in, a.n_frames, C, F, m, a.halo_before, a.halo_after, avail);
+      float in[CV][16];
+      float2 d[CV][8];
+      if (avail > 0)
+        {
+          if constexpr (CV == 2)
+            fetch_stereo (src, 0, avail, lane, in[0], in[1]);
+          else
+            fetch_channel (src, 0, avail, C, ch0, lane, in[0]);
+          const long long g = a.first_frame + m;                       // frame index in the whole stream
+          const long long row = (frame_number0 + g) % total_rows;      // reference wmadd.cc:326-344
+          const int8_t *mod_row = a.frame_mod + row * NB;
+          if constexpr (CV == 2 && PAIR)
+            {
+              window_pack (in[0], s_win, lane, d[0]);
+              window_pack (in[1], s_win, lane, d[1]);
+              frame_delta2 (d[0], d[1], mod_row, a.neg_delta_up, a.neg_delta_down, xbuf, zd, s_tw, s_tw3, s_twb, lane);
+            }
+          else
+            {
+#pragma unroll
+              for (int c = 0; c < CV; c++)
+                {
+                  window_pack (in[c], s_win, lane, d[c]);
+                  frame_delta (d[c], mod_row, a.neg_delta_up, a.neg_delta_down, xbuf, zd, s_tw, s_tw3, s_twb, lane);
+                }
+            }
+        }
+      else
+        {
+#pragma unroll
+          for (int c = 0; c < CV; c++)
+            {
+#pragma unroll
+              for (int j = 0; j < 16; j++)
+                in[c][j] = 0.f;
+#pragma unroll
+              for (int j = 0; j < 8; j++)
+                d[c][j] = make_float2 (0.f, 0.f);
+            }
+        }
+
+      if (a.delta_only)
+        {
+          // WatermarkGen::run alone: the mix below then adds 0 instead of the input
+#pragma unroll
+          for (int c = 0; c < CV; c++)
+#pragma unroll
+            for (int j = 0; j < 16; j++)
+              in[c][j] = 0.f;
+        }
+      const FramePlace fp = frame_place ((a.first_frame + m) * 1024, BS, a.first_block, m >= s && m < e, m - 1 >= s && m - 1 < e);
+      float o[CV][16];
+      overlap_add_mix<CV> (o, d, in, head2, tail_s1, tail_in, w1_head, w2_head, w1_tail, w0_tail);
+#pragma unroll
+      for (int c = 0; c < CV; c++)
+        {
+          tail_in[c][0] = in[c][14];
+          tail_in[c][1] = in[c][15];
+        }
+      emit_frame<CV, true> (a.out, a.block_max, o, m, fp, a.n_frames, a.n_blocks, C, ch0, lane);
+    }
+}
+
+template<int CV> __global__ void __launch_bounds__ (64 * WAVES)
+add_mix_kernel (DevTables t, AddMixArgs a, long long frame_number0, int block_frames)
+{
+  add_mix_body<CV, false> (t, a, frame_number0, block_frames);
+}
+// stereo: four waves per SIMD (122 registers, 39 KB of LDS per workgroup: four workgroups per CU)
+template<int CV> __global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
+add_mix_kernel_w4 (DevTables t, AddMixArgs a, long long frame_number0, int block_frames)
+{
+  add_mix_body<CV, true> (t, a, frame_number0, block_frames);
+}
+// the same with the two channels' transforms pipelined over the wave's one exchange tile (frame_delta2)
+__global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
+add_mix_pair_kernel (DevTables t, AddMixArgs a, long long frame_number0, int block_frames)
+{
+  add_mix_body<2, true, true> (t, a, frame_number0, block_frames);
+}
+/* a batch of clips in ONE launch (stereo): blockIdx.y = clip, its arguments from an array on the device (uniform: scalar loads); the grid's
+ * x extent covers the clip with the most spans, the others' surplus workgroups return at once */
+__global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
+add_mix_pair_batch_kernel (DevTables t, const AddMixArgs *args, long long frame_number0, int block_frames)
+{
+  const AddMixArgs a = args[blockIdx.y];
+  add_mix_body<2, true, true> (t, a, frame_number0, block_frames);
+}
+int add_mix_waves_per_simd() { return 4; }
+int g_fft_pair = 1;              // (debug toggle: stereo add with frame_delta2)
+extern "C" void awm_debug_set_fft_pair (int on) { g_fft_pair = on; }
+
+hipError_t
+launch_add_mix (hipStream_t st, const DevTables& t, const AddMixArgs& a)
+{
+  if (a.n_frames <= 0)
+    return hipSuccess;
+  const long long F = (a.n_frames + 1023) / 1024;
+  const long long n_spans = (F + a.frames_per_span - 1) / a.frames_per_span;
+  const bool stereo = a.n_channels == 2;
+  const long long items = n_spans * (stereo ? 1 : a.n_channels);
+  const unsigned grid = unsigned ((items + WAVES - 1) / WAVES);
+  const int block_frames = a.block_frames;
+  const long long frame_number0 = 2LL * block_frames - a.frames_pad_start;       // reference wmadd.cc:293-294
+  // stereo: both channels in one wave, four waves per SIMD (122 registers; three waves + prefetch of the next frame: 3 - 5 % slower)
+  if (stereo && g_fft_pair)
+    hipLaunchKernelGGL (add_mix_pair_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
+  else if (stereo)
+    hipLaunchKernelGGL (add_mix_kernel_w4<2>, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
+  else
+    hipLaunchKernelGGL (add_mix_kernel<1>, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
+  return hipGetLastError();
+}
+
+hipError_t
+launch_add_mix_batch (hipStream_t st, const DevTables& t, const AddMixArgs *args_dev, int n_clips, long long max_spans, int block_frames, int frames_pad_start)
+{
+  if (n_clips <= 0 || max_spans <= 0)
+    return hipSuccess;
+  const long long frame_number0 = 2LL * block_frames - frames_pad_start;         // reference wmadd.cc:293-294
+  hipLaunchKernelGGL (add_mix_pair_batch_kernel, dim3 (unsigned ((max_spans + WAVES - 1) / WAVES), unsigned (n_clips)), dim3 (64 * WAVES), 0, st,
+                      t, args_dev, frame_number0, block_frames);
+  return hipGetLastError();
+}
+
+/* ==========================================================================================
+ * K2m: fused add of ONE stream with several payloads (kernels.hh AddMixMultiArgs)
+ *
+ * What of K2 does not depend on the payload runs once per frame: the fetch, the window, the forward transform, the real split
+ * of the 81 bands and BOTH band factors (the frame_mod tables of two payloads differ only in UP <-> DOWN of data frames,
+ * reference wmadd.cc:86-162).  Per output follow the choice of D by its table, the inverse transform, the overlap-add, the mix,
+ * the stores and the block maxima.  The body is assembled from K2's own pieces above (frame_forward[2], frame_inverse[2], halfspec_store,
+ * overlap_add_mix, frame_place, emit_frame, frame_source, span_partition, add_load_tables); its own text is the band edit with both
+ * exponents and the choice of D, so output p is bit for bit what K2 writes with table p by construction.  The outputs of a launch are
+ * unrolled: their overlap-add carry (8 floats per lane and stereo output) stays in registers.
+ *
+ * Two forms of one body: a whole stream (frame 0 is sample 0, no halos) and, SPAN = true, a span of a stream (kernels.hh AddMixSpan:
+ * first_frame, halos, first_block with add_mix_body's meaning) -- the halo frames go through the shared forward half like every other
+ * frame.  The whole-stream form is the span at frame 0 and block 0 with these as constants: frame_source<false> has no halo branch,
+ * emit_frame<CV, false> no test for a block in front of the array.
+ * ========================================================================================== */
 
 template<int CV, bool SPAN = false> __device__ __forceinline__ void
 add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSpan& sp)
@@ -866,12 +831,8 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSp
   __shared__ float2 s_syn[4][64];                          // the lanes' synthesis window pieces (the same in every wave)
   const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane (threadIdx.x >> 6);
   int lane = lane0;
-  load_shared_tables (t, s_tw, s_win, s_twb);
-  fft512_load_twiddles_inverse (t.tw512, s_tw3);
-  for (int i = lane; i < 256; i += 64)
-    s_zd[wave][i] = make_float2 (0.f, 0.f);
-  // synthesis window pieces a lane needs (see add_mix_body): head = samples 2 lane, 2 lane + 1 of a frame (slots W1, W2), tail = samples
-  // 896 + 2 lane (+ 1) (slots W1, W0).  In LDS, read per output: eight registers less across the outputs
+  add_load_tables (t, s_tw, s_tw3, s_win, s_twb, s_zd[wave], lane);
+  // synthesis window pieces a lane needs (overlap_add_mix).  In LDS, read per output: eight registers less across the outputs
   if (wave == 0)
     {
       s_syn[0][lane] = reinterpret_cast<const float2 *> (t.synth + 1024)[lane];
@@ -882,16 +843,10 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSp
   __syncthreads();
 
   const int C = a.n_channels;
-  const int n_cg = CV == 2 ? 1 : C;
-  const long long F = (a.n_frames + 1023) / 1024;
-  const int L = a.frames_per_span;
-  const long long n_spans = (F + L - 1) / L;
-  const long long item = (long long) blockIdx.x * WAVES + wave;
-  if (item >= n_spans * n_cg)
+  long long F, s, e;
+  int ch0;
+  if (!span_partition<CV> (a.n_frames, C, a.frames_per_span, wave, F, s, e, ch0))
     return;
-  const long long span = item / n_cg;
-  const int ch0 = int (item % n_cg);
-  const long long s = span * L, e = (s + L < F) ? s + L : F;
   float2 *xbuf = s_x[wave], *zd = s_zd[wave];
 
   // overlap-add carry: the watermark signal's per output, the input's once
@@ -909,36 +864,20 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSp
   const long long total_rows = 2LL * a.block_frames;
   const long long frame_number0 = total_rows - a.frames_pad_start;     // reference wmadd.cc:293-294
   const float2 zero = make_float2 (0.f, 0.f);
-  auto zposb = [] (int k) { const int p = zpos (k); return p < 128 ? p + 128 : p - 128; };
 
   for (long long m = s - 1; m <= e; m++)
     {
       // (the lane index opaque per frame: twiddle factors are re-read from LDS instead of living in registers for the span, see add_mix_body)
       lane = lane0;
       asm volatile ("" : "+v" (lane));
-      int avail = 0;
-      if (m >= 0 && m < F)
-        {
-          const long long left = a.n_frames - m * 1024;
-          avail = left < 1024 ? int (left) : 1024;
-        }
-      // a span of a stream: frame -1 / frame F from the halos, as add_mix_body's frame_source
-      const float *halo = nullptr;
-      if constexpr (SPAN)
-        if (m < 0 || m >= F)
-          {
-            halo = m < 0 ? sp.halo_before : sp.halo_after;
-            avail = halo ? 1024 : 0;
-          }
+      // a span of a stream: frame -1 / frame F from the halos
+      int avail;
+      const float *src = frame_source<SPAN> (a.pcm_in, a.n_frames, C, F, m, sp.halo_before, sp.halo_after, avail);
       float in[CV][16];
       float2 d_up[CV][2], d_down[CV][2];             // per pass of the bands: X (|X|^-delta - 1), X (|X|^+delta - 1)
       int mod[2];                                    // frame_mod of every output for the lane's band: 2 bits each (bit 0 touched, bit 1 UP)
       if (avail > 0)
         {
-          const float *src = a.pcm_in + m * 1024 * C;
-          if constexpr (SPAN)
-            if (halo)
-              src = halo;
           if constexpr (CV == 2)
             fetch_stereo (src, 0, avail, lane, in[0], in[1]);
           else
@@ -967,29 +906,9 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSp
           for (int c = 0; c < CV; c++)
             window_pack (in[c], s_win, lane, z[c]);
           if constexpr (CV == 2)
-            {
-              // frame_delta2's forward half
-              fft512_forward2 (z[0], z[1], xbuf, s_tw, lane);
-              lds_st (&xbuf[0 * 64 + lane], z[0][0]);
-              lds_st (&xbuf[1 * 64 + lane], z[0][1]);
-              lds_st (&xbuf[6 * 64 + lane], z[0][6]);
-              lds_st (&xbuf[7 * 64 + lane], z[0][7]);
-              lds_st (&xbuf[2 * 64 + lane], z[1][0]);
-              lds_st (&xbuf[3 * 64 + lane], z[1][1]);
-              lds_st (&xbuf[4 * 64 + lane], z[1][6]);
-              lds_st (&xbuf[5 * 64 + lane], z[1][7]);
-              wave_sync_pinned();
-            }
+            frame_forward2 (z[0], z[1], xbuf, s_tw, lane);
           else
-            {
-              // frame_delta's forward half
-              fft512_forward (z[0], xbuf, s_tw, lane);
-              xbuf[0 * 64 + lane] = z[0][0];
-              xbuf[1 * 64 + lane] = z[0][1];
-              xbuf[6 * 64 + lane] = z[0][6];
-              xbuf[7 * 64 + lane] = z[0][7];
-              wave_sync();
-            }
+            frame_forward (z[0], xbuf, s_tw, lane);
 #pragma unroll
           for (int pass = 0; pass < 2; pass++)
             {
@@ -1032,24 +951,8 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSp
               in[c][j] = 0.f;
         }
 
-      FramePlace fp;
-      fp.own = m >= s && m < e;
-      fp.own_prev = m - 1 >= s && m - 1 < e;
-      long long gs_m = m * 1024;
-      if constexpr (SPAN)
-        gs_m = (sp.first_frame + m) * 1024;                                      // the frame's first sample in the whole stream
-      const long long b0 = gs_m >= 0 ? gs_m / BS : 0;
-      const long long gs_p = gs_m - 1024;
-      const long long pb0 = gs_p >= 0 ? gs_p / BS : 0;
-      fp.b0 = int (b0);
-      fp.bound = int (std::min<long long> ((b0 + 1) * BS - gs_m, 2048));        // (only compared with offsets below 1024)
-      fp.pb0 = int (pb0);
-      fp.pbound = int (std::min<long long> ((pb0 + 1) * BS - gs_p, 2048));
-      if constexpr (SPAN)
-        {
-          fp.b0 = int (b0 - sp.first_block);
-          fp.pb0 = int (pb0 - sp.first_block);
-        }
+      // the frame's first sample in the whole stream; the whole-stream form is the span that starts at frame 0 and block 0
+      const FramePlace fp = frame_place ((SPAN ? sp.first_frame + m : m) * 1024, BS, SPAN ? sp.first_block : 0, m >= s && m < e, m - 1 >= s && m - 1 < e);
 
 #pragma unroll
       for (int p = 0; p < PT; p++)
@@ -1060,7 +963,7 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSp
             float2 d[CV][8];
             if (avail > 0)
               {
-                // the output's choice of D per band (frame_mod: 1 UP, 0 untouched, anything else DOWN), then frame_delta's / frame_delta2's inverse half
+                // the output's choice of D per band (frame_mod: 1 UP, 0 untouched, anything else DOWN), then the inverse half
                 float2 D[CV][2], O[CV][2];
 #pragma unroll
                 for (int pass = 0; pass < 2; pass++)
@@ -1079,52 +982,18 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSp
                       }
                   }
                 if constexpr (CV == 2)
-                  {
-#pragma unroll
-                    for (int c = 0; c < 2; c++)
-                      {
-                        wave_sync_pinned();
-#pragma unroll
-                        for (int pass = 0; pass < 2; pass++)
-                          {
-                            const int k = MIN_BAND + lane + 64 * pass;
-                            if (k <= 100)
-                              {
-                                lds_st (&zd[zdpos (k)],       make_float2 (D[c][pass].x - O[c][pass].y, D[c][pass].y + O[c][pass].x));
-                                lds_st (&zd[zdpos (512 - k)], make_float2 (D[c][pass].x + O[c][pass].y, O[c][pass].x - D[c][pass].y));
-                              }
-                          }
-                        wave_sync_pinned();
-                        d[c][0] = lds_ld (&zd[0 * 64 + lane]);
-                        d[c][1] = lds_ld (&zd[1 * 64 + lane]);
-                        d[c][2] = zero; d[c][3] = zero; d[c][4] = zero; d[c][5] = zero;
-                        d[c][6] = lds_ld (&zd[2 * 64 + lane]);
-                        d[c][7] = lds_ld (&zd[3 * 64 + lane]);
-                      }
-                    wave_sync_pinned();
-                    fft512_inverse2 (d[0], d[CV - 1], xbuf, s_tw, s_tw3, lane);
-                  }
+                  frame_inverse2 (d[0], d[CV - 1], D[0], O[0], D[CV - 1], O[CV - 1], xbuf, zd, s_tw, s_tw3, lane);
                 else
                   {
-                    wave_sync();
+                    wave_sync();              // (K2m's own: K2 stores zd in the pass that edits the bands)
 #pragma unroll
                     for (int pass = 0; pass < 2; pass++)
                       {
                         const int k = MIN_BAND + lane + 64 * pass;
                         if (k <= 100)
-                          {
-                            zd[zdpos (k)]       = make_float2 (D[0][pass].x - O[0][pass].y, D[0][pass].y + O[0][pass].x);
-                            zd[zdpos (512 - k)] = make_float2 (D[0][pass].x + O[0][pass].y, O[0][pass].x - D[0][pass].y);
-                          }
+                          halfspec_store (zd, k, D[0][pass], O[0][pass]);
                       }
-                    wave_sync();
-                    d[0][0] = zd[0 * 64 + lane];
-                    d[0][1] = zd[1 * 64 + lane];
-                    d[0][2] = zero; d[0][3] = zero; d[0][4] = zero; d[0][5] = zero;
-                    d[0][6] = zd[2 * 64 + lane];
-                    d[0][7] = zd[3 * 64 + lane];
-                    wave_sync();
-                    fft512_inverse (d[0], xbuf, s_tw, s_tw3, lane);
+                    frame_inverse (d[0], xbuf, zd, s_tw, s_tw3, lane);
                   }
               }
             else
@@ -1136,30 +1005,9 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSp
                     d[c][j] = zero;
               }
 
-            // output frame m = d[m-1] W2 + d[m] W1 + d[m+1] W0 + in[m]   (reference wmadd.cc:228-238, 564-565), as add_mix_body
-            const float2 w1_head = s_syn[0][lane], w2_head = s_syn[1][lane], w1_tail = s_syn[2][lane], w0_tail = s_syn[3][lane];
             float o[CV][16];
-#pragma unroll
-            for (int c = 0; c < CV; c++)
-              {
-                const float s1x = __fadd_rn (head2[p][c][0], __fmul_rn (d[c][0].x, w1_head.x));
-                const float s1y = __fadd_rn (head2[p][c][1], __fmul_rn (d[c][0].y, w1_head.y));
-                o[c][0] = __fadd_rn (s1x, in[c][0]);
-                o[c][1] = __fadd_rn (s1y, in[c][1]);
-                head2[p][c][0] = __fmul_rn (d[c][0].x, w2_head.x);
-                head2[p][c][1] = __fmul_rn (d[c][0].y, w2_head.y);
-#pragma unroll
-                for (int j = 1; j < 7; j++)
-                  {
-                    o[c][2 * j]     = __fadd_rn (d[c][j].x, in[c][2 * j]);
-                    o[c][2 * j + 1] = __fadd_rn (d[c][j].y, in[c][2 * j + 1]);
-                  }
-                o[c][14] = __fadd_rn (__fadd_rn (tail_s1[p][c][0], __fmul_rn (d[c][7].x, w0_tail.x)), tail_in[c][0]);
-                o[c][15] = __fadd_rn (__fadd_rn (tail_s1[p][c][1], __fmul_rn (d[c][7].y, w0_tail.y)), tail_in[c][1]);
-                tail_s1[p][c][0] = __fmul_rn (d[c][7].x, w1_tail.x);
-                tail_s1[p][c][1] = __fmul_rn (d[c][7].y, w1_tail.y);
-              }
-            multi_emit<CV, SPAN> (a.o[p].out, a.o[p].block_max, o, m, fp, a.n_frames, a.n_blocks, C, ch0, lane);
+            overlap_add_mix<CV> (o, d, in, head2[p], tail_s1[p], tail_in, s_syn[0][lane], s_syn[1][lane], s_syn[2][lane], s_syn[3][lane]);
+            emit_frame<CV, SPAN> (a.o[p].out, a.o[p].block_max, o, m, fp, a.n_frames, a.n_blocks, C, ch0, lane);
           }
 #pragma unroll
       for (int c = 0; c < CV; c++)

@@ -87,6 +87,48 @@ frames_per_span (awm_ctx *ctx, long long n_frames1024, int waves_per_simd = 0)  
   return int (std::min<long long> (best_l, 4096));
 }
 
+// the fields of K2's (AddMixArgs) and K2m's (AddMixMultiArgs) arguments that depend on no stream, span or payload
+template<class Args> void
+fill_add_mix_common (Args& a, double water_delta)
+{
+  // powf (mag, -params().water_delta * data_bit_sign): double product converted to float (reference wmadd.cc:79)
+  a.neg_delta_up = float (-water_delta * 1);
+  a.neg_delta_down = float (-water_delta * -1);
+  a.limiter_block = LIMITER_BLOCK;
+  a.block_frames = int (mark_block_frame_count());
+  a.frames_pad_start = int (Params::frames_pad_start);
+}
+
+/* K2m over n_payloads outputs: passes of at most ADD_MULTI_TILE outputs and of nearly equal size (5 payloads: 3 + 2, not 4 + 1: a pass costs the
+ * input read and the forward transforms whatever it carries).  output (p, o) fills in output p (false: give up; the tables of a pass are looked
+ * up when it is launched), launch() enqueues the pass that a describes, after (p0, n) what follows the pass of outputs p0 .. p0 + n - 1 */
+template<class Output, class Launch, class After> int
+add_mix_multi_passes (awm_ctx *ctx, hipStream_t st, awmk::AddMixMultiArgs& a, size_t n_payloads, Output&& output, Launch&& launch, After&& after)
+{
+  const size_t n_passes = (n_payloads + awmk::ADD_MULTI_TILE - 1) / awmk::ADD_MULTI_TILE;
+  size_t p0 = 0;
+  for (size_t pass = 0; pass < n_passes; pass++)
+    {
+      const size_t n = n_payloads / n_passes + (pass < n_payloads % n_passes ? 1 : 0);
+      for (size_t i = 0; i < size_t (awmk::ADD_MULTI_TILE); i++)
+        {
+          a.o[i] = awmk::AddMixOut {};
+          if (i < n && !output (p0 + i, a.o[i]))
+            return AWM_ERR_ARG;
+        }
+      a.n_out = int (n);
+      {
+        ProfScope ps (ctx, PROF_ADD_MIX_MULTI, double (1 + n) * double (a.n_frames) * a.n_channels * 4.0, st);     // the input once, every output once
+        if (int rc = launch())
+          return rc;
+      }
+      if (int rc = after (p0, n))
+        return rc;
+      p0 += n;
+    }
+  return 0;
+}
+
 void
 fill_pattern (const ResultSet::Pattern& p, awm_pattern& o)
 {
@@ -161,18 +203,13 @@ add_mix_impl (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames
   a.n_frames = (long long) n_frames;
   a.n_channels = n_channels;
   a.frame_mod = frame_mod_dev;
-  // powf (mag, -params().water_delta * data_bit_sign): double product converted to float (reference wmadd.cc:79)
-  a.neg_delta_up = float (-water_delta * 1);
-  a.neg_delta_down = float (-water_delta * -1);
+  fill_add_mix_common (a, water_delta);
   a.first_frame = (long long) first_frame;
   a.halo_before = halo_before_d;
   a.halo_after = halo_after_d;
   a.block_max = reinterpret_cast<unsigned int *> (block_max_d);
   a.first_block = (long long) first_block;
   a.n_blocks = (long long) n_blocks;
-  a.limiter_block = LIMITER_BLOCK;
-  a.block_frames = int (mark_block_frame_count());
-  a.frames_pad_start = int (Params::frames_pad_start);
   a.frames_per_span = frames_per_span (ctx, (long long) (n_frames + 1023) / 1024);
   {
     ProfScope ps (ctx, PROF_ADD_MIX, double (n_frames) * n_channels * 8.0, st);     // read + write every sample once
@@ -511,11 +548,7 @@ add_full_rate (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frame
     a.n_frames = (long long) n44;
     a.n_channels = C;
     a.frame_mod = frame_mod_dev;
-    a.neg_delta_up = float (-water_delta * 1);
-    a.neg_delta_down = float (-water_delta * -1);
-    a.limiter_block = LIMITER_BLOCK;
-    a.block_frames = int (mark_block_frame_count());
-    a.frames_pad_start = int (Params::frames_pad_start);
+    fill_add_mix_common (a, water_delta);
     a.frames_per_span = frames_per_span (ctx, (long long) (F + 1));
     a.delta_only = 1;
     ProfScope ps (ctx, PROF_ADD_MIX, double (n44) * C * 8.0);
@@ -1252,46 +1285,33 @@ awm_add_watermark_payloads_d (awm_ctx *ctx, const uint8_t key[16], const char *c
   a.pcm_in = pcm_in_d;
   a.n_frames = (long long) n_frames;
   a.n_channels = n_channels;
-  a.neg_delta_up = float (-water_delta * 1);             // as add_mix_impl
-  a.neg_delta_down = float (-water_delta * -1);
+  fill_add_mix_common (a, water_delta);
   a.n_blocks = (long long) n_blocks;
-  a.limiter_block = LIMITER_BLOCK;
-  a.block_frames = int (mark_block_frame_count());
-  a.frames_pad_start = int (Params::frames_pad_start);
   a.frames_per_span = frames_per_span (ctx, (long long) (n_frames + 1023) / 1024, awmk::add_mix_multi_waves_per_simd());
-  // tile passes of nearly equal size (5 payloads: 3 + 2, not 4 + 1: a pass costs the input read and the forward transforms whatever it carries)
-  const size_t n_passes = (n_payloads + awmk::ADD_MULTI_TILE - 1) / awmk::ADD_MULTI_TILE;
-  size_t p0 = 0;
-  for (size_t pass = 0; pass < n_passes; pass++)
-    {
-      const size_t n = n_payloads / n_passes + (pass < n_payloads % n_passes ? 1 : 0);
-      // (the tables of a pass are looked up when it is launched: the cache holds far more than a tile, and drains the device before it drops one)
-      for (size_t i = 0; i < n; i++)
+  const int rc = add_mix_multi_passes (ctx, st, a, n_payloads,
+    [&] (size_t p, awmk::AddMixOut& o) {
+      // (the cache holds far more than a tile, and drains the device before it drops one)
+      FrameModTable *fm = ctx->get_frame_mod (k, payload_hex[p]);
+      if (!fm)
+        return false;
+      o.out = out_d[p];
+      o.frame_mod = fm->dev.as<int8_t>();
+      o.block_max = use_limiter ? reinterpret_cast<unsigned int *> (block_max + p * n_blocks) : nullptr;
+      return true;
+    },
+    [&] () { AWM_HIP_CHECK (awmk::launch_add_mix_multi (st, ctx->tabs, a)); return 0; },
+    [&] (size_t p0, size_t n) {
+      for (size_t p = p0; use_limiter && p < p0 + n; p++)
         {
-          FrameModTable *fm = ctx->get_frame_mod (k, payload_hex[p0 + i]);
-          if (!fm)
-            return AWM_ERR_ARG;
-          a.o[i].out = out_d[p0 + i];
-          a.o[i].frame_mod = fm->dev.as<int8_t>();
-          a.o[i].block_max = use_limiter ? reinterpret_cast<unsigned int *> (block_max + (p0 + i) * n_blocks) : nullptr;
+          ProfScope ps (ctx, PROF_LIMITER, double (n_frames) * n_channels * 8.0, st);
+          // (the outputs share the ramp table: the passes run in stream order, each rebuilds the entries)
+          AWM_HIP_CHECK (awmk::launch_limiter (st, out_d[p], (long long) n_frames, n_channels, 0, block_max + p * n_blocks, 0, (long long) n_blocks,
+                                               LIMITER_BLOCK, LIMITER_CEILING, ctx->ws_limit_tab.as<float2>(), tab_entries));
         }
-      for (size_t i = n; i < size_t (awmk::ADD_MULTI_TILE); i++)
-        a.o[i] = awmk::AddMixOut {};
-      a.n_out = int (n);
-      {
-        ProfScope ps (ctx, PROF_ADD_MIX_MULTI, double (1 + n) * double (n_frames) * n_channels * 4.0, st);     // the input once, every output once
-        AWM_HIP_CHECK (awmk::launch_add_mix_multi (st, ctx->tabs, a));
-      }
-      if (use_limiter)
-        for (size_t i = 0; i < n; i++)
-          {
-            ProfScope ps (ctx, PROF_LIMITER, double (n_frames) * n_channels * 8.0, st);
-            // (the outputs share the ramp table: the passes run in stream order, each rebuilds the entries)
-            AWM_HIP_CHECK (awmk::launch_limiter (st, out_d[p0 + i], (long long) n_frames, n_channels, 0, block_max + (p0 + i) * n_blocks, 0, (long long) n_blocks,
-                                                 LIMITER_BLOCK, LIMITER_CEILING, ctx->ws_limit_tab.as<float2>(), tab_entries));
-          }
-      p0 += n;
-    }
+      return 0;
+    });
+  if (rc)
+    return rc;
   g_add_payloads_fused_in_use = 1;
   return 0;
 }
@@ -1318,38 +1338,25 @@ add_mix_payloads_impl (awm_ctx *ctx, const float *pcm_in_d, float *const *out_d,
   a.pcm_in = pcm_in_d;
   a.n_frames = (long long) n_frames;
   a.n_channels = n_channels;
-  a.neg_delta_up = float (-water_delta * 1);             // as add_mix_impl
-  a.neg_delta_down = float (-water_delta * -1);
+  fill_add_mix_common (a, water_delta);
   a.n_blocks = (long long) n_blocks;
-  a.limiter_block = LIMITER_BLOCK;
-  a.block_frames = int (mark_block_frame_count());
-  a.frames_pad_start = int (Params::frames_pad_start);
   a.frames_per_span = frames_per_span (ctx, (long long) (n_frames + 1023) / 1024, awmk::add_mix_multi_span_waves_per_simd());
   awmk::AddMixSpan sp {};
   sp.first_frame = (long long) first_frame;
   sp.halo_before = halo_before_d;
   sp.halo_after = halo_after_d;
   sp.first_block = (long long) first_block;
-  const size_t n_passes = (n_payloads + awmk::ADD_MULTI_TILE - 1) / awmk::ADD_MULTI_TILE;
-  size_t p0 = 0;
-  for (size_t pass = 0; pass < n_passes; pass++)
-    {
-      const size_t n = n_payloads / n_passes + (pass < n_payloads % n_passes ? 1 : 0);
-      for (size_t i = 0; i < size_t (awmk::ADD_MULTI_TILE); i++)
-        {
-          a.o[i] = awmk::AddMixOut {};
-          if (i < n)
-            {
-              a.o[i].out = out_d[p0 + i];
-              a.o[i].frame_mod = frame_mod_dev[p0 + i];
-              a.o[i].block_max = block_max_d ? reinterpret_cast<unsigned int *> (block_max_d[p0 + i]) : nullptr;
-            }
-        }
-      a.n_out = int (n);
-      ProfScope ps (ctx, PROF_ADD_MIX_MULTI, double (1 + n) * double (n_frames) * n_channels * 4.0, st);     // the input once, every output once
-      AWM_HIP_CHECK (awmk::launch_add_mix_multi_span (st, ctx->tabs, a, sp));
-      p0 += n;
-    }
+  const int rc = add_mix_multi_passes (ctx, st, a, n_payloads,
+    [&] (size_t p, awmk::AddMixOut& o) {
+      o.out = out_d[p];
+      o.frame_mod = frame_mod_dev[p];
+      o.block_max = block_max_d ? reinterpret_cast<unsigned int *> (block_max_d[p]) : nullptr;
+      return true;
+    },
+    [&] () { AWM_HIP_CHECK (awmk::launch_add_mix_multi_span (st, ctx->tabs, a, sp)); return 0; },
+    [] (size_t, size_t) { return 0; });
+  if (rc)
+    return rc;
   g_add_payloads_fused_in_use = 1;
   return 0;
 }
@@ -1572,13 +1579,9 @@ add_batch_stage (awm_ctx *ctx, hipStream_t st, size_t n_clips, const float *cons
       a.n_frames = (long long) n_frames[i];
       a.n_channels = C;
       a.frame_mod = tables.size() == 1 ? tables[0] : tables[i];
-      a.neg_delta_up = float (-params().water_delta * 1);
-      a.neg_delta_down = float (-params().water_delta * -1);
+      fill_add_mix_common (a, params().water_delta);
       a.block_max = use_limiter ? reinterpret_cast<unsigned int *> (b.block_max + i * b.nb_max) : nullptr;
       a.n_blocks = (long long) (n_frames[i] / LIMITER_BLOCK + 2);
-      a.limiter_block = LIMITER_BLOCK;
-      a.block_frames = int (mark_block_frame_count());
-      a.frames_pad_start = int (Params::frames_pad_start);
       a.frames_per_span = b.L;
       h_mix[i] = a;
       h_lim[i] = { out_d[i], (long long) n_frames[i], b.block_max + i * b.nb_max, a.n_blocks, tabs + i * tab_max,
@@ -1833,15 +1836,11 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
       a.n_frames = (long long) g.len;
       a.n_channels = 2;
       a.frame_mod = ctx->ws_keytab.as<int8_t>() + (payload_of[i] % TABLE_GROUP) * table_stride;
-      a.neg_delta_up = float (-params().water_delta * 1);
-      a.neg_delta_down = float (-params().water_delta * -1);
+      fill_add_mix_common (a, params().water_delta);
       a.first_frame = (long long) (g.skipped / FRAME);
       a.block_max = use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr;
       a.first_block = (long long) g.first_block;
       a.n_blocks = (long long) g.n_blocks;
-      a.limiter_block = LIMITER_BLOCK;
-      a.block_frames = int (block_frames);
-      a.frames_pad_start = int (Params::frames_pad_start);
       a.frames_per_span = L;
       h_mix[i] = a;
       h_lim[i] = { out, (long long) g.len, block_max + g.max_off, (long long) g.n_blocks, tabs + g.tab_off, (long long) g.n_tab,

@@ -188,6 +188,39 @@ def test_spans_equal_one_launch(gpu, whole, name, ch, windows):
         same_bits(gpu.host(out), limited, f"limited spans {cuts}")
 
 
+@pytest.mark.parametrize("ch,pair", [(1, 1), (2, 1), (2, 0), (3, 1)], ids=["mono", "stereo_paired", "stereo_unpaired", "three_channels"])
+def test_span_with_a_block_in_front_of_its_maxima(gpu, ch, pair):
+    """every instantiation of K2 (a channel per wave; stereo with the paired and with the single transforms) on ONE span through
+    awm_add_mix_d: first_frame 3, both halos, first_block 1 -- the maximum of block 0 falls in front of the array and is dropped --, and
+    43 frames + 1000 samples: a ragged last frame, and the block boundary 44100 = frame 43 + 68 inside a frame (bounded stores, two running
+    maxima) and, one frame later, in front of that frame's tail.  The maxima against the numpy restatement on the returned mix, the mix
+    against the whole-stream launch over the enclosing stream (whose samples behind the ragged frame's 1000 are silence up to the halo)"""
+    t = gpu.torch
+    first, n = 3 * 1024, 43 * 1024 + 1000
+    end, halo = first + n, 47 * 1024
+    assert first < BS < end < halo and halo - end == 24
+    x = np.random.default_rng(40 + ch).uniform(-1, 1, (50 * 1024, ch)).astype(np.float32)
+    x[:BS] *= 1.5                         # block 0 is the louder one: its maximum stored at index 0 instead of dropped would show
+    x[BS:] *= 1.2
+    x[end:halo] = 0
+    xd = gpu.dev(x)
+    fm = gpu.awm.tab_frame_mod(None, PAY1)
+    out_whole, out = t.empty_like(xd), t.empty_like(xd[first:end])
+    bm = t.empty(2, dtype=t.float32, device="cuda")
+    gpu.ctx.add_init_block_max(bm)
+    gpu.awm.lib.awm_debug_set_fft_pair(pair)
+    try:
+        gpu.ctx.add_mix(xd, out_whole, fm, 0.01, 0, None, None, None)
+        gpu.ctx.add_mix(xd[first:end], out, fm, 0.01, 3, xd[first - 1024:first].contiguous(), xd[halo:halo + 1024].contiguous(), bm, first_block=1)
+        mix = gpu.host(out)
+        same_bits(mix, gpu.host(out_whole)[first:end], "mix of the span against the whole-stream launch")
+    finally:
+        gpu.awm.lib.awm_debug_set_fft_pair(1)
+    in_block_0, in_block_1 = lim.block_maxima(mix[:BS - first], BS), lim.block_maxima(mix[BS - first:], BS)
+    assert len(in_block_0) == len(in_block_1) == 1 and in_block_0[0] > in_block_1[0] > lim.CEILING
+    same_bits(bm.cpu().numpy(), np.array([in_block_1[0], lim.CEILING], np.float32), "block maxima from block 1 on")
+
+
 # ---- 3. K3 alone, with hand-made block maxima -------------------------------------------------------------------------------------
 # entries under the ceiling count as the ceiling; blocks 2 - 4 are under it: the ramp of block 3 is the identity (K3 skips its runs), those
 # of 2 and 4 are not; with the window that begins at block 2, blocks 0 - 3 are the identity
