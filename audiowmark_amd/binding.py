@@ -159,6 +159,8 @@ lib.awm_add_watermark_file.argtypes = [_vp, _vp, C.c_char_p, C.c_char_p, C.c_cha
 lib.awm_add_stream_watermark_file.argtypes = [_vp, _vp, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(RawFormat), C.POINTER(RawFormat), C.c_size_t]
 lib.awm_add_stream_create_at.argtypes = [_vp, _vp, C.c_char_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(_vp)]
 lib.awm_debug_sync_db_sliding_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, _vp]
+lib.awm_debug_sync_db_sliding_rows_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, C.c_longlong, C.c_longlong,
+                                                 _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_longlong, _vp, C.c_longlong]
 lib.awm_get_watermark_file.argtypes = [_vp, _vp, C.c_char_p, C.POINTER(RawFormat), C.c_size_t, _vp]
 lib.awm_add_get_watermark_file.argtypes = [_vp, _vp, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(RawFormat), C.POINTER(RawFormat), C.c_size_t, _vp]
 lib.awm_add_stream_create.argtypes = [_vp, _vp, C.c_char_p, C.c_int, C.c_size_t, C.POINTER(_vp)]
@@ -774,6 +776,28 @@ class Context:
                "awm_debug_sync_db_sliding_d")
         self.synchronize()
         return out
+
+    def sync_db_sliding_rows(self, pcm, n_frames, bases, counts, count0, rows_per_plane, row_perm, band_pos, first, last, out, have,
+                             tail=None, stream_range=None, range_index=None, range_div=1, tables_per_slice=0):
+        """K4s alone as the refinement launches it (awm_debug_sync_db_sliding_rows_d): the gathered layout, every table and every buffer the
+        caller's own CUDA tensor.  pcm [>= n_frames][channels] float32, bases int64 / counts int32 [n_streams], row_perm int32 and band_pos
+        uint8 [slices][rows_per_plane]([81]), out float32 [slots][60][ld], have int8 [slots][stride], tail float32 [slots][stride] or None,
+        stream_range int64 [slices][2] and range_index int32 or None.  Writes out / have / tail in place."""
+        import torch
+        n, ch = _pcm_shape(pcm)
+        assert 0 <= n_frames <= n
+        want = ((bases, torch.int64, 1), (counts, torch.int32, 1), (row_perm, torch.int32, 0), (band_pos, torch.uint8, 0), (out, torch.float32, 3),
+                (have, torch.int8, 2), (tail, torch.float32, 2), (stream_range, torch.int64, 2), (range_index, torch.int32, 1))
+        for t, dtype, dim in want:
+            assert t is None or (t.dtype == dtype and t.is_cuda and t.is_contiguous() and (not dim or t.dim() == dim))
+        assert bases.numel() == counts.numel() and out.shape[1] == 60 and out.shape[0] == have.shape[0] and (tail is None or tail.shape[0] == out.shape[0])
+        opt = lambda t: _dev_ptr(t) if t is not None else None
+        _check(lib.awm_debug_sync_db_sliding_rows_d(self._h, _dev_ptr(pcm), n_frames, ch, _dev_ptr(bases), _dev_ptr(counts), bases.numel(), count0,
+                                                    rows_per_plane, _dev_ptr(row_perm), _dev_ptr(band_pos), first, last, opt(stream_range),
+                                                    opt(range_index), range_div, tables_per_slice, out.shape[2], _dev_ptr(out), opt(tail),
+                                                    tail.shape[1] if tail is not None else 0, _dev_ptr(have), have.shape[1]),
+               "awm_debug_sync_db_sliding_rows_d")
+        self.synchronize()
 
     def add_watermark_tiles(self, key, payload_hex, pcm, tile_frames1024=128, zero_frames=0):
         """awm_add_stream: `add` as a tile loop over resident PCM (the bounded-memory form the file path uses); returns the

@@ -2557,7 +2557,10 @@ sync_db_sliding3_kernel (DevTables t, SyncDbArgs a)
  *     every 32 offsets and writes 16 bytes per lane: eight lanes complete a line, an instruction eight rows; offset 64 (a candidate
  *     has 65) goes to a compact array of its own (`tail`: 60 floats per stream, one coalesced store), which K5g's tail wave reads.
  * U32 = false: every floating point operation and its order is the old kernel's: the values are BIT-IDENTICAL (pinned by
- * tests/test_gpu_parity.py::test_refinement_kernel_forms).
+ * tests/test_gpu_parity.py::test_refinement_kernel_forms in the bands layout and by tests/test_gpu_sliding_edges.py in the gathered
+ * one), and they are the float64 transform's: tests/test_gpu_sliding_edges.py holds every value, have flag and untouched cell of
+ * this kernel (gathered, ld = 64 + tail, through awm_debug_sync_db_sliding_rows_d) and of sync_db_sliding_kernel<1> to
+ * tests/_sliding.py::ref_db at a tolerance derived per value.
  * U32 = true: the update term U[k] = sum_j d[j] W^{jk} -- 16 of the 19 double precision operations per bin and offset -- is
  * accumulated in FLOAT (d = x[s + N + j] - x[s + j] rounded to float, rotation folded into the table: T_j = W^{jk} rho_k as
  * float2), converted once and added to R rho in double: R' = R rho + U'.  The state R itself, the recurrence and the Hann combination
@@ -2960,7 +2963,7 @@ sync_db_sliding4_body (const DevTables& t, const SyncDbArgs& a)
     a.have[out_slot * a.have_stream_stride + 64] = have_64;
 }
 
-// (gathered: 60 rows; rows = the 81 bands: awm_debug_sync_db_sliding_d and nothing else)
+// (gathered: 60 rows -- the refinement and awm_debug_sync_db_sliding_rows_d; rows = the 81 bands: awm_debug_sync_db_sliding_d and nothing else)
 __global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (3, 3)))
 sync_db_sliding4_kernel (DevTables t, SyncDbArgs a)
 {

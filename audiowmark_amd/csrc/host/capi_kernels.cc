@@ -1005,6 +1005,83 @@ awm_debug_sync_db_sliding_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, 
 }
 
 int
+awm_debug_sync_db_sliding_rows_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channels, const long long *base_d, const int *count_d,
+                                  size_t n_streams, int count0, int rows_per_plane, const int *row_perm_d, const unsigned char *band_pos_d,
+                                  long long first, long long last, const long long *stream_range_d, const int *range_index_d, int range_div,
+                                  int tables_per_slice, int ld, float *out_d, float *tail_d, long long tail_stream_stride, char *have_d,
+                                  long long have_stream_stride)
+{
+  AWM_ENTER (ctx);
+  const char *bad = nullptr;
+  if (!pcm_d || !base_d || !count_d || !row_perm_d || !band_pos_d || !out_d || !have_d)
+    bad = "null pointer";
+  else if (n_channels != 1 && n_channels != 2)
+    bad = "1 or 2 channels";
+  else if (count0 < 0 || count0 > 65 || have_stream_stride < count0)
+    bad = "count0 within 0 .. 65 and within a stream's have flags";
+  else if (rows_per_plane < 1 || range_div < 1 || (tables_per_slice != 0 && tables_per_slice != 1))
+    bad = "rows_per_plane, range_div or tables_per_slice";
+  else if (tail_d && (!awmk::sliding_rows_have_tail (n_channels) || tail_stream_stride < 60))
+    bad = "only forms 4 / 5 write a tail (stereo), 60 values per stream";
+  else if (ld < std::min (count0, tail_d ? 64 : 65))
+    bad = "ld below the offsets of a row (64 only with a tail)";
+  if (!bad && n_streams)
+    {
+      // what the kernels take on trust from the refinement (syncfinder.cc:520-551): counts within count0, every window inside the stream
+      std::vector<long long> base (n_streams);
+      std::vector<int> count (n_streams);
+      AWM_HIP_CHECK (hipMemcpyAsync (base.data(), base_d, n_streams * sizeof (long long), hipMemcpyDeviceToHost, ctx->stream));
+      AWM_HIP_CHECK (hipMemcpyAsync (count.data(), count_d, n_streams * sizeof (int), hipMemcpyDeviceToHost, ctx->stream));
+      AWM_HIP_CHECK (hipStreamSynchronize (ctx->stream));
+      for (size_t s = 0; s < n_streams && !bad; s++)
+        {
+          if (count[s] < 0 || count[s] > count0)
+            bad = "a stream's count outside 0 .. count0";
+          else if (count[s] && (base[s] < 0 || base[s] + 8LL * (count[s] - 1) + (long long) Params::frame_size > (long long) n_frames))
+            bad = "a stream's windows outside the samples";
+        }
+    }
+  if (bad)
+    {
+      set_error (std::string ("awm_debug_sync_db_sliding_rows_d: ") + bad);
+      return AWM_ERR_ARG;
+    }
+  // (the fields and their order: SyncFinder's refinement, syncfinder.cc "K4s: sliding DFT over the fine offsets")
+  awmk::SyncDbArgs da {};
+  da.pcm = pcm_d;
+  da.n_frames = (long long) n_frames;
+  da.n_channels = n_channels;
+  da.per_channel = 0;
+  da.stream_base = base_d;
+  da.stream_count = count_d;
+  da.count0 = count0;
+  da.n_streams = (long long) n_streams;
+  da.hop = Params::sync_search_fine;
+  da.out = out_d;
+  da.out_stream_stride = 60LL * ld;
+  da.row_perm = row_perm_d;
+  da.band_pos = band_pos_d;
+  da.rows_per_plane = rows_per_plane;
+  da.ld = ld;
+  da.tail = tail_d;
+  da.tail_stream_stride = tail_stream_stride;
+  da.have = have_d;
+  da.have_stream_stride = have_stream_stride;
+  da.first = first;
+  da.last = last;
+  if (stream_range_d || tables_per_slice)
+    {
+      da.stream_range = stream_range_d;
+      da.range_index = range_index_d;
+      da.range_div = range_div;
+      da.tables_per_slice = tables_per_slice;
+    }
+  da.tile_frames = ld;
+  AWM_HIP_CHECK (awmk::launch_sync_db_sliding (ctx->stream, ctx->tabs, da));
+  return 0;
+}
+
+int
 awm_sync_fft_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channels, size_t index, size_t frame_count,
                 const char *want_frames, size_t first, size_t last, float *db_out_d, char *have_out_d)
 {

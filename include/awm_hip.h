@@ -543,6 +543,19 @@ void awm_debug_set_k4s_ablate (int flags);     /* measurement only (tools/gpu_k4
  * forms 4 / 5 the 65th values at out_d + n_streams * 60 * 64 (n_streams * 60 floats more). */
 int  awm_debug_sync_db_sliding_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channels, const long long *base_d, size_t n_streams,
                                   int count, int ld, float *out_d);
+/* K4s alone as the refinement launches it (tests only): the gathered layout with every table from the caller, all of them device pointers.
+ * Stream s = plane * rows_per_plane + w has count_d[s] (0 .. count0 <= 65) windows from base_d[s] + 8 o and writes band b of offset o to
+ *   out_d[(slot * 60 + band_pos_d[(slice * rows_per_plane + w) * 81 + b]) * ld + o]   (255: the band is dropped),
+ *   slot = plane * rows_per_plane + row_perm_d[slice * rows_per_plane + w],  have_d[slot * have_stream_stride + o] = the offset was transformed,
+ * and with tail_d (forms 4 / 5, stereo) offset 64 to tail_d[slot * tail_stream_stride + row] instead, so that ld may be 64.
+ * [first, last) is the non-silent value range of the skip rules; stream_range_d (optional, [slices][2]) replaces it per stream by the range
+ * of slice range_index_d[s / range_div] (s / range_div without range_index_d; first < 0: nothing but silence), and with tables_per_slice = 1
+ * row_perm_d / band_pos_d hold one table per slice (slice = 0 otherwise).  Counts and windows are checked on the host (one synchronisation). */
+int  awm_debug_sync_db_sliding_rows_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channels, const long long *base_d, const int *count_d,
+                                       size_t n_streams, int count0, int rows_per_plane, const int *row_perm_d, const unsigned char *band_pos_d,
+                                       long long first, long long last, const long long *stream_range_d, const int *range_index_d, int range_div,
+                                       int tables_per_slice, int ld, float *out_d, float *tail_d, long long tail_stream_stride, char *have_d,
+                                       long long have_stream_stride);
 void awm_debug_set_soft_bits_generic (int on); /* K7: one thread per soft bit for every shape (the fallback kernel) | four bits per wave */
 void awm_debug_set_scan_generic (int on);      /* K5w: 1 the approximate search takes launch_sync_scan_window's fallback, the generic K5 (scores identical) | 0 (default) the streaming kernel */
 int  awm_debug_scan_generic_launches (void);   /* K5w: how often launch_sync_scan_window has taken that fallback in this process, by the switch or by its own conditions */
