@@ -130,8 +130,21 @@ lib.awm_debug_add_payloads_tile.argtypes = []
 lib.awm_debug_add_payloads_tile.restype = C.c_int
 lib.awm_add_watermark_batch_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
 lib.awm_add_watermark_segments_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int]
+lib.awm_add_watermark_segments_rate_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
+
+
+class SegmentPlan(C.Structure):
+    """awm_segment_plan (include/awm_hip.h): the window of one stream segment at another sample rate"""
+    _fields_ = [(n, C.c_uint64) for n in ("mix_first", "frame_first", "frame_last", "slice_first", "slice_last", "down_first", "down_last",
+                                          "in_first", "in_last", "limiter_block", "first_block", "n_blocks")] + \
+               [(n, C.c_int) for n in ("down_hl", "down_np", "down_step", "up_hl", "up_np", "up_step")]
+
+
+lib.awm_add_segment_plan.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(SegmentPlan)]
 lib.awm_debug_add_segments_fused_in_use.argtypes = []
 lib.awm_debug_add_segments_fused_in_use.restype = C.c_int
+lib.awm_debug_alloc_bytes.argtypes = []
+lib.awm_debug_alloc_bytes.restype = C.c_ulonglong
 lib.awm_debug_payload_tables_d.argtypes = [_vp, _vp, _vp, C.c_size_t, _vp]
 lib.awm_get_watermark_batch_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
 lib.awm_add_watermark_batch_keys_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
@@ -388,6 +401,13 @@ def add_segments_fused_in_use():
     return lib.awm_debug_add_segments_fused_in_use()
 
 
+def add_segment_plan(sample_rate, zero_frames, n_frames):
+    """awm_add_segment_plan: the window of one stream segment at another sample rate, as a dict of the struct's fields (no GPU needed)"""
+    plan = SegmentPlan()
+    _check(lib.awm_add_segment_plan(int(sample_rate), int(zero_frames), int(n_frames), C.byref(plan)), "awm_add_segment_plan")
+    return {name: int(getattr(plan, name)) for name, _ in SegmentPlan._fields_}
+
+
 def tab_sync_bits(key, clip_mode=False):
     rows = 170 if clip_mode else 85
     out = np.zeros((6, rows, 61), np.int32)
@@ -633,10 +653,12 @@ class Context:
                "awm_add_watermark_batch_d")
         return outs
 
-    def add_watermark_segments(self, key, payloads, segments, zero_frames, outs=None):
-        """awm_add_watermark_segments_d: a batch of stream segments (resident, 44.1 kHz, one channel count) with one key, segment i with
-        payloads[i] and starting zero_frames[i] samples into its stream; outs[i] == add_watermark_tiles(key, payloads[i], segments[i],
-        zero_frames=zero_frames[i]) bit for bit.  Segments may be one tensor many times (one programme, many subscribers)."""
+    def add_watermark_segments(self, key, payloads, segments, zero_frames, outs=None, sample_rate=44100):
+        """awm_add_watermark_segments_d: a batch of stream segments (resident, at sample_rate, one channel count) with one key, segment i with
+        payloads[i] and starting zero_frames[i] samples into its stream; at 44.1 kHz outs[i] == add_watermark_tiles(key, payloads[i],
+        segments[i], zero_frames=zero_frames[i]) bit for bit.  Segments may be one tensor many times (one programme, many subscribers).
+        Another sample_rate: awm_add_watermark_segments_rate_d; outs[i] == add_watermark(key, payloads[i], zero_frames[i] zeros + segments[i],
+        sample_rate)[zero_frames[i]:] bit for bit, computed from a window around the segment."""
         import torch
         payloads, segments, zero_frames = list(payloads), list(segments), list(zero_frames)
         if not (len(payloads) == len(segments) == len(zero_frames)):
@@ -657,6 +679,10 @@ class Context:
         src = (C.c_void_p * n)(*[_dev_ptr(s) for s in segments])
         dst = (C.c_void_p * n)(*[_dev_ptr(o) for o in outs])
         frames = (C.c_size_t * n)(*[s[0] for s in shapes])
+        if sample_rate != 44100:
+            _check(lib.awm_add_watermark_segments_rate_d(self._h, key_bytes(key), n, hexes, zf, src, dst, frames, ch, sample_rate),
+                   "awm_add_watermark_segments_rate_d")
+            return outs
         _check(lib.awm_add_watermark_segments_d(self._h, key_bytes(key), n, hexes, zf, src, dst, frames, ch), "awm_add_watermark_segments_d")
         return outs
 

@@ -142,10 +142,40 @@ struct ResampleArgs
   long long    n_out;       // frames to produce
 };
 hipError_t launch_resample (hipStream_t st, const ResampleArgs& a);
+/* K10w: K10 for WINDOWS of streams, a batch of them in one launch (blockIdx.y = slice, its arguments from an array on the device).  A slice
+ * is a run of outputs of one stream and the part of that stream's input that is resident: output out0 + k (k < n_out) goes to out[k], input
+ * frame j of the stream is in[j - in0] for in0 <= j < in0 + n_in and reads as zero everywhere else.  Window start, phase, products and sums
+ * are K10's for the GLOBAL output index (m step in 64 bits: m < 2^41 and step <= 16000, see awm_add_segment_plan); ctab / hl / np / step /
+ * n_channels come from `a`, whose in / out fields are not read.  Stereo with every pointer 8-byte aligned (stereo_aligned) stages the
+ * tile's window in LDS like K10; everything else takes the generic taps. */
+struct ResampleSlice
+{
+  const float *in;
+  long long    n_in, in0;
+  long long    out0, n_out;
+  float       *out;
+};
+hipError_t launch_resample_slices (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, int n_slices, long long max_n_out,
+                                   bool stereo_aligned);
+hipError_t launch_resample_slice (hipStream_t st, const ResampleArgs& a, const ResampleSlice& slice);     // one slice, arguments by value
 
 /* K11: out = wm + orig (reference wmadd.cc:564-565) and the per-limiter-block maxima of the result (limiter.cc:90-97) */
 hipError_t launch_mix_max (hipStream_t st, const float *orig, const float *wm, float *out, long long n_frames, int n_channels,
                            unsigned int *block_max, long long n_blocks, int limiter_block);
+/* K11 for a batch of stream segments (blockIdx.y = segment): out[0 .. n_frames) = wm[pre ..] + orig, where orig[0] / out[0] are sample
+ * first_sample of the segment's stream and wm[0] is sample first_sample - pre of the watermark signal.  The `pre` samples in front are
+ * watermark alone (the stream is silent there): nothing is stored for them, but they count for the block maxima like the rest.
+ * block_max[0] belongs to limiter block first_block (nullptr: no maxima). */
+struct MixSegment
+{
+  const float  *orig, *wm;
+  float        *out;
+  long long     n_frames, pre, first_sample;
+  unsigned int *block_max;
+  long long     first_block, n_blocks;
+};
+hipError_t launch_mix_max_segments (hipStream_t st, const MixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int limiter_block);
+hipError_t launch_mix_max_segment (hipStream_t st, const MixSegment& seg, int n_channels, int limiter_block);   // one segment, arguments by value
 
 /* `add --snr`: acc[0] += sum (mixed - orig)^2, acc[1] += sum orig^2 in double (reference wmadd.cc:553-563) */
 hipError_t launch_power_sums (hipStream_t st, const float *orig, const float *mixed, long long n_values, double *acc);

@@ -1328,9 +1328,10 @@ resample_output_staged (const ResampleArgs& a, const float *tab, int stride, lon
   reinterpret_cast<float2 *> (a.out)[m] = make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f));
 }
 
-// one output frame m; tab: coefficient rows with `stride` floats each (LDS or global)
+// one output frame m; tab: coefficient rows with `stride` floats each (LDS or global).  K10w: a.in[0] is input frame in0 of the stream
+// (a.n_in frames from there, zeros everywhere else) and the result goes to a.out[k]
 template<int CT> __device__ __forceinline__ void
-resample_output (const ResampleArgs& a, const float *tab, int stride, long long m)
+resample_output (const ResampleArgs& a, const float *tab, int stride, long long m, long long in0, long long k)
 {
   const int C = CT ? CT : a.n_channels, hl = a.hl;
   const long long t = m * a.step;
@@ -1338,7 +1339,7 @@ resample_output (const ResampleArgs& a, const float *tab, int stride, long long 
   const int ph = int (t - b * a.np);
   const float *c1 = tab + stride * ph;
   const float *c2 = tab + stride * (a.np - ph);
-  const long long first = b - (hl - 1);                       // input frame of P[b]
+  const long long first = b - (hl - 1) - in0;                 // input frame of P[b], from a.in[0]
   if (CT == 2)
     {
       const float2 *in2 = reinterpret_cast<const float2 *> (a.in);
@@ -1363,7 +1364,7 @@ resample_output (const ResampleArgs& a, const float *tab, int stride, long long 
             s0 = __fadd_rn (s0, __fadd_rn (__fmul_rn (x1.x, c1[i]), __fmul_rn (x2.x, c2[i])));
             s1 = __fadd_rn (s1, __fadd_rn (__fmul_rn (x1.y, c1[i]), __fmul_rn (x2.y, c2[i])));
           }
-      reinterpret_cast<float2 *> (a.out)[m] = make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f));
+      reinterpret_cast<float2 *> (a.out)[k] = make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f));
       return;
     }
   for (int c = 0; c < C; c++)
@@ -1376,8 +1377,13 @@ resample_output (const ResampleArgs& a, const float *tab, int stride, long long 
           const float x2 = (j2 >= 0 && j2 < a.n_in) ? a.in[j2 * C + c] : 0.f;
           sum = __fadd_rn (sum, __fadd_rn (__fmul_rn (x1, c1[i]), __fmul_rn (x2, c2[i])));
         }
-      a.out[m * C + c] = __fsub_rn (sum, 1e-20f);
+      a.out[k * C + c] = __fsub_rn (sum, 1e-20f);
     }
+}
+template<int CT> __device__ __forceinline__ void
+resample_output (const ResampleArgs& a, const float *tab, int stride, long long m)
+{
+  resample_output<CT> (a, tab, stride, m, 0, m);
 }
 
 /* Neighbouring outputs use different phases, i.e. different coefficient rows: read from global memory every load
@@ -1564,6 +1570,125 @@ launch_resample (hipStream_t st, const ResampleArgs& a)
   return hipGetLastError();
 }
 
+/* K10w (kernels.hh ResampleSlice): resample_kernel for windows of streams.  Like K10 a workgroup stages the coefficient table once and
+ * keeps it for `tiles_per_wg` consecutive tiles of RS_TILE outputs of its slice (staging the table costs as much as the taps of one tile);
+ * window start and phase come from each tile's first GLOBAL output index, the staged window is filled from the slice's resident input
+ * and zeros.  The taps are resample_output_staged / resample_output themselves. */
+template<int CT> __device__ __forceinline__ void
+resample_slice_body (const ResampleArgs& a0, const ResampleSlice& s, int lds_floats, int in_span, int tiles_per_wg)
+{
+  extern __shared__ float s_tab[];
+  if ((long long) blockIdx.x * tiles_per_wg * RS_TILE >= s.n_out)
+    return;                                                                    // (uniform: a shorter slice of the batch)
+  ResampleArgs a = a0;
+  a.in = s.in;
+  a.n_in = s.n_in;
+  a.out = s.out;
+  const int stride = a.hl | 1;
+  const bool in_lds = lds_floats > 0;
+  const bool staged = CT == 2 && in_lds && in_span > 0;
+  float2 *s_in = reinterpret_cast<float2 *> (s_tab + ((lds_floats + 1) & ~1));
+  if (in_lds)
+    {
+      const int n = (a.np + 1) * a.hl;
+      for (int i = threadIdx.x; i < n; i += 256)
+        {
+          const int r = i / a.hl;
+          s_tab[r * stride + (i - r * a.hl)] = a.ctab[i];
+        }
+    }
+  for (int t = 0; t < tiles_per_wg; t++)
+    {
+      const long long tile0 = ((long long) blockIdx.x * tiles_per_wg + t) * RS_TILE;
+      if (tile0 >= s.n_out)
+        break;                                                                 // (uniform)
+      const long long g0 = s.out0 + tile0;                                     // the tile's first output in the stream
+      const long long b0 = (g0 * a.step) / a.np;
+      const unsigned int r0 = (unsigned int) (g0 * a.step - b0 * a.np);
+      if (staged)
+        {
+          if (t)
+            __syncthreads();                                                   // the previous tile's windows have been read
+          const long long first0 = b0 - (a.hl - 1) - s.in0;                    // s_in[0], counted from s.in[0]
+          const float2 *in2 = reinterpret_cast<const float2 *> (s.in);
+          for (int i = threadIdx.x; i < in_span; i += 256)
+            {
+              const long long j = first0 + i;
+              s_in[i] = (j >= 0 && j < s.n_in) ? in2[j] : make_float2 (0.f, 0.f);
+            }
+        }
+      if (in_lds && (staged || t == 0))
+        __syncthreads();
+      for (int q = 0; q < RS_TILE / 256; q++)
+        {
+          const long long k = tile0 + q * 256 + threadIdx.x;
+          if (k >= s.n_out)
+            break;
+          if (staged)
+            resample_output_staged (a, s_tab, stride, k, s_in, r0 + (unsigned int) (q * 256 + threadIdx.x) * (unsigned int) a.step);
+          else if (in_lds)
+            resample_output<CT> (a, s_tab, stride, s.out0 + k, s.in0, k);
+          else
+            resample_output<CT> (a, a.ctab, a.hl, s.out0 + k, s.in0, k);
+        }
+    }
+}
+template<int CT> __global__ void __launch_bounds__ (256)
+resample_slices_kernel (ResampleArgs a, const ResampleSlice *slices, int lds_floats, int in_span, int tiles_per_wg)
+{
+  const ResampleSlice s = slices[blockIdx.y];
+  resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg);
+}
+template<int CT> __global__ void __launch_bounds__ (256)
+resample_slice_kernel (ResampleArgs a, ResampleSlice s, int lds_floats, int in_span, int tiles_per_wg)
+{
+  resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg);
+}
+
+static hipError_t
+launch_resample_slices_any (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, const ResampleSlice *one, int n_slices,
+                            long long max_n_out, bool stereo_aligned)
+{
+  if (n_slices <= 0 || max_n_out <= 0)
+    return hipSuccess;
+  if (n_slices > 65535 || a.hl < 1 || a.np < 1 || a.step < 1 || a.n_channels < 1)
+    return hipErrorInvalidValue;
+  // as in launch_resample: at least 4096 workgroups first (here over all slices), then up to 8 tiles per workgroup and table
+  const long long n_tiles = (max_n_out + RS_TILE - 1) / RS_TILE;
+  const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_slices / 4096)));
+  const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg), unsigned (n_slices));
+  // the table and the tile's window in LDS exactly as launch_resample sizes them
+  const int want = (a.np + 1) * (a.hl | 1);
+  const int lds_floats = want <= RS_MAX_TAB ? want : 0;
+  const long long span = ((long long) (RS_TILE - 1) * a.step) / a.np + 2 + 2LL * a.hl;
+  const bool stereo = a.n_channels == 2 && stereo_aligned;
+  const bool stage = stereo && lds_floats > 0 && span <= 4096 && (long long) RS_TILE * a.step + a.np < (1LL << 31);
+  const int in_span = stage ? int (span) : 0;
+  const size_t lds_bytes = size_t ((lds_floats + 1) & ~1) * sizeof (float) + size_t (in_span) * sizeof (float2);
+  if (one && stereo)
+    hipLaunchKernelGGL (resample_slice_kernel<2>, grid, dim3 (256), lds_bytes, st, a, *one, lds_floats, in_span, tiles_per_wg);
+  else if (one)
+    hipLaunchKernelGGL (resample_slice_kernel<0>, grid, dim3 (256), lds_bytes, st, a, *one, lds_floats, in_span, tiles_per_wg);
+  else if (stereo)
+    hipLaunchKernelGGL (resample_slices_kernel<2>, grid, dim3 (256), lds_bytes, st, a, slices_dev, lds_floats, in_span, tiles_per_wg);
+  else
+    hipLaunchKernelGGL (resample_slices_kernel<0>, grid, dim3 (256), lds_bytes, st, a, slices_dev, lds_floats, in_span, tiles_per_wg);
+  return hipGetLastError();
+}
+hipError_t
+launch_resample_slices (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, int n_slices, long long max_n_out, bool stereo_aligned)
+{
+  return launch_resample_slices_any (st, a, slices_dev, nullptr, n_slices, max_n_out, stereo_aligned);
+}
+hipError_t
+launch_resample_slice (hipStream_t st, const ResampleArgs& a, const ResampleSlice& slice)
+{
+  if (slice.n_in < 0 || slice.in0 < 0 || slice.out0 < 0)
+    return hipErrorInvalidValue;
+  const bool aligned = (reinterpret_cast<uintptr_t> (slice.in) & 7) == 0 && (reinterpret_cast<uintptr_t> (slice.out) & 7) == 0;
+  return launch_resample_slices_any (st, a, nullptr, &slice, 1, slice.n_out, aligned);
+}
+
 constexpr int MIX_RUN = 2048;            // values per thread group run: 256 threads x 8
 
 /* `add --snr` (reference wmadd.cc:553-563): power of the input and of (mix - input) BEFORE the limiter, in double like the
@@ -1658,6 +1783,90 @@ launch_mix_max (hipStream_t st, const float *orig, const float *wm, float *out, 
     return hipErrorInvalidValue;                               // a run may only straddle one block boundary
   hipLaunchKernelGGL (mix_max_kernel, dim3 (unsigned ((n_values + MIX_RUN - 1) / MIX_RUN)), dim3 (256), 0, st, orig, wm, out, n_values,
                       n_channels, block_max, n_blocks, limiter_block);
+  return hipGetLastError();
+}
+
+/* K11 for stream segments (kernels.hh MixSegment): mix_max_kernel with the segment's place in its stream -- the limiter block of a value
+ * comes from first_sample - pre + its frame, the maxima go to block_max[block - first_block] -- and `pre` frames of watermark alone in front */
+__device__ __forceinline__ void
+mix_max_segment_body (const MixSegment& s, int C, int BS)
+{
+  __shared__ float s_m0[4], s_m1[4];
+  const long long n_values = (s.pre + s.n_frames) * C, pre_values = s.pre * C;
+  const long long base = (long long) blockIdx.x * MIX_RUN;
+  if (base >= n_values)
+    return;                                                   // (uniform)
+  const long long start = s.first_sample - s.pre;             // sample of the stream that wm[0] belongs to
+  const long long b0 = (start + base / C) / BS;
+  const long long bound = ((b0 + 1) * BS - start) * C;        // first value of the next limiter block
+  float m0 = 0.f, m1 = 0.f;
+  for (int j = 0; j < MIX_RUN / 256; j++)
+    {
+      const long long v = base + threadIdx.x + 256LL * j;
+      if (v < n_values)
+        {
+          float r = s.wm[v];
+          if (v >= pre_values)
+            {
+              r = __fadd_rn (r, s.orig[v - pre_values]);
+              s.out[v - pre_values] = r;
+            }
+          if (v < bound)
+            m0 = fmaxf (m0, fabsf (r));
+          else
+            m1 = fmaxf (m1, fabsf (r));
+        }
+    }
+  m0 = wave_max (m0);
+  m1 = wave_max (m1);
+  if ((threadIdx.x & 63) == 0)
+    {
+      s_m0[threadIdx.x >> 6] = m0;
+      s_m1[threadIdx.x >> 6] = m1;
+    }
+  __syncthreads();
+  if (threadIdx.x == 0 && s.block_max)
+    {
+      m0 = fmaxf (fmaxf (s_m0[0], s_m0[1]), fmaxf (s_m0[2], s_m0[3]));
+      m1 = fmaxf (fmaxf (s_m1[0], s_m1[1]), fmaxf (s_m1[2], s_m1[3]));
+      const long long i0 = b0 - s.first_block, i1 = i0 + 1;
+      if (i0 >= 0 && i0 < s.n_blocks && m0 > 0.f) atomicMax (s.block_max + i0, __float_as_uint (m0));
+      if (i1 >= 0 && i1 < s.n_blocks && m1 > 0.f) atomicMax (s.block_max + i1, __float_as_uint (m1));
+    }
+}
+__global__ void __launch_bounds__ (256)
+mix_max_segments_kernel (const MixSegment *segs, int C, int BS)
+{
+  const MixSegment s = segs[blockIdx.y];
+  mix_max_segment_body (s, C, BS);
+}
+__global__ void __launch_bounds__ (256)
+mix_max_segment_kernel (MixSegment s, int C, int BS)
+{
+  mix_max_segment_body (s, C, BS);
+}
+
+hipError_t
+launch_mix_max_segments (hipStream_t st, const MixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int limiter_block)
+{
+  if (n_segs <= 0 || max_frames <= 0)
+    return hipSuccess;
+  if (n_segs > 65535 || n_channels < 1 || (long long) limiter_block * n_channels < MIX_RUN)
+    return hipErrorInvalidValue;                               // a run may only straddle one block boundary
+  const long long max_values = max_frames * n_channels;
+  hipLaunchKernelGGL (mix_max_segments_kernel, dim3 (unsigned ((max_values + MIX_RUN - 1) / MIX_RUN), unsigned (n_segs)), dim3 (256), 0, st,
+                      segs_dev, n_channels, limiter_block);
+  return hipGetLastError();
+}
+hipError_t
+launch_mix_max_segment (hipStream_t st, const MixSegment& seg, int n_channels, int limiter_block)
+{
+  const long long n_values = (seg.pre + seg.n_frames) * n_channels;
+  if (n_values <= 0)
+    return hipSuccess;
+  if (n_channels < 1 || seg.pre < 0 || seg.first_sample < seg.pre || (long long) limiter_block * n_channels < MIX_RUN)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL (mix_max_segment_kernel, dim3 (unsigned ((n_values + MIX_RUN - 1) / MIX_RUN)), dim3 (256), 0, st, seg, n_channels, limiter_block);
   return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include <atomic>
 #include <future>
 #include <thread>
+#include <tuple>
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1982,22 +1983,21 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
   return 0;
 }
 
-int
-awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
-                              const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels)
+/* what both segment entry points check before anything is enqueued (fn: the entry point, for the messages), and the distinct payloads'
+ * codes: payload_index[i] = index of segment i's payload among the distinct ones, coded = [distinct][2 (A, B)][n_code] bytes */
+static int
+segments_check (awm_ctx *ctx, const char *fn, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, std::vector<size_t>& payload_index,
+                std::vector<unsigned char>& coded, size_t& n_code)
 {
-  AWM_ENTER (ctx);
-  g_add_segments_fused_in_use = 0;
-  if (!n_segments)
-    return 0;
   if (!key || !payload_hex || !zero_frames || !pcm_in_d || !out_d || !n_frames || n_channels < 1)
     {
-      set_error ("awm_add_watermark_segments_d: bad argument");
+      set_error (string_printf ("%s: bad argument", fn));
       return AWM_ERR_ARG;
     }
   if (ctx->snr_on)
     {
-      set_error ("awm_add_watermark_segments_d: not available while the SNR meter is armed (awm_ctx_snr_begin)");
+      set_error (string_printf ("%s: not available while the SNR meter is armed (awm_ctx_snr_begin)", fn));
       return AWM_ERR_ARG;
     }
   // everything is checked before anything is enqueued
@@ -2005,14 +2005,14 @@ awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segm
   for (size_t i = 0; i < n_segments; i++)
     if (!payload_hex[i] || (n_frames[i] && (!pcm_in_d[i] || !out_d[i])))
       {
-        set_error (string_printf ("awm_add_watermark_segments_d: null pointer at index %zu", i));
+        set_error (string_printf ("%s: null pointer at index %zu", fn, i));
         return AWM_ERR_ARG;
       }
   // the distinct payloads in order of appearance: parse_payload + code_encode (A and B) is all the host does per payload
-  const size_t n_code = code_size (ConvBlockType::a, params().payload_size);
+  n_code = code_size (ConvBlockType::a, params().payload_size);
   std::map<std::string, size_t> distinct;
-  std::vector<size_t> payload_index (n_segments);
-  std::vector<unsigned char> coded;
+  payload_index.assign (n_segments, 0);
+  coded.clear();
   for (size_t i = 0; i < n_segments; i++)
     {
       auto it = distinct.find (payload_hex[i]);
@@ -2021,7 +2021,7 @@ awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segm
           const std::vector<int> bits = parse_payload (payload_hex[i]);
           if (bits.empty())
             {
-              set_error (string_printf ("awm_add_watermark_segments_d: cannot parse payload '%s' at index %zu", payload_hex[i], i));
+              set_error (string_printf ("%s: cannot parse payload '%s' at index %zu", fn, payload_hex[i], i));
               return AWM_ERR_ARG;
             }
           if (!n_frames[i])                                // (a segment without samples: its payload is checked, no table is made for it)
@@ -2060,7 +2060,7 @@ awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segm
       {
         if (r.out ? r.a < end_any : r.a < end_out)
           {
-            set_error (string_printf ("awm_add_watermark_segments_d: the output of segment %zu overlaps a buffer of segment %zu",
+            set_error (string_printf ("%s: the output of segment %zu overlaps a buffer of segment %zu", fn,
                                       r.out ? r.seg : seg_out, r.out ? seg_any : r.seg));
             return AWM_ERR_ARG;
           }
@@ -2068,6 +2068,38 @@ awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segm
         if (r.out && r.b > end_out) { end_out = r.b; seg_out = r.seg; }
       }
   }
+  return 0;
+}
+
+/* the segments with samples, by payload: the segments of a group of payloads are neighbours */
+static void
+segments_by_payload (size_t n_segments, const size_t *n_frames, const std::vector<size_t>& payload_index, std::vector<size_t>& segs,
+                     std::vector<size_t>& payload_of)
+{
+  segs.clear();
+  for (size_t i = 0; i < n_segments; i++)
+    if (n_frames[i])
+      segs.push_back (i);
+  std::stable_sort (segs.begin(), segs.end(), [&] (size_t x, size_t y) { return payload_index[x] < payload_index[y]; });
+  payload_of.resize (segs.size());
+  for (size_t i = 0; i < segs.size(); i++)
+    payload_of[i] = payload_index[segs[i]];
+}
+
+int
+awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                              const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels)
+{
+  AWM_ENTER (ctx);
+  g_add_segments_fused_in_use = 0;
+  if (!n_segments)
+    return 0;
+  std::vector<size_t> payload_index;
+  std::vector<unsigned char> coded;
+  size_t n_code = 0;
+  if (int rc = segments_check (ctx, "awm_add_watermark_segments_d", key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels,
+                               payload_index, coded, n_code))
+    return rc;
   bool fused = g_add_batched && n_channels == 2 && n_segments >= 2;
   for (size_t i = 0; i < n_segments && fused; i++)
     if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) & 15) || (reinterpret_cast<uintptr_t> (out_d[i]) & 15)))
@@ -2080,19 +2112,409 @@ awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segm
             return rc;
       return 0;
     }
-  // the segments with samples, by payload: the segments of a group of payloads are neighbours
-  std::vector<size_t> segs;
-  for (size_t i = 0; i < n_segments; i++)
-    if (n_frames[i])
-      segs.push_back (i);
-  std::stable_sort (segs.begin(), segs.end(), [&] (size_t x, size_t y) { return payload_index[x] < payload_index[y]; });
-  std::vector<size_t> payload_of (segs.size());
-  for (size_t i = 0; i < segs.size(); i++)
-    payload_of[i] = payload_index[segs[i]];
+  std::vector<size_t> segs, payload_of;
+  segments_by_payload (n_segments, n_frames, payload_index, segs, payload_of);
   g_add_segments_fused_in_use = 1;
   if (segs.empty())
     return 0;
   return add_segments_fused (ctx, key, segs, payload_of, coded, n_code, zero_frames, pcm_in_d, out_d, n_frames);
+}
+
+/* ---- the same at another sample rate: awm_add_watermark_segments_rate_d (include/awm_hip.h).  add_full_rate's stages
+ * -- resample down, K2 for the watermark signal alone, resample up, mix + block maxima, limiter -- run on the WINDOW of each segment that
+ * awm_add_segment_plan describes: the 44.1 kHz frames around the segment, at their global indices (table row, resampler phase, limiter
+ * block and phase).  Nothing in front of the window is stored or computed. ---- */
+struct SegmentWindow
+{
+  awm_segment_plan p;
+  size_t Z, n, pre;            // zero_frames, n_frames, samples of watermark alone in front (Z - mix_first)
+  size_t slice_frames;         // 44.1 kHz frames K2 runs over
+  size_t n_tab;                // limiter ramp table entries
+};
+
+static int
+segment_window (int rate, size_t zero_frames, size_t n_frames, SegmentWindow& w)
+{
+  if (int rc = awm_add_segment_plan (rate, zero_frames, n_frames, &w.p))
+    return rc;
+  w.Z = zero_frames;
+  w.n = n_frames;
+  w.pre = zero_frames - size_t (w.p.mix_first);
+  w.slice_frames = size_t (w.p.slice_last - w.p.slice_first + 1);
+  w.n_tab = awmk::limiter_tab_entries ((long long) n_frames, (long long) zero_frames, int (w.p.limiter_block));
+  return 0;
+}
+
+static awmk::ResampleArgs
+resample_table_args (const ResampleTable& t, int C)
+{
+  awmk::ResampleArgs ra {};
+  ra.n_channels = C;
+  ra.ctab = t.ctab.as<float>();
+  ra.hl = t.hl;
+  ra.np = t.np;
+  ra.step = t.step;
+  return ra;
+}
+
+// the three slices of a window: `in` = the segment, x44 / wm44 = slice_frames * 1024 frames each, wm = pre + n frames
+static awmk::ResampleSlice
+window_down_slice (const SegmentWindow& w, const float *in, int C, float *x44)
+{
+  return { in + size_t (w.p.in_first) * C, (long long) (w.p.in_last - w.p.in_first + 1), (long long) (w.Z + w.p.in_first),
+           (long long) w.p.down_first, (long long) (w.slice_frames * Params::frame_size), x44 };
+}
+static awmk::AddMixArgs
+window_mix_args (const SegmentWindow& w, const float *x44, float *wm44, int C, const int8_t *frame_mod, double water_delta, int frames_per_span)
+{
+  awmk::AddMixArgs a {};
+  a.pcm_in = x44;
+  a.out = wm44;
+  a.n_frames = (long long) (w.slice_frames * Params::frame_size);
+  a.n_channels = C;
+  a.frame_mod = frame_mod;
+  fill_add_mix_common (a, water_delta);
+  a.first_frame = (long long) w.p.slice_first;
+  a.frames_per_span = frames_per_span;
+  a.delta_only = 1;
+  return a;
+}
+static awmk::ResampleSlice
+window_up_slice (const SegmentWindow& w, const float *wm44, int C, float *wm)
+{
+  // only the complete frames are handed over: a read outside them would come back as zero and show in the result
+  return { wm44 + size_t (w.p.frame_first - w.p.slice_first) * Params::frame_size * C,
+           (long long) ((w.p.frame_last - w.p.frame_first + 1) * Params::frame_size), (long long) (w.p.frame_first * Params::frame_size),
+           (long long) w.p.mix_first, (long long) (w.pre + w.n), wm };
+}
+
+/* one segment through the single-stream launchers (what every segment of a call that cannot take the fused path goes through) */
+static int
+add_segment_rate (awm_ctx *ctx, const ResampleTable& down, const ResampleTable& up, const uint8_t key[16], const char *payload_hex, size_t zero_frames,
+                  const float *pcm_in_d, float *out_d, size_t n_frames, int C, int rate)
+{
+  SegmentWindow w;
+  if (int rc = segment_window (rate, zero_frames, n_frames, w))
+    return rc;
+  FrameModTable *fm = ctx->get_frame_mod (capi_key (key), payload_hex);
+  if (!fm)
+    return AWM_ERR_ARG;
+  const int use_limiter = !params().test_no_limiter, lim_block = int (w.p.limiter_block);
+  const size_t n44 = w.slice_frames * Params::frame_size;
+  if (int rc = ctx->ws_rate_a.reserve (n44 * C * sizeof (float))) return rc;
+  if (int rc = ctx->ws_rate_b.reserve (n44 * C * sizeof (float))) return rc;
+  if (int rc = ctx->ws_rate_c.reserve ((w.pre + n_frames) * C * sizeof (float))) return rc;
+  float *x44 = ctx->ws_rate_a.as<float>(), *wm44 = ctx->ws_rate_b.as<float>(), *wm = ctx->ws_rate_c.as<float>();
+  hipStream_t st = ctx->stream;
+  {
+    const awmk::ResampleSlice s = window_down_slice (w, pcm_in_d, C, x44);
+    ProfScope ps (ctx, PROF_RESAMPLE, double (s.n_in + s.n_out) * C * 4.0);
+    AWM_HIP_CHECK (awmk::launch_resample_slice (st, resample_table_args (down, C), s));
+  }
+  {
+    const awmk::AddMixArgs a = window_mix_args (w, x44, wm44, C, fm->dev.as<int8_t>(), params().water_delta, frames_per_span (ctx, (long long) w.slice_frames));
+    ProfScope ps (ctx, PROF_ADD_MIX, double (n44) * C * 8.0);
+    AWM_HIP_CHECK (awmk::launch_add_mix (st, ctx->tabs, a));
+  }
+  {
+    const awmk::ResampleSlice s = window_up_slice (w, wm44, C, wm);
+    ProfScope ps (ctx, PROF_RESAMPLE, double (s.n_in + s.n_out) * C * 4.0);
+    AWM_HIP_CHECK (awmk::launch_resample_slice (st, resample_table_args (up, C), s));
+  }
+  const size_t n_blocks = size_t (w.p.n_blocks);
+  if (use_limiter)
+    {
+      if (int rc = ctx->ws_block_max.reserve (n_blocks * sizeof (float))) return rc;
+      if (int rc = awm_add_init_block_max_d (ctx, ctx->ws_block_max.as<float>(), n_blocks)) return rc;
+    }
+  const awmk::MixSegment ms { pcm_in_d, wm, out_d, (long long) n_frames, (long long) w.pre, (long long) zero_frames,
+                              use_limiter ? ctx->ws_block_max.as<unsigned int>() : nullptr, (long long) w.p.first_block, (long long) n_blocks };
+  AWM_HIP_CHECK (awmk::launch_mix_max_segment (st, ms, C, lim_block));
+  if (use_limiter)
+    {
+      if (int rc = ctx->ws_limit_tab.reserve ((w.n_tab + 1) * sizeof (float2))) return rc;
+      ProfScope ps (ctx, PROF_LIMITER, double (n_frames) * C * 8.0);
+      AWM_HIP_CHECK (awmk::launch_limiter (st, out_d, (long long) n_frames, C, (long long) zero_frames, ctx->ws_block_max.as<float>(),
+                                           (long long) w.p.first_block, (long long) n_blocks, lim_block, LIMITER_CEILING,
+                                           ctx->ws_limit_tab.as<float2>(), w.n_tab));
+    }
+  return 0;
+}
+
+constexpr size_t WS_MAX_FLOATS = size_t (1) << 28;         // 1 GiB per workspace (44.1 kHz slices, watermark frames, watermark signals): a batch that would need more is split
+
+/* a segment whose window alone exceeds a workspace (about 50 minutes of stereo) cannot be part of a batch: such a call goes segment by
+ * segment, where the workspaces grow to what the segment needs */
+static bool
+segments_rate_fit_the_workspaces (size_t n_segments, const size_t *zero_frames, const size_t *n_frames, int C, int rate)
+{
+  for (size_t i = 0; i < n_segments; i++)
+    {
+      SegmentWindow w;
+      if (n_frames[i] && (segment_window (rate, zero_frames[i], n_frames[i], w) || w.slice_frames * Params::frame_size * C > WS_MAX_FLOATS
+                          || (w.pre + w.n) * C + 3 > WS_MAX_FLOATS))
+        return false;
+    }
+  return true;
+}
+
+/* the fused path (stereo): segs / payload_of / coded as for add_segments_fused */
+static int
+add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const ResampleTable& up, const uint8_t key[16], const std::vector<size_t>& segs,
+                         const std::vector<size_t>& payload_of, const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames,
+                         const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int rate)
+{
+  constexpr size_t PER_LAUNCH = 4096, TABLE_GROUP = 1024;  // as in add_segments_fused
+  const int C = 2;
+  const size_t FRAME = Params::frame_size, n = segs.size(), n_distinct = coded.size() / (2 * n_code);
+  const int use_limiter = !params().test_no_limiter;
+  const size_t block_frames = mark_block_frame_count();
+  const size_t table_stride = awmk::payload_table_stride (block_frames);
+  hipStream_t st = ctx->stream;
+
+  FrameModTemplate *tmpl = ctx->get_frame_mod_template (capi_key (key));
+  if (!tmpl)
+    return AWM_ERR_HIP;
+
+  // the window of every segment and the batches: consecutive segments (in payload order) of one table group, at most PER_LAUNCH of them.
+  // Segments of a batch that agree in input, length and offset share one down-resampled slice
+  struct Seg { SegmentWindow w; size_t down, x44_off, wm44_off, wm_off, max_off, tab_off; };
+  struct Batch { size_t i0, i1, d0, d1, x44_floats, wm44_floats, wm_floats, max_n44, max_out, max_tab; long long frames1024; };
+  std::vector<Seg> geo (n);
+  std::vector<Batch> batches;
+  std::vector<size_t> down_owner;                          // (ordered) segment whose window a down slice is made for
+  std::map<std::tuple<const float *, size_t, size_t>, size_t> shared;
+  size_t max_total = 0, tab_total = 0;
+  int lim_block = 0;
+  for (size_t i = 0; i < n; i++)
+    {
+      Seg& g = geo[i];
+      const size_t s = segs[i];
+      if (int rc = segment_window (rate, zero_frames[s], n_frames[s], g.w))
+        return rc;
+      lim_block = int (g.w.p.limiter_block);
+      // (a segment that alone exceeds a workspace never gets here: segments_rate_fit_the_workspaces)
+      const size_t n44_floats = g.w.slice_frames * FRAME * C, wm_floats = ((g.w.pre + g.w.n) * C + 3) / 4 * 4;
+      const auto id = std::make_tuple (pcm_in_d[s], n_frames[s], zero_frames[s]);
+      bool fresh = batches.empty() || i - batches.back().i0 >= PER_LAUNCH || payload_of[i] / TABLE_GROUP != payload_of[batches.back().i0] / TABLE_GROUP;
+      if (!fresh)
+        {
+          const Batch& b = batches.back();
+          const bool have = shared.count (id) > 0;
+          fresh = b.wm44_floats + n44_floats > WS_MAX_FLOATS || b.wm_floats + wm_floats > WS_MAX_FLOATS || (!have && b.x44_floats + n44_floats > WS_MAX_FLOATS);
+        }
+      if (fresh)
+        {
+          batches.push_back ({ i, i, down_owner.size(), down_owner.size(), 0, 0, 0, 0, 0, 0, 0 });
+          shared.clear();
+        }
+      Batch& b = batches.back();
+      auto it = shared.find (id);
+      if (it == shared.end())
+        {
+          it = shared.emplace (id, i).first;
+          g.x44_off = b.x44_floats;
+          b.x44_floats += n44_floats;
+          down_owner.push_back (i);
+          b.d1 = down_owner.size();
+        }
+      else
+        g.x44_off = geo[it->second].x44_off;
+      g.wm44_off = b.wm44_floats;
+      b.wm44_floats += n44_floats;
+      g.wm_off = b.wm_floats;
+      b.wm_floats += wm_floats;
+      g.max_off = max_total;
+      g.tab_off = tab_total;
+      max_total += size_t (g.w.p.n_blocks);
+      tab_total += g.w.n_tab + 1;
+      b.i1 = i + 1;
+      b.max_n44 = std::max (b.max_n44, g.w.slice_frames * FRAME);
+      b.max_out = std::max (b.max_out, g.w.pre + g.w.n);
+      b.max_tab = std::max (b.max_tab, g.w.n_tab);
+      b.frames1024 += (long long) g.w.slice_frames;
+    }
+  size_t x44_max = 0, wm44_max = 0, wm_max = 0;
+  long long frames_max = 0;
+  for (const Batch& b : batches)
+    {
+      x44_max = std::max (x44_max, b.x44_floats);
+      wm44_max = std::max (wm44_max, b.wm44_floats);
+      wm_max = std::max (wm_max, b.wm_floats);
+      frames_max = std::max (frames_max, b.frames1024);
+    }
+  const int L = frames_per_span (ctx, frames_max);
+  const size_t n_down = down_owner.size();
+
+  // one page-locked block, one upload: the kernel arguments of every stage and the payloads' codes
+  const size_t off_mix = n_down * sizeof (awmk::ResampleSlice), off_up = off_mix + n * sizeof (awmk::AddMixArgs),
+               off_mm = off_up + n * sizeof (awmk::ResampleSlice), off_lim = off_mm + n * sizeof (awmk::MixSegment),
+               off_coded = off_lim + n * sizeof (awmk::LimiterClip), arg_bytes = off_coded + coded.size();
+  if (int rc = ctx->ws_add_batch.reserve (arg_bytes)) return rc;
+  if (int rc = ctx->ws_keytab.reserve (std::min (n_distinct, TABLE_GROUP) * table_stride)) return rc;
+  if (int rc = ctx->ws_rate_a.reserve (x44_max * sizeof (float))) return rc;
+  if (int rc = ctx->ws_rate_b.reserve (wm44_max * sizeof (float))) return rc;
+  if (int rc = ctx->ws_rate_c.reserve (wm_max * sizeof (float))) return rc;
+  if (use_limiter)
+    {
+      if (int rc = ctx->ws_block_max.reserve (max_total * sizeof (float))) return rc;
+      if (int rc = ctx->ws_limit_tab.reserve (tab_total * sizeof (float2))) return rc;
+    }
+  if (ctx->ev_add_batch)
+    AWM_HIP_CHECK (hipEventSynchronize (ctx->ev_add_batch));            // (an earlier batch's staging has been copied)
+  else
+    AWM_HIP_CHECK (hipEventCreateWithFlags (&ctx->ev_add_batch, hipEventDisableTiming));
+  if (int rc = ctx->pin_add_batch.reserve (arg_bytes)) return rc;
+  char *h = ctx->pin_add_batch.as<char>(), *d = ctx->ws_add_batch.as<char>();
+  auto *h_down = reinterpret_cast<awmk::ResampleSlice *> (h), *h_up = reinterpret_cast<awmk::ResampleSlice *> (h + off_up);
+  auto *h_mix = reinterpret_cast<awmk::AddMixArgs *> (h + off_mix);
+  auto *h_mm = reinterpret_cast<awmk::MixSegment *> (h + off_mm);
+  auto *h_lim = reinterpret_cast<awmk::LimiterClip *> (h + off_lim);
+  const auto *d_down = reinterpret_cast<const awmk::ResampleSlice *> (d), *d_up = reinterpret_cast<const awmk::ResampleSlice *> (d + off_up);
+  const auto *d_mix = reinterpret_cast<const awmk::AddMixArgs *> (d + off_mix);
+  const auto *d_mm = reinterpret_cast<const awmk::MixSegment *> (d + off_mm);
+  const auto *d_lim = reinterpret_cast<const awmk::LimiterClip *> (d + off_lim);
+  const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
+  std::memcpy (h + off_coded, coded.data(), coded.size());
+  float *x44 = ctx->ws_rate_a.as<float>(), *wm44 = ctx->ws_rate_b.as<float>(), *wm = ctx->ws_rate_c.as<float>();
+  float *block_max = ctx->ws_block_max.as<float>();
+  float2 *tabs = ctx->ws_limit_tab.as<float2>();
+  for (size_t k = 0; k < n_down; k++)
+    {
+      const Seg& g = geo[down_owner[k]];
+      h_down[k] = window_down_slice (g.w, pcm_in_d[segs[down_owner[k]]], C, x44 + g.x44_off);
+    }
+  for (size_t i = 0; i < n; i++)
+    {
+      const Seg& g = geo[i];
+      const size_t s = segs[i];
+      const int8_t *table = ctx->ws_keytab.as<int8_t>() + (payload_of[i] % TABLE_GROUP) * table_stride;
+      h_mix[i] = window_mix_args (g.w, x44 + g.x44_off, wm44 + g.wm44_off, C, table, params().water_delta, L);
+      h_up[i] = window_up_slice (g.w, wm44 + g.wm44_off, C, wm + g.wm_off);
+      h_mm[i] = { pcm_in_d[s], wm + g.wm_off, out_d[s], (long long) g.w.n, (long long) g.w.pre, (long long) g.w.Z,
+                  use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr, (long long) g.w.p.first_block, (long long) g.w.p.n_blocks };
+      h_lim[i] = { out_d[s], (long long) g.w.n, use_limiter ? block_max + g.max_off : nullptr, (long long) g.w.p.n_blocks,
+                   use_limiter ? tabs + g.tab_off : nullptr, (long long) g.w.n_tab, (long long) g.w.Z, (long long) g.w.p.first_block };
+    }
+  AWM_HIP_CHECK (hipMemcpyAsync (d, h, arg_bytes, hipMemcpyHostToDevice, st));
+  AWM_HIP_CHECK (hipEventRecord (ctx->ev_add_batch, st));
+
+  const awmk::ResampleArgs ra_down = resample_table_args (down, C), ra_up = resample_table_args (up, C);
+  size_t group_built = size_t (-1);
+  for (const Batch& b : batches)
+    {
+      const size_t group = payload_of[b.i0] / TABLE_GROUP, nb = b.i1 - b.i0;
+      if (group != group_built)
+        {
+          awmk::PayloadTableArgs pa {};
+          pa.tmpl = tmpl->dev.as<short>();
+          pa.coded = d_coded + group * TABLE_GROUP * 2 * n_code;
+          pa.tables = ctx->ws_keytab.as<signed char>();
+          pa.table_stride = (long long) table_stride;
+          pa.half_entries = int (block_frames * Params::n_bands);
+          pa.n_code = int (n_code);
+          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
+          ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (pa.n_payloads) * table_stride, st);          // the tables out, once
+          AWM_HIP_CHECK (awmk::launch_payload_tables (st, pa));
+          group_built = group;
+        }
+      double down_values = 0, up_values = 0, n44_values = 0, out_values = 0;
+      long long max_spans = 0;
+      for (size_t k = b.d0; k < b.d1; k++)
+        down_values += double (h_down[k].n_in + h_down[k].n_out) * C;
+      for (size_t i = b.i0; i < b.i1; i++)
+        {
+          up_values += double (h_up[i].n_in + h_up[i].n_out) * C;
+          n44_values += double (geo[i].w.slice_frames * FRAME) * C;
+          out_values += double (geo[i].w.n) * C;
+          max_spans = std::max (max_spans, ((long long) geo[i].w.slice_frames + L - 1) / L);
+        }
+      {
+        ProfScope ps (ctx, PROF_RESAMPLE, down_values * 4.0, st);                     // every input and output sample once
+        AWM_HIP_CHECK (awmk::launch_resample_slices (st, ra_down, d_down + b.d0, int (b.d1 - b.d0), (long long) b.max_n44, true));
+      }
+      if (use_limiter)
+        {
+          unsigned int bits;
+          std::memcpy (&bits, &LIMITER_CEILING, sizeof (bits));
+          const size_t m0 = geo[b.i0].max_off, m1 = geo[b.i1 - 1].max_off + size_t (geo[b.i1 - 1].w.p.n_blocks);
+          AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (block_max + m0), bits, m1 - m0));
+        }
+      {
+        ProfScope ps (ctx, PROF_ADD_MIX, n44_values * 8.0, st);
+        AWM_HIP_CHECK (awmk::launch_add_mix_batch (st, ctx->tabs, d_mix + b.i0, int (nb), max_spans, int (block_frames), int (Params::frames_pad_start)));
+      }
+      {
+        ProfScope ps (ctx, PROF_RESAMPLE, up_values * 4.0, st);
+        AWM_HIP_CHECK (awmk::launch_resample_slices (st, ra_up, d_up + b.i0, int (nb), (long long) b.max_out, true));
+      }
+      AWM_HIP_CHECK (awmk::launch_mix_max_segments (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, lim_block));
+      if (use_limiter)
+        {
+          ProfScope ps (ctx, PROF_LIMITER, out_values * 8.0, st);
+          size_t max_len = 0;
+          for (size_t i = b.i0; i < b.i1; i++)
+            max_len = std::max (max_len, geo[i].w.n);
+          AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_lim + b.i0, int (nb), (long long) max_len, C, lim_block, LIMITER_CEILING, (long long) b.max_tab));
+        }
+    }
+  return 0;
+}
+
+int
+awm_add_watermark_segments_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                   const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_add_watermark_segments_d (ctx, key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels);
+  AWM_ENTER (ctx);
+  g_add_segments_fused_in_use = 0;
+  const char *fn = "awm_add_watermark_segments_rate_d";
+  awm_segment_plan probe;
+  if (awm_add_segment_plan (sample_rate, 0, 0, &probe))
+    {
+      set_error (sample_rate <= 0 ? string_printf ("%s: bad sample rate %d", fn, sample_rate)
+                                  : string_printf ("%s: no fixed-ratio resampler between %d Hz and %d Hz (zita's VResampler is not offered here)", fn,
+                                                   sample_rate, Params::mark_sample_rate));
+      return AWM_ERR_ARG;
+    }
+  if (!n_segments)
+    return 0;
+  std::vector<size_t> payload_index;
+  std::vector<unsigned char> coded;
+  size_t n_code = 0;
+  if (int rc = segments_check (ctx, fn, key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, payload_index, coded, n_code))
+    return rc;
+  for (size_t i = 0; i < n_segments; i++)
+    if (awm_add_segment_plan (sample_rate, zero_frames[i], n_frames[i], &probe))
+      {
+        set_error (string_printf ("%s: zero_frames + n_frames of segment %zu is not below 2^40", fn, i));
+        return AWM_ERR_ARG;
+      }
+  const ResampleTable *down = ctx->get_resample_table (sample_rate, Params::mark_sample_rate);
+  const ResampleTable *up = ctx->get_resample_table (Params::mark_sample_rate, sample_rate);
+  if (!down || !up)
+    return AWM_ERR_HIP;
+  // (the batched limiter needs blocks of at least four of its runs: launch_limiter_batch)
+  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2 && probe.limiter_block >= 8192
+               && segments_rate_fit_the_workspaces (n_segments, zero_frames, n_frames, n_channels, sample_rate);
+  for (size_t i = 0; i < n_segments && fused; i++)
+    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) & 15) || (reinterpret_cast<uintptr_t> (out_d[i]) & 15)))
+      fused = false;
+  if (!fused)
+    {
+      for (size_t i = 0; i < n_segments; i++)
+        if (n_frames[i])
+          if (int rc = add_segment_rate (ctx, *down, *up, key, payload_hex[i], zero_frames[i], pcm_in_d[i], out_d[i], n_frames[i], n_channels, sample_rate))
+            return rc;
+      return 0;
+    }
+  std::vector<size_t> segs, payload_of;
+  segments_by_payload (n_segments, n_frames, payload_index, segs, payload_of);
+  g_add_segments_fused_in_use = 1;
+  if (segs.empty())
+    return 0;
+  return add_segments_rate_fused (ctx, *down, *up, key, segs, payload_of, coded, n_code, zero_frames, pcm_in_d, out_d, n_frames, sample_rate);
 }
 
 /* K16p alone (measurements, tests): the tables of n_payloads payloads with one key built on the device and copied to the host,

@@ -3,6 +3,7 @@
 #include "utils.hh"
 #include "wmspeed.hh"
 #include "random.hh"
+#include <algorithm>
 #include <cstring>
 #include <memory>
 
@@ -133,6 +134,67 @@ awm_tab_synth_window (float *out)
 {
   const auto w = gen_synth_window();
   std::copy (w.begin(), w.end(), out);
+  return 0;
+}
+
+/* The window of one stream segment at another sample rate (include/awm_hip.h).  With b_X (m) = floor (m step_X /
+ * np_X), output m of resampler X reads inputs b_X (m) - hl_X + 1 ... b_X (m) + hl_X of its stream (kernels.hh ResampleArgs), so the
+ * smallest m that reaches input j is ceil ((j - hl_X) np_X / step_X).  Every index is below 2^40 + 2^12 at the stream's rate and below
+ * 2^45 at 44.1 kHz (the down ratio is at least 1 / 16), np <= 1000 and step <= 16000 (Resampler::setup): every product below fits 2^59. */
+int
+awm_add_segment_plan (int sample_rate, size_t zero_frames, size_t n_frames, awm_segment_plan *plan)
+{
+  if (!plan)
+    {
+      set_error ("awm_add_segment_plan: bad argument");
+      return AWM_ERR_ARG;
+    }
+  *plan = awm_segment_plan {};
+  int hd, nd, sd, hu, nu, su;
+  if (sample_rate <= 0 || !resample_fixed_ratio (sample_rate, Params::mark_sample_rate, hd, nd, sd)
+      || !resample_fixed_ratio (Params::mark_sample_rate, sample_rate, hu, nu, su))
+    {
+      set_error (string_printf ("awm_add_segment_plan: no fixed-ratio resampler between %d Hz and %d Hz", sample_rate, Params::mark_sample_rate));
+      return AWM_ERR_ARG;
+    }
+  constexpr uint64_t LIMIT = uint64_t (1) << 40;
+  if (uint64_t (zero_frames) >= LIMIT || uint64_t (n_frames) >= LIMIT || uint64_t (zero_frames) + uint64_t (n_frames) >= LIMIT)
+    {
+      set_error ("awm_add_segment_plan: zero_frames + n_frames must stay below 2^40");
+      return AWM_ERR_ARG;
+    }
+  plan->down_hl = hd; plan->down_np = nd; plan->down_step = sd;
+  plan->up_hl = hu; plan->up_np = nu; plan->up_step = su;
+  plan->limiter_block = uint64_t (sample_rate) * uint64_t (Params::limiter_block_size_ms) / 1000;
+  if (!n_frames || !plan->limiter_block)
+    return 0;
+  const uint64_t FRAME = Params::frame_size, Z = zero_frames, n = n_frames;
+  auto b = [] (uint64_t m, int step, int np) { return m * uint64_t (step) / uint64_t (np); };
+  auto first_reaching = [] (uint64_t j, int hl, int step, int np) {            // the smallest m with b (m) + hl >= j
+    return j <= uint64_t (hl) ? uint64_t (0) : ((j - uint64_t (hl)) * uint64_t (np) + uint64_t (step) - 1) / uint64_t (step);
+  };
+  // in front of the segment the stream is silent, but the watermark is not: the first 44.1 kHz sample that sees the segment lies in frame
+  // f0, whose spectrum also shapes frame f0 - 1; the first output the up-resampler makes from those frames is where the mix begins
+  const uint64_t f0 = first_reaching (Z, hd, sd, nd) / FRAME;
+  const uint64_t w0 = (f0 ? f0 - 1 : 0) * FRAME;
+  plan->mix_first = std::min<uint64_t> (Z, first_reaching (w0, hu, su, nu));
+  // up: watermark samples the outputs mix_first ... Z + n - 1 read, and their frames
+  const uint64_t ub = b (plan->mix_first, su, nu), wm_first = ub + 1 > uint64_t (hu) ? ub + 1 - uint64_t (hu) : 0;
+  const uint64_t wm_last = b (Z + n - 1, su, nu) + uint64_t (hu);
+  plan->frame_first = wm_first / FRAME;
+  plan->frame_last = wm_last / FRAME;
+  // K2: a frame is complete once both neighbours were transformed (frame 0 has none in front)
+  plan->slice_first = plan->frame_first ? plan->frame_first - 1 : 0;
+  plan->slice_last = plan->frame_last + 1;
+  // down: the samples of those frames, and the part of the segment they read
+  plan->down_first = plan->slice_first * FRAME;
+  plan->down_last = (plan->slice_last + 1) * FRAME - 1;
+  const uint64_t db = b (plan->down_first, sd, nd), in_lo = db + 1 > uint64_t (hd) ? db + 1 - uint64_t (hd) : 0;
+  const uint64_t in_hi = b (plan->down_last, sd, nd) + uint64_t (hd);
+  plan->in_first = in_lo > Z ? std::min (in_lo - Z, n - 1) : 0;
+  plan->in_last = in_hi >= Z ? std::min (in_hi - Z, n - 1) : 0;
+  plan->first_block = plan->mix_first / plan->limiter_block;
+  plan->n_blocks = (Z + n) / plan->limiter_block + 2 - plan->first_block;
   return 0;
 }
 

@@ -18,6 +18,7 @@ std::string hip_error_string (hipError_t e) { return std::string (hipGetErrorNam
 // the runtime took for them -- what a FIRST call pays before its workspaces exist
 static std::atomic<long>   g_dev_allocs { 0 }, g_pin_allocs { 0 };
 static std::atomic<double> g_dev_alloc_ms { 0.0 }, g_pin_alloc_ms { 0.0 };
+static std::atomic<unsigned long long> g_dev_alloc_bytes { 0 };       // device bytes asked for by all DevBuffers so far (awm_debug_alloc_bytes)
 static void
 note_alloc (std::atomic<long>& count, std::atomic<double>& ms, std::chrono::steady_clock::time_point t0)
 {
@@ -47,6 +48,7 @@ DevBuffer::reserve (size_t want)
   const auto t0 = std::chrono::steady_clock::now();
   hipError_t e = hipMalloc (&ptr, cap);
   note_alloc (g_dev_allocs, g_dev_alloc_ms, t0);
+  g_dev_alloc_bytes.fetch_add (cap, std::memory_order_relaxed);
   if (e != hipSuccess)
     {
       ptr = nullptr;
@@ -107,6 +109,8 @@ awm_debug_alloc_stats (long *dev_allocs, double *dev_ms, long *pinned_allocs, do
   if (pinned_allocs) *pinned_allocs = awm::g_pin_allocs.load();
   if (pinned_ms) *pinned_ms = awm::g_pin_alloc_ms.load();
 }
+
+extern "C" unsigned long long awm_debug_alloc_bytes (void) { return awm::g_dev_alloc_bytes.load(); }
 
 hipEvent_t
 awm::ReadyMarks::next_event()
@@ -437,15 +441,11 @@ awm_ctx::get_key_tables (const Key& key)
 
 /* zita-resampler 1.x, Resampler::setup (fs_inp, fs_out, nchan, hlen) and Resampler_table::Resampler_table (fr, hl, np),
  * restated from the library's published algorithm (the library itself is not part of the reference tree): parity unpinned. */
-ResampleTable *
-awm_ctx::get_resample_table (int rate_in, int rate_out)
+bool
+awm::resample_fixed_ratio (int rate_in, int rate_out, int& hl, int& np, int& step, double *frel_out)
 {
-  std::lock_guard<std::mutex> lock (table_mutex);
-  for (auto& t : resample_tables)
-    if (t->rate_in == rate_in && t->rate_out == rate_out)
-      return t.get();
   if (rate_in <= 0 || rate_out <= 0)
-    return nullptr;
+    return false;
   const int hlen = 16;
   double frel = 1.0 - 2.6 / hlen;
   const double r = double (rate_out) / double (rate_in);
@@ -458,20 +458,39 @@ awm_ctx::get_resample_table (int rate_in, int rate_out)
     }
   const unsigned n = unsigned (rate_out) / a, s = unsigned (rate_in) / a;
   if (!(16 * r >= 1 && n <= 1000))
-    return nullptr;                      // zita's Resampler::setup refuses: ResamplerImpl::create falls back to VResampler (capi_kernels.cc)
+    return false;                        // zita's Resampler::setup refuses: ResamplerImpl::create falls back to VResampler (capi_kernels.cc)
   unsigned h = hlen;
   if (r < 1)
     {
       frel *= r;
       h = unsigned (std::ceil (h / r));
     }
-  const std::vector<float> ctab = zita_table (frel, h, n);
+  hl = int (h);
+  np = int (n);
+  step = int (s);
+  if (frel_out)
+    *frel_out = frel;
+  return true;
+}
+
+ResampleTable *
+awm_ctx::get_resample_table (int rate_in, int rate_out)
+{
+  std::lock_guard<std::mutex> lock (table_mutex);
+  for (auto& t : resample_tables)
+    if (t->rate_in == rate_in && t->rate_out == rate_out)
+      return t.get();
+  int h, n, s;
+  double frel;
+  if (!resample_fixed_ratio (rate_in, rate_out, h, n, s, &frel))
+    return nullptr;
+  const std::vector<float> ctab = zita_table (frel, unsigned (h), unsigned (n));
   auto rt = std::make_unique<ResampleTable>();
   rt->rate_in = rate_in;
   rt->rate_out = rate_out;
-  rt->hl = int (h);
-  rt->np = int (n);
-  rt->step = int (s);
+  rt->hl = h;
+  rt->np = n;
+  rt->step = s;
   if (upload (rt->ctab, ctab.data(), ctab.size() * sizeof (float), stream))
     return nullptr;
   resample_tables.push_back (std::move (rt));

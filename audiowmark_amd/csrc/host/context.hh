@@ -141,6 +141,8 @@ struct ResampleTable
   DevBuffer ctab;                  // (np + 1) * hl floats
 };
 
+// geometry of that table (Resampler::setup): false where zita's fixed-ratio Resampler refuses the two rates.  Pure arithmetic, no device
+bool resample_fixed_ratio (int rate_in, int rate_out, int& hl, int& np, int& step, double *frel_out = nullptr);
 // coefficient table of zita-resampler (Resampler_table): (np + 1) * hl floats
 std::vector<float> zita_table (double frel, unsigned hl, unsigned np);
 // grow `buf` to `bytes` and copy host memory into it on `st`; returns when the copy is done (the source may be a temporary)

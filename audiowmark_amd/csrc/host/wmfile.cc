@@ -1239,7 +1239,8 @@ add_tiles_payloads (awm_ctx *ctx, const Key& key, AudioInputStream *in_stream, c
 }
 
 /* `add` at another sample rate: the WatermarkResampler path works on the whole stream in HBM (awm_add_watermark_d); the
- * host side is still bounded (chunked staging both ways) */
+ * host side is still bounded (chunked staging both ways).  A stream that continues zero_frames samples in goes through the one-segment
+ * window form (awm_add_watermark_segments_rate_d): device memory does not grow with zero_frames -- unless an SNR meter is running */
 int
 add_whole (awm_ctx *ctx, const Key& key, AudioInputStream *in_stream, AudioOutputStream *out_stream, const std::string& payload_hex,
            size_t zero_frames, size_t& n_frames)
@@ -1257,9 +1258,36 @@ add_whole (awm_ctx *ctx, const Key& key, AudioInputStream *in_stream, AudioOutpu
   n_frames = n_values / C;
   if (!n_values)
     return 0;
+  if (zero_frames && !params().snr && !ctx->snr_on)
+    {
+      // the resamplers' skip (resample.cc:150-168) leaves them in the state zeros would have: the result is that part of the watermarked
+      // stream "zero_frames zeros, then the input".  awm_add_watermark_segments_rate_d computes it from a window of 44.1 kHz frames around
+      // the input: no zero is stored, the cost does not depend on zero_frames
+      const char *hex = payload_hex.c_str();
+      const float *in_d = d_in.as<float>();
+      if (d_out.reserve (n_values * sizeof (float)))
+        {
+          error ("audiowmark: GPU watermarking failed: %s\n", awm_last_error());
+          return fail (AWM_ERR_HIP);
+        }
+      float *out_d = d_out.as<float>();
+      if (int rc = awm_add_watermark_segments_rate_d (ctx, key.aes_key(), 1, &hex, &zero_frames, &in_d, &out_d, &n_frames, C, in_stream->sample_rate()))
+        {
+          error ("audiowmark: GPU watermarking failed: %s\n", awm_last_error());
+          return fail (rc == AWM_ERR_ARG ? AWM_ERR_ARG : AWM_ERR_HIP);      // (an argument the window form refuses, such as zero_frames + n_frames >= 2^40)
+        }
+      err = store_device_to_stream (ctx, out_stream, out_d, n_values);
+      if (err)
+        {
+          error ("audiowmark output write failed: %s\n", err.message());
+          return fail (AWM_ERR_IO);
+        }
+      return 0;
+    }
   if (zero_frames)
     {
-      // the resamplers' skip (resample.cc:150-168) leaves them in the state zeros would have: the stream behind zero_frames zeros
+      // with --snr, or a meter the caller armed (awm_ctx_snr_begin), the powers are those of the whole zero-prefixed stream: the zeros are
+      // written out and the stream is watermarked as one
       const size_t zero_values = zero_frames * C;
       if (zero_frames > (DevBuffer::MAX_BYTES / sizeof (float) - n_values) / C)
         {

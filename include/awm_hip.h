@@ -252,7 +252,7 @@ int awm_add_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], const char *
  * (hls.cc:244-279: a few seconds of audio with up to 3 x 1024 samples of context on either side, watermarked for one subscriber by
  * add_stream_watermark (key, in, out, bits, start_pos - prev_size), hls.cc:279).  For every i, out_d[i] receives n_frames[i] * n_channels
  * floats: bit for bit the concatenated output of an awm_add_stream_create_at (ctx, key, payload_hex[i], n_channels, ..., zero_frames[i])
- * stream fed that segment.  44100 Hz only, as for the other batch entry points; the context's parameters apply as for awm_add_watermark_d
+ * stream fed that segment.  44100 Hz (other rates: awm_add_watermark_segments_rate_d below); the context's parameters apply as for awm_add_watermark_d
  * (water_delta, mix, frames_per_bit, test_no_limiter).  Inputs may alias each other (the same segment for many subscribers).
  * AWM_ERR_ARG with nothing enqueued: a NULL pointer (pcm_in_d[i] / out_d[i] may be NULL where n_frames[i] is 0), an output that overlaps
  * an input or another output, a payload that does not parse (awm_last_error names its index), a call while the SNR meter is armed.
@@ -267,10 +267,51 @@ int awm_add_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], const char *
  * the limiter work there, one scatter launch brings the results home without the r samples (a batch stages at most 1 GiB per direction,
  * more is split); segments with r = 0 are read from and written to the caller's buffers directly.  Everything else (other channel
  * counts, a misaligned pointer, a single segment, awm_debug_set_add_batched (0)) goes segment by segment through the tile stream, with
- * the same results.  Not offered in this form: the command line, the awm_multi_* / sharded forms, a key per segment. */
+ * the same results.  Not offered in this form: the command line, a tile-stream object at other rates, the awm_multi_* / sharded forms,
+ * a key per segment. */
 int awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
                                   const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
                                   int n_channels);
+
+/* The same at ANY sample rate that zita's fixed-ratio Resampler takes in both directions (48000, 32000, 96000, 22050, 88200, ...: what the
+ * reference's HLS mode does with add_stream_watermark at the rate of the programme, WatermarkResampler, wmadd.cc:353-430).  With S = the
+ * stream "zero_frames[i] zeros, then segment i" and W = what awm_add_watermark_d (ctx, key, payload_hex[i], S, W, zero_frames[i] +
+ * n_frames[i], n_channels, sample_rate) writes, out_d[i] receives W[zero_frames[i] ... zero_frames[i] + n_frames[i]), bit for bit -- but
+ * no zero is ever stored and nothing is computed outside a WINDOW of a few 44.1 kHz frames around the segment (awm_add_segment_plan): every
+ * stage of the resampled add is a function of global sample and frame indices.  The cost does not depend on zero_frames.
+ * Arguments and rules are awm_add_watermark_segments_d's (AWM_ERR_ARG with nothing enqueued, the overlap sweep, aliasing inputs, the payload
+ * index in the error, refused while the SNR meter is armed, n_segments == 0 and empty segments accepted; the context's water_delta, mix,
+ * frames_per_bit, test_no_limiter apply); sample_rate == 44100 IS that function.  Refused in addition, with AWM_ERR_ARG and nothing written:
+ * sample_rate <= 0, a rate without a fixed-ratio table in either direction (e.g. 44101: the reference would use zita's VResampler there,
+ * which this entry point does not offer), zero_frames[i] + n_frames[i] >= 2^40.
+ * Stereo, 16-byte aligned pointers, n_segments >= 2 (and a rate of at least 8192 Hz) take the fused path, per batch: [K16p], K10w down
+ * (blockIdx.y = slice; segments that agree in pcm_in_d, n_frames and zero_frames share ONE 44.1 kHz slice), fill, K2 (watermark signal
+ * alone, per segment), K10w up, mix + block maxima, K3a, K3b -- the number of launches does not depend on n_segments up to the 4096 a launch
+ * takes; the 44.1 kHz slices and the watermark signals live in three context workspaces of at most 1 GiB each, larger batches are split.
+ * Everything else (other channel counts, a misaligned pointer, a single segment, awm_debug_set_add_batched (0), a call with a segment
+ * whose window alone exceeds such a workspace: about 50 minutes of stereo) runs the same stages segment by segment with the same window
+ * arguments and the same results; awm_debug_add_segments_fused_in_use () tells which path ran.
+ * Not offered in this form: the command line, a tile-stream object at other rates, the awm_multi_* / sharded forms, a key per segment. */
+int awm_add_watermark_segments_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
+                                       const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
+                                       int n_channels, int sample_rate);
+/* The window of one such segment (pure host arithmetic, no context, no device; the device path calls it per segment).  Frames and samples
+ * are indices into the segment's stream: at 44.1 kHz for the frames (of 1024 samples) and the down_* samples, at sample_rate otherwise. */
+typedef struct
+{
+  uint64_t mix_first;                /* first sample of the stream whose mix counts: the watermark begins this far in front of zero_frames
+                                        (resampler pre-ringing, the frames that see the segment's first sample); it is needed only for the
+                                        limiter's block maxima */
+  uint64_t frame_first, frame_last;  /* 44.1 kHz frames K2 must produce completely (those the up-resampler reads) */
+  uint64_t slice_first, slice_last;  /* frames K2 runs over: one more on either side, transformed but incomplete (none in front of frame 0) */
+  uint64_t down_first, down_last;    /* 44.1 kHz samples the down-resampler must deliver: those of the slice's frames */
+  uint64_t in_first, in_last;        /* samples of the segment (relative to it) those depend on */
+  uint64_t limiter_block;            /* samples per limiter block at sample_rate */
+  uint64_t first_block, n_blocks;    /* limiter blocks whose maxima are kept: from the block of mix_first */
+  int      down_hl, down_np, down_step, up_hl, up_np, up_step;     /* the two resamplers' tables (kernels.hh ResampleArgs) */
+} awm_segment_plan;
+/* 0, or AWM_ERR_ARG for what awm_add_watermark_segments_rate_d refuses (rate, 2^40).  n_frames == 0: only the tables and limiter_block */
+int awm_add_segment_plan (int sample_rate, size_t zero_frames, size_t n_frames, awm_segment_plan *plan);
 
 /* The batch entry points with ONE KEY PER CLIP (keys = n_clips * 16 bytes; BASELINE configs[4]: `--test-key k` for clip k).  The key
  * tables -- frame_mod for `add`; CLIP sync tables, mix table and bit order for `get` (wmcommon.cc:143-202, wmadd.cc:86-162,
@@ -368,8 +409,11 @@ int awm_add_watermark_file (awm_ctx *ctx, const uint8_t key[16], const char *pay
                             const awm_raw_format *raw_in, const awm_raw_format *raw_out);
 /* add_stream_watermark (key, in_stream, out_stream, bits, zero_frames) (wmcommon.hh:226, wmadd.cc:448-618) on files: the input is the
  * continuation of a stream that is `zero_frames` samples in (hls.cc:279 watermarks a segment this way); zero_frames = 0 is
- * awm_add_watermark_file.  At 44.1 kHz the start offset costs nothing (a frame counter and a limiter block phase); at other rates the
- * zeros are materialised in HBM in front of the input (the resamplers see them, resample.cc:150-168). */
+ * awm_add_watermark_file.  At 44.1 kHz the start offset costs nothing (a frame counter and a limiter block phase); at other rates (those
+ * awm_add_watermark_segments_rate_d takes) the output is computed from a window of 44.1 kHz frames around the input, at its global
+ * indices (the resamplers' skip leaves them in the state zeros would have, resample.cc:150-168): no zero is stored, the cost does not
+ * depend on zero_frames.  While an SNR meter is running (`--snr`, or awm_ctx_snr_begin by the caller) the zeros are still materialised in HBM,
+ * as before: the powers are those of the whole zero-prefixed stream. */
 int awm_add_stream_watermark_file (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, const char *in_path, const char *out_path,
                                    const awm_raw_format *raw_in, const awm_raw_format *raw_out, size_t zero_frames);
 /* awm_add_watermark_file / awm_add_stream_watermark_file of ONE input file with n_payloads payloads and one key: out_path[p] is byte for
@@ -586,7 +630,7 @@ void awm_debug_set_add_batched (int on);   /* add of a batch of stereo clips: 2 
 void awm_debug_set_add_slab_mb (int mb);   /* add: 0 (default) one fused add over the stream, then the limiter | > 0: in slabs of that many MB (cache experiment) */
 void awm_debug_set_add_payloads_fused (int on);   /* awm_add_watermark_payloads_d, awm_add_mix_payloads_d: 1 (default) the fused kernel | 0 a loop over the single-payload path */
 int  awm_debug_add_payloads_fused_in_use (void);  /* 1 if the last awm_add_watermark_payloads_d / awm_add_mix_payloads_d (also inside a stream push) ran the fused kernel */
-int  awm_debug_add_segments_fused_in_use (void);  /* 1 if the last awm_add_watermark_segments_d took the fused path (one launch per stage), 0: segment by segment */
+int  awm_debug_add_segments_fused_in_use (void);  /* 1 if the last awm_add_watermark_segments_d / _rate_d took the fused path (one launch per stage), 0: segment by segment */
 int  awm_debug_payload_tables_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int8_t *tables_out);
                                              /* K16p alone: the frame_mod tables of 1 .. 1024 payloads with one key, expanded on the device from the key's template,
                                               * n_payloads x 2 x block frames x 81 bytes to host memory (they equal awm_tab_frame_mod payload by payload);
@@ -609,6 +653,7 @@ void awm_debug_set_group_fallback (int on); /* clip batches: every clip takes th
 void awm_debug_alloc_stats (long *dev_allocs, double *dev_ms, long *pinned_allocs, double *pinned_ms);
                                            /* process-wide census of hipMalloc / hipHostMalloc calls made by the library's grow-only buffers and the
                                             * time the runtime took for them (what a first call pays); any pointer may be NULL */
+unsigned long long awm_debug_alloc_bytes (void);   /* ... and the device bytes those buffers asked hipMalloc for, summed over the process's life */
 void awm_debug_file_timing (double ms_out[8]);
                                            /* where the calling thread's time went in its last file level `add` at the watermark rate (milliseconds):
                                             * [0] set-up (add stream, rings), [1] waiting for input tiles, [2] waiting for a free output slot, [3] queueing GPU
