@@ -126,6 +126,10 @@ lib.awm_debug_set_add_payloads_fused.argtypes = [C.c_int]
 lib.awm_debug_set_add_payloads_fused.restype = None
 lib.awm_debug_add_payloads_fused_in_use.argtypes = []
 lib.awm_debug_add_payloads_fused_in_use.restype = C.c_int
+lib.awm_debug_set_add_payloads_rate_fused.argtypes = [C.c_int]
+lib.awm_debug_set_add_payloads_rate_fused.restype = None
+lib.awm_debug_add_payloads_rate_fused_in_use.argtypes = []
+lib.awm_debug_add_payloads_rate_fused_in_use.restype = C.c_int
 lib.awm_debug_add_payloads_tile.argtypes = []
 lib.awm_debug_add_payloads_tile.restype = C.c_int
 lib.awm_add_watermark_batch_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
@@ -566,6 +570,17 @@ def set_add_payloads_fused(on):
 def add_payloads_fused_in_use():
     """1 if the last add_watermark_payloads ran the fused kernel"""
     return lib.awm_debug_add_payloads_fused_in_use()
+
+
+def set_add_payloads_rate_fused(mode):
+    """(tests, measurements) add_watermark_payloads at another sample rate: 2 (default) one down-resample, K2m and K10m where it applies,
+    1 one down-resample and K2m, then K10 and K11 per output, 0 a loop over the single-payload path"""
+    lib.awm_debug_set_add_payloads_rate_fused(int(mode))
+
+
+def add_payloads_rate_fused_in_use():
+    """which of these paths the last add_watermark_payloads took (0 at 44.1 kHz)"""
+    return lib.awm_debug_add_payloads_rate_fused_in_use()
 
 
 ADD_PAYLOADS_TILE = lib.awm_debug_add_payloads_tile()     # outputs per pass of the fused kernel over the input

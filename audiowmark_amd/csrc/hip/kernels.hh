@@ -85,6 +85,7 @@ struct AddMixMultiArgs
   int          frames_pad_start;
   int          n_out;             // 1 .. ADD_MULTI_TILE
   AddMixOut    o[ADD_MULTI_TILE];
+  int          delta_only = 0;    // as in AddMixArgs: every output receives the watermark signal alone (the stream at another sample rate)
 };
 hipError_t launch_add_mix_multi (hipStream_t st, const DevTables& t, const AddMixMultiArgs& a);
 int        add_mix_multi_waves_per_simd();   // occupancy K2m is built for (sizes its spans)
@@ -158,6 +159,34 @@ struct ResampleSlice
 hipError_t launch_resample_slices (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, int n_slices, long long max_n_out,
                                    bool stereo_aligned);
 hipError_t launch_resample_slice (hipStream_t st, const ResampleArgs& a, const ResampleSlice& slice);     // one slice, arguments by value
+
+/* K10m: K10 on the way up (44.1 -> 48 kHz: np 160, step 147, hl 16) for the watermark signals of up to ADD_MULTI_TILE outputs of ONE
+ * stereo stream, fused with K11: out[o][m] = K10's output m of wm44[o] + orig[m], one rounded add, and block_max[o] receives the maxima of
+ * |out[o]| per limiter block (float bits, atomicMax; nullptr: none).  A thread owns a phase: its coefficients stay in registers for the
+ * launch, the samples of orig that it adds to for a tile's outputs.  out[o] is bit for bit what launch_resample into a buffer and
+ * launch_mix_max from it write, and so are the maxima.  Every pointer 8-byte aligned, limiter_block >= 2560 (the tile):
+ * resample_mix_multi_takes says whether a call qualifies, the launcher refuses what does not. */
+struct ResampleMixOut
+{
+  const float  *wm44;       // the output's watermark signal at 44.1 kHz, n_in frames (everything else reads as zero)
+  float        *out;        // n_out frames
+  unsigned int *block_max;  // n_blocks maxima from limiter block 0, or nullptr
+};
+struct ResampleMixArgs
+{
+  const float *orig;        // the stream at the rate, n_out frames
+  long long    n_in;
+  int          n_channels;
+  const float *ctab;        // device, (np + 1) * hl
+  int          hl, np, step;
+  long long    n_out;
+  long long    n_blocks;
+  int          limiter_block;
+  int          n;           // 1 .. ADD_MULTI_TILE
+  ResampleMixOut o[ADD_MULTI_TILE];
+};
+bool       resample_mix_multi_takes (const ResampleMixArgs& a);
+hipError_t launch_resample_mix_multi (hipStream_t st, const ResampleMixArgs& a);
 
 /* K11: out = wm + orig (reference wmadd.cc:564-565) and the per-limiter-block maxima of the result (limiter.cc:90-97) */
 hipError_t launch_mix_max (hipStream_t st, const float *orig, const float *wm, float *out, long long n_frames, int n_channels,

@@ -951,6 +951,15 @@ add_mix_multi_body (const DevTables& t, const AddMixMultiArgs& a, const AddMixSp
               in[c][j] = 0.f;
         }
 
+      if (a.delta_only)
+        {
+          // WatermarkGen::run alone, as in add_mix_body: the mix below then adds 0 instead of the input
+#pragma unroll
+          for (int c = 0; c < CV; c++)
+#pragma unroll
+            for (int j = 0; j < 16; j++)
+              in[c][j] = 0.f;
+        }
       // the frame's first sample in the whole stream; the whole-stream form is the span that starts at frame 0 and block 0
       const FramePlace fp = frame_place ((SPAN ? sp.first_frame + m : m) * 1024, BS, SPAN ? sp.first_block : 0, m >= s && m < e, m - 1 >= s && m - 1 < e);
 
@@ -1570,7 +1579,140 @@ launch_resample (hipStream_t st, const ResampleArgs& a)
   return hipGetLastError();
 }
 
-/* K10w (kernels.hh ResampleSlice): resample_kernel for windows of streams.  Like K10 a workgroup stages the coefficient table once and
+/* K10m (kernels.hh ResampleMixArgs): resample_phase_kernel for the watermark signals of several outputs of ONE stream, with K11 behind it.
+ * What does not depend on the output is done once per tile: a thread's phase and its 2 hl coefficients (registers, for the launch) and the
+ * J samples of the stream at the rate that its J outputs are added to (registers, for the tile's outputs).  Per output the workgroup
+ * stages the tile's window of that output's 44.1 kHz signal, a thread forms zita's sum for each of its J frames with resample_phase_kernel's
+ * own sequence of products and sums, stores (sum - 1e-20f) + orig -- K10's stored value, then K11's one rounded add -- and keeps the maxima
+ * of |out| for the limiter block the tile starts in and for the next one (a tile is shorter than a block: one boundary at most), which
+ * go out per wave with atomicMax on the float bits as in mix_max_kernel.  Maxima do not depend on how the stream is cut, so the array is
+ * what K11 leaves.  Every product, sum and the final add is an explicit __f*_rn call (nothing here may be contracted).
+ * The window is ONE buffer that the outputs use in turn (two barriers per output): the 19 KB would admit eight workgroups per CU, the
+ * 125 registers (coefficients, the tile's input samples, the unrolled frames' taps in flight) admit three, which cover each other's
+ * staging.  Measured: 1.56 ms per output and hour against 0.96 + 0.66 ms for K10 and K11; prefetching the next
+ * output's window into a second buffer needs 16 registers that are not there and is not built. */
+template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ ((NP * R + 63) / 64 * 64)
+resample_mix_multi_kernel (ResampleMixArgs a, int tiles_per_wg)
+{
+  static_assert (STEP <= NP, "the way up: a thread per phase");
+  constexpr int SPAN = R * J * STEP + 2 * HL;                 // frames of a tile's window
+  constexpr int TILE = R * J * NP;                            // outputs of a tile
+  constexpr int WG = (NP * R + 63) / 64 * 64;
+  __shared__ float2 s_in[SPAN];
+  const int tid = threadIdx.x;
+  const bool active = tid < NP * R;
+  const int rep = active ? tid / NP : 0, p = active ? tid - rep * NP : 0;
+  const int ph = (p * STEP) % NP, b_p = (p * STEP) / NP;      // phase and window start of output p of a tile (tiles start at multiples of np)
+  float c1[HL], c2[HL];
+#pragma unroll
+  for (int i = 0; i < HL; i++)
+    {
+      c1[i] = a.ctab[ph * HL + i];
+      c2[i] = a.ctab[(NP - ph) * HL + i];
+    }
+  const float2 *orig2 = reinterpret_cast<const float2 *> (a.orig);
+  const int BS = a.limiter_block;
+  for (int t = 0; t < tiles_per_wg; t++)
+    {
+      const long long tile = (long long) blockIdx.x * tiles_per_wg + t;
+      const long long tile0 = tile * TILE;
+      if (tile0 >= a.n_out)
+        break;                                                                 // (uniform)
+      const long long first0 = tile * (R * J * STEP) - (HL - 1);              // frame of s_in[0]
+      const long long b0 = tile0 / BS;
+      const long long bound = (b0 + 1) * BS;                                   // first frame of the next limiter block
+      float2 x[J];
+#pragma unroll
+      for (int j = 0; j < J; j++)
+        {
+          const long long m = tile0 + p + NP * (rep + R * j);
+          x[j] = (active && m < a.n_out) ? orig2[m] : make_float2 (0.f, 0.f);
+        }
+#pragma unroll
+      for (int o = 0; o < ADD_MULTI_TILE; o++)
+        if (o < a.n)                                                           // (uniform)
+          {
+            if (t || o)
+              __syncthreads();                                                 // the previous windows have been read
+            const float2 *in2 = reinterpret_cast<const float2 *> (a.o[o].wm44);
+            for (int i = tid; i < SPAN; i += WG)
+              {
+                const long long j = first0 + i;
+                s_in[i] = (j >= 0 && j < a.n_in) ? in2[j] : make_float2 (0.f, 0.f);
+              }
+            __syncthreads();
+            float2 *out2 = reinterpret_cast<float2 *> (a.o[o].out);
+            float m0 = 0.f, m1 = 0.f;
+#pragma unroll
+            for (int j = 0; j < J; j++)
+              {
+                const int q = rep + R * j;                                     // which group of np outputs of the tile
+                const long long m = tile0 + p + NP * q;
+                if (active && m < a.n_out)
+                  {
+                    const float2 *p1 = s_in + b_p + STEP * q, *p2 = p1 + 2 * HL - 1;
+                    float s0 = 1e-20f, s1 = 1e-20f;
+#pragma unroll
+                    for (int i = 0; i < HL; i++)
+                      {
+                        const float2 x1 = p1[i], x2 = p2[-i];
+                        s0 = __fadd_rn (s0, __fadd_rn (__fmul_rn (x1.x, c1[i]), __fmul_rn (x2.x, c2[i])));
+                        s1 = __fadd_rn (s1, __fadd_rn (__fmul_rn (x1.y, c1[i]), __fmul_rn (x2.y, c2[i])));
+                      }
+                    const float2 r = make_float2 (__fadd_rn (__fsub_rn (s0, 1e-20f), x[j].x), __fadd_rn (__fsub_rn (s1, 1e-20f), x[j].y));
+                    out2[m] = r;
+                    const float mx = fmaxf (fabsf (r.x), fabsf (r.y));
+                    if (m < bound)
+                      m0 = fmaxf (m0, mx);
+                    else
+                      m1 = fmaxf (m1, mx);
+                  }
+              }
+            unsigned int *block_max = a.o[o].block_max;
+            if (block_max)                                                     // (uniform)
+              {
+                m0 = wave_max (m0);
+                m1 = wave_max (m1);
+                if ((tid & 63) == 0)
+                  {
+                    if (b0 < a.n_blocks && m0 > 0.f) atomicMax (block_max + b0, __float_as_uint (m0));
+                    if (b0 + 1 < a.n_blocks && m1 > 0.f) atomicMax (block_max + b0 + 1, __float_as_uint (m1));
+                  }
+              }
+          }
+    }
+}
+
+bool
+resample_mix_multi_takes (const ResampleMixArgs& a)
+{
+  if (a.n_channels != 2 || a.np != 160 || a.step != 147 || a.hl != 16 || a.limiter_block < 2 * 8 * 160 || a.n < 1 || a.n > ADD_MULTI_TILE)
+    return false;
+  uintptr_t bits = reinterpret_cast<uintptr_t> (a.orig);
+  for (int o = 0; o < a.n; o++)
+    bits |= reinterpret_cast<uintptr_t> (a.o[o].wm44) | reinterpret_cast<uintptr_t> (a.o[o].out);
+  return (bits & 7) == 0;
+}
+
+hipError_t
+launch_resample_mix_multi (hipStream_t st, const ResampleMixArgs& a)
+{
+  constexpr int NP = 160, STEP = 147, HL = 16, R = 2, J = 8;
+  if (a.n_out <= 0)
+    return hipSuccess;
+  if (!resample_mix_multi_takes (a) || a.n_in < 0 || a.n_blocks < 0 || !a.orig || !a.ctab)
+    return hipErrorInvalidValue;
+  for (int o = 0; o < a.n; o++)
+    if (!a.o[o].wm44 || !a.o[o].out)
+      return hipErrorInvalidValue;
+  const long long n_tiles = (a.n_out + R * J * NP - 1) / (R * J * NP);
+  const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles / 4096)));     // as launch_resample_phase
+  const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg));
+  hipLaunchKernelGGL ((resample_mix_multi_kernel<NP, STEP, HL, R, J>), grid, dim3 ((NP * R + 63) / 64 * 64), 0, st, a, tiles_per_wg);
+  return hipGetLastError();
+}
+
+/* K10w (kernels.hh ResampleSlice): resample_kernel for windows of streams. Like K10 a workgroup stages the coefficient table once and
  * keeps it for `tiles_per_wg` consecutive tiles of RS_TILE outputs of its slice (staging the table costs as much as the taps of one tile);
  * window start and phase come from each tile's first GLOBAL output index, the staged window is filled from the slice's resident input
  * and zeros.  The taps are resample_output_staged / resample_output themselves. */

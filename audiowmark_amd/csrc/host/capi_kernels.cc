@@ -1276,10 +1276,130 @@ awm_add_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_he
 
 /* One input, many payloads (include/awm_hip.h).  At 44.1 kHz the payloads go through K2m in tiles of ADD_MULTI_TILE outputs: a tile pass
  * reads the input once and transforms every frame forward once, whatever the number of its outputs; block maxima and limiter ramp are
- * per output.  Other sample rates (and the debug toggle) loop over the single-payload path. */
+ * per output.  At a rate with fixed-ratio tables both ways the stream is resampled to 44.1 kHz once, K2m writes the watermark signals of
+ * a pass alone and they go up and into the outputs per pass (add_payloads_rate); every other rate, one payload and the debug toggles
+ * loop over the single-payload path. */
 extern "C" void awm_debug_set_add_payloads_fused (int on) { g_add_payloads_fused = on; }
 extern "C" int  awm_debug_add_payloads_fused_in_use (void) { return g_add_payloads_fused_in_use; }
 extern "C" int  awm_debug_add_payloads_tile (void) { return awmk::ADD_MULTI_TILE; }
+static int g_add_payloads_rate_fused = 2, g_add_payloads_rate_fused_in_use = 0;
+extern "C" void awm_debug_set_add_payloads_rate_fused (int mode) { g_add_payloads_rate_fused = mode < 0 ? 0 : mode > 2 ? 2 : mode; }
+extern "C" int  awm_debug_add_payloads_rate_fused_in_use (void) { return g_add_payloads_rate_fused_in_use; }
+
+/* awm_add_watermark_payloads_d at another sample rate: add_full_rate's stages with everything that does not depend
+ * on the payload done once.  The stream goes down to 44.1 kHz once for the call (x44; F, n44 and last44 are add_full_rate's); per balanced
+ * pass of at most ADD_MULTI_TILE payloads K2m (delta_only) reads x44 once and writes the pass's watermark signals, which K10m takes up to
+ * the rate and adds to the stream in one kernel (stereo 44.1 -> 48 kHz, every pointer 8-byte aligned: path 2) or K10 and K11 once per
+ * output (everything else: path 1); then the limiter per output.  Every output is computed by add_full_rate's own arithmetic, value for
+ * value, and block maxima are maxima: the outputs are the loop's bit for bit.
+ * Workspaces: x44 and min (P, ADD_MULTI_TILE) watermark signals of n44 C floats each, path 1 also one signal at the rate -- 60 min of
+ * stereo at 48 kHz with P >= 4: 5 x 1.27 GB = 6.4 GB for path 2 (the loop: 2 x 1.27 + 1.38 = 3.9 GB).  *taken = false, nothing enqueued:
+ * a reservation failed (what had been reserved is freed again) and the caller runs the loop. */
+static int
+add_payloads_rate (awm_ctx *ctx, const Key& k, const char *const *payload_hex, size_t n_payloads, const float *pcm_in_d, float *const *out_d,
+                   size_t n_frames, int C, double water_delta, int use_limiter, int rate, const RateConverter& down, const RateConverter& up,
+                   bool *taken)
+{
+  hipStream_t st = ctx->stream;
+  const size_t last44 = up.window_start (n_frames - 1) + size_t (up.hl()) + 1;
+  const size_t F = last44 / Params::frame_size + 1;              // watermark frames 0 .. F - 1 are needed
+  const size_t n44 = (F + 1) * Params::frame_size;               // frame F's delta completes frame F - 1
+  const size_t n_ws = std::min<size_t> (n_payloads, size_t (awmk::ADD_MULTI_TILE)), ws_values = n44 * size_t (C);
+  const int lim_block = int (size_t (rate) * size_t (Params::limiter_block_size_ms) / 1000);
+  const size_t n_blocks = n_frames / lim_block + 2;
+  const ResampleTable& ut = *up.fixed;
+  awmk::ResampleMixArgs ma {};
+  ma.orig = pcm_in_d;
+  ma.n_in = (long long) (F * Params::frame_size);                // only frames 0 .. F - 1 of a signal are complete (add_full_rate)
+  ma.n_channels = C;
+  ma.ctab = ut.ctab.as<float>();
+  ma.hl = ut.hl;
+  ma.np = ut.np;
+  ma.step = ut.step;
+  ma.n_out = (long long) n_frames;
+  ma.n_blocks = (long long) n_blocks;
+  ma.limiter_block = lim_block;
+  ma.n = 1;
+  bool mixed = g_add_payloads_rate_fused == 2;
+  for (size_t p = 0; mixed && p < n_payloads; p++)
+    {
+      ma.o[0].wm44 = pcm_in_d;                                   // (the workspaces are aligned; the launcher checks them again)
+      ma.o[0].out = out_d[p];
+      mixed = awmk::resample_mix_multi_takes (ma);
+    }
+  *taken = false;
+  if (ctx->ws_rate_a.reserve (ws_values * sizeof (float)) || ctx->ws_rate_b.reserve (n_ws * ws_values * sizeof (float))
+      || (!mixed && ctx->ws_rate_c.reserve (n_frames * C * sizeof (float))))
+    {
+      ctx->ws_rate_a.release();
+      ctx->ws_rate_b.release();
+      ctx->ws_rate_c.release();
+      return 0;
+    }
+  float *block_max = nullptr;
+  size_t tab_entries = 0;
+  if (use_limiter)
+    {
+      if (int rc = ctx->ws_block_max.reserve (n_payloads * n_blocks * sizeof (float))) return rc;
+      tab_entries = awmk::limiter_tab_entries ((long long) n_frames, 0, lim_block);
+      if (int rc = ctx->ws_limit_tab.reserve ((tab_entries + 1) * sizeof (float2))) return rc;
+      block_max = ctx->ws_block_max.as<float>();
+      unsigned int bits;
+      std::memcpy (&bits, &LIMITER_CEILING, sizeof (bits));
+      AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (block_max), bits, n_payloads * n_blocks));
+    }
+  *taken = true;
+  float *x44 = ctx->ws_rate_a.as<float>(), *wm44 = ctx->ws_rate_b.as<float>(), *wm = ctx->ws_rate_c.as<float>();
+  if (int rc = resample_device (ctx, down, pcm_in_d, n_frames, C, x44, n44)) return rc;
+  awmk::AddMixMultiArgs a {};
+  a.pcm_in = x44;
+  a.n_frames = (long long) n44;
+  a.n_channels = C;
+  fill_add_mix_common (a, water_delta);
+  a.frames_per_span = frames_per_span (ctx, (long long) (F + 1), awmk::add_mix_multi_waves_per_simd());
+  a.delta_only = 1;
+  auto maxima = [&] (size_t p) { return use_limiter ? reinterpret_cast<unsigned int *> (block_max + p * n_blocks) : nullptr; };
+  const int rc = add_mix_multi_passes (ctx, st, a, n_payloads,
+    [&] (size_t p, awmk::AddMixOut& o) {
+      FrameModTable *fm = ctx->get_frame_mod (k, payload_hex[p]);
+      if (!fm)
+        return false;
+      o.out = wm44 + size_t (&o - a.o) * ws_values;             // the pass's i-th signal
+      o.frame_mod = fm->dev.as<int8_t>();
+      o.block_max = nullptr;
+      return true;
+    },
+    [&] () { AWM_HIP_CHECK (awmk::launch_add_mix_multi (st, ctx->tabs, a)); return 0; },
+    [&] (size_t p0, size_t n) {
+      if (mixed)
+        {
+          ma.n = int (n);
+          for (size_t i = 0; i < size_t (awmk::ADD_MULTI_TILE); i++)
+            ma.o[i] = i < n ? awmk::ResampleMixOut { wm44 + i * ws_values, out_d[p0 + i], maxima (p0 + i) } : awmk::ResampleMixOut {};
+          // the stream once, every signal and every output once
+          ProfScope ps (ctx, PROF_RESAMPLE_MIX, (double (n_frames) * (1 + n) + double (ma.n_in) * n) * C * 4.0, st);
+          AWM_HIP_CHECK (awmk::launch_resample_mix_multi (st, ma));
+        }
+      else
+        for (size_t i = 0; i < n; i++)
+          {
+            if (int r = resample_device (ctx, up, wm44 + i * ws_values, F * Params::frame_size, C, wm, n_frames)) return r;
+            AWM_HIP_CHECK (awmk::launch_mix_max (st, pcm_in_d, wm, out_d[p0 + i], (long long) n_frames, C, maxima (p0 + i), (long long) n_blocks, lim_block));
+          }
+      for (size_t p = p0; use_limiter && p < p0 + n; p++)
+        {
+          ProfScope ps (ctx, PROF_LIMITER, double (n_frames) * C * 8.0, st);
+          // (the outputs share the ramp table: the passes run in stream order, each rebuilds the entries)
+          AWM_HIP_CHECK (awmk::launch_limiter (st, out_d[p], (long long) n_frames, C, 0, block_max + p * n_blocks, 0, (long long) n_blocks,
+                                               lim_block, LIMITER_CEILING, ctx->ws_limit_tab.as<float2>(), tab_entries));
+        }
+      return 0;
+    });
+  if (rc)
+    return rc;
+  g_add_payloads_rate_fused_in_use = mixed ? 2 : 1;
+  return 0;
+}
 
 int
 awm_add_watermark_payloads_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
@@ -1287,6 +1407,7 @@ awm_add_watermark_payloads_d (awm_ctx *ctx, const uint8_t key[16], const char *c
 {
   AWM_ENTER (ctx);
   g_add_payloads_fused_in_use = 0;
+  g_add_payloads_rate_fused_in_use = 0;
   if (!n_payloads || !n_frames)
     return 0;
   if (!key || !payload_hex || !pcm_in_d || !out_d || n_channels < 1)
@@ -1329,6 +1450,21 @@ awm_add_watermark_payloads_d (awm_ctx *ctx, const uint8_t key[16], const char *c
   const Key k = capi_key (key);
   const double water_delta = params().water_delta;
   const int use_limiter = !params().test_no_limiter;
+  if (n_payloads > 1 && g_add_payloads_fused && g_add_payloads_rate_fused && sample_rate != Params::mark_sample_rate && sample_rate > 0)
+    {
+      // rates that only the VResampler takes have no table one way or the other: the loop
+      RateConverter down, up;
+      down.fixed = ctx->get_resample_table (sample_rate, Params::mark_sample_rate);
+      up.fixed = down.fixed ? ctx->get_resample_table (Params::mark_sample_rate, sample_rate) : nullptr;
+      if (down.fixed && up.fixed)
+        {
+          bool taken = false;
+          const int rc = add_payloads_rate (ctx, k, payload_hex, n_payloads, pcm_in_d, out_d, n_frames, n_channels, water_delta, use_limiter,
+                                            sample_rate, down, up, &taken);
+          if (rc || taken)
+            return rc;
+        }
+    }
   if (n_payloads == 1 || !g_add_payloads_fused || sample_rate != Params::mark_sample_rate)
     {
       for (size_t p = 0; p < n_payloads; p++)

@@ -598,7 +598,8 @@ static const char *prof_names[awm::PROF_COUNT] = {
   "sync_db_kernel(refine)", "sync_scan_kernel(refine)", "sync_db_kernel(block)", "soft_bits_kernel", "viterbi_kernel",
   "stft_full_kernel",
   "resample_kernel", "resample_var_kernel", "speed_mags_kernel", "speed_compare_kernel", "frame_mod_table_kernel",
-  "add_mix_multi_kernel", "payload_table_kernel"
+  "add_mix_multi_kernel", "payload_table_kernel",
+  "resample_mix_multi_kernel"
 };
 
 extern "C" {

@@ -1335,6 +1335,76 @@ add_whole (awm_ctx *ctx, const Key& key, AudioInputStream *in_stream, AudioOutpu
   return 0;
 }
 
+/* add_whole for ONE input and P payloads (awm_add_watermark_payloads_file at another sample rate): the input goes to HBM once; the outputs
+ * are produced there in balanced passes of at most four (5 payloads: 3 + 2) into buffers that the passes reuse -- a stream that starts at
+ * sample 0 through awm_add_watermark_payloads_d (one down-resample for the pass), one that continues zero_frames
+ * samples in through awm_add_watermark_segments_rate_d with the pass's payloads as segments that alias the input (they share the
+ * down-resampled slice) -- and written one after the other in payload order.  Every call computes what add_whole's call computes for
+ * that payload, so every file is add_whole's byte for byte.  The caller has ruled out `snr`. */
+int
+add_whole_payloads (awm_ctx *ctx, const Key& key, AudioInputStream *in_stream, const std::vector<AudioOutputStream *>& out_streams,
+                    const std::vector<std::string>& payload_hex, size_t zero_frames, size_t& n_frames)
+{
+  constexpr size_t PASS = 4;
+  const int C = in_stream->n_channels();
+  const size_t P = out_streams.size();
+  DevBuffer d_in, d_out[PASS];
+  struct Guard { DevBuffer& a; DevBuffer (&b)[PASS]; ~Guard() { a.release(); for (auto& o : b) o.release(); } } guard { d_in, d_out };
+  size_t n_values = 0;
+  Error err = load_stream_to_device (ctx, in_stream, d_in, n_values);
+  if (err)
+    {
+      error ("audiowmark: input stream read failed: %s\n", err.message());
+      return fail (AWM_ERR_IO);
+    }
+  n_frames = n_values / C;
+  if (!n_values)
+    return 0;
+  const size_t n_passes = (P + PASS - 1) / PASS;
+  for (size_t i = 0; i < std::min (P, PASS); i++)
+    if (d_out[i].reserve (n_values * sizeof (float)))
+      {
+        error ("audiowmark: GPU watermarking failed: %s\n", awm_last_error());
+        return fail (AWM_ERR_HIP);
+      }
+  size_t p0 = 0;
+  for (size_t pass = 0; pass < n_passes; pass++)
+    {
+      const size_t n = P / n_passes + (pass < P % n_passes ? 1 : 0);
+      const char *hex[PASS];
+      const float *in_d[PASS];
+      float *out_d[PASS];
+      size_t zf[PASS], nf[PASS];
+      for (size_t i = 0; i < n; i++)
+        {
+          hex[i] = payload_hex[p0 + i].c_str();
+          in_d[i] = d_in.as<float>();
+          out_d[i] = d_out[i].as<float>();
+          zf[i] = zero_frames;
+          nf[i] = n_frames;
+        }
+      const int rc = zero_frames
+                   ? awm_add_watermark_segments_rate_d (ctx, key.aes_key(), n, hex, zf, in_d, out_d, nf, C, in_stream->sample_rate())
+                   : awm_add_watermark_payloads_d (ctx, key.aes_key(), hex, n, in_d[0], out_d, n_frames, C, in_stream->sample_rate());
+      if (rc)
+        {
+          error ("audiowmark: GPU watermarking failed: %s\n", awm_last_error());
+          return fail (rc == AWM_ERR_ARG ? AWM_ERR_ARG : AWM_ERR_HIP);      // (an argument the window form refuses, such as zero_frames + n_frames >= 2^40)
+        }
+      for (size_t i = 0; i < n; i++)
+        {
+          err = store_device_to_stream (ctx, out_streams[p0 + i], out_d[i], n_values);
+          if (err)
+            {
+              error ("audiowmark output write failed: %s\n", err.message());
+              return fail (AWM_ERR_IO);
+            }
+        }
+      p0 += n;
+    }
+  return 0;
+}
+
 } // namespace
 
 int
@@ -1479,9 +1549,11 @@ add_watermark_payloads_at (awm_ctx *ctx, const Key& key, const std::string& infi
       error ("audiowmark: error opening %s: %s\n", infile.c_str(), err.message());
       return fail (AWM_ERR_IO);
     }
-  if (in_stream->sample_rate() != Params::mark_sample_rate)
+  const bool at_rate = in_stream->sample_rate() != Params::mark_sample_rate;
+  if (at_rate && (ctx->snr_on || !ctx->get_resample_table (in_stream->sample_rate(), Params::mark_sample_rate)
+                  || !ctx->get_resample_table (Params::mark_sample_rate, in_stream->sample_rate())))
     {
-      // the resampled add is not fused: one pass over the file per payload
+      // a rate without fixed-ratio tables (or a meter the caller armed): one pass over the file per payload
       in_stream.reset();
       return loop();
     }
@@ -1537,7 +1609,7 @@ add_watermark_payloads_at (awm_ctx *ctx, const Key& key, const std::string& infi
    * output frame -- stay within PINNED_CAP of page-locked memory; never below the 128 frames an awm_add_stream needs */
   constexpr size_t PINNED_CAP = size_t (1) << 30, TILE_MAX = 4096, TILE_MIN = 128;
   size_t tile_frames1024 = size_t (g_payloads_file_tile.load (std::memory_order_relaxed));
-  if (!tile_frames1024)
+  if (!tile_frames1024 && !at_rate)
     {
       RawFormat ofmt;
       bool direct16 = false;
@@ -1548,7 +1620,9 @@ add_watermark_payloads_at (awm_ctx *ctx, const Key& key, const std::string& infi
     }
   tile_frames1024 = std::max (TILE_MIN, tile_frames1024);
   size_t n_frames = 0;
-  if (int rc = add_tiles_payloads (ctx, key, in_stream.get(), outs, hexes, zero_frames, tile_frames1024, n_frames))
+  // another sample rate: the whole stream in HBM once, the outputs in passes (add_whole_payloads)
+  if (int rc = at_rate ? add_whole_payloads (ctx, key, in_stream.get(), outs, hexes, zero_frames, n_frames)
+                       : add_tiles_payloads (ctx, key, in_stream.get(), outs, hexes, zero_frames, tile_frames1024, n_frames))
     return rc;
   const bool short_input = in_stream->n_frames() != AudioInputStream::N_FRAMES_UNKNOWN && n_frames != in_stream->n_frames();
   for (size_t p = 0; p < P; p++)

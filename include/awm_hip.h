@@ -338,8 +338,13 @@ int awm_add_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payloa
  * 44100 Hz one kernel (K2m, hip/kernels.hip) reads, windows and transforms every frame once and computes both band factors once; the
  * choice per band, the inverse transform, overlap-add, mix, block maxima and limiter run per output, ADD_MULTI_TILE (4) outputs per pass
  * over the input.  Every channel count takes the fused kernel (stereo with both channels in a wave, anything else a channel per wave).
- * Other sample rates loop over the single-payload path (the resampled add is not fused).  The context's parameters apply as for
- * awm_add_watermark_d.  n_payloads == 0 or n_frames == 0: returns 0, writes nothing; n_payloads == 1: the single-payload path.
+ * At another sample rate with fixed-ratio tables both ways (48, 32, 96, 22.05, 88.2 kHz ...) the payload-independent work of the resampled
+ * add is shared as well: the stream goes down to 44.1 kHz once per call, K2m writes the watermark signals of a pass
+ * alone, and per pass they go up to the rate and into the outputs -- stereo at 48 kHz with 8-byte aligned pointers in one kernel (K10m:
+ * up-resample, add the input, block maxima), everything else through K10 and K11 once per output; the limiter per output.  Workspaces: the
+ * 44.1 kHz stream and min (n_payloads, 4) watermark signals of its size, 6.4 GB for 60 min of stereo at 48 kHz (the loop: 3.9 GB); if they
+ * cannot be reserved the call frees them and loops.  Rates that only the VResampler takes (44101 Hz) loop over the single-payload path.
+ * The context's parameters apply as for awm_add_watermark_d.  n_payloads == 0 or n_frames == 0: returns 0, writes nothing; n_payloads == 1: the single-payload path.
  * AWM_ERR_ARG with nothing enqueued: a payload that does not parse (awm_last_error names its index), a NULL pointer, an output that
  * overlaps the input or another output, a call while the SNR meter is armed (awm_ctx_snr_begin).
  * The same for a span of a stream: awm_add_mix_payloads_d; with bounded memory: awm_add_stream_create_payloads_at; for files:
@@ -423,8 +428,12 @@ int awm_add_stream_watermark_file (awm_ctx *ctx, const uint8_t key[16], const ch
  * stays bounded whatever the file length and n_payloads: the tile is the largest number of 1024-sample frames, at most 4096 and never
  * below 128, for which the output rings together -- n_payloads rings x 4 slots x tile x bytes per output frame -- stay within 1 GiB of
  * page-locked memory (stereo 16 bit: 4096 frames up to 16 payloads, 1024 frames at 64).  The additional rings belong to the call.
- * Other sample rates, `snr` in the parameters, n_payloads == 1 and more than AWM_ADD_STREAM_MAX_PAYLOADS payloads: a loop over
- * awm_add_stream_watermark_file.  n_payloads == 0: returns 0 and touches nothing.
+ * At another sample rate (those awm_add_watermark_segments_rate_d takes) the input is read, uploaded and sample-decoded ONCE into HBM and
+ * the outputs are produced there in passes of at most four payloads -- zero_frames == 0: awm_add_watermark_payloads_d, else
+ * awm_add_watermark_segments_rate_d with the pass's payloads as segments that alias the input -- and written one after the other, in payload
+ * order, from output buffers that the passes reuse.
+ * `snr` in the parameters, n_payloads == 1, more than AWM_ADD_STREAM_MAX_PAYLOADS payloads and rates without fixed-ratio tables: a loop
+ * over awm_add_stream_watermark_file.  n_payloads == 0: returns 0 and touches nothing.
  * AWM_ERR_ARG before any file is opened or truncated: a NULL pointer, a payload that does not parse, two equal output paths, an output
  * path equal to the input path.  Information lines appear once per output, in payload order. */
 int awm_add_watermark_payloads_file (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
@@ -629,7 +638,11 @@ void awm_debug_set_add_batched (int on);   /* add of a batch of stereo clips: 2 
                                             * outputs are the same */
 void awm_debug_set_add_slab_mb (int mb);   /* add: 0 (default) one fused add over the stream, then the limiter | > 0: in slabs of that many MB (cache experiment) */
 void awm_debug_set_add_payloads_fused (int on);   /* awm_add_watermark_payloads_d, awm_add_mix_payloads_d: 1 (default) the fused kernel | 0 a loop over the single-payload path */
-int  awm_debug_add_payloads_fused_in_use (void);  /* 1 if the last awm_add_watermark_payloads_d / awm_add_mix_payloads_d (also inside a stream push) ran the fused kernel */
+int  awm_debug_add_payloads_fused_in_use (void);  /* 1 if the last awm_add_watermark_payloads_d / awm_add_mix_payloads_d (also inside a stream push) ran the 44.1 kHz kernel (0 at every other rate) */
+void awm_debug_set_add_payloads_rate_fused (int mode);  /* awm_add_watermark_payloads_d at another sample rate: 2 (default) shared down-resample + K2m + K10m where K10m applies | 1 shared
+                                                         * down-resample + K2m, then K10 and K11 per output | 0 a loop over the single-payload path (as awm_debug_set_add_payloads_fused (0) at every rate) */
+int  awm_debug_add_payloads_rate_fused_in_use (void);   /* which of these the last awm_add_watermark_payloads_d took: 2 | 1 (also: not stereo, another fixed ratio than 44.1 -> 48 kHz, a pointer
+                                                         * that is only 4-byte aligned) | 0 (also: 44.1 kHz, one payload, a VResampler rate, workspaces that could not be reserved) */
 int  awm_debug_add_segments_fused_in_use (void);  /* 1 if the last awm_add_watermark_segments_d / _rate_d took the fused path (one launch per stage), 0: segment by segment */
 int  awm_debug_payload_tables_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int8_t *tables_out);
                                              /* K16p alone: the frame_mod tables of 1 .. 1024 payloads with one key, expanded on the device from the key's template,
