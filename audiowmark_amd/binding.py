@@ -153,6 +153,12 @@ lib.awm_debug_payload_tables_d.argtypes = [_vp, _vp, _vp, C.c_size_t, _vp]
 lib.awm_get_watermark_batch_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
 lib.awm_add_watermark_batch_keys_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
 lib.awm_get_watermark_batch_keys_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
+lib.awm_get_watermark_rate_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, _vp]
+lib.awm_get_watermark_batch_rate_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
+lib.awm_get_watermark_batch_keys_rate_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
+lib.awm_debug_clip_slice_values.argtypes = [C.c_int]
+lib.awm_debug_clip_slice_values.restype = C.c_size_t
+lib.awm_debug_clip_stage_d.argtypes = [_vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, _vp, _vp]
 lib.awm_decode_chunk_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, _vp]
 lib.awm_tab_up_down.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp]
 lib.awm_tab_bit_pos.argtypes = [_vp, _vp]
@@ -748,8 +754,9 @@ class Context:
                "awm_add_watermark_batch_keys_d")
         return outs
 
-    def get_watermark_batch_keys(self, keys, clips, n_threads=0, max_out_per_clip=64):
-        """get_watermark of many independent resident clips, clip i with keys[i] alone (awm_get_watermark_batch_keys_d)"""
+    def get_watermark_batch_keys(self, keys, clips, n_threads=0, max_out_per_clip=64, sample_rate=44100):
+        """get_watermark of many independent resident clips, clip i with keys[i] alone (awm_get_watermark_batch_keys_d; at another
+        sample rate awm_get_watermark_batch_keys_rate_d)"""
         if not clips:
             return []
         assert len(keys) == len(clips)
@@ -762,8 +769,13 @@ class Context:
         flat = b"".join(key_bytes(k) for k in keys)
         while True:
             buf = self._pattern_buffer(len(clips) * max_out_per_clip)
-            _check(lib.awm_get_watermark_batch_keys_d(self._h, flat, len(clips), ptrs, frames, ch, n_threads, max_out_per_clip,
-                                                      C.cast(buf, C.c_void_p), n_out), "awm_get_watermark_batch_keys_d")
+            if sample_rate != 44100:
+                _check(lib.awm_get_watermark_batch_keys_rate_d(self._h, flat, len(clips), ptrs, frames, ch, sample_rate, n_threads,
+                                                               max_out_per_clip, C.cast(buf, C.c_void_p), n_out),
+                       "awm_get_watermark_batch_keys_rate_d")
+            else:
+                _check(lib.awm_get_watermark_batch_keys_d(self._h, flat, len(clips), ptrs, frames, ch, n_threads, max_out_per_clip,
+                                                          C.cast(buf, C.c_void_p), n_out), "awm_get_watermark_batch_keys_d")
             most = max(n_out)
             if most <= max_out_per_clip:
                 return [patterns_to_dicts(buf, n_out[i], i * max_out_per_clip) for i in range(len(clips))]
@@ -1103,9 +1115,32 @@ class Context:
             max_out = cnt
 
     # get_watermark on resident PCM (chunk loop, BlockDecoder, ClipDecoder, merge, sort)
-    def get_watermark(self, key, pcm):
+    def get_watermark(self, key, pcm, sample_rate=44100):
+        """sample_rate != 44100 (awm_get_watermark_rate_d): the result of get_watermark on resample (pcm, sample_rate, 44100)"""
         n, ch = _pcm_shape(pcm)
+        if sample_rate != 44100:
+            return self._patterns(lib.awm_get_watermark_rate_d, "awm_get_watermark_rate_d", self._h, key_bytes(key), _dev_ptr(pcm), n, ch,
+                                  sample_rate)
         return self._patterns(lib.awm_get_watermark_d, "awm_get_watermark_d", self._h, key_bytes(key), _dev_ptr(pcm), n, ch)
+
+    def clip_stage(self, clips, sample_rate, out=None):
+        """awm_debug_clip_stage_d: stage 0 of one group of 1 .. 64 short clips alone -> (slices [n_clips, slice values] float32 on the
+        device, ranges [n_clips, 2] int64: first non-zero value / last + 1 as absolute indices, -1 / 0 for a silent clip).  out: a
+        buffer of that shape to write into (what the stage leaves out keeps its contents)."""
+        import torch
+        shapes = [_pcm_shape(c) for c in clips]
+        ch = shapes[0][1]
+        assert all(s[1] == ch for s in shapes)
+        values = lib.awm_debug_clip_slice_values(ch)
+        if out is None:
+            out = torch.zeros((len(clips), values), dtype=torch.float32, device=clips[0].device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == len(clips) * values
+        ptrs = (C.c_void_p * len(clips))(*[_dev_ptr(c) for c in clips])
+        frames = (C.c_size_t * len(clips))(*[s[0] for s in shapes])
+        ranges = np.zeros((len(clips), 2), np.int64)
+        _check(lib.awm_debug_clip_stage_d(self._h, len(clips), ptrs, frames, ch, sample_rate, _dev_ptr(out), _np(ranges)),
+               "awm_debug_clip_stage_d")
+        return out, ranges
 
     def add_get_watermark(self, key, payload_hex, pcm, out, sample_rate=44100):
         """awm_add_get_watermark_d: add_watermark into `out`, then get_watermark of `out`, as one call (`get` starts a chunk as soon as
@@ -1165,9 +1200,10 @@ class Context:
         return self._patterns_keys(lib.awm_get_watermark_keys_file, "awm_get_watermark_keys_file", keys, os.fsencode(in_path),
                                    C.byref(raw_in) if raw_in is not None else None)
 
-    def get_watermark_batch(self, key, clips, n_threads=0, max_out_per_clip=64):
+    def get_watermark_batch(self, key, clips, n_threads=0, max_out_per_clip=64, sample_rate=44100):
         """get_watermark of many independent resident clips (same channel count), spread over the context's work lanes;
-        returns one pattern list per clip."""
+        returns one pattern list per clip.  sample_rate != 44100 (awm_get_watermark_batch_rate_d): every clip is at that rate, its
+        result that of the clip resampled to 44.1 kHz."""
         if not clips:
             return []
         shapes = [_pcm_shape(c) for c in clips]
@@ -1178,8 +1214,12 @@ class Context:
         n_out = (C.c_int * len(clips))()
         while True:
             buf = self._pattern_buffer(len(clips) * max_out_per_clip)
-            _check(lib.awm_get_watermark_batch_d(self._h, key_bytes(key), len(clips), ptrs, frames, ch, n_threads, max_out_per_clip,
-                                                 C.cast(buf, C.c_void_p), n_out), "awm_get_watermark_batch_d")
+            if sample_rate != 44100:
+                _check(lib.awm_get_watermark_batch_rate_d(self._h, key_bytes(key), len(clips), ptrs, frames, ch, sample_rate, n_threads,
+                                                          max_out_per_clip, C.cast(buf, C.c_void_p), n_out), "awm_get_watermark_batch_rate_d")
+            else:
+                _check(lib.awm_get_watermark_batch_d(self._h, key_bytes(key), len(clips), ptrs, frames, ch, n_threads, max_out_per_clip,
+                                                     C.cast(buf, C.c_void_p), n_out), "awm_get_watermark_batch_d")
             most = max(n_out)
             if most <= max_out_per_clip:
                 return [patterns_to_dicts(buf, n_out[i], i * max_out_per_clip) for i in range(len(clips))]

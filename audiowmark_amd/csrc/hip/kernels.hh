@@ -510,6 +510,17 @@ struct ClipSrc { const float *data; long long n_values; long long pad_start; };
  * margin_values >= slice_values writes whole slices. */
 hipError_t launch_clip_pad (hipStream_t st, const ClipSrc *src /* device */, int n_clips, float *dst, long long slice_values, long long margin_values,
                             long long *range);
+/* K10c: stage 0 for a group of clips at ANOTHER RATE whose ratio the fixed-ratio resampler takes -- K10 straight into the padded slices,
+ * one launch per group (blockIdx.y = clip).  Clip i has n_in frames at its rate at `in` (4-byte aligned; nothing outside them is read) and
+ * n44 frames at 44.1 kHz: output frame m of K10's definition above, for the stream "hl - 1 null frames, the clip, null frames for ever",
+ * goes to pad_start + m C of slice i, zeros go to the rest of the window that launch_clip_pad writes, and range receives the non-silent
+ * range of what was stored -- slices and ranges are bit for bit those of launch_resample into a buffer and launch_clip_pad from it.  The
+ * products and sums are K10's through K10's own tap code.  Forms, chosen as launch_resample chooses: 48 -> 44.1 kHz stereo with every input
+ * 8-byte aligned (stereo_aligned): a phase per thread; other ratios, stereo_aligned: table and the tile's window in LDS; everything else
+ * the generic taps.  ctab / hl / np / step / n_channels come from `a`; max_n44 is the largest n44 of the group. */
+struct ClipResampleSrc { const float *in; long long n_in, n44, pad_start; };
+hipError_t launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src /* device */, int n_clips, long long max_n44,
+                                     bool stereo_aligned, float *dst, long long slice_values, long long margin_values, long long *range);
 }
 
 namespace awmk {

@@ -1314,9 +1314,18 @@ launch_limiter (hipStream_t st, float *data, long long n_frames, int n_channels,
 constexpr int RS_TILE = 1024;             // outputs per workgroup
 constexpr int RS_MAX_TAB = 12288;         // floats of LDS for the coefficient table (48 KiB)
 
+/* Where the taps put their results (one copy of the taps for every kernel that runs them): put (k, v) is value k, put2 (k, v) stereo
+ * frame k, counted from the sink's own origin.  ResampleStore: K10 / K10w, a plain store. */
+struct ResampleStore
+{
+  float *out;
+  __device__ __forceinline__ void put (long long k, float v) { out[k] = v; }
+  __device__ __forceinline__ void put2 (long long k, float2 v) { reinterpret_cast<float2 *> (out)[k] = v; }
+};
+
 /* stereo, input window of the tile staged in LDS (zero extended): s_in[0] is input frame first0; same products and sums as below */
-__device__ __forceinline__ void
-resample_output_staged (const ResampleArgs& a, const float *tab, int stride, long long m, const float2 *s_in, unsigned int t_rel)
+template<class Sink> __device__ __forceinline__ void
+resample_output_staged (const ResampleArgs& a, const float *tab, int stride, long long m, const float2 *s_in, unsigned int t_rel, Sink& sink)
 {
   // m step = tile0 step + t_rel - r0, r0 = (tile0 step) mod np: window start and phase relative to the tile in 32 bits (a 64-bit
   // division per output cost as much as the taps)
@@ -1334,13 +1343,13 @@ resample_output_staged (const ResampleArgs& a, const float *tab, int stride, lon
       s0 = __fadd_rn (s0, __fadd_rn (__fmul_rn (x1.x, c1[i]), __fmul_rn (x2.x, c2[i])));
       s1 = __fadd_rn (s1, __fadd_rn (__fmul_rn (x1.y, c1[i]), __fmul_rn (x2.y, c2[i])));
     }
-  reinterpret_cast<float2 *> (a.out)[m] = make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f));
+  sink.put2 (m, make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f)));
 }
 
 // one output frame m; tab: coefficient rows with `stride` floats each (LDS or global).  K10w: a.in[0] is input frame in0 of the stream
-// (a.n_in frames from there, zeros everywhere else) and the result goes to a.out[k]
-template<int CT> __device__ __forceinline__ void
-resample_output (const ResampleArgs& a, const float *tab, int stride, long long m, long long in0, long long k)
+// (a.n_in frames from there, zeros everywhere else) and the result goes to frame k of the sink
+template<int CT, class Sink> __device__ __forceinline__ void
+resample_output (const ResampleArgs& a, const float *tab, int stride, long long m, long long in0, long long k, Sink& sink)
 {
   const int C = CT ? CT : a.n_channels, hl = a.hl;
   const long long t = m * a.step;
@@ -1373,7 +1382,7 @@ resample_output (const ResampleArgs& a, const float *tab, int stride, long long 
             s0 = __fadd_rn (s0, __fadd_rn (__fmul_rn (x1.x, c1[i]), __fmul_rn (x2.x, c2[i])));
             s1 = __fadd_rn (s1, __fadd_rn (__fmul_rn (x1.y, c1[i]), __fmul_rn (x2.y, c2[i])));
           }
-      reinterpret_cast<float2 *> (a.out)[k] = make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f));
+      sink.put2 (k, make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f)));
       return;
     }
   for (int c = 0; c < C; c++)
@@ -1386,13 +1395,13 @@ resample_output (const ResampleArgs& a, const float *tab, int stride, long long 
           const float x2 = (j2 >= 0 && j2 < a.n_in) ? a.in[j2 * C + c] : 0.f;
           sum = __fadd_rn (sum, __fadd_rn (__fmul_rn (x1, c1[i]), __fmul_rn (x2, c2[i])));
         }
-      a.out[k * C + c] = __fsub_rn (sum, 1e-20f);
+      sink.put (k * C + c, __fsub_rn (sum, 1e-20f));
     }
 }
-template<int CT> __device__ __forceinline__ void
-resample_output (const ResampleArgs& a, const float *tab, int stride, long long m)
+template<int CT, class Sink> __device__ __forceinline__ void
+resample_output (const ResampleArgs& a, const float *tab, int stride, long long m, Sink& sink)
 {
-  resample_output<CT> (a, tab, stride, m, 0, m);
+  resample_output<CT> (a, tab, stride, m, 0, m, sink);
 }
 
 /* Neighbouring outputs use different phases, i.e. different coefficient rows: read from global memory every load
@@ -1413,6 +1422,7 @@ resample_kernel (ResampleArgs a, int lds_floats, int in_span, int tiles_per_wg)
   const bool in_lds = lds_floats > 0;
   const bool staged = CT == 2 && in_lds && in_span > 0;
   float2 *s_in = reinterpret_cast<float2 *> (s_tab + ((lds_floats + 1) & ~1));
+  ResampleStore sink { a.out };
   if (in_lds)
     {
       const int n = (a.np + 1) * a.hl;
@@ -1449,11 +1459,11 @@ resample_kernel (ResampleArgs a, int lds_floats, int in_span, int tiles_per_wg)
           if (m >= a.n_out)
             break;
           if (staged)
-            resample_output_staged (a, s_tab, stride, m, s_in, r0 + (unsigned int) (q * 256 + threadIdx.x) * (unsigned int) a.step);
+            resample_output_staged (a, s_tab, stride, m, s_in, r0 + (unsigned int) (q * 256 + threadIdx.x) * (unsigned int) a.step, sink);
           else if (in_lds)
-            resample_output<CT> (a, s_tab, stride, m);
+            resample_output<CT> (a, s_tab, stride, m, sink);
           else
-            resample_output<CT> (a, a.ctab, a.hl, m);
+            resample_output<CT> (a, a.ctab, a.hl, m, sink);
         }
     }
 }
@@ -1471,8 +1481,10 @@ resample_kernel (ResampleArgs a, int lds_floats, int in_span, int tiles_per_wg)
  * window read a two-way conflict (measured: 1.54 ms for an hour at 48 kHz against 0.96 ms for the way up, whose starts never skip).
  * There the threads are numbered by WINDOW START instead -- `step` slots per replica, the 13 starts that belong to no phase idle --
  * and neighbouring lanes read neighbouring words.  Going up, neighbouring phases share or succeed each other's start already. */
-template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
-resample_phase_kernel (ResampleArgs a, int tiles_per_wg)
+/* The kernel's body, for K10 and for K10c (clip_resample_pad_phase_kernel): outputs 0 .. n_out - 1 of the stream whose n_in frames are at
+ * `in`, tiles dealt to the workgroups by blockIdx.x, every result through the sink. */
+template<int NP, int STEP, int HL, int R, int J, class Sink> __device__ __forceinline__ void
+resample_phase_body (const float *ctab, const float *in, long long n_in, long long n_out, int tiles_per_wg, Sink& sink)
 {
   constexpr int SPAN = R * J * STEP + 2 * HL;                 // input frames of a tile
   constexpr int TILE = R * J * NP;                            // outputs of a tile
@@ -1489,16 +1501,15 @@ resample_phase_kernel (ResampleArgs a, int tiles_per_wg)
 #pragma unroll
   for (int i = 0; i < HL; i++)
     {
-      c1[i] = a.ctab[ph * HL + i];
-      c2[i] = a.ctab[(NP - ph) * HL + i];
+      c1[i] = ctab[ph * HL + i];
+      c2[i] = ctab[(NP - ph) * HL + i];
     }
-  const float2 *in2 = reinterpret_cast<const float2 *> (a.in);
-  float2 *out2 = reinterpret_cast<float2 *> (a.out);
+  const float2 *in2 = reinterpret_cast<const float2 *> (in);
   for (int t = 0; t < tiles_per_wg; t++)
     {
       const long long tile = (long long) blockIdx.x * tiles_per_wg + t;
       const long long tile0 = tile * TILE;
-      if (tile0 >= a.n_out)
+      if (tile0 >= n_out)
         break;                                                                 // (uniform)
       const long long first0 = tile * (R * J * STEP) - (HL - 1);              // input frame of s_in[0]
       if (t)
@@ -1506,7 +1517,7 @@ resample_phase_kernel (ResampleArgs a, int tiles_per_wg)
       for (int i = tid; i < SPAN; i += WG)
         {
           const long long j = first0 + i;
-          s_in[i] = (j >= 0 && j < a.n_in) ? in2[j] : make_float2 (0.f, 0.f);
+          s_in[i] = (j >= 0 && j < n_in) ? in2[j] : make_float2 (0.f, 0.f);
         }
       __syncthreads();
       if (active)
@@ -1516,7 +1527,7 @@ resample_phase_kernel (ResampleArgs a, int tiles_per_wg)
             {
               const int q = rep + R * j;                                       // which group of np outputs of the tile
               const long long m = tile0 + p + NP * q;
-              if (m >= a.n_out)
+              if (m >= n_out)
                 break;
               const float2 *p1 = s_in + b_p + STEP * q, *p2 = p1 + 2 * HL - 1;
               float s0 = 1e-20f, s1 = 1e-20f;
@@ -1527,10 +1538,17 @@ resample_phase_kernel (ResampleArgs a, int tiles_per_wg)
                   s0 = __fadd_rn (s0, __fadd_rn (__fmul_rn (x1.x, c1[i]), __fmul_rn (x2.x, c2[i])));
                   s1 = __fadd_rn (s1, __fadd_rn (__fmul_rn (x1.y, c1[i]), __fmul_rn (x2.y, c2[i])));
                 }
-              out2[m] = make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f));
+              sink.put2 (m, make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f)));
             }
         }
     }
+}
+
+template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
+resample_phase_kernel (ResampleArgs a, int tiles_per_wg)
+{
+  ResampleStore sink { a.out };
+  resample_phase_body<NP, STEP, HL, R, J> (a.ctab, a.in, a.n_in, a.n_out, tiles_per_wg, sink);
 }
 
 /* (measurement knob) 1 (default): the phase-per-thread kernel for stereo 48 <-> 44.1 kHz | 0: the generic kernel for every ratio */
@@ -1716,8 +1734,8 @@ launch_resample_mix_multi (hipStream_t st, const ResampleMixArgs& a)
  * keeps it for `tiles_per_wg` consecutive tiles of RS_TILE outputs of its slice (staging the table costs as much as the taps of one tile);
  * window start and phase come from each tile's first GLOBAL output index, the staged window is filled from the slice's resident input
  * and zeros.  The taps are resample_output_staged / resample_output themselves. */
-template<int CT> __device__ __forceinline__ void
-resample_slice_body (const ResampleArgs& a0, const ResampleSlice& s, int lds_floats, int in_span, int tiles_per_wg)
+template<int CT, class Sink> __device__ __forceinline__ void
+resample_slice_body (const ResampleArgs& a0, const ResampleSlice& s, int lds_floats, int in_span, int tiles_per_wg, Sink& sink)
 {
   extern __shared__ float s_tab[];
   if ((long long) blockIdx.x * tiles_per_wg * RS_TILE >= s.n_out)
@@ -1725,7 +1743,6 @@ resample_slice_body (const ResampleArgs& a0, const ResampleSlice& s, int lds_flo
   ResampleArgs a = a0;
   a.in = s.in;
   a.n_in = s.n_in;
-  a.out = s.out;
   const int stride = a.hl | 1;
   const bool in_lds = lds_floats > 0;
   const bool staged = CT == 2 && in_lds && in_span > 0;
@@ -1767,11 +1784,11 @@ resample_slice_body (const ResampleArgs& a0, const ResampleSlice& s, int lds_flo
           if (k >= s.n_out)
             break;
           if (staged)
-            resample_output_staged (a, s_tab, stride, k, s_in, r0 + (unsigned int) (q * 256 + threadIdx.x) * (unsigned int) a.step);
+            resample_output_staged (a, s_tab, stride, k, s_in, r0 + (unsigned int) (q * 256 + threadIdx.x) * (unsigned int) a.step, sink);
           else if (in_lds)
-            resample_output<CT> (a, s_tab, stride, s.out0 + k, s.in0, k);
+            resample_output<CT> (a, s_tab, stride, s.out0 + k, s.in0, k, sink);
           else
-            resample_output<CT> (a, a.ctab, a.hl, s.out0 + k, s.in0, k);
+            resample_output<CT> (a, a.ctab, a.hl, s.out0 + k, s.in0, k, sink);
         }
     }
 }
@@ -1779,12 +1796,14 @@ template<int CT> __global__ void __launch_bounds__ (256)
 resample_slices_kernel (ResampleArgs a, const ResampleSlice *slices, int lds_floats, int in_span, int tiles_per_wg)
 {
   const ResampleSlice s = slices[blockIdx.y];
-  resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg);
+  ResampleStore sink { s.out };
+  resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg, sink);
 }
 template<int CT> __global__ void __launch_bounds__ (256)
 resample_slice_kernel (ResampleArgs a, ResampleSlice s, int lds_floats, int in_span, int tiles_per_wg)
 {
-  resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg);
+  ResampleStore sink { s.out };
+  resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg, sink);
 }
 
 static hipError_t
@@ -4025,6 +4044,39 @@ launch_nonzero_range (hipStream_t st, const float *data, long long n_values, uns
   return hipGetLastError();
 }
 
+/* the non-silent range a workgroup of WAVES waves found in its part of a slice -- first = smallest absolute index of a non-zero value
+ * (all ones: none), last = largest + 1 -- into the clip's range[0 .. 1]: one pair of atomics per workgroup */
+template<int WAVES> __device__ __forceinline__ void
+clip_range_commit (unsigned long long first, unsigned long long last, unsigned long long *range)
+{
+  for (int o = 32; o > 0; o >>= 1)
+    {
+      const unsigned long long f = __shfl_xor (first, o), l = __shfl_xor (last, o);
+      first = f < first ? f : first;
+      last = l > last ? l : last;
+    }
+  __shared__ unsigned long long s_first[WAVES], s_last[WAVES];
+  if ((threadIdx.x & 63) == 0)
+    {
+      s_first[threadIdx.x >> 6] = first;
+      s_last[threadIdx.x >> 6] = last;
+    }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    {
+      for (int w = 1; w < WAVES; w++)
+        {
+          first = s_first[w] < first ? s_first[w] : first;
+          last = s_last[w] > last ? s_last[w] : last;
+        }
+      if (first != ~0ULL)
+        {
+          atomicMin (range, first);                           // all ones (= -1 as the signed value the consumers read) if nothing is found
+          atomicMax (range + 1, last);
+        }
+    }
+}
+
 /* kernels.hh launch_clip_pad: grid (parts, clips); slice_values % 4 == 0, 16-byte stores */
 __global__ void __launch_bounds__ (256)
 clip_pad_kernel (const ClipSrc *src, float *dst, long long slice_values, long long margin_values, unsigned long long *range)
@@ -4060,32 +4112,7 @@ clip_pad_kernel (const ClipSrc *src, float *dst, long long slice_values, long lo
         }
       out[q] = make_float4 (v[0], v[1], v[2], v[3]);
     }
-  for (int o = 32; o > 0; o >>= 1)
-    {
-      const unsigned long long f = __shfl_xor (first, o), l = __shfl_xor (last, o);
-      first = f < first ? f : first;
-      last = l > last ? l : last;
-    }
-  __shared__ unsigned long long s_first[4], s_last[4];
-  if ((threadIdx.x & 63) == 0)
-    {
-      s_first[threadIdx.x >> 6] = first;
-      s_last[threadIdx.x >> 6] = last;
-    }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    {
-      for (int w = 1; w < 4; w++)
-        {
-          first = s_first[w] < first ? s_first[w] : first;
-          last = s_last[w] > last ? s_last[w] : last;
-        }
-      if (first != ~0ULL)
-        {
-          atomicMin (range + 2 * blockIdx.y, first);          // all ones (= -1 as the signed value the consumers read) if nothing is found
-          atomicMax (range + 2 * blockIdx.y + 1, last);
-        }
-    }
+  clip_range_commit<4> (first, last, range + 2 * blockIdx.y);
 }
 
 __global__ void
@@ -4117,6 +4144,122 @@ launch_clip_pad (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, lo
   auto *r = reinterpret_cast<unsigned long long *> (range);
   hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
   hipLaunchKernelGGL (clip_pad_kernel, dim3 (128, unsigned (n_clips)), dim3 (256), 0, st, src, dst, slice_values, margin_values, r);
+  return hipGetLastError();
+}
+
+/* K10c (kernels.hh launch_clip_resample_pad): K10 into the padded slices.  The sink of the taps: output frame m of the clip goes to
+ * pad_start + m C of its slice, and the thread keeps the first / last absolute index of the non-zero values it stored. */
+struct ClipStore
+{
+  float *out;                           // the clip's output 0 in its slice
+  unsigned long long at0;               // absolute index of out[0] in the group's buffer
+  unsigned long long first = ~0ULL, last = 0;
+  __device__ __forceinline__ void note (unsigned long long at, float v)
+  {
+    if (v != 0.f)
+      {
+        first = at < first ? at : first;
+        last = at + 1 > last ? at + 1 : last;
+      }
+  }
+  __device__ __forceinline__ void put (long long k, float v)
+  {
+    out[k] = v;
+    note (at0 + (unsigned long long) k, v);
+  }
+  __device__ __forceinline__ void put2 (long long k, float2 v)
+  {
+    reinterpret_cast<float2 *> (out)[k] = v;
+    note (at0 + 2 * (unsigned long long) k, v.x);
+    note (at0 + 2 * (unsigned long long) k + 1, v.y);
+  }
+};
+
+/* the zeros of a slice's window on either side of the clip, [pad_start - margin, pad_start) and [pad_start + n_values, ... + margin) rounded
+ * out to whole quads and clipped to the slice as clip_pad_kernel writes them; the clip's workgroups share them */
+__device__ __forceinline__ void
+clip_window_zeros (float *slice, long long pad_start, long long n_values, long long slice_values, long long margin_values)
+{
+  long long lo = (pad_start - margin_values) / 4 * 4, hi = (pad_start + n_values + margin_values + 3) / 4 * 4;
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > slice_values ? slice_values : hi;
+  const long long end = pad_start + n_values, n_front = pad_start - lo, n_zeros = n_front + (hi - end);
+  const long long stride = (long long) gridDim.x * blockDim.x;
+  for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n_zeros; i += stride)
+    slice[i < n_front ? lo + i : end + (i - n_front)] = 0.f;
+}
+
+/* the generic form: resample_slice_body (table and, for stereo with 8-byte aligned inputs, the tile's window in LDS) on the clip as a
+ * stream of its own; grid (workgroups of the longest clip, clips) */
+template<int CT> __global__ void __launch_bounds__ (256)
+clip_resample_pad_kernel (ResampleArgs a, const ClipResampleSrc *src, float *dst, long long slice_values, long long margin_values,
+                          unsigned long long *range, int lds_floats, int in_span, int tiles_per_wg)
+{
+  const ClipResampleSrc c = src[blockIdx.y];
+  const long long slice0 = (long long) blockIdx.y * slice_values;
+  ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
+  clip_window_zeros (dst + slice0, c.pad_start, c.n44 * a.n_channels, slice_values, margin_values);
+  const ResampleSlice s { c.in, c.n_in, 0, 0, c.n44, nullptr };
+  resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg, sink);
+  clip_range_commit<4> (sink.first, sink.last, range + 2 * blockIdx.y);
+}
+
+/* the phase-per-thread form (resample_phase_body): a clip starts at output 0, so its tiles start on multiples of np */
+template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
+clip_resample_pad_phase_kernel (const float *ctab, const ClipResampleSrc *src, float *dst, long long slice_values, long long margin_values,
+                                unsigned long long *range, int tiles_per_wg)
+{
+  const ClipResampleSrc c = src[blockIdx.y];
+  const long long slice0 = (long long) blockIdx.y * slice_values;
+  ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
+  clip_window_zeros (dst + slice0, c.pad_start, c.n44 * 2, slice_values, margin_values);
+  if ((long long) blockIdx.x * tiles_per_wg * (R * J * NP) < c.n44)                // (uniform: a shorter clip of the group)
+    resample_phase_body<NP, STEP, HL, R, J> (ctab, c.in, c.n_in, c.n44, tiles_per_wg, sink);
+  clip_range_commit<((STEP > NP ? STEP : NP) * R + 63) / 64> (sink.first, sink.last, range + 2 * blockIdx.y);
+}
+
+hipError_t
+launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src, int n_clips, long long max_n44, bool stereo_aligned,
+                          float *dst, long long slice_values, long long margin_values, long long *range)
+{
+  if (n_clips <= 0 || slice_values <= 0)
+    return hipSuccess;
+  if (n_clips > 65535 || max_n44 < 0 || slice_values % 4 || margin_values < 0 || (reinterpret_cast<uintptr_t> (dst) & 15)
+      || a.hl < 1 || a.np < 1 || a.step < 1 || a.n_channels < 1 || !a.ctab)
+    return hipErrorInvalidValue;
+  if (g_clip_poison)
+    if (hipError_t e = hipMemsetAsync (dst, 0xff, size_t (n_clips) * size_t (slice_values) * sizeof (float), st))
+      return e;
+  auto *r = reinterpret_cast<unsigned long long *> (range);
+  hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
+  const bool stereo = a.n_channels == 2 && stereo_aligned;
+  // the forms and their tiles per workgroup as launch_resample / launch_resample_slices choose them: at least 4096 workgroups over all
+  // clips first, then up to 8 tiles per workgroup
+  if (g_resample_phase && stereo && a.np == 147 && a.step == 160 && a.hl == 18)
+    {
+      constexpr int NP = 147, STEP = 160, HL = 18, R = 2, J = 8;
+      const long long n_tiles = std::max<long long> (1, (max_n44 + R * J * NP - 1) / (R * J * NP));
+      const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_clips / 4096)));
+      const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg), unsigned (n_clips));
+      hipLaunchKernelGGL ((clip_resample_pad_phase_kernel<NP, STEP, HL, R, J>), grid, dim3 ((STEP * R + 63) / 64 * 64), 0, st, a.ctab, src, dst,
+                          slice_values, margin_values, r, tiles_per_wg);
+      return hipGetLastError();
+    }
+  const long long n_tiles = std::max<long long> (1, (max_n44 + RS_TILE - 1) / RS_TILE);
+  const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_clips / 4096)));
+  const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg), unsigned (n_clips));
+  const int want = (a.np + 1) * (a.hl | 1);
+  const int lds_floats = want <= RS_MAX_TAB ? want : 0;
+  const long long span = ((long long) (RS_TILE - 1) * a.step) / a.np + 2 + 2LL * a.hl;
+  const bool stage = stereo && lds_floats > 0 && span <= 4096 && (long long) RS_TILE * a.step + a.np < (1LL << 31);
+  const int in_span = stage ? int (span) : 0;
+  const size_t lds_bytes = size_t ((lds_floats + 1) & ~1) * sizeof (float) + size_t (in_span) * sizeof (float2);
+  if (stereo)
+    hipLaunchKernelGGL (clip_resample_pad_kernel<2>, grid, dim3 (256), lds_bytes, st, a, src, dst, slice_values, margin_values, r, lds_floats, in_span,
+                        tiles_per_wg);
+  else
+    hipLaunchKernelGGL (clip_resample_pad_kernel<0>, grid, dim3 (256), lds_bytes, st, a, src, dst, slice_values, margin_values, r, lds_floats, in_span,
+                        tiles_per_wg);
   return hipGetLastError();
 }
 

@@ -145,6 +145,18 @@ fill_pattern (const ResultSet::Pattern& p, awm_pattern& o)
     o.bits[b] = p.bit_vec[b];
 }
 
+// the results of a batch of clips: clip i's patterns to out[i * max_out_per_clip ...], their number (possibly more) to n_out[i]
+void
+fill_batch_patterns (const std::vector<ResultSet>& sets, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  for (size_t i = 0; i < sets.size(); i++)
+    {
+      n_out[i] = int (sets[i].patterns.size());
+      for (size_t j = 0; j < sets[i].patterns.size() && j < max_out_per_clip; j++)
+        fill_pattern (sets[i].patterns[j], out[i * max_out_per_clip + j]);
+    }
+}
+
 DeviceWav
 make_wav (const float *pcm_d, size_t n_frames, int n_channels)
 {
@@ -153,6 +165,14 @@ make_wav (const float *pcm_d, size_t n_frames, int n_channels)
   w.n_frames = n_frames;
   w.n_channels = n_channels;
   w.sample_rate = Params::mark_sample_rate;
+  return w;
+}
+
+DeviceWav
+make_wav_rate (const float *pcm_d, size_t n_frames, int n_channels, int rate)
+{
+  DeviceWav w = make_wav (pcm_d, n_frames, n_channels);
+  w.sample_rate = rate;
   return w;
 }
 
@@ -451,7 +471,7 @@ struct RateConverter
   size_t stream_frames (size_t n_in) const
   {
     if (fixed)
-      return size_t ((static_cast<unsigned __int128> (n_in) * unsigned (fixed->np) + unsigned (fixed->step) - 1) / unsigned (fixed->step));
+      return resample_fixed_frames (*fixed, n_in);
     return var.stream_frames (n_in);
   }
 };
@@ -3149,12 +3169,7 @@ awm_get_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, 
   std::vector<ResultSet> sets;
   if (int rc = get_watermark_batch_device (ctx, { capi_key (key) }, clips, sets, n_threads))
     return rc;
-  for (size_t i = 0; i < n_clips; i++)
-    {
-      n_out[i] = int (sets[i].patterns.size());
-      for (size_t j = 0; j < sets[i].patterns.size() && j < max_out_per_clip; j++)
-        fill_pattern (sets[i].patterns[j], out[i * max_out_per_clip + j]);
-    }
+  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
   return 0;
 }
 
@@ -3175,13 +3190,127 @@ awm_get_watermark_batch_keys_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clip
   std::vector<ResultSet> sets;
   if (int rc = get_watermark_batch_device (ctx, {}, clips, sets, n_threads, &clip_keys))
     return rc;
-  for (size_t i = 0; i < n_clips; i++)
-    {
-      n_out[i] = int (sets[i].patterns.size());
-      for (size_t j = 0; j < sets[i].patterns.size() && j < max_out_per_clip; j++)
-        fill_pattern (sets[i].patterns[j], out[i * max_out_per_clip + j]);
-    }
+  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
   return 0;
+}
+
+/* `get` at another sample rate: the rate's converter and every clip's length at 44.1 kHz.  AWM_ERR_ARG (message set) for what
+ * awm_resample_frames answers with 0 */
+static int
+clip_rates (awm_ctx *ctx, int sample_rate, size_t n_clips, const size_t *n_frames, ClipRates& rates)
+{
+  const RateConverter conv = rate_converter (ctx, sample_rate, Params::mark_sample_rate);
+  if (!conv.ok())
+    {
+      set_error (string_printf ("resampling from old_rate=%d to new_rate=%d not implemented", sample_rate, int (Params::mark_sample_rate)));
+      return AWM_ERR_ARG;
+    }
+  rates.sample_rate = sample_rate;
+  rates.table = conv.fixed;
+  rates.n44.clear();
+  for (size_t i = 0; i < n_clips; i++)
+    rates.n44.push_back (conv.stream_frames (n_frames[i]));
+  return 0;
+}
+
+static int
+get_watermark_batch_rate (awm_ctx *ctx, const uint8_t key[16], const uint8_t *keys, size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
+                          int n_channels, int sample_rate, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  ClipRates rates;
+  if (int rc = clip_rates (ctx, sample_rate, n_clips, n_frames, rates))
+    return rc;
+  if (!n_clips)
+    return 0;
+  std::vector<DeviceWav> clips;
+  for (size_t i = 0; i < n_clips; i++)
+    clips.push_back (make_wav_rate (pcm_d[i], n_frames[i], n_channels, sample_rate));
+  std::vector<Key> clip_keys;
+  if (keys)
+    clip_keys = key_list_from (keys, int (n_clips));
+  std::vector<ResultSet> sets;
+  if (int rc = get_watermark_batch_device (ctx, keys ? std::vector<Key> {} : std::vector<Key> { capi_key (key) }, clips, sets, n_threads,
+                                           keys ? &clip_keys : nullptr, &rates))
+    return rc;
+  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
+  return 0;
+}
+
+int
+awm_get_watermark_rate_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels,
+                          int sample_rate, size_t max_out, awm_pattern *out)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_get_watermark_d (ctx, key, pcm_d, n_frames, n_channels, max_out, out);
+  AWM_ENTER (ctx);
+  if ((n_frames && !pcm_d) || n_channels < 1 || (max_out && !out))
+    {
+      set_error ("awm_get_watermark_rate_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  ClipRates rates;
+  if (int rc = clip_rates (ctx, sample_rate, 1, &n_frames, rates))
+    return rc;
+  DeviceWav wav44;
+  if (int rc = resample_to_mark_rate (ctx, ctx, rates, make_wav_rate (pcm_d, n_frames, n_channels, sample_rate), rates.n44[0], wav44))
+    return rc;
+  ResultSet rs;
+  if (int rc = get_watermark_device (ctx, { capi_key (key) }, wav44, rs))
+    return rc;
+  for (size_t i = 0; i < rs.patterns.size() && i < max_out; i++)
+    fill_pattern (rs.patterns[i], out[i]);
+  return int (rs.patterns.size());
+}
+
+int
+awm_get_watermark_batch_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
+                                int n_channels, int sample_rate, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_get_watermark_batch_d (ctx, key, n_clips, pcm_d, n_frames, n_channels, n_threads, max_out_per_clip, out, n_out);
+  AWM_ENTER (ctx);
+  if (n_clips && (!pcm_d || !n_frames || !n_out || (max_out_per_clip && !out)))
+    {
+      set_error ("awm_get_watermark_batch_rate_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  return get_watermark_batch_rate (ctx, key, nullptr, n_clips, pcm_d, n_frames, n_channels, sample_rate, n_threads, max_out_per_clip, out, n_out);
+}
+
+int
+awm_get_watermark_batch_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
+                                     int n_channels, int sample_rate, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_get_watermark_batch_keys_d (ctx, keys, n_clips, pcm_d, n_frames, n_channels, n_threads, max_out_per_clip, out, n_out);
+  AWM_ENTER (ctx);
+  if (n_clips && (!keys || !pcm_d || !n_frames || !n_out || (max_out_per_clip && !out)))
+    {
+      set_error ("awm_get_watermark_batch_keys_rate_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  return get_watermark_batch_rate (ctx, nullptr, keys, n_clips, pcm_d, n_frames, n_channels, sample_rate, n_threads, max_out_per_clip, out, n_out);
+}
+
+int
+awm_debug_clip_stage_d (awm_ctx *ctx, size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels, int sample_rate,
+                        float *slices_d, long long *range_out)
+{
+  AWM_ENTER (ctx);
+  if (!n_clips || !pcm_d || !n_frames || n_channels < 1)
+    {
+      set_error ("awm_debug_clip_stage_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  ClipRates rates;
+  const bool at_rate = sample_rate != Params::mark_sample_rate;
+  if (at_rate)
+    if (int rc = clip_rates (ctx, sample_rate, n_clips, n_frames, rates))
+      return rc;
+  std::vector<DeviceWav> clips;
+  for (size_t i = 0; i < n_clips; i++)
+    clips.push_back (make_wav_rate (pcm_d[i], n_frames[i], n_channels, sample_rate));
+  return clip_stage_device (ctx, clips, at_rate ? &rates : nullptr, slices_d, range_out);
 }
 
 int
@@ -3513,14 +3642,6 @@ awm_decode_chunk_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, siz
 }
 
 /* ---- speed detection (reference wmspeed.cc) ---------------------------------------------------------------------- */
-static DeviceWav
-make_wav_rate (const float *pcm_d, size_t n_frames, int n_channels, int rate)
-{
-  DeviceWav w = make_wav (pcm_d, n_frames, n_channels);
-  w.sample_rate = rate;
-  return w;
-}
-
 void
 awm_set_speed_params (int detect_speed, int detect_speed_patient, double try_speed, double test_speed)
 {

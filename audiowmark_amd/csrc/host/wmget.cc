@@ -1417,9 +1417,14 @@ static int g_staged_threads = 0;
 extern "C" void awm_debug_set_staged_threads (int n) { g_staged_threads = n < 0 ? 0 : (n > 8 ? 8 : n); }
 
 static bool
+clip_is_short (size_t n_frames)
+{
+  return n_frames > 0 && n_frames < (mark_block_frame_count() + 2) * Params::frame_size;
+}
+static bool
 clip_is_short (const DeviceWav& w)
 {
-  return w.n_frames > 0 && w.n_frames < (mark_block_frame_count() + 2) * Params::frame_size;
+  return clip_is_short (w.n_frames);
 }
 
 /* The key tables of a group of clips with ONE KEY PER CLIP: built on host threads (2226 up / down draws, three shuffles per key:
@@ -1728,11 +1733,109 @@ extern "C" void awm_debug_set_clip_pad_margin (int frames) { g_clip_pad_margin =
 static int g_group_force_fallback = 0;
 extern "C" void awm_debug_set_group_fallback (int on) { g_group_force_fallback = on; }
 
+int
+resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, const DeviceWav& in, size_t n44, DeviceWav& out)
+{
+  const int C = in.n_channels;
+  if (int rc = lane->ws_rate.reserve (std::max<size_t> (16, n44 * C * sizeof (float)))) return rc;
+  out.data = lane->ws_rate.as<float>();
+  out.n_frames = n44;
+  out.n_channels = C;
+  out.sample_rate = Params::mark_sample_rate;
+  if (!rates.table)
+    return resample_var_device (ctx, lane, in.data, in.n_frames, C, double (Params::mark_sample_rate) / rates.sample_rate, lane->ws_rate.as<float>(), n44);
+  awmk::ResampleArgs ra {};
+  ra.in = in.data;
+  ra.n_in = (long long) in.n_frames;
+  ra.n_channels = C;
+  ra.ctab = rates.table->ctab.as<float>();
+  ra.hl = rates.table->hl;
+  ra.np = rates.table->np;
+  ra.step = rates.table->step;
+  ra.out = lane->ws_rate.as<float>();
+  ra.n_out = (long long) n44;
+  ProfScope ps (ctx, PROF_RESAMPLE, double (in.n_frames + n44) * C * 4.0, lane->stream);      // every input and output sample once
+  AWM_HIP_CHECK (awmk::launch_resample (lane->stream, ra));
+  return 0;
+}
+
+/* Stage 0 of a group: the padded copies of clips[which[0 .. gn)] (reference wmget.cc:830-867, START position: data + padding cover one long
+ * block) in `slices` and the non-silent range of every slice, on the lane's stream.  At 44.1 kHz a copy (launch_clip_pad); with `rates`, whose
+ * table is set, the clips are resampled straight into their slices (K10c, launch_clip_resample_pad). */
+struct ClipStage0
+{
+  std::vector<long long> pad_start, n_values;       // per clip, in values at 44.1 kHz
+  long long              margin_values = 0;
+  long long             *d_range = nullptr;         // device, [gn][2]
+};
+static int
+clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& clips, const size_t *which, size_t gn, const ClipRates *rates,
+                    float *slices, size_t slice_values, ClipStage0& s0)
+{
+  hipStream_t st = lane->stream;
+  const int C = clips[which[0]].n_channels;
+  const size_t n = slice_values / 3;
+  const size_t desc_bytes = gn * (rates ? sizeof (awmk::ClipResampleSrc) : sizeof (awmk::ClipSrc));
+  if (int rc = lane->pin_group.reserve (desc_bytes)) return rc;
+  if (int rc = lane->ws_group.reserve (desc_bytes + gn * 2 * sizeof (long long))) return rc;
+  AWM_HIP_CHECK (stream_wait (st));                                             // (the previous group's descriptors are consumed)
+  s0.pad_start.resize (gn);
+  s0.n_values.resize (gn);
+  for (size_t i = 0; i < gn; i++)
+    {
+      s0.n_values[i] = (long long) ((rates ? rates->n44[which[i]] : clips[which[i]].n_frames) * C);
+      s0.pad_start[i] = (long long) (n + (n - s0.n_values[i]));
+    }
+  s0.d_range = reinterpret_cast<long long *> (lane->ws_group.as<char>() + desc_bytes);
+  // (only CLIP_PAD_MARGIN frames of zeros on either side of a clip are written: nothing further out is read -- kernels.hh)
+  s0.margin_values = (long long) std::max (g_clip_pad_margin, CLIP_PAD_MARGIN) * C;
+  if (!rates)
+    {
+      auto *desc = lane->pin_group.as<awmk::ClipSrc>();
+      for (size_t i = 0; i < gn; i++)
+        desc[i] = { clips[which[i]].data, s0.n_values[i], s0.pad_start[i] };
+      auto *d_desc = lane->ws_group.as<awmk::ClipSrc>();
+      AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
+      AWM_HIP_CHECK (awmk::launch_clip_pad (st, d_desc, int (gn), slices, (long long) slice_values, s0.margin_values, s0.d_range));
+      return 0;
+    }
+  auto *desc = lane->pin_group.as<awmk::ClipResampleSrc>();
+  uintptr_t bits = 0;
+  long long max_n44 = 0;
+  double samples = 0;
+  for (size_t i = 0; i < gn; i++)
+    {
+      const DeviceWav& wav = clips[which[i]];
+      desc[i] = { wav.data, (long long) wav.n_frames, s0.n_values[i] / C, s0.pad_start[i] };
+      bits |= reinterpret_cast<uintptr_t> (wav.data);
+      max_n44 = std::max (max_n44, desc[i].n44);
+      samples += double (wav.n_frames) + double (desc[i].n44);
+    }
+  auto *d_desc = lane->ws_group.as<awmk::ClipResampleSrc>();
+  AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
+  awmk::ResampleArgs ra {};
+  ra.n_channels = C;
+  ra.ctab = rates->table->ctab.as<float>();
+  ra.hl = rates->table->hl;
+  ra.np = rates->table->np;
+  ra.step = rates->table->step;
+  ProfScope ps (ctx, PROF_CLIP_RESAMPLE, samples * C * 4.0, st);               // every input and output sample of the group once
+  AWM_HIP_CHECK (awmk::launch_clip_resample_pad (st, ra, d_desc, int (gn), max_n44, (bits & 7) == 0, slices, (long long) slice_values,
+                                                 s0.margin_values, s0.d_range));
+  return 0;
+}
+
+extern "C" size_t
+awm_debug_clip_slice_values (int n_channels)
+{
+  return n_channels < 1 ? 0 : 3 * (mark_block_frame_count() + 5) * Params::frame_size * size_t (n_channels);
+}
+
 /* clip_keys (may be null): one key per clip -- clip i is searched and decoded with (*clip_keys)[i] alone (key_list is not used then) */
 static int
 clip_batch_staged (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_list, const std::vector<DeviceWav>& clips, const std::vector<size_t>& which,
                    std::vector<ResultSet>& result_sets, const std::vector<Key> *clip_keys = nullptr, WorkLane *table_lane = nullptr,
-                   const DeviceGroupTables *all_tables = nullptr, const std::vector<int> *slot_of_clip = nullptr)
+                   const DeviceGroupTables *all_tables = nullptr, const std::vector<int> *slot_of_clip = nullptr, const ClipRates *rates = nullptr)
 {
   const size_t count = mark_block_frame_count();
   const int n_bits_a = int (mark_data_frame_count() / params().frames_per_bit);
@@ -1785,33 +1888,20 @@ clip_batch_staged (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_lis
         // (profiling only) frames of the group's slices that carry samples: a clip's own frames + one at each edge
         double live = 0;
         for (size_t i = 0; i < gn; i++)
-          live += double (clips[which[g0 + i]].n_frames) / Params::frame_size + 2;
+          live += double (rates ? rates->n44[which[g0 + i]] : clips[which[g0 + i]].n_frames) / Params::frame_size + 2;
         lane->prof_live_fraction = std::min (1.0, live / (double (gn) * double (slice_frames) / Params::frame_size));
       }
-      // stage 0: padded copies (reference wmget.cc:830-867, START position: data + padding cover one long block) and the
-      // non-silent range of every slice
+      // stage 0: the padded copies and the non-silent range of every slice
       if (int rc = lane->ws_clip.reserve (gn * slice_values * sizeof (float))) return rc;
-      const size_t desc_bytes = gn * sizeof (awmk::ClipSrc);
-      if (int rc = lane->pin_group.reserve (desc_bytes)) return rc;
-      if (int rc = lane->ws_group.reserve (desc_bytes + gn * 2 * sizeof (long long))) return rc;
-      AWM_HIP_CHECK (stream_wait (st));                                             // (the previous group's descriptors are consumed)
-      auto *desc = lane->pin_group.as<awmk::ClipSrc>();
-      for (size_t i = 0; i < gn; i++)
-        {
-          const DeviceWav& wav = clips[which[g0 + i]];
-          desc[i] = { wav.data, (long long) wav.n_values(), (long long) (n + (n - wav.n_values())) };
-        }
-      auto *d_desc = lane->ws_group.as<awmk::ClipSrc>();
-      auto *d_range = reinterpret_cast<long long *> (lane->ws_group.as<char>() + desc_bytes);
-      AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
-      // (only CLIP_PAD_MARGIN frames of zeros on either side of a clip are written: nothing further out is read -- kernels.hh)
-      const long long margin_values = (long long) std::max (g_clip_pad_margin, CLIP_PAD_MARGIN) * C;
-      AWM_HIP_CHECK (awmk::launch_clip_pad (st, d_desc, int (gn), lane->ws_clip.as<float>(), (long long) slice_values, margin_values, d_range));
+      ClipStage0 s0;
+      if (int rc = clip_stage0_launch (ctx, lane, clips, which.data() + g0, gn, rates, lane->ws_clip.as<float>(), slice_values, s0)) return rc;
+      long long *const d_range = s0.d_range;
+      const long long margin_values = s0.margin_values;
       DeviceWav group;
       group.data = lane->ws_clip.as<float>();
       group.n_frames = gn * slice_frames;
       group.n_channels = C;
-      group.sample_rate = clips[which[g0]].sample_rate;
+      group.sample_rate = rates ? int (Params::mark_sample_rate) : clips[which[g0]].sample_rate;
       std::vector<ResultSet *> ptrs;
       for (auto& cs : chunk_sets)
         ptrs.push_back (&cs);
@@ -1889,8 +1979,8 @@ clip_batch_staged (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_lis
                   slice.data = group.data + i * slice_values;
                   slice.n_frames = slice_frames;
                   // (that search scans and transforms the whole slice: the zeros the padded copy left out are written now)
-                  const long long lo = std::max<long long> (0, (desc[i].pad_start - margin_values) / 4 * 4);
-                  const long long hi = std::min<long long> ((long long) slice_values, (desc[i].pad_start + desc[i].n_values + margin_values + 3) / 4 * 4);
+                  const long long lo = std::max<long long> (0, (s0.pad_start[i] - margin_values) / 4 * 4);
+                  const long long hi = std::min<long long> ((long long) slice_values, (s0.pad_start[i] + s0.n_values[i] + margin_values + 3) / 4 * 4);
                   float *slice_w = lane->ws_clip.as<float>() + i * slice_values;
                   if (lo > 0)
                     AWM_HIP_CHECK (hipMemsetAsync (slice_w, 0, size_t (lo) * sizeof (float), st));
@@ -1964,10 +2054,21 @@ clip_batch_staged (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_lis
  * get_watermark_device per clip. */
 int
 get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, const std::vector<DeviceWav>& clips,
-                            std::vector<ResultSet>& result_sets, int n_threads, const std::vector<Key> *clip_keys)
+                            std::vector<ResultSet>& result_sets, int n_threads, const std::vector<Key> *clip_keys, const ClipRates *rates)
 {
   // clip_keys: one key per clip (clip i is decoded with (*clip_keys)[i] alone); else every clip with the whole key_list
   auto keys_of = [&] (size_t i) { return clip_keys ? std::vector<Key> { (*clip_keys)[i] } : key_list; };
+  // one clip on one lane: at another rate its 44.1 kHz copy goes into the lane's workspace first
+  auto get_one = [&] (WorkLane *lane, bool spread, size_t i) {
+    if (!rates)
+      return get_watermark_on (ctx, lane, spread, keys_of (i), clips[i], result_sets[i]);
+    if (!rates->n44[i])
+      return 0;                                      // an empty clip: no patterns
+    DeviceWav wav44;
+    if (int rc = resample_to_mark_rate (ctx, lane, *rates, clips[i], rates->n44[i], wav44))
+      return rc;
+    return get_watermark_on (ctx, lane, spread, keys_of (i), wav44, result_sets[i]);
+  };
   result_sets.clear();
   result_sets.resize (clips.size());
   if (clips.empty())
@@ -1978,12 +2079,13 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
     {
       // the speed search and the stretched copy of a clip live in per-context buffers: one clip after the other
       for (size_t i = 0; i < clips.size(); i++)
-        if (int rc = get_watermark_on (ctx, ctx, true, keys_of (i), clips[i], result_sets[i]))
+        if (int rc = get_one (ctx, true, i))
           return rc;
       return 0;
     }
+  // (at another rate a clip is short by its 44.1 kHz length, and the groups take only what K10c resamples: the fixed-ratio rates)
   for (size_t i = 0; i < clips.size(); i++)
-    (clip_is_short (clips[i]) ? staged : threaded).push_back (i);
+    ((rates ? rates->table && clip_is_short (rates->n44[i]) : clip_is_short (clips[i])) ? staged : threaded).push_back (i);
   if (!staged.empty())
     {
       if (!ctx->ev_sync)
@@ -2049,11 +2151,11 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
         workers.emplace_back ([&, t] {
           ParamsBind bind (pv);
           (void) hipSetDevice (ctx->device);
-          rcs[t] = clip_batch_staged (ctx, staged_lanes[t], key_list, clips, share[t], result_sets, clip_keys, table_lanes[t], all_ptr, &slot_of_clip);
+          rcs[t] = clip_batch_staged (ctx, staged_lanes[t], key_list, clips, share[t], result_sets, clip_keys, table_lanes[t], all_ptr, &slot_of_clip, rates);
           if (rcs[t])
             messages[t] = last_error();
         });
-      rcs[0] = clip_batch_staged (ctx, staged_lanes[0], key_list, clips, share[0], result_sets, clip_keys, table_lanes[0], all_ptr, &slot_of_clip);
+      rcs[0] = clip_batch_staged (ctx, staged_lanes[0], key_list, clips, share[0], result_sets, clip_keys, table_lanes[0], all_ptr, &slot_of_clip, rates);
       for (auto& w : workers)
         w.join();
       for (int t = 0; t < n_staged_threads; t++)
@@ -2109,7 +2211,7 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
         if (t >= threaded.size())
           break;
         const size_t i = threaded[t];
-        if (int r = get_watermark_on (ctx, lanes[li], false, keys_of (i), clips[i], result_sets[i]))
+        if (int r = get_one (lanes[li], false, i))
           {
             rc[li] = r;
             err[li] = last_error();
@@ -2130,6 +2232,34 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
         set_error (err[li]);
         return rc[li];
       }
+  return 0;
+}
+
+/* (awm_debug_clip_stage_d) stage 0 of ONE group alone, into the caller's buffer on the context's stream */
+int
+clip_stage_device (awm_ctx *ctx, const std::vector<DeviceWav>& clips, const ClipRates *rates, float *slices, long long *range_out)
+{
+  if (clips.empty() || clips.size() > size_t (CLIP_GROUP) || !slices || !range_out || (reinterpret_cast<uintptr_t> (slices) & 15)
+      || (rates && !rates->table))
+    {
+      set_error ("awm_debug_clip_stage_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  std::vector<size_t> which;
+  for (size_t i = 0; i < clips.size(); i++)
+    {
+      if (!clips[i].data || clips[i].n_channels != clips[0].n_channels || !clip_is_short (rates ? rates->n44[i] : clips[i].n_frames))
+        {
+          set_error ("awm_debug_clip_stage_d: not a short clip");
+          return AWM_ERR_ARG;
+        }
+      which.push_back (i);
+    }
+  const size_t slice_values = awm_debug_clip_slice_values (clips[0].n_channels);
+  ClipStage0 s0;
+  if (int rc = clip_stage0_launch (ctx, ctx, clips, which.data(), clips.size(), rates, slices, slice_values, s0)) return rc;
+  AWM_HIP_CHECK (hipMemcpyAsync (range_out, s0.d_range, clips.size() * 2 * sizeof (long long), hipMemcpyDeviceToHost, ctx->stream));
+  AWM_HIP_CHECK (hipStreamSynchronize (ctx->stream));
   return 0;
 }
 

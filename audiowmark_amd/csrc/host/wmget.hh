@@ -55,8 +55,21 @@ int decode_chunks (awm_ctx *ctx, const std::vector<Key>& key_list, const DeviceW
 int get_watermark_device (awm_ctx *ctx, const std::vector<Key>& key_list, const DeviceWav& wav, ResultSet& result_set);
 // many independent inputs at once (one lane + host thread per input in flight); n_threads <= 0: as many as there are lanes
 // clip_keys: one key per clip instead of the key list for all
+// rates (may be null): the clips are at another sample rate -- clips[i] is the clip as the caller holds it, its result that of the clip
+// resampled to 44.1 kHz (WavChunkLoader, reference wavchunkloader.cc:70-71, 200-216)
+struct ClipRates
+{
+  int                  sample_rate = 0;
+  const ResampleTable *table = nullptr;    // the fixed-ratio resampler's table, or null: the VResampler with ratio 44100 / sample_rate
+  std::vector<size_t>  n44;                // frames of clip i at 44.1 kHz
+};
 int get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, const std::vector<DeviceWav>& clips,
-                                std::vector<ResultSet>& result_sets, int n_threads, const std::vector<Key> *clip_keys = nullptr);
+                                std::vector<ResultSet>& result_sets, int n_threads, const std::vector<Key> *clip_keys = nullptr,
+                                const ClipRates *rates = nullptr);
+// stage 0 of one group of 1 .. 64 short clips alone (awm_debug_clip_stage_d): slices and host ranges [n][2], synchronised
+int clip_stage_device (awm_ctx *ctx, const std::vector<DeviceWav>& clips, const ClipRates *rates, float *slices, long long *range_out);
+// the 44.1 kHz copy of one clip (n44 frames) in the lane's own grow-only workspace, on the lane's stream: what the decoders are given
+int resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, const DeviceWav& in, size_t n44, DeviceWav& out);
 
 // soft bits of whole blocks (fft_range + mix_decode), raw mix order
 int block_soft_bits (awm_ctx *ctx, KeyTables *kt, const DeviceWav& wav, const std::vector<size_t>& index,

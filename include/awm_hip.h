@@ -390,6 +390,25 @@ int awm_get_watermark_keys_d (awm_ctx *ctx, const uint8_t *keys, int n_keys, con
 int awm_get_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const float *const *pcm_d,
                                const size_t *n_frames, int n_channels, int n_threads, size_t max_out_per_clip,
                                awm_pattern *out, int *n_out);
+/* The device-pointer `get` for material at ANOTHER SAMPLE RATE (HLS and video audio: 48 kHz): what the reference's loader does in front
+ * of the decoder (WavChunkLoader resamples every chunk to 44.1 kHz, wavchunkloader.cc:70-71, 200-216), for one resident stream, a batch
+ * of clips, and a batch with a key per clip.  Definition: with y_i = what awm_resample_d (clip i, sample_rate -> 44100) writes,
+ * awm_resample_frames (n_frames[i], sample_rate, 44100) frames, the result for clip i is field for field what awm_get_watermark_d returns
+ * for y_i (sync_index is an index into the 44.1 kHz stream, as in the reference) -- with that clip's key in the keys form.  One rate per
+ * call.  A clip is short (the grouped path of awm_get_watermark_batch_d) by its 44.1 kHz length.  Short clips at a rate of the fixed-ratio
+ * Resampler are resampled STRAIGHT INTO the group's padded slices (K10c, one launch per group: no resampled copies, no launch per clip,
+ * no second read); long clips, VResampler rates and calls with a speed parameter set resample each clip into a grow-only workspace of its
+ * lane first (awm_ctx_trim gives these back).  sample_rate == 44100 is the existing function.  AWM_ERR_ARG with nothing enqueued and n_out
+ * untouched: sample_rate <= 0, or a ratio that neither zita class takes (awm_resample_frames gives 0).  Empty clips: n_out[i] = 0.
+ * Not offered in this form: a rate per clip, the sharded / multi-context batches. */
+int awm_get_watermark_rate_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels,
+                              int sample_rate, size_t max_out, awm_pattern *out);
+int awm_get_watermark_batch_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const float *const *pcm_d,
+                                    const size_t *n_frames, int n_channels, int sample_rate, int n_threads,
+                                    size_t max_out_per_clip, awm_pattern *out, int *n_out);
+int awm_get_watermark_batch_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const float *const *pcm_d,
+                                         const size_t *n_frames, int n_channels, int sample_rate, int n_threads,
+                                         size_t max_out_per_clip, awm_pattern *out, int *n_out);
 /* decode() of one chunk only (wmget.cc:886-939) -- the unit `get` is sharded by */
 int awm_decode_chunk_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames,
                         int n_channels, int first_chunk, size_t max_out, awm_pattern *out);
@@ -653,6 +672,13 @@ int  awm_debug_add_payloads_tile (void);          /* outputs per pass of the fus
 void awm_debug_set_fft_pair (int on);      /* stereo add: both channels' transforms pipelined in one wave (default) | one after the other */
 void awm_debug_set_clip_poison (int on);    /* clip batches: the padded slices are filled with NaNs before the copies are written (the copy writes a clip and 2048
                                             * frames of zeros on either side, not the rest of the padding: a consumer that read further would change its result) */
+size_t awm_debug_clip_slice_values (int n_channels);   /* clip batches: values of one padded slice, 3 (block frames + 5) 1024 C with the parameters in force */
+int  awm_debug_clip_stage_d (awm_ctx *ctx, size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels, int sample_rate,
+                             float *slices_d, long long *range_out);
+                                           /* stage 0 of a group alone: the padded slices of 1 .. 64 short clips into slices_d (n_clips x slice values, 16-byte aligned) on the
+                                            * context's stream, their non-silent ranges to range_out (host, [n_clips][2]), synchronised.  44100: the padded copy; a rate of the
+                                            * fixed-ratio Resampler: K10c.  AWM_ERR_ARG: a VResampler rate, a clip that is not short, more than 64 clips.  Honours
+                                            * awm_debug_set_clip_poison */
 void awm_debug_set_clip_pad_margin (int frames); /* clip batches: frames of zeros written on either side of a clip (default and minimum 2048; one slice = 6693 frames
                                             * or more: whole slices, the A side of the measurement in tools/gpu_clip_margin_ab.py) */
 void awm_debug_set_staged_threads (int n);  /* clip batches: host threads (= lanes) working on groups of clips; 0 = default (4; 2 with a key per clip only where the
