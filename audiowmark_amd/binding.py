@@ -145,6 +145,20 @@ class SegmentPlan(C.Structure):
 
 
 lib.awm_add_segment_plan.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(SegmentPlan)]
+
+
+class StreamRatePlan(C.Structure):
+    """awm_stream_rate_plan (include/awm_hip.h): the look-ahead of the tile stream at another sample rate"""
+    _fields_ = [(n, C.c_uint64) for n in ("limiter_block", "down_ahead", "mix_ahead", "min_tile")] + \
+               [(n, C.c_int) for n in ("down_hl", "down_np", "down_step", "up_hl", "up_np", "up_step")]
+
+
+lib.awm_add_stream_rate_plan.argtypes = [C.c_int, C.POINTER(StreamRatePlan)]
+lib.awm_add_stream_create_rate_at.argtypes = [_vp, _vp, C.c_char_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(_vp)]
+lib.awm_add_stream_create_payloads_rate_at.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(_vp)]
+lib.awm_add_stream_sample_rate.argtypes = [_vp]
+lib.awm_add_stream_sample_rate.restype = C.c_int
+lib.awm_debug_resample_span_d.argtypes = [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_int)]
 lib.awm_debug_add_segments_fused_in_use.argtypes = []
 lib.awm_debug_add_segments_fused_in_use.restype = C.c_int
 lib.awm_debug_alloc_bytes.argtypes = []
@@ -416,6 +430,13 @@ def add_segment_plan(sample_rate, zero_frames, n_frames):
     plan = SegmentPlan()
     _check(lib.awm_add_segment_plan(int(sample_rate), int(zero_frames), int(n_frames), C.byref(plan)), "awm_add_segment_plan")
     return {name: int(getattr(plan, name)) for name, _ in SegmentPlan._fields_}
+
+
+def add_stream_rate_plan(sample_rate):
+    """awm_add_stream_rate_plan: the look-ahead and the smallest tile of the tile stream at another sample rate, as a dict (no GPU needed)"""
+    plan = StreamRatePlan()
+    _check(lib.awm_add_stream_rate_plan(int(sample_rate), C.byref(plan)), "awm_add_stream_rate_plan")
+    return {name: int(getattr(plan, name)) for name, _ in StreamRatePlan._fields_}
 
 
 def tab_sync_bits(key, clip_mode=False):
@@ -852,15 +873,20 @@ class Context:
                "awm_debug_sync_db_sliding_rows_d")
         self.synchronize()
 
-    def add_watermark_tiles(self, key, payload_hex, pcm, tile_frames1024=128, zero_frames=0):
+    def add_watermark_tiles(self, key, payload_hex, pcm, tile_frames1024=128, zero_frames=0, sample_rate=44100):
         """awm_add_stream: `add` as a tile loop over resident PCM (the bounded-memory form the file path uses); returns the
         concatenated output -- bit-identical to add_watermark on the whole stream.  zero_frames: the stream starts that many
-        samples into the frame / block grid (add_stream_watermark's zero_frames, reference wmadd.cc:501-526)."""
+        samples into the frame / block grid (add_stream_watermark's zero_frames, reference wmadd.cc:501-526).  sample_rate: another
+        rate takes awm_add_stream_create_rate_at, whose tiles are counted at that rate."""
         import torch
         n, ch = _pcm_shape(pcm)
         h = C.c_void_p()
-        _check(lib.awm_add_stream_create_at(self._h, key_bytes(key), payload_hex.encode(), ch, tile_frames1024, zero_frames, C.byref(h)),
-               "awm_add_stream_create_at")
+        if sample_rate == 44100:
+            _check(lib.awm_add_stream_create_at(self._h, key_bytes(key), payload_hex.encode(), ch, tile_frames1024, zero_frames, C.byref(h)),
+                   "awm_add_stream_create_at")
+        else:
+            _check(lib.awm_add_stream_create_rate_at(self._h, key_bytes(key), payload_hex.encode(), ch, sample_rate, tile_frames1024, zero_frames,
+                                                     C.byref(h)), "awm_add_stream_create_rate_at")
         out = torch.empty_like(pcm)
         tile = tile_frames1024 * 1024
         done_p = (C.c_void_p * 3)()
@@ -887,9 +913,10 @@ class Context:
         assert written == n
         return out
 
-    def add_watermark_payloads_tiles(self, key, payloads, pcm, tile_frames1024=128, zero_frames=0):
+    def add_watermark_payloads_tiles(self, key, payloads, pcm, tile_frames1024=128, zero_frames=0, sample_rate=44100):
         """awm_add_stream with P payloads: the tile loop over resident PCM for one input and many payloads; returns the list of
-        concatenated outputs, outs[p] == add_watermark_tiles(key, payloads[p], pcm, tile_frames1024, zero_frames) bit for bit."""
+        concatenated outputs, outs[p] == add_watermark_tiles(key, payloads[p], pcm, tile_frames1024, zero_frames) bit for bit.
+        sample_rate: another rate takes awm_add_stream_create_payloads_rate_at."""
         import torch
         payloads = list(payloads)
         check_payload_outputs(payloads, pcm, None)
@@ -897,8 +924,12 @@ class Context:
         P = len(payloads)
         hexes = (C.c_char_p * P)(*[p.encode() for p in payloads])
         h = C.c_void_p()
-        _check(lib.awm_add_stream_create_payloads_at(self._h, key_bytes(key), hexes, P, ch, tile_frames1024, zero_frames, C.byref(h)),
-               "awm_add_stream_create_payloads_at")
+        if sample_rate == 44100:
+            _check(lib.awm_add_stream_create_payloads_at(self._h, key_bytes(key), hexes, P, ch, tile_frames1024, zero_frames, C.byref(h)),
+                   "awm_add_stream_create_payloads_at")
+        else:
+            _check(lib.awm_add_stream_create_payloads_rate_at(self._h, key_bytes(key), hexes, P, ch, sample_rate, tile_frames1024, zero_frames,
+                                                              C.byref(h)), "awm_add_stream_create_payloads_rate_at")
         outs = [torch.empty_like(pcm) for _ in payloads]
         tile = tile_frames1024 * 1024
         done_p = (C.c_void_p * (3 * P))()
@@ -941,6 +972,17 @@ class Context:
         out = _out_tensor(out, (m, ch), torch.float32, pcm.device, "resample")
         _check(lib.awm_resample_d(self._h, _dev_ptr(pcm), n, ch, rate_in, rate_out, _dev_ptr(out), m), "awm_resample_d")
         return out
+
+    def resample_span(self, resident, in0, out0, n_out, rate_in, rate_out, out=None):
+        """awm_debug_resample_span_d: outputs out0 .. out0 + n_out - 1 of `resample` from the frames in0 .. in0 + len (resident) - 1 of the
+        stream (everything else reads as zero) -> (out, 1 if the phase-per-thread kernel ran else 0)"""
+        import torch
+        n, ch = _pcm_shape(resident)
+        out = _out_tensor(out, (n_out, ch) if resident.dim() > 1 else (n_out,), torch.float32, resident.device, "resample_span")
+        used = C.c_int(-1)
+        _check(lib.awm_debug_resample_span_d(self._h, _dev_ptr(resident), n, in0, out0, n_out, ch, rate_in, rate_out, _dev_ptr(out), C.byref(used)),
+               "awm_debug_resample_span_d")
+        return out, used.value
 
     def resample_ratio_frames(self, n_frames, n_channels, ratio, rate=44100, max_in_seconds=-1.0):
         return lib.awm_resample_ratio_frames(n_frames, n_channels, rate, ratio, max_in_seconds)

@@ -159,6 +159,12 @@ struct ResampleSlice
 hipError_t launch_resample_slices (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, int n_slices, long long max_n_out,
                                    bool stereo_aligned);
 hipError_t launch_resample_slice (hipStream_t st, const ResampleArgs& a, const ResampleSlice& slice);     // one slice, arguments by value
+/* K10s: one slice whose caller chooses where it begins (the tile stream at another rate, which ends every launch on a multiple of np and
+ * carries the rest).  Stereo 48 <-> 44.1 kHz with every pointer 8-byte aligned, out0 a multiple of np and awm_debug_set_resample_phase on
+ * runs K10's phase-per-thread body at the slice's place in its stream (resample_span_takes_phase says whether); everything else is
+ * launch_resample_slice.  The bits are the same either way. */
+bool       resample_span_takes_phase (const ResampleArgs& a, const ResampleSlice& slice);
+hipError_t launch_resample_span (hipStream_t st, ResampleArgs a, ResampleSlice slice);
 
 /* K10m: K10 on the way up (44.1 -> 48 kHz: np 160, step 147, hl 16) for the watermark signals of up to ADD_MULTI_TILE outputs of ONE
  * stereo stream, fused with K11: out[o][m] = K10's output m of wm44[o] + orig[m], one rounded add, and block_max[o] receives the maxima of

@@ -1483,14 +1483,19 @@ resample_kernel (ResampleArgs a, int lds_floats, int in_span, int tiles_per_wg)
  * and neighbouring lanes read neighbouring words.  Going up, neighbouring phases share or succeed each other's start already. */
 /* The kernel's body, for K10 and for K10c (clip_resample_pad_phase_kernel): outputs 0 .. n_out - 1 of the stream whose n_in frames are at
  * `in`, tiles dealt to the workgroups by blockIdx.x, every result through the sink. */
-template<int NP, int STEP, int HL, int R, int J, class Sink> __device__ __forceinline__ void
-resample_phase_body (const float *ctab, const float *in, long long n_in, long long n_out, int tiles_per_wg, Sink& sink)
+/* SPAN (K10s, launch_resample_span): the same for a run of outputs that begins at group `group0` of NP outputs of its stream -- output
+ * group0 NP + k is local output k, which is what the sink is given -- with `in` holding the stream's frames in0 .. in0 + n_in - 1 and
+ * zeros everywhere else.  A tile's window then starts group0 STEP frames later (64 bits) and is fetched from in[j - in0]; the slots, the
+ * coefficients and everything behind the staging of s_in are untouched, and with SPAN false both values are constants that fold away. */
+template<int NP, int STEP, int HL, int R, int J, bool SPAN = false, class Sink> __device__ __forceinline__ void
+resample_phase_body (const float *ctab, const float *in, long long n_in, long long n_out, int tiles_per_wg, Sink& sink, long long group0 = 0,
+                     long long in0 = 0)
 {
-  constexpr int SPAN = R * J * STEP + 2 * HL;                 // input frames of a tile
+  constexpr int IN_SPAN = R * J * STEP + 2 * HL;              // input frames of a tile
   constexpr int TILE = R * J * NP;                            // outputs of a tile
   constexpr int SLOTS = STEP > NP ? STEP : NP;                // threads per replica
   constexpr int WG = (SLOTS * R + 63) / 64 * 64;
-  __shared__ float2 s_in[SPAN];
+  __shared__ float2 s_in[IN_SPAN];
   const int tid = threadIdx.x;
   const int rep = tid < SLOTS * R ? tid / SLOTS : 0, slot = tid < SLOTS * R ? tid - rep * SLOTS : 0;
   const int p_of_slot = STEP > NP ? (slot * NP + STEP - 1) / STEP : slot;              // the phase whose window starts at frame `slot`, if any
@@ -1511,10 +1516,10 @@ resample_phase_body (const float *ctab, const float *in, long long n_in, long lo
       const long long tile0 = tile * TILE;
       if (tile0 >= n_out)
         break;                                                                 // (uniform)
-      const long long first0 = tile * (R * J * STEP) - (HL - 1);              // input frame of s_in[0]
+      const long long first0 = (SPAN ? group0 * STEP - in0 : 0) + tile * (R * J * STEP) - (HL - 1);     // frame of s_in[0], counted from in[0]
       if (t)
         __syncthreads();                                                       // the previous tile's windows have been read
-      for (int i = tid; i < SPAN; i += WG)
+      for (int i = tid; i < IN_SPAN; i += WG)
         {
           const long long j = first0 + i;
           s_in[i] = (j >= 0 && j < n_in) ? in2[j] : make_float2 (0.f, 0.f);
@@ -1594,6 +1599,25 @@ launch_resample (hipStream_t st, const ResampleArgs& a)
     hipLaunchKernelGGL (resample_kernel<2>, grid, dim3 (256), lds_bytes, st, a, lds_floats, in_span, tiles_per_wg);
   else
     hipLaunchKernelGGL (resample_kernel<0>, grid, dim3 (256), lds_bytes, st, a, lds_floats, in_span, tiles_per_wg);
+  return hipGetLastError();
+}
+
+template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
+resample_phase_span_kernel (const float *ctab, ResampleSlice s, int tiles_per_wg)
+{
+  ResampleStore sink { s.out };
+  resample_phase_body<NP, STEP, HL, R, J, true> (ctab, s.in, s.n_in, s.n_out, tiles_per_wg, sink, s.out0 / NP, s.in0);
+}
+
+template<int NP, int STEP, int HL> static hipError_t
+launch_resample_phase_span (hipStream_t st, const ResampleArgs& a, const ResampleSlice& s)
+{
+  constexpr int R = 2, J = 8;
+  const long long n_tiles = (s.n_out + R * J * NP - 1) / (R * J * NP);
+  const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles / 4096)));     // as launch_resample_phase
+  const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg));
+  hipLaunchKernelGGL ((resample_phase_span_kernel<NP, STEP, HL, R, J>), grid, dim3 (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64), 0, st, a.ctab, s,
+                      tiles_per_wg);
   return hipGetLastError();
 }
 
@@ -1848,6 +1872,26 @@ launch_resample_slice (hipStream_t st, const ResampleArgs& a, const ResampleSlic
     return hipErrorInvalidValue;
   const bool aligned = (reinterpret_cast<uintptr_t> (slice.in) & 7) == 0 && (reinterpret_cast<uintptr_t> (slice.out) & 7) == 0;
   return launch_resample_slices_any (st, a, nullptr, &slice, 1, slice.n_out, aligned);
+}
+
+/* K10s (kernels.hh): a slice that begins on a multiple of np through the phase-per-thread kernel, everything else through K10w */
+bool
+resample_span_takes_phase (const ResampleArgs& a, const ResampleSlice& s)
+{
+  const bool aligned = (reinterpret_cast<uintptr_t> (s.in) & 7) == 0 && (reinterpret_cast<uintptr_t> (s.out) & 7) == 0;
+  const bool ratio = (a.np == 147 && a.step == 160 && a.hl == 18) || (a.np == 160 && a.step == 147 && a.hl == 16);
+  return g_resample_phase && a.n_channels == 2 && aligned && ratio && s.out0 >= 0 && s.out0 % a.np == 0;
+}
+hipError_t
+launch_resample_span (hipStream_t st, ResampleArgs a, ResampleSlice s)
+{
+  if (s.n_out <= 0)
+    return hipSuccess;
+  if (!resample_span_takes_phase (a, s))
+    return launch_resample_slice (st, a, s);
+  if (a.np == 147)
+    return launch_resample_phase_span<147, 160, 18> (st, a, s);
+  return launch_resample_phase_span<160, 147, 16> (st, a, s);
 }
 
 constexpr int MIX_RUN = 2048;            // values per thread group run: 256 threads x 8

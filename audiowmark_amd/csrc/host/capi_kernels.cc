@@ -215,7 +215,7 @@ static int
 add_mix_impl (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
               const int8_t *frame_mod_dev, double water_delta, size_t first_frame,
               const float *halo_before_d, const float *halo_after_d, float *block_max_d, size_t first_block, size_t n_blocks,
-              WorkLane *lane = nullptr)
+              WorkLane *lane = nullptr, int delta_only = 0)
 {
   hipStream_t st = lane ? lane->stream : ctx->stream;
   awmk::AddMixArgs a {};
@@ -232,6 +232,7 @@ add_mix_impl (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames
   a.first_block = (long long) first_block;
   a.n_blocks = (long long) n_blocks;
   a.frames_per_span = frames_per_span (ctx, (long long) (n_frames + 1023) / 1024);
+  a.delta_only = delta_only;
   {
     ProfScope ps (ctx, PROF_ADD_MIX, double (n_frames) * n_channels * 8.0, st);     // read + write every sample once
     AWM_HIP_CHECK (awmk::launch_add_mix (st, ctx->tabs, a));
@@ -603,7 +604,12 @@ add_full_rate (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frame
 static int g_add_payloads_fused = 1, g_add_payloads_fused_in_use = 0;        // (awm_debug_set_add_payloads_fused, below)
 static int add_mix_payloads_impl (awm_ctx *ctx, const float *pcm_in_d, float *const *out_d, size_t n_payloads, size_t n_frames, int n_channels,
                                   const int8_t *const *frame_mod_dev, double water_delta, size_t first_frame, const float *halo_before_d,
-                                  const float *halo_after_d, float *const *block_max_d, size_t first_block, size_t n_blocks);
+                                  const float *halo_after_d, float *const *block_max_d, size_t first_block, size_t n_blocks, int delta_only = 0);
+struct AddStreamRate;                 // the state of the object at another sample rate (below)
+static void add_stream_rate_release (AddStreamRate *r);
+static float *add_stream_rate_input (awm_add_stream *s);
+static int add_stream_rate_push (awm_add_stream *s, size_t n_frames, int last, const float **out_d, size_t out_frames[3], const char *who);
+static awmk::ResampleArgs resample_table_args (const ResampleTable& t, int C);
 
 /* ---- add as a tile loop (reference add_stream_watermark, wmadd.cc:520-589: the stream is processed frame by frame with
  * WatermarkSynth holding one frame back (wmadd.cc:220-222) and the Limiter holding up to two blocks back (limiter.cc:51-64)).
@@ -631,6 +637,7 @@ struct awm_add_stream
   size_t    skipped = 0;              // zero_frames rounded down to whole 1024-sample frames
   size_t    prefix = 0;               // zero_frames % 1024: zeros in front of the caller's first sample inside tile 0
   size_t    first_block = 0;          // limiter block of sample `skipped`: block_max[0]
+  AddStreamRate *rate = nullptr;      // another sample rate (awm_add_stream_create_rate_at): of the slots above only `mix` is used then
 };
 
 static int
@@ -773,12 +780,15 @@ awm_add_stream_destroy (awm_add_stream *s)
     b.release();
   for (int i = 0; i < 3; i++)
     s->in[i].release();
+  add_stream_rate_release (s->rate);
   delete s;
 }
 
 float *
 awm_add_stream_input (awm_add_stream *s)
 {
+  if (s && s->rate)
+    return add_stream_rate_input (s);
   return s && !s->finished ? s->in[s->t % 3].as<float>() + s->prefix * s->C : nullptr;
 }
 
@@ -792,6 +802,8 @@ add_stream_push (awm_add_stream *s, size_t n_frames, int last, const float **out
       set_error (std::string (who) + ": every tile but the last one must be full, nothing may follow the last one");
       return AWM_ERR_ARG;
     }
+  if (s->rate)
+    return add_stream_rate_push (s, n_frames, last, out_d, out_frames, who);
   const int C = s->C;
   const size_t N = Params::frame_size, P = s->P;
   const long long t = s->t;
@@ -908,6 +920,460 @@ awm_add_stream_push_payloads (awm_add_stream *s, size_t n_frames, int last, cons
       return AWM_ERR_ARG;
     }
   return add_stream_push (s, n_frames, last, out_d, out_frames, "awm_add_stream_push_payloads");
+}
+
+/* ---- the tile loop at another sample rate (include/awm_hip.h).  add_full_rate's stages at GLOBAL sample and frame
+ * indices, each continuing where the previous push stopped:
+ *   down (K10s)  the 44.1 kHz samples whose windows lie in what has been pushed, up to a multiple of np;
+ *   K2 / K2m     the watermark signal alone for the whole frames that became available but the last, which is the halo behind them (the
+ *                frame in front of them is the halo before): a frame's signal is complete once the next frame was transformed;
+ *   up (K10s)    per payload, the outputs whose windows lie in complete frames, up to a multiple of np, into one scratch buffer;
+ *   K11          scratch + input -> the mix slots of the tiles the run crosses, with the block maxima (in front of the stream the stretch
+ *                mix_first .. zero_frames - 1 of watermark alone, which only counts for the maxima);
+ *   K3           tile t - 2, once the limiter block behind its last sample is mixed.
+ * Every buffer is linear: it holds the samples base .. end - 1 of its stream, and after a push what the next push still reads is copied to
+ * the front of its twin (the input that the next windows and the next mix reach back to, two 44.1 kHz frames and the remainder, the
+ * watermark samples the next up window starts in).  awm_add_stream_rate_plan says how far the mix lags behind the input. ---- */
+struct AddStreamRate
+{
+  int       rate = 0;
+  awm_stream_rate_plan plan {};
+  const ResampleTable *down = nullptr, *up = nullptr;
+  uint64_t  Z = 0;                                // zero_frames: sample of the stream where the caller's first sample lies
+  uint64_t  mix_first = 0, frame_first = 0, slice_first = 0;          // awm_add_segment_plan's, which depend on Z alone
+  DevBuffer in[2];                                // the stream at the rate: in[in_cur] holds samples in_base .. in_end - 1, the caller writes behind them
+  int       in_cur = 0;
+  uint64_t  in_base = 0, in_end = 0;
+  size_t    in_cap = 0;                           // samples per channel each of them takes
+  DevBuffer x44[2];                               // the stream at 44.1 kHz: x44[x_cur] holds samples x_base .. d_done - 1
+  int       x_cur = 0;
+  uint64_t  x_base = 0, d_done = 0;
+  size_t    cap44 = 0;
+  std::vector<DevBuffer> wm44;                    // [2][P] the watermark at 44.1 kHz: wm44[w_cur * P + p] holds samples w_base .. w_end - 1
+  int       w_cur = 0;
+  uint64_t  w_base = 0, w_end = 0;                // w_end = k_done * 1024: the end of the complete frames
+  uint64_t  k_done = 0;                           // the next frame K2 produces
+  DevBuffer wm;                                   // the watermark at the rate for the outputs of one push (one payload after the other)
+  size_t    wm_cap = 0;
+  uint64_t  u_done = 0;                           // the next output to be mixed
+  long long limited = 0;                          // tiles handed out so far
+  DevBuffer limit_tab;
+  size_t    tab_entries = 0;
+};
+
+static void
+add_stream_rate_release (AddStreamRate *r)
+{
+  if (!r)
+    return;
+  for (int i = 0; i < 2; i++)
+    {
+      r->in[i].release();
+      r->x44[i].release();
+    }
+  for (DevBuffer& b : r->wm44)
+    b.release();
+  r->wm.release();
+  r->limit_tab.release();
+  delete r;
+}
+
+static float *
+add_stream_rate_input (awm_add_stream *s)
+{
+  AddStreamRate *r = s->rate;
+  return s->finished ? nullptr : r->in[r->in_cur].as<float>() + (r->in_end - r->in_base) * s->C;
+}
+
+// what the next push still reads of a linear buffer: samples new_base .. end - 1 to the front of its twin
+static int
+add_stream_rate_carry (hipStream_t st, const DevBuffer& from, DevBuffer& to, uint64_t base, uint64_t new_base, uint64_t end, int C)
+{
+  if (end > new_base)
+    AWM_HIP_CHECK (hipMemcpyAsync (to.ptr, from.as<float>() + (new_base - base) * C, (end - new_base) * C * sizeof (float),
+                                   hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+static int
+add_stream_create_rate (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int n_channels, int sample_rate,
+                        size_t tile_frames1024, size_t zero_frames, awm_add_stream **out, const char *who)
+{
+  awm_stream_rate_plan plan;
+  if (int rc = awm_add_stream_rate_plan (sample_rate, &plan))
+    return rc;
+  constexpr uint64_t LIMIT = uint64_t (1) << 40;
+  if (tile_frames1024 >= LIMIT / Params::frame_size || tile_frames1024 * Params::frame_size < plan.min_tile)
+    {
+      set_error (string_printf ("%s: a tile of %zu samples at %d Hz (min_tile, awm_add_stream_rate_plan: %llu samples; at most 2^40)", who,
+                                tile_frames1024 * Params::frame_size, sample_rate, (unsigned long long) plan.min_tile));
+      return AWM_ERR_ARG;
+    }
+  if (ctx->snr_on)
+    {
+      set_error (std::string (who) + ": not available at this sample rate while the SNR meter is armed (awm_ctx_snr_begin)");
+      return AWM_ERR_ARG;
+    }
+  awm_segment_plan sp;
+  if (int rc = awm_add_segment_plan (sample_rate, zero_frames, 1, &sp))          // (refuses zero_frames + 1 >= 2^40)
+    return rc;
+  auto s = std::make_unique<awm_add_stream>();
+  s->ctx = ctx;
+  s->C = n_channels;
+  s->P = n_payloads;
+  s->tile = tile_frames1024 * Params::frame_size;
+  s->limiter = !params().test_no_limiter;
+  s->first_block = size_t (sp.first_block);
+  s->table.resize (n_payloads);
+  s->mix.resize (3 * n_payloads);
+  AddStreamRate *r = s->rate = new AddStreamRate;
+  auto fail = [&] (int rc) { awm_add_stream_destroy (s.release()); return rc; };
+  const size_t table_bytes = 2 * mark_block_frame_count() * Params::n_bands;
+  for (size_t p = 0; p < n_payloads; p++)
+    {
+      FrameModTable *fm = ctx->get_frame_mod (capi_key (key), payload_hex[p]);
+      if (!fm)
+        return fail (AWM_ERR_ARG);
+      if (int rc = s->table[p].reserve (table_bytes)) return fail (rc);
+      if (hipMemcpyAsync (s->table[p].ptr, fm->dev.ptr, table_bytes, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess
+          || hipStreamSynchronize (ctx->stream) != hipSuccess)
+        return fail (AWM_ERR_HIP);
+    }
+  r->rate = sample_rate;
+  r->plan = plan;
+  r->down = ctx->get_resample_table (sample_rate, Params::mark_sample_rate);
+  r->up = ctx->get_resample_table (Params::mark_sample_rate, sample_rate);
+  if (!r->down || !r->up)
+    return fail (AWM_ERR_HIP);
+  r->Z = zero_frames;
+  r->mix_first = sp.mix_first;
+  r->frame_first = sp.frame_first;
+  r->slice_first = sp.slice_first;
+  r->in_base = r->in_end = zero_frames;
+  r->x_base = r->d_done = sp.down_first;
+  r->k_done = sp.slice_first;
+  r->w_base = r->w_end = sp.slice_first * Params::frame_size;
+  r->u_done = sp.mix_first;
+  // room: a tile and what is carried.  The mix lags at most mix_ahead + down_step + up_np + 1 behind the input (the launches end on
+  // multiples of np), the watermark in front of the stream is shorter than mix_ahead, the flush adds two frames and the windows
+  const size_t slack = size_t (plan.mix_ahead) + 2 * size_t (plan.down_hl) + 4 * size_t (plan.down_step) + 2 * size_t (plan.up_np) + Params::frame_size;
+  r->in_cap = s->tile + slack;
+  r->cap44 = size_t (s->tile * uint64_t (plan.down_np) / uint64_t (plan.down_step)) + 8 * Params::frame_size + 2 * size_t (plan.down_np) + 64;
+  r->wm_cap = s->tile + size_t (plan.mix_ahead) + slack;
+  r->tab_entries = s->tile / size_t (plan.limiter_block) + 3;
+  const size_t C = size_t (n_channels);
+  r->wm44.resize (2 * n_payloads);
+  for (int i = 0; i < 2; i++)
+    {
+      if (int rc = r->in[i].reserve (r->in_cap * C * sizeof (float))) return fail (rc);
+      if (int rc = r->x44[i].reserve (r->cap44 * C * sizeof (float))) return fail (rc);
+      for (size_t p = 0; p < n_payloads; p++)
+        if (int rc = r->wm44[i * n_payloads + p].reserve (r->cap44 * C * sizeof (float))) return fail (rc);
+    }
+  if (int rc = r->wm.reserve (r->wm_cap * C * sizeof (float))) return fail (rc);
+  if (int rc = r->limit_tab.reserve ((r->tab_entries + 1) * sizeof (float2))) return fail (rc);
+  for (size_t i = 0; i < 3 * n_payloads; i++)
+    if (int rc = s->mix[i].reserve (s->tile * C * sizeof (float))) return fail (rc);
+  if (s->limiter)                                            // the first 4096 block maxima (68 minutes) now: a push allocates only beyond them
+    if (int rc = add_stream_grow_blocks (s.get(), 1)) return fail (rc);
+  *out = s.release();
+  return 0;
+}
+
+static int
+add_stream_rate_push (awm_add_stream *s, size_t n_frames, int last, const float **out_d, size_t out_frames[3], const char *who)
+{
+  awm_ctx *ctx = s->ctx;
+  AddStreamRate *r = s->rate;
+  hipStream_t st = ctx->stream;
+  const size_t C = size_t (s->C), P = s->P, FRAME = Params::frame_size;
+  const awm_stream_rate_plan& pl = r->plan;
+  const uint64_t Z = r->Z, tile = s->tile, B = pl.limiter_block;
+  const uint64_t hd = uint64_t (pl.down_hl), nd = uint64_t (pl.down_np), sd = uint64_t (pl.down_step);
+  const uint64_t hu = uint64_t (pl.up_hl), nu = uint64_t (pl.up_np), su = uint64_t (pl.up_step);
+  for (size_t i = 0; i < 3; i++)
+    {
+      for (size_t p = 0; p < P; p++)
+        out_d[i * P + p] = nullptr;
+      out_frames[i] = 0;
+    }
+  if (ctx->snr_on)
+    {
+      set_error (std::string (who) + ": not available at this sample rate while the SNR meter is armed (awm_ctx_snr_begin)");
+      return AWM_ERR_ARG;
+    }
+  if (r->in_end + n_frames >= (uint64_t (1) << 40))
+    {
+      set_error (std::string (who) + ": zero_frames + the samples pushed must stay below 2^40");
+      return AWM_ERR_ARG;
+    }
+  auto internal = [&] (const char *what) {
+    set_error (std::string (who) + ": " + what + " (the tile is too short for this sample rate: awm_add_stream_rate_plan)");
+    return AWM_ERR_GENERIC;
+  };
+  // the windows: output m of a resampler reads inputs floor (m step / np) - hl + 1 ... floor (m step / np) + hl
+  auto window_first = [] (uint64_t m, uint64_t hl, uint64_t step, uint64_t np) { const uint64_t b = m * step / np; return b + 1 > hl ? b + 1 - hl : 0; };
+  auto outputs_within = [] (uint64_t end, uint64_t hl, uint64_t step, uint64_t np) {        // how many outputs read nothing from `end` on
+    return end > hl ? ((end - hl) * np + step - 1) / step : uint64_t (0);
+  };
+  r->in_end += n_frames;
+  const uint64_t in_end = r->in_end;
+  if (last && in_end == Z)                                   // nothing was ever pushed
+    {
+      s->finished = true;
+      s->t++;
+      return 0;
+    }
+  if (s->limiter)
+    if (int rc = add_stream_grow_blocks (s, size_t (in_end / B + 2 - s->first_block))) return rc;
+  const float *in = r->in[r->in_cur].as<float>();
+  float *x44 = r->x44[r->x_cur].as<float>();
+
+  // 1. down.  At the end of the stream: the frames the last output's window reaches, and the frame behind them
+  uint64_t d_new;
+  if (last)
+    d_new = ((((in_end - 1) * su / nu + hu) / FRAME) + 2) * FRAME;
+  else
+    d_new = outputs_within (in_end, hd, sd, nd) / nd * nd;
+  d_new = std::max (d_new, r->d_done);
+  if (d_new > r->d_done)
+    {
+      if (d_new - r->x_base > r->cap44)
+        return internal ("the 44.1 kHz slot is full");
+      const awmk::ResampleSlice sl { in, (long long) (in_end - r->in_base), (long long) r->in_base, (long long) r->d_done,
+                                     (long long) (d_new - r->d_done), x44 + (r->d_done - r->x_base) * C };
+      ProfScope ps (ctx, PROF_RESAMPLE, double (sl.n_in + sl.n_out) * C * 4.0);
+      AWM_HIP_CHECK (awmk::launch_resample_span (st, resample_table_args (*r->down, int (C)), sl));
+    }
+  r->d_done = d_new;
+
+  // 2. the watermark signal of the frames k_done .. fb - 2; frame fb - 1 is the halo behind them
+  const uint64_t fb = d_new / FRAME;
+  if (fb > r->k_done + 1)
+    {
+      const uint64_t k0 = r->k_done, k1 = fb - 1;
+      if (k1 * FRAME - r->w_base > r->cap44)
+        return internal ("the watermark slot is full");
+      const float *before = k0 > r->slice_first ? x44 + ((k0 - 1) * FRAME - r->x_base) * C : nullptr;
+      const float *after = x44 + (k1 * FRAME - r->x_base) * C;
+      const float *src = x44 + (k0 * FRAME - r->x_base) * C;
+      std::vector<float *> outs (P);
+      std::vector<const int8_t *> tables (P);
+      for (size_t p = 0; p < P; p++)
+        {
+          outs[p] = r->wm44[r->w_cur * P + p].as<float>() + (k0 * FRAME - r->w_base) * C;
+          tables[p] = s->table[p].as<int8_t>();
+        }
+      if (P == 1)
+        {
+          if (int rc = add_mix_impl (ctx, src, outs[0], size_t ((k1 - k0) * FRAME), int (C), tables[0], params().water_delta, size_t (k0), before,
+                                     after, nullptr, 0, 0, nullptr, 1))
+            return rc;
+        }
+      else if (int rc = add_mix_payloads_impl (ctx, src, outs.data(), P, size_t ((k1 - k0) * FRAME), int (C), tables.data(), params().water_delta,
+                                               size_t (k0), before, after, nullptr, 0, 0, 1))
+        return rc;
+      r->k_done = k1;
+      r->w_end = k1 * FRAME;
+    }
+
+  // 3. up and mix, per payload: the outputs whose windows lie in complete frames
+  uint64_t u_new;
+  if (last)
+    {
+      u_new = in_end;
+      if (outputs_within (r->w_end, hu, su, nu) < u_new)
+        return internal ("the last frames are missing");
+    }
+  else
+    u_new = std::min (outputs_within (r->w_end, hu, su, nu), in_end) / nu * nu;
+  u_new = std::max (u_new, r->u_done);
+  if (u_new > r->u_done)
+    {
+      const uint64_t u0 = r->u_done;
+      if (u_new - u0 > r->wm_cap)
+        return internal ("the watermark signal's slot is full");
+      if (std::max (u0, Z) < r->in_base)
+        return internal ("the input of the mix is gone");
+      const uint64_t res0 = std::max (r->w_base, r->frame_first * FRAME);        // only complete frames are handed over
+      if (r->w_end < res0)
+        return internal ("no complete frame");
+      float *wm = r->wm.as<float>();
+      for (size_t p = 0; p < P; p++)
+        {
+          {
+            const awmk::ResampleSlice sl { r->wm44[r->w_cur * P + p].as<float>() + (res0 - r->w_base) * C, (long long) (r->w_end - res0), (long long) res0,
+                                           (long long) u0, (long long) (u_new - u0), wm };
+            ProfScope ps (ctx, PROF_RESAMPLE, double (sl.n_in + sl.n_out) * C * 4.0);
+            AWM_HIP_CHECK (awmk::launch_resample_span (st, resample_table_args (*r->up, int (C)), sl));
+          }
+          unsigned int *block_max = s->limiter ? s->block_max.as<unsigned int>() + p * s->n_blocks : nullptr;
+          for (uint64_t a = u0; a < u_new; )                 // one piece per tile the run crosses
+            {
+              const uint64_t lo = std::max (a, Z), k = (lo - Z) / tile;
+              const uint64_t b = std::min (u_new, Z + (k + 1) * tile);
+              const uint64_t n = b > lo ? b - lo : 0, pre = a < Z ? std::min (b, Z) - a : 0;
+              if (n && (long long) k >= r->limited + 3)
+                return internal ("a mix slot is still in use");
+              const awmk::MixSegment ms { in + (lo - r->in_base) * C, wm + (a - u0) * C, s->mix[(k % 3) * P + p].as<float>() + (lo - (Z + k * tile)) * C,
+                                          (long long) n, (long long) pre, (long long) (a + pre), block_max, (long long) s->first_block,
+                                          (long long) s->n_blocks };
+              AWM_HIP_CHECK (awmk::launch_mix_max_segment (st, ms, int (C), int (B)));
+              a = b;
+            }
+        }
+    }
+  r->u_done = u_new;
+
+  // 4. the limiter: a tile's last sample needs the maximum of the limiter block behind its own
+  int n_out = 0;
+  const long long t = s->t;
+  while (r->limited <= t)
+    {
+      const uint64_t k = uint64_t (r->limited), t0 = Z + k * tile, t1 = std::min (t0 + tile, in_end);
+      const uint64_t n = t1 > t0 ? t1 - t0 : 0;
+      if (!last && (n < tile || u_new < ((t1 - 1) / B + 2) * B))
+        break;
+      if (n)
+        {
+          if (n_out == 3)
+            return internal ("more than three tiles became final");
+          for (size_t p = 0; p < P; p++)
+            {
+              float *data = s->mix[(k % 3) * P + p].as<float>();
+              if (s->limiter)
+                {
+                  ProfScope ps (ctx, PROF_LIMITER, double (n) * C * 8.0);
+                  AWM_HIP_CHECK (awmk::launch_limiter (st, data, (long long) n, int (C), (long long) t0, s->block_max.as<float>() + p * s->n_blocks,
+                                                       (long long) s->first_block, (long long) s->n_blocks, int (B), LIMITER_CEILING,
+                                                       r->limit_tab.as<float2>(), r->tab_entries));
+                }
+              out_d[n_out * P + p] = data;
+            }
+          out_frames[n_out++] = size_t (n);
+        }
+      r->limited++;
+    }
+  if (!last && t >= 2 && r->limited < t - 1)
+    return internal ("a tile is not final two pushes after its own");
+
+  // 5. what the next push reads, to the front of the twins
+  if (last)
+    s->finished = true;
+  else
+    {
+      {
+        const uint64_t from = std::max (std::min (window_first (d_new, hd, sd, nd), u_new), r->in_base);      // the next windows, the next mix
+        const uint64_t keep = from < in_end ? (in_end - from + 3) / 4 * 4 : 0;        // the caller's pointer stays 16-byte aligned
+        if (keep > in_end - r->in_base || keep + tile > r->in_cap)
+          return internal ("the input slot is full");
+        if (int rc = add_stream_rate_carry (st, r->in[r->in_cur], r->in[r->in_cur ^ 1], r->in_base, in_end - keep, in_end, int (C))) return rc;
+        r->in_base = in_end - keep;
+        r->in_cur ^= 1;
+      }
+      {
+        const uint64_t from = r->k_done > r->slice_first ? (r->k_done - 1) * FRAME : r->x_base;
+        if (int rc = add_stream_rate_carry (st, r->x44[r->x_cur], r->x44[r->x_cur ^ 1], r->x_base, from, d_new, int (C))) return rc;
+        r->x_base = from;
+        r->x_cur ^= 1;
+      }
+      {
+        const uint64_t from = std::min (std::max (window_first (u_new, hu, su, nu), r->w_base), r->w_end);
+        for (size_t p = 0; p < P; p++)
+          if (int rc = add_stream_rate_carry (st, r->wm44[r->w_cur * P + p], r->wm44[(r->w_cur ^ 1) * P + p], r->w_base, from, r->w_end, int (C)))
+            return rc;
+        r->w_base = from;
+        r->w_cur ^= 1;
+      }
+    }
+  s->t++;
+  return n_out;
+}
+
+static int
+add_stream_rate_args_ok (const char *who, const void *out, int n_channels, int sample_rate, size_t tile_frames1024)
+{
+  if (!out || n_channels < 1 || tile_frames1024 < 128)
+    {
+      set_error (std::string (who) + ": bad argument (a tile is at least 128 frames: the limiter looks one second ahead)");
+      return AWM_ERR_ARG;
+    }
+  if (sample_rate <= 0)
+    {
+      set_error (string_printf ("%s: sample_rate %d", who, sample_rate));
+      return AWM_ERR_ARG;
+    }
+  return 0;
+}
+
+int
+awm_add_stream_create_rate_at (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, int n_channels, int sample_rate,
+                               size_t tile_frames1024, size_t zero_frames, awm_add_stream **out)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_add_stream_create_at (ctx, key, payload_hex, n_channels, tile_frames1024, zero_frames, out);
+  AWM_ENTER (ctx);
+  if (int rc = add_stream_rate_args_ok ("awm_add_stream_create_rate_at", out, n_channels, sample_rate, tile_frames1024))
+    return rc;
+  if (!payload_hex)
+    payload_hex = "";
+  return add_stream_create_rate (ctx, key, &payload_hex, 1, n_channels, sample_rate, tile_frames1024, zero_frames, out, "awm_add_stream_create_rate_at");
+}
+
+int
+awm_add_stream_create_payloads_rate_at (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int n_channels,
+                                        int sample_rate, size_t tile_frames1024, size_t zero_frames, awm_add_stream **out)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_add_stream_create_payloads_at (ctx, key, payload_hex, n_payloads, n_channels, tile_frames1024, zero_frames, out);
+  AWM_ENTER (ctx);
+  const char *who = "awm_add_stream_create_payloads_rate_at";
+  if (int rc = add_stream_rate_args_ok (who, payload_hex ? (const void *) out : nullptr, n_channels, sample_rate, tile_frames1024))
+    return rc;
+  if (n_payloads < 1 || n_payloads > AWM_ADD_STREAM_MAX_PAYLOADS)
+    {
+      set_error (string_printf ("%s: %zu payloads (1 .. %d are possible)", who, n_payloads, AWM_ADD_STREAM_MAX_PAYLOADS));
+      return AWM_ERR_ARG;
+    }
+  for (size_t p = 0; p < n_payloads; p++)
+    if (!payload_hex[p] || parse_payload (payload_hex[p]).empty())
+      {
+        set_error (string_printf ("%s: cannot parse payload '%s' at index %zu", who, payload_hex[p] ? payload_hex[p] : "(null)", p));
+        return AWM_ERR_ARG;
+      }
+  return add_stream_create_rate (ctx, key, payload_hex, n_payloads, n_channels, sample_rate, tile_frames1024, zero_frames, out, who);
+}
+
+int
+awm_add_stream_sample_rate (const awm_add_stream *s)
+{
+  return !s ? 0 : s->rate ? s->rate->rate : Params::mark_sample_rate;
+}
+
+int
+awm_debug_resample_span_d (awm_ctx *ctx, const float *in_d, size_t n_in, uint64_t in0, uint64_t out0, size_t n_out, int n_channels,
+                           int rate_in, int rate_out, float *out_d, int *phase_form_used)
+{
+  AWM_ENTER (ctx);
+  constexpr uint64_t LIMIT = uint64_t (1) << 41;             // K10w: m step in 64 bits
+  if ((n_in && !in_d) || (n_out && !out_d) || n_channels < 1 || in0 >= LIMIT || n_in >= LIMIT || out0 >= LIMIT || n_out >= LIMIT)
+    {
+      set_error ("awm_debug_resample_span_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  const ResampleTable *t = rate_in > 0 && rate_out > 0 ? ctx->get_resample_table (rate_in, rate_out) : nullptr;
+  if (!t)
+    {
+      set_error (string_printf ("awm_debug_resample_span_d: no fixed-ratio resampler from %d Hz to %d Hz", rate_in, rate_out));
+      return AWM_ERR_ARG;
+    }
+  const awmk::ResampleArgs ra = resample_table_args (*t, n_channels);
+  const awmk::ResampleSlice sl { in_d, (long long) n_in, (long long) in0, (long long) out0, (long long) n_out, out_d };
+  if (phase_form_used)
+    *phase_form_used = n_out && awmk::resample_span_takes_phase (ra, sl) ? 1 : 0;
+  ProfScope ps (ctx, PROF_RESAMPLE, double (n_in + n_out) * n_channels * 4.0);
+  AWM_HIP_CHECK (awmk::launch_resample_span (ctx->stream, ra, sl));
+  return 0;
 }
 
 int
@@ -1556,14 +2022,14 @@ awm_add_watermark_payloads_d (awm_ctx *ctx, const uint8_t key[16], const char *c
 static int
 add_mix_payloads_impl (awm_ctx *ctx, const float *pcm_in_d, float *const *out_d, size_t n_payloads, size_t n_frames, int n_channels,
                        const int8_t *const *frame_mod_dev, double water_delta, size_t first_frame, const float *halo_before_d,
-                       const float *halo_after_d, float *const *block_max_d, size_t first_block, size_t n_blocks)
+                       const float *halo_after_d, float *const *block_max_d, size_t first_block, size_t n_blocks, int delta_only)
 {
   g_add_payloads_fused_in_use = 0;
   if (n_payloads == 1 || !g_add_payloads_fused)
     {
       for (size_t p = 0; p < n_payloads; p++)
         if (int rc = add_mix_impl (ctx, pcm_in_d, out_d[p], n_frames, n_channels, frame_mod_dev[p], water_delta, first_frame, halo_before_d,
-                                   halo_after_d, block_max_d ? block_max_d[p] : nullptr, first_block, n_blocks))
+                                   halo_after_d, block_max_d ? block_max_d[p] : nullptr, first_block, n_blocks, nullptr, delta_only))
           return rc;
       return 0;
     }
@@ -1575,6 +2041,7 @@ add_mix_payloads_impl (awm_ctx *ctx, const float *pcm_in_d, float *const *out_d,
   fill_add_mix_common (a, water_delta);
   a.n_blocks = (long long) n_blocks;
   a.frames_per_span = frames_per_span (ctx, (long long) (n_frames + 1023) / 1024, awmk::add_mix_multi_span_waves_per_simd());
+  a.delta_only = delta_only;
   awmk::AddMixSpan sp {};
   sp.first_frame = (long long) first_frame;
   sp.halo_before = halo_before_d;

@@ -198,6 +198,58 @@ awm_add_segment_plan (int sample_rate, size_t zero_frames, size_t n_frames, awm_
   return 0;
 }
 
+/* The look-ahead of the tile stream at another sample rate (include/awm_hip.h), with awm_add_segment_plan's window
+ * rule.  The mix of output m reads watermark samples up to wl = b_up (m) + hl_up, which lie in frame f = wl / 1024; that frame is complete
+ * once frame f + 1 was transformed, whose last sample q = (f + 2) 1024 - 1 reads the stream up to b_down (q) + hl_down.  For one f the
+ * distance to m is largest at the first m that reaches the frame, and the whole chain repeats after lcm (1024, np_down) samples at 44.1 kHz
+ * (np_down / gcd (np_down, 1024) <= 1000 frames): one loop over those frames finds the maximum. */
+int
+awm_add_stream_rate_plan (int sample_rate, awm_stream_rate_plan *plan)
+{
+  if (!plan)
+    {
+      set_error ("awm_add_stream_rate_plan: bad argument");
+      return AWM_ERR_ARG;
+    }
+  *plan = awm_stream_rate_plan {};
+  awm_segment_plan tables;
+  if (awm_add_segment_plan (sample_rate, 0, 0, &tables) || !tables.limiter_block)
+    {
+      set_error (string_printf ("awm_add_stream_rate_plan: no fixed-ratio resampler between %d Hz and %d Hz", sample_rate,
+                                Params::mark_sample_rate));
+      return AWM_ERR_ARG;
+    }
+  const int hd = tables.down_hl, nd = tables.down_np, sd = tables.down_step, hu = tables.up_hl, nu = tables.up_np, su = tables.up_step;
+  plan->down_hl = hd; plan->down_np = nd; plan->down_step = sd;
+  plan->up_hl = hu; plan->up_np = nu; plan->up_step = su;
+  plan->limiter_block = tables.limiter_block;
+  plan->down_ahead = uint64_t (hd);                // 44.1 kHz sample q reads b_down (q) - hl + 1 ... b_down (q) + hl
+  const uint64_t FRAME = Params::frame_size;
+  uint64_t period = uint64_t (nd), two = FRAME;    // frames after which the chain repeats: np_down / gcd (np_down, 1024)
+  while (two > 1 && period % 2 == 0)
+    {
+      period /= 2;
+      two /= 2;
+    }
+  uint64_t ahead = 0;
+  for (uint64_t f = 0; f <= period + 1; f++)
+    {
+      const uint64_t j = f * FRAME;                // the first m with b_up (m) + hl_up >= j
+      const uint64_t m = j <= uint64_t (hu) ? 0 : ((j - uint64_t (hu)) * uint64_t (nu) + uint64_t (su) - 1) / uint64_t (su);
+      const uint64_t q = (f + 2) * FRAME - 1;
+      const uint64_t last_in = q * uint64_t (sd) / uint64_t (nd) + uint64_t (hd);
+      if (last_in > m)
+        ahead = std::max (ahead, last_in - m);
+    }
+  plan->mix_ahead = ahead;
+  /* Tile t is limited once the block behind its last sample is mixed: up to 2 limiter blocks - 1 behind its end.  After the push of tile
+   * t + 2 the mix has reached 2 tiles - mix_ahead - (what the launches that end on multiples of np hold back: less than down_step + up_np + 1
+   * <= mix_ahead) behind that end, so one limiter block + mix_ahead per tile is enough; and never less than the 44.1 kHz object's 128 frames. */
+  const uint64_t need = plan->limiter_block + plan->mix_ahead;
+  plan->min_tile = std::max<uint64_t> (128 * FRAME, (need + FRAME - 1) / FRAME * FRAME);
+  return 0;
+}
+
 int
 awm_conv_encode (int block_type, const int *bits, size_t n, int *out)
 {

@@ -1016,21 +1016,28 @@ struct SnrMeter
  * staging chunks of input and three of output on the host, three input and three mix tiles in HBM, whatever the length of
  * the stream (also for pipes of unknown length).  Per tile: file read -> H2D (copy stream) -> sample decode -> fused STFT /
  * band edit / inverse / overlap-add / mix of the PREVIOUS tile -> limiter + sample encode of the tile before that -> D2H
- * (copy stream) -> file write (writer thread); the stages of neighbouring tiles overlap. */
+ * (copy stream) -> file write (writer thread); the stages of neighbouring tiles overlap.
+ * At another sample rate that the object takes (awm_add_stream_create_rate_at) the loop is the same; the object
+ * then resamples inside and holds (3 + 3) tiles at the rate and (2 + 2) at 44.1 kHz. */
 int
 add_tiles (awm_ctx *ctx, const Key& key, AudioInputStream *in_stream, AudioOutputStream *out_stream, const std::string& payload_hex,
            size_t zero_frames, size_t& n_frames)
 {
-  constexpr size_t TILE_FRAMES1024 = 4096;                 // 95 s of audio, 32 MiB of float32 stereo
-  const size_t tile = TILE_FRAMES1024 * Params::frame_size;
-  const int C = in_stream->n_channels();
+  size_t tile_frames1024 = 4096;                           // 95 s of audio, 32 MiB of float32 stereo
+  const int C = in_stream->n_channels(), rate = in_stream->sample_rate();
+  // another sample rate (the caller has checked that the object takes it): the same loop, the tile counted at that rate and raised to the
+  // object's minimum where a second of look-ahead is longer than 4096 frames
+  awm_stream_rate_plan rate_plan;
+  if (rate != Params::mark_sample_rate && awm_add_stream_rate_plan (rate, &rate_plan) == 0)
+    tile_frames1024 = std::max (tile_frames1024, size_t (rate_plan.min_tile + Params::frame_size - 1) / Params::frame_size);
+  const size_t tile = tile_frames1024 * Params::frame_size;
   n_frames = 0;
   for (double& v : tl_file_ms)
     v = 0;
   Lap lap;
   struct TeardownLap { Lap& l; ~TeardownLap() { l.to (6); } };
   awm_add_stream *add = nullptr;
-  if (awm_add_stream_create_at (ctx, key.aes_key(), payload_hex.c_str(), C, TILE_FRAMES1024, zero_frames, &add))
+  if (awm_add_stream_create_rate_at (ctx, key.aes_key(), payload_hex.c_str(), C, rate, tile_frames1024, zero_frames, &add))
     {
       error ("audiowmark: GPU watermarking failed: %s\n", awm_last_error());
       return fail (AWM_ERR_HIP);
@@ -1446,7 +1453,12 @@ add_stream_watermark (awm_ctx *ctx, const Key& key, AudioInputStream *in_stream,
 
   const int C = in_stream->n_channels();
   size_t n_frames = 0;
-  int rc = in_stream->sample_rate() == Params::mark_sample_rate
+  // the tile loop: at the watermark rate, and at every rate the tile stream takes (fixed-ratio tables in both directions) unless the SNR
+  // meter is on -- by --snr or armed by the caller --, whose powers are defined over the whole stream; everything else stays whole in HBM
+  awm_stream_rate_plan rate_plan;
+  const bool tiles = in_stream->sample_rate() == Params::mark_sample_rate
+                  || (!params().snr && !ctx->snr_on && awm_add_stream_rate_plan (in_stream->sample_rate(), &rate_plan) == 0);
+  int rc = tiles
          ? add_tiles (ctx, key, in_stream, out_stream, bit_vec_to_str (bitvec), zero_frames, n_frames)
          : add_whole (ctx, key, in_stream, out_stream, bit_vec_to_str (bitvec), zero_frames, n_frames);
   if (rc)

@@ -188,6 +188,43 @@ size_t awm_add_stream_payloads (const awm_add_stream *s);        /* 0 for NULL *
 int    awm_add_stream_push_payloads (awm_add_stream *s, size_t n_frames, int last,
                                      const float **out_d /* [3][n_payloads] */, size_t out_frames[3]);
 
+/* The tile loop at ANY sample rate that zita's fixed-ratio Resampler takes in both directions (what awm_add_watermark_segments_rate_d takes;
+ * DESIGN.md section 9.5): the same object, the same input / push / push_payloads / payloads / destroy calls and the same contract -- every
+ * tile but the last full, last = 1 ends the stream, a push only enqueues on the context's stream (no host synchronise but for the growth of
+ * the block maxima), 0 .. 3 finished tiles per push in stream order, tile t final no later than the push of tile t + 2, pointers valid
+ * until the next push.  A tile is tile_frames1024 * 1024 samples per channel AT sample_rate, and output tiles have exactly the lengths of
+ * the input tiles: every stage works at global sample and frame indices, so zero_frames needs no zeros inside the object.
+ * With x = the concatenated input, output p is bit for bit what awm_add_watermark_d (ctx, key, payload_hex[p], x, ..., sample_rate) writes
+ * for zero_frames == 0 and what awm_add_watermark_segments_rate_d writes for the single segment (zero_frames, x) otherwise; the end of the
+ * stream need not be known, both see zeros behind it.  sample_rate == 44100 forwards to awm_add_stream_create_at /
+ * awm_add_stream_create_payloads_at.
+ * Per push: resample what arrived down to 44.1 kHz as far as the windows are filled (K10s: launches end on multiples of np, the rest is
+ * carried), K2 / K2m for the watermark signal alone over the whole frames that became available (the last one is the halo), per payload
+ * resample the complete frames up, mix + block maxima (in front of the stream the stretch of watermark alone that only counts for the
+ * maxima), then the limiter for tile t - 2.  The number of launches of a push does not depend on the tiles before it.
+ * HBM, reserved at creation (T = a tile, T44 = T * 44100 / sample_rate, both plus a few thousand samples of carry): 2 T input + 2 T44 at
+ * 44.1 kHz + 2 n_payloads T44 watermark frames + 1 T watermark signal + 3 n_payloads T mix slots: (3 + 3 n_payloads) T + (2 + 2 n_payloads) T44;
+ * (the context's allocator rounds every buffer up, by half at most); the block maxima (4 bytes per second and payload: the first 4096 with
+ * the object) grow as before.
+ * AWM_ERR_ARG, nothing allocated or enqueued: what the 44.1 kHz constructors refuse, sample_rate <= 0, a rate without a fixed-ratio table
+ * in either direction (e.g. 44101), a tile below awm_add_stream_rate_plan's min_tile, creation or a push while the SNR meter is armed (the
+ * powers of the resampled add are defined over the whole stream), a push that takes zero_frames + the samples pushed to 2^40 or beyond. */
+int    awm_add_stream_create_rate_at (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, int n_channels, int sample_rate,
+                                      size_t tile_frames1024, size_t zero_frames, awm_add_stream **out);
+int    awm_add_stream_create_payloads_rate_at (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads,
+                                               int n_channels, int sample_rate, size_t tile_frames1024, size_t zero_frames,
+                                               awm_add_stream **out);
+int    awm_add_stream_sample_rate (const awm_add_stream *s);      /* 44100 for the objects of the constructors above, 0 for NULL */
+/* The look-ahead of that object (pure host arithmetic, no context, no device; the object calls it).  With b_X (m) = floor (m step_X / np_X):
+ *   down_ahead: 44.1 kHz sample q reads the stream up to b_down (q) + down_ahead;
+ *   mix_ahead:  the smallest L such that the mix of output sample m, for every m, depends on no input sample beyond m + L (up window ->
+ *               frame of the last watermark sample read -> the frame after it -> its last 44.1 kHz sample -> that sample's down window);
+ *   min_tile:   the smallest tile in samples for which tile t is final after the push of tile t + 2: one limiter block + mix_ahead,
+ *               rounded up to 1024, and at least 128 * 1024.
+ * 0, or AWM_ERR_ARG for a rate the object refuses. */
+typedef struct { uint64_t limiter_block, down_ahead, mix_ahead, min_tile; int down_hl, down_np, down_step, up_hl, up_np, up_step; } awm_stream_rate_plan;
+int    awm_add_stream_rate_plan (int sample_rate, awm_stream_rate_plan *plan);
+
 /* I/O staging: RawConverter::from_raw / to_raw (rawconverter.cc:155-286) on the device, so that files cross PCIe in
  * their own sample format.  bit_depth 8/16/24/32 (integer) or 32/64 (float); encoding 0 signed, 1 unsigned, 2 float.
  * direct16 != 0 selects the reference's native little-endian signed-16 rule (truncate at 16 bit, what its stdout / raw
@@ -267,8 +304,7 @@ int awm_add_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], const char *
  * the limiter work there, one scatter launch brings the results home without the r samples (a batch stages at most 1 GiB per direction,
  * more is split); segments with r = 0 are read from and written to the caller's buffers directly.  Everything else (other channel
  * counts, a misaligned pointer, a single segment, awm_debug_set_add_batched (0)) goes segment by segment through the tile stream, with
- * the same results.  Not offered in this form: the command line, a tile-stream object at other rates, the awm_multi_* / sharded forms,
- * a key per segment. */
+ * the same results.  Not offered in this form: the command line, the awm_multi_* / sharded forms, a key per segment. */
 int awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
                                   const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
                                   int n_channels);
@@ -291,7 +327,7 @@ int awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_
  * Everything else (other channel counts, a misaligned pointer, a single segment, awm_debug_set_add_batched (0), a call with a segment
  * whose window alone exceeds such a workspace: about 50 minutes of stereo) runs the same stages segment by segment with the same window
  * arguments and the same results; awm_debug_add_segments_fused_in_use () tells which path ran.
- * Not offered in this form: the command line, a tile-stream object at other rates, the awm_multi_* / sharded forms, a key per segment. */
+ * Not offered in this form: the command line, the awm_multi_* / sharded forms, a key per segment. */
 int awm_add_watermark_segments_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
                                        const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
                                        int n_channels, int sample_rate);
@@ -634,6 +670,12 @@ int  awm_debug_scan_generic_launches (void);   /* K5w: how often launch_sync_sca
 void awm_debug_set_chunk_stagger (int mode); /* get: phase offset between the chunk lanes -- 0 all chunks start together | 1 chunk i + 1 behind chunk i's
                                              * dB kernel | 2 behind its scan | -1 (default) 1 for streams of up to `lanes` chunks, 2 for longer ones */
 void awm_debug_set_resample_phase (int on);  /* K10: 1 (default) the phase-per-thread kernel for stereo 48 <-> 44.1 kHz | 0 the generic kernel (outputs identical) */
+/* K10s alone: outputs out0 .. out0 + n_out - 1 of the fixed-ratio resampler rate_in -> rate_out to out_d[0 ..], from the frames in0 .. in0 +
+ * n_in - 1 of the stream at in_d (everything else reads as zero): the same values awm_resample_d writes for those outputs of the whole
+ * stream.  *phase_form_used: 1 if the phase-per-thread kernel ran (stereo 48 <-> 44.1 kHz, 8-byte aligned pointers, out0 a multiple of np,
+ * the switch above on), 0 for K10w. */
+int  awm_debug_resample_span_d (awm_ctx *ctx, const float *in_d, size_t n_in, uint64_t in0, uint64_t out0, size_t n_out, int n_channels,
+                                int rate_in, int rate_out, float *out_d, int *phase_form_used);
 void awm_debug_set_get_overlap (int on);    /* file level get: 1 (default) the chunks start while the rest of the stream is still crossing PCIe (a loader thread, a mark per
                                              * tile; streams of announced length at 44.1 kHz with two chunks or more) | 0 the whole stream first (rounds 1 - 5) */
 void awm_debug_set_speed_compare_wide (int on); /* K14: 1 all relative speeds of a centre (<= 12) in one thread / 0 (default) groups of six: measured slower, see hip/speed.hip */
