@@ -135,6 +135,8 @@ lib.awm_debug_add_payloads_tile.restype = C.c_int
 lib.awm_add_watermark_batch_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
 lib.awm_add_watermark_segments_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int]
 lib.awm_add_watermark_segments_rate_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
+lib.awm_add_watermark_segments_keys_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int]
+lib.awm_add_watermark_segments_keys_rate_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
 
 
 class SegmentPlan(C.Structure):
@@ -164,6 +166,8 @@ lib.awm_debug_add_segments_fused_in_use.restype = C.c_int
 lib.awm_debug_alloc_bytes.argtypes = []
 lib.awm_debug_alloc_bytes.restype = C.c_ulonglong
 lib.awm_debug_payload_tables_d.argtypes = [_vp, _vp, _vp, C.c_size_t, _vp]
+lib.awm_debug_key_templates_d.argtypes = [_vp, _vp, C.c_size_t, _vp]
+lib.awm_debug_key_payload_tables_d.argtypes = [_vp, _vp, _vp, C.c_size_t, _vp]
 lib.awm_get_watermark_batch_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
 lib.awm_add_watermark_batch_keys_d.argtypes = [_vp, _vp, C.c_char_p, C.c_size_t, _vp, _vp, _vp, C.c_int]
 lib.awm_get_watermark_batch_keys_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
@@ -727,6 +731,58 @@ class Context:
             return outs
         _check(lib.awm_add_watermark_segments_d(self._h, key_bytes(key), n, hexes, zf, src, dst, frames, ch), "awm_add_watermark_segments_d")
         return outs
+
+    def add_watermark_segments_keys(self, keys, payloads, segments, zero_frames, outs=None, sample_rate=44100):
+        """awm_add_watermark_segments_keys_d / _rate_d: add_watermark_segments with a key per segment (None, test_key(n) or 16 bytes each);
+        outs[i] == add_watermark_segments(keys[i], [payloads[i]], [segments[i]], [zero_frames[i]], sample_rate=sample_rate)[0] bit for bit."""
+        import torch
+        keys, payloads, segments, zero_frames = list(keys), list(payloads), list(segments), list(zero_frames)
+        if not (len(keys) == len(payloads) == len(segments) == len(zero_frames)):
+            raise ValueError("add_watermark_segments_keys: keys, payloads, segments and zero_frames must have one length")
+        if not segments:
+            return []
+        shapes = [_pcm_shape(s) for s in segments]
+        ch = shapes[0][1]
+        if any(s[1] != ch for s in shapes):
+            raise ValueError("add_watermark_segments_keys: the segments must have one channel count")
+        if outs is None:
+            outs = [torch.empty_like(s) for s in segments]
+        elif len(outs) != len(segments) or any(o.shape != s.shape or o.dtype != s.dtype or not o.is_contiguous() for o, s in zip(outs, segments)):
+            raise ValueError("add_watermark_segments_keys: outs must match the segments")
+        n = len(segments)
+        kb = b"".join(key_bytes(k) for k in keys)
+        hexes = (C.c_char_p * n)(*[p.encode() for p in payloads])
+        zf = (C.c_size_t * n)(*[int(z) for z in zero_frames])
+        src = (C.c_void_p * n)(*[_dev_ptr(s) for s in segments])
+        dst = (C.c_void_p * n)(*[_dev_ptr(o) for o in outs])
+        frames = (C.c_size_t * n)(*[s[0] for s in shapes])
+        if sample_rate != 44100:
+            _check(lib.awm_add_watermark_segments_keys_rate_d(self._h, kb, n, hexes, zf, src, dst, frames, ch, sample_rate),
+                   "awm_add_watermark_segments_keys_rate_d")
+            return outs
+        _check(lib.awm_add_watermark_segments_keys_d(self._h, kb, n, hexes, zf, src, dst, frames, ch), "awm_add_watermark_segments_keys_d")
+        return outs
+
+    def key_templates(self, keys):
+        """K16t alone (awm_debug_key_templates_d): the templates of the keys, built on the device, int16 [len(keys)][360624]; the first
+        2 * 2226 * 81 entries of row i == frame_mod_template(keys[i]), zeros behind.  The default geometry only (AwmError otherwise)."""
+        keys = list(keys)
+        stride = (2 * BLOCK_FRAMES * N_BANDS + 15) // 16 * 16
+        out = np.full((len(keys), stride), -1, np.int16)
+        _check(lib.awm_debug_key_templates_d(self._h, b"".join(key_bytes(k) for k in keys), len(keys), _np(out)), "awm_debug_key_templates_d")
+        return out
+
+    def key_payload_tables(self, keys, payloads):
+        """K16t + K16p (awm_debug_key_payload_tables_d): the frame_mod tables of (keys[i], payloads[i]), built on the device, int8
+        [n][2][2226][81]; == tab_frame_mod(keys[i], payloads[i]).  The default geometry only (AwmError otherwise)."""
+        keys, payloads = list(keys), list(payloads)
+        if len(keys) != len(payloads):
+            raise ValueError("key_payload_tables: keys and payloads must have one length")
+        hexes = (C.c_char_p * len(payloads))(*[p.encode() for p in payloads])
+        out = np.full((len(payloads), 2, BLOCK_FRAMES, N_BANDS), -1, np.int8)
+        _check(lib.awm_debug_key_payload_tables_d(self._h, b"".join(key_bytes(k) for k in keys), hexes, len(payloads), _np(out)),
+               "awm_debug_key_payload_tables_d")
+        return out
 
     def payload_tables(self, key, payloads, block_frames=None):
         """K16p alone (awm_debug_payload_tables_d): the frame_mod tables of the payloads, built on the device; == tab_frame_mod per payload"""

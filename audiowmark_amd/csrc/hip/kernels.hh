@@ -450,14 +450,31 @@ size_t key_table_scratch_bytes();
 size_t key_table_bytes();
 hipError_t launch_frame_mod_tables (hipStream_t st, const KeyTableArgs& a);
 
+/* K16t (keytab.hip): the TEMPLATES of many keys in one launch, one workgroup per key with K16's draws and shuffles: key i of the launch
+ * writes tmpl + i * stride, stride entries of int16 in the format of host/wmcommon.cc build_frame_mod_template ([2 (A, B)][2226][81], zeros
+ * behind the last one) -- what K16p reads.  tmpl is 16-byte aligned, stride a multiple of 16 of at least key_table_bytes() entries
+ * (payload_table_stride (2226)).  KeyTableArgs::coded and ::tables are not used.  The default geometry only, like K16: mix on, two
+ * frames per bit, 858 coded bits. */
+struct KeyTemplateOut
+{
+  short    *tmpl;
+  long long stride;
+};
+hipError_t launch_key_templates (hipStream_t st, const KeyTableArgs& a, const KeyTemplateOut& t);
+
 /* K16p (keytab.hip): the frame_mod tables of MANY PAYLOADS with one key, expanded from the key's template (host/wmcommon.cc
  * build_frame_mod_template: int16 per (block type, frame, band): 0 / 1 / 2 as they are, 4 + 2 k + s = UP if coded bit k of the block type
  * xor s, else DOWN) in one launch: blockIdx.y = payload.  coded: n_payloads x [2 (A, B)][n_code] bytes 0 / 1; tables: n_payloads tables
  * of table_stride bytes each in K2's format, [2 * half_entries] int8 + padding.  table_stride is a multiple of 16 >= 2 * half_entries,
- * and the template holds table_stride entries (zeros behind the last one): every load and store is a whole 16-byte piece. */
+ * and the template holds table_stride entries (zeros behind the last one): every load and store is a whole 16-byte piece.
+ * A template per table: tmpl_of (device, n_payloads ints) names the slot of table blockIdx.y, slot s begins at tmpl + s * tmpl_stride
+ * (tmpl_stride: entries, a multiple of 8 >= table_stride); nullptr: every table reads tmpl itself.  The caller orders the tables by
+ * slot, so that neighbouring workgroups share a template in L2. */
 struct PayloadTableArgs
 {
   const short         *tmpl;
+  const int           *tmpl_of;
+  long long            tmpl_stride;
   const unsigned char *coded;
   signed char         *tables;
   long long            table_stride;

@@ -1,6 +1,7 @@
 // keytab.hip -- K16: the frame_mod table of `add` built ON THE DEVICE, one workgroup per key; K16g: the same draws and shuffles turned
 // into the tables `get` needs for a clip with a key of its own (clip_key_tables_tail below); K16p: the tables of many PAYLOADS with one
-// key, expanded from the key's template (payload_table_kernel, at the end of the file).
+// key, expanded from the key's template (payload_table_kernel, at the end of the file); K16t: the same draws and shuffles turned into the
+// key's TEMPLATE, many keys per launch (key_template_tail below), for batches of segments with a key each: K16p then takes a template per table.
 //
 // Replaces, for batches with one key per clip (awm_add_watermark_batch_keys_d), the host's build_frame_mod_table
 // (host/wmcommon.cc; reference wmadd.cc:86-162 "init_frame_mod_vec", wmcommon.cc:143-202 UpDownGen / BitPosGen / gen_mix_entries,
@@ -231,8 +232,83 @@ clip_key_tables_tail (const ClipKeyTableOut& o, long long key, int tid, unsigned
     }
 }
 
-template<bool GET> __device__ __forceinline__ void
-key_tables_body (const KeyTableArgs& a, const ClipKeyTableOut& o)
+/* K16t's own part, after the shuffles (arguments as for clip_key_tables_tail): the key's TEMPLATE in the format of the host's
+ * build_frame_mod_template (host/wmcommon.cc) -- K16's table with, in place of UP / DOWN of a data band, the name of the coded bit that
+ * decides it: 4 + 2 k + s, k = s_order[p / 60] for mix entry p, s = 0 for the entry's up band, 1 for its down band.  The sync bands
+ * are values (A carries 010101, B 101010); the A and the B half carry the same names, K16p picks the block type by half_entries.
+ * The structure is that of K16's tail: zero fill with wide stores, then the scatter, eight entries per lane with their loads ahead of
+ * the 2-byte stores; every (frame, band) is written at most once. */
+__device__ __forceinline__ void
+key_template_tail (const KeyTemplateOut& t, long long key, int tid, const unsigned short *s_perm, const unsigned short *s_pos, const unsigned short *s_order,
+                   const unsigned char *updown)
+{
+  short *tmpl = t.tmpl + key * t.stride;
+  {
+    // (the base is 16-byte aligned and the stride a multiple of 16 entries: whole 16-byte pieces, the padding behind the last entry included)
+    uint4 *t16 = reinterpret_cast<uint4 *> (tmpl);
+    const long long n16 = t.stride / 8;
+    for (long long i = tid; i < n16; i += KT_WG)
+      t16[i] = make_uint4 (0, 0, 0, 0);
+  }
+  __threadfence_block();
+  __syncthreads();
+  constexpr short UP = 1, DOWN = 2, DATA = 4;
+  short *block_a = tmpl, *block_b = tmpl + size_t (KT_BLOCK) * KT_NB;
+  constexpr int UB = 8;
+  for (int e0 = tid; e0 < KT_SYNC * KT_BPF; e0 += KT_WG * UB)
+    {
+      int pos[UB], up[UB], down[UB], bit[UB];
+#pragma unroll
+      for (int k = 0; k < UB; k++)
+        {
+          const int e = min (e0 + k * KT_WG, KT_SYNC * KT_BPF - 1);
+          const int f = e / KT_BPF, i = e % KT_BPF;
+          bit[k] = (f / KT_SYNC_FPB) & 1;                                     // A carries 010101, B 101010
+          pos[k] = s_pos[f];
+          up[k] = updown[size_t (f) * 60 + i] - KT_MIN_BAND;
+          down[k] = updown[size_t (f) * 60 + 30 + i] - KT_MIN_BAND;
+        }
+#pragma unroll
+      for (int k = 0; k < UB; k++)
+        if (e0 + k * KT_WG < KT_SYNC * KT_BPF)
+          {
+            block_a[pos[k] * KT_NB + up[k]] = bit[k] ? UP : DOWN;
+            block_a[pos[k] * KT_NB + down[k]] = bit[k] ? DOWN : UP;
+            block_b[pos[k] * KT_NB + up[k]] = bit[k] ? DOWN : UP;
+            block_b[pos[k] * KT_NB + down[k]] = bit[k] ? UP : DOWN;
+          }
+    }
+  for (int p0 = tid; p0 < KT_MIX; p0 += KT_WG * UB)
+    {
+      int pos[UB], up[UB], down[UB], name[UB];
+#pragma unroll
+      for (int k = 0; k < UB; k++)
+        {
+          const int p = min (p0 + k * KT_WG, KT_MIX - 1);
+          const int e = s_perm[p];                                            // entry (data frame f, i) that the shuffle put at position p
+          const int f = e / KT_BPF, i = e % KT_BPF;
+          name[k] = DATA + 2 * s_order[p / (KT_BPF * KT_FPB)];                // fec[p / 60] = coded[order[p / 60]]
+          pos[k] = s_pos[KT_SYNC + f];
+          up[k] = updown[size_t (KT_SYNC + f) * 60 + i] - KT_MIN_BAND;
+          down[k] = updown[size_t (KT_SYNC + f) * 60 + 30 + i] - KT_MIN_BAND;
+        }
+#pragma unroll
+      for (int k = 0; k < UB; k++)
+        if (p0 + k * KT_WG < KT_MIX)
+          {
+            block_a[pos[k] * KT_NB + up[k]] = short (name[k]);
+            block_a[pos[k] * KT_NB + down[k]] = short (name[k] + 1);
+            block_b[pos[k] * KT_NB + up[k]] = short (name[k]);
+            block_b[pos[k] * KT_NB + down[k]] = short (name[k] + 1);
+          }
+    }
+}
+
+/* what the workgroup writes once the shuffles are done: K16 the table, K16g the tables of `get`, K16t the key's template */
+enum { KT_TABLE, KT_GET, KT_TEMPLATE };
+
+template<int MODE> __device__ __forceinline__ void
+key_tables_body (const KeyTableArgs& a, const ClipKeyTableOut& o, const KeyTemplateOut& t)
 {
   __shared__ unsigned short s_perm[KT_MIX];                // the mix shuffle's array: entry numbers
   __shared__ unsigned short s_pos[KT_BLOCK], s_pos_t[KT_BLOCK];      // frame positions and their swap targets
@@ -483,9 +559,14 @@ key_tables_body (const KeyTableArgs& a, const ClipKeyTableOut& o)
     apply_swaps (s_order, s_order_t, KT_CODED);
   __syncthreads();
 
-  if (GET)
+  if (MODE == KT_GET)
     {
       clip_key_tables_tail (o, key, tid, s_perm, s_pos, s_order, updown);
+      return;
+    }
+  if (MODE == KT_TEMPLATE)
+    {
+      key_template_tail (t, key, tid, s_perm, s_pos, s_order, updown);
       return;
     }
   // ---- the table: KEEP everywhere, then the bands of the sync frames and of the mix entries (wmcommon.cc build_frame_mod_table)
@@ -560,13 +641,19 @@ key_tables_body (const KeyTableArgs& a, const ClipKeyTableOut& o)
 __global__ void __launch_bounds__ (KT_WG)
 frame_mod_table_kernel (KeyTableArgs a)
 {
-  key_tables_body<false> (a, ClipKeyTableOut {});
+  key_tables_body<KT_TABLE> (a, ClipKeyTableOut {}, KeyTemplateOut {});
 }
 
 __global__ void __launch_bounds__ (KT_WG)
 clip_key_table_kernel (KeyTableArgs a, ClipKeyTableOut o)
 {
-  key_tables_body<true> (a, o);
+  key_tables_body<KT_GET> (a, o, KeyTemplateOut {});
+}
+
+__global__ void __launch_bounds__ (KT_WG)
+key_template_kernel (KeyTableArgs a, KeyTemplateOut t)
+{
+  key_tables_body<KT_TEMPLATE> (a, ClipKeyTableOut {}, t);
 }
 
 hipError_t
@@ -580,8 +667,21 @@ launch_frame_mod_tables (hipStream_t st, const KeyTableArgs& a)
   return hipGetLastError();
 }
 
+hipError_t
+launch_key_templates (hipStream_t st, const KeyTableArgs& a, const KeyTemplateOut& t)
+{
+  if (a.n_keys <= 0)
+    return hipSuccess;
+  if (!a.round_keys || !a.sbox || !a.scratch || !t.tmpl || a.scratch_slots <= 0 || a.n_keys > a.scratch_slots
+      || (reinterpret_cast<uintptr_t> (t.tmpl) & 15) || (t.stride & 15) || t.stride < (long long) key_table_bytes())
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL (key_template_kernel, dim3 ((unsigned) a.n_keys), dim3 (KT_WG), 0, st, a, t);
+  return hipGetLastError();
+}
+
 /* ==========================================================================================
- * K16p: the tables of many payloads with ONE key (kernels.hh PayloadTableArgs)
+ * K16p: the tables of many payloads with ONE key (kernels.hh PayloadTableArgs), or, with tmpl_of, of many (key, payload) pairs: table
+ * blockIdx.y is expanded from the template in slot tmpl_of[blockIdx.y] (K16t's output, or templates the host built)
  *
  * For one key the tables of two payloads differ only in UP <-> DOWN of the data bands (reference wmadd.cc:86-162): no AES, no shuffle --
  * the key's template names, per band, the coded bit that decides it.  A workgroup keeps its payload's 2 x n_code coded bits in LDS and
@@ -600,7 +700,8 @@ payload_table_kernel (PayloadTableArgs a)
   __syncthreads();
 
   const long long n_pieces = a.table_stride / 16;
-  const uint4 *tmpl = reinterpret_cast<const uint4 *> (a.tmpl);
+  // (a template per table: the callers order the tables by key, so neighbouring workgroups still share theirs in L2)
+  const uint4 *tmpl = reinterpret_cast<const uint4 *> (a.tmpl + (a.tmpl_of ? a.tmpl_of[blockIdx.y] * a.tmpl_stride : 0));
   uint4 *table = reinterpret_cast<uint4 *> (a.tables + size_t (blockIdx.y) * a.table_stride);
   const long long piece0 = (long long) blockIdx.x * (PT_WG * PT_PIECES) + threadIdx.x;
   uint4 lo[PT_PIECES], hi[PT_PIECES];
@@ -654,6 +755,9 @@ launch_payload_tables (hipStream_t st, const PayloadTableArgs& a)
     return hipSuccess;
   if (!a.tmpl || !a.coded || !a.tables || a.n_payloads > 65535 || a.n_code <= 0 || a.half_entries <= 0 || (a.table_stride & 15)
       || a.table_stride < 2LL * a.half_entries || (reinterpret_cast<uintptr_t> (a.tmpl) & 15) || (reinterpret_cast<uintptr_t> (a.tables) & 15))
+    return hipErrorInvalidValue;
+  // (a template per table: every slot begins on 16 bytes and holds the table_stride entries a workgroup reads)
+  if (a.tmpl_of && ((a.tmpl_stride & 7) || a.tmpl_stride < a.table_stride))
     return hipErrorInvalidValue;
   const long long n_pieces = a.table_stride / 16;
   const unsigned grid_x = unsigned ((n_pieces + PT_WG * PT_PIECES - 1) / (PT_WG * PT_PIECES));

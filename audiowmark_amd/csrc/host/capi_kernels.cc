@@ -11,6 +11,7 @@
 #include <thread>
 #include <tuple>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -2433,12 +2434,104 @@ add_segment_stream (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex
   return 0;
 }
 
+/* ---- segments with a KEY EACH (awm_add_watermark_segments_keys_d, below): what the two fused paths need beyond one key.  The tables are
+ * the distinct (key, payload) pairs, ordered by key; K16t (hip/keytab.hip) builds the templates of the keys a table group needs, at
+ * most KEY_TMPL_LAUNCH per launch, into slot key mod KEY_TMPL_SLOTS of a workspace, and K16p reads table t's template through tmpl_of[t].
+ * A group's keys are neighbours and no more than its tables, so within a group no two of them share a slot; a key whose template an
+ * earlier group built (the group boundary fell inside its run) is still there.  Geometries K16t does not cover, and
+ * awm_debug_set_key_tables_on_device (0), take the host's templates from the context's cache instead: one copy per key. ---- */
+constexpr size_t KEY_TMPL_SLOTS = 1024, KEY_TMPL_LAUNCH = 256;
+
+static bool
+key_templates_on_device_possible()
+{
+  return params().mix && params().frames_per_bit == 2 && mark_block_frame_count() == 2226 && mark_sync_frame_count() == 510
+         && code_size (ConvBlockType::a, params().payload_size) == 858;
+}
+
+struct SegmentKeys
+{
+  std::vector<std::array<uint8_t, 16>> keys;   // the distinct keys, ascending
+  std::vector<int> key_of_table;               // table -> key: non-decreasing
+  // set by the fused path
+  bool       on_device = false;
+  size_t     stride = 0;                       // entries of a template slot (awmk::payload_table_stride)
+  size_t     built = 0;                        // keys 0 .. built - 1 have had their templates made
+  const int *d_tmpl_of = nullptr;
+  const unsigned char *d_aux = nullptr;        // [S-box 256][key schedules: keys x 176]
+
+  /* bytes behind the (16-byte aligned) end of the other arguments: tmpl_of, then what K16t reads */
+  size_t arg_bytes() const { return key_of_table.size() * sizeof (int) + (on_device ? 256 + 176 * keys.size() : 0); }
+  int
+  reserve (awm_ctx *ctx, size_t table_stride)
+  {
+    on_device = g_key_tables_on_device && key_templates_on_device_possible();
+    stride = table_stride;
+    if (int rc = ctx->ws_key_tmpl.reserve (std::min (keys.size(), KEY_TMPL_SLOTS) * stride * sizeof (int16_t))) return rc;
+    if (on_device)
+      if (int rc = ctx->ws_keytab_scratch.reserve (KEY_TMPL_LAUNCH * awmk::key_table_scratch_bytes())) return rc;
+    return 0;
+  }
+  void
+  fill (char *h, const char *d)
+  {
+    int *tmpl_of = reinterpret_cast<int *> (h);
+    for (size_t t = 0; t < key_of_table.size(); t++)
+      tmpl_of[t] = int (size_t (key_of_table[t]) % KEY_TMPL_SLOTS);
+    d_tmpl_of = reinterpret_cast<const int *> (d);
+    if (!on_device)
+      return;
+    unsigned char *aux = reinterpret_cast<unsigned char *> (h) + key_of_table.size() * sizeof (int);
+    std::memcpy (aux, Aes128::sbox(), 256);
+    for (size_t k = 0; k < keys.size(); k++)
+      {
+        Aes128 aes;
+        aes.set_key (keys[k].data());
+        std::memcpy (aux + 256 + 176 * k, aes.round_keys(), 176);
+      }
+    d_aux = reinterpret_cast<const unsigned char *> (d) + key_of_table.size() * sizeof (int);
+  }
+  /* the templates of the keys that the tables up to t1 - 1 need and that are not there yet (the groups come in order) */
+  int
+  build (awm_ctx *ctx, hipStream_t st, size_t t1)
+  {
+    const size_t k1 = size_t (key_of_table[t1 - 1]) + 1;
+    short *slots = ctx->ws_key_tmpl.as<short>();
+    while (built < k1)
+      {
+        const size_t slot = built % KEY_TMPL_SLOTS;
+        if (!on_device)
+          {
+            FrameModTemplate *tmpl = ctx->get_frame_mod_template (capi_key (keys[built].data()));
+            if (!tmpl)
+              return AWM_ERR_HIP;
+            AWM_HIP_CHECK (hipMemcpyAsync (slots + slot * stride, tmpl->dev.ptr, stride * sizeof (int16_t), hipMemcpyDeviceToDevice, st));
+            built++;
+            continue;
+          }
+        const size_t kn = std::min ({ KEY_TMPL_LAUNCH, k1 - built, KEY_TMPL_SLOTS - slot });
+        awmk::KeyTableArgs ka {};
+        ka.sbox = d_aux;
+        ka.round_keys = d_aux + 256 + 176 * built;
+        ka.scratch = ctx->ws_keytab_scratch.as<unsigned char>();
+        ka.scratch_slots = int (KEY_TMPL_LAUNCH);
+        ka.n_keys = (long long) kn;
+        const awmk::KeyTemplateOut out { slots + slot * stride, (long long) stride };
+        ProfScope ps (ctx, PROF_KEY_TEMPLATE, double (kn) * stride * sizeof (int16_t), st);       // the templates out, once (721 KB per key)
+        AWM_HIP_CHECK (awmk::launch_key_templates (st, ka, out));
+        built += kn;
+      }
+    return 0;
+  }
+};
+
 /* the fused path: segs = the segments with samples, ordered by payload; payload_of[i] = index of segment i's payload among the distinct
- * ones; coded = their codes, [distinct][2 (A, B)][n_code] bytes */
+ * ones; coded = their codes, [distinct][2 (A, B)][n_code] bytes.  With a key per segment (mk; key is not used): ordered by (key, payload),
+ * and "payload" reads "(key, payload) pair" -- a table each, expanded from the template of its key */
 static int
 add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_t>& segs, const std::vector<size_t>& payload_of,
                     const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames, const float *const *pcm_in_d,
-                    float *const *out_d, const size_t *n_frames)
+                    float *const *out_d, const size_t *n_frames, SegmentKeys *mk = nullptr)
 {
   constexpr size_t PER_LAUNCH = 4096;                      // (blockIdx.y <= 65535; a launch of 4096 clips fills the device many times over)
   constexpr size_t TABLE_GROUP = 1024;                     // distinct payloads whose tables exist at a time (~370 MB at the default geometry)
@@ -2449,8 +2542,8 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
   const size_t table_stride = awmk::payload_table_stride (block_frames);
   hipStream_t st = ctx->stream;
 
-  FrameModTemplate *tmpl = ctx->get_frame_mod_template (capi_key (key));
-  if (!tmpl)
+  FrameModTemplate *tmpl = mk ? nullptr : ctx->get_frame_mod_template (capi_key (key));      // (a key per segment: SegmentKeys' templates)
+  if (!tmpl && !mk)
     return AWM_ERR_HIP;
 
   // geometry of every segment and the batches: consecutive segments (in payload order) of one table group, at most PER_LAUNCH of them
@@ -2494,7 +2587,10 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
   // one page-locked block, one upload: the segments' kernel arguments, the gather / scatter lists of the staged ones, the payloads' codes
   const size_t off_lim = n * sizeof (awmk::AddMixArgs), off_gather = off_lim + n * sizeof (awmk::LimiterClip),
                off_scatter = off_gather + n_staged * sizeof (awmk::SegmentCopy), off_coded = off_scatter + n_staged * sizeof (awmk::SegmentCopy),
-               arg_bytes = off_coded + coded.size();
+               off_keys = (off_coded + coded.size() + 15) / 16 * 16;
+  if (mk)
+    if (int rc = mk->reserve (ctx, table_stride)) return rc;
+  const size_t arg_bytes = mk ? off_keys + mk->arg_bytes() : off_coded + coded.size();
   if (int rc = ctx->ws_add_batch.reserve (arg_bytes)) return rc;
   if (int rc = ctx->ws_keytab.reserve (std::min (n_distinct, TABLE_GROUP) * table_stride)) return rc;
   if (use_limiter)
@@ -2521,6 +2617,8 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
   const auto *d_gather = reinterpret_cast<const awmk::SegmentCopy *> (d + off_gather), *d_scatter = reinterpret_cast<const awmk::SegmentCopy *> (d + off_scatter);
   const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
   std::memcpy (h + off_coded, coded.data(), coded.size());
+  if (mk)
+    mk->fill (h + off_keys, d + off_keys);
   float *block_max = ctx->ws_block_max.as<float>();
   float2 *tabs = ctx->ws_limit_tab.as<float2>();
   std::vector<long long> spans (n);
@@ -2564,13 +2662,19 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
       if (group != group_built)
         {
           awmk::PayloadTableArgs pa {};
-          pa.tmpl = tmpl->dev.as<short>();
+          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
+          pa.tmpl = mk ? ctx->ws_key_tmpl.as<short>() : tmpl->dev.as<short>();
+          if (mk)
+            {
+              if (int rc = mk->build (ctx, st, group * TABLE_GROUP + size_t (pa.n_payloads))) return rc;
+              pa.tmpl_of = mk->d_tmpl_of + group * TABLE_GROUP;
+              pa.tmpl_stride = (long long) table_stride;
+            }
           pa.coded = d_coded + group * TABLE_GROUP * 2 * n_code;
           pa.tables = ctx->ws_keytab.as<signed char>();
           pa.table_stride = (long long) table_stride;
           pa.half_entries = int (block_frames * Params::n_bands);
           pa.n_code = int (n_code);
-          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
           ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (pa.n_payloads) * table_stride, st);          // the tables out, once
           AWM_HIP_CHECK (awmk::launch_payload_tables (st, pa));
           group_built = group;
@@ -2885,7 +2989,7 @@ segments_rate_fit_the_workspaces (size_t n_segments, const size_t *zero_frames, 
 static int
 add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const ResampleTable& up, const uint8_t key[16], const std::vector<size_t>& segs,
                          const std::vector<size_t>& payload_of, const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames,
-                         const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int rate)
+                         const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int rate, SegmentKeys *mk = nullptr)
 {
   constexpr size_t PER_LAUNCH = 4096, TABLE_GROUP = 1024;  // as in add_segments_fused
   const int C = 2;
@@ -2895,8 +2999,8 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
   const size_t table_stride = awmk::payload_table_stride (block_frames);
   hipStream_t st = ctx->stream;
 
-  FrameModTemplate *tmpl = ctx->get_frame_mod_template (capi_key (key));
-  if (!tmpl)
+  FrameModTemplate *tmpl = mk ? nullptr : ctx->get_frame_mod_template (capi_key (key));      // (a key per segment: SegmentKeys' templates)
+  if (!tmpl && !mk)
     return AWM_ERR_HIP;
 
   // the window of every segment and the batches: consecutive segments (in payload order) of one table group, at most PER_LAUNCH of them.
@@ -2972,7 +3076,10 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
   // one page-locked block, one upload: the kernel arguments of every stage and the payloads' codes
   const size_t off_mix = n_down * sizeof (awmk::ResampleSlice), off_up = off_mix + n * sizeof (awmk::AddMixArgs),
                off_mm = off_up + n * sizeof (awmk::ResampleSlice), off_lim = off_mm + n * sizeof (awmk::MixSegment),
-               off_coded = off_lim + n * sizeof (awmk::LimiterClip), arg_bytes = off_coded + coded.size();
+               off_coded = off_lim + n * sizeof (awmk::LimiterClip), off_keys = (off_coded + coded.size() + 15) / 16 * 16;
+  if (mk)
+    if (int rc = mk->reserve (ctx, table_stride)) return rc;
+  const size_t arg_bytes = mk ? off_keys + mk->arg_bytes() : off_coded + coded.size();
   if (int rc = ctx->ws_add_batch.reserve (arg_bytes)) return rc;
   if (int rc = ctx->ws_keytab.reserve (std::min (n_distinct, TABLE_GROUP) * table_stride)) return rc;
   if (int rc = ctx->ws_rate_a.reserve (x44_max * sizeof (float))) return rc;
@@ -2999,6 +3106,8 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
   const auto *d_lim = reinterpret_cast<const awmk::LimiterClip *> (d + off_lim);
   const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
   std::memcpy (h + off_coded, coded.data(), coded.size());
+  if (mk)
+    mk->fill (h + off_keys, d + off_keys);
   float *x44 = ctx->ws_rate_a.as<float>(), *wm44 = ctx->ws_rate_b.as<float>(), *wm = ctx->ws_rate_c.as<float>();
   float *block_max = ctx->ws_block_max.as<float>();
   float2 *tabs = ctx->ws_limit_tab.as<float2>();
@@ -3030,13 +3139,19 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
       if (group != group_built)
         {
           awmk::PayloadTableArgs pa {};
-          pa.tmpl = tmpl->dev.as<short>();
+          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
+          pa.tmpl = mk ? ctx->ws_key_tmpl.as<short>() : tmpl->dev.as<short>();
+          if (mk)
+            {
+              if (int rc = mk->build (ctx, st, group * TABLE_GROUP + size_t (pa.n_payloads))) return rc;
+              pa.tmpl_of = mk->d_tmpl_of + group * TABLE_GROUP;
+              pa.tmpl_stride = (long long) table_stride;
+            }
           pa.coded = d_coded + group * TABLE_GROUP * 2 * n_code;
           pa.tables = ctx->ws_keytab.as<signed char>();
           pa.table_stride = (long long) table_stride;
           pa.half_entries = int (block_frames * Params::n_bands);
           pa.n_code = int (n_code);
-          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
           ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (pa.n_payloads) * table_stride, st);          // the tables out, once
           AWM_HIP_CHECK (awmk::launch_payload_tables (st, pa));
           group_built = group;
@@ -3138,6 +3253,271 @@ awm_add_watermark_segments_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n
   if (segs.empty())
     return 0;
   return add_segments_rate_fused (ctx, *down, *up, key, segs, payload_of, coded, n_code, zero_frames, pcm_in_d, out_d, n_frames, sample_rate);
+}
+
+/* ---- segments with a key each: awm_add_watermark_segments_keys_d / _rate_d (include/awm_hip.h).  The fused paths
+ * above with one thing more per table: the template it is expanded from (SegmentKeys). ---- */
+static bool
+segments_share_one_key (const uint8_t *keys, size_t n_segments)
+{
+  for (size_t i = 1; i < n_segments; i++)
+    if (std::memcmp (keys, keys + 16 * i, 16))
+      return false;
+  return true;
+}
+
+/* the segments with samples by (key, payload); the tables = the distinct pairs in that order (table_of[i]: the table of ordered segment
+ * i, coded_tables: their codes), the distinct keys and the key of every table (mk) */
+static void
+segments_by_key_and_payload (size_t n_segments, const uint8_t *keys, const size_t *n_frames, const std::vector<size_t>& payload_index,
+                             const std::vector<unsigned char>& coded, size_t n_code, SegmentKeys& mk, std::vector<size_t>& segs,
+                             std::vector<size_t>& table_of, std::vector<unsigned char>& coded_tables)
+{
+  segs.clear();
+  for (size_t i = 0; i < n_segments; i++)
+    if (n_frames[i])
+      segs.push_back (i);
+  std::stable_sort (segs.begin(), segs.end(), [&] (size_t x, size_t y) {
+    const int c = std::memcmp (keys + 16 * x, keys + 16 * y, 16);
+    return c ? c < 0 : payload_index[x] < payload_index[y];
+  });
+  table_of.resize (segs.size());
+  coded_tables.clear();
+  for (size_t i = 0; i < segs.size(); i++)
+    {
+      const uint8_t *key = keys + 16 * segs[i];
+      const bool new_key = !i || std::memcmp (key, keys + 16 * segs[i - 1], 16);
+      if (new_key)
+        {
+          mk.keys.emplace_back();
+          std::memcpy (mk.keys.back().data(), key, 16);
+        }
+      if (new_key || payload_index[segs[i]] != payload_index[segs[i - 1]])
+        {
+          mk.key_of_table.push_back (int (mk.keys.size() - 1));
+          const unsigned char *code = coded.data() + payload_index[segs[i]] * 2 * n_code;
+          coded_tables.insert (coded_tables.end(), code, code + 2 * n_code);
+        }
+      table_of[i] = mk.key_of_table.size() - 1;
+    }
+}
+
+int
+awm_add_watermark_segments_keys_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                   const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels)
+{
+  // one key for all segments IS the one-key function
+  if (ctx && keys && n_segments && segments_share_one_key (keys, n_segments))
+    return awm_add_watermark_segments_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels);
+  AWM_ENTER (ctx);
+  g_add_segments_fused_in_use = 0;
+  if (!n_segments)
+    return 0;
+  std::vector<size_t> payload_index;
+  std::vector<unsigned char> coded;
+  size_t n_code = 0;
+  if (int rc = segments_check (ctx, "awm_add_watermark_segments_keys_d", keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels,
+                               payload_index, coded, n_code))
+    return rc;
+  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2;
+  for (size_t i = 0; i < n_segments && fused; i++)
+    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) & 15) || (reinterpret_cast<uintptr_t> (out_d[i]) & 15)))
+      fused = false;
+  if (!fused)
+    {
+      for (size_t i = 0; i < n_segments; i++)
+        if (n_frames[i])
+          if (int rc = add_segment_stream (ctx, keys + 16 * i, payload_hex[i], zero_frames[i], pcm_in_d[i], out_d[i], n_frames[i], n_channels))
+            return rc;
+      return 0;
+    }
+  SegmentKeys mk;
+  std::vector<size_t> segs, table_of;
+  std::vector<unsigned char> coded_tables;
+  segments_by_key_and_payload (n_segments, keys, n_frames, payload_index, coded, n_code, mk, segs, table_of, coded_tables);
+  g_add_segments_fused_in_use = 1;
+  if (segs.empty())
+    return 0;
+  return add_segments_fused (ctx, nullptr, segs, table_of, coded_tables, n_code, zero_frames, pcm_in_d, out_d, n_frames, &mk);
+}
+
+int
+awm_add_watermark_segments_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                        const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_add_watermark_segments_keys_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels);
+  if (ctx && keys && n_segments && segments_share_one_key (keys, n_segments))
+    return awm_add_watermark_segments_rate_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, sample_rate);
+  AWM_ENTER (ctx);
+  g_add_segments_fused_in_use = 0;
+  const char *fn = "awm_add_watermark_segments_keys_rate_d";
+  awm_segment_plan probe;
+  if (awm_add_segment_plan (sample_rate, 0, 0, &probe))
+    {
+      set_error (sample_rate <= 0 ? string_printf ("%s: bad sample rate %d", fn, sample_rate)
+                                  : string_printf ("%s: no fixed-ratio resampler between %d Hz and %d Hz (zita's VResampler is not offered here)", fn,
+                                                   sample_rate, Params::mark_sample_rate));
+      return AWM_ERR_ARG;
+    }
+  if (!n_segments)
+    return 0;
+  std::vector<size_t> payload_index;
+  std::vector<unsigned char> coded;
+  size_t n_code = 0;
+  if (int rc = segments_check (ctx, fn, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, payload_index, coded, n_code))
+    return rc;
+  for (size_t i = 0; i < n_segments; i++)
+    if (awm_add_segment_plan (sample_rate, zero_frames[i], n_frames[i], &probe))
+      {
+        set_error (string_printf ("%s: zero_frames + n_frames of segment %zu is not below 2^40", fn, i));
+        return AWM_ERR_ARG;
+      }
+  const ResampleTable *down = ctx->get_resample_table (sample_rate, Params::mark_sample_rate);
+  const ResampleTable *up = ctx->get_resample_table (Params::mark_sample_rate, sample_rate);
+  if (!down || !up)
+    return AWM_ERR_HIP;
+  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2 && probe.limiter_block >= 8192
+               && segments_rate_fit_the_workspaces (n_segments, zero_frames, n_frames, n_channels, sample_rate);
+  for (size_t i = 0; i < n_segments && fused; i++)
+    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) & 15) || (reinterpret_cast<uintptr_t> (out_d[i]) & 15)))
+      fused = false;
+  if (!fused)
+    {
+      for (size_t i = 0; i < n_segments; i++)
+        if (n_frames[i])
+          if (int rc = add_segment_rate (ctx, *down, *up, keys + 16 * i, payload_hex[i], zero_frames[i], pcm_in_d[i], out_d[i], n_frames[i], n_channels, sample_rate))
+            return rc;
+      return 0;
+    }
+  SegmentKeys mk;
+  std::vector<size_t> segs, table_of;
+  std::vector<unsigned char> coded_tables;
+  segments_by_key_and_payload (n_segments, keys, n_frames, payload_index, coded, n_code, mk, segs, table_of, coded_tables);
+  g_add_segments_fused_in_use = 1;
+  if (segs.empty())
+    return 0;
+  return add_segments_rate_fused (ctx, *down, *up, nullptr, segs, table_of, coded_tables, n_code, zero_frames, pcm_in_d, out_d, n_frames, sample_rate, &mk);
+}
+
+/* K16t alone (measurements, tests): the templates of n_keys keys built on the device, KEY_TMPL_LAUNCH per launch, and copied to the host,
+ * n_keys x awmk::payload_table_stride (2226) entries -- they must equal awm_tab_frame_mod_template key by key, zeros behind.  out may be
+ * NULL: the launches alone, on the context's stream (for timing) */
+int
+awm_debug_key_templates_d (awm_ctx *ctx, const uint8_t *keys, size_t n_keys, int16_t *out)
+{
+  AWM_ENTER (ctx);
+  if (!keys || !n_keys || !key_templates_on_device_possible())
+    {
+      set_error ("awm_debug_key_templates_d: bad argument (keys; the default geometry: mix, two frames per bit, 128 payload bits)");
+      return AWM_ERR_ARG;
+    }
+  const size_t stride = awmk::payload_table_stride (mark_block_frame_count()), aux_bytes = 256 + KEY_TMPL_LAUNCH * 176;
+  if (int rc = ctx->ws_keytab_aux.reserve (aux_bytes)) return rc;
+  if (int rc = ctx->ws_key_tmpl.reserve (std::min (n_keys, KEY_TMPL_LAUNCH) * stride * sizeof (int16_t))) return rc;
+  if (int rc = ctx->ws_keytab_scratch.reserve (KEY_TMPL_LAUNCH * awmk::key_table_scratch_bytes())) return rc;
+  std::vector<unsigned char> aux (aux_bytes);
+  std::memcpy (aux.data(), Aes128::sbox(), 256);
+  for (size_t g0 = 0; g0 < n_keys; g0 += KEY_TMPL_LAUNCH)
+    {
+      const size_t gn = std::min (KEY_TMPL_LAUNCH, n_keys - g0);
+      for (size_t i = 0; i < gn; i++)
+        {
+          Aes128 aes;
+          aes.set_key (keys + 16 * (g0 + i));
+          std::memcpy (aux.data() + 256 + 176 * i, aes.round_keys(), 176);
+        }
+      unsigned char *d_aux = ctx->ws_keytab_aux.as<unsigned char>();
+      AWM_HIP_CHECK (hipMemcpyAsync (d_aux, aux.data(), aux_bytes, hipMemcpyHostToDevice, ctx->stream));
+      awmk::KeyTableArgs ka {};
+      ka.sbox = d_aux;
+      ka.round_keys = d_aux + 256;
+      ka.scratch = ctx->ws_keytab_scratch.as<unsigned char>();
+      ka.scratch_slots = int (KEY_TMPL_LAUNCH);
+      ka.n_keys = (long long) gn;
+      const awmk::KeyTemplateOut t { ctx->ws_key_tmpl.as<short>(), (long long) stride };
+      {
+        ProfScope ps (ctx, PROF_KEY_TEMPLATE, double (gn) * stride * sizeof (int16_t));
+        AWM_HIP_CHECK (awmk::launch_key_templates (ctx->stream, ka, t));
+      }
+      if (out)
+        AWM_HIP_CHECK (hipMemcpyAsync (out + g0 * stride, ctx->ws_key_tmpl.ptr, gn * stride * sizeof (int16_t), hipMemcpyDeviceToHost, ctx->stream));
+      AWM_HIP_CHECK (stream_wait (ctx->stream));              // (the staging vector is refilled for the next launch)
+    }
+  return 0;
+}
+
+/* K16t + K16p (tests): the tables of n (key, payload) pairs, pair i with keys + 16 i, built on the device and copied to the host,
+ * n x [2][2226][81] bytes -- they must equal awm_tab_frame_mod (key i, payload i) */
+int
+awm_debug_key_payload_tables_d (awm_ctx *ctx, const uint8_t *keys, const char *const *payload_hex, size_t n, int8_t *tables_out)
+{
+  AWM_ENTER (ctx);
+  if (!keys || !payload_hex || !tables_out || !n || n > 1024 || !key_templates_on_device_possible())
+    {
+      set_error ("awm_debug_key_payload_tables_d: bad argument (1 .. 1024 pairs; the default geometry: mix, two frames per bit, 128 payload bits)");
+      return AWM_ERR_ARG;
+    }
+  const size_t n_code = code_size (ConvBlockType::a, params().payload_size), block_frames = mark_block_frame_count();
+  const size_t table_stride = awmk::payload_table_stride (block_frames), table_bytes = 2 * block_frames * Params::n_bands;
+  // the pairs by key (K16p's tables are ordered by template); pair order[t] becomes table t
+  std::vector<size_t> order (n);
+  for (size_t i = 0; i < n; i++)
+    order[i] = i;
+  std::stable_sort (order.begin(), order.end(), [&] (size_t x, size_t y) { return std::memcmp (keys + 16 * x, keys + 16 * y, 16) < 0; });
+  SegmentKeys mk;
+  std::vector<unsigned char> coded;
+  for (size_t t = 0; t < n; t++)
+    {
+      const size_t p = order[t];
+      const std::vector<int> bits = parse_payload (payload_hex[p] ? payload_hex[p] : "");
+      if (bits.empty())
+        {
+          set_error (string_printf ("awm_debug_key_payload_tables_d: cannot parse the payload at index %zu", p));
+          return AWM_ERR_ARG;
+        }
+      for (int ab = 0; ab < 2; ab++)
+        for (int c : code_encode (ab ? ConvBlockType::b : ConvBlockType::a, bits))
+          coded.push_back ((unsigned char) (c & 1));
+      if (!t || std::memcmp (keys + 16 * p, keys + 16 * order[t - 1], 16))
+        {
+          mk.keys.emplace_back();
+          std::memcpy (mk.keys.back().data(), keys + 16 * p, 16);
+        }
+      mk.key_of_table.push_back (int (mk.keys.size() - 1));
+    }
+  if (coded.size() != n * 2 * n_code)
+    {
+      set_error ("conv code of unexpected size");
+      return AWM_ERR_GENERIC;
+    }
+  if (int rc = mk.reserve (ctx, table_stride)) return rc;
+  const size_t off_keys = (coded.size() + 15) / 16 * 16;
+  std::vector<char> args (off_keys + mk.arg_bytes());
+  std::memcpy (args.data(), coded.data(), coded.size());
+  if (int rc = ctx->ws_keytab.reserve (n * table_stride)) return rc;
+  if (int rc = ctx->ws_keytab_aux.reserve (args.size())) return rc;
+  mk.fill (args.data() + off_keys, ctx->ws_keytab_aux.as<char>() + off_keys);
+  if (int rc = upload_sync (ctx->ws_keytab_aux, args.data(), args.size(), ctx->stream)) return rc;
+  if (int rc = mk.build (ctx, ctx->stream, n)) return rc;
+  awmk::PayloadTableArgs pa {};
+  pa.tmpl = ctx->ws_key_tmpl.as<short>();
+  pa.tmpl_of = mk.d_tmpl_of;
+  pa.tmpl_stride = (long long) table_stride;
+  pa.coded = ctx->ws_keytab_aux.as<unsigned char>();
+  pa.tables = ctx->ws_keytab.as<signed char>();
+  pa.table_stride = (long long) table_stride;
+  pa.half_entries = int (block_frames * Params::n_bands);
+  pa.n_code = int (n_code);
+  pa.n_payloads = int (n);
+  {
+    ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (n) * table_stride);
+    AWM_HIP_CHECK (awmk::launch_payload_tables (ctx->stream, pa));
+  }
+  for (size_t t = 0; t < n; t++)
+    AWM_HIP_CHECK (hipMemcpyAsync (tables_out + order[t] * table_bytes, ctx->ws_keytab.as<int8_t>() + t * table_stride, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  AWM_HIP_CHECK (stream_wait (ctx->stream));
+  return 0;
 }
 
 /* K16p alone (measurements, tests): the tables of n_payloads payloads with one key built on the device and copied to the host,

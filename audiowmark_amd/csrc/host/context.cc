@@ -599,7 +599,7 @@ static const char *prof_names[awm::PROF_COUNT] = {
   "stft_full_kernel",
   "resample_kernel", "resample_var_kernel", "speed_mags_kernel", "speed_compare_kernel", "frame_mod_table_kernel",
   "add_mix_multi_kernel", "payload_table_kernel",
-  "resample_mix_multi_kernel", "clip_resample_pad_kernel"
+  "resample_mix_multi_kernel", "clip_resample_pad_kernel", "key_template_kernel"
 };
 
 extern "C" {
@@ -833,6 +833,7 @@ awm_ctx_trim (awm_ctx *ctx)
   ctx->ws_add_batch.release();
   ctx->pin_add_batch.release();
   ctx->ws_seg_in.release();
+  ctx->ws_key_tmpl.release();
   ctx->ws_seg_out.release();
   ctx->ws_merge_soft.release();
   ctx->ws_rate_a.release();
@@ -862,6 +863,7 @@ awm_ctx_destroy (awm_ctx *ctx)
   awm::speed_workspace_free (ctx);
   ctx->ws_snr.release();
   ctx->ws_seg_in.release();
+  ctx->ws_key_tmpl.release();
   ctx->ws_seg_out.release();
   ctx->ws_add_batch.release();
   ctx->pin_add_batch.release();

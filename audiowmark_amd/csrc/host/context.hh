@@ -231,7 +231,7 @@ namespace awm {
 enum ProfId { PROF_ADD_MIX, PROF_LIMITER, PROF_SYNC_DB, PROF_SYNC_SCAN, PROF_LOCAL_MEAN, PROF_REFINE_DB, PROF_REFINE_SCAN,
               PROF_BLOCK_DB, PROF_SOFT_BITS, PROF_VITERBI, PROF_STFT,
               PROF_RESAMPLE, PROF_RESAMPLE_VAR, PROF_SPEED_MAGS, PROF_SPEED_COMPARE, PROF_KEYTAB, PROF_ADD_MIX_MULTI, PROF_PAYLOAD_TAB,
-              PROF_RESAMPLE_MIX, PROF_CLIP_RESAMPLE, PROF_COUNT };
+              PROF_RESAMPLE_MIX, PROF_CLIP_RESAMPLE, PROF_KEY_TEMPLATE, PROF_COUNT };
 struct ProfPending { int id; hipEvent_t start, stop; };
 }
 
@@ -289,6 +289,7 @@ struct awm_ctx : awm::WorkLane
   awm::PinnedBuffer pin_add_batch;       // their page-locked staging,
   hipEvent_t        ev_add_batch = nullptr;   // and "the staging has been copied" (the next batch may overwrite it)
   awm::DevBuffer ws_seg_in, ws_seg_out;  // awm_add_watermark_segments_d: the staged slices ("r zeros, then the segment") of segments that begin inside a frame, and their results
+  awm::DevBuffer ws_key_tmpl;            // awm_add_watermark_segments_keys_d: the templates of the keys of a table group (K16t's output, or copies of the host's), at most 1024 slots
   awm::DevBuffer ws_snr;                 // `add --snr`: { power of the watermark signal, power of the input } accumulated by every mix while snr_on
   bool           snr_on = false;
   int            chunk_lanes = awm::CHUNK_LANES;   // lanes the chunks of one stream may be spread over (awm_ctx_set_chunk_lanes)

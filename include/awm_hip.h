@@ -304,7 +304,8 @@ int awm_add_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], const char *
  * the limiter work there, one scatter launch brings the results home without the r samples (a batch stages at most 1 GiB per direction,
  * more is split); segments with r = 0 are read from and written to the caller's buffers directly.  Everything else (other channel
  * counts, a misaligned pointer, a single segment, awm_debug_set_add_batched (0)) goes segment by segment through the tile stream, with
- * the same results.  Not offered in this form: the command line, the awm_multi_* / sharded forms, a key per segment. */
+ * the same results.  Not offered in this form: the command line, the awm_multi_* / sharded forms.  A key per segment:
+ * awm_add_watermark_segments_keys_d below. */
 int awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
                                   const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
                                   int n_channels);
@@ -327,10 +328,36 @@ int awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_
  * Everything else (other channel counts, a misaligned pointer, a single segment, awm_debug_set_add_batched (0), a call with a segment
  * whose window alone exceeds such a workspace: about 50 minutes of stereo) runs the same stages segment by segment with the same window
  * arguments and the same results; awm_debug_add_segments_fused_in_use () tells which path ran.
- * Not offered in this form: the command line, the awm_multi_* / sharded forms, a key per segment. */
+ * Not offered in this form: the command line, the awm_multi_* / sharded forms.  A key per segment: awm_add_watermark_segments_keys_rate_d
+ * below. */
 int awm_add_watermark_segments_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
                                        const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
                                        int n_channels, int sample_rate);
+
+/* The same two with a KEY PER SEGMENT (a service that carries several programmes or tenants, a key each, in one queue): keys = n_segments x
+ * 16 bytes in host memory, and out_d[i] is bit for bit what awm_add_watermark_segments_d (at a rate: awm_add_watermark_segments_rate_d)
+ * writes for segment i alone with keys + 16 i.  Arguments, refusals with nothing enqueued (NULL pointers, the overlap sweep, a payload that
+ * does not parse with its index in awm_last_error, the SNR meter; at a rate: the rate and 2^40), aliasing inputs, empty segments and
+ * sample_rate == 44100 are those functions'; in addition keys == NULL with n_segments > 0 is AWM_ERR_ARG.  A call whose segments all
+ * carry one key IS the one-key function.
+ * The fused path (stereo, 16-byte aligned pointers, n_segments >= 2) orders the segments by (key, payload); equal pairs share a table.  The
+ * host contributes the 176-byte AES key schedule per distinct key and parse_payload + conv_encode per distinct payload: no table and,
+ * at the default geometry, no template is built on the host.  Per table group of at most 1024 distinct pairs, K16t (hip/keytab.hip) builds
+ * the templates of the keys the group needs and that an earlier group has not left behind -- one workgroup per key, at most 256 keys per
+ * launch --, K16p expands every pair's table from its key's template in one launch, and the stages of the one-key path run unchanged
+ * (at a rate, segments that agree in input, length and offset still share their 44.1 kHz slice whatever their keys).  At fixed numbers of
+ * distinct keys and pairs the number of launches does not depend on n_segments.  The templates (721 KB per key, at most 1024 slots) and
+ * K16t's scratch live in grow-only context workspaces that awm_ctx_trim gives back.  Other geometries (mix off, frames_per_bit != 2,
+ * another payload size) and awm_debug_set_key_tables_on_device (0) take the host's templates through the context's cache, one copy per
+ * key, with the same results.  Everything the fused path does not take goes segment by segment through the one-key per-segment path with
+ * that segment's key; awm_debug_add_segments_fused_in_use () tells which path ran.
+ * Not offered in this form: the command line, the file level, the awm_multi_* / sharded forms. */
+int awm_add_watermark_segments_keys_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex,
+                                       const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
+                                       int n_channels);
+int awm_add_watermark_segments_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex,
+                                            const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
+                                            int n_channels, int sample_rate);
 /* The window of one such segment (pure host arithmetic, no context, no device; the device path calls it per segment).  Frames and samples
  * are indices into the segment's stream: at 44.1 kHz for the frames (of 1024 samples) and the down_* samples, at sample_rate otherwise. */
 typedef struct
@@ -704,8 +731,15 @@ void awm_debug_set_add_payloads_rate_fused (int mode);  /* awm_add_watermark_pay
                                                          * down-resample + K2m, then K10 and K11 per output | 0 a loop over the single-payload path (as awm_debug_set_add_payloads_fused (0) at every rate) */
 int  awm_debug_add_payloads_rate_fused_in_use (void);   /* which of these the last awm_add_watermark_payloads_d took: 2 | 1 (also: not stereo, another fixed ratio than 44.1 -> 48 kHz, a pointer
                                                          * that is only 4-byte aligned) | 0 (also: 44.1 kHz, one payload, a VResampler rate, workspaces that could not be reserved) */
-int  awm_debug_add_segments_fused_in_use (void);  /* 1 if the last awm_add_watermark_segments_d / _rate_d took the fused path (one launch per stage), 0: segment by segment */
+int  awm_debug_add_segments_fused_in_use (void);  /* 1 if the last awm_add_watermark_segments_d / _rate_d / _keys_d / _keys_rate_d took the fused path (one launch per stage), 0: segment by segment */
 int  awm_debug_payload_tables_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int8_t *tables_out);
+/* K16t alone: the templates of n_keys keys (16 bytes each) built on the device, 256 keys per launch, copied to out: n_keys x 360624 int16
+ * (awm_tab_frame_mod_template's 2 x 2226 x 81 entries and the zeros up to a multiple of 16); out may be NULL (the launches alone).
+ * K16t + K16p: the tables of n <= 1024 (key, payload) pairs, pair i with keys + 16 i, n x 2 x 2226 x 81 bytes == awm_tab_frame_mod per pair.
+ * Both return AWM_ERR_ARG for a geometry K16t does not build (mix off, frames_per_bit != 2, a payload size other than 128 bits); the
+ * fused path of awm_add_watermark_segments_keys_d takes the host's templates there. */
+int  awm_debug_key_templates_d (awm_ctx *ctx, const uint8_t *keys, size_t n_keys, int16_t *out);
+int  awm_debug_key_payload_tables_d (awm_ctx *ctx, const uint8_t *keys, const char *const *payload_hex, size_t n, int8_t *tables_out);
                                              /* K16p alone: the frame_mod tables of 1 .. 1024 payloads with one key, expanded on the device from the key's template,
                                               * n_payloads x 2 x block frames x 81 bytes to host memory (they equal awm_tab_frame_mod payload by payload);
                                               * tables_out NULL: the launch alone, on the context's stream (timing) */
