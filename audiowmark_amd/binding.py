@@ -177,6 +177,10 @@ lib.awm_get_watermark_batch_keys_rate_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _
 lib.awm_debug_clip_slice_values.argtypes = [C.c_int]
 lib.awm_debug_clip_slice_values.restype = C.c_size_t
 lib.awm_debug_clip_stage_d.argtypes = [_vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, _vp, _vp]
+lib.awm_get_watermark_batch_rates_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, _vp, C.c_int, C.c_size_t, _vp, _vp]
+lib.awm_get_watermark_batch_keys_rates_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, _vp, C.c_int, C.c_size_t, _vp, _vp]
+lib.awm_debug_clip_stage_rates_d.argtypes = [_vp, C.c_size_t, _vp, _vp, C.c_int, _vp, _vp, _vp]
+lib.awm_get_batch_rates_plan.argtypes = [C.c_size_t, _vp, _vp, _vp, _vp]
 lib.awm_decode_chunk_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, _vp]
 lib.awm_tab_up_down.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp]
 lib.awm_tab_bit_pos.argtypes = [_vp, _vp]
@@ -441,6 +445,28 @@ def add_stream_rate_plan(sample_rate):
     plan = StreamRatePlan()
     _check(lib.awm_add_stream_rate_plan(int(sample_rate), C.byref(plan)), "awm_add_stream_rate_plan")
     return {name: int(getattr(plan, name)) for name, _ in StreamRatePlan._fields_}
+
+
+def _rates_array(sample_rate, n_clips):
+    """a sequence of sample rates, one per clip, as a C int array; None for a scalar rate (which keeps meaning one rate for the call)"""
+    if isinstance(sample_rate, (int, np.integer)):
+        return None
+    rates = [int(r) for r in sample_rate]
+    if len(rates) != n_clips:
+        raise ValueError(f"sample_rate: {len(rates)} rates for {n_clips} clips")
+    return (C.c_int * n_clips)(*rates)
+
+
+def get_batch_rates_plan(n_frames, sample_rates):
+    """awm_get_batch_rates_plan: which way every clip of a batch `get` with a rate per clip goes (0 a group | 1 a lane, fixed-ratio
+    resampler | 2 a lane, VResampler | 3 empty) and its length at 44.1 kHz -> (paths, n44), two int64 arrays (no GPU needed).  A rate
+    that the batch refuses raises AwmError."""
+    n = len(n_frames)
+    rates = _rates_array(list(sample_rates), n)
+    frames = (C.c_size_t * n)(*[int(f) for f in n_frames])
+    paths, n44 = (C.c_int * n)(), (C.c_size_t * n)()
+    _check(lib.awm_get_batch_rates_plan(n, frames, rates, paths, n44), "awm_get_batch_rates_plan")
+    return np.array(list(paths), np.int64), np.array(list(n44), np.int64)
 
 
 def tab_sync_bits(key, clip_mode=False):
@@ -833,10 +859,11 @@ class Context:
 
     def get_watermark_batch_keys(self, keys, clips, n_threads=0, max_out_per_clip=64, sample_rate=44100):
         """get_watermark of many independent resident clips, clip i with keys[i] alone (awm_get_watermark_batch_keys_d; at another
-        sample rate awm_get_watermark_batch_keys_rate_d)"""
+        sample rate awm_get_watermark_batch_keys_rate_d; sample_rate a sequence, one rate per clip: awm_get_watermark_batch_keys_rates_d)"""
         if not clips:
             return []
         assert len(keys) == len(clips)
+        rates = _rates_array(sample_rate, len(clips))
         shapes = [_pcm_shape(c) for c in clips]
         ch = shapes[0][1]
         assert all(s[1] == ch for s in shapes)
@@ -846,7 +873,11 @@ class Context:
         flat = b"".join(key_bytes(k) for k in keys)
         while True:
             buf = self._pattern_buffer(len(clips) * max_out_per_clip)
-            if sample_rate != 44100:
+            if rates is not None:
+                _check(lib.awm_get_watermark_batch_keys_rates_d(self._h, flat, len(clips), ptrs, frames, ch, rates, n_threads,
+                                                                max_out_per_clip, C.cast(buf, C.c_void_p), n_out),
+                       "awm_get_watermark_batch_keys_rates_d")
+            elif sample_rate != 44100:
                 _check(lib.awm_get_watermark_batch_keys_rate_d(self._h, flat, len(clips), ptrs, frames, ch, sample_rate, n_threads,
                                                                max_out_per_clip, C.cast(buf, C.c_void_p), n_out),
                        "awm_get_watermark_batch_keys_rate_d")
@@ -1224,8 +1255,10 @@ class Context:
     def clip_stage(self, clips, sample_rate, out=None):
         """awm_debug_clip_stage_d: stage 0 of one group of 1 .. 64 short clips alone -> (slices [n_clips, slice values] float32 on the
         device, ranges [n_clips, 2] int64: first non-zero value / last + 1 as absolute indices, -1 / 0 for a silent clip).  out: a
-        buffer of that shape to write into (what the stage leaves out keeps its contents)."""
+        buffer of that shape to write into (what the stage leaves out keeps its contents).  sample_rate a sequence, one rate per clip:
+        awm_debug_clip_stage_rates_d."""
         import torch
+        rates = _rates_array(sample_rate, len(clips))
         shapes = [_pcm_shape(c) for c in clips]
         ch = shapes[0][1]
         assert all(s[1] == ch for s in shapes)
@@ -1236,8 +1269,12 @@ class Context:
         ptrs = (C.c_void_p * len(clips))(*[_dev_ptr(c) for c in clips])
         frames = (C.c_size_t * len(clips))(*[s[0] for s in shapes])
         ranges = np.zeros((len(clips), 2), np.int64)
-        _check(lib.awm_debug_clip_stage_d(self._h, len(clips), ptrs, frames, ch, sample_rate, _dev_ptr(out), _np(ranges)),
-               "awm_debug_clip_stage_d")
+        if rates is not None:
+            _check(lib.awm_debug_clip_stage_rates_d(self._h, len(clips), ptrs, frames, ch, rates, _dev_ptr(out), _np(ranges)),
+                   "awm_debug_clip_stage_rates_d")
+        else:
+            _check(lib.awm_debug_clip_stage_d(self._h, len(clips), ptrs, frames, ch, sample_rate, _dev_ptr(out), _np(ranges)),
+                   "awm_debug_clip_stage_d")
         return out, ranges
 
     def add_get_watermark(self, key, payload_hex, pcm, out, sample_rate=44100):
@@ -1301,9 +1338,10 @@ class Context:
     def get_watermark_batch(self, key, clips, n_threads=0, max_out_per_clip=64, sample_rate=44100):
         """get_watermark of many independent resident clips (same channel count), spread over the context's work lanes;
         returns one pattern list per clip.  sample_rate != 44100 (awm_get_watermark_batch_rate_d): every clip is at that rate, its
-        result that of the clip resampled to 44.1 kHz."""
+        result that of the clip resampled to 44.1 kHz.  sample_rate a sequence (awm_get_watermark_batch_rates_d): one rate per clip."""
         if not clips:
             return []
+        rates = _rates_array(sample_rate, len(clips))
         shapes = [_pcm_shape(c) for c in clips]
         ch = shapes[0][1]
         assert all(s[1] == ch for s in shapes)
@@ -1312,7 +1350,10 @@ class Context:
         n_out = (C.c_int * len(clips))()
         while True:
             buf = self._pattern_buffer(len(clips) * max_out_per_clip)
-            if sample_rate != 44100:
+            if rates is not None:
+                _check(lib.awm_get_watermark_batch_rates_d(self._h, key_bytes(key), len(clips), ptrs, frames, ch, rates, n_threads,
+                                                           max_out_per_clip, C.cast(buf, C.c_void_p), n_out), "awm_get_watermark_batch_rates_d")
+            elif sample_rate != 44100:
                 _check(lib.awm_get_watermark_batch_rate_d(self._h, key_bytes(key), len(clips), ptrs, frames, ch, sample_rate, n_threads,
                                                           max_out_per_clip, C.cast(buf, C.c_void_p), n_out), "awm_get_watermark_batch_rate_d")
             else:

@@ -544,6 +544,43 @@ hipError_t launch_clip_pad (hipStream_t st, const ClipSrc *src /* device */, int
 struct ClipResampleSrc { const float *in; long long n_in, n44, pad_start; };
 hipError_t launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src /* device */, int n_clips, long long max_n44,
                                      bool stereo_aligned, float *dst, long long slice_values, long long margin_values, long long *range);
+/* K10x: stage 0 for a group whose clips do NOT share one rate.  Every clip brings its own descriptor: its frames, n44 and pad_start as
+ * above and its OWN resampler geometry and table (ctab / hl / np / step of its rate's ResampleTable); np == 0 marks a clip that is at
+ * 44.1 kHz already and is copied (n_in == n44).  Slice i and range[2 i ..] are bit for bit what launch_clip_resample_pad (np > 0) or
+ * launch_clip_pad (np == 0) writes for clip i alone in slice i: the taps are K10's own code (resample_slice_body / resample_phase_body), which
+ * reads its geometry from the clip's descriptor -- uniform per workgroup, scalar registers -- instead of from the launch.
+ * Launches: clip_range_init_kernel and one per FORM present in the group, whatever the number of clips or of distinct rates --
+ *   CLIP_FORM_GENERIC  the table and, for stereo with every resampled input 8-byte aligned, the tile's window in LDS (the generic taps where
+ *                      the clip's table or window does not fit); grid.y = every clip of the group, the workgroups of the other forms'
+ *                      clips leave at once; dynamic LDS = the largest of the group
+ *   CLIP_FORM_PHASE    the phase-per-thread form <147, 160, 18, 2, 8> for the aligned stereo 48 kHz clips (awm_debug_set_resample_phase)
+ *   CLIP_FORM_COPY     the 44.1 kHz clips
+ * the last two over their own clips only, whose slice indices they read from `list`.
+ * clip_stage_mixed_plan (host) chooses the form of every clip, fills form / lds_floats / in_span of src[0 .. n_clips) by the rule
+ * launch_clip_resample_pad applies to its one rate, and writes list[0 .. n_clips): the slices of the phase form from the front, those of the
+ * copy form from the back.  The launcher is given the plan and the device copies of src and list. */
+enum { CLIP_FORM_GENERIC = 0, CLIP_FORM_PHASE = 1, CLIP_FORM_COPY = 2 };
+struct ClipMixedSrc
+{
+  const float *in;
+  long long    n_in, n44, pad_start;
+  const float *ctab;                 // device, (np + 1) * hl; null for a copied clip
+  int          hl, np, step;
+  int          form;                 // CLIP_FORM_*
+  int          lds_floats, in_span;  // CLIP_FORM_GENERIC: floats of the table in LDS (0: from global memory), frames of the tile's window (0: not staged)
+};
+struct ClipMixedPlan
+{
+  int       n_channels = 0, n_clips = 0;
+  int       n_form[3] = { 0, 0, 0 };
+  long long max_n44 = 0;             // the group's longest clip: tiles per workgroup
+  long long max_n44_form[3] = { 0, 0, 0 };
+  bool      stereo_aligned = false;  // stereo and every resampled input 8-byte aligned
+  size_t    lds_bytes = 0;           // CLIP_FORM_GENERIC: the largest table + window of the group
+};
+ClipMixedPlan clip_stage_mixed_plan (ClipMixedSrc *src /* host */, int n_clips, int n_channels, int *list /* host */);
+hipError_t launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& plan, const ClipMixedSrc *src /* device */, const int *list /* device */,
+                                    float *dst, long long slice_values, long long margin_values, long long *range);
 }
 
 namespace awmk {

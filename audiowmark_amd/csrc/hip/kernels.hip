@@ -4121,13 +4121,39 @@ clip_range_commit (unsigned long long first, unsigned long long last, unsigned l
     }
 }
 
-/* kernels.hh launch_clip_pad: grid (parts, clips); slice_values % 4 == 0, 16-byte stores */
-__global__ void __launch_bounds__ (256)
-clip_pad_kernel (const ClipSrc *src, float *dst, long long slice_values, long long margin_values, unsigned long long *range)
+/* where a workgroup of clip_pad_kernel finds its clip and its slice (both uniform): clip and slice blockIdx.y of the launch's descriptors
+ * (launch_clip_pad), or -- the copy form of K10x, which runs over the 44.1 kHz clips of a group alone -- slice list[blockIdx.y] and that
+ * slice's descriptor */
+struct ClipPadEvery
 {
-  const ClipSrc c = src[blockIdx.y];
-  float4 *out = reinterpret_cast<float4 *> (dst + (long long) blockIdx.y * slice_values);
-  const long long slice0 = (long long) blockIdx.y * slice_values;
+  const ClipSrc *src;
+  __device__ __forceinline__ ClipSrc clip (unsigned int& slice) const
+  {
+    slice = blockIdx.y;
+    return src[blockIdx.y];
+  }
+};
+struct ClipPadListed
+{
+  const ClipMixedSrc *src;
+  const int          *list;
+  int                 n_channels;
+  __device__ __forceinline__ ClipSrc clip (unsigned int& slice) const
+  {
+    slice = (unsigned int) list[blockIdx.y];
+    const ClipMixedSrc c = src[slice];
+    return { c.in, c.n44 * n_channels, c.pad_start };
+  }
+};
+
+/* kernels.hh launch_clip_pad: grid (parts, clips); slice_values % 4 == 0, 16-byte stores */
+template<class From> __global__ void __launch_bounds__ (256)
+clip_pad_kernel (From from, float *dst, long long slice_values, long long margin_values, unsigned long long *range)
+{
+  unsigned int slice;
+  const ClipSrc c = from.clip (slice);
+  float4 *out = reinterpret_cast<float4 *> (dst + (long long) slice * slice_values);
+  const long long slice0 = (long long) slice * slice_values;
   const long long stride = (long long) gridDim.x * blockDim.x;
   unsigned long long first = ~0ULL, last = 0;
   // only [pad_start - margin, pad_start + n_values + margin) of the slice is written: the consumers skip every frame that lies
@@ -4156,7 +4182,7 @@ clip_pad_kernel (const ClipSrc *src, float *dst, long long slice_values, long lo
         }
       out[q] = make_float4 (v[0], v[1], v[2], v[3]);
     }
-  clip_range_commit<4> (first, last, range + 2 * blockIdx.y);
+  clip_range_commit<4> (first, last, range + 2 * slice);
 }
 
 __global__ void
@@ -4187,7 +4213,8 @@ launch_clip_pad (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, lo
       return e;
   auto *r = reinterpret_cast<unsigned long long *> (range);
   hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
-  hipLaunchKernelGGL (clip_pad_kernel, dim3 (128, unsigned (n_clips)), dim3 (256), 0, st, src, dst, slice_values, margin_values, r);
+  hipLaunchKernelGGL (clip_pad_kernel<ClipPadEvery>, dim3 (128, unsigned (n_clips)), dim3 (256), 0, st, ClipPadEvery { src }, dst, slice_values,
+                      margin_values, r);
   return hipGetLastError();
 }
 
@@ -4304,6 +4331,136 @@ launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResam
   else
     hipLaunchKernelGGL (clip_resample_pad_kernel<0>, grid, dim3 (256), lds_bytes, st, a, src, dst, slice_values, margin_values, r, lds_floats, in_span,
                         tiles_per_wg);
+  return hipGetLastError();
+}
+
+/* K10x (kernels.hh launch_clip_stage_mixed): K10c for a group of clips at several rates.  The three kernels are clip_resample_pad_kernel,
+ * clip_resample_pad_phase_kernel and clip_pad_kernel with the geometry, the table and (phase, copy) the slice index read from the clip's
+ * descriptor: one uniform load per workgroup, the values stay in scalar registers.  The taps are the same functions, and the copy form is
+ * clip_pad_kernel<ClipPadListed>. */
+/* the generic form: grid (workgroups of the longest clip, clips of the group); another form's clip: nothing to do (uniform) */
+template<int CT> __global__ void __launch_bounds__ (256)
+clip_stage_mixed_kernel (const ClipMixedSrc *__restrict__ src, int n_channels, float *dst, long long slice_values, long long margin_values,
+                         unsigned long long *range, int tiles_per_wg)
+{
+  const ClipMixedSrc c = src[blockIdx.y];
+  if (c.form != CLIP_FORM_GENERIC)
+    return;
+  ResampleArgs a {};
+  a.n_channels = n_channels;
+  a.ctab = c.ctab;
+  a.hl = c.hl;
+  a.np = c.np;
+  a.step = c.step;
+  const long long slice0 = (long long) blockIdx.y * slice_values;
+  ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
+  clip_window_zeros (dst + slice0, c.pad_start, c.n44 * n_channels, slice_values, margin_values);
+  const ResampleSlice s { c.in, c.n_in, 0, 0, c.n44, nullptr };
+  resample_slice_body<CT> (a, s, c.lds_floats, c.in_span, tiles_per_wg, sink);
+  clip_range_commit<4> (sink.first, sink.last, range + 2 * blockIdx.y);
+}
+
+/* the phase-per-thread form: grid (workgroups of the longest of these clips, these clips), slice = list[blockIdx.y] */
+template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
+clip_stage_mixed_phase_kernel (const ClipMixedSrc *__restrict__ src, const int *__restrict__ list, float *dst, long long slice_values,
+                               long long margin_values, unsigned long long *range, int tiles_per_wg)
+{
+  const int slice = list[blockIdx.y];
+  const ClipMixedSrc c = src[slice];
+  const long long slice0 = (long long) slice * slice_values;
+  ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
+  clip_window_zeros (dst + slice0, c.pad_start, c.n44 * 2, slice_values, margin_values);
+  if ((long long) blockIdx.x * tiles_per_wg * (R * J * NP) < c.n44)                // (uniform: a shorter clip of the group)
+    resample_phase_body<NP, STEP, HL, R, J> (c.ctab, c.in, c.n_in, c.n44, tiles_per_wg, sink);
+  clip_range_commit<((STEP > NP ? STEP : NP) * R + 63) / 64> (sink.first, sink.last, range + 2 * slice);
+}
+
+ClipMixedPlan
+clip_stage_mixed_plan (ClipMixedSrc *src, int n_clips, int n_channels, int *list)
+{
+  ClipMixedPlan p;
+  p.n_channels = n_channels;
+  p.n_clips = n_clips;
+  uintptr_t bits = 0;
+  for (int i = 0; i < n_clips; i++)
+    if (src[i].np > 0)
+      bits |= reinterpret_cast<uintptr_t> (src[i].in);
+  p.stereo_aligned = n_channels == 2 && (bits & 7) == 0;
+  for (int i = 0; i < n_clips; i++)
+    {
+      ClipMixedSrc& c = src[i];
+      c.lds_floats = c.in_span = 0;
+      if (c.np <= 0)
+        c.form = CLIP_FORM_COPY;
+      else if (g_resample_phase && p.stereo_aligned && c.np == 147 && c.step == 160 && c.hl == 18)
+        c.form = CLIP_FORM_PHASE;
+      else
+        {
+          // the table and the tile's window in LDS exactly as launch_clip_resample_pad sizes them for the clip's rate
+          c.form = CLIP_FORM_GENERIC;
+          const int want = (c.np + 1) * (c.hl | 1);
+          c.lds_floats = want <= RS_MAX_TAB ? want : 0;
+          const long long span = ((long long) (RS_TILE - 1) * c.step) / c.np + 2 + 2LL * c.hl;
+          const bool stage = p.stereo_aligned && c.lds_floats > 0 && span <= 4096 && (long long) RS_TILE * c.step + c.np < (1LL << 31);
+          c.in_span = stage ? int (span) : 0;
+          p.lds_bytes = std::max (p.lds_bytes, size_t ((c.lds_floats + 1) & ~1) * sizeof (float) + size_t (c.in_span) * sizeof (float2));
+        }
+      p.max_n44 = std::max (p.max_n44, c.n44);
+      p.max_n44_form[c.form] = std::max (p.max_n44_form[c.form], c.n44);
+      if (c.form == CLIP_FORM_PHASE)
+        list[p.n_form[CLIP_FORM_PHASE]] = i;
+      else if (c.form == CLIP_FORM_COPY)
+        list[n_clips - 1 - p.n_form[CLIP_FORM_COPY]] = i;
+      p.n_form[c.form]++;
+    }
+  return p;
+}
+
+hipError_t
+launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& p, const ClipMixedSrc *src, const int *list, float *dst, long long slice_values,
+                         long long margin_values, long long *range)
+{
+  const int n_clips = p.n_clips;
+  if (n_clips <= 0 || slice_values <= 0)
+    return hipSuccess;
+  if (n_clips > 65535 || p.max_n44 < 0 || slice_values % 4 || margin_values < 0 || (reinterpret_cast<uintptr_t> (dst) & 15) || p.n_channels < 1
+      || !src || !list || p.n_form[0] + p.n_form[1] + p.n_form[2] != n_clips || p.lds_bytes > size_t (64 * 1024))
+    return hipErrorInvalidValue;
+  if (g_clip_poison)
+    if (hipError_t e = hipMemsetAsync (dst, 0xff, size_t (n_clips) * size_t (slice_values) * sizeof (float), st))
+      return e;
+  auto *r = reinterpret_cast<unsigned long long *> (range);
+  hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
+  // tiles per workgroup by launch_clip_resample_pad's rule over the GROUP: tiles of its longest clip x its clips / 4096, between 1 and 8;
+  // the grid of a form reaches as far as the longest clip of that form
+  auto tiles = [&] (int tile, int form, int& tiles_per_wg) {
+    const long long n_tiles = std::max<long long> (1, (p.max_n44 + tile - 1) / tile);
+    tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_clips / 4096)));
+    const long long form_tiles = std::max<long long> (1, (p.max_n44_form[form] + tile - 1) / tile);
+    return unsigned ((form_tiles + tiles_per_wg - 1) / tiles_per_wg);
+  };
+  if (p.n_form[CLIP_FORM_GENERIC])
+    {
+      int tiles_per_wg;
+      const dim3 grid (tiles (RS_TILE, CLIP_FORM_GENERIC, tiles_per_wg), unsigned (n_clips));
+      if (p.stereo_aligned)
+        hipLaunchKernelGGL (clip_stage_mixed_kernel<2>, grid, dim3 (256), p.lds_bytes, st, src, p.n_channels, dst, slice_values, margin_values, r,
+                            tiles_per_wg);
+      else
+        hipLaunchKernelGGL (clip_stage_mixed_kernel<0>, grid, dim3 (256), p.lds_bytes, st, src, p.n_channels, dst, slice_values, margin_values, r,
+                            tiles_per_wg);
+    }
+  if (p.n_form[CLIP_FORM_PHASE])
+    {
+      constexpr int NP = 147, STEP = 160, HL = 18, R = 2, J = 8;
+      int tiles_per_wg;
+      const dim3 grid (tiles (R * J * NP, CLIP_FORM_PHASE, tiles_per_wg), unsigned (p.n_form[CLIP_FORM_PHASE]));
+      hipLaunchKernelGGL ((clip_stage_mixed_phase_kernel<NP, STEP, HL, R, J>), grid, dim3 ((STEP * R + 63) / 64 * 64), 0, st, src, list, dst,
+                          slice_values, margin_values, r, tiles_per_wg);
+    }
+  if (p.n_form[CLIP_FORM_COPY])
+    hipLaunchKernelGGL (clip_pad_kernel<ClipPadListed>, dim3 (128, unsigned (p.n_form[CLIP_FORM_COPY])), dim3 (256), 0, st,
+                        ClipPadListed { src, list + (n_clips - p.n_form[CLIP_FORM_COPY]), p.n_channels }, dst, slice_values, margin_values, r);
   return hipGetLastError();
 }
 

@@ -4052,11 +4052,133 @@ clip_rates (awm_ctx *ctx, int sample_rate, size_t n_clips, const size_t *n_frame
       set_error (string_printf ("resampling from old_rate=%d to new_rate=%d not implemented", sample_rate, int (Params::mark_sample_rate)));
       return AWM_ERR_ARG;
     }
-  rates.sample_rate = sample_rate;
-  rates.table = conv.fixed;
+  rates.sample_rate.assign (n_clips, sample_rate);
+  rates.table.assign (n_clips, conv.fixed);
   rates.n44.clear();
   for (size_t i = 0; i < n_clips; i++)
     rates.n44.push_back (conv.stream_frames (n_frames[i]));
+  return 0;
+}
+
+/* ... with a rate per clip.  A clip's way through the batch and its length at 44.1 kHz, without a context (awm_get_batch_rates_plan): false
+ * for a rate that is not positive or that neither resampler class takes */
+enum { RATES_PATH_GROUP = 0, RATES_PATH_LANE_FIXED = 1, RATES_PATH_LANE_VAR = 2, RATES_PATH_EMPTY = 3 };
+static bool
+clip_rate_plan (size_t n_frames, int sample_rate, int& path, size_t& n44)
+{
+  path = -1;
+  n44 = 0;
+  if (sample_rate <= 0)
+    return false;
+  bool fixed = true;
+  if (sample_rate == Params::mark_sample_rate)
+    n44 = n_frames;
+  else
+    {
+      ResampleTable t;
+      fixed = resample_fixed_ratio (sample_rate, Params::mark_sample_rate, t.hl, t.np, t.step);
+      if (fixed)
+        n44 = resample_fixed_frames (t, n_frames);
+      else
+        {
+          const VarResampleGeometry var = var_resample_geometry (double (Params::mark_sample_rate) / sample_rate);
+          if (!var.ok)
+            return false;
+          n44 = var.stream_frames (n_frames);
+        }
+    }
+  path = !n44 ? RATES_PATH_EMPTY : !fixed ? RATES_PATH_LANE_VAR : clip_is_short (n44) ? RATES_PATH_GROUP : RATES_PATH_LANE_FIXED;
+  return true;
+}
+
+/* the refusals of a call with a rate per clip: AWM_ERR_ARG and a message that names the first offending clip, before anything is enqueued */
+static int
+check_clip_rates (const char *who, size_t n_clips, const size_t *n_frames, const int *sample_rates)
+{
+  if (!sample_rates)
+    {
+      set_error (string_printf ("%s: sample_rates is null", who));
+      return AWM_ERR_ARG;
+    }
+  for (size_t i = 0; i < n_clips; i++)
+    {
+      int path;
+      size_t n44;
+      if (!clip_rate_plan (n_frames[i], sample_rates[i], path, n44))
+        {
+          set_error (string_printf ("%s: clip %zu: resampling from old_rate=%d to new_rate=%d not implemented", who, i, sample_rates[i],
+                                    int (Params::mark_sample_rate)));
+          return AWM_ERR_ARG;
+        }
+    }
+  return 0;
+}
+
+/* the converters of the (checked) rates of a call, one table per distinct rate from the context, and every clip's length at 44.1 kHz */
+static int
+clip_rates_each (awm_ctx *ctx, const int *sample_rates, size_t n_clips, const size_t *n_frames, ClipRates& rates)
+{
+  std::map<int, RateConverter> convs;
+  rates.sample_rate.assign (sample_rates, sample_rates + n_clips);
+  rates.table.assign (n_clips, nullptr);
+  rates.n44.assign (n_clips, 0);
+  for (size_t i = 0; i < n_clips; i++)
+    {
+      if (sample_rates[i] == Params::mark_sample_rate)
+        {
+          rates.n44[i] = n_frames[i];
+          continue;
+        }
+      auto it = convs.find (sample_rates[i]);
+      if (it == convs.end())
+        it = convs.emplace (sample_rates[i], rate_converter (ctx, sample_rates[i], Params::mark_sample_rate)).first;
+      if (!it->second.ok())
+        return AWM_ERR_ARG;
+      rates.table[i] = it->second.fixed;
+      rates.n44[i] = it->second.stream_frames (n_frames[i]);
+    }
+  return 0;
+}
+
+static bool
+rates_all_equal (size_t n_clips, const int *sample_rates)
+{
+  if (!n_clips || !sample_rates)
+    return false;
+  for (size_t i = 1; i < n_clips; i++)
+    if (sample_rates[i] != sample_rates[0])
+      return false;
+  return true;
+}
+
+static int
+get_watermark_batch_rates (awm_ctx *ctx, const char *who, const uint8_t key[16], const uint8_t *keys, size_t n_clips, const float *const *pcm_d,
+                           const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out,
+                           int *n_out)
+{
+  if (!n_clips)
+    return 0;
+  if (!pcm_d || !n_frames || !n_out || (max_out_per_clip && !out) || (!key && !keys) || n_channels < 1)
+    {
+      set_error (string_printf ("%s: bad argument", who));
+      return AWM_ERR_ARG;
+    }
+  if (int rc = check_clip_rates (who, n_clips, n_frames, sample_rates))
+    return rc;
+  ClipRates rates;
+  if (int rc = clip_rates_each (ctx, sample_rates, n_clips, n_frames, rates))
+    return rc;
+  std::vector<DeviceWav> clips;
+  for (size_t i = 0; i < n_clips; i++)
+    clips.push_back (make_wav_rate (pcm_d[i], n_frames[i], n_channels, sample_rates[i]));
+  std::vector<Key> clip_keys;
+  if (keys)
+    clip_keys = key_list_from (keys, int (n_clips));
+  std::vector<ResultSet> sets;
+  if (int rc = get_watermark_batch_device (ctx, keys ? std::vector<Key> {} : std::vector<Key> { capi_key (key) }, clips, sets, n_threads,
+                                           keys ? &clip_keys : nullptr, &rates))
+    return rc;
+  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
   return 0;
 }
 
@@ -4099,7 +4221,7 @@ awm_get_watermark_rate_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_
   if (int rc = clip_rates (ctx, sample_rate, 1, &n_frames, rates))
     return rc;
   DeviceWav wav44;
-  if (int rc = resample_to_mark_rate (ctx, ctx, rates, make_wav_rate (pcm_d, n_frames, n_channels, sample_rate), rates.n44[0], wav44))
+  if (int rc = resample_to_mark_rate (ctx, ctx, rates, 0, make_wav_rate (pcm_d, n_frames, n_channels, sample_rate), wav44))
     return rc;
   ResultSet rs;
   if (int rc = get_watermark_device (ctx, { capi_key (key) }, wav44, rs))
@@ -4158,6 +4280,87 @@ awm_debug_clip_stage_d (awm_ctx *ctx, size_t n_clips, const float *const *pcm_d,
   for (size_t i = 0; i < n_clips; i++)
     clips.push_back (make_wav_rate (pcm_d[i], n_frames[i], n_channels, sample_rate));
   return clip_stage_device (ctx, clips, at_rate ? &rates : nullptr, slices_d, range_out);
+}
+
+int
+awm_get_watermark_batch_rates_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
+                                 int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  if (rates_all_equal (n_clips, sample_rates))           // IS the one-rate function (which hands 44.1 kHz on), before anything else happens
+    return awm_get_watermark_batch_rate_d (ctx, key, n_clips, pcm_d, n_frames, n_channels, sample_rates[0], n_threads, max_out_per_clip, out, n_out);
+  AWM_ENTER (ctx);
+  if (n_clips && !key)
+    {
+      set_error ("awm_get_watermark_batch_rates_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  return get_watermark_batch_rates (ctx, "awm_get_watermark_batch_rates_d", key, nullptr, n_clips, pcm_d, n_frames, n_channels, sample_rates, n_threads,
+                                    max_out_per_clip, out, n_out);
+}
+
+int
+awm_get_watermark_batch_keys_rates_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
+                                      int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  if (rates_all_equal (n_clips, sample_rates))
+    return awm_get_watermark_batch_keys_rate_d (ctx, keys, n_clips, pcm_d, n_frames, n_channels, sample_rates[0], n_threads, max_out_per_clip, out,
+                                                n_out);
+  AWM_ENTER (ctx);
+  if (n_clips && !keys)
+    {
+      set_error ("awm_get_watermark_batch_keys_rates_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  return get_watermark_batch_rates (ctx, "awm_get_watermark_batch_keys_rates_d", nullptr, keys, n_clips, pcm_d, n_frames, n_channels, sample_rates,
+                                    n_threads, max_out_per_clip, out, n_out);
+}
+
+int
+awm_debug_clip_stage_rates_d (awm_ctx *ctx, size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels, const int *sample_rates,
+                              float *slices_d, long long *range_out)
+{
+  AWM_ENTER (ctx);
+  if (!n_clips || !pcm_d || !n_frames || n_channels < 1)
+    {
+      set_error ("awm_debug_clip_stage_rates_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  if (int rc = check_clip_rates ("awm_debug_clip_stage_rates_d", n_clips, n_frames, sample_rates))
+    return rc;
+  ClipRates rates;
+  if (int rc = clip_rates_each (ctx, sample_rates, n_clips, n_frames, rates))
+    return rc;
+  std::vector<DeviceWav> clips;
+  for (size_t i = 0; i < n_clips; i++)
+    clips.push_back (make_wav_rate (pcm_d[i], n_frames[i], n_channels, sample_rates[i]));
+  return clip_stage_device (ctx, clips, &rates, slices_d, range_out);
+}
+
+int
+awm_get_batch_rates_plan (size_t n_clips, const size_t *n_frames, const int *sample_rates, int *path_out, size_t *n44_out)
+{
+  if (n_clips && (!n_frames || !sample_rates))
+    {
+      set_error ("awm_get_batch_rates_plan: bad argument");
+      return AWM_ERR_ARG;
+    }
+  int rc = 0;
+  for (size_t i = 0; i < n_clips; i++)
+    {
+      int path;
+      size_t n44;
+      if (!clip_rate_plan (n_frames[i], sample_rates[i], path, n44) && !rc)
+        {
+          set_error (string_printf ("awm_get_batch_rates_plan: clip %zu: resampling from old_rate=%d to new_rate=%d not implemented", i, sample_rates[i],
+                                    int (Params::mark_sample_rate)));
+          rc = AWM_ERR_ARG;
+        }
+      if (path_out)
+        path_out[i] = path;
+      if (n44_out)
+        n44_out[i] = n44;
+    }
+  return rc;
 }
 
 int

@@ -599,7 +599,7 @@ static const char *prof_names[awm::PROF_COUNT] = {
   "stft_full_kernel",
   "resample_kernel", "resample_var_kernel", "speed_mags_kernel", "speed_compare_kernel", "frame_mod_table_kernel",
   "add_mix_multi_kernel", "payload_table_kernel",
-  "resample_mix_multi_kernel", "clip_resample_pad_kernel", "key_template_kernel"
+  "resample_mix_multi_kernel", "clip_resample_pad_kernel", "key_template_kernel", "clip_stage_mixed_kernel"
 };
 
 extern "C" {

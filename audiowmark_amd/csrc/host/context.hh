@@ -231,7 +231,7 @@ namespace awm {
 enum ProfId { PROF_ADD_MIX, PROF_LIMITER, PROF_SYNC_DB, PROF_SYNC_SCAN, PROF_LOCAL_MEAN, PROF_REFINE_DB, PROF_REFINE_SCAN,
               PROF_BLOCK_DB, PROF_SOFT_BITS, PROF_VITERBI, PROF_STFT,
               PROF_RESAMPLE, PROF_RESAMPLE_VAR, PROF_SPEED_MAGS, PROF_SPEED_COMPARE, PROF_KEYTAB, PROF_ADD_MIX_MULTI, PROF_PAYLOAD_TAB,
-              PROF_RESAMPLE_MIX, PROF_CLIP_RESAMPLE, PROF_KEY_TEMPLATE, PROF_COUNT };
+              PROF_RESAMPLE_MIX, PROF_CLIP_RESAMPLE, PROF_KEY_TEMPLATE, PROF_CLIP_STAGE_MIXED, PROF_COUNT };
 struct ProfPending { int id; hipEvent_t start, stop; };
 }
 

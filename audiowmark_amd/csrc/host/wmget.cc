@@ -1416,7 +1416,7 @@ extern "C" void awm_debug_clip_key_timing (double out[3]) { for (int i = 0; i < 
 static int g_staged_threads = 0;
 extern "C" void awm_debug_set_staged_threads (int n) { g_staged_threads = n < 0 ? 0 : (n > 8 ? 8 : n); }
 
-static bool
+bool
 clip_is_short (size_t n_frames)
 {
   return n_frames > 0 && n_frames < (mark_block_frame_count() + 2) * Params::frame_size;
@@ -1734,24 +1734,31 @@ static int g_group_force_fallback = 0;
 extern "C" void awm_debug_set_group_fallback (int on) { g_group_force_fallback = on; }
 
 int
-resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, const DeviceWav& in, size_t n44, DeviceWav& out)
+resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, size_t i, const DeviceWav& in, DeviceWav& out)
 {
   const int C = in.n_channels;
+  const size_t n44 = rates.n44[i];
+  const ResampleTable *table = rates.table[i];
+  if (rates.at_mark_rate (i))
+    {
+      out = in;                                      // (a clip of a call with a rate per clip that is at 44.1 kHz)
+      return 0;
+    }
   if (int rc = lane->ws_rate.reserve (std::max<size_t> (16, n44 * C * sizeof (float)))) return rc;
   out.data = lane->ws_rate.as<float>();
   out.n_frames = n44;
   out.n_channels = C;
   out.sample_rate = Params::mark_sample_rate;
-  if (!rates.table)
-    return resample_var_device (ctx, lane, in.data, in.n_frames, C, double (Params::mark_sample_rate) / rates.sample_rate, lane->ws_rate.as<float>(), n44);
+  if (!table)
+    return resample_var_device (ctx, lane, in.data, in.n_frames, C, double (Params::mark_sample_rate) / rates.sample_rate[i], lane->ws_rate.as<float>(), n44);
   awmk::ResampleArgs ra {};
   ra.in = in.data;
   ra.n_in = (long long) in.n_frames;
   ra.n_channels = C;
-  ra.ctab = rates.table->ctab.as<float>();
-  ra.hl = rates.table->hl;
-  ra.np = rates.table->np;
-  ra.step = rates.table->step;
+  ra.ctab = table->ctab.as<float>();
+  ra.hl = table->hl;
+  ra.np = table->np;
+  ra.step = table->step;
   ra.out = lane->ws_rate.as<float>();
   ra.n_out = (long long) n44;
   ProfScope ps (ctx, PROF_RESAMPLE, double (in.n_frames + n44) * C * 4.0, lane->stream);      // every input and output sample once
@@ -1760,8 +1767,10 @@ resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, con
 }
 
 /* Stage 0 of a group: the padded copies of clips[which[0 .. gn)] (reference wmget.cc:830-867, START position: data + padding cover one long
- * block) in `slices` and the non-silent range of every slice, on the lane's stream.  At 44.1 kHz a copy (launch_clip_pad); with `rates`, whose
- * table is set, the clips are resampled straight into their slices (K10c, launch_clip_resample_pad). */
+ * block) in `slices` and the non-silent range of every slice, on the lane's stream.  Three forms: at 44.1 kHz -- no `rates`, or every clip of
+ * the group at 44.1 kHz -- a copy (launch_clip_pad); a group whose clips share one other rate is resampled straight into its slices (K10c,
+ * launch_clip_resample_pad); a group whose clips do NOT share one rate goes through K10x (launch_clip_stage_mixed), every clip with the
+ * table of its own rate and the 44.1 kHz clips copied.  Every clip's rate has a table or is 44.1 kHz (ClipRates::groupable). */
 struct ClipStage0
 {
   std::vector<long long> pad_start, n_values;       // per clip, in values at 44.1 kHz
@@ -1775,7 +1784,14 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
   hipStream_t st = lane->stream;
   const int C = clips[which[0]].n_channels;
   const size_t n = slice_values / 3;
-  const size_t desc_bytes = gn * (rates ? sizeof (awmk::ClipResampleSrc) : sizeof (awmk::ClipSrc));
+  // which form: one rate for the whole group (44.1 kHz: the copy), or a rate per clip
+  bool one_rate = true;
+  if (rates)
+    for (size_t i = 1; i < gn; i++)
+      one_rate = one_rate && rates->sample_rate[which[i]] == rates->sample_rate[which[0]];
+  const bool copy = !rates || (one_rate && rates->at_mark_rate (which[0]));
+  const size_t desc_bytes = copy ? gn * sizeof (awmk::ClipSrc) : one_rate ? gn * sizeof (awmk::ClipResampleSrc)
+                                 : (gn * (sizeof (awmk::ClipMixedSrc) + sizeof (int)) + 7) / 8 * 8;      // (K10x: the descriptors, then the list)
   if (int rc = lane->pin_group.reserve (desc_bytes)) return rc;
   if (int rc = lane->ws_group.reserve (desc_bytes + gn * 2 * sizeof (long long))) return rc;
   AWM_HIP_CHECK (stream_wait (st));                                             // (the previous group's descriptors are consumed)
@@ -1789,7 +1805,7 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
   s0.d_range = reinterpret_cast<long long *> (lane->ws_group.as<char>() + desc_bytes);
   // (only CLIP_PAD_MARGIN frames of zeros on either side of a clip are written: nothing further out is read -- kernels.hh)
   s0.margin_values = (long long) std::max (g_clip_pad_margin, CLIP_PAD_MARGIN) * C;
-  if (!rates)
+  if (copy)
     {
       auto *desc = lane->pin_group.as<awmk::ClipSrc>();
       for (size_t i = 0; i < gn; i++)
@@ -1797,6 +1813,27 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
       auto *d_desc = lane->ws_group.as<awmk::ClipSrc>();
       AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
       AWM_HIP_CHECK (awmk::launch_clip_pad (st, d_desc, int (gn), slices, (long long) slice_values, s0.margin_values, s0.d_range));
+      return 0;
+    }
+  if (!one_rate)
+    {
+      auto *desc = lane->pin_group.as<awmk::ClipMixedSrc>();
+      int *list = reinterpret_cast<int *> (desc + gn);
+      double samples = 0;
+      for (size_t i = 0; i < gn; i++)
+        {
+          const DeviceWav& wav = clips[which[i]];
+          const ResampleTable *t = rates->table[which[i]];                      // (null: a clip at 44.1 kHz, copied)
+          desc[i] = { wav.data, (long long) wav.n_frames, s0.n_values[i] / C, s0.pad_start[i], t ? t->ctab.as<float>() : nullptr,
+                      t ? t->hl : 0, t ? t->np : 0, t ? t->step : 0, 0, 0, 0 };
+          samples += double (wav.n_frames) + double (desc[i].n44);
+        }
+      const awmk::ClipMixedPlan plan = awmk::clip_stage_mixed_plan (desc, int (gn), C, list);
+      auto *d_desc = lane->ws_group.as<awmk::ClipMixedSrc>();
+      AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
+      ProfScope ps (ctx, PROF_CLIP_STAGE_MIXED, samples * C * 4.0, st);         // every input and output sample of the group once
+      AWM_HIP_CHECK (awmk::launch_clip_stage_mixed (st, plan, d_desc, reinterpret_cast<const int *> (d_desc + gn), slices, (long long) slice_values,
+                                                    s0.margin_values, s0.d_range));
       return 0;
     }
   auto *desc = lane->pin_group.as<awmk::ClipResampleSrc>();
@@ -1813,12 +1850,13 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
     }
   auto *d_desc = lane->ws_group.as<awmk::ClipResampleSrc>();
   AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
+  const ResampleTable *table = rates->table[which[0]];
   awmk::ResampleArgs ra {};
   ra.n_channels = C;
-  ra.ctab = rates->table->ctab.as<float>();
-  ra.hl = rates->table->hl;
-  ra.np = rates->table->np;
-  ra.step = rates->table->step;
+  ra.ctab = table->ctab.as<float>();
+  ra.hl = table->hl;
+  ra.np = table->np;
+  ra.step = table->step;
   ProfScope ps (ctx, PROF_CLIP_RESAMPLE, samples * C * 4.0, st);               // every input and output sample of the group once
   AWM_HIP_CHECK (awmk::launch_clip_resample_pad (st, ra, d_desc, int (gn), max_n44, (bits & 7) == 0, slices, (long long) slice_values,
                                                  s0.margin_values, s0.d_range));
@@ -2065,7 +2103,7 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
     if (!rates->n44[i])
       return 0;                                      // an empty clip: no patterns
     DeviceWav wav44;
-    if (int rc = resample_to_mark_rate (ctx, lane, *rates, clips[i], rates->n44[i], wav44))
+    if (int rc = resample_to_mark_rate (ctx, lane, *rates, i, clips[i], wav44))
       return rc;
     return get_watermark_on (ctx, lane, spread, keys_of (i), wav44, result_sets[i]);
   };
@@ -2083,9 +2121,10 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
           return rc;
       return 0;
     }
-  // (at another rate a clip is short by its 44.1 kHz length, and the groups take only what K10c resamples: the fixed-ratio rates)
+  // (at another rate a clip is short by its 44.1 kHz length, and the groups take only what stage 0 resamples or copies: the fixed-ratio
+  // rates and 44.1 kHz.  The groups fill in call order whatever the rates of their clips)
   for (size_t i = 0; i < clips.size(); i++)
-    ((rates ? rates->table && clip_is_short (rates->n44[i]) : clip_is_short (clips[i])) ? staged : threaded).push_back (i);
+    ((rates ? rates->groupable (i) && clip_is_short (rates->n44[i]) : clip_is_short (clips[i])) ? staged : threaded).push_back (i);
   if (!staged.empty())
     {
       if (!ctx->ev_sync)
@@ -2190,7 +2229,7 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
   AWM_HIP_CHECK (hipEventRecord (ctx->ev_sync, ctx->stream));
   for (size_t i = 1; i < lanes.size(); i++)
     AWM_HIP_CHECK (hipStreamWaitEvent (lanes[i]->stream, ctx->ev_sync, 0));
-  std::atomic<size_t> next { 0 };
+  std::atomic<size_t> next { lanes.size() };
   std::vector<int> rc (lanes.size(), 0);
   std::vector<std::string> err (lanes.size());
   ParamValues *const pv = &params();
@@ -2205,11 +2244,10 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
         err[li] = "hipSetDevice failed in a batch worker";
         return;
       }
-    for (;;)
+    // the first clip of every lane is dealt (clip li to lane li), the rest is pulled: a call of no more clips than lanes -- the few long
+    // clips or VResampler rates of a batch of short clips -- grows the same lanes' workspaces every time it is repeated
+    for (size_t t = li; t < threaded.size(); t = next.fetch_add (1))
       {
-        const size_t t = next.fetch_add (1);
-        if (t >= threaded.size())
-          break;
         const size_t i = threaded[t];
         if (int r = get_one (lanes[li], false, i))
           {
@@ -2239,8 +2277,7 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
 int
 clip_stage_device (awm_ctx *ctx, const std::vector<DeviceWav>& clips, const ClipRates *rates, float *slices, long long *range_out)
 {
-  if (clips.empty() || clips.size() > size_t (CLIP_GROUP) || !slices || !range_out || (reinterpret_cast<uintptr_t> (slices) & 15)
-      || (rates && !rates->table))
+  if (clips.empty() || clips.size() > size_t (CLIP_GROUP) || !slices || !range_out || (reinterpret_cast<uintptr_t> (slices) & 15))
     {
       set_error ("awm_debug_clip_stage_d: bad argument");
       return AWM_ERR_ARG;
@@ -2248,6 +2285,11 @@ clip_stage_device (awm_ctx *ctx, const std::vector<DeviceWav>& clips, const Clip
   std::vector<size_t> which;
   for (size_t i = 0; i < clips.size(); i++)
     {
+      if (rates && !rates->groupable (i))
+        {
+          set_error ("awm_debug_clip_stage_d: a rate that the fixed-ratio resampler does not take");
+          return AWM_ERR_ARG;
+        }
       if (!clips[i].data || clips[i].n_channels != clips[0].n_channels || !clip_is_short (rates ? rates->n44[i] : clips[i].n_frames))
         {
           set_error ("awm_debug_clip_stage_d: not a short clip");

@@ -57,19 +57,26 @@ int get_watermark_device (awm_ctx *ctx, const std::vector<Key>& key_list, const 
 // clip_keys: one key per clip instead of the key list for all
 // rates (may be null): the clips are at another sample rate -- clips[i] is the clip as the caller holds it, its result that of the clip
 // resampled to 44.1 kHz (WavChunkLoader, reference wavchunkloader.cc:70-71, 200-216)
+// (a rate per clip: awm_get_watermark_batch_rates_d; the one-rate calls fill in the same rate and table for every clip)
 struct ClipRates
 {
-  int                  sample_rate = 0;
-  const ResampleTable *table = nullptr;    // the fixed-ratio resampler's table, or null: the VResampler with ratio 44100 / sample_rate
-  std::vector<size_t>  n44;                // frames of clip i at 44.1 kHz
+  std::vector<int>                   sample_rate;   // of clip i
+  std::vector<const ResampleTable *> table;         // the fixed-ratio resampler's table for clip i's rate, or null: the VResampler with ratio
+                                                    // 44100 / sample_rate -- or a clip at 44.1 kHz, which is not resampled
+  std::vector<size_t>                n44;           // frames of clip i at 44.1 kHz
+  bool at_mark_rate (size_t i) const { return sample_rate[i] == Params::mark_sample_rate; }
+  bool groupable (size_t i) const { return table[i] || at_mark_rate (i); }       // stage 0 of the groups takes it (K10c / K10x / the copy)
 };
+// a clip of this many frames at 44.1 kHz runs in the groups (below one block + 2 frames), not on a lane of its own
+bool clip_is_short (size_t n_frames);
 int get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, const std::vector<DeviceWav>& clips,
                                 std::vector<ResultSet>& result_sets, int n_threads, const std::vector<Key> *clip_keys = nullptr,
                                 const ClipRates *rates = nullptr);
 // stage 0 of one group of 1 .. 64 short clips alone (awm_debug_clip_stage_d): slices and host ranges [n][2], synchronised
 int clip_stage_device (awm_ctx *ctx, const std::vector<DeviceWav>& clips, const ClipRates *rates, float *slices, long long *range_out);
-// the 44.1 kHz copy of one clip (n44 frames) in the lane's own grow-only workspace, on the lane's stream: what the decoders are given
-int resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, const DeviceWav& in, size_t n44, DeviceWav& out);
+// the 44.1 kHz copy of clip i of `rates` (n44[i] frames) in the lane's own grow-only workspace, on the lane's stream: what the decoders are
+// given.  A clip at 44.1 kHz is handed on as it is
+int resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, size_t i, const DeviceWav& in, DeviceWav& out);
 
 // soft bits of whole blocks (fft_range + mix_decode), raw mix order
 int block_soft_bits (awm_ctx *ctx, KeyTables *kt, const DeviceWav& wav, const std::vector<size_t>& index,

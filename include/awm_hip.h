@@ -463,7 +463,7 @@ int awm_get_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], size_t n_cli
  * no second read); long clips, VResampler rates and calls with a speed parameter set resample each clip into a grow-only workspace of its
  * lane first (awm_ctx_trim gives these back).  sample_rate == 44100 is the existing function.  AWM_ERR_ARG with nothing enqueued and n_out
  * untouched: sample_rate <= 0, or a ratio that neither zita class takes (awm_resample_frames gives 0).  Empty clips: n_out[i] = 0.
- * Not offered in this form: a rate per clip, the sharded / multi-context batches. */
+ * Not offered in this form: the sharded / multi-context batches.  A rate per clip: awm_get_watermark_batch_rates_d below. */
 int awm_get_watermark_rate_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels,
                               int sample_rate, size_t max_out, awm_pattern *out);
 int awm_get_watermark_batch_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const float *const *pcm_d,
@@ -472,6 +472,32 @@ int awm_get_watermark_batch_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t 
 int awm_get_watermark_batch_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const float *const *pcm_d,
                                          const size_t *n_frames, int n_channels, int sample_rate, int n_threads,
                                          size_t max_out_per_clip, awm_pattern *out, int *n_out);
+/* The batches with a SAMPLE RATE PER CLIP: a detection queue is not sorted by rate (uploads and monitored programmes at 44.1, 48, 32, 22.05,
+ * 88.2 and 96 kHz side by side), and one call per rate leaves every rate's last group of 64 underfilled.  Clip i is at sample_rates[i].
+ * Definition: the result for clip i is field for field what awm_get_watermark_rate_d (ctx, key_i, pcm_d[i], n_frames[i], n_channels,
+ * sample_rates[i], ...) returns -- awm_get_watermark_d on awm_resample_d (clip i, sample_rates[i] -> 44100), and on the clip itself where its
+ * rate is 44100; key_i = key, or keys + 16 i in the keys form; sync_index counts 44.1 kHz samples.
+ * Paths: a clip is short by its 44.1 kHz length.  Short clips at 44100 or at a rate of the fixed-ratio Resampler fill the groups of 64 in
+ * call order WHATEVER THEIR RATES; stage 0 of a group whose clips do not share one rate is K10x (every clip resampled with its own rate's
+ * table, or copied, straight into its padded slice: one launch per form present in the group, not per clip or rate), a group that happens
+ * to share one rate runs as in the one-rate call.  Long clips, VResampler rates and 44.1 kHz long clips go over the work lanes, each
+ * resampled with its own rate into its lane's grow-only workspace first; so does every clip while a speed parameter is set.  A call
+ * whose rates are all equal IS the one-rate function above (44100: the 44.1 kHz function).
+ * Refusals, AWM_ERR_ARG with nothing enqueued and n_out / out untouched, awm_last_error names the index of the first offending clip:
+ * sample_rates NULL with n_clips > 0, a sample_rates[i] <= 0, a ratio that neither zita class takes (awm_resample_frames gives 0 for a
+ * non-empty clip).  n_clips == 0 returns 0; an empty clip gives n_out[i] = 0.
+ * Not offered in this form: the command line, the file level, the awm_multi_* / sharded batches. */
+int awm_get_watermark_batch_rates_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const float *const *pcm_d,
+                                     const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads,
+                                     size_t max_out_per_clip, awm_pattern *out, int *n_out);
+int awm_get_watermark_batch_keys_rates_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const float *const *pcm_d,
+                                          const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads,
+                                          size_t max_out_per_clip, awm_pattern *out, int *n_out);
+/* Pure host, no context, no device: which way clip i of such a call goes -- path_out[i] = 0 a group | 1 a lane, fixed-ratio resampler (or
+ * a long clip at 44100, which is not resampled) | 2 a lane, VResampler | 3 empty, nothing to do -- and its length at 44.1 kHz, with the
+ * parameters in force (the short / long border is block frames + 2).  Either output may be NULL.  AWM_ERR_ARG for the rates that the calls
+ * above refuse, with -1 in that clip's path_out (the other clips are still filled in). */
+int awm_get_batch_rates_plan (size_t n_clips, const size_t *n_frames, const int *sample_rates, int *path_out, size_t *n44_out);
 /* decode() of one chunk only (wmget.cc:886-939) -- the unit `get` is sharded by */
 int awm_decode_chunk_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames,
                         int n_channels, int first_chunk, size_t max_out, awm_pattern *out);
@@ -755,6 +781,10 @@ int  awm_debug_clip_stage_d (awm_ctx *ctx, size_t n_clips, const float *const *p
                                             * context's stream, their non-silent ranges to range_out (host, [n_clips][2]), synchronised.  44100: the padded copy; a rate of the
                                             * fixed-ratio Resampler: K10c.  AWM_ERR_ARG: a VResampler rate, a clip that is not short, more than 64 clips.  Honours
                                             * awm_debug_set_clip_poison */
+int  awm_debug_clip_stage_rates_d (awm_ctx *ctx, size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels,
+                                   const int *sample_rates, float *slices_d, long long *range_out);
+                                           /* its twin with a rate per clip: a group whose clips do not share one rate goes through K10x, one that does as above.
+                                            * The same refusals, and those of awm_get_watermark_batch_rates_d */
 void awm_debug_set_clip_pad_margin (int frames); /* clip batches: frames of zeros written on either side of a clip (default and minimum 2048; one slice = 6693 frames
                                             * or more: whole slices, the A side of the measurement in tools/gpu_clip_margin_ab.py) */
 void awm_debug_set_staged_threads (int n);  /* clip batches: host threads (= lanes) working on groups of clips; 0 = default (4; 2 with a key per clip only where the
