@@ -181,6 +181,13 @@ lib.awm_get_watermark_batch_rates_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, 
 lib.awm_get_watermark_batch_keys_rates_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, _vp, C.c_int, C.c_size_t, _vp, _vp]
 lib.awm_debug_clip_stage_rates_d.argtypes = [_vp, C.c_size_t, _vp, _vp, C.c_int, _vp, _vp, _vp]
 lib.awm_get_batch_rates_plan.argtypes = [C.c_size_t, _vp, _vp, _vp, _vp]
+lib.awm_get_watermark_batch_rates_s16_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, _vp, C.c_int, C.c_size_t, _vp, _vp]
+lib.awm_get_watermark_batch_keys_rates_s16_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, _vp, C.c_int, C.c_size_t, _vp, _vp]
+lib.awm_debug_clip_stage_rates_s16_d.argtypes = [_vp, C.c_size_t, _vp, _vp, C.c_int, _vp, _vp, _vp]
+lib.awm_debug_clip_form_launches.argtypes = [_vp]
+lib.awm_debug_clip_form_launches.restype = None
+lib.awm_debug_lane_pcm_bytes.argtypes = [_vp]
+lib.awm_debug_lane_pcm_bytes.restype = C.c_size_t
 lib.awm_decode_chunk_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, _vp]
 lib.awm_tab_up_down.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp]
 lib.awm_tab_bit_pos.argtypes = [_vp, _vp]
@@ -1363,6 +1370,63 @@ class Context:
             if most <= max_out_per_clip:
                 return [patterns_to_dicts(buf, n_out[i], i * max_out_per_clip) for i in range(len(clips))]
             max_out_per_clip = most           # a clip found more patterns than a slot holds: repeat with slots that fit
+
+    # ---- the batches on clips that are resident as signed 16-bit PCM ----
+    @staticmethod
+    def _s16_clips(clips, sample_rate):
+        """(pointers, frames, channels, rates or None) of torch.int16 clips shaped [frames, channels] or [frames]; a scalar rate becomes a rate
+        per clip, 44100 the NULL that means "all at 44.1 kHz" """
+        import torch
+        for c in clips:
+            assert c.dtype == torch.int16 and c.is_cuda and c.is_contiguous()
+        ch = 1 if clips[0].dim() == 1 else clips[0].shape[1]
+        assert all((1 if c.dim() == 1 else c.shape[1]) == ch for c in clips)
+        rates = _rates_array(sample_rate, len(clips))
+        if rates is None and sample_rate != 44100:
+            rates = (C.c_int * len(clips))(*[int(sample_rate)] * len(clips))
+        ptrs = (C.c_void_p * len(clips))(*[C.c_void_p(c.data_ptr()) for c in clips])
+        frames = (C.c_size_t * len(clips))(*[c.shape[0] for c in clips])
+        return ptrs, frames, ch, rates
+
+    def _batch_s16(self, fn, what, key_arg, clips, n_threads, max_out_per_clip, sample_rate):
+        if not clips:
+            return []
+        ptrs, frames, ch, rates = self._s16_clips(clips, sample_rate)
+        n_out = (C.c_int * len(clips))()
+        while True:
+            buf = self._pattern_buffer(len(clips) * max_out_per_clip)
+            _check(fn(self._h, key_arg, len(clips), ptrs, frames, ch, rates, n_threads, max_out_per_clip, C.cast(buf, C.c_void_p), n_out), what)
+            most = max(n_out)
+            if most <= max_out_per_clip:
+                return [patterns_to_dicts(buf, n_out[i], i * max_out_per_clip) for i in range(len(clips))]
+            max_out_per_clip = most
+
+    def get_watermark_batch_s16(self, key, clips, n_threads=0, max_out_per_clip=64, sample_rate=44100):
+        """awm_get_watermark_batch_rates_s16_d: get_watermark_batch on torch.int16 clips (signed 16-bit PCM, interleaved) as they are -- the
+        result is that of the float call on pcm_decode of every clip, and a short clip is never copied to float.  sample_rate: one rate
+        or a sequence, one rate per clip."""
+        return self._batch_s16(lib.awm_get_watermark_batch_rates_s16_d, "awm_get_watermark_batch_rates_s16_d", key_bytes(key), clips, n_threads,
+                               max_out_per_clip, sample_rate)
+
+    def get_watermark_batch_keys_s16(self, keys, clips, n_threads=0, max_out_per_clip=64, sample_rate=44100):
+        """awm_get_watermark_batch_keys_rates_s16_d: the same with keys[i] for clip i alone"""
+        assert len(keys) == len(clips)
+        return self._batch_s16(lib.awm_get_watermark_batch_keys_rates_s16_d, "awm_get_watermark_batch_keys_rates_s16_d",
+                               b"".join(key_bytes(k) for k in keys), clips, n_threads, max_out_per_clip, sample_rate)
+
+    def clip_stage_s16(self, clips, sample_rate=44100, out=None):
+        """awm_debug_clip_stage_rates_s16_d: clip_stage on torch.int16 clips -> (slices, ranges), bit for bit those of clip_stage on the
+        decoded clips"""
+        import torch
+        ptrs, frames, ch, rates = self._s16_clips(clips, sample_rate)
+        values = lib.awm_debug_clip_slice_values(ch)
+        if out is None:
+            out = torch.zeros((len(clips), values), dtype=torch.float32, device=clips[0].device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == len(clips) * values
+        ranges = np.zeros((len(clips), 2), np.int64)
+        _check(lib.awm_debug_clip_stage_rates_s16_d(self._h, len(clips), ptrs, frames, ch, rates, _dev_ptr(out), _np(ranges)),
+               "awm_debug_clip_stage_rates_s16_d")
+        return out, ranges
 
     def decode_chunks(self, key, pcm, chunks, first_is_stream_start, max_out=8192):
         """decode() of several chunks [(first_frame, n_frames), ...] of one resident buffer; returns one pattern list per

@@ -575,12 +575,29 @@ struct ClipMixedPlan
   int       n_form[3] = { 0, 0, 0 };
   long long max_n44 = 0;             // the group's longest clip: tiles per workgroup
   long long max_n44_form[3] = { 0, 0, 0 };
-  bool      stereo_aligned = false;  // stereo and every resampled input 8-byte aligned
+  bool      stereo_aligned = false;  // stereo and every resampled input 8-byte aligned (s16: 4-byte aligned)
   size_t    lds_bytes = 0;           // CLIP_FORM_GENERIC: the largest table + window of the group
+  bool      s16 = false;             // the plan of launch_clip_stage_mixed_s16
 };
-ClipMixedPlan clip_stage_mixed_plan (ClipMixedSrc *src /* host */, int n_clips, int n_channels, int *list /* host */);
+ClipMixedPlan clip_stage_mixed_plan (ClipMixedSrc *src /* host */, int n_clips, int n_channels, int *list /* host */, bool s16 = false);
 hipError_t launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& plan, const ClipMixedSrc *src /* device */, const int *list /* device */,
                                     float *dst, long long slice_values, long long margin_values, long long *range);
+/* Stage 0 straight from SIGNED 16-BIT PCM (little-endian, interleaved: the reference's native format, rawconverter.cc): the three launchers
+ * above for clips whose values are int16.  The descriptors are the same structs -- their `data` / `in` fields hold the ADDRESS of the
+ * clip's int16 values, n_values / n_in count values / frames as before -- and slices and ranges are bit for bit what the float launcher
+ * writes for the decoded clips, float (v) * (1 / 32768) (launch_pcm_decode): the same kernels instantiated for the other input type, whose
+ * loads convert and whose taps, sums, sinks, zeros and ranges are the same code.  A value is converted once: on its way into the LDS
+ * window of the staged forms (the window stays float2, so the taps' LDS reads are what they were), or as the unstaged taps and the copy read
+ * it.  Same forms, same plan rule (clip_stage_mixed_plan with s16 = true), same tiles per workgroup, same number of launches.
+ * Alignment: a clip may begin at any EVEN address.  A 16-bit stereo frame is 4 bytes, so stereo_aligned here means that every resampled
+ * input of the group is 4-byte aligned (one 4-byte load per frame); a group with an input that is not, or with another channel count,
+ * takes the generic taps with 2-byte loads.  Nothing outside a clip's values is read. */
+hipError_t launch_clip_pad_s16 (hipStream_t st, const ClipSrc *src /* device */, int n_clips, float *dst, long long slice_values, long long margin_values,
+                                long long *range);
+hipError_t launch_clip_resample_pad_s16 (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src /* device */, int n_clips, long long max_n44,
+                                         bool stereo_aligned, float *dst, long long slice_values, long long margin_values, long long *range);
+hipError_t launch_clip_stage_mixed_s16 (hipStream_t st, const ClipMixedPlan& plan, const ClipMixedSrc *src /* device */, const int *list /* device */,
+                                        float *dst, long long slice_values, long long margin_values, long long *range);
 }
 
 namespace awmk {

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <type_traits>
+#include <atomic>
 
 namespace awmk {
 
@@ -1323,6 +1324,26 @@ struct ResampleStore
   __device__ __forceinline__ void put2 (long long k, float2 v) { reinterpret_cast<float2 *> (out)[k] = v; }
 };
 
+/* What the taps READ (stage 0 of the clip groups straight from 16-bit PCM, kernels.hh launch_clip_pad_s16): the type of a value and of
+ * a stereo frame in global memory, and the conversion to the float the taps work on.  PcmF32, the default of every template below: the
+ * values as they are.  PcmS16: signed 16 bit, the exact decode of pcm_decode_s16le_kernel, float (v) * (1 / 32768) with one rounded
+ * product; a stereo frame is one 4-byte load.  A value is converted once, where it leaves global memory -- on its way into the LDS
+ * window (which stays float2) or, in the unstaged taps and the copy, as it is read -- and nothing behind the load differs. */
+struct PcmF32
+{
+  typedef float  value;
+  typedef float2 frame2;
+  static __device__ __forceinline__ float  conv (float v) { return v; }
+  static __device__ __forceinline__ float2 conv2 (float2 v) { return v; }
+};
+struct PcmS16
+{
+  typedef short  value;
+  typedef short2 frame2;
+  static __device__ __forceinline__ float  conv (short v) { return __fmul_rn (float (v), 1.0f / 32768.0f); }
+  static __device__ __forceinline__ float2 conv2 (short2 v) { return make_float2 (conv (v.x), conv (v.y)); }
+};
+
 /* stereo, input window of the tile staged in LDS (zero extended): s_in[0] is input frame first0; same products and sums as below */
 template<class Sink> __device__ __forceinline__ void
 resample_output_staged (const ResampleArgs& a, const float *tab, int stride, long long m, const float2 *s_in, unsigned int t_rel, Sink& sink)
@@ -1348,7 +1369,7 @@ resample_output_staged (const ResampleArgs& a, const float *tab, int stride, lon
 
 // one output frame m; tab: coefficient rows with `stride` floats each (LDS or global).  K10w: a.in[0] is input frame in0 of the stream
 // (a.n_in frames from there, zeros everywhere else) and the result goes to frame k of the sink
-template<int CT, class Sink> __device__ __forceinline__ void
+template<int CT, class In = PcmF32, class Sink> __device__ __forceinline__ void
 resample_output (const ResampleArgs& a, const float *tab, int stride, long long m, long long in0, long long k, Sink& sink)
 {
   const int C = CT ? CT : a.n_channels, hl = a.hl;
@@ -1360,15 +1381,15 @@ resample_output (const ResampleArgs& a, const float *tab, int stride, long long 
   const long long first = b - (hl - 1) - in0;                 // input frame of P[b], from a.in[0]
   if (CT == 2)
     {
-      const float2 *in2 = reinterpret_cast<const float2 *> (a.in);
+      const typename In::frame2 *in2 = reinterpret_cast<const typename In::frame2 *> (a.in);
       float s0 = 1e-20f, s1 = 1e-20f;
       if (__all (first >= 0 && first + 2 * hl <= a.n_in))      // the whole wave is away from the ends: no bounds checks
         {
-          const float2 *p1 = in2 + first, *p2 = in2 + first + 2 * hl - 1;
+          const typename In::frame2 *p1 = in2 + first, *p2 = in2 + first + 2 * hl - 1;
 #pragma unroll 4
           for (int i = 0; i < hl; i++)
             {
-              const float2 x1 = p1[i], x2 = p2[-i];
+              const float2 x1 = In::conv2 (p1[i]), x2 = In::conv2 (p2[-i]);
               s0 = __fadd_rn (s0, __fadd_rn (__fmul_rn (x1.x, c1[i]), __fmul_rn (x2.x, c2[i])));
               s1 = __fadd_rn (s1, __fadd_rn (__fmul_rn (x1.y, c1[i]), __fmul_rn (x2.y, c2[i])));
             }
@@ -1377,31 +1398,32 @@ resample_output (const ResampleArgs& a, const float *tab, int stride, long long 
         for (int i = 0; i < hl; i++)
           {
             const long long j1 = first + i, j2 = first + 2 * hl - 1 - i;
-            const float2 x1 = (j1 >= 0 && j1 < a.n_in) ? in2[j1] : make_float2 (0.f, 0.f);
-            const float2 x2 = (j2 >= 0 && j2 < a.n_in) ? in2[j2] : make_float2 (0.f, 0.f);
+            const float2 x1 = (j1 >= 0 && j1 < a.n_in) ? In::conv2 (in2[j1]) : make_float2 (0.f, 0.f);
+            const float2 x2 = (j2 >= 0 && j2 < a.n_in) ? In::conv2 (in2[j2]) : make_float2 (0.f, 0.f);
             s0 = __fadd_rn (s0, __fadd_rn (__fmul_rn (x1.x, c1[i]), __fmul_rn (x2.x, c2[i])));
             s1 = __fadd_rn (s1, __fadd_rn (__fmul_rn (x1.y, c1[i]), __fmul_rn (x2.y, c2[i])));
           }
       sink.put2 (k, make_float2 (__fsub_rn (s0, 1e-20f), __fsub_rn (s1, 1e-20f)));
       return;
     }
+  const typename In::value *in1 = reinterpret_cast<const typename In::value *> (a.in);
   for (int c = 0; c < C; c++)
     {
       float sum = 1e-20f;
       for (int i = 0; i < hl; i++)
         {
           const long long j1 = first + i, j2 = first + 2 * hl - 1 - i;
-          const float x1 = (j1 >= 0 && j1 < a.n_in) ? a.in[j1 * C + c] : 0.f;
-          const float x2 = (j2 >= 0 && j2 < a.n_in) ? a.in[j2 * C + c] : 0.f;
+          const float x1 = (j1 >= 0 && j1 < a.n_in) ? In::conv (in1[j1 * C + c]) : 0.f;
+          const float x2 = (j2 >= 0 && j2 < a.n_in) ? In::conv (in1[j2 * C + c]) : 0.f;
           sum = __fadd_rn (sum, __fadd_rn (__fmul_rn (x1, c1[i]), __fmul_rn (x2, c2[i])));
         }
       sink.put (k * C + c, __fsub_rn (sum, 1e-20f));
     }
 }
-template<int CT, class Sink> __device__ __forceinline__ void
+template<int CT, class In = PcmF32, class Sink> __device__ __forceinline__ void
 resample_output (const ResampleArgs& a, const float *tab, int stride, long long m, Sink& sink)
 {
-  resample_output<CT> (a, tab, stride, m, 0, m, sink);
+  resample_output<CT, In> (a, tab, stride, m, 0, m, sink);
 }
 
 /* Neighbouring outputs use different phases, i.e. different coefficient rows: read from global memory every load
@@ -1487,7 +1509,7 @@ resample_kernel (ResampleArgs a, int lds_floats, int in_span, int tiles_per_wg)
  * group0 NP + k is local output k, which is what the sink is given -- with `in` holding the stream's frames in0 .. in0 + n_in - 1 and
  * zeros everywhere else.  A tile's window then starts group0 STEP frames later (64 bits) and is fetched from in[j - in0]; the slots, the
  * coefficients and everything behind the staging of s_in are untouched, and with SPAN false both values are constants that fold away. */
-template<int NP, int STEP, int HL, int R, int J, bool SPAN = false, class Sink> __device__ __forceinline__ void
+template<int NP, int STEP, int HL, int R, int J, bool SPAN = false, class In = PcmF32, class Sink> __device__ __forceinline__ void
 resample_phase_body (const float *ctab, const float *in, long long n_in, long long n_out, int tiles_per_wg, Sink& sink, long long group0 = 0,
                      long long in0 = 0)
 {
@@ -1509,7 +1531,7 @@ resample_phase_body (const float *ctab, const float *in, long long n_in, long lo
       c1[i] = ctab[ph * HL + i];
       c2[i] = ctab[(NP - ph) * HL + i];
     }
-  const float2 *in2 = reinterpret_cast<const float2 *> (in);
+  const typename In::frame2 *in2 = reinterpret_cast<const typename In::frame2 *> (in);
   for (int t = 0; t < tiles_per_wg; t++)
     {
       const long long tile = (long long) blockIdx.x * tiles_per_wg + t;
@@ -1522,7 +1544,7 @@ resample_phase_body (const float *ctab, const float *in, long long n_in, long lo
       for (int i = tid; i < IN_SPAN; i += WG)
         {
           const long long j = first0 + i;
-          s_in[i] = (j >= 0 && j < n_in) ? in2[j] : make_float2 (0.f, 0.f);
+          s_in[i] = (j >= 0 && j < n_in) ? In::conv2 (in2[j]) : make_float2 (0.f, 0.f);
         }
       __syncthreads();
       if (active)
@@ -1758,7 +1780,7 @@ launch_resample_mix_multi (hipStream_t st, const ResampleMixArgs& a)
  * keeps it for `tiles_per_wg` consecutive tiles of RS_TILE outputs of its slice (staging the table costs as much as the taps of one tile);
  * window start and phase come from each tile's first GLOBAL output index, the staged window is filled from the slice's resident input
  * and zeros.  The taps are resample_output_staged / resample_output themselves. */
-template<int CT, class Sink> __device__ __forceinline__ void
+template<int CT, class In = PcmF32, class Sink> __device__ __forceinline__ void
 resample_slice_body (const ResampleArgs& a0, const ResampleSlice& s, int lds_floats, int in_span, int tiles_per_wg, Sink& sink)
 {
   extern __shared__ float s_tab[];
@@ -1793,11 +1815,11 @@ resample_slice_body (const ResampleArgs& a0, const ResampleSlice& s, int lds_flo
           if (t)
             __syncthreads();                                                   // the previous tile's windows have been read
           const long long first0 = b0 - (a.hl - 1) - s.in0;                    // s_in[0], counted from s.in[0]
-          const float2 *in2 = reinterpret_cast<const float2 *> (s.in);
+          const typename In::frame2 *in2 = reinterpret_cast<const typename In::frame2 *> (s.in);
           for (int i = threadIdx.x; i < in_span; i += 256)
             {
               const long long j = first0 + i;
-              s_in[i] = (j >= 0 && j < s.n_in) ? in2[j] : make_float2 (0.f, 0.f);
+              s_in[i] = (j >= 0 && j < s.n_in) ? In::conv2 (in2[j]) : make_float2 (0.f, 0.f);
             }
         }
       if (in_lds && (staged || t == 0))
@@ -1810,9 +1832,9 @@ resample_slice_body (const ResampleArgs& a0, const ResampleSlice& s, int lds_flo
           if (staged)
             resample_output_staged (a, s_tab, stride, k, s_in, r0 + (unsigned int) (q * 256 + threadIdx.x) * (unsigned int) a.step, sink);
           else if (in_lds)
-            resample_output<CT> (a, s_tab, stride, s.out0 + k, s.in0, k, sink);
+            resample_output<CT, In> (a, s_tab, stride, s.out0 + k, s.in0, k, sink);
           else
-            resample_output<CT> (a, a.ctab, a.hl, s.out0 + k, s.in0, k, sink);
+            resample_output<CT, In> (a, a.ctab, a.hl, s.out0 + k, s.in0, k, sink);
         }
     }
 }
@@ -4146,12 +4168,14 @@ struct ClipPadListed
   }
 };
 
-/* kernels.hh launch_clip_pad: grid (parts, clips); slice_values % 4 == 0, 16-byte stores */
-template<class From> __global__ void __launch_bounds__ (256)
+/* kernels.hh launch_clip_pad: grid (parts, clips); slice_values % 4 == 0, 16-byte stores.  In: what the clip's values are (PcmS16: scalar
+ * 2-byte loads, any even address) */
+template<class From, class In = PcmF32> __global__ void __launch_bounds__ (256)
 clip_pad_kernel (From from, float *dst, long long slice_values, long long margin_values, unsigned long long *range)
 {
   unsigned int slice;
   const ClipSrc c = from.clip (slice);
+  const typename In::value *data = reinterpret_cast<const typename In::value *> (c.data);
   float4 *out = reinterpret_cast<float4 *> (dst + (long long) slice * slice_values);
   const long long slice0 = (long long) slice * slice_values;
   const long long stride = (long long) gridDim.x * blockDim.x;
@@ -4170,7 +4194,7 @@ clip_pad_kernel (From from, float *dst, long long slice_values, long long margin
 #pragma unroll
           for (int j = 0; j < 4; j++)
             if (k + j >= 0 && k + j < c.n_values)
-              v[j] = c.data[k + j];
+              v[j] = In::conv (data[k + j]);
 #pragma unroll
           for (int j = 0; j < 4; j++)
             if (v[j] != 0.f)
@@ -4201,8 +4225,19 @@ clip_range_init_kernel (unsigned long long *range, int n_clips)
 int g_clip_poison = 0;
 extern "C" void awm_debug_set_clip_poison (int on) { g_clip_poison = on; }
 
-hipError_t
-launch_clip_pad (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, long long slice_values, long long margin_values, long long *range)
+/* (test probe) kernels of stage 0 launched so far by this process, by form (CLIP_FORM_*): the profiling scopes count a group's stage as
+ * one whatever its forms, and which form an alignment leads to is part of the contract */
+static std::atomic<long> g_clip_form_launches[3];
+extern "C" void
+awm_debug_clip_form_launches (long out[3])
+{
+  for (int f = 0; f < 3; f++)
+    out[f] = g_clip_form_launches[f].load();
+}
+
+/* the launchers of stage 0, one copy for both input types: the float entry points instantiate what they always did */
+template<class In> static hipError_t
+launch_clip_pad_in (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, long long slice_values, long long margin_values, long long *range)
 {
   if (n_clips <= 0 || slice_values <= 0)
     return hipSuccess;
@@ -4213,9 +4248,20 @@ launch_clip_pad (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, lo
       return e;
   auto *r = reinterpret_cast<unsigned long long *> (range);
   hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
-  hipLaunchKernelGGL (clip_pad_kernel<ClipPadEvery>, dim3 (128, unsigned (n_clips)), dim3 (256), 0, st, ClipPadEvery { src }, dst, slice_values,
+  g_clip_form_launches[CLIP_FORM_COPY]++;
+  hipLaunchKernelGGL ((clip_pad_kernel<ClipPadEvery, In>), dim3 (128, unsigned (n_clips)), dim3 (256), 0, st, ClipPadEvery { src }, dst, slice_values,
                       margin_values, r);
   return hipGetLastError();
+}
+hipError_t
+launch_clip_pad (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, long long slice_values, long long margin_values, long long *range)
+{
+  return launch_clip_pad_in<PcmF32> (st, src, n_clips, dst, slice_values, margin_values, range);
+}
+hipError_t
+launch_clip_pad_s16 (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, long long slice_values, long long margin_values, long long *range)
+{
+  return launch_clip_pad_in<PcmS16> (st, src, n_clips, dst, slice_values, margin_values, range);
 }
 
 /* K10c (kernels.hh launch_clip_resample_pad): K10 into the padded slices.  The sink of the taps: output frame m of the clip goes to
@@ -4262,7 +4308,7 @@ clip_window_zeros (float *slice, long long pad_start, long long n_values, long l
 
 /* the generic form: resample_slice_body (table and, for stereo with 8-byte aligned inputs, the tile's window in LDS) on the clip as a
  * stream of its own; grid (workgroups of the longest clip, clips) */
-template<int CT> __global__ void __launch_bounds__ (256)
+template<int CT, class In = PcmF32> __global__ void __launch_bounds__ (256)
 clip_resample_pad_kernel (ResampleArgs a, const ClipResampleSrc *src, float *dst, long long slice_values, long long margin_values,
                           unsigned long long *range, int lds_floats, int in_span, int tiles_per_wg)
 {
@@ -4271,12 +4317,12 @@ clip_resample_pad_kernel (ResampleArgs a, const ClipResampleSrc *src, float *dst
   ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
   clip_window_zeros (dst + slice0, c.pad_start, c.n44 * a.n_channels, slice_values, margin_values);
   const ResampleSlice s { c.in, c.n_in, 0, 0, c.n44, nullptr };
-  resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg, sink);
+  resample_slice_body<CT, In> (a, s, lds_floats, in_span, tiles_per_wg, sink);
   clip_range_commit<4> (sink.first, sink.last, range + 2 * blockIdx.y);
 }
 
 /* the phase-per-thread form (resample_phase_body): a clip starts at output 0, so its tiles start on multiples of np */
-template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
+template<int NP, int STEP, int HL, int R, int J, class In = PcmF32> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
 clip_resample_pad_phase_kernel (const float *ctab, const ClipResampleSrc *src, float *dst, long long slice_values, long long margin_values,
                                 unsigned long long *range, int tiles_per_wg)
 {
@@ -4285,13 +4331,13 @@ clip_resample_pad_phase_kernel (const float *ctab, const ClipResampleSrc *src, f
   ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
   clip_window_zeros (dst + slice0, c.pad_start, c.n44 * 2, slice_values, margin_values);
   if ((long long) blockIdx.x * tiles_per_wg * (R * J * NP) < c.n44)                // (uniform: a shorter clip of the group)
-    resample_phase_body<NP, STEP, HL, R, J> (ctab, c.in, c.n_in, c.n44, tiles_per_wg, sink);
+    resample_phase_body<NP, STEP, HL, R, J, false, In> (ctab, c.in, c.n_in, c.n44, tiles_per_wg, sink);
   clip_range_commit<((STEP > NP ? STEP : NP) * R + 63) / 64> (sink.first, sink.last, range + 2 * blockIdx.y);
 }
 
-hipError_t
-launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src, int n_clips, long long max_n44, bool stereo_aligned,
-                          float *dst, long long slice_values, long long margin_values, long long *range)
+template<class In> static hipError_t
+launch_clip_resample_pad_in (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src, int n_clips, long long max_n44, bool stereo_aligned,
+                             float *dst, long long slice_values, long long margin_values, long long *range)
 {
   if (n_clips <= 0 || slice_values <= 0)
     return hipSuccess;
@@ -4312,7 +4358,8 @@ launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResam
       const long long n_tiles = std::max<long long> (1, (max_n44 + R * J * NP - 1) / (R * J * NP));
       const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_clips / 4096)));
       const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg), unsigned (n_clips));
-      hipLaunchKernelGGL ((clip_resample_pad_phase_kernel<NP, STEP, HL, R, J>), grid, dim3 ((STEP * R + 63) / 64 * 64), 0, st, a.ctab, src, dst,
+      g_clip_form_launches[CLIP_FORM_PHASE]++;
+      hipLaunchKernelGGL ((clip_resample_pad_phase_kernel<NP, STEP, HL, R, J, In>), grid, dim3 ((STEP * R + 63) / 64 * 64), 0, st, a.ctab, src, dst,
                           slice_values, margin_values, r, tiles_per_wg);
       return hipGetLastError();
     }
@@ -4325,13 +4372,26 @@ launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResam
   const bool stage = stereo && lds_floats > 0 && span <= 4096 && (long long) RS_TILE * a.step + a.np < (1LL << 31);
   const int in_span = stage ? int (span) : 0;
   const size_t lds_bytes = size_t ((lds_floats + 1) & ~1) * sizeof (float) + size_t (in_span) * sizeof (float2);
+  g_clip_form_launches[CLIP_FORM_GENERIC]++;
   if (stereo)
-    hipLaunchKernelGGL (clip_resample_pad_kernel<2>, grid, dim3 (256), lds_bytes, st, a, src, dst, slice_values, margin_values, r, lds_floats, in_span,
-                        tiles_per_wg);
+    hipLaunchKernelGGL ((clip_resample_pad_kernel<2, In>), grid, dim3 (256), lds_bytes, st, a, src, dst, slice_values, margin_values, r, lds_floats,
+                        in_span, tiles_per_wg);
   else
-    hipLaunchKernelGGL (clip_resample_pad_kernel<0>, grid, dim3 (256), lds_bytes, st, a, src, dst, slice_values, margin_values, r, lds_floats, in_span,
-                        tiles_per_wg);
+    hipLaunchKernelGGL ((clip_resample_pad_kernel<0, In>), grid, dim3 (256), lds_bytes, st, a, src, dst, slice_values, margin_values, r, lds_floats,
+                        in_span, tiles_per_wg);
   return hipGetLastError();
+}
+hipError_t
+launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src, int n_clips, long long max_n44, bool stereo_aligned,
+                          float *dst, long long slice_values, long long margin_values, long long *range)
+{
+  return launch_clip_resample_pad_in<PcmF32> (st, a, src, n_clips, max_n44, stereo_aligned, dst, slice_values, margin_values, range);
+}
+hipError_t
+launch_clip_resample_pad_s16 (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src, int n_clips, long long max_n44, bool stereo_aligned,
+                              float *dst, long long slice_values, long long margin_values, long long *range)
+{
+  return launch_clip_resample_pad_in<PcmS16> (st, a, src, n_clips, max_n44, stereo_aligned, dst, slice_values, margin_values, range);
 }
 
 /* K10x (kernels.hh launch_clip_stage_mixed): K10c for a group of clips at several rates.  The three kernels are clip_resample_pad_kernel,
@@ -4339,7 +4399,7 @@ launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResam
  * descriptor: one uniform load per workgroup, the values stay in scalar registers.  The taps are the same functions, and the copy form is
  * clip_pad_kernel<ClipPadListed>. */
 /* the generic form: grid (workgroups of the longest clip, clips of the group); another form's clip: nothing to do (uniform) */
-template<int CT> __global__ void __launch_bounds__ (256)
+template<int CT, class In = PcmF32> __global__ void __launch_bounds__ (256)
 clip_stage_mixed_kernel (const ClipMixedSrc *__restrict__ src, int n_channels, float *dst, long long slice_values, long long margin_values,
                          unsigned long long *range, int tiles_per_wg)
 {
@@ -4356,12 +4416,12 @@ clip_stage_mixed_kernel (const ClipMixedSrc *__restrict__ src, int n_channels, f
   ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
   clip_window_zeros (dst + slice0, c.pad_start, c.n44 * n_channels, slice_values, margin_values);
   const ResampleSlice s { c.in, c.n_in, 0, 0, c.n44, nullptr };
-  resample_slice_body<CT> (a, s, c.lds_floats, c.in_span, tiles_per_wg, sink);
+  resample_slice_body<CT, In> (a, s, c.lds_floats, c.in_span, tiles_per_wg, sink);
   clip_range_commit<4> (sink.first, sink.last, range + 2 * blockIdx.y);
 }
 
 /* the phase-per-thread form: grid (workgroups of the longest of these clips, these clips), slice = list[blockIdx.y] */
-template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
+template<int NP, int STEP, int HL, int R, int J, class In = PcmF32> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
 clip_stage_mixed_phase_kernel (const ClipMixedSrc *__restrict__ src, const int *__restrict__ list, float *dst, long long slice_values,
                                long long margin_values, unsigned long long *range, int tiles_per_wg)
 {
@@ -4371,21 +4431,22 @@ clip_stage_mixed_phase_kernel (const ClipMixedSrc *__restrict__ src, const int *
   ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
   clip_window_zeros (dst + slice0, c.pad_start, c.n44 * 2, slice_values, margin_values);
   if ((long long) blockIdx.x * tiles_per_wg * (R * J * NP) < c.n44)                // (uniform: a shorter clip of the group)
-    resample_phase_body<NP, STEP, HL, R, J> (c.ctab, c.in, c.n_in, c.n44, tiles_per_wg, sink);
+    resample_phase_body<NP, STEP, HL, R, J, false, In> (c.ctab, c.in, c.n_in, c.n44, tiles_per_wg, sink);
   clip_range_commit<((STEP > NP ? STEP : NP) * R + 63) / 64> (sink.first, sink.last, range + 2 * slice);
 }
 
 ClipMixedPlan
-clip_stage_mixed_plan (ClipMixedSrc *src, int n_clips, int n_channels, int *list)
+clip_stage_mixed_plan (ClipMixedSrc *src, int n_clips, int n_channels, int *list, bool s16)
 {
   ClipMixedPlan p;
   p.n_channels = n_channels;
   p.n_clips = n_clips;
+  p.s16 = s16;
   uintptr_t bits = 0;
   for (int i = 0; i < n_clips; i++)
     if (src[i].np > 0)
       bits |= reinterpret_cast<uintptr_t> (src[i].in);
-  p.stereo_aligned = n_channels == 2 && (bits & 7) == 0;
+  p.stereo_aligned = n_channels == 2 && (bits & (s16 ? 3 : 7)) == 0;             // a stereo frame is one load
   for (int i = 0; i < n_clips; i++)
     {
       ClipMixedSrc& c = src[i];
@@ -4416,14 +4477,14 @@ clip_stage_mixed_plan (ClipMixedSrc *src, int n_clips, int n_channels, int *list
   return p;
 }
 
-hipError_t
-launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& p, const ClipMixedSrc *src, const int *list, float *dst, long long slice_values,
-                         long long margin_values, long long *range)
+template<class In> static hipError_t
+launch_clip_stage_mixed_in (hipStream_t st, const ClipMixedPlan& p, const ClipMixedSrc *src, const int *list, float *dst, long long slice_values,
+                            long long margin_values, long long *range)
 {
   const int n_clips = p.n_clips;
   if (n_clips <= 0 || slice_values <= 0)
     return hipSuccess;
-  if (n_clips > 65535 || p.max_n44 < 0 || slice_values % 4 || margin_values < 0 || (reinterpret_cast<uintptr_t> (dst) & 15) || p.n_channels < 1
+  if (p.s16 != std::is_same<In, PcmS16>::value || n_clips > 65535 || p.max_n44 < 0 || slice_values % 4 || margin_values < 0 || (reinterpret_cast<uintptr_t> (dst) & 15) || p.n_channels < 1
       || !src || !list || p.n_form[0] + p.n_form[1] + p.n_form[2] != n_clips || p.lds_bytes > size_t (64 * 1024))
     return hipErrorInvalidValue;
   if (g_clip_poison)
@@ -4433,6 +4494,8 @@ launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& p, const ClipMixed
   hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
   // tiles per workgroup by launch_clip_resample_pad's rule over the GROUP: tiles of its longest clip x its clips / 4096, between 1 and 8;
   // the grid of a form reaches as far as the longest clip of that form
+  for (int f = 0; f < 3; f++)
+    g_clip_form_launches[f] += p.n_form[f] ? 1 : 0;
   auto tiles = [&] (int tile, int form, int& tiles_per_wg) {
     const long long n_tiles = std::max<long long> (1, (p.max_n44 + tile - 1) / tile);
     tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_clips / 4096)));
@@ -4444,10 +4507,10 @@ launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& p, const ClipMixed
       int tiles_per_wg;
       const dim3 grid (tiles (RS_TILE, CLIP_FORM_GENERIC, tiles_per_wg), unsigned (n_clips));
       if (p.stereo_aligned)
-        hipLaunchKernelGGL (clip_stage_mixed_kernel<2>, grid, dim3 (256), p.lds_bytes, st, src, p.n_channels, dst, slice_values, margin_values, r,
+        hipLaunchKernelGGL ((clip_stage_mixed_kernel<2, In>), grid, dim3 (256), p.lds_bytes, st, src, p.n_channels, dst, slice_values, margin_values, r,
                             tiles_per_wg);
       else
-        hipLaunchKernelGGL (clip_stage_mixed_kernel<0>, grid, dim3 (256), p.lds_bytes, st, src, p.n_channels, dst, slice_values, margin_values, r,
+        hipLaunchKernelGGL ((clip_stage_mixed_kernel<0, In>), grid, dim3 (256), p.lds_bytes, st, src, p.n_channels, dst, slice_values, margin_values, r,
                             tiles_per_wg);
     }
   if (p.n_form[CLIP_FORM_PHASE])
@@ -4455,13 +4518,25 @@ launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& p, const ClipMixed
       constexpr int NP = 147, STEP = 160, HL = 18, R = 2, J = 8;
       int tiles_per_wg;
       const dim3 grid (tiles (R * J * NP, CLIP_FORM_PHASE, tiles_per_wg), unsigned (p.n_form[CLIP_FORM_PHASE]));
-      hipLaunchKernelGGL ((clip_stage_mixed_phase_kernel<NP, STEP, HL, R, J>), grid, dim3 ((STEP * R + 63) / 64 * 64), 0, st, src, list, dst,
+      hipLaunchKernelGGL ((clip_stage_mixed_phase_kernel<NP, STEP, HL, R, J, In>), grid, dim3 ((STEP * R + 63) / 64 * 64), 0, st, src, list, dst,
                           slice_values, margin_values, r, tiles_per_wg);
     }
   if (p.n_form[CLIP_FORM_COPY])
-    hipLaunchKernelGGL (clip_pad_kernel<ClipPadListed>, dim3 (128, unsigned (p.n_form[CLIP_FORM_COPY])), dim3 (256), 0, st,
+    hipLaunchKernelGGL ((clip_pad_kernel<ClipPadListed, In>), dim3 (128, unsigned (p.n_form[CLIP_FORM_COPY])), dim3 (256), 0, st,
                         ClipPadListed { src, list + (n_clips - p.n_form[CLIP_FORM_COPY]), p.n_channels }, dst, slice_values, margin_values, r);
   return hipGetLastError();
+}
+hipError_t
+launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& p, const ClipMixedSrc *src, const int *list, float *dst, long long slice_values,
+                         long long margin_values, long long *range)
+{
+  return launch_clip_stage_mixed_in<PcmF32> (st, p, src, list, dst, slice_values, margin_values, range);
+}
+hipError_t
+launch_clip_stage_mixed_s16 (hipStream_t st, const ClipMixedPlan& p, const ClipMixedSrc *src, const int *list, float *dst, long long slice_values,
+                             long long margin_values, long long *range)
+{
+  return launch_clip_stage_mixed_in<PcmS16> (st, p, src, list, dst, slice_values, margin_values, range);
 }
 
 /* kernels.hh launch_segment_copy: grid (runs, segments).  A segment that starts r samples into its first frame is 8 r bytes off the

@@ -4336,6 +4336,100 @@ awm_debug_clip_stage_rates_d (awm_ctx *ctx, size_t n_clips, const float *const *
   return clip_stage_device (ctx, clips, &rates, slices_d, range_out);
 }
 
+/* The batches on 16-bit clips (awm_get_watermark_batch_rates_s16_d and its twins): the refusals, the converters and the clips of a call.
+ * sample_rates may be null (every clip at 44.1 kHz).  Always the path with a rate per clip: a group that shares one rate runs the one-rate
+ * stage there as well, and a call at 44.1 kHz the copy */
+static int
+clips_s16 (awm_ctx *ctx, const char *who, size_t n_clips, const int16_t *const *pcm_d, const size_t *n_frames, int n_channels, const int *sample_rates,
+           ClipRates& rates, std::vector<DeviceWav>& clips)
+{
+  std::vector<int> mark_rates;
+  if (!sample_rates)
+    {
+      mark_rates.assign (n_clips, int (Params::mark_sample_rate));
+      sample_rates = mark_rates.data();
+    }
+  if (int rc = check_clip_rates (who, n_clips, n_frames, sample_rates))
+    return rc;
+  for (size_t i = 0; i < n_clips; i++)
+    if ((reinterpret_cast<uintptr_t> (pcm_d[i]) & 1) || (!pcm_d[i] && n_frames[i]))
+      {
+        set_error (string_printf ("%s: clip %zu: %s", who, i, pcm_d[i] ? "pcm_d is not 2-byte aligned" : "pcm_d is null"));
+        return AWM_ERR_ARG;
+      }
+  if (int rc = clip_rates_each (ctx, sample_rates, n_clips, n_frames, rates))
+    return rc;
+  for (size_t i = 0; i < n_clips; i++)
+    {
+      DeviceWav w = make_wav_rate (nullptr, n_frames[i], n_channels, sample_rates[i]);
+      w.pcm16 = pcm_d[i];
+      clips.push_back (w);
+    }
+  return 0;
+}
+
+static int
+get_watermark_batch_s16 (awm_ctx *ctx, const char *who, const uint8_t key[16], const uint8_t *keys, size_t n_clips, const int16_t *const *pcm_d,
+                         const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out,
+                         int *n_out)
+{
+  if (!n_clips)
+    return 0;
+  if (!pcm_d || !n_frames || !n_out || (max_out_per_clip && !out) || (!key && !keys) || n_channels < 1)
+    {
+      set_error (string_printf ("%s: bad argument", who));
+      return AWM_ERR_ARG;
+    }
+  ClipRates rates;
+  std::vector<DeviceWav> clips;
+  if (int rc = clips_s16 (ctx, who, n_clips, pcm_d, n_frames, n_channels, sample_rates, rates, clips))
+    return rc;
+  std::vector<Key> clip_keys;
+  if (keys)
+    clip_keys = key_list_from (keys, int (n_clips));
+  std::vector<ResultSet> sets;
+  if (int rc = get_watermark_batch_device (ctx, keys ? std::vector<Key> {} : std::vector<Key> { capi_key (key) }, clips, sets, n_threads,
+                                           keys ? &clip_keys : nullptr, &rates))
+    return rc;
+  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
+  return 0;
+}
+
+int
+awm_get_watermark_batch_rates_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const int16_t *const *pcm_d, const size_t *n_frames,
+                                     int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  AWM_ENTER (ctx);
+  return get_watermark_batch_s16 (ctx, "awm_get_watermark_batch_rates_s16_d", key, nullptr, n_clips, pcm_d, n_frames, n_channels, sample_rates, n_threads,
+                                  max_out_per_clip, out, n_out);
+}
+
+int
+awm_get_watermark_batch_keys_rates_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const int16_t *const *pcm_d, const size_t *n_frames,
+                                          int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  AWM_ENTER (ctx);
+  return get_watermark_batch_s16 (ctx, "awm_get_watermark_batch_keys_rates_s16_d", nullptr, keys, n_clips, pcm_d, n_frames, n_channels, sample_rates,
+                                  n_threads, max_out_per_clip, out, n_out);
+}
+
+int
+awm_debug_clip_stage_rates_s16_d (awm_ctx *ctx, size_t n_clips, const int16_t *const *pcm_d, const size_t *n_frames, int n_channels,
+                                  const int *sample_rates, float *slices_d, long long *range_out)
+{
+  AWM_ENTER (ctx);
+  if (!n_clips || !pcm_d || !n_frames || n_channels < 1)
+    {
+      set_error ("awm_debug_clip_stage_rates_s16_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  ClipRates rates;
+  std::vector<DeviceWav> clips;
+  if (int rc = clips_s16 (ctx, "awm_debug_clip_stage_rates_s16_d", n_clips, pcm_d, n_frames, n_channels, sample_rates, rates, clips))
+    return rc;
+  return clip_stage_device (ctx, clips, &rates, slices_d, range_out);
+}
+
 int
 awm_get_batch_rates_plan (size_t n_clips, const size_t *n_frames, const int *sample_rates, int *path_out, size_t *n44_out)
 {

@@ -171,7 +171,7 @@ void
 awm::WorkLane::release_lane()
 {
   for (DevBuffer *b : { &ws_db, &ws_block_db, &ws_have, &ws_q, &ws_raw, &ws_mean, &ws_misc, &ws_refine, &ws_refine_have, &ws_soft, &ws_viterbi,
-                        &ws_viterbi_in, &ws_viterbi_bits, &ws_viterbi_err, &ws_viterbi_sync, &ws_block_max, &ws_clip, &ws_idx, &ws_limit_tab, &ws_jobs, &ws_group, &ws_keytab, &ws_keytab_aux, &ws_keytab_scratch, &ws_rate, &ws_shard_edge, &ws_shard_tail, &ws_shard_q })
+                        &ws_viterbi_in, &ws_viterbi_bits, &ws_viterbi_err, &ws_viterbi_sync, &ws_block_max, &ws_clip, &ws_idx, &ws_limit_tab, &ws_jobs, &ws_group, &ws_keytab, &ws_keytab_aux, &ws_keytab_scratch, &ws_rate, &ws_pcm, &ws_shard_edge, &ws_shard_tail, &ws_shard_q })
     b->release();
   for (PinnedBuffer *b : { &pin_refine_in[0], &pin_refine_in[1], &pin_refine_q[0], &pin_refine_q[1], &pin_peaks, &pin_blocks, &pin_jobs, &pin_bits, &pin_small, &pin_group, &pin_shard, &pin_shard_up, &pin_keytab })
     b->release();
@@ -599,7 +599,8 @@ static const char *prof_names[awm::PROF_COUNT] = {
   "stft_full_kernel",
   "resample_kernel", "resample_var_kernel", "speed_mags_kernel", "speed_compare_kernel", "frame_mod_table_kernel",
   "add_mix_multi_kernel", "payload_table_kernel",
-  "resample_mix_multi_kernel", "clip_resample_pad_kernel", "key_template_kernel", "clip_stage_mixed_kernel"
+  "resample_mix_multi_kernel", "clip_resample_pad_kernel", "key_template_kernel", "clip_stage_mixed_kernel",
+  "clip_pad_s16_kernel", "clip_resample_pad_s16_kernel", "clip_stage_mixed_s16_kernel"
 };
 
 extern "C" {
@@ -843,6 +844,20 @@ awm_ctx_trim (awm_ctx *ctx)
     if (h && h != ctx)
       if (int rc = awm_ctx_trim (h)) return rc;
   return 0;
+}
+
+/* (test probe) bytes the lanes of the context hold as float copies of 16-bit clips (WorkLane::ws_pcm): 0 after awm_ctx_trim and for as
+ * long as the 16-bit batches see short clips only */
+size_t
+awm_debug_lane_pcm_bytes (awm_ctx *ctx)
+{
+  if (!ctx)
+    return 0;
+  size_t bytes = ctx->ws_pcm.bytes;
+  for (auto& l : ctx->extra_lanes)
+    if (l)
+      bytes += l->ws_pcm.bytes;
+  return bytes;
 }
 
 void

@@ -231,7 +231,8 @@ namespace awm {
 enum ProfId { PROF_ADD_MIX, PROF_LIMITER, PROF_SYNC_DB, PROF_SYNC_SCAN, PROF_LOCAL_MEAN, PROF_REFINE_DB, PROF_REFINE_SCAN,
               PROF_BLOCK_DB, PROF_SOFT_BITS, PROF_VITERBI, PROF_STFT,
               PROF_RESAMPLE, PROF_RESAMPLE_VAR, PROF_SPEED_MAGS, PROF_SPEED_COMPARE, PROF_KEYTAB, PROF_ADD_MIX_MULTI, PROF_PAYLOAD_TAB,
-              PROF_RESAMPLE_MIX, PROF_CLIP_RESAMPLE, PROF_KEY_TEMPLATE, PROF_CLIP_STAGE_MIXED, PROF_COUNT };
+              PROF_RESAMPLE_MIX, PROF_CLIP_RESAMPLE, PROF_KEY_TEMPLATE, PROF_CLIP_STAGE_MIXED,
+              PROF_CLIP_PAD_S16, PROF_CLIP_RESAMPLE_S16, PROF_CLIP_STAGE_MIXED_S16, PROF_COUNT };
 struct ProfPending { int id; hipEvent_t start, stop; };
 }
 
@@ -247,6 +248,7 @@ struct WorkLane
   DevBuffer ws_db, ws_block_db, ws_have, ws_q, ws_raw, ws_mean, ws_misc, ws_refine, ws_refine_have, ws_soft,
             ws_viterbi, ws_viterbi_in, ws_viterbi_bits, ws_viterbi_err, ws_viterbi_sync, ws_block_max, ws_clip, ws_idx, ws_limit_tab, ws_jobs, ws_group, ws_keytab, ws_keytab_aux, ws_keytab_scratch;
   DevBuffer ws_rate;                                       // `get` of material at another rate (wmget.cc resample_to_mark_rate): the 44.1 kHz copy of the clip this lane works on
+  DevBuffer ws_pcm;                                        // `get` of a batch of 16-bit clips (wmget.cc decode_clip_on_lane): the float copy of the clip this lane works on -- long clips, VResampler rates, speed search; the groups never use it
   DevBuffer ws_shard_edge, ws_shard_tail, ws_shard_q;      // multi-GPU protocol (wmshard.cc): edge frames, stitched tail buffer, score blocks
   // host staging (two refinement slots: see SyncFinder::SearchJob)
   PinnedBuffer pin_refine_in[2], pin_refine_q[2], pin_peaks, pin_blocks, pin_jobs, pin_bits, pin_small, pin_group, pin_shard, pin_shard_up, pin_keytab;

@@ -14,6 +14,9 @@ struct DeviceWav
   size_t       n_frames = 0;      // samples per channel
   int          n_channels = 0;
   int          sample_rate = 44100;
+  // a clip of a batch that the caller holds as signed 16-bit PCM (wmget.hh get_watermark_batch_device): its values, `data` is null.
+  // Stage 0 of the groups reads them as they are; every other consumer is given a float DeviceWav
+  const int16_t *pcm16 = nullptr;
   size_t n_values() const { return n_frames * n_channels; }
 };
 

@@ -1784,6 +1784,11 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
   hipStream_t st = lane->stream;
   const int C = clips[which[0]].n_channels;
   const size_t n = slice_values / 3;
+  // 16-bit clips (all clips of a call or none): the same three forms through the launchers that read int16, under scopes of their own; the
+  // descriptors carry the address of the clip's values whatever their type (kernels.hh launch_clip_pad_s16)
+  const bool s16 = clips[which[0]].pcm16 != nullptr;
+  auto values_of = [s16] (const DeviceWav& wav) { return s16 ? reinterpret_cast<const float *> (wav.pcm16) : wav.data; };
+  const double sample_bytes_in = s16 ? 2.0 : 4.0;
   // which form: one rate for the whole group (44.1 kHz: the copy), or a rate per clip
   bool one_rate = true;
   if (rates)
@@ -1809,9 +1814,18 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
     {
       auto *desc = lane->pin_group.as<awmk::ClipSrc>();
       for (size_t i = 0; i < gn; i++)
-        desc[i] = { clips[which[i]].data, s0.n_values[i], s0.pad_start[i] };
+        desc[i] = { values_of (clips[which[i]]), s0.n_values[i], s0.pad_start[i] };
       auto *d_desc = lane->ws_group.as<awmk::ClipSrc>();
       AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
+      if (s16)
+        {
+          double values = 0;
+          for (size_t i = 0; i < gn; i++)
+            values += double (s0.n_values[i]);
+          ProfScope ps (ctx, PROF_CLIP_PAD_S16, values * (2.0 + 4.0), st);      // every value read as int16 and written as float once
+          AWM_HIP_CHECK (awmk::launch_clip_pad_s16 (st, d_desc, int (gn), slices, (long long) slice_values, s0.margin_values, s0.d_range));
+          return 0;
+        }
       AWM_HIP_CHECK (awmk::launch_clip_pad (st, d_desc, int (gn), slices, (long long) slice_values, s0.margin_values, s0.d_range));
       return 0;
     }
@@ -1824,16 +1838,16 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
         {
           const DeviceWav& wav = clips[which[i]];
           const ResampleTable *t = rates->table[which[i]];                      // (null: a clip at 44.1 kHz, copied)
-          desc[i] = { wav.data, (long long) wav.n_frames, s0.n_values[i] / C, s0.pad_start[i], t ? t->ctab.as<float>() : nullptr,
+          desc[i] = { values_of (wav), (long long) wav.n_frames, s0.n_values[i] / C, s0.pad_start[i], t ? t->ctab.as<float>() : nullptr,
                       t ? t->hl : 0, t ? t->np : 0, t ? t->step : 0, 0, 0, 0 };
-          samples += double (wav.n_frames) + double (desc[i].n44);
+          samples += double (wav.n_frames) * (sample_bytes_in / 4.0) + double (desc[i].n44);
         }
-      const awmk::ClipMixedPlan plan = awmk::clip_stage_mixed_plan (desc, int (gn), C, list);
+      const awmk::ClipMixedPlan plan = awmk::clip_stage_mixed_plan (desc, int (gn), C, list, s16);
       auto *d_desc = lane->ws_group.as<awmk::ClipMixedSrc>();
       AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
-      ProfScope ps (ctx, PROF_CLIP_STAGE_MIXED, samples * C * 4.0, st);         // every input and output sample of the group once
-      AWM_HIP_CHECK (awmk::launch_clip_stage_mixed (st, plan, d_desc, reinterpret_cast<const int *> (d_desc + gn), slices, (long long) slice_values,
-                                                    s0.margin_values, s0.d_range));
+      ProfScope ps (ctx, s16 ? PROF_CLIP_STAGE_MIXED_S16 : PROF_CLIP_STAGE_MIXED, samples * C * 4.0, st);     // every input and output sample of the group once
+      AWM_HIP_CHECK ((s16 ? awmk::launch_clip_stage_mixed_s16 : awmk::launch_clip_stage_mixed) (st, plan, d_desc, reinterpret_cast<const int *> (d_desc + gn),
+                                                                                                slices, (long long) slice_values, s0.margin_values, s0.d_range));
       return 0;
     }
   auto *desc = lane->pin_group.as<awmk::ClipResampleSrc>();
@@ -1843,10 +1857,10 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
   for (size_t i = 0; i < gn; i++)
     {
       const DeviceWav& wav = clips[which[i]];
-      desc[i] = { wav.data, (long long) wav.n_frames, s0.n_values[i] / C, s0.pad_start[i] };
-      bits |= reinterpret_cast<uintptr_t> (wav.data);
+      desc[i] = { values_of (wav), (long long) wav.n_frames, s0.n_values[i] / C, s0.pad_start[i] };
+      bits |= reinterpret_cast<uintptr_t> (desc[i].in);
       max_n44 = std::max (max_n44, desc[i].n44);
-      samples += double (wav.n_frames) + double (desc[i].n44);
+      samples += double (wav.n_frames) * (sample_bytes_in / 4.0) + double (desc[i].n44);
     }
   auto *d_desc = lane->ws_group.as<awmk::ClipResampleSrc>();
   AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
@@ -1857,9 +1871,13 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
   ra.hl = table->hl;
   ra.np = table->np;
   ra.step = table->step;
-  ProfScope ps (ctx, PROF_CLIP_RESAMPLE, samples * C * 4.0, st);               // every input and output sample of the group once
-  AWM_HIP_CHECK (awmk::launch_clip_resample_pad (st, ra, d_desc, int (gn), max_n44, (bits & 7) == 0, slices, (long long) slice_values,
-                                                 s0.margin_values, s0.d_range));
+  ProfScope ps (ctx, s16 ? PROF_CLIP_RESAMPLE_S16 : PROF_CLIP_RESAMPLE, samples * C * 4.0, st);      // every input and output sample of the group once
+  if (s16)                                                                      // (a 16-bit stereo frame is 4 bytes)
+    AWM_HIP_CHECK (awmk::launch_clip_resample_pad_s16 (st, ra, d_desc, int (gn), max_n44, (bits & 3) == 0, slices, (long long) slice_values,
+                                                       s0.margin_values, s0.d_range));
+  else
+    AWM_HIP_CHECK (awmk::launch_clip_resample_pad (st, ra, d_desc, int (gn), max_n44, (bits & 7) == 0, slices, (long long) slice_values,
+                                                   s0.margin_values, s0.d_range));
   return 0;
 }
 
@@ -2097,13 +2115,23 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
   // clip_keys: one key per clip (clip i is decoded with (*clip_keys)[i] alone); else every clip with the whole key_list
   auto keys_of = [&] (size_t i) { return clip_keys ? std::vector<Key> { (*clip_keys)[i] } : key_list; };
   // one clip on one lane: at another rate its 44.1 kHz copy goes into the lane's workspace first
+  // (a 16-bit clip that goes this way is decoded into the lane's workspace first: one launch, the exact conversion of the file level)
   auto get_one = [&] (WorkLane *lane, bool spread, size_t i) {
+    DeviceWav clip = clips[i];
+    if (clip.pcm16 && clip.n_values())
+      {
+        if (int rc = lane->ws_pcm.reserve (std::max<size_t> (16, clip.n_values() * sizeof (float)))) return rc;
+        AWM_HIP_CHECK (awmk::launch_pcm_decode (lane->stream, reinterpret_cast<const unsigned char *> (clip.pcm16), lane->ws_pcm.as<float>(),
+                                                (long long) clip.n_values(), awmk::PcmFormatDev { 2, 0, 0, 0 }));
+        clip.data = lane->ws_pcm.as<float>();
+      }
+    clip.pcm16 = nullptr;
     if (!rates)
-      return get_watermark_on (ctx, lane, spread, keys_of (i), clips[i], result_sets[i]);
+      return get_watermark_on (ctx, lane, spread, keys_of (i), clip, result_sets[i]);
     if (!rates->n44[i])
       return 0;                                      // an empty clip: no patterns
     DeviceWav wav44;
-    if (int rc = resample_to_mark_rate (ctx, lane, *rates, i, clips[i], wav44))
+    if (int rc = resample_to_mark_rate (ctx, lane, *rates, i, clip, wav44))
       return rc;
     return get_watermark_on (ctx, lane, spread, keys_of (i), wav44, result_sets[i]);
   };
@@ -2290,7 +2318,7 @@ clip_stage_device (awm_ctx *ctx, const std::vector<DeviceWav>& clips, const Clip
           set_error ("awm_debug_clip_stage_d: a rate that the fixed-ratio resampler does not take");
           return AWM_ERR_ARG;
         }
-      if (!clips[i].data || clips[i].n_channels != clips[0].n_channels || !clip_is_short (rates ? rates->n44[i] : clips[i].n_frames))
+      if ((!clips[i].data && !clips[i].pcm16) || !clips[i].pcm16 != !clips[0].pcm16 || clips[i].n_channels != clips[0].n_channels || !clip_is_short (rates ? rates->n44[i] : clips[i].n_frames))
         {
           set_error ("awm_debug_clip_stage_d: not a short clip");
           return AWM_ERR_ARG;

@@ -58,6 +58,8 @@ int get_watermark_device (awm_ctx *ctx, const std::vector<Key>& key_list, const 
 // rates (may be null): the clips are at another sample rate -- clips[i] is the clip as the caller holds it, its result that of the clip
 // resampled to 44.1 kHz (WavChunkLoader, reference wavchunkloader.cc:70-71, 200-216)
 // (a rate per clip: awm_get_watermark_batch_rates_d; the one-rate calls fill in the same rate and table for every clip)
+// 16-bit clips (DeviceWav::pcm16 set in every clip of the call, awm_get_watermark_batch_rates_s16_d): stage 0 of the groups reads them as
+// they are; a clip that goes over a lane is decoded into the lane's ws_pcm first
 struct ClipRates
 {
   std::vector<int>                   sample_rate;   // of clip i

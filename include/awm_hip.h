@@ -496,8 +496,35 @@ int awm_get_watermark_batch_keys_rates_d (awm_ctx *ctx, const uint8_t *keys, siz
 /* Pure host, no context, no device: which way clip i of such a call goes -- path_out[i] = 0 a group | 1 a lane, fixed-ratio resampler (or
  * a long clip at 44100, which is not resampled) | 2 a lane, VResampler | 3 empty, nothing to do -- and its length at 44.1 kHz, with the
  * parameters in force (the short / long border is block frames + 2).  Either output may be NULL.  AWM_ERR_ARG for the rates that the calls
- * above refuse, with -1 in that clip's path_out (the other clips are still filled in). */
+ * above refuse, with -1 in that clip's path_out (the other clips are still filled in).  The 16-bit batches below take the same paths:
+ * the sample format does not change them. */
 int awm_get_batch_rates_plan (size_t n_clips, const size_t *n_frames, const int *sample_rates, int *path_out, size_t *n44_out);
+/* The batches with a rate per clip on clips that are resident as SIGNED 16-BIT PCM (little-endian, interleaved: what a decoder or a capture
+ * card hands out, the reference's native rule, rawconverter.cc) -- no float copy of a clip beside or instead of its 16-bit original, no
+ * decode launch per clip.  Clip i = n_frames[i] frames of n_channels int16 values at pcm_d[i] (device pointers), at sample_rates[i];
+ * sample_rates == NULL: every clip is at 44100.
+ * Definition: with f_i = what awm_pcm_decode_d (ctx, pcm_d[i], n_frames[i] * n_channels, 16, 0, 0, f_i) writes -- float (v) * (1 / 32768),
+ * exact -- the result for clip i is field for field what awm_get_watermark_batch_rates_d returns for f_i at sample_rates[i]; key_i = key, or
+ * keys + 16 i in the keys form.
+ * Paths: those of awm_get_watermark_batch_rates_d (awm_get_batch_rates_plan).  Stage 0 of a group of short clips READS THE 16-BIT VALUES:
+ * the copy, K10c and K10x are the same kernels instantiated for 16-bit input, which convert where a value leaves global memory (once per
+ * input value) and are bit for bit the float kernels on f_i behind that; a short clip never has a float copy and never costs a launch of
+ * its own.  Long clips, VResampler rates and every clip while a speed parameter is set are decoded into a grow-only workspace of their lane
+ * first (one launch; awm_ctx_trim gives it back) and go on as in the float call.
+ * Alignment: pcm_d[i] need only be 2-byte aligned.  A stereo group whose resampled clips are all 4-byte aligned loads whole frames
+ * and keeps the phase-per-thread form for 48 kHz; one clip on an address that is only 2-byte aligned sends its group to the generic taps
+ * (same bits).  Nothing outside a clip's values is read.
+ * Refusals, AWM_ERR_ARG with nothing enqueued and n_out / out untouched, awm_last_error names the index of the first offending clip:
+ * those of awm_get_watermark_batch_rates_d for the rates (except that sample_rates may be NULL), an odd pcm_d[i], a NULL pcm_d[i] with
+ * n_frames[i] > 0.  n_clips == 0 returns 0; an empty clip gives n_out[i] = 0.
+ * Not offered in this form: other sample formats, a format per clip, the command line, the file level (which converts its files' formats
+ * itself), the awm_multi_* / sharded batches, the `add` side. */
+int awm_get_watermark_batch_rates_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const int16_t *const *pcm_d,
+                                         const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads,
+                                         size_t max_out_per_clip, awm_pattern *out, int *n_out);
+int awm_get_watermark_batch_keys_rates_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const int16_t *const *pcm_d,
+                                              const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads,
+                                              size_t max_out_per_clip, awm_pattern *out, int *n_out);
 /* decode() of one chunk only (wmget.cc:886-939) -- the unit `get` is sharded by */
 int awm_decode_chunk_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames,
                         int n_channels, int first_chunk, size_t max_out, awm_pattern *out);
@@ -785,6 +812,14 @@ int  awm_debug_clip_stage_rates_d (awm_ctx *ctx, size_t n_clips, const float *co
                                    const int *sample_rates, float *slices_d, long long *range_out);
                                            /* its twin with a rate per clip: a group whose clips do not share one rate goes through K10x, one that does as above.
                                             * The same refusals, and those of awm_get_watermark_batch_rates_d */
+int  awm_debug_clip_stage_rates_s16_d (awm_ctx *ctx, size_t n_clips, const int16_t *const *pcm_d, const size_t *n_frames, int n_channels,
+                                       const int *sample_rates, float *slices_d, long long *range_out);
+                                           /* ... and on 16-bit clips (awm_get_watermark_batch_rates_s16_d; sample_rates NULL: all at 44100): slices and ranges are bit for
+                                            * bit those of awm_debug_clip_stage_rates_d on the decoded clips.  The same refusals, and an odd or (with frames) NULL pcm_d[i] */
+void awm_debug_clip_form_launches (long out[3]); /* clip batches: stage 0 kernels launched by this process so far, by form: [0] generic taps, [1] phase per thread, [2] copy (the
+                                            * profiling scopes count a group's stage 0 as one launch whatever its forms) */
+size_t awm_debug_lane_pcm_bytes (awm_ctx *ctx); /* bytes the context's lanes hold as float copies of 16-bit clips (long clips, VResampler rates, speed search): 0 after
+                                            * awm_ctx_trim and for as long as the 16-bit batches see short clips only */
 void awm_debug_set_clip_pad_margin (int frames); /* clip batches: frames of zeros written on either side of a clip (default and minimum 2048; one slice = 6693 frames
                                             * or more: whole slices, the A side of the measurement in tools/gpu_clip_margin_ab.py) */
 void awm_debug_set_staged_threads (int n);  /* clip batches: host threads (= lanes) working on groups of clips; 0 = default (4; 2 with a key per clip only where the
