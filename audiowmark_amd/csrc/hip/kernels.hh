@@ -523,44 +523,42 @@ hipError_t launch_pcm_encode (hipStream_t st, const float *in, unsigned char *by
  * reference syncfinder.cc:155-169); result[0] = first (n_values if all zero), result[1] = last */
 hipError_t launch_nonzero_range (hipStream_t st, const float *data, long long n_values, unsigned long long *result);
 
-/* The padded copies of a group of clips (ClipDecoder, reference wmget.cc:830-867, START position) side by side in one buffer:
- * slice i = [pad_start_i zeros][clip i][pad zeros], slice_values each, and the non-silent range of every slice
- * (range[2 i] = first non-zero value, absolute index in dst, -1 if there is none; range[2 i + 1] = last + 1). */
-struct ClipSrc { const float *data; long long n_values; long long pad_start; };
-/* Of the padding only `margin_values` on either side of a clip are written (the rest of a slice keeps whatever the buffer held): every
+/* Stage 0 of a group of clips (ClipDecoder, reference wmget.cc:830-867, START position): the padded clips at 44.1 kHz side by side in one
+ * buffer -- slice i = [pad_start_i zeros][clip i][pad zeros], slice_values each -- and the non-silent range of every slice (range[2 i] =
+ * first non-zero value, absolute index in dst, -1 if there is none; range[2 i + 1] = last + 1).
+ * Of the padding only `margin_values` on either side of a clip are written (the rest of a slice keeps whatever the buffer held): every
  * consumer of the slices skips the frames outside the non-silent range -- K4 / K4b per frame, K4s per row of fine offsets, K7 per item --
  * and the frames it does read reach at most 1024 + 8 * 64 frames (K4s: a row of 65 fine offsets, plus its read-ahead) beyond that range.
- * margin_values >= slice_values writes whole slices. */
-hipError_t launch_clip_pad (hipStream_t st, const ClipSrc *src /* device */, int n_clips, float *dst, long long slice_values, long long margin_values,
-                            long long *range);
-/* K10c: stage 0 for a group of clips at ANOTHER RATE whose ratio the fixed-ratio resampler takes -- K10 straight into the padded slices,
- * one launch per group (blockIdx.y = clip).  Clip i has n_in frames at its rate at `in` (4-byte aligned; nothing outside them is read) and
- * n44 frames at 44.1 kHz: output frame m of K10's definition above, for the stream "hl - 1 null frames, the clip, null frames for ever",
- * goes to pad_start + m C of slice i, zeros go to the rest of the window that launch_clip_pad writes, and range receives the non-silent
- * range of what was stored -- slices and ranges are bit for bit those of launch_resample into a buffer and launch_clip_pad from it.  The
- * products and sums are K10's through K10's own tap code.  Forms, chosen as launch_resample chooses: 48 -> 44.1 kHz stereo with every input
- * 8-byte aligned (stereo_aligned): a phase per thread; other ratios, stereo_aligned: table and the tile's window in LDS; everything else
- * the generic taps.  ctab / hl / np / step / n_channels come from `a`; max_n44 is the largest n44 of the group. */
-struct ClipResampleSrc { const float *in; long long n_in, n44, pad_start; };
-hipError_t launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src /* device */, int n_clips, long long max_n44,
-                                     bool stereo_aligned, float *dst, long long slice_values, long long margin_values, long long *range);
-/* K10x: stage 0 for a group whose clips do NOT share one rate.  Every clip brings its own descriptor: its frames, n44 and pad_start as
- * above and its OWN resampler geometry and table (ctab / hl / np / step of its rate's ResampleTable); np == 0 marks a clip that is at
- * 44.1 kHz already and is copied (n_in == n44).  Slice i and range[2 i ..] are bit for bit what launch_clip_resample_pad (np > 0) or
- * launch_clip_pad (np == 0) writes for clip i alone in slice i: the taps are K10's own code (resample_slice_body / resample_phase_body), which
- * reads its geometry from the clip's descriptor -- uniform per workgroup, scalar registers -- instead of from the launch.
- * Launches: clip_range_init_kernel and one per FORM present in the group, whatever the number of clips or of distinct rates --
- *   CLIP_FORM_GENERIC  the table and, for stereo with every resampled input 8-byte aligned, the tile's window in LDS (the generic taps where
- *                      the clip's table or window does not fit); grid.y = every clip of the group, the workgroups of the other forms'
- *                      clips leave at once; dynamic LDS = the largest of the group
- *   CLIP_FORM_PHASE    the phase-per-thread form <147, 160, 18, 2, 8> for the aligned stereo 48 kHz clips (awm_debug_set_resample_phase)
+ * margin_values >= slice_values writes whole slices.
+ * Every clip brings its descriptor: n_in frames at its own rate at `in` (nothing outside them is read), n44 frames at 44.1 kHz, pad_start,
+ * and the geometry and table of its rate's fixed-ratio resampler (ctab / hl / np / step of the ResampleTable).  np == 0 marks a clip that
+ * is at 44.1 kHz already (n_in == n44, no table): it is copied.  A resampled clip is K10 straight into its slice: output frame m of K10's
+ * definition above, for the stream "hl - 1 null frames, the clip, null frames for ever", goes to pad_start + m C -- slice and range are bit
+ * for bit those of launch_resample into a buffer and a copy from it, the products and sums come from K10's own tap code
+ * (resample_slice_body / resample_phase_body), which reads its geometry from the descriptor: uniform per workgroup, scalar registers.
+ * Three forms, one kernel each, each over its own clips only (grid.y):
+ *   CLIP_FORM_GENERIC  the table and, for stereo with every resampled input of the group aligned, the tile's window in LDS (the generic taps
+ *                      where the clip's table or window does not fit); dynamic LDS = the largest of the group
+ *   CLIP_FORM_PHASE    the phase-per-thread form <147, 160, 18, 2, 8> for aligned stereo 48 kHz clips (awm_debug_set_resample_phase)
  *   CLIP_FORM_COPY     the 44.1 kHz clips
- * the last two over their own clips only, whose slice indices they read from `list`.
- * clip_stage_mixed_plan (host) chooses the form of every clip, fills form / lds_floats / in_span of src[0 .. n_clips) by the rule
- * launch_clip_resample_pad applies to its one rate, and writes list[0 .. n_clips): the slices of the phase form from the front, those of the
- * copy form from the back.  The launcher is given the plan and the device copies of src and list. */
+ * clip_stage_plan (host) chooses the form of every clip as launch_resample chooses for a stream of that rate, fills form / lds_floats /
+ * in_span of src[0 .. n_clips) and writes list[0 .. n_clips): the slice indices form by form, in the order of the enum.  The launcher is
+ * given the plan and the device copies of src and list; a form's workgroups find their slice in the form's part of the list -- or, where
+ * every clip of the group has that form (a group at one rate), take blockIdx.y and load no list.  Launches per group:
+ * clip_range_init_kernel and one per form PRESENT, whatever the number of clips or of distinct rates -- two for a group at one rate.
+ * Tiles per workgroup: tiles of the group's longest clip x its clips / 4096, between 1 and 8.  Refused (hipErrorInvalidValue): dst not
+ * 16-byte aligned, slice_values % 4, more than 65535 clips, more than 64 KiB of LDS, a plan made for the other input type.
+ * Input types: launch_clip_stage reads float clips, launch_clip_stage_s16 SIGNED 16-BIT PCM (little-endian, interleaved: the reference's
+ * native format, rawconverter.cc) with the plan made for it (s16 = true).  The descriptors are the same -- `in` holds the ADDRESS of the
+ * clip's int16 values -- and slices and ranges are bit for bit what the float launcher writes for the decoded clips, float (v) * (1 /
+ * 32768) (launch_pcm_decode): the same kernels instantiated for the other input type, whose loads convert and whose taps, sums, sinks,
+ * zeros and ranges are the same code.  A value is converted once: on its way into the LDS window of the staged forms (the window stays
+ * float2), or as the unstaged taps and the copy read it.
+ * Alignment: a float clip may begin at any 4-byte address, an int16 clip at any EVEN address.  "Aligned" (stereo_aligned) means that a
+ * stereo frame is one load -- every resampled input of the group 8-byte aligned (float) or 4-byte aligned (int16); a group with an input
+ * that is not, or with another channel count, takes the generic taps with loads of one value.  The copy form loads single values. */
 enum { CLIP_FORM_GENERIC = 0, CLIP_FORM_PHASE = 1, CLIP_FORM_COPY = 2 };
-struct ClipMixedSrc
+struct ClipStageSrc
 {
   const float *in;
   long long    n_in, n44, pad_start;
@@ -569,7 +567,7 @@ struct ClipMixedSrc
   int          form;                 // CLIP_FORM_*
   int          lds_floats, in_span;  // CLIP_FORM_GENERIC: floats of the table in LDS (0: from global memory), frames of the tile's window (0: not staged)
 };
-struct ClipMixedPlan
+struct ClipStagePlan
 {
   int       n_channels = 0, n_clips = 0;
   int       n_form[3] = { 0, 0, 0 };
@@ -577,27 +575,13 @@ struct ClipMixedPlan
   long long max_n44_form[3] = { 0, 0, 0 };
   bool      stereo_aligned = false;  // stereo and every resampled input 8-byte aligned (s16: 4-byte aligned)
   size_t    lds_bytes = 0;           // CLIP_FORM_GENERIC: the largest table + window of the group
-  bool      s16 = false;             // the plan of launch_clip_stage_mixed_s16
+  bool      s16 = false;             // the plan of launch_clip_stage_s16
 };
-ClipMixedPlan clip_stage_mixed_plan (ClipMixedSrc *src /* host */, int n_clips, int n_channels, int *list /* host */, bool s16 = false);
-hipError_t launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& plan, const ClipMixedSrc *src /* device */, const int *list /* device */,
-                                    float *dst, long long slice_values, long long margin_values, long long *range);
-/* Stage 0 straight from SIGNED 16-BIT PCM (little-endian, interleaved: the reference's native format, rawconverter.cc): the three launchers
- * above for clips whose values are int16.  The descriptors are the same structs -- their `data` / `in` fields hold the ADDRESS of the
- * clip's int16 values, n_values / n_in count values / frames as before -- and slices and ranges are bit for bit what the float launcher
- * writes for the decoded clips, float (v) * (1 / 32768) (launch_pcm_decode): the same kernels instantiated for the other input type, whose
- * loads convert and whose taps, sums, sinks, zeros and ranges are the same code.  A value is converted once: on its way into the LDS
- * window of the staged forms (the window stays float2, so the taps' LDS reads are what they were), or as the unstaged taps and the copy read
- * it.  Same forms, same plan rule (clip_stage_mixed_plan with s16 = true), same tiles per workgroup, same number of launches.
- * Alignment: a clip may begin at any EVEN address.  A 16-bit stereo frame is 4 bytes, so stereo_aligned here means that every resampled
- * input of the group is 4-byte aligned (one 4-byte load per frame); a group with an input that is not, or with another channel count,
- * takes the generic taps with 2-byte loads.  Nothing outside a clip's values is read. */
-hipError_t launch_clip_pad_s16 (hipStream_t st, const ClipSrc *src /* device */, int n_clips, float *dst, long long slice_values, long long margin_values,
-                                long long *range);
-hipError_t launch_clip_resample_pad_s16 (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src /* device */, int n_clips, long long max_n44,
-                                         bool stereo_aligned, float *dst, long long slice_values, long long margin_values, long long *range);
-hipError_t launch_clip_stage_mixed_s16 (hipStream_t st, const ClipMixedPlan& plan, const ClipMixedSrc *src /* device */, const int *list /* device */,
-                                        float *dst, long long slice_values, long long margin_values, long long *range);
+ClipStagePlan clip_stage_plan (ClipStageSrc *src /* host */, int n_clips, int n_channels, int *list /* host */, bool s16 = false);
+hipError_t launch_clip_stage (hipStream_t st, const ClipStagePlan& plan, const ClipStageSrc *src /* device */, const int *list /* device */,
+                              float *dst, long long slice_values, long long margin_values, long long *range);
+hipError_t launch_clip_stage_s16 (hipStream_t st, const ClipStagePlan& plan, const ClipStageSrc *src /* device */, const int *list /* device */,
+                                  float *dst, long long slice_values, long long margin_values, long long *range);
 }
 
 namespace awmk {

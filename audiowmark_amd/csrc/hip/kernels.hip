@@ -1324,7 +1324,7 @@ struct ResampleStore
   __device__ __forceinline__ void put2 (long long k, float2 v) { reinterpret_cast<float2 *> (out)[k] = v; }
 };
 
-/* What the taps READ (stage 0 of the clip groups straight from 16-bit PCM, kernels.hh launch_clip_pad_s16): the type of a value and of
+/* What the taps READ (stage 0 of the clip groups straight from 16-bit PCM, kernels.hh launch_clip_stage_s16): the type of a value and of
  * a stereo frame in global memory, and the conversion to the float the taps work on.  PcmF32, the default of every template below: the
  * values as they are.  PcmS16: signed 16 bit, the exact decode of pcm_decode_s16le_kernel, float (v) * (1 / 32768) with one rounded
  * product; a stereo frame is one 4-byte load.  A value is converted once, where it leaves global memory -- on its way into the LDS
@@ -1503,7 +1503,7 @@ resample_kernel (ResampleArgs a, int lds_floats, int in_span, int tiles_per_wg)
  * window read a two-way conflict (measured: 1.54 ms for an hour at 48 kHz against 0.96 ms for the way up, whose starts never skip).
  * There the threads are numbered by WINDOW START instead -- `step` slots per replica, the 13 starts that belong to no phase idle --
  * and neighbouring lanes read neighbouring words.  Going up, neighbouring phases share or succeed each other's start already. */
-/* The kernel's body, for K10 and for K10c (clip_resample_pad_phase_kernel): outputs 0 .. n_out - 1 of the stream whose n_in frames are at
+/* The kernel's body, for K10 and for stage 0 of the clip groups (clip_stage_phase_kernel): outputs 0 .. n_out - 1 of the stream whose n_in frames are at
  * `in`, tiles dealt to the workgroups by blockIdx.x, every result through the sink. */
 /* SPAN (K10s, launch_resample_span): the same for a run of outputs that begins at group `group0` of NP outputs of its stream -- output
  * group0 NP + k is local output k, which is what the sink is given -- with `in` holding the stream's frames in0 .. in0 + n_in - 1 and
@@ -4143,38 +4143,38 @@ clip_range_commit (unsigned long long first, unsigned long long last, unsigned l
     }
 }
 
-/* where a workgroup of clip_pad_kernel finds its clip and its slice (both uniform): clip and slice blockIdx.y of the launch's descriptors
- * (launch_clip_pad), or -- the copy form of K10x, which runs over the 44.1 kHz clips of a group alone -- slice list[blockIdx.y] and that
- * slice's descriptor */
-struct ClipPadEvery
-{
-  const ClipSrc *src;
-  __device__ __forceinline__ ClipSrc clip (unsigned int& slice) const
-  {
-    slice = blockIdx.y;
-    return src[blockIdx.y];
-  }
-};
-struct ClipPadListed
-{
-  const ClipMixedSrc *src;
-  const int          *list;
-  int                 n_channels;
-  __device__ __forceinline__ ClipSrc clip (unsigned int& slice) const
-  {
-    slice = (unsigned int) list[blockIdx.y];
-    const ClipMixedSrc c = src[slice];
-    return { c.in, c.n44 * n_channels, c.pad_start };
-  }
-};
+/* the copy form's view of a clip: its values (any input type) and where they go in the slice */
+struct ClipSrc { const float *data; long long n_values; long long pad_start; };
 
-/* kernels.hh launch_clip_pad: grid (parts, clips); slice_values % 4 == 0, 16-byte stores.  In: what the clip's values are (PcmS16: scalar
- * 2-byte loads, any even address) */
-template<class From, class In = PcmF32> __global__ void __launch_bounds__ (256)
-clip_pad_kernel (From from, float *dst, long long slice_values, long long margin_values, unsigned long long *range)
+/* the slice of a workgroup of stage 0 (uniform): entry blockIdx.y of its form's list -- or, without a list, blockIdx.y itself: every clip of
+ * the group has this form, and the workgroup is spared a load that its descriptor's load would have to wait for */
+__device__ __forceinline__ unsigned int
+clip_stage_slice (const int *__restrict__ list)
 {
-  unsigned int slice;
-  const ClipSrc c = from.clip (slice);
+  return list ? (unsigned int) list[blockIdx.y] : blockIdx.y;
+}
+
+/* A clip's descriptor (uniform), read as CONSTANT memory -- which it is for the kernel: the host wrote it before the launch.  The compiler
+ * then takes the addresses in it (the clip's values, its table) for addresses of global memory, as it takes a kernel argument's.  Read as
+ * plain global memory they could point anywhere: their loads would be flat ones, which keep their order with the LDS stores beside them,
+ * and the loop that stages the table (resample_slice_body) is then not unrolled -- 5 % of the stage at 32 kHz */
+__device__ __forceinline__ ClipStageSrc
+clip_stage_src (const ClipStageSrc *__restrict__ src, unsigned int slice)
+{
+  ClipStageSrc c;
+  __builtin_memcpy (&c, (const __attribute__ ((address_space (4))) ClipStageSrc *) (src + slice), sizeof c);
+  return c;
+}
+
+/* the copy form of stage 0 (kernels.hh launch_clip_stage): grid (parts, 44.1 kHz clips of the group); slice_values % 4 == 0, 16-byte
+ * stores.  In: what the clip's values are (PcmS16: scalar 2-byte loads, any even address) */
+template<class In = PcmF32> __global__ void __launch_bounds__ (256)
+clip_pad_kernel (const ClipStageSrc *__restrict__ src, const int *__restrict__ list, int n_channels, float *dst, long long slice_values,
+                 long long margin_values, unsigned long long *range)
+{
+  const unsigned int slice = clip_stage_slice (list);
+  const ClipStageSrc s = clip_stage_src (src, slice);
+  const ClipSrc c { s.in, s.n44 * n_channels, s.pad_start };
   const typename In::value *data = reinterpret_cast<const typename In::value *> (c.data);
   float4 *out = reinterpret_cast<float4 *> (dst + (long long) slice * slice_values);
   const long long slice0 = (long long) slice * slice_values;
@@ -4235,37 +4235,8 @@ awm_debug_clip_form_launches (long out[3])
     out[f] = g_clip_form_launches[f].load();
 }
 
-/* the launchers of stage 0, one copy for both input types: the float entry points instantiate what they always did */
-template<class In> static hipError_t
-launch_clip_pad_in (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, long long slice_values, long long margin_values, long long *range)
-{
-  if (n_clips <= 0 || slice_values <= 0)
-    return hipSuccess;
-  if (slice_values % 4 || margin_values < 0 || (reinterpret_cast<uintptr_t> (dst) & 15))
-    return hipErrorInvalidValue;
-  if (g_clip_poison)
-    if (hipError_t e = hipMemsetAsync (dst, 0xff, size_t (n_clips) * size_t (slice_values) * sizeof (float), st))
-      return e;
-  auto *r = reinterpret_cast<unsigned long long *> (range);
-  hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
-  g_clip_form_launches[CLIP_FORM_COPY]++;
-  hipLaunchKernelGGL ((clip_pad_kernel<ClipPadEvery, In>), dim3 (128, unsigned (n_clips)), dim3 (256), 0, st, ClipPadEvery { src }, dst, slice_values,
-                      margin_values, r);
-  return hipGetLastError();
-}
-hipError_t
-launch_clip_pad (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, long long slice_values, long long margin_values, long long *range)
-{
-  return launch_clip_pad_in<PcmF32> (st, src, n_clips, dst, slice_values, margin_values, range);
-}
-hipError_t
-launch_clip_pad_s16 (hipStream_t st, const ClipSrc *src, int n_clips, float *dst, long long slice_values, long long margin_values, long long *range)
-{
-  return launch_clip_pad_in<PcmS16> (st, src, n_clips, dst, slice_values, margin_values, range);
-}
-
-/* K10c (kernels.hh launch_clip_resample_pad): K10 into the padded slices.  The sink of the taps: output frame m of the clip goes to
- * pad_start + m C of its slice, and the thread keeps the first / last absolute index of the non-zero values it stored. */
+/* The resampling forms of stage 0 (kernels.hh launch_clip_stage): K10 into the padded slices.  The sink of the taps: output frame m of the
+ * clip goes to pad_start + m C of its slice, and the thread keeps the first / last absolute index of the non-zero values it stored. */
 struct ClipStore
 {
   float *out;                           // the clip's output 0 in its slice
@@ -4306,127 +4277,37 @@ clip_window_zeros (float *slice, long long pad_start, long long n_values, long l
     slice[i < n_front ? lo + i : end + (i - n_front)] = 0.f;
 }
 
-/* the generic form: resample_slice_body (table and, for stereo with 8-byte aligned inputs, the tile's window in LDS) on the clip as a
- * stream of its own; grid (workgroups of the longest clip, clips) */
+/* The geometry and the table come from the clip's descriptor: one uniform load per workgroup, the values stay in scalar registers.  Grid
+ * of both: (workgroups of the longest of the form's clips, the form's clips). */
+/* the generic form: resample_slice_body (table and, for stereo with aligned inputs, the tile's window in LDS) on the clip as a stream of its
+ * own */
 template<int CT, class In = PcmF32> __global__ void __launch_bounds__ (256)
-clip_resample_pad_kernel (ResampleArgs a, const ClipResampleSrc *src, float *dst, long long slice_values, long long margin_values,
-                          unsigned long long *range, int lds_floats, int in_span, int tiles_per_wg)
+clip_stage_kernel (const ClipStageSrc *__restrict__ src, const int *__restrict__ list, int n_channels, float *dst, long long slice_values,
+                   long long margin_values, unsigned long long *range, int tiles_per_wg)
 {
-  const ClipResampleSrc c = src[blockIdx.y];
-  const long long slice0 = (long long) blockIdx.y * slice_values;
-  ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
-  clip_window_zeros (dst + slice0, c.pad_start, c.n44 * a.n_channels, slice_values, margin_values);
-  const ResampleSlice s { c.in, c.n_in, 0, 0, c.n44, nullptr };
-  resample_slice_body<CT, In> (a, s, lds_floats, in_span, tiles_per_wg, sink);
-  clip_range_commit<4> (sink.first, sink.last, range + 2 * blockIdx.y);
-}
-
-/* the phase-per-thread form (resample_phase_body): a clip starts at output 0, so its tiles start on multiples of np */
-template<int NP, int STEP, int HL, int R, int J, class In = PcmF32> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
-clip_resample_pad_phase_kernel (const float *ctab, const ClipResampleSrc *src, float *dst, long long slice_values, long long margin_values,
-                                unsigned long long *range, int tiles_per_wg)
-{
-  const ClipResampleSrc c = src[blockIdx.y];
-  const long long slice0 = (long long) blockIdx.y * slice_values;
-  ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
-  clip_window_zeros (dst + slice0, c.pad_start, c.n44 * 2, slice_values, margin_values);
-  if ((long long) blockIdx.x * tiles_per_wg * (R * J * NP) < c.n44)                // (uniform: a shorter clip of the group)
-    resample_phase_body<NP, STEP, HL, R, J, false, In> (ctab, c.in, c.n_in, c.n44, tiles_per_wg, sink);
-  clip_range_commit<((STEP > NP ? STEP : NP) * R + 63) / 64> (sink.first, sink.last, range + 2 * blockIdx.y);
-}
-
-template<class In> static hipError_t
-launch_clip_resample_pad_in (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src, int n_clips, long long max_n44, bool stereo_aligned,
-                             float *dst, long long slice_values, long long margin_values, long long *range)
-{
-  if (n_clips <= 0 || slice_values <= 0)
-    return hipSuccess;
-  if (n_clips > 65535 || max_n44 < 0 || slice_values % 4 || margin_values < 0 || (reinterpret_cast<uintptr_t> (dst) & 15)
-      || a.hl < 1 || a.np < 1 || a.step < 1 || a.n_channels < 1 || !a.ctab)
-    return hipErrorInvalidValue;
-  if (g_clip_poison)
-    if (hipError_t e = hipMemsetAsync (dst, 0xff, size_t (n_clips) * size_t (slice_values) * sizeof (float), st))
-      return e;
-  auto *r = reinterpret_cast<unsigned long long *> (range);
-  hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
-  const bool stereo = a.n_channels == 2 && stereo_aligned;
-  // the forms and their tiles per workgroup as launch_resample / launch_resample_slices choose them: at least 4096 workgroups over all
-  // clips first, then up to 8 tiles per workgroup
-  if (g_resample_phase && stereo && a.np == 147 && a.step == 160 && a.hl == 18)
-    {
-      constexpr int NP = 147, STEP = 160, HL = 18, R = 2, J = 8;
-      const long long n_tiles = std::max<long long> (1, (max_n44 + R * J * NP - 1) / (R * J * NP));
-      const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_clips / 4096)));
-      const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg), unsigned (n_clips));
-      g_clip_form_launches[CLIP_FORM_PHASE]++;
-      hipLaunchKernelGGL ((clip_resample_pad_phase_kernel<NP, STEP, HL, R, J, In>), grid, dim3 ((STEP * R + 63) / 64 * 64), 0, st, a.ctab, src, dst,
-                          slice_values, margin_values, r, tiles_per_wg);
-      return hipGetLastError();
-    }
-  const long long n_tiles = std::max<long long> (1, (max_n44 + RS_TILE - 1) / RS_TILE);
-  const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_clips / 4096)));
-  const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg), unsigned (n_clips));
-  const int want = (a.np + 1) * (a.hl | 1);
-  const int lds_floats = want <= RS_MAX_TAB ? want : 0;
-  const long long span = ((long long) (RS_TILE - 1) * a.step) / a.np + 2 + 2LL * a.hl;
-  const bool stage = stereo && lds_floats > 0 && span <= 4096 && (long long) RS_TILE * a.step + a.np < (1LL << 31);
-  const int in_span = stage ? int (span) : 0;
-  const size_t lds_bytes = size_t ((lds_floats + 1) & ~1) * sizeof (float) + size_t (in_span) * sizeof (float2);
-  g_clip_form_launches[CLIP_FORM_GENERIC]++;
-  if (stereo)
-    hipLaunchKernelGGL ((clip_resample_pad_kernel<2, In>), grid, dim3 (256), lds_bytes, st, a, src, dst, slice_values, margin_values, r, lds_floats,
-                        in_span, tiles_per_wg);
-  else
-    hipLaunchKernelGGL ((clip_resample_pad_kernel<0, In>), grid, dim3 (256), lds_bytes, st, a, src, dst, slice_values, margin_values, r, lds_floats,
-                        in_span, tiles_per_wg);
-  return hipGetLastError();
-}
-hipError_t
-launch_clip_resample_pad (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src, int n_clips, long long max_n44, bool stereo_aligned,
-                          float *dst, long long slice_values, long long margin_values, long long *range)
-{
-  return launch_clip_resample_pad_in<PcmF32> (st, a, src, n_clips, max_n44, stereo_aligned, dst, slice_values, margin_values, range);
-}
-hipError_t
-launch_clip_resample_pad_s16 (hipStream_t st, const ResampleArgs& a, const ClipResampleSrc *src, int n_clips, long long max_n44, bool stereo_aligned,
-                              float *dst, long long slice_values, long long margin_values, long long *range)
-{
-  return launch_clip_resample_pad_in<PcmS16> (st, a, src, n_clips, max_n44, stereo_aligned, dst, slice_values, margin_values, range);
-}
-
-/* K10x (kernels.hh launch_clip_stage_mixed): K10c for a group of clips at several rates.  The three kernels are clip_resample_pad_kernel,
- * clip_resample_pad_phase_kernel and clip_pad_kernel with the geometry, the table and (phase, copy) the slice index read from the clip's
- * descriptor: one uniform load per workgroup, the values stay in scalar registers.  The taps are the same functions, and the copy form is
- * clip_pad_kernel<ClipPadListed>. */
-/* the generic form: grid (workgroups of the longest clip, clips of the group); another form's clip: nothing to do (uniform) */
-template<int CT, class In = PcmF32> __global__ void __launch_bounds__ (256)
-clip_stage_mixed_kernel (const ClipMixedSrc *__restrict__ src, int n_channels, float *dst, long long slice_values, long long margin_values,
-                         unsigned long long *range, int tiles_per_wg)
-{
-  const ClipMixedSrc c = src[blockIdx.y];
-  if (c.form != CLIP_FORM_GENERIC)
-    return;
+  const unsigned int slice = clip_stage_slice (list);
+  const ClipStageSrc c = clip_stage_src (src, slice);
   ResampleArgs a {};
   a.n_channels = n_channels;
   a.ctab = c.ctab;
   a.hl = c.hl;
   a.np = c.np;
   a.step = c.step;
-  const long long slice0 = (long long) blockIdx.y * slice_values;
+  const long long slice0 = (long long) slice * slice_values;
   ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
   clip_window_zeros (dst + slice0, c.pad_start, c.n44 * n_channels, slice_values, margin_values);
   const ResampleSlice s { c.in, c.n_in, 0, 0, c.n44, nullptr };
   resample_slice_body<CT, In> (a, s, c.lds_floats, c.in_span, tiles_per_wg, sink);
-  clip_range_commit<4> (sink.first, sink.last, range + 2 * blockIdx.y);
+  clip_range_commit<4> (sink.first, sink.last, range + 2 * slice);
 }
 
-/* the phase-per-thread form: grid (workgroups of the longest of these clips, these clips), slice = list[blockIdx.y] */
+/* the phase-per-thread form (resample_phase_body): a clip starts at output 0, so its tiles start on multiples of np */
 template<int NP, int STEP, int HL, int R, int J, class In = PcmF32> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
-clip_stage_mixed_phase_kernel (const ClipMixedSrc *__restrict__ src, const int *__restrict__ list, float *dst, long long slice_values,
-                               long long margin_values, unsigned long long *range, int tiles_per_wg)
+clip_stage_phase_kernel (const ClipStageSrc *__restrict__ src, const int *__restrict__ list, float *dst, long long slice_values,
+                         long long margin_values, unsigned long long *range, int tiles_per_wg)
 {
-  const int slice = list[blockIdx.y];
-  const ClipMixedSrc c = src[slice];
+  const unsigned int slice = clip_stage_slice (list);
+  const ClipStageSrc c = clip_stage_src (src, slice);
   const long long slice0 = (long long) slice * slice_values;
   ClipStore sink { dst + slice0 + c.pad_start, (unsigned long long) (slice0 + c.pad_start) };
   clip_window_zeros (dst + slice0, c.pad_start, c.n44 * 2, slice_values, margin_values);
@@ -4435,10 +4316,10 @@ clip_stage_mixed_phase_kernel (const ClipMixedSrc *__restrict__ src, const int *
   clip_range_commit<((STEP > NP ? STEP : NP) * R + 63) / 64> (sink.first, sink.last, range + 2 * slice);
 }
 
-ClipMixedPlan
-clip_stage_mixed_plan (ClipMixedSrc *src, int n_clips, int n_channels, int *list, bool s16)
+ClipStagePlan
+clip_stage_plan (ClipStageSrc *src, int n_clips, int n_channels, int *list, bool s16)
 {
-  ClipMixedPlan p;
+  ClipStagePlan p;
   p.n_channels = n_channels;
   p.n_clips = n_clips;
   p.s16 = s16;
@@ -4449,7 +4330,7 @@ clip_stage_mixed_plan (ClipMixedSrc *src, int n_clips, int n_channels, int *list
   p.stereo_aligned = n_channels == 2 && (bits & (s16 ? 3 : 7)) == 0;             // a stereo frame is one load
   for (int i = 0; i < n_clips; i++)
     {
-      ClipMixedSrc& c = src[i];
+      ClipStageSrc& c = src[i];
       c.lds_floats = c.in_span = 0;
       if (c.np <= 0)
         c.form = CLIP_FORM_COPY;
@@ -4457,7 +4338,7 @@ clip_stage_mixed_plan (ClipMixedSrc *src, int n_clips, int n_channels, int *list
         c.form = CLIP_FORM_PHASE;
       else
         {
-          // the table and the tile's window in LDS exactly as launch_clip_resample_pad sizes them for the clip's rate
+          // the table and the tile's window in LDS as launch_resample sizes them for the clip's rate
           c.form = CLIP_FORM_GENERIC;
           const int want = (c.np + 1) * (c.hl | 1);
           c.lds_floats = want <= RS_MAX_TAB ? want : 0;
@@ -4468,18 +4349,17 @@ clip_stage_mixed_plan (ClipMixedSrc *src, int n_clips, int n_channels, int *list
         }
       p.max_n44 = std::max (p.max_n44, c.n44);
       p.max_n44_form[c.form] = std::max (p.max_n44_form[c.form], c.n44);
-      if (c.form == CLIP_FORM_PHASE)
-        list[p.n_form[CLIP_FORM_PHASE]] = i;
-      else if (c.form == CLIP_FORM_COPY)
-        list[n_clips - 1 - p.n_form[CLIP_FORM_COPY]] = i;
       p.n_form[c.form]++;
     }
+  int at[3] = { 0, p.n_form[0], p.n_form[0] + p.n_form[1] };                     // the list: the slices form by form
+  for (int i = 0; i < n_clips; i++)
+    list[at[src[i].form]++] = i;
   return p;
 }
 
 template<class In> static hipError_t
-launch_clip_stage_mixed_in (hipStream_t st, const ClipMixedPlan& p, const ClipMixedSrc *src, const int *list, float *dst, long long slice_values,
-                            long long margin_values, long long *range)
+launch_clip_stage_in (hipStream_t st, const ClipStagePlan& p, const ClipStageSrc *src, const int *list, float *dst, long long slice_values,
+                      long long margin_values, long long *range)
 {
   const int n_clips = p.n_clips;
   if (n_clips <= 0 || slice_values <= 0)
@@ -4492,10 +4372,12 @@ launch_clip_stage_mixed_in (hipStream_t st, const ClipMixedPlan& p, const ClipMi
       return e;
   auto *r = reinterpret_cast<unsigned long long *> (range);
   hipLaunchKernelGGL (clip_range_init_kernel, dim3 (unsigned ((n_clips + 255) / 256)), dim3 (256), 0, st, r, n_clips);
-  // tiles per workgroup by launch_clip_resample_pad's rule over the GROUP: tiles of its longest clip x its clips / 4096, between 1 and 8;
-  // the grid of a form reaches as far as the longest clip of that form
+  // tiles per workgroup as launch_resample / launch_resample_slices choose them, over the GROUP: tiles of its longest clip x its clips /
+  // 4096, between 1 and 8; the grid of a form reaches as far as the longest clip of that form
   for (int f = 0; f < 3; f++)
     g_clip_form_launches[f] += p.n_form[f] ? 1 : 0;
+  // (a form that every clip of the group has runs without its list: clip_stage_slice)
+  auto list_of = [&] (int form) { return p.n_form[form] == n_clips ? nullptr : list + (form > 0 ? p.n_form[0] : 0) + (form > 1 ? p.n_form[1] : 0); };
   auto tiles = [&] (int tile, int form, int& tiles_per_wg) {
     const long long n_tiles = std::max<long long> (1, (p.max_n44 + tile - 1) / tile);
     tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_clips / 4096)));
@@ -4505,38 +4387,38 @@ launch_clip_stage_mixed_in (hipStream_t st, const ClipMixedPlan& p, const ClipMi
   if (p.n_form[CLIP_FORM_GENERIC])
     {
       int tiles_per_wg;
-      const dim3 grid (tiles (RS_TILE, CLIP_FORM_GENERIC, tiles_per_wg), unsigned (n_clips));
+      const dim3 grid (tiles (RS_TILE, CLIP_FORM_GENERIC, tiles_per_wg), unsigned (p.n_form[CLIP_FORM_GENERIC]));
       if (p.stereo_aligned)
-        hipLaunchKernelGGL ((clip_stage_mixed_kernel<2, In>), grid, dim3 (256), p.lds_bytes, st, src, p.n_channels, dst, slice_values, margin_values, r,
-                            tiles_per_wg);
+        hipLaunchKernelGGL ((clip_stage_kernel<2, In>), grid, dim3 (256), p.lds_bytes, st, src, list_of (CLIP_FORM_GENERIC), p.n_channels, dst,
+                            slice_values, margin_values, r, tiles_per_wg);
       else
-        hipLaunchKernelGGL ((clip_stage_mixed_kernel<0, In>), grid, dim3 (256), p.lds_bytes, st, src, p.n_channels, dst, slice_values, margin_values, r,
-                            tiles_per_wg);
+        hipLaunchKernelGGL ((clip_stage_kernel<0, In>), grid, dim3 (256), p.lds_bytes, st, src, list_of (CLIP_FORM_GENERIC), p.n_channels, dst,
+                            slice_values, margin_values, r, tiles_per_wg);
     }
   if (p.n_form[CLIP_FORM_PHASE])
     {
       constexpr int NP = 147, STEP = 160, HL = 18, R = 2, J = 8;
       int tiles_per_wg;
       const dim3 grid (tiles (R * J * NP, CLIP_FORM_PHASE, tiles_per_wg), unsigned (p.n_form[CLIP_FORM_PHASE]));
-      hipLaunchKernelGGL ((clip_stage_mixed_phase_kernel<NP, STEP, HL, R, J, In>), grid, dim3 ((STEP * R + 63) / 64 * 64), 0, st, src, list, dst,
-                          slice_values, margin_values, r, tiles_per_wg);
+      hipLaunchKernelGGL ((clip_stage_phase_kernel<NP, STEP, HL, R, J, In>), grid, dim3 ((STEP * R + 63) / 64 * 64), 0, st, src,
+                          list_of (CLIP_FORM_PHASE), dst, slice_values, margin_values, r, tiles_per_wg);
     }
   if (p.n_form[CLIP_FORM_COPY])
-    hipLaunchKernelGGL ((clip_pad_kernel<ClipPadListed, In>), dim3 (128, unsigned (p.n_form[CLIP_FORM_COPY])), dim3 (256), 0, st,
-                        ClipPadListed { src, list + (n_clips - p.n_form[CLIP_FORM_COPY]), p.n_channels }, dst, slice_values, margin_values, r);
+    hipLaunchKernelGGL ((clip_pad_kernel<In>), dim3 (128, unsigned (p.n_form[CLIP_FORM_COPY])), dim3 (256), 0, st, src, list_of (CLIP_FORM_COPY),
+                        p.n_channels, dst, slice_values, margin_values, r);
   return hipGetLastError();
 }
 hipError_t
-launch_clip_stage_mixed (hipStream_t st, const ClipMixedPlan& p, const ClipMixedSrc *src, const int *list, float *dst, long long slice_values,
-                         long long margin_values, long long *range)
+launch_clip_stage (hipStream_t st, const ClipStagePlan& p, const ClipStageSrc *src, const int *list, float *dst, long long slice_values,
+                   long long margin_values, long long *range)
 {
-  return launch_clip_stage_mixed_in<PcmF32> (st, p, src, list, dst, slice_values, margin_values, range);
+  return launch_clip_stage_in<PcmF32> (st, p, src, list, dst, slice_values, margin_values, range);
 }
 hipError_t
-launch_clip_stage_mixed_s16 (hipStream_t st, const ClipMixedPlan& p, const ClipMixedSrc *src, const int *list, float *dst, long long slice_values,
-                             long long margin_values, long long *range)
+launch_clip_stage_s16 (hipStream_t st, const ClipStagePlan& p, const ClipStageSrc *src, const int *list, float *dst, long long slice_values,
+                       long long margin_values, long long *range)
 {
-  return launch_clip_stage_mixed_in<PcmS16> (st, p, src, list, dst, slice_values, margin_values, range);
+  return launch_clip_stage_in<PcmS16> (st, p, src, list, dst, slice_values, margin_values, range);
 }
 
 /* kernels.hh launch_segment_copy: grid (runs, segments).  A segment that starts r samples into its first frame is 8 r bytes off the

@@ -4000,6 +4000,35 @@ awm_get_watermark_keys_d (awm_ctx *ctx, const uint8_t *keys, int n_keys, const f
   return fill_patterns_keys (rs, list, max_out, out, key_of_pattern);
 }
 
+/* The tail of every batch entry point: the key list -- `key` for all clips, or (keys set) one key per clip --, the batch and its patterns.
+ * rates (may be null): the clips are at other rates than 44.1 kHz */
+static int
+get_batch_tail (awm_ctx *ctx, const uint8_t key[16], const uint8_t *keys, const std::vector<DeviceWav>& clips, const ClipRates *rates, int n_threads,
+                size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  if (clips.empty())
+    return 0;
+  std::vector<Key> clip_keys;
+  if (keys)
+    clip_keys = key_list_from (keys, int (clips.size()));
+  std::vector<ResultSet> sets;
+  if (int rc = get_watermark_batch_device (ctx, keys ? std::vector<Key> {} : std::vector<Key> { capi_key (key) }, clips, sets, n_threads,
+                                           keys ? &clip_keys : nullptr, rates))
+    return rc;
+  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
+  return 0;
+}
+
+/* the clips of a call, clip i at sample_rates[i] (null: every clip at 44.1 kHz); pcm_d null: 16-bit clips, whose values the caller fills in */
+static std::vector<DeviceWav>
+make_clips (size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels, const int *sample_rates)
+{
+  std::vector<DeviceWav> clips;
+  for (size_t i = 0; i < n_clips; i++)
+    clips.push_back (make_wav_rate (pcm_d ? pcm_d[i] : nullptr, n_frames[i], n_channels, sample_rates ? sample_rates[i] : int (Params::mark_sample_rate)));
+  return clips;
+}
+
 int
 awm_get_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
                            int n_channels, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
@@ -4010,14 +4039,7 @@ awm_get_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, 
       set_error ("awm_get_watermark_batch_d: bad argument");
       return AWM_ERR_ARG;
     }
-  std::vector<DeviceWav> clips;
-  for (size_t i = 0; i < n_clips; i++)
-    clips.push_back (make_wav (pcm_d[i], n_frames[i], n_channels));
-  std::vector<ResultSet> sets;
-  if (int rc = get_watermark_batch_device (ctx, { capi_key (key) }, clips, sets, n_threads))
-    return rc;
-  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
-  return 0;
+  return get_batch_tail (ctx, key, nullptr, make_clips (n_clips, pcm_d, n_frames, n_channels, nullptr), nullptr, n_threads, max_out_per_clip, out, n_out);
 }
 
 int
@@ -4030,38 +4052,11 @@ awm_get_watermark_batch_keys_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clip
       set_error ("awm_get_watermark_batch_keys_d: bad argument");
       return AWM_ERR_ARG;
     }
-  std::vector<DeviceWav> clips;
-  for (size_t i = 0; i < n_clips; i++)
-    clips.push_back (make_wav (pcm_d[i], n_frames[i], n_channels));
-  const std::vector<Key> clip_keys = key_list_from (keys, int (n_clips));
-  std::vector<ResultSet> sets;
-  if (int rc = get_watermark_batch_device (ctx, {}, clips, sets, n_threads, &clip_keys))
-    return rc;
-  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
-  return 0;
+  return get_batch_tail (ctx, nullptr, keys, make_clips (n_clips, pcm_d, n_frames, n_channels, nullptr), nullptr, n_threads, max_out_per_clip, out, n_out);
 }
 
-/* `get` at another sample rate: the rate's converter and every clip's length at 44.1 kHz.  AWM_ERR_ARG (message set) for what
- * awm_resample_frames answers with 0 */
-static int
-clip_rates (awm_ctx *ctx, int sample_rate, size_t n_clips, const size_t *n_frames, ClipRates& rates)
-{
-  const RateConverter conv = rate_converter (ctx, sample_rate, Params::mark_sample_rate);
-  if (!conv.ok())
-    {
-      set_error (string_printf ("resampling from old_rate=%d to new_rate=%d not implemented", sample_rate, int (Params::mark_sample_rate)));
-      return AWM_ERR_ARG;
-    }
-  rates.sample_rate.assign (n_clips, sample_rate);
-  rates.table.assign (n_clips, conv.fixed);
-  rates.n44.clear();
-  for (size_t i = 0; i < n_clips; i++)
-    rates.n44.push_back (conv.stream_frames (n_frames[i]));
-  return 0;
-}
-
-/* ... with a rate per clip.  A clip's way through the batch and its length at 44.1 kHz, without a context (awm_get_batch_rates_plan): false
- * for a rate that is not positive or that neither resampler class takes */
+/* A clip's way through a batch with a rate per clip and its length at 44.1 kHz, without a context (awm_get_batch_rates_plan): false for a
+ * rate that is not positive or that neither resampler class takes */
 enum { RATES_PATH_GROUP = 0, RATES_PATH_LANE_FIXED = 1, RATES_PATH_LANE_VAR = 2, RATES_PATH_EMPTY = 3 };
 static bool
 clip_rate_plan (size_t n_frames, int sample_rate, int& path, size_t& n44)
@@ -4114,7 +4109,9 @@ check_clip_rates (const char *who, size_t n_clips, const size_t *n_frames, const
   return 0;
 }
 
-/* the converters of the (checked) rates of a call, one table per distinct rate from the context, and every clip's length at 44.1 kHz */
+/* `get` at other sample rates: the converters of a call's rates, one table per distinct rate from the context, and every clip's length at
+ * 44.1 kHz.  A call at ONE rate hands in n_clips equal rates.  AWM_ERR_ARG (message set) for a rate that awm_resample_frames answers with 0
+ * -- the calls with a rate per clip have refused it before (check_clip_rates), naming the clip */
 static int
 clip_rates_each (awm_ctx *ctx, const int *sample_rates, size_t n_clips, const size_t *n_frames, ClipRates& rates)
 {
@@ -4133,7 +4130,10 @@ clip_rates_each (awm_ctx *ctx, const int *sample_rates, size_t n_clips, const si
       if (it == convs.end())
         it = convs.emplace (sample_rates[i], rate_converter (ctx, sample_rates[i], Params::mark_sample_rate)).first;
       if (!it->second.ok())
-        return AWM_ERR_ARG;
+        {
+          set_error (string_printf ("resampling from old_rate=%d to new_rate=%d not implemented", sample_rates[i], int (Params::mark_sample_rate)));
+          return AWM_ERR_ARG;
+        }
       rates.table[i] = it->second.fixed;
       rates.n44[i] = it->second.stream_frames (n_frames[i]);
     }
@@ -4151,58 +4151,18 @@ rates_all_equal (size_t n_clips, const int *sample_rates)
   return true;
 }
 
-static int
-get_watermark_batch_rates (awm_ctx *ctx, const char *who, const uint8_t key[16], const uint8_t *keys, size_t n_clips, const float *const *pcm_d,
-                           const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out,
-                           int *n_out)
-{
-  if (!n_clips)
-    return 0;
-  if (!pcm_d || !n_frames || !n_out || (max_out_per_clip && !out) || (!key && !keys) || n_channels < 1)
-    {
-      set_error (string_printf ("%s: bad argument", who));
-      return AWM_ERR_ARG;
-    }
-  if (int rc = check_clip_rates (who, n_clips, n_frames, sample_rates))
-    return rc;
-  ClipRates rates;
-  if (int rc = clip_rates_each (ctx, sample_rates, n_clips, n_frames, rates))
-    return rc;
-  std::vector<DeviceWav> clips;
-  for (size_t i = 0; i < n_clips; i++)
-    clips.push_back (make_wav_rate (pcm_d[i], n_frames[i], n_channels, sample_rates[i]));
-  std::vector<Key> clip_keys;
-  if (keys)
-    clip_keys = key_list_from (keys, int (n_clips));
-  std::vector<ResultSet> sets;
-  if (int rc = get_watermark_batch_device (ctx, keys ? std::vector<Key> {} : std::vector<Key> { capi_key (key) }, clips, sets, n_threads,
-                                           keys ? &clip_keys : nullptr, &rates))
-    return rc;
-  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
-  return 0;
-}
-
+/* the batch at ONE other rate (44.1 kHz went to the plain call) */
 static int
 get_watermark_batch_rate (awm_ctx *ctx, const uint8_t key[16], const uint8_t *keys, size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
                           int n_channels, int sample_rate, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
 {
+  // (a call without clips is still refused a rate that no resampler takes: one clip of no frames stands in)
+  const size_t none = 0;
+  const std::vector<int> each (std::max<size_t> (n_clips, 1), sample_rate);
   ClipRates rates;
-  if (int rc = clip_rates (ctx, sample_rate, n_clips, n_frames, rates))
+  if (int rc = clip_rates_each (ctx, each.data(), each.size(), n_clips ? n_frames : &none, rates))
     return rc;
-  if (!n_clips)
-    return 0;
-  std::vector<DeviceWav> clips;
-  for (size_t i = 0; i < n_clips; i++)
-    clips.push_back (make_wav_rate (pcm_d[i], n_frames[i], n_channels, sample_rate));
-  std::vector<Key> clip_keys;
-  if (keys)
-    clip_keys = key_list_from (keys, int (n_clips));
-  std::vector<ResultSet> sets;
-  if (int rc = get_watermark_batch_device (ctx, keys ? std::vector<Key> {} : std::vector<Key> { capi_key (key) }, clips, sets, n_threads,
-                                           keys ? &clip_keys : nullptr, &rates))
-    return rc;
-  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
-  return 0;
+  return get_batch_tail (ctx, key, keys, make_clips (n_clips, pcm_d, n_frames, n_channels, each.data()), &rates, n_threads, max_out_per_clip, out, n_out);
 }
 
 int
@@ -4218,7 +4178,7 @@ awm_get_watermark_rate_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_
       return AWM_ERR_ARG;
     }
   ClipRates rates;
-  if (int rc = clip_rates (ctx, sample_rate, 1, &n_frames, rates))
+  if (int rc = clip_rates_each (ctx, &sample_rate, 1, &n_frames, rates))
     return rc;
   DeviceWav wav44;
   if (int rc = resample_to_mark_rate (ctx, ctx, rates, 0, make_wav_rate (pcm_d, n_frames, n_channels, sample_rate), wav44))
@@ -4271,69 +4231,26 @@ awm_debug_clip_stage_d (awm_ctx *ctx, size_t n_clips, const float *const *pcm_d,
       set_error ("awm_debug_clip_stage_d: bad argument");
       return AWM_ERR_ARG;
     }
+  const std::vector<int> each (n_clips, sample_rate);
   ClipRates rates;
   const bool at_rate = sample_rate != Params::mark_sample_rate;
   if (at_rate)
-    if (int rc = clip_rates (ctx, sample_rate, n_clips, n_frames, rates))
+    if (int rc = clip_rates_each (ctx, each.data(), n_clips, n_frames, rates))
       return rc;
-  std::vector<DeviceWav> clips;
-  for (size_t i = 0; i < n_clips; i++)
-    clips.push_back (make_wav_rate (pcm_d[i], n_frames[i], n_channels, sample_rate));
-  return clip_stage_device (ctx, clips, at_rate ? &rates : nullptr, slices_d, range_out);
+  return clip_stage_device (ctx, make_clips (n_clips, pcm_d, n_frames, n_channels, each.data()), at_rate ? &rates : nullptr, slices_d, range_out);
 }
 
-int
-awm_get_watermark_batch_rates_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
-                                 int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+/* the refusals, the converters and the float clips of a call with a rate per clip */
+static int
+clips_rates (awm_ctx *ctx, const char *who, size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels, const int *sample_rates,
+             ClipRates& rates, std::vector<DeviceWav>& clips)
 {
-  if (rates_all_equal (n_clips, sample_rates))           // IS the one-rate function (which hands 44.1 kHz on), before anything else happens
-    return awm_get_watermark_batch_rate_d (ctx, key, n_clips, pcm_d, n_frames, n_channels, sample_rates[0], n_threads, max_out_per_clip, out, n_out);
-  AWM_ENTER (ctx);
-  if (n_clips && !key)
-    {
-      set_error ("awm_get_watermark_batch_rates_d: bad argument");
-      return AWM_ERR_ARG;
-    }
-  return get_watermark_batch_rates (ctx, "awm_get_watermark_batch_rates_d", key, nullptr, n_clips, pcm_d, n_frames, n_channels, sample_rates, n_threads,
-                                    max_out_per_clip, out, n_out);
-}
-
-int
-awm_get_watermark_batch_keys_rates_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
-                                      int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
-{
-  if (rates_all_equal (n_clips, sample_rates))
-    return awm_get_watermark_batch_keys_rate_d (ctx, keys, n_clips, pcm_d, n_frames, n_channels, sample_rates[0], n_threads, max_out_per_clip, out,
-                                                n_out);
-  AWM_ENTER (ctx);
-  if (n_clips && !keys)
-    {
-      set_error ("awm_get_watermark_batch_keys_rates_d: bad argument");
-      return AWM_ERR_ARG;
-    }
-  return get_watermark_batch_rates (ctx, "awm_get_watermark_batch_keys_rates_d", nullptr, keys, n_clips, pcm_d, n_frames, n_channels, sample_rates,
-                                    n_threads, max_out_per_clip, out, n_out);
-}
-
-int
-awm_debug_clip_stage_rates_d (awm_ctx *ctx, size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels, const int *sample_rates,
-                              float *slices_d, long long *range_out)
-{
-  AWM_ENTER (ctx);
-  if (!n_clips || !pcm_d || !n_frames || n_channels < 1)
-    {
-      set_error ("awm_debug_clip_stage_rates_d: bad argument");
-      return AWM_ERR_ARG;
-    }
-  if (int rc = check_clip_rates ("awm_debug_clip_stage_rates_d", n_clips, n_frames, sample_rates))
+  if (int rc = check_clip_rates (who, n_clips, n_frames, sample_rates))
     return rc;
-  ClipRates rates;
   if (int rc = clip_rates_each (ctx, sample_rates, n_clips, n_frames, rates))
     return rc;
-  std::vector<DeviceWav> clips;
-  for (size_t i = 0; i < n_clips; i++)
-    clips.push_back (make_wav_rate (pcm_d[i], n_frames[i], n_channels, sample_rates[i]));
-  return clip_stage_device (ctx, clips, &rates, slices_d, range_out);
+  clips = make_clips (n_clips, pcm_d, n_frames, n_channels, sample_rates);
+  return 0;
 }
 
 /* The batches on 16-bit clips (awm_get_watermark_batch_rates_s16_d and its twins): the refusals, the converters and the clips of a call.
@@ -4359,40 +4276,81 @@ clips_s16 (awm_ctx *ctx, const char *who, size_t n_clips, const int16_t *const *
       }
   if (int rc = clip_rates_each (ctx, sample_rates, n_clips, n_frames, rates))
     return rc;
+  clips = make_clips (n_clips, nullptr, n_frames, n_channels, sample_rates);
   for (size_t i = 0; i < n_clips; i++)
-    {
-      DeviceWav w = make_wav_rate (nullptr, n_frames[i], n_channels, sample_rates[i]);
-      w.pcm16 = pcm_d[i];
-      clips.push_back (w);
-    }
+    clips[i].pcm16 = pcm_d[i];
   return 0;
 }
 
+/* the batch with a rate per clip, float (pcm_d) or 16-bit (pcm16_d) clips, after the entry point's own checks */
 static int
-get_watermark_batch_s16 (awm_ctx *ctx, const char *who, const uint8_t key[16], const uint8_t *keys, size_t n_clips, const int16_t *const *pcm_d,
-                         const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out,
-                         int *n_out)
+get_watermark_batch_each (awm_ctx *ctx, const char *who, const uint8_t key[16], const uint8_t *keys, size_t n_clips, const float *const *pcm_d,
+                          const int16_t *const *pcm16_d, const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads,
+                          size_t max_out_per_clip, awm_pattern *out, int *n_out)
 {
   if (!n_clips)
     return 0;
-  if (!pcm_d || !n_frames || !n_out || (max_out_per_clip && !out) || (!key && !keys) || n_channels < 1)
+  if ((!pcm_d && !pcm16_d) || !n_frames || !n_out || (max_out_per_clip && !out) || (!key && !keys) || n_channels < 1)
     {
       set_error (string_printf ("%s: bad argument", who));
       return AWM_ERR_ARG;
     }
   ClipRates rates;
   std::vector<DeviceWav> clips;
-  if (int rc = clips_s16 (ctx, who, n_clips, pcm_d, n_frames, n_channels, sample_rates, rates, clips))
+  if (int rc = pcm16_d ? clips_s16 (ctx, who, n_clips, pcm16_d, n_frames, n_channels, sample_rates, rates, clips)
+                       : clips_rates (ctx, who, n_clips, pcm_d, n_frames, n_channels, sample_rates, rates, clips))
     return rc;
-  std::vector<Key> clip_keys;
-  if (keys)
-    clip_keys = key_list_from (keys, int (n_clips));
-  std::vector<ResultSet> sets;
-  if (int rc = get_watermark_batch_device (ctx, keys ? std::vector<Key> {} : std::vector<Key> { capi_key (key) }, clips, sets, n_threads,
-                                           keys ? &clip_keys : nullptr, &rates))
+  return get_batch_tail (ctx, key, keys, clips, &rates, n_threads, max_out_per_clip, out, n_out);
+}
+
+int
+awm_get_watermark_batch_rates_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
+                                 int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  if (rates_all_equal (n_clips, sample_rates))           // IS the one-rate function (which hands 44.1 kHz on), before anything else happens
+    return awm_get_watermark_batch_rate_d (ctx, key, n_clips, pcm_d, n_frames, n_channels, sample_rates[0], n_threads, max_out_per_clip, out, n_out);
+  AWM_ENTER (ctx);
+  if (n_clips && !key)
+    {
+      set_error ("awm_get_watermark_batch_rates_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  return get_watermark_batch_each (ctx, "awm_get_watermark_batch_rates_d", key, nullptr, n_clips, pcm_d, nullptr, n_frames, n_channels, sample_rates,
+                                   n_threads, max_out_per_clip, out, n_out);
+}
+
+int
+awm_get_watermark_batch_keys_rates_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
+                                      int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
+{
+  if (rates_all_equal (n_clips, sample_rates))
+    return awm_get_watermark_batch_keys_rate_d (ctx, keys, n_clips, pcm_d, n_frames, n_channels, sample_rates[0], n_threads, max_out_per_clip, out,
+                                                n_out);
+  AWM_ENTER (ctx);
+  if (n_clips && !keys)
+    {
+      set_error ("awm_get_watermark_batch_keys_rates_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  return get_watermark_batch_each (ctx, "awm_get_watermark_batch_keys_rates_d", nullptr, keys, n_clips, pcm_d, nullptr, n_frames, n_channels,
+                                   sample_rates, n_threads, max_out_per_clip, out, n_out);
+}
+
+int
+awm_debug_clip_stage_rates_d (awm_ctx *ctx, size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels, const int *sample_rates,
+                              float *slices_d, long long *range_out)
+{
+  AWM_ENTER (ctx);
+  if (!n_clips || !pcm_d || !n_frames || n_channels < 1)
+    {
+      set_error ("awm_debug_clip_stage_rates_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  ClipRates rates;
+  std::vector<DeviceWav> clips;
+  if (int rc = clips_rates (ctx, "awm_debug_clip_stage_rates_d", n_clips, pcm_d, n_frames, n_channels, sample_rates, rates, clips))
     return rc;
-  fill_batch_patterns (sets, max_out_per_clip, out, n_out);
-  return 0;
+  return clip_stage_device (ctx, clips, &rates, slices_d, range_out);
 }
 
 int
@@ -4400,8 +4358,8 @@ awm_get_watermark_batch_rates_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t
                                      int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
 {
   AWM_ENTER (ctx);
-  return get_watermark_batch_s16 (ctx, "awm_get_watermark_batch_rates_s16_d", key, nullptr, n_clips, pcm_d, n_frames, n_channels, sample_rates, n_threads,
-                                  max_out_per_clip, out, n_out);
+  return get_watermark_batch_each (ctx, "awm_get_watermark_batch_rates_s16_d", key, nullptr, n_clips, nullptr, pcm_d, n_frames, n_channels, sample_rates,
+                                   n_threads, max_out_per_clip, out, n_out);
 }
 
 int
@@ -4409,8 +4367,8 @@ awm_get_watermark_batch_keys_rates_s16_d (awm_ctx *ctx, const uint8_t *keys, siz
                                           int n_channels, const int *sample_rates, int n_threads, size_t max_out_per_clip, awm_pattern *out, int *n_out)
 {
   AWM_ENTER (ctx);
-  return get_watermark_batch_s16 (ctx, "awm_get_watermark_batch_keys_rates_s16_d", nullptr, keys, n_clips, pcm_d, n_frames, n_channels, sample_rates,
-                                  n_threads, max_out_per_clip, out, n_out);
+  return get_watermark_batch_each (ctx, "awm_get_watermark_batch_keys_rates_s16_d", nullptr, keys, n_clips, nullptr, pcm_d, n_frames, n_channels,
+                                   sample_rates, n_threads, max_out_per_clip, out, n_out);
 }
 
 int

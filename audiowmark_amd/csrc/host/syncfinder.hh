@@ -90,7 +90,7 @@ public:
     // batched clip search: `wav` is a row of equal slices, candidate c lives in slice cand_slice[c] (its index is relative to it)
     std::vector<int> cand_slice;
     size_t           slice_frames = 0;      // 0: no slices
-    const long long *slice_range = nullptr; // device, [slices][2]: non-silent value range of every slice (kernels.hh launch_clip_pad)
+    const long long *slice_range = nullptr; // device, [slices][2]: non-silent value range of every slice (kernels.hh launch_clip_stage)
   };
   int search_launch (const Key& key, const DeviceWav& wav, Mode mode, SearchJob& job, bool db_ready = false);     // = approx_launch + select_refine
   int search_finish (SearchJob& job, std::vector<Score>& out);
@@ -101,7 +101,7 @@ public:
   int select_refine (SearchJob& job);
 
 
-  /* The CLIP search for a GROUP of padded clips that lie side by side in one buffer (equal slices, kernels.hh launch_clip_pad), stage by
+  /* The CLIP search for a GROUP of padded clips that lie side by side in one buffer (equal slices, kernels.hh launch_clip_stage), stage by
    * stage with ONE launch per kernel and ONE wait per stage for the whole group -- a 30 s clip alone keeps the GPU busy for a
    * fraction of the time its ~20 launches and 3 round trips take.  Results per slice are those of search (key, slice, Mode::CLIP).
    * A slice whose selection needs the rare sequential path (more peaks above the threshold than the head list holds, a tie at the

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <map>
+#include <optional>
 
 namespace awm {
 int g_key_tables_on_device = 1;         // awm_debug_set_key_tables_on_device (capi_kernels.cc): batches with one key per clip build their tables on the device
@@ -44,7 +45,7 @@ int
 block_soft_bits_dev (awm_ctx *ctx, WorkLane *lane, KeyTables *kt, const DeviceWav& wav, const std::vector<size_t>& index,
                      std::vector<int>& slot_of, std::vector<char>& ok, const long long *slice_range, size_t slice_frames)
 {
-  // slice_range (a row of padded clips, kernels.hh launch_clip_pad): frames in the padding are not transformed, their dB values
+  // slice_range (a row of padded clips, kernels.hh launch_clip_stage): frames in the padding are not transformed, their dB values
   // are written directly (a frame of zeros transforms to exactly -96 dB per band)
   const size_t count = mark_block_frame_count();
   const int n_bits = mark_data_frame_count() / params().frames_per_bit;
@@ -1723,7 +1724,7 @@ clip_key_tables_check (awm_ctx *ctx, const uint8_t *keys, size_t n_keys, long lo
   return 0;
 }
 
-/* frames of zeros written on either side of a clip in its padded slice (kernels.hh launch_clip_pad: the consumers read at most
+/* frames of zeros written on either side of a clip in its padded slice (kernels.hh launch_clip_stage: the consumers read at most
  * 1024 + 8 * 64 + read-ahead frames beyond the clip) */
 constexpr int CLIP_PAD_MARGIN = 2048;
 /* (measurement knob) another margin, in frames; one slice or more = whole slices are written, as before this margin existed */
@@ -1767,10 +1768,9 @@ resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, siz
 }
 
 /* Stage 0 of a group: the padded copies of clips[which[0 .. gn)] (reference wmget.cc:830-867, START position: data + padding cover one long
- * block) in `slices` and the non-silent range of every slice, on the lane's stream.  Three forms: at 44.1 kHz -- no `rates`, or every clip of
- * the group at 44.1 kHz -- a copy (launch_clip_pad); a group whose clips share one other rate is resampled straight into its slices (K10c,
- * launch_clip_resample_pad); a group whose clips do NOT share one rate goes through K10x (launch_clip_stage_mixed), every clip with the
- * table of its own rate and the 44.1 kHz clips copied.  Every clip's rate has a table or is 44.1 kHz (ClipRates::groupable). */
+ * block) in `slices` and the non-silent range of every slice, on the lane's stream: one descriptor per clip, one plan, one launcher
+ * (kernels.hh launch_clip_stage).  A clip at 44.1 kHz -- no `rates`, or its rate says so -- is copied, every other clip is resampled into its
+ * slice with the table of its own rate.  Every clip's rate has a table or is 44.1 kHz (ClipRates::groupable). */
 struct ClipStage0
 {
   std::vector<long long> pad_start, n_values;       // per clip, in values at 44.1 kHz
@@ -1784,100 +1784,47 @@ clip_stage0_launch (awm_ctx *ctx, WorkLane *lane, const std::vector<DeviceWav>& 
   hipStream_t st = lane->stream;
   const int C = clips[which[0]].n_channels;
   const size_t n = slice_values / 3;
-  // 16-bit clips (all clips of a call or none): the same three forms through the launchers that read int16, under scopes of their own; the
-  // descriptors carry the address of the clip's values whatever their type (kernels.hh launch_clip_pad_s16)
+  // 16-bit clips (all clips of a call or none): the launcher that reads int16, under scopes of their own; the descriptors carry the address
+  // of the clip's values whatever their type
   const bool s16 = clips[which[0]].pcm16 != nullptr;
-  auto values_of = [s16] (const DeviceWav& wav) { return s16 ? reinterpret_cast<const float *> (wav.pcm16) : wav.data; };
-  const double sample_bytes_in = s16 ? 2.0 : 4.0;
-  // which form: one rate for the whole group (44.1 kHz: the copy), or a rate per clip
-  bool one_rate = true;
-  if (rates)
-    for (size_t i = 1; i < gn; i++)
-      one_rate = one_rate && rates->sample_rate[which[i]] == rates->sample_rate[which[0]];
-  const bool copy = !rates || (one_rate && rates->at_mark_rate (which[0]));
-  const size_t desc_bytes = copy ? gn * sizeof (awmk::ClipSrc) : one_rate ? gn * sizeof (awmk::ClipResampleSrc)
-                                 : (gn * (sizeof (awmk::ClipMixedSrc) + sizeof (int)) + 7) / 8 * 8;      // (K10x: the descriptors, then the list)
+  const size_t desc_bytes = (gn * (sizeof (awmk::ClipStageSrc) + sizeof (int)) + 7) / 8 * 8;      // (the descriptors, then the list)
   if (int rc = lane->pin_group.reserve (desc_bytes)) return rc;
   if (int rc = lane->ws_group.reserve (desc_bytes + gn * 2 * sizeof (long long))) return rc;
   AWM_HIP_CHECK (stream_wait (st));                                             // (the previous group's descriptors are consumed)
   s0.pad_start.resize (gn);
   s0.n_values.resize (gn);
-  for (size_t i = 0; i < gn; i++)
-    {
-      s0.n_values[i] = (long long) ((rates ? rates->n44[which[i]] : clips[which[i]].n_frames) * C);
-      s0.pad_start[i] = (long long) (n + (n - s0.n_values[i]));
-    }
   s0.d_range = reinterpret_cast<long long *> (lane->ws_group.as<char>() + desc_bytes);
   // (only CLIP_PAD_MARGIN frames of zeros on either side of a clip are written: nothing further out is read -- kernels.hh)
   s0.margin_values = (long long) std::max (g_clip_pad_margin, CLIP_PAD_MARGIN) * C;
-  if (copy)
-    {
-      auto *desc = lane->pin_group.as<awmk::ClipSrc>();
-      for (size_t i = 0; i < gn; i++)
-        desc[i] = { values_of (clips[which[i]]), s0.n_values[i], s0.pad_start[i] };
-      auto *d_desc = lane->ws_group.as<awmk::ClipSrc>();
-      AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
-      if (s16)
-        {
-          double values = 0;
-          for (size_t i = 0; i < gn; i++)
-            values += double (s0.n_values[i]);
-          ProfScope ps (ctx, PROF_CLIP_PAD_S16, values * (2.0 + 4.0), st);      // every value read as int16 and written as float once
-          AWM_HIP_CHECK (awmk::launch_clip_pad_s16 (st, d_desc, int (gn), slices, (long long) slice_values, s0.margin_values, s0.d_range));
-          return 0;
-        }
-      AWM_HIP_CHECK (awmk::launch_clip_pad (st, d_desc, int (gn), slices, (long long) slice_values, s0.margin_values, s0.d_range));
-      return 0;
-    }
-  if (!one_rate)
-    {
-      auto *desc = lane->pin_group.as<awmk::ClipMixedSrc>();
-      int *list = reinterpret_cast<int *> (desc + gn);
-      double samples = 0;
-      for (size_t i = 0; i < gn; i++)
-        {
-          const DeviceWav& wav = clips[which[i]];
-          const ResampleTable *t = rates->table[which[i]];                      // (null: a clip at 44.1 kHz, copied)
-          desc[i] = { values_of (wav), (long long) wav.n_frames, s0.n_values[i] / C, s0.pad_start[i], t ? t->ctab.as<float>() : nullptr,
-                      t ? t->hl : 0, t ? t->np : 0, t ? t->step : 0, 0, 0, 0 };
-          samples += double (wav.n_frames) * (sample_bytes_in / 4.0) + double (desc[i].n44);
-        }
-      const awmk::ClipMixedPlan plan = awmk::clip_stage_mixed_plan (desc, int (gn), C, list, s16);
-      auto *d_desc = lane->ws_group.as<awmk::ClipMixedSrc>();
-      AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
-      ProfScope ps (ctx, s16 ? PROF_CLIP_STAGE_MIXED_S16 : PROF_CLIP_STAGE_MIXED, samples * C * 4.0, st);     // every input and output sample of the group once
-      AWM_HIP_CHECK ((s16 ? awmk::launch_clip_stage_mixed_s16 : awmk::launch_clip_stage_mixed) (st, plan, d_desc, reinterpret_cast<const int *> (d_desc + gn),
-                                                                                                slices, (long long) slice_values, s0.margin_values, s0.d_range));
-      return 0;
-    }
-  auto *desc = lane->pin_group.as<awmk::ClipResampleSrc>();
-  uintptr_t bits = 0;
-  long long max_n44 = 0;
+  auto *desc = lane->pin_group.as<awmk::ClipStageSrc>();
+  int *list = reinterpret_cast<int *> (desc + gn);
+  bool one_rate = true;
   double samples = 0;
   for (size_t i = 0; i < gn; i++)
     {
       const DeviceWav& wav = clips[which[i]];
-      desc[i] = { values_of (wav), (long long) wav.n_frames, s0.n_values[i] / C, s0.pad_start[i] };
-      bits |= reinterpret_cast<uintptr_t> (desc[i].in);
-      max_n44 = std::max (max_n44, desc[i].n44);
-      samples += double (wav.n_frames) * (sample_bytes_in / 4.0) + double (desc[i].n44);
+      const ResampleTable *t = rates ? rates->table[which[i]] : nullptr;        // (null: a clip at 44.1 kHz, copied)
+      const long long n44 = (long long) (rates ? rates->n44[which[i]] : wav.n_frames);
+      s0.n_values[i] = n44 * C;
+      s0.pad_start[i] = (long long) (n + (n - s0.n_values[i]));
+      desc[i] = { s16 ? reinterpret_cast<const float *> (wav.pcm16) : wav.data, (long long) wav.n_frames, n44, s0.pad_start[i],
+                  t ? t->ctab.as<float>() : nullptr, t ? t->hl : 0, t ? t->np : 0, t ? t->step : 0, 0, 0, 0 };
+      one_rate = one_rate && (!rates || rates->sample_rate[which[i]] == rates->sample_rate[which[0]]);
+      samples += double (wav.n_frames) * (s16 ? 0.5 : 1.0) + double (n44);
     }
-  auto *d_desc = lane->ws_group.as<awmk::ClipResampleSrc>();
+  const awmk::ClipStagePlan plan = awmk::clip_stage_plan (desc, int (gn), C, list, s16);
+  auto *d_desc = lane->ws_group.as<awmk::ClipStageSrc>();
   AWM_HIP_CHECK (hipMemcpyAsync (d_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
-  const ResampleTable *table = rates->table[which[0]];
-  awmk::ResampleArgs ra {};
-  ra.n_channels = C;
-  ra.ctab = table->ctab.as<float>();
-  ra.hl = table->hl;
-  ra.np = table->np;
-  ra.step = table->step;
-  ProfScope ps (ctx, s16 ? PROF_CLIP_RESAMPLE_S16 : PROF_CLIP_RESAMPLE, samples * C * 4.0, st);      // every input and output sample of the group once
-  if (s16)                                                                      // (a 16-bit stereo frame is 4 bytes)
-    AWM_HIP_CHECK (awmk::launch_clip_resample_pad_s16 (st, ra, d_desc, int (gn), max_n44, (bits & 3) == 0, slices, (long long) slice_values,
-                                                       s0.margin_values, s0.d_range));
-  else
-    AWM_HIP_CHECK (awmk::launch_clip_resample_pad (st, ra, d_desc, int (gn), max_n44, (bits & 7) == 0, slices, (long long) slice_values,
-                                                   s0.margin_values, s0.d_range));
+  // the profiling scope names the group's COMPOSITION, as it did when each had kernels of its own: every clip at 44.1 kHz (float: no
+  // scope), one other rate for all, or anything else.  Bytes: every input and output sample of the group once
+  const bool copy = one_rate && (!rates || rates->at_mark_rate (which[0]));
+  const int scope = copy ? (s16 ? PROF_CLIP_PAD_S16 : -1) : one_rate ? (s16 ? PROF_CLIP_RESAMPLE_S16 : PROF_CLIP_RESAMPLE)
+                         : (s16 ? PROF_CLIP_STAGE_MIXED_S16 : PROF_CLIP_STAGE_MIXED);
+  std::optional<ProfScope> ps;
+  if (scope >= 0)
+    ps.emplace (ctx, scope, samples * C * 4.0, st);
+  AWM_HIP_CHECK ((s16 ? awmk::launch_clip_stage_s16 : awmk::launch_clip_stage) (st, plan, d_desc, reinterpret_cast<const int *> (d_desc + gn), slices,
+                                                                              (long long) slice_values, s0.margin_values, s0.d_range));
   return 0;
 }
 

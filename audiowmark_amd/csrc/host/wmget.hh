@@ -67,7 +67,7 @@ struct ClipRates
                                                     // 44100 / sample_rate -- or a clip at 44.1 kHz, which is not resampled
   std::vector<size_t>                n44;           // frames of clip i at 44.1 kHz
   bool at_mark_rate (size_t i) const { return sample_rate[i] == Params::mark_sample_rate; }
-  bool groupable (size_t i) const { return table[i] || at_mark_rate (i); }       // stage 0 of the groups takes it (K10c / K10x / the copy)
+  bool groupable (size_t i) const { return table[i] || at_mark_rate (i); }       // stage 0 of the groups takes it (kernels.hh launch_clip_stage)
 };
 // a clip of this many frames at 44.1 kHz runs in the groups (below one block + 2 frames), not on a lane of its own
 bool clip_is_short (size_t n_frames);

@@ -459,7 +459,7 @@ int awm_get_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], size_t n_cli
  * awm_resample_frames (n_frames[i], sample_rate, 44100) frames, the result for clip i is field for field what awm_get_watermark_d returns
  * for y_i (sync_index is an index into the 44.1 kHz stream, as in the reference) -- with that clip's key in the keys form.  One rate per
  * call.  A clip is short (the grouped path of awm_get_watermark_batch_d) by its 44.1 kHz length.  Short clips at a rate of the fixed-ratio
- * Resampler are resampled STRAIGHT INTO the group's padded slices (K10c, one launch per group: no resampled copies, no launch per clip,
+ * Resampler are resampled STRAIGHT INTO the group's padded slices (stage 0 of the group, one launch per group: no resampled copies, no launch per clip,
  * no second read); long clips, VResampler rates and calls with a speed parameter set resample each clip into a grow-only workspace of its
  * lane first (awm_ctx_trim gives these back).  sample_rate == 44100 is the existing function.  AWM_ERR_ARG with nothing enqueued and n_out
  * untouched: sample_rate <= 0, or a ratio that neither zita class takes (awm_resample_frames gives 0).  Empty clips: n_out[i] = 0.
@@ -478,9 +478,9 @@ int awm_get_watermark_batch_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size
  * sample_rates[i], ...) returns -- awm_get_watermark_d on awm_resample_d (clip i, sample_rates[i] -> 44100), and on the clip itself where its
  * rate is 44100; key_i = key, or keys + 16 i in the keys form; sync_index counts 44.1 kHz samples.
  * Paths: a clip is short by its 44.1 kHz length.  Short clips at 44100 or at a rate of the fixed-ratio Resampler fill the groups of 64 in
- * call order WHATEVER THEIR RATES; stage 0 of a group whose clips do not share one rate is K10x (every clip resampled with its own rate's
- * table, or copied, straight into its padded slice: one launch per form present in the group, not per clip or rate), a group that happens
- * to share one rate runs as in the one-rate call.  Long clips, VResampler rates and 44.1 kHz long clips go over the work lanes, each
+ * call order WHATEVER THEIR RATES; stage 0 of a group whose clips do not share one rate is the same launcher (every clip resampled with its own
+ * rate's table, or copied, straight into its padded slice: one launch per form present in the group, not per clip or rate), a group that
+ * happens to share one rate runs as in the one-rate call.  Long clips, VResampler rates and 44.1 kHz long clips go over the work lanes, each
  * resampled with its own rate into its lane's grow-only workspace first; so does every clip while a speed parameter is set.  A call
  * whose rates are all equal IS the one-rate function above (44100: the 44.1 kHz function).
  * Refusals, AWM_ERR_ARG with nothing enqueued and n_out / out untouched, awm_last_error names the index of the first offending clip:
@@ -507,7 +507,7 @@ int awm_get_batch_rates_plan (size_t n_clips, const size_t *n_frames, const int 
  * exact -- the result for clip i is field for field what awm_get_watermark_batch_rates_d returns for f_i at sample_rates[i]; key_i = key, or
  * keys + 16 i in the keys form.
  * Paths: those of awm_get_watermark_batch_rates_d (awm_get_batch_rates_plan).  Stage 0 of a group of short clips READS THE 16-BIT VALUES:
- * the copy, K10c and K10x are the same kernels instantiated for 16-bit input, which convert where a value leaves global memory (once per
+ * the copy and the resampling forms are the same kernels instantiated for 16-bit input, which convert where a value leaves global memory (once per
  * input value) and are bit for bit the float kernels on f_i behind that; a short clip never has a float copy and never costs a launch of
  * its own.  Long clips, VResampler rates and every clip while a speed parameter is set are decoded into a grow-only workspace of their lane
  * first (one launch; awm_ctx_trim gives it back) and go on as in the float call.
@@ -806,11 +806,11 @@ int  awm_debug_clip_stage_d (awm_ctx *ctx, size_t n_clips, const float *const *p
                              float *slices_d, long long *range_out);
                                            /* stage 0 of a group alone: the padded slices of 1 .. 64 short clips into slices_d (n_clips x slice values, 16-byte aligned) on the
                                             * context's stream, their non-silent ranges to range_out (host, [n_clips][2]), synchronised.  44100: the padded copy; a rate of the
-                                            * fixed-ratio Resampler: K10c.  AWM_ERR_ARG: a VResampler rate, a clip that is not short, more than 64 clips.  Honours
+                                            * fixed-ratio Resampler: resampled into the slices.  AWM_ERR_ARG: a VResampler rate, a clip that is not short, more than 64 clips.  Honours
                                             * awm_debug_set_clip_poison */
 int  awm_debug_clip_stage_rates_d (awm_ctx *ctx, size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels,
                                    const int *sample_rates, float *slices_d, long long *range_out);
-                                           /* its twin with a rate per clip: a group whose clips do not share one rate goes through K10x, one that does as above.
+                                           /* its twin with a rate per clip: every clip with the form of its own rate (one launch per form present).
                                             * The same refusals, and those of awm_get_watermark_batch_rates_d */
 int  awm_debug_clip_stage_rates_s16_d (awm_ctx *ctx, size_t n_clips, const int16_t *const *pcm_d, const size_t *n_frames, int n_channels,
                                        const int *sample_rates, float *slices_d, long long *range_out);
