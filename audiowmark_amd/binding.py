@@ -137,6 +137,8 @@ lib.awm_add_watermark_segments_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp
 lib.awm_add_watermark_segments_rate_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
 lib.awm_add_watermark_segments_keys_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int]
 lib.awm_add_watermark_segments_keys_rate_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
+lib.awm_add_watermark_segments_rate_s16_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
+lib.awm_add_watermark_segments_keys_rate_s16_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
 
 
 class SegmentPlan(C.Structure):
@@ -438,6 +440,49 @@ def frame_mod_template(key, block_frames=None):
 def add_segments_fused_in_use():
     """1 if the last add_watermark_segments took the fused path (one launch per stage for the batch)"""
     return lib.awm_debug_add_segments_fused_in_use()
+
+
+def _add_segments_s16(ctx, name, key_arg, payloads, segments, zero_frames, outs, sample_rate):
+    import torch
+    payloads, segments, zero_frames = list(payloads), list(segments), list(zero_frames)
+    if not (len(payloads) == len(segments) == len(zero_frames)):
+        raise ValueError(name + ": payloads, segments and zero_frames must have one length")
+    if not segments:
+        return []
+    if any(s.dtype != torch.int16 or not s.is_cuda or not s.is_contiguous() for s in segments):
+        raise ValueError(name + ": the segments must be contiguous int16 tensors on the device")
+    shapes = [(s.shape[0], 1 if s.dim() == 1 else s.shape[1]) for s in segments]
+    ch = shapes[0][1]
+    if any(s[1] != ch for s in shapes):
+        raise ValueError(name + ": the segments must have one channel count")
+    if outs is None:
+        outs = [torch.empty_like(s) for s in segments]
+    elif len(outs) != len(segments) or any(o.shape != s.shape or o.dtype != s.dtype or not o.is_contiguous() for o, s in zip(outs, segments)):
+        raise ValueError(name + ": outs must match the segments")
+    n = len(segments)
+    hexes = (C.c_char_p * n)(*[p.encode() for p in payloads])
+    zf = (C.c_size_t * n)(*[int(z) for z in zero_frames])
+    src = (C.c_void_p * n)(*[_dev_ptr(s) for s in segments])
+    dst = (C.c_void_p * n)(*[_dev_ptr(o) for o in outs])
+    frames = (C.c_size_t * n)(*[s[0] for s in shapes])
+    _check(getattr(lib, name)(ctx._h, key_arg, n, hexes, zf, src, dst, frames, ch, int(sample_rate)), name)
+    return outs
+
+
+def add_watermark_segments_s16(ctx, key, payloads, segments, zero_frames, outs=None, sample_rate=44100):
+    """awm_add_watermark_segments_rate_s16_d: Context.add_watermark_segments on segments that are resident as signed 16-bit PCM (int16
+    tensors, [frames, channels]), written as 16-bit PCM: outs[i] == pcm_encode(add_watermark_segments(key, ..., pcm_decode(segments[i]), ...),
+    16, direct16=True) value for value, without a float copy of a segment and without a launch per segment."""
+    return _add_segments_s16(ctx, "awm_add_watermark_segments_rate_s16_d", key_bytes(key), payloads, segments, zero_frames, outs, sample_rate)
+
+
+def add_watermark_segments_keys_s16(ctx, keys, payloads, segments, zero_frames, outs=None, sample_rate=44100):
+    """awm_add_watermark_segments_keys_rate_s16_d: add_watermark_segments_s16 with a key per segment (None, test_key(n) or 16 bytes each)"""
+    keys = list(keys)
+    if len(keys) != len(list(segments)):
+        raise ValueError("awm_add_watermark_segments_keys_rate_s16_d: keys and segments must have one length")
+    return _add_segments_s16(ctx, "awm_add_watermark_segments_keys_rate_s16_d", b"".join(key_bytes(k) for k in keys), payloads, segments,
+                             zero_frames, outs, sample_rate)
 
 
 def add_segment_plan(sample_rate, zero_frames, n_frames):
@@ -795,6 +840,14 @@ class Context:
             return outs
         _check(lib.awm_add_watermark_segments_keys_d(self._h, kb, n, hexes, zf, src, dst, frames, ch), "awm_add_watermark_segments_keys_d")
         return outs
+
+    def add_watermark_segments_s16(self, key, payloads, segments, zero_frames, outs=None, sample_rate=44100):
+        """awm_add_watermark_segments_rate_s16_d (binding.add_watermark_segments_s16): int16 segments in, int16 segments out"""
+        return add_watermark_segments_s16(self, key, payloads, segments, zero_frames, outs, sample_rate)
+
+    def add_watermark_segments_keys_s16(self, keys, payloads, segments, zero_frames, outs=None, sample_rate=44100):
+        """awm_add_watermark_segments_keys_rate_s16_d (binding.add_watermark_segments_keys_s16): the same with a key per segment"""
+        return add_watermark_segments_keys_s16(self, keys, payloads, segments, zero_frames, outs, sample_rate)
 
     def key_templates(self, keys):
         """K16t alone (awm_debug_key_templates_d): the templates of the keys, built on the device, int16 [len(keys)][360624]; the first

@@ -123,6 +123,31 @@ struct SegmentCopy { const float *src; float *dst; long long n_values, zeros; };
 hipError_t launch_segment_copy (hipStream_t st, const SegmentCopy *copies_dev, int n_copies, long long max_values);
 hipError_t launch_limiter_batch (hipStream_t st, const LimiterClip *clips_dev, int n_clips, long long max_frames, int n_channels, int limiter_block,
                                  float ceiling, long long max_tab = 0);
+/* the first of launch_limiter_batch's two launches alone: the ramp tables of the clips (data and n_frames are not read) */
+hipError_t launch_limiter_table_batch (hipStream_t st, const LimiterClip *clips_dev, int n_clips, long long max_frames, int limiter_block, float ceiling,
+                                       long long max_tab = 0);
+/* The 16-BIT SEGMENT BATCHES (awm_add_watermark_segments_rate_s16_d): signed 16-bit PCM, little-endian, interleaved stereo, every address
+ * 4-byte aligned (a stereo frame is one load or store).
+ * launch_segment_gather_s16: launch_segment_copy whose sources are int16 -- `src` holds their ADDRESS --, decoded as launch_pcm_decode
+ * decodes them, float (v) * (1 / 32768): dst[0 .. zeros) = 0, dst[zeros .. zeros + n_values) = the decoded values.
+ * launch_limit_encode_segments: limiter ramp and encode in one pass over a batch of segments, blockIdx.y = segment.  The un-limited mix of
+ * frame f is wm[f] (mix false) or wm[f] + the decoded orig[f] (mix true: launch_mix_max_segments' add, nothing of it was stored; `orig`
+ * holds the address of the segment's int16 values); it is multiplied by the ramp launch_limiter_batch applies -- tab[b - tab_first_block]
+ * is the (scale_start, scale_step) of limiter block b, frame f is sample first_sample + f of its stream; tab null: no ramp -- and goes
+ * through launch_pcm_encode's direct16 rule (v * 32768, saturated at 32767 / -32768, truncated) to out[f].  out is bit for bit what
+ * launch_limiter_batch over the stored mix and launch_pcm_encode write.  Nothing outside out[0 .. 2 n_frames) is written: 16-byte stores
+ * from the first 16-byte boundary of out, single frames in front and behind.  limiter_block >= 2048. */
+hipError_t launch_segment_gather_s16 (hipStream_t st, const SegmentCopy *copies_dev, int n_copies, long long max_values);
+struct LimitEncodeSegment
+{
+  const void   *orig;
+  const float  *wm;
+  short        *out;
+  long long     n_frames, first_sample;
+  const float2 *tab;
+  long long     tab_first_block;
+};
+hipError_t launch_limit_encode_segments (hipStream_t st, const LimitEncodeSegment *segs_dev, int n_segs, long long max_frames, bool mix, int limiter_block);
 /* entries launch_limiter needs in scale_tab for this span (one (scale_start, scale_step) pair per limiter block) */
 size_t     limiter_tab_entries (long long n_frames, long long first_sample, int limiter_block);
 hipError_t launch_fill_u32 (hipStream_t st, unsigned int *p, unsigned int v, size_t n);
@@ -159,6 +184,11 @@ struct ResampleSlice
 hipError_t launch_resample_slices (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, int n_slices, long long max_n_out,
                                    bool stereo_aligned);
 hipError_t launch_resample_slice (hipStream_t st, const ResampleArgs& a, const ResampleSlice& slice);     // one slice, arguments by value
+/* K10w over slices whose input is SIGNED 16-BIT PCM (the kernels instantiated for PcmS16, like stage 0 of the clip groups: `in` holds the
+ * ADDRESS of the int16 values, a value is converted once, where it leaves global memory): out is bit for bit what launch_resample_slices
+ * writes for the decoded input.  stereo_aligned: every input 4-byte aligned, every output 8-byte aligned */
+hipError_t launch_resample_slices_s16 (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, int n_slices, long long max_n_out,
+                                       bool stereo_aligned);
 /* K10s: one slice whose caller chooses where it begins (the tile stream at another rate, which ends every launch on a multiple of np and
  * carries the rest).  Stereo 48 <-> 44.1 kHz with every pointer 8-byte aligned, out0 a multiple of np and awm_debug_set_resample_phase on
  * runs K10's phase-per-thread body at the slice's place in its stream (resample_span_takes_phase says whether); everything else is
@@ -211,6 +241,9 @@ struct MixSegment
 };
 hipError_t launch_mix_max_segments (hipStream_t st, const MixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int limiter_block);
 hipError_t launch_mix_max_segment (hipStream_t st, const MixSegment& seg, int n_channels, int limiter_block);   // one segment, arguments by value
+/* the block maxima of launch_mix_max_segments ALONE, for segments of signed 16-bit PCM (`orig` holds the address of the int16 values,
+ * decoded as they are read): the same add, the same maxima, `out` is not read or written */
+hipError_t launch_max_segments_s16 (hipStream_t st, const MixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int limiter_block);
 
 /* `add --snr`: acc[0] += sum (mixed - orig)^2, acc[1] += sum orig^2 in double (reference wmadd.cc:553-563) */
 hipError_t launch_power_sums (hipStream_t st, const float *orig, const float *mixed, long long n_values, double *acc);

@@ -1241,6 +1241,20 @@ limiter_apply_batch_kernel (const LimiterClip *clips, int BS)
 }
 
 hipError_t
+launch_limiter_table_batch (hipStream_t st, const LimiterClip *clips_dev, int n_clips, long long max_frames, int limiter_block, float ceiling,
+                            long long max_tab)
+{
+  if (n_clips <= 0 || max_frames <= 0)
+    return hipSuccess;
+  if (limiter_block < 1)
+    return hipErrorInvalidValue;
+  if (max_tab <= 0)
+    max_tab = limiter_tab_entries (max_frames, 0, limiter_block);
+  hipLaunchKernelGGL (limiter_table_batch_kernel, dim3 (unsigned ((max_tab + 255) / 256), unsigned (n_clips)), dim3 (256), 0, st, clips_dev, limiter_block, ceiling);
+  return hipGetLastError();
+}
+
+hipError_t
 launch_limiter_batch (hipStream_t st, const LimiterClip *clips_dev, int n_clips, long long max_frames, int n_channels, int limiter_block, float ceiling,
                       long long max_tab)
 {
@@ -1248,9 +1262,8 @@ launch_limiter_batch (hipStream_t st, const LimiterClip *clips_dev, int n_clips,
     return hipSuccess;
   if ((n_channels != 1 && n_channels != 2) || limiter_block < 4 * LIMITER_RUN)
     return hipErrorInvalidValue;
-  if (max_tab <= 0)
-    max_tab = limiter_tab_entries (max_frames, 0, limiter_block);
-  hipLaunchKernelGGL (limiter_table_batch_kernel, dim3 (unsigned ((max_tab + 255) / 256), unsigned (n_clips)), dim3 (256), 0, st, clips_dev, limiter_block, ceiling);
+  if (hipError_t e = launch_limiter_table_batch (st, clips_dev, n_clips, max_frames, limiter_block, ceiling, max_tab))
+    return e;
   const long long max_vec = std::max<long long> (1, max_frames * n_channels / 4);
   const dim3 grid (unsigned ((max_vec + LIMITER_RUN - 1) / LIMITER_RUN), unsigned (n_clips));
   if (n_channels == 2)
@@ -1838,12 +1851,12 @@ resample_slice_body (const ResampleArgs& a0, const ResampleSlice& s, int lds_flo
         }
     }
 }
-template<int CT> __global__ void __launch_bounds__ (256)
+template<int CT, class In = PcmF32> __global__ void __launch_bounds__ (256)
 resample_slices_kernel (ResampleArgs a, const ResampleSlice *slices, int lds_floats, int in_span, int tiles_per_wg)
 {
   const ResampleSlice s = slices[blockIdx.y];
   ResampleStore sink { s.out };
-  resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg, sink);
+  resample_slice_body<CT, In> (a, s, lds_floats, in_span, tiles_per_wg, sink);
 }
 template<int CT> __global__ void __launch_bounds__ (256)
 resample_slice_kernel (ResampleArgs a, ResampleSlice s, int lds_floats, int in_span, int tiles_per_wg)
@@ -1852,13 +1865,13 @@ resample_slice_kernel (ResampleArgs a, ResampleSlice s, int lds_floats, int in_s
   resample_slice_body<CT> (a, s, lds_floats, in_span, tiles_per_wg, sink);
 }
 
-static hipError_t
+template<class In = PcmF32> static hipError_t
 launch_resample_slices_any (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, const ResampleSlice *one, int n_slices,
                             long long max_n_out, bool stereo_aligned)
 {
   if (n_slices <= 0 || max_n_out <= 0)
     return hipSuccess;
-  if (n_slices > 65535 || a.hl < 1 || a.np < 1 || a.step < 1 || a.n_channels < 1)
+  if (n_slices > 65535 || a.hl < 1 || a.np < 1 || a.step < 1 || a.n_channels < 1 || (one && !std::is_same<In, PcmF32>::value))
     return hipErrorInvalidValue;
   // as in launch_resample: at least 4096 workgroups first (here over all slices), then up to 8 tiles per workgroup and table
   const long long n_tiles = (max_n_out + RS_TILE - 1) / RS_TILE;
@@ -1877,15 +1890,20 @@ launch_resample_slices_any (hipStream_t st, const ResampleArgs& a, const Resampl
   else if (one)
     hipLaunchKernelGGL (resample_slice_kernel<0>, grid, dim3 (256), lds_bytes, st, a, *one, lds_floats, in_span, tiles_per_wg);
   else if (stereo)
-    hipLaunchKernelGGL (resample_slices_kernel<2>, grid, dim3 (256), lds_bytes, st, a, slices_dev, lds_floats, in_span, tiles_per_wg);
+    hipLaunchKernelGGL ((resample_slices_kernel<2, In>), grid, dim3 (256), lds_bytes, st, a, slices_dev, lds_floats, in_span, tiles_per_wg);
   else
-    hipLaunchKernelGGL (resample_slices_kernel<0>, grid, dim3 (256), lds_bytes, st, a, slices_dev, lds_floats, in_span, tiles_per_wg);
+    hipLaunchKernelGGL ((resample_slices_kernel<0, In>), grid, dim3 (256), lds_bytes, st, a, slices_dev, lds_floats, in_span, tiles_per_wg);
   return hipGetLastError();
 }
 hipError_t
 launch_resample_slices (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, int n_slices, long long max_n_out, bool stereo_aligned)
 {
   return launch_resample_slices_any (st, a, slices_dev, nullptr, n_slices, max_n_out, stereo_aligned);
+}
+hipError_t
+launch_resample_slices_s16 (hipStream_t st, const ResampleArgs& a, const ResampleSlice *slices_dev, int n_slices, long long max_n_out, bool stereo_aligned)
+{
+  return launch_resample_slices_any<PcmS16> (st, a, slices_dev, nullptr, n_slices, max_n_out, stereo_aligned);
 }
 hipError_t
 launch_resample_slice (hipStream_t st, const ResampleArgs& a, const ResampleSlice& slice)
@@ -2014,8 +2032,10 @@ launch_mix_max (hipStream_t st, const float *orig, const float *wm, float *out, 
 }
 
 /* K11 for stream segments (kernels.hh MixSegment): mix_max_kernel with the segment's place in its stream -- the limiter block of a value
- * comes from first_sample - pre + its frame, the maxima go to block_max[block - first_block] -- and `pre` frames of watermark alone in front */
-__device__ __forceinline__ void
+ * comes from first_sample - pre + its frame, the maxima go to block_max[block - first_block] -- and `pre` frames of watermark alone in front.
+ * In: what the segment's values are (PcmS16: s.orig holds the address of int16 values, converted as they are read); STORE false: the maxima
+ * alone, s.out is not touched (the 16-bit batches, whose last pass computes the mix again: limit_encode_segments_kernel) */
+template<class In = PcmF32, bool STORE = true> __device__ __forceinline__ void
 mix_max_segment_body (const MixSegment& s, int C, int BS)
 {
   __shared__ float s_m0[4], s_m1[4];
@@ -2026,6 +2046,7 @@ mix_max_segment_body (const MixSegment& s, int C, int BS)
   const long long start = s.first_sample - s.pre;             // sample of the stream that wm[0] belongs to
   const long long b0 = (start + base / C) / BS;
   const long long bound = ((b0 + 1) * BS - start) * C;        // first value of the next limiter block
+  const typename In::value *orig = reinterpret_cast<const typename In::value *> (s.orig);
   float m0 = 0.f, m1 = 0.f;
   for (int j = 0; j < MIX_RUN / 256; j++)
     {
@@ -2035,8 +2056,9 @@ mix_max_segment_body (const MixSegment& s, int C, int BS)
           float r = s.wm[v];
           if (v >= pre_values)
             {
-              r = __fadd_rn (r, s.orig[v - pre_values]);
-              s.out[v - pre_values] = r;
+              r = __fadd_rn (r, In::conv (orig[v - pre_values]));
+              if (STORE)
+                s.out[v - pre_values] = r;
             }
           if (v < bound)
             m0 = fmaxf (m0, fabsf (r));
@@ -2072,6 +2094,12 @@ mix_max_segment_kernel (MixSegment s, int C, int BS)
 {
   mix_max_segment_body (s, C, BS);
 }
+__global__ void __launch_bounds__ (256)
+max_segments_s16_kernel (const MixSegment *segs, int C, int BS)
+{
+  const MixSegment s = segs[blockIdx.y];
+  mix_max_segment_body<PcmS16, false> (s, C, BS);
+}
 
 hipError_t
 launch_mix_max_segments (hipStream_t st, const MixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int limiter_block)
@@ -2082,6 +2110,18 @@ launch_mix_max_segments (hipStream_t st, const MixSegment *segs_dev, int n_segs,
     return hipErrorInvalidValue;                               // a run may only straddle one block boundary
   const long long max_values = max_frames * n_channels;
   hipLaunchKernelGGL (mix_max_segments_kernel, dim3 (unsigned ((max_values + MIX_RUN - 1) / MIX_RUN), unsigned (n_segs)), dim3 (256), 0, st,
+                      segs_dev, n_channels, limiter_block);
+  return hipGetLastError();
+}
+hipError_t
+launch_max_segments_s16 (hipStream_t st, const MixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int limiter_block)
+{
+  if (n_segs <= 0 || max_frames <= 0)
+    return hipSuccess;
+  if (n_segs > 65535 || n_channels < 1 || (long long) limiter_block * n_channels < MIX_RUN)
+    return hipErrorInvalidValue;
+  const long long max_values = max_frames * n_channels;
+  hipLaunchKernelGGL (max_segments_s16_kernel, dim3 (unsigned ((max_values + MIX_RUN - 1) / MIX_RUN), unsigned (n_segs)), dim3 (256), 0, st,
                       segs_dev, n_channels, limiter_block);
   return hipGetLastError();
 }
@@ -4423,9 +4463,10 @@ launch_clip_stage_s16 (hipStream_t st, const ClipStagePlan& p, const ClipStageSr
 
 /* kernels.hh launch_segment_copy: grid (runs, segments).  A segment that starts r samples into its first frame is 8 r bytes off the
  * 16-byte grid of its staged slice, so the pieces are float2 (a stereo frame): always aligned on both sides, a wave moves 512 bytes per
- * instruction.  A workgroup owns a run of SEG_RUN pieces, loads first. */
+ * instruction.  A workgroup owns a run of SEG_RUN pieces, loads first.  In: what the source's values are (PcmS16, the gather of the 16-bit
+ * batches: c.src holds the address of int16 values, a piece is one 4-byte load, decoded as it is read) */
 constexpr int SEG_RUN = 2048;
-__global__ void __launch_bounds__ (256)
+template<class In = PcmF32> __global__ void __launch_bounds__ (256)
 segment_copy_kernel (const SegmentCopy *copies)
 {
   const SegmentCopy c = copies[blockIdx.y];
@@ -4433,7 +4474,7 @@ segment_copy_kernel (const SegmentCopy *copies)
   const long long base = (long long) blockIdx.x * SEG_RUN;
   if (c.n_values <= 0 || base >= n_total)
     return;
-  const float2 *src = reinterpret_cast<const float2 *> (c.src);
+  const typename In::frame2 *src = reinterpret_cast<const typename In::frame2 *> (c.src);
   float2 *dst = reinterpret_cast<float2 *> (c.dst);
   constexpr int U = SEG_RUN / 256;
   float2 v[U];
@@ -4441,7 +4482,7 @@ segment_copy_kernel (const SegmentCopy *copies)
   for (int j = 0; j < U; j++)
     {
       const long long q = base + threadIdx.x + 256 * j;
-      v[j] = q >= n_zero && q < n_total ? src[q - n_zero] : make_float2 (0.f, 0.f);
+      v[j] = q >= n_zero && q < n_total ? In::conv2 (src[q - n_zero]) : make_float2 (0.f, 0.f);
     }
 #pragma unroll
   for (int j = 0; j < U; j++)
@@ -4458,7 +4499,125 @@ launch_segment_copy (hipStream_t st, const SegmentCopy *copies_dev, int n_copies
   if (n_copies <= 0 || max_values <= 0)
     return hipSuccess;
   const long long max_pieces = (max_values + 1) / 2;
-  hipLaunchKernelGGL (segment_copy_kernel, dim3 (unsigned ((max_pieces + SEG_RUN - 1) / SEG_RUN), unsigned (n_copies)), dim3 (256), 0, st, copies_dev);
+  hipLaunchKernelGGL (segment_copy_kernel<>, dim3 (unsigned ((max_pieces + SEG_RUN - 1) / SEG_RUN), unsigned (n_copies)), dim3 (256), 0, st, copies_dev);
+  return hipGetLastError();
+}
+hipError_t
+launch_segment_gather_s16 (hipStream_t st, const SegmentCopy *copies_dev, int n_copies, long long max_values)
+{
+  if (n_copies <= 0 || max_values <= 0)
+    return hipSuccess;
+  const long long max_pieces = (max_values + 1) / 2;
+  hipLaunchKernelGGL (segment_copy_kernel<PcmS16>, dim3 (unsigned ((max_pieces + SEG_RUN - 1) / SEG_RUN), unsigned (n_copies)), dim3 (256), 0, st, copies_dev);
+  return hipGetLastError();
+}
+
+/* kernels.hh launch_limit_encode_segments: the last pass of the 16-bit segment batches, grid (runs, segments).  A value is the un-limited
+ * mix -- MIX: computed again as wm + conv (orig), mix_max_segment_body's add; else read from `wm` --, times the ramp of limiter_apply_run
+ * (the same table entries, the same rounded product and sum; tab null: the entry (1, 0), v * 1.0f == v), through the direct16 rule of
+ * pcm_encode_s16le_kernel, stored as int16.  A thread owns groups of four stereo frames, one 16-byte store each; the groups begin at the
+ * first 16-byte boundary of `out`, and the up to three frames in front of them and behind them (the peel and the tail) are single frames,
+ * 4-byte stores, of workgroup 0.  A workgroup owns a run of ENC_RUN groups, 2048 frames -- shorter than a limiter block, so it meets at
+ * most two table entries --, loads first. */
+constexpr int ENC_RUN = 512;
+__device__ __forceinline__ unsigned int
+encode_direct16_frame (float2 v, float scale)
+{
+  const float s0 = __fmul_rn (__fmul_rn (v.x, scale), 32768.f), s1 = __fmul_rn (__fmul_rn (v.y, scale), 32768.f);
+  const int i0 = s0 >= 32767.f ? 32767 : (s0 <= -32768.f ? -32768 : int (s0));
+  const int i1 = s1 >= 32767.f ? 32767 : (s1 <= -32768.f ? -32768 : int (s1));
+  return ((unsigned int) i0 & 0xffffu) | ((unsigned int) i1 << 16);
+}
+template<bool MIX> __global__ void __launch_bounds__ (256)
+limit_encode_segments_kernel (const LimitEncodeSegment *segs, int BS)
+{
+  const LimitEncodeSegment s = segs[blockIdx.y];
+  const long long n = s.n_frames;
+  const long long to_grid = (long long) (((16 - (reinterpret_cast<uintptr_t> (s.out) & 15)) & 15) / 4);
+  const long long peel = to_grid < n ? to_grid : n;             // frames in front of the first 16-byte boundary of out
+  const long long n_groups = (n - peel) / 4;
+  const long long base = (long long) blockIdx.x * ENC_RUN;
+  const short2 *orig = reinterpret_cast<const short2 *> (s.orig);
+  const float2 *wm = reinterpret_cast<const float2 *> (s.wm);
+  unsigned int *out = reinterpret_cast<unsigned int *> (s.out);  // a stereo frame
+  auto value = [&] (long long f) -> float2 {
+    float2 v = wm[f];
+    if (MIX)
+      {
+        const float2 o = PcmS16::conv2 (orig[f]);
+        v = make_float2 (__fadd_rn (v.x, o.x), __fadd_rn (v.y, o.y));
+      }
+    return v;
+  };
+  if (base < n_groups)
+    {
+      const long long gs0 = s.first_sample + peel + 4 * base;
+      float2 t0 = make_float2 (1.f, 0.f), t1 = t0;
+      int i0 = 0;
+      if (s.tab)
+        {
+          const long long b0 = gs0 / BS;                      // uniform: once per workgroup
+          i0 = int (gs0 - b0 * BS);
+          const float2 *tb = s.tab + (b0 - s.tab_first_block);
+          t0 = tb[0];
+          t1 = tb[1];
+        }
+      auto scale = [&] (int i) -> float {
+        const bool next = i >= BS;
+        const float2 t = next ? t1 : t0;
+        return __fadd_rn (t.x, __fmul_rn (float (next ? i - BS : i), t.y));
+      };
+      constexpr int U = ENC_RUN / 256;
+      float2 v[U][4];
+#pragma unroll
+      for (int j = 0; j < U; j++)
+        {
+          const long long q = base + threadIdx.x + 256 * j;
+#pragma unroll
+          for (int k = 0; k < 4; k++)
+            v[j][k] = q < n_groups ? value (peel + 4 * q + k) : make_float2 (0.f, 0.f);
+        }
+      uint4 *out4 = reinterpret_cast<uint4 *> (out + peel);
+#pragma unroll
+      for (int j = 0; j < U; j++)
+        {
+          const long long q = base + threadIdx.x + 256 * j;
+          const int i = i0 + 4 * (int (threadIdx.x) + 256 * j);
+          if (q < n_groups)
+            out4[q] = make_uint4 (encode_direct16_frame (v[j][0], scale (i)), encode_direct16_frame (v[j][1], scale (i + 1)),
+                                  encode_direct16_frame (v[j][2], scale (i + 2)), encode_direct16_frame (v[j][3], scale (i + 3)));
+        }
+    }
+  // the peel and the tail, with the same table entries and arithmetic
+  if (blockIdx.x == 0)
+    {
+      const long long f = threadIdx.x < peel ? threadIdx.x : peel + 4 * n_groups + (threadIdx.x - peel);
+      if (f < n)
+        {
+          float sc = 1.f;
+          if (s.tab)
+            {
+              const long long gs = s.first_sample + f, b = gs / BS;
+              const float2 t = s.tab[b - s.tab_first_block];
+              sc = __fadd_rn (t.x, __fmul_rn (float (int (gs - b * BS)), t.y));
+            }
+          out[f] = encode_direct16_frame (value (f), sc);
+        }
+    }
+}
+
+hipError_t
+launch_limit_encode_segments (hipStream_t st, const LimitEncodeSegment *segs_dev, int n_segs, long long max_frames, bool mix, int limiter_block)
+{
+  if (n_segs <= 0 || max_frames <= 0)
+    return hipSuccess;
+  if (n_segs > 65535 || limiter_block < 4 * ENC_RUN)
+    return hipErrorInvalidValue;                               // a run may only straddle one block boundary
+  const dim3 grid (unsigned (std::max<long long> (1, (max_frames / 4 + ENC_RUN - 1) / ENC_RUN)), unsigned (n_segs));
+  if (mix)
+    hipLaunchKernelGGL (limit_encode_segments_kernel<true>, grid, dim3 (256), 0, st, segs_dev, limiter_block);
+  else
+    hipLaunchKernelGGL (limit_encode_segments_kernel<false>, grid, dim3 (256), 0, st, segs_dev, limiter_block);
   return hipGetLastError();
 }
 

@@ -1416,6 +1416,7 @@ awm_pcm_decode_d (awm_ctx *ctx, const void *bytes_d, size_t n_values, int bit_de
       return AWM_ERR_ARG;
     }
   const awmk::PcmFormatDev f { bit_depth / 8, encoding, big_endian != 0, 0 };
+  ProfScope ps (ctx, PROF_PCM_DECODE, double (n_values) * (bit_depth / 8 + 4));
   AWM_HIP_CHECK (awmk::launch_pcm_decode (ctx->stream, static_cast<const unsigned char *> (bytes_d), out_d, (long long) n_values, f));
   return 0;
 }
@@ -1431,6 +1432,7 @@ awm_pcm_encode_d (awm_ctx *ctx, const float *in_d, size_t n_values, int bit_dept
     }
   const bool d16 = direct16 && bit_depth == 16 && encoding == 0 && !big_endian;
   const awmk::PcmFormatDev f { bit_depth / 8, encoding, big_endian != 0, d16 };
+  ProfScope ps (ctx, PROF_PCM_ENCODE, double (n_values) * (bit_depth / 8 + 4));
   AWM_HIP_CHECK (awmk::launch_pcm_encode (ctx->stream, in_d, static_cast<unsigned char *> (bytes_d), (long long) n_values, f));
   return 0;
 }
@@ -2527,12 +2529,19 @@ struct SegmentKeys
 
 /* the fused path: segs = the segments with samples, ordered by payload; payload_of[i] = index of segment i's payload among the distinct
  * ones; coded = their codes, [distinct][2 (A, B)][n_code] bytes.  With a key per segment (mk; key is not used): ordered by (key, payload),
- * and "payload" reads "(key, payload) pair" -- a table each, expanded from the template of its key */
-static int
+ * and "payload" reads "(key, payload) pair" -- a table each, expanded from the template of its key.
+ * T = int16_t (awm_add_watermark_segments_rate_s16_d): segments of signed 16-bit PCM.  EVERY segment is staged, the
+ * r == 0 ones too -- the gather decodes on its way into ws_seg_in, K2 and the limiter's table run on the slices as for float --, and the
+ * scatter is the limiter's apply pass with a 16-bit sink: it reads the un-limited mix from ws_seg_out behind the r samples, scales,
+ * encodes and stores to out_d */
+extern "C++" {
+template<class T> static int
 add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_t>& segs, const std::vector<size_t>& payload_of,
-                    const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames, const float *const *pcm_in_d,
-                    float *const *out_d, const size_t *n_frames, SegmentKeys *mk = nullptr)
+                    const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames, const T *const *pcm_in_d,
+                    T *const *out_d, const size_t *n_frames, SegmentKeys *mk = nullptr)
 {
+  constexpr bool S16 = std::is_same<T, int16_t>::value;
+  typedef typename std::conditional<S16, awmk::LimitEncodeSegment, awmk::SegmentCopy>::type Scatter;
   constexpr size_t PER_LAUNCH = 4096;                      // (blockIdx.y <= 65535; a launch of 4096 clips fills the device many times over)
   constexpr size_t TABLE_GROUP = 1024;                     // distinct payloads whose tables exist at a time (~370 MB at the default geometry)
   constexpr size_t STAGE_MAX_FLOATS = size_t (1) << 28;    // staged samples per batch and direction (1 GiB): a batch that would need more is split
@@ -2568,7 +2577,8 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
       max_total += g.n_blocks;
       tab_total += g.n_tab + 1;
       total_frames1024 += (long long) ((g.len + FRAME - 1) / FRAME);
-      const size_t stage_floats = g.r ? (g.len * 2 + 3) / 4 * 4 : 0;
+      const bool stage = g.r || S16;
+      const size_t stage_floats = stage ? (g.len * 2 + 3) / 4 * 4 : 0;
       if (batches.empty() || i - batches.back().i0 >= PER_LAUNCH || payload_of[i] / TABLE_GROUP != payload_of[batches.back().i0] / TABLE_GROUP
           || (batches.back().stage_floats && batches.back().stage_floats + stage_floats > STAGE_MAX_FLOATS))
         batches.push_back ({ i, i, n_staged, n_staged, 0, 0, 0 });
@@ -2578,7 +2588,7 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
       b.i1 = i + 1;
       b.max_len = std::max (b.max_len, g.len);
       b.max_tab = std::max (b.max_tab, g.n_tab);
-      if (g.r)
+      if (stage)
         b.g1 = ++n_staged;
       stage_max = std::max (stage_max, b.stage_floats);
     }
@@ -2586,7 +2596,7 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
 
   // one page-locked block, one upload: the segments' kernel arguments, the gather / scatter lists of the staged ones, the payloads' codes
   const size_t off_lim = n * sizeof (awmk::AddMixArgs), off_gather = off_lim + n * sizeof (awmk::LimiterClip),
-               off_scatter = off_gather + n_staged * sizeof (awmk::SegmentCopy), off_coded = off_scatter + n_staged * sizeof (awmk::SegmentCopy),
+               off_scatter = off_gather + n_staged * sizeof (awmk::SegmentCopy), off_coded = off_scatter + n_staged * sizeof (Scatter),
                off_keys = (off_coded + coded.size() + 15) / 16 * 16;
   if (mk)
     if (int rc = mk->reserve (ctx, table_stride)) return rc;
@@ -2611,10 +2621,12 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
   char *h = ctx->pin_add_batch.as<char>(), *d = ctx->ws_add_batch.as<char>();
   auto *h_mix = reinterpret_cast<awmk::AddMixArgs *> (h);
   auto *h_lim = reinterpret_cast<awmk::LimiterClip *> (h + off_lim);
-  auto *h_gather = reinterpret_cast<awmk::SegmentCopy *> (h + off_gather), *h_scatter = reinterpret_cast<awmk::SegmentCopy *> (h + off_scatter);
+  auto *h_gather = reinterpret_cast<awmk::SegmentCopy *> (h + off_gather);
+  auto *h_scatter = reinterpret_cast<Scatter *> (h + off_scatter);
   const auto *d_mix = reinterpret_cast<const awmk::AddMixArgs *> (d);
   const auto *d_lim = reinterpret_cast<const awmk::LimiterClip *> (d + off_lim);
-  const auto *d_gather = reinterpret_cast<const awmk::SegmentCopy *> (d + off_gather), *d_scatter = reinterpret_cast<const awmk::SegmentCopy *> (d + off_scatter);
+  const auto *d_gather = reinterpret_cast<const awmk::SegmentCopy *> (d + off_gather);
+  const auto *d_scatter = reinterpret_cast<const Scatter *> (d + off_scatter);
   const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
   std::memcpy (h + off_coded, coded.data(), coded.size());
   if (mk)
@@ -2627,8 +2639,14 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
     {
       const Seg& g = geo[i];
       const size_t s = segs[i];
-      const float *in = g.r ? ctx->ws_seg_in.as<float>() + g.stage_off : pcm_in_d[s];
-      float *out = g.r ? ctx->ws_seg_out.as<float>() + g.stage_off : out_d[s];
+      const float *in = ctx->ws_seg_in.as<float>() + g.stage_off;
+      float *out = ctx->ws_seg_out.as<float>() + g.stage_off;
+      if constexpr (!S16)
+        if (!g.r)
+          {
+            in = pcm_in_d[s];
+            out = out_d[s];
+          }
       awmk::AddMixArgs a {};
       a.pcm_in = in;
       a.out = out;
@@ -2645,10 +2663,16 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
       h_lim[i] = { out, (long long) g.len, block_max + g.max_off, (long long) g.n_blocks, tabs + g.tab_off, (long long) g.n_tab,
                    (long long) g.skipped, (long long) g.first_block };
       spans[i] = ((long long) ((g.len + FRAME - 1) / FRAME) + L - 1) / L;
-      if (g.r)
+      if (g.r || S16)
         {
-          h_gather[staged] = { pcm_in_d[s], ctx->ws_seg_in.as<float>() + g.stage_off, (long long) (n_frames[s] * 2), (long long) (g.r * 2) };
-          h_scatter[staged] = { out + g.r * 2, out_d[s], (long long) (n_frames[s] * 2), 0 };
+          // (16-bit: `src` holds the address of the int16 values, launch_segment_gather_s16)
+          h_gather[staged] = { reinterpret_cast<const float *> (pcm_in_d[s]), ctx->ws_seg_in.as<float>() + g.stage_off, (long long) (n_frames[s] * 2),
+                               (long long) (g.r * 2) };
+          if constexpr (S16)
+            h_scatter[staged] = { nullptr, out + g.r * 2, out_d[s], (long long) n_frames[s], (long long) zero_frames[s],
+                                  use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.skipped / LIMITER_BLOCK) };
+          else
+            h_scatter[staged] = { out + g.r * 2, out_d[s], (long long) (n_frames[s] * 2), 0 };
           staged++;
         }
     }
@@ -2686,7 +2710,12 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
           max_spans = std::max (max_spans, spans[i]);
           values += double (geo[i].len) * 2;
         }
-      if (b.g1 > b.g0)
+      if constexpr (S16)
+        {
+          ProfScope ps (ctx, PROF_SEGMENT_GATHER_S16, values * 6.0, st);            // int16 in, float out
+          AWM_HIP_CHECK (awmk::launch_segment_gather_s16 (st, d_gather + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
+        }
+      else if (b.g1 > b.g0)
         AWM_HIP_CHECK (awmk::launch_segment_copy (st, d_gather + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
       if (use_limiter)
         {
@@ -2699,22 +2728,36 @@ add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_
         ProfScope ps (ctx, PROF_ADD_MIX, values * 8.0, st);                          // read + write every sample once
         AWM_HIP_CHECK (awmk::launch_add_mix_batch (st, ctx->tabs, d_mix + b.i0, int (nb), max_spans, int (block_frames), int (Params::frames_pad_start)));
       }
-      if (use_limiter)
+      if constexpr (S16)
         {
-          ProfScope ps (ctx, PROF_LIMITER, values * 8.0, st);
-          AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_lim + b.i0, int (nb), (long long) b.max_len, 2, LIMITER_BLOCK, LIMITER_CEILING, (long long) b.max_tab));
+          // the ramp tables alone, then limit + encode from the staged mix to the caller's buffers
+          if (use_limiter)
+            AWM_HIP_CHECK (awmk::launch_limiter_table_batch (st, d_lim + b.i0, int (nb), (long long) b.max_len, LIMITER_BLOCK, LIMITER_CEILING, (long long) b.max_tab));
+          ProfScope ps (ctx, PROF_LIMIT_ENCODE_S16, values * 6.0, st);               // float in, int16 out
+          AWM_HIP_CHECK (awmk::launch_limit_encode_segments (st, d_scatter + b.g0, int (b.g1 - b.g0), (long long) b.max_len, false, LIMITER_BLOCK));
         }
-      if (b.g1 > b.g0)
-        AWM_HIP_CHECK (awmk::launch_segment_copy (st, d_scatter + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
+      else
+        {
+          if (use_limiter)
+            {
+              ProfScope ps (ctx, PROF_LIMITER, values * 8.0, st);
+              AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_lim + b.i0, int (nb), (long long) b.max_len, 2, LIMITER_BLOCK, LIMITER_CEILING, (long long) b.max_tab));
+            }
+          if (b.g1 > b.g0)
+            AWM_HIP_CHECK (awmk::launch_segment_copy (st, d_scatter + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
+        }
     }
   return 0;
 }
+} // extern "C++"
 
 /* what both segment entry points check before anything is enqueued (fn: the entry point, for the messages), and the distinct payloads'
- * codes: payload_index[i] = index of segment i's payload among the distinct ones, coded = [distinct][2 (A, B)][n_code] bytes */
-static int
+ * codes: payload_index[i] = index of segment i's payload among the distinct ones, coded = [distinct][2 (A, B)][n_code] bytes.  T: the sample
+ * type, float or int16_t -- the buffers of a segment are n C sizeof (T) bytes, and an int16 buffer at an odd address is refused */
+extern "C++" {
+template<class T> static int
 segments_check (awm_ctx *ctx, const char *fn, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
-                const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, std::vector<size_t>& payload_index,
+                const T *const *pcm_in_d, T *const *out_d, const size_t *n_frames, int n_channels, std::vector<size_t>& payload_index,
                 std::vector<unsigned char>& coded, size_t& n_code)
 {
   if (!key || !payload_hex || !zero_frames || !pcm_in_d || !out_d || !n_frames || n_channels < 1)
@@ -2735,6 +2778,13 @@ segments_check (awm_ctx *ctx, const char *fn, const uint8_t key[16], size_t n_se
         set_error (string_printf ("%s: null pointer at index %zu", fn, i));
         return AWM_ERR_ARG;
       }
+  if (std::is_same<T, int16_t>::value)
+    for (size_t i = 0; i < n_segments; i++)
+      if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) | reinterpret_cast<uintptr_t> (out_d[i])) & 1))
+        {
+          set_error (string_printf ("%s: a buffer of 16-bit samples at an odd address at index %zu", fn, i));
+          return AWM_ERR_ARG;
+        }
   // the distinct payloads in order of appearance: parse_payload + code_encode (A and B) is all the host does per payload
   n_code = code_size (ConvBlockType::a, params().payload_size);
   std::map<std::string, size_t> distinct;
@@ -2776,7 +2826,7 @@ segments_check (awm_ctx *ctx, const char *fn, const uint8_t key[16], size_t n_se
     for (size_t i = 0; i < n_segments; i++)
       if (n_frames[i])
         {
-          const uintptr_t bytes = n_frames[i] * C * sizeof (float);
+          const uintptr_t bytes = n_frames[i] * C * sizeof (T);
           ranges.push_back ({ reinterpret_cast<uintptr_t> (pcm_in_d[i]), reinterpret_cast<uintptr_t> (pcm_in_d[i]) + bytes, i, false });
           ranges.push_back ({ reinterpret_cast<uintptr_t> (out_d[i]), reinterpret_cast<uintptr_t> (out_d[i]) + bytes, i, true });
         }
@@ -2797,6 +2847,7 @@ segments_check (awm_ctx *ctx, const char *fn, const uint8_t key[16], size_t n_se
   }
   return 0;
 }
+} // extern "C++"
 
 /* the segments with samples, by payload: the segments of a group of payloads are neighbours */
 static void
@@ -2885,12 +2936,15 @@ resample_table_args (const ResampleTable& t, int C)
 }
 
 // the three slices of a window: `in` = the segment, x44 / wm44 = slice_frames * 1024 frames each, wm = pre + n frames
-static awmk::ResampleSlice
-window_down_slice (const SegmentWindow& w, const float *in, int C, float *x44)
+// (T = int16_t: `in` of the slice holds the address of the int16 values, launch_resample_slices_s16)
+extern "C++" {
+template<class T> static awmk::ResampleSlice
+window_down_slice (const SegmentWindow& w, const T *in, int C, float *x44)
 {
-  return { in + size_t (w.p.in_first) * C, (long long) (w.p.in_last - w.p.in_first + 1), (long long) (w.Z + w.p.in_first),
+  return { reinterpret_cast<const float *> (in + size_t (w.p.in_first) * C), (long long) (w.p.in_last - w.p.in_first + 1), (long long) (w.Z + w.p.in_first),
            (long long) w.p.down_first, (long long) (w.slice_frames * Params::frame_size), x44 };
 }
+} // extern "C++"
 static awmk::AddMixArgs
 window_mix_args (const SegmentWindow& w, const float *x44, float *wm44, int C, const int8_t *frame_mod, double water_delta, int frames_per_span)
 {
@@ -2985,12 +3039,17 @@ segments_rate_fit_the_workspaces (size_t n_segments, const size_t *zero_frames, 
   return true;
 }
 
-/* the fused path (stereo): segs / payload_of / coded as for add_segments_fused */
-static int
+/* the fused path (stereo): segs / payload_of / coded as for add_segments_fused.
+ * T = int16_t (awm_add_watermark_segments_rate_s16_d): the down-resampler reads the int16 segments, K2 and the
+ * up-resampler are as for float, the mix is computed twice and stored never -- once for the block maxima, once in the last pass, which
+ * scales by the limiter's ramp, encodes and stores int16 to out_d.  No workspace beyond ws_rate_a / b / c */
+extern "C++" {
+template<class T> static int
 add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const ResampleTable& up, const uint8_t key[16], const std::vector<size_t>& segs,
                          const std::vector<size_t>& payload_of, const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames,
-                         const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int rate, SegmentKeys *mk = nullptr)
+                         const T *const *pcm_in_d, T *const *out_d, const size_t *n_frames, int rate, SegmentKeys *mk = nullptr)
 {
+  constexpr bool S16 = std::is_same<T, int16_t>::value;
   constexpr size_t PER_LAUNCH = 4096, TABLE_GROUP = 1024;  // as in add_segments_fused
   const int C = 2;
   const size_t FRAME = Params::frame_size, n = segs.size(), n_distinct = coded.size() / (2 * n_code);
@@ -3010,7 +3069,7 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
   std::vector<Seg> geo (n);
   std::vector<Batch> batches;
   std::vector<size_t> down_owner;                          // (ordered) segment whose window a down slice is made for
-  std::map<std::tuple<const float *, size_t, size_t>, size_t> shared;
+  std::map<std::tuple<const T *, size_t, size_t>, size_t> shared;
   size_t max_total = 0, tab_total = 0;
   int lim_block = 0;
   for (size_t i = 0; i < n; i++)
@@ -3076,7 +3135,8 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
   // one page-locked block, one upload: the kernel arguments of every stage and the payloads' codes
   const size_t off_mix = n_down * sizeof (awmk::ResampleSlice), off_up = off_mix + n * sizeof (awmk::AddMixArgs),
                off_mm = off_up + n * sizeof (awmk::ResampleSlice), off_lim = off_mm + n * sizeof (awmk::MixSegment),
-               off_coded = off_lim + n * sizeof (awmk::LimiterClip), off_keys = (off_coded + coded.size() + 15) / 16 * 16;
+               off_enc = off_lim + n * sizeof (awmk::LimiterClip), off_coded = off_enc + (S16 ? n * sizeof (awmk::LimitEncodeSegment) : 0),
+               off_keys = (off_coded + coded.size() + 15) / 16 * 16;
   if (mk)
     if (int rc = mk->reserve (ctx, table_stride)) return rc;
   const size_t arg_bytes = mk ? off_keys + mk->arg_bytes() : off_coded + coded.size();
@@ -3100,10 +3160,12 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
   auto *h_mix = reinterpret_cast<awmk::AddMixArgs *> (h + off_mix);
   auto *h_mm = reinterpret_cast<awmk::MixSegment *> (h + off_mm);
   auto *h_lim = reinterpret_cast<awmk::LimiterClip *> (h + off_lim);
+  auto *h_enc = reinterpret_cast<awmk::LimitEncodeSegment *> (h + off_enc);                 // (16-bit only)
   const auto *d_down = reinterpret_cast<const awmk::ResampleSlice *> (d), *d_up = reinterpret_cast<const awmk::ResampleSlice *> (d + off_up);
   const auto *d_mix = reinterpret_cast<const awmk::AddMixArgs *> (d + off_mix);
   const auto *d_mm = reinterpret_cast<const awmk::MixSegment *> (d + off_mm);
   const auto *d_lim = reinterpret_cast<const awmk::LimiterClip *> (d + off_lim);
+  const auto *d_enc = reinterpret_cast<const awmk::LimitEncodeSegment *> (d + off_enc);
   const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
   std::memcpy (h + off_coded, coded.data(), coded.size());
   if (mk)
@@ -3123,10 +3185,16 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
       const int8_t *table = ctx->ws_keytab.as<int8_t>() + (payload_of[i] % TABLE_GROUP) * table_stride;
       h_mix[i] = window_mix_args (g.w, x44 + g.x44_off, wm44 + g.wm44_off, C, table, params().water_delta, L);
       h_up[i] = window_up_slice (g.w, wm44 + g.wm44_off, C, wm + g.wm_off);
-      h_mm[i] = { pcm_in_d[s], wm + g.wm_off, out_d[s], (long long) g.w.n, (long long) g.w.pre, (long long) g.w.Z,
+      float *mix_out = nullptr;                                   // (16-bit: no mix is stored; `orig` holds the address of the int16 values)
+      if constexpr (!S16)
+        mix_out = out_d[s];
+      h_mm[i] = { reinterpret_cast<const float *> (pcm_in_d[s]), wm + g.wm_off, mix_out, (long long) g.w.n, (long long) g.w.pre, (long long) g.w.Z,
                   use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr, (long long) g.w.p.first_block, (long long) g.w.p.n_blocks };
-      h_lim[i] = { out_d[s], (long long) g.w.n, use_limiter ? block_max + g.max_off : nullptr, (long long) g.w.p.n_blocks,
+      h_lim[i] = { mix_out, (long long) g.w.n, use_limiter ? block_max + g.max_off : nullptr, (long long) g.w.p.n_blocks,
                    use_limiter ? tabs + g.tab_off : nullptr, (long long) g.w.n_tab, (long long) g.w.Z, (long long) g.w.p.first_block };
+      if constexpr (S16)
+        h_enc[i] = { pcm_in_d[s], wm + g.wm_off + g.w.pre * C, out_d[s], (long long) g.w.n, (long long) g.w.Z,
+                     use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.w.Z / size_t (g.w.p.limiter_block)) };
     }
   AWM_HIP_CHECK (hipMemcpyAsync (d, h, arg_bytes, hipMemcpyHostToDevice, st));
   AWM_HIP_CHECK (hipEventRecord (ctx->ev_add_batch, st));
@@ -3169,7 +3237,10 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
         }
       {
         ProfScope ps (ctx, PROF_RESAMPLE, down_values * 4.0, st);                     // every input and output sample once
-        AWM_HIP_CHECK (awmk::launch_resample_slices (st, ra_down, d_down + b.d0, int (b.d1 - b.d0), (long long) b.max_n44, true));
+        if constexpr (S16)
+          AWM_HIP_CHECK (awmk::launch_resample_slices_s16 (st, ra_down, d_down + b.d0, int (b.d1 - b.d0), (long long) b.max_n44, true));
+        else
+          AWM_HIP_CHECK (awmk::launch_resample_slices (st, ra_down, d_down + b.d0, int (b.d1 - b.d0), (long long) b.max_n44, true));
       }
       if (use_limiter)
         {
@@ -3186,18 +3257,33 @@ add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const Resample
         ProfScope ps (ctx, PROF_RESAMPLE, up_values * 4.0, st);
         AWM_HIP_CHECK (awmk::launch_resample_slices (st, ra_up, d_up + b.i0, int (nb), (long long) b.max_out, true));
       }
-      AWM_HIP_CHECK (awmk::launch_mix_max_segments (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, lim_block));
-      if (use_limiter)
+      size_t max_len = 0;
+      for (size_t i = b.i0; i < b.i1; i++)
+        max_len = std::max (max_len, geo[i].w.n);
+      if constexpr (S16)
         {
-          ProfScope ps (ctx, PROF_LIMITER, out_values * 8.0, st);
-          size_t max_len = 0;
-          for (size_t i = b.i0; i < b.i1; i++)
-            max_len = std::max (max_len, geo[i].w.n);
-          AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_lim + b.i0, int (nb), (long long) max_len, C, lim_block, LIMITER_CEILING, (long long) b.max_tab));
+          // the block maxima from the mix, the ramp tables, then the mix again: limited, encoded and stored as int16
+          if (use_limiter)
+            {
+              AWM_HIP_CHECK (awmk::launch_max_segments_s16 (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, lim_block));
+              AWM_HIP_CHECK (awmk::launch_limiter_table_batch (st, d_lim + b.i0, int (nb), (long long) max_len, lim_block, LIMITER_CEILING, (long long) b.max_tab));
+            }
+          ProfScope ps (ctx, PROF_LIMIT_ENCODE_S16, out_values * 8.0, st);            // int16 and float in, int16 out
+          AWM_HIP_CHECK (awmk::launch_limit_encode_segments (st, d_enc + b.i0, int (nb), (long long) max_len, true, lim_block));
+        }
+      else
+        {
+          AWM_HIP_CHECK (awmk::launch_mix_max_segments (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, lim_block));
+          if (use_limiter)
+            {
+              ProfScope ps (ctx, PROF_LIMITER, out_values * 8.0, st);
+              AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_lim + b.i0, int (nb), (long long) max_len, C, lim_block, LIMITER_CEILING, (long long) b.max_tab));
+            }
         }
     }
   return 0;
 }
+} // extern "C++"
 
 int
 awm_add_watermark_segments_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
@@ -3398,6 +3484,106 @@ awm_add_watermark_segments_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size_
   if (segs.empty())
     return 0;
   return add_segments_rate_fused (ctx, *down, *up, nullptr, segs, table_of, coded_tables, n_code, zero_frames, pcm_in_d, out_d, n_frames, sample_rate, &mk);
+}
+
+/* ---- segments of signed 16-bit PCM: awm_add_watermark_segments_rate_s16_d / _keys_rate_s16_d (include/awm_hip.h).
+ * One body for both (per_key: keys + 16 i is the key of segment i) and for every rate.  The fused paths above with T = int16_t take stereo
+ * batches whose pointers are 4-byte aligned; everything else goes segment by segment through the definition itself: awm_pcm_decode_d into
+ * ws_seg_in, the float path of one segment into ws_seg_out, awm_pcm_encode_d (direct16) into the caller's buffer. ---- */
+static int
+add_segments_s16 (awm_ctx *ctx, const char *fn, const uint8_t *keys, bool per_key, size_t n_segments, const char *const *payload_hex,
+                  const size_t *zero_frames, const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
+{
+  AWM_ENTER (ctx);
+  g_add_segments_fused_in_use = 0;
+  const bool at_rate = sample_rate != Params::mark_sample_rate;
+  awm_segment_plan probe {};
+  if (at_rate && awm_add_segment_plan (sample_rate, 0, 0, &probe))
+    {
+      set_error (sample_rate <= 0 ? string_printf ("%s: bad sample rate %d", fn, sample_rate)
+                                  : string_printf ("%s: no fixed-ratio resampler between %d Hz and %d Hz (zita's VResampler is not offered here)", fn,
+                                                   sample_rate, Params::mark_sample_rate));
+      return AWM_ERR_ARG;
+    }
+  if (!n_segments)
+    return 0;
+  std::vector<size_t> payload_index;
+  std::vector<unsigned char> coded;
+  size_t n_code = 0;
+  if (int rc = segments_check (ctx, fn, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, payload_index, coded, n_code))
+    return rc;
+  const ResampleTable *down = nullptr, *up = nullptr;
+  if (at_rate)
+    {
+      for (size_t i = 0; i < n_segments; i++)
+        if (awm_add_segment_plan (sample_rate, zero_frames[i], n_frames[i], &probe))
+          {
+            set_error (string_printf ("%s: zero_frames + n_frames of segment %zu is not below 2^40", fn, i));
+            return AWM_ERR_ARG;
+          }
+      down = ctx->get_resample_table (sample_rate, Params::mark_sample_rate);
+      up = ctx->get_resample_table (Params::mark_sample_rate, sample_rate);
+      if (!down || !up)
+        return AWM_ERR_HIP;
+    }
+  if (per_key && segments_share_one_key (keys, n_segments))      // one key for all segments IS the one-key call
+    per_key = false;
+  // the fused paths: stereo, a stereo frame one load or store; at a rate the floor of the batched limiter and windows that fit the workspaces
+  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2;
+  if (at_rate)
+    fused = fused && probe.limiter_block >= 8192 && segments_rate_fit_the_workspaces (n_segments, zero_frames, n_frames, n_channels, sample_rate);
+  for (size_t i = 0; i < n_segments && fused; i++)
+    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) | reinterpret_cast<uintptr_t> (out_d[i])) & 3))
+      fused = false;
+  if (!fused)
+    {
+      for (size_t i = 0; i < n_segments; i++)
+        if (n_frames[i])
+          {
+            const size_t n_values = n_frames[i] * size_t (n_channels);
+            if (int rc = ctx->ws_seg_in.reserve (n_values * sizeof (float))) return rc;
+            if (int rc = ctx->ws_seg_out.reserve (n_values * sizeof (float))) return rc;
+            float *f = ctx->ws_seg_in.as<float>(), *g = ctx->ws_seg_out.as<float>();
+            const uint8_t *key = per_key ? keys + 16 * i : keys;
+            if (int rc = awm_pcm_decode_d (ctx, pcm_in_d[i], n_values, 16, 0, 0, f)) return rc;
+            if (int rc = at_rate ? add_segment_rate (ctx, *down, *up, key, payload_hex[i], zero_frames[i], f, g, n_frames[i], n_channels, sample_rate)
+                                 : add_segment_stream (ctx, key, payload_hex[i], zero_frames[i], f, g, n_frames[i], n_channels))
+              return rc;
+            if (int rc = awm_pcm_encode_d (ctx, g, n_values, 16, 0, 0, 1, out_d[i])) return rc;
+          }
+      return 0;
+    }
+  SegmentKeys mk;
+  std::vector<size_t> segs, table_of;
+  std::vector<unsigned char> coded_tables;
+  if (per_key)
+    segments_by_key_and_payload (n_segments, keys, n_frames, payload_index, coded, n_code, mk, segs, table_of, coded_tables);
+  else
+    segments_by_payload (n_segments, n_frames, payload_index, segs, table_of);
+  g_add_segments_fused_in_use = 1;
+  if (segs.empty())
+    return 0;
+  const std::vector<unsigned char>& codes = per_key ? coded_tables : coded;
+  if (at_rate)
+    return add_segments_rate_fused (ctx, *down, *up, per_key ? nullptr : keys, segs, table_of, codes, n_code, zero_frames, pcm_in_d, out_d, n_frames,
+                                    sample_rate, per_key ? &mk : nullptr);
+  return add_segments_fused (ctx, per_key ? nullptr : keys, segs, table_of, codes, n_code, zero_frames, pcm_in_d, out_d, n_frames, per_key ? &mk : nullptr);
+}
+
+int
+awm_add_watermark_segments_rate_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                       const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
+{
+  return add_segments_s16 (ctx, "awm_add_watermark_segments_rate_s16_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, sample_rate);
+}
+
+int
+awm_add_watermark_segments_keys_rate_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                            const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
+{
+  return add_segments_s16 (ctx, "awm_add_watermark_segments_keys_rate_s16_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, sample_rate);
 }
 
 /* K16t alone (measurements, tests): the templates of n_keys keys built on the device, KEY_TMPL_LAUNCH per launch, and copied to the host,

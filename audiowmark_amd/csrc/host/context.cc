@@ -600,7 +600,8 @@ static const char *prof_names[awm::PROF_COUNT] = {
   "resample_kernel", "resample_var_kernel", "speed_mags_kernel", "speed_compare_kernel", "frame_mod_table_kernel",
   "add_mix_multi_kernel", "payload_table_kernel",
   "resample_mix_multi_kernel", "clip_resample_pad_kernel", "key_template_kernel", "clip_stage_mixed_kernel",
-  "clip_pad_s16_kernel", "clip_resample_pad_s16_kernel", "clip_stage_mixed_s16_kernel"
+  "clip_pad_s16_kernel", "clip_resample_pad_s16_kernel", "clip_stage_mixed_s16_kernel",
+  "pcm_decode_kernel", "pcm_encode_kernel", "segment_gather_s16_kernel", "limit_encode_s16_kernel"
 };
 
 extern "C" {

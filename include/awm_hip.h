@@ -358,6 +358,39 @@ int awm_add_watermark_segments_keys_d (awm_ctx *ctx, const uint8_t *keys, size_t
 int awm_add_watermark_segments_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex,
                                             const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
                                             int n_channels, int sample_rate);
+/* The segment batches FROM AND TO SIGNED 16-BIT PCM (little-endian, interleaved: what a decoder hands out and an encoder takes back, the
+ * reference's native rule, rawconverter.cc:197-198) -- no float copy of a segment that the caller can see, no decode or encode launch
+ * per segment.  Segment i = n_frames[i] frames of n_channels int16 values at pcm_in_d[i]; out_d[i] receives as many.  sample_rate == 44100
+ * is the 44.1 kHz form (there are no symbols of their own for it).
+ * Definition: with f_i = what awm_pcm_decode_d (ctx, pcm_in_d[i], n_frames[i] * n_channels, 16, 0, 0, f_i) writes and g_i = what
+ * awm_add_watermark_segments_rate_d (the keys form: awm_add_watermark_segments_keys_rate_d, with keys + 16 i) writes for segment i on the
+ * inputs f_i, out_d[i] is value for value what awm_pcm_encode_d (ctx, g_i, n, 16, 0, 0, 1, out_d[i]) writes: v * 32768, saturated at 32767
+ * and -32768, truncated.
+ * Rules: those of the float functions -- AWM_ERR_ARG with nothing enqueued and nothing written, the index of the offending segment in
+ * awm_last_error, aliasing inputs, empty segments and n_segments == 0 accepted, refused while the SNR meter is armed, the rate and 2^40, the
+ * context's water_delta, mix, frames_per_bit and test_no_limiter, keys == NULL, one key for all segments IS the one-key call.  The overlap
+ * sweep works on the byte ranges of n C 2 bytes; a pcm_in_d[i] or out_d[i] at an odd address is refused.  Pointers need only 2-byte
+ * alignment, and nothing outside [out_d[i], out_d[i] + n C) is written.
+ * The fused paths take stereo, n_segments >= 2 and every pointer 4-byte aligned (a stereo frame is one load or store; at a rate: at least
+ * 8192 Hz).  The float intermediates are the context's batch workspaces of the float paths and nothing else, and the number of launches
+ * does not depend on n_segments.  At a rate: K10w down READS THE 16-BIT VALUES (the kernel instantiated for 16-bit input: a value is
+ * converted once, where it leaves global memory; segments that agree in input, length and offset share one slice), K2 and K10w up are
+ * unchanged, the block maxima come from decode (in) + wm without a stored mix, and one last kernel computes that sum again, scales by the
+ * limiter's ramp, encodes and stores int16 to out_d.  At 44.1 kHz: one gather decodes every segment into its staged slice ("r zeros, then
+ * the segment", the r == 0 segments too), K2 and the limiter's table run there, and the limiter's apply pass with a 16-bit sink reads the
+ * un-limited mix behind the r samples, scales, encodes and stores to out_d.
+ * Everything else (other channel counts, a pointer that is only 2-byte aligned, a single segment, awm_debug_set_add_batched (0), at a rate a
+ * segment whose window exceeds a workspace) goes segment by segment through the definition: decode into a context workspace, the float
+ * path of one segment, encode into out_d[i]; awm_ctx_trim gives the workspace back, awm_debug_add_segments_fused_in_use () tells which path
+ * ran.
+ * Not offered in this form: other sample formats, `add` batches of whole clips, the tile stream, the command line, the file level (which
+ * converts its files' formats itself), the awm_multi_* / sharded forms. */
+int awm_add_watermark_segments_rate_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
+                                           const size_t *zero_frames, const int16_t *const *pcm_in_d, int16_t *const *out_d,
+                                           const size_t *n_frames, int n_channels, int sample_rate);
+int awm_add_watermark_segments_keys_rate_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex,
+                                                const size_t *zero_frames, const int16_t *const *pcm_in_d, int16_t *const *out_d,
+                                                const size_t *n_frames, int n_channels, int sample_rate);
 /* The window of one such segment (pure host arithmetic, no context, no device; the device path calls it per segment).  Frames and samples
  * are indices into the segment's stream: at 44.1 kHz for the frames (of 1024 samples) and the down_* samples, at sample_rate otherwise. */
 typedef struct
@@ -518,7 +551,7 @@ int awm_get_batch_rates_plan (size_t n_clips, const size_t *n_frames, const int 
  * those of awm_get_watermark_batch_rates_d for the rates (except that sample_rates may be NULL), an odd pcm_d[i], a NULL pcm_d[i] with
  * n_frames[i] > 0.  n_clips == 0 returns 0; an empty clip gives n_out[i] = 0.
  * Not offered in this form: other sample formats, a format per clip, the command line, the file level (which converts its files' formats
- * itself), the awm_multi_* / sharded batches, the `add` side. */
+ * itself), the awm_multi_* / sharded batches.  The `add` side: awm_add_watermark_segments_rate_s16_d, for the segment batches. */
 int awm_get_watermark_batch_rates_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t n_clips, const int16_t *const *pcm_d,
                                          const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads,
                                          size_t max_out_per_clip, awm_pattern *out, int *n_out);
