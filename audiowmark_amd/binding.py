@@ -139,6 +139,10 @@ lib.awm_add_watermark_segments_keys_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp
 lib.awm_add_watermark_segments_keys_rate_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
 lib.awm_add_watermark_segments_rate_s16_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
 lib.awm_add_watermark_segments_keys_rate_s16_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
+lib.awm_add_watermark_segments_rates_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
+lib.awm_add_watermark_segments_keys_rates_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
+lib.awm_add_watermark_segments_rates_s16_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
+lib.awm_add_watermark_segments_keys_rates_s16_d.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
 
 
 class SegmentPlan(C.Structure):
@@ -449,6 +453,7 @@ def _add_segments_s16(ctx, name, key_arg, payloads, segments, zero_frames, outs,
         raise ValueError(name + ": payloads, segments and zero_frames must have one length")
     if not segments:
         return []
+    per_segment, rates = _segment_rates(sample_rate, len(segments))
     if any(s.dtype != torch.int16 or not s.is_cuda or not s.is_contiguous() for s in segments):
         raise ValueError(name + ": the segments must be contiguous int16 tensors on the device")
     shapes = [(s.shape[0], 1 if s.dim() == 1 else s.shape[1]) for s in segments]
@@ -465,6 +470,10 @@ def _add_segments_s16(ctx, name, key_arg, payloads, segments, zero_frames, outs,
     src = (C.c_void_p * n)(*[_dev_ptr(s) for s in segments])
     dst = (C.c_void_p * n)(*[_dev_ptr(o) for o in outs])
     frames = (C.c_size_t * n)(*[s[0] for s in shapes])
+    if per_segment:
+        name = name.replace("_rate_s16_d", "_rates_s16_d")
+        _check(getattr(lib, name)(ctx._h, key_arg, n, hexes, zf, src, dst, frames, ch, rates), name)
+        return outs
     _check(getattr(lib, name)(ctx._h, key_arg, n, hexes, zf, src, dst, frames, ch, int(sample_rate)), name)
     return outs
 
@@ -507,6 +516,15 @@ def _rates_array(sample_rate, n_clips):
     if len(rates) != n_clips:
         raise ValueError(f"sample_rate: {len(rates)} rates for {n_clips} clips")
     return (C.c_int * n_clips)(*rates)
+
+
+def _segment_rates(sample_rate, n_segments):
+    """the sample_rate argument of the segment batches -> (a rate per segment?, C int array or None).  An int is one rate for the call; a
+    sequence (one rate per segment: ValueError before anything is called otherwise) and None (no array: NULL) take the *_rates_* entry points"""
+    if sample_rate is None:
+        return True, None
+    rates = _rates_array(sample_rate, n_segments)
+    return rates is not None, rates
 
 
 def get_batch_rates_plan(n_frames, sample_rates):
@@ -782,13 +800,16 @@ class Context:
         payloads[i] and starting zero_frames[i] samples into its stream; at 44.1 kHz outs[i] == add_watermark_tiles(key, payloads[i],
         segments[i], zero_frames=zero_frames[i]) bit for bit.  Segments may be one tensor many times (one programme, many subscribers).
         Another sample_rate: awm_add_watermark_segments_rate_d; outs[i] == add_watermark(key, payloads[i], zero_frames[i] zeros + segments[i],
-        sample_rate)[zero_frames[i]:] bit for bit, computed from a window around the segment."""
+        sample_rate)[zero_frames[i]:] bit for bit, computed from a window around the segment.
+        sample_rate may be a sequence with one rate per segment (a queue that is not sorted by rate, awm_add_watermark_segments_rates_d):
+        outs[i] is bit for bit what the call with segment i alone at sample_rate[i] gives.  The same holds for the three twins below."""
         import torch
         payloads, segments, zero_frames = list(payloads), list(segments), list(zero_frames)
         if not (len(payloads) == len(segments) == len(zero_frames)):
             raise ValueError("add_watermark_segments: payloads, segments and zero_frames must have one length")
         if not segments:
             return []
+        per_segment, rates = _segment_rates(sample_rate, len(segments))
         shapes = [_pcm_shape(s) for s in segments]
         ch = shapes[0][1]
         if any(s[1] != ch for s in shapes):
@@ -803,6 +824,10 @@ class Context:
         src = (C.c_void_p * n)(*[_dev_ptr(s) for s in segments])
         dst = (C.c_void_p * n)(*[_dev_ptr(o) for o in outs])
         frames = (C.c_size_t * n)(*[s[0] for s in shapes])
+        if per_segment:
+            _check(lib.awm_add_watermark_segments_rates_d(self._h, key_bytes(key), n, hexes, zf, src, dst, frames, ch, rates),
+                   "awm_add_watermark_segments_rates_d")
+            return outs
         if sample_rate != 44100:
             _check(lib.awm_add_watermark_segments_rate_d(self._h, key_bytes(key), n, hexes, zf, src, dst, frames, ch, sample_rate),
                    "awm_add_watermark_segments_rate_d")
@@ -819,6 +844,7 @@ class Context:
             raise ValueError("add_watermark_segments_keys: keys, payloads, segments and zero_frames must have one length")
         if not segments:
             return []
+        per_segment, rates = _segment_rates(sample_rate, len(segments))
         shapes = [_pcm_shape(s) for s in segments]
         ch = shapes[0][1]
         if any(s[1] != ch for s in shapes):
@@ -834,6 +860,10 @@ class Context:
         src = (C.c_void_p * n)(*[_dev_ptr(s) for s in segments])
         dst = (C.c_void_p * n)(*[_dev_ptr(o) for o in outs])
         frames = (C.c_size_t * n)(*[s[0] for s in shapes])
+        if per_segment:
+            _check(lib.awm_add_watermark_segments_keys_rates_d(self._h, kb, n, hexes, zf, src, dst, frames, ch, rates),
+                   "awm_add_watermark_segments_keys_rates_d")
+            return outs
         if sample_rate != 44100:
             _check(lib.awm_add_watermark_segments_keys_rate_d(self._h, kb, n, hexes, zf, src, dst, frames, ch, sample_rate),
                    "awm_add_watermark_segments_keys_rate_d")

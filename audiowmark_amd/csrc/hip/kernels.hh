@@ -245,6 +245,42 @@ hipError_t launch_mix_max_segment (hipStream_t st, const MixSegment& seg, int n_
  * decoded as they are read): the same add, the same maxima, `out` is not read or written */
 hipError_t launch_max_segments_s16 (hipStream_t st, const MixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int limiter_block);
 
+/* The SEGMENT BATCHES WITH A RATE PER SEGMENT (awm_add_watermark_segments_rates_d): the launchers above whose
+ * launch-uniform rate-dependent argument -- the resampler's geometry, the limiter block -- comes from the descriptor of blockIdx.y instead.
+ * Each descriptor is the one-rate descriptor and the rate's values behind it; each kernel reads them once per workgroup (uniform: scalar
+ * registers) and runs the body of its one-rate kernel, so slice / segment i is bit for bit what the one-rate launcher writes for it with
+ * that rate's arguments.  Grids are sized by the longest slice / segment / ramp table of the batch, the launchers' lower bounds on the
+ * limiter block hold for min_limiter_block, the smallest of the batch.
+ * K10w: ctab / hl / np / step of the slice's table (down: rate -> 44.1 kHz, up: 44.1 kHz -> rate), lds_floats = floats of the table in LDS
+ * or 0 (taps from global memory), in_span = frames of the tile's window or 0 (not staged) -- resample_slice_geometry fills both as
+ * launch_resample_slices decides for a launch at that rate.  Dynamic LDS is the largest table + window among the slices (lds_bytes: the
+ * maximum of resample_slice_lds_bytes over them). */
+struct RateResampleSlice
+{
+  ResampleSlice s;
+  const float  *ctab;
+  int           hl, np, step;
+  int           lds_floats, in_span;
+};
+void       resample_slice_geometry (RateResampleSlice& r /* ctab, hl, np, step set */, int n_channels, bool stereo_aligned);
+size_t     resample_slice_lds_bytes (const RateResampleSlice& r);
+hipError_t launch_resample_slices_rates (hipStream_t st, const RateResampleSlice *slices_dev, int n_slices, int n_channels, long long max_n_out,
+                                         bool stereo_aligned, size_t lds_bytes);
+hipError_t launch_resample_slices_rates_s16 (hipStream_t st, const RateResampleSlice *slices_dev, int n_slices, int n_channels, long long max_n_out,
+                                             bool stereo_aligned, size_t lds_bytes);
+struct RateMixSegment { MixSegment s; int limiter_block; };
+hipError_t launch_mix_max_segments_rates (hipStream_t st, const RateMixSegment *segs_dev, int n_segs, long long max_frames, int n_channels,
+                                          int min_limiter_block);
+hipError_t launch_max_segments_rates_s16 (hipStream_t st, const RateMixSegment *segs_dev, int n_segs, long long max_frames, int n_channels,
+                                          int min_limiter_block);
+struct RateLimiterClip { LimiterClip c; int limiter_block; };
+hipError_t launch_limiter_table_batch_rates (hipStream_t st, const RateLimiterClip *clips_dev, int n_clips, float ceiling, long long max_tab);
+hipError_t launch_limiter_batch_rates (hipStream_t st, const RateLimiterClip *clips_dev, int n_clips, long long max_frames, int n_channels,
+                                       int min_limiter_block, float ceiling, long long max_tab);
+struct RateLimitEncodeSegment { LimitEncodeSegment s; int limiter_block; };
+hipError_t launch_limit_encode_segments_rates (hipStream_t st, const RateLimitEncodeSegment *segs_dev, int n_segs, long long max_frames, bool mix,
+                                               int min_limiter_block);
+
 /* `add --snr`: acc[0] += sum (mixed - orig)^2, acc[1] += sum orig^2 in double (reference wmadd.cc:553-563) */
 hipError_t launch_power_sums (hipStream_t st, const float *orig, const float *mixed, long long n_values, double *acc);
 

@@ -1203,10 +1203,9 @@ limiter_apply_kernel (float4 *data, long long n_vec, long long first_sample, con
 /* K3 for a batch of clips, every clip a stream of its own: blockIdx.y = clip.  data[0] is sample first_sample of the clip's stream and
  * block_max[0] belongs to limiter block first_block (launch_limiter's meaning; 0 / 0: the stream starts at sample 0); the ramp table
  * begins at the block of first_sample. */
-__global__ void
-limiter_table_batch_kernel (const LimiterClip *clips, int BS, float ceiling)
+__device__ __forceinline__ void
+limiter_table_clip_body (const LimiterClip& c, int BS, float ceiling)
 {
-  const LimiterClip c = clips[blockIdx.y];
   const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= c.n_tab)
     return;
@@ -1222,11 +1221,23 @@ limiter_table_batch_kernel (const LimiterClip *clips, int BS, float ceiling)
   const float scale_end   = __fdiv_rn (ceiling, fmaxf (m_cur, m_next));
   c.tab[k] = make_float2 (scale_start, __fdiv_rn (__fsub_rn (scale_end, scale_start), float (BS)));
 }
-
-template<int C> __global__ void __launch_bounds__ (256)
-limiter_apply_batch_kernel (const LimiterClip *clips, int BS)
+__global__ void
+limiter_table_batch_kernel (const LimiterClip *clips, int BS, float ceiling)
 {
   const LimiterClip c = clips[blockIdx.y];
+  limiter_table_clip_body (c, BS, ceiling);
+}
+// (a limiter block per clip: RateLimiterClip, kernels.hh)
+__global__ void
+limiter_table_batch_rates_kernel (const RateLimiterClip *clips, float ceiling)
+{
+  const RateLimiterClip r = clips[blockIdx.y];
+  limiter_table_clip_body (r.c, r.limiter_block, ceiling);
+}
+
+template<int C> __device__ __forceinline__ void
+limiter_apply_clip_body (const LimiterClip& c, int BS)
+{
   const long long n_values = c.n_frames * C, n_vec = n_values / 4;
   const long long tab_first = c.first_sample / BS;
   if ((long long) blockIdx.x * LIMITER_RUN < n_vec)
@@ -1238,6 +1249,18 @@ limiter_apply_batch_kernel (const LimiterClip *clips, int BS)
       const float2 t = c.tab[b - tab_first];
       c.data[v] = __fmul_rn (c.data[v], __fadd_rn (t.x, __fmul_rn (float (int (f - b * BS)), t.y)));
     }
+}
+template<int C> __global__ void __launch_bounds__ (256)
+limiter_apply_batch_kernel (const LimiterClip *clips, int BS)
+{
+  const LimiterClip c = clips[blockIdx.y];
+  limiter_apply_clip_body<C> (c, BS);
+}
+template<int C> __global__ void __launch_bounds__ (256)
+limiter_apply_batch_rates_kernel (const RateLimiterClip *clips)
+{
+  const RateLimiterClip r = clips[blockIdx.y];
+  limiter_apply_clip_body<C> (r.c, r.limiter_block);
 }
 
 hipError_t
@@ -1270,6 +1293,36 @@ launch_limiter_batch (hipStream_t st, const LimiterClip *clips_dev, int n_clips,
     hipLaunchKernelGGL (limiter_apply_batch_kernel<2>, grid, dim3 (256), 0, st, clips_dev, limiter_block);
   else
     hipLaunchKernelGGL (limiter_apply_batch_kernel<1>, grid, dim3 (256), 0, st, clips_dev, limiter_block);
+  return hipGetLastError();
+}
+
+hipError_t
+launch_limiter_table_batch_rates (hipStream_t st, const RateLimiterClip *clips_dev, int n_clips, float ceiling, long long max_tab)
+{
+  if (n_clips <= 0 || max_tab <= 0)
+    return hipSuccess;
+  if (n_clips > 65535)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL (limiter_table_batch_rates_kernel, dim3 (unsigned ((max_tab + 255) / 256), unsigned (n_clips)), dim3 (256), 0, st, clips_dev, ceiling);
+  return hipGetLastError();
+}
+
+hipError_t
+launch_limiter_batch_rates (hipStream_t st, const RateLimiterClip *clips_dev, int n_clips, long long max_frames, int n_channels, int min_limiter_block,
+                            float ceiling, long long max_tab)
+{
+  if (n_clips <= 0 || max_frames <= 0)
+    return hipSuccess;
+  if ((n_channels != 1 && n_channels != 2) || min_limiter_block < 4 * LIMITER_RUN || max_tab <= 0)
+    return hipErrorInvalidValue;
+  if (hipError_t e = launch_limiter_table_batch_rates (st, clips_dev, n_clips, ceiling, max_tab))
+    return e;
+  const long long max_vec = std::max<long long> (1, max_frames * n_channels / 4);
+  const dim3 grid (unsigned ((max_vec + LIMITER_RUN - 1) / LIMITER_RUN), unsigned (n_clips));
+  if (n_channels == 2)
+    hipLaunchKernelGGL (limiter_apply_batch_rates_kernel<2>, grid, dim3 (256), 0, st, clips_dev);
+  else
+    hipLaunchKernelGGL (limiter_apply_batch_rates_kernel<1>, grid, dim3 (256), 0, st, clips_dev);
   return hipGetLastError();
 }
 
@@ -1905,6 +1958,70 @@ launch_resample_slices_s16 (hipStream_t st, const ResampleArgs& a, const Resampl
 {
   return launch_resample_slices_any<PcmS16> (st, a, slices_dev, nullptr, n_slices, max_n_out, stereo_aligned);
 }
+
+/* K10w with a geometry per slice (kernels.hh RateResampleSlice): the descriptor of blockIdx.y brings the table and what the one-rate
+ * launcher derives from it; a workgroup reads it once (uniform: scalar registers) and runs resample_slice_body.  The window of a slice
+ * begins behind ITS table in the dynamic LDS, which is sized for the largest table + window of the batch */
+template<int CT, class In = PcmF32> __global__ void __launch_bounds__ (256)
+resample_slices_rates_kernel (const RateResampleSlice *slices, int n_channels, int tiles_per_wg)
+{
+  const RateResampleSlice r = slices[blockIdx.y];
+  ResampleArgs a {};
+  a.n_channels = n_channels;
+  a.ctab = r.ctab;
+  a.hl = r.hl;
+  a.np = r.np;
+  a.step = r.step;
+  ResampleStore sink { r.s.out };
+  resample_slice_body<CT, In> (a, r.s, r.lds_floats, r.in_span, tiles_per_wg, sink);
+}
+
+void
+resample_slice_geometry (RateResampleSlice& r, int n_channels, bool stereo_aligned)
+{
+  // the table and the tile's window in LDS exactly as launch_resample_slices_any sizes them for a launch with this table
+  const int want = (r.np + 1) * (r.hl | 1);
+  r.lds_floats = want <= RS_MAX_TAB ? want : 0;
+  const long long span = ((long long) (RS_TILE - 1) * r.step) / r.np + 2 + 2LL * r.hl;
+  const bool stage = n_channels == 2 && stereo_aligned && r.lds_floats > 0 && span <= 4096 && (long long) RS_TILE * r.step + r.np < (1LL << 31);
+  r.in_span = stage ? int (span) : 0;
+}
+size_t
+resample_slice_lds_bytes (const RateResampleSlice& r)
+{
+  return size_t ((r.lds_floats + 1) & ~1) * sizeof (float) + size_t (r.in_span) * sizeof (float2);
+}
+template<class In> static hipError_t
+launch_resample_slices_rates_any (hipStream_t st, const RateResampleSlice *slices_dev, int n_slices, int n_channels, long long max_n_out,
+                                  bool stereo_aligned, size_t lds_bytes)
+{
+  if (n_slices <= 0 || max_n_out <= 0)
+    return hipSuccess;
+  // (the largest a one-rate launch can ask for: RS_MAX_TAB floats of table and 4096 frames of window)
+  if (n_slices > 65535 || n_channels < 1 || lds_bytes > size_t ((RS_MAX_TAB + 1) & ~1) * sizeof (float) + 4096 * sizeof (float2))
+    return hipErrorInvalidValue;
+  const long long n_tiles = (max_n_out + RS_TILE - 1) / RS_TILE;
+  const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles * n_slices / 4096)));
+  const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg), unsigned (n_slices));
+  if (n_channels == 2 && stereo_aligned)
+    hipLaunchKernelGGL ((resample_slices_rates_kernel<2, In>), grid, dim3 (256), lds_bytes, st, slices_dev, n_channels, tiles_per_wg);
+  else
+    hipLaunchKernelGGL ((resample_slices_rates_kernel<0, In>), grid, dim3 (256), lds_bytes, st, slices_dev, n_channels, tiles_per_wg);
+  return hipGetLastError();
+}
+hipError_t
+launch_resample_slices_rates (hipStream_t st, const RateResampleSlice *slices_dev, int n_slices, int n_channels, long long max_n_out,
+                              bool stereo_aligned, size_t lds_bytes)
+{
+  return launch_resample_slices_rates_any<PcmF32> (st, slices_dev, n_slices, n_channels, max_n_out, stereo_aligned, lds_bytes);
+}
+hipError_t
+launch_resample_slices_rates_s16 (hipStream_t st, const RateResampleSlice *slices_dev, int n_slices, int n_channels, long long max_n_out,
+                                  bool stereo_aligned, size_t lds_bytes)
+{
+  return launch_resample_slices_rates_any<PcmS16> (st, slices_dev, n_slices, n_channels, max_n_out, stereo_aligned, lds_bytes);
+}
+
 hipError_t
 launch_resample_slice (hipStream_t st, const ResampleArgs& a, const ResampleSlice& slice)
 {
@@ -2100,6 +2217,19 @@ max_segments_s16_kernel (const MixSegment *segs, int C, int BS)
   const MixSegment s = segs[blockIdx.y];
   mix_max_segment_body<PcmS16, false> (s, C, BS);
 }
+// (a limiter block per segment: RateMixSegment, kernels.hh)
+__global__ void __launch_bounds__ (256)
+mix_max_segments_rates_kernel (const RateMixSegment *segs, int C)
+{
+  const RateMixSegment r = segs[blockIdx.y];
+  mix_max_segment_body (r.s, C, r.limiter_block);
+}
+__global__ void __launch_bounds__ (256)
+max_segments_rates_s16_kernel (const RateMixSegment *segs, int C)
+{
+  const RateMixSegment r = segs[blockIdx.y];
+  mix_max_segment_body<PcmS16, false> (r.s, C, r.limiter_block);
+}
 
 hipError_t
 launch_mix_max_segments (hipStream_t st, const MixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int limiter_block)
@@ -2123,6 +2253,30 @@ launch_max_segments_s16 (hipStream_t st, const MixSegment *segs_dev, int n_segs,
   const long long max_values = max_frames * n_channels;
   hipLaunchKernelGGL (max_segments_s16_kernel, dim3 (unsigned ((max_values + MIX_RUN - 1) / MIX_RUN), unsigned (n_segs)), dim3 (256), 0, st,
                       segs_dev, n_channels, limiter_block);
+  return hipGetLastError();
+}
+hipError_t
+launch_mix_max_segments_rates (hipStream_t st, const RateMixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int min_limiter_block)
+{
+  if (n_segs <= 0 || max_frames <= 0)
+    return hipSuccess;
+  if (n_segs > 65535 || n_channels < 1 || (long long) min_limiter_block * n_channels < MIX_RUN)
+    return hipErrorInvalidValue;                               // a run may only straddle one block boundary
+  const long long max_values = max_frames * n_channels;
+  hipLaunchKernelGGL (mix_max_segments_rates_kernel, dim3 (unsigned ((max_values + MIX_RUN - 1) / MIX_RUN), unsigned (n_segs)), dim3 (256), 0, st,
+                      segs_dev, n_channels);
+  return hipGetLastError();
+}
+hipError_t
+launch_max_segments_rates_s16 (hipStream_t st, const RateMixSegment *segs_dev, int n_segs, long long max_frames, int n_channels, int min_limiter_block)
+{
+  if (n_segs <= 0 || max_frames <= 0)
+    return hipSuccess;
+  if (n_segs > 65535 || n_channels < 1 || (long long) min_limiter_block * n_channels < MIX_RUN)
+    return hipErrorInvalidValue;
+  const long long max_values = max_frames * n_channels;
+  hipLaunchKernelGGL (max_segments_rates_s16_kernel, dim3 (unsigned ((max_values + MIX_RUN - 1) / MIX_RUN), unsigned (n_segs)), dim3 (256), 0, st,
+                      segs_dev, n_channels);
   return hipGetLastError();
 }
 hipError_t
@@ -4528,10 +4682,9 @@ encode_direct16_frame (float2 v, float scale)
   const int i1 = s1 >= 32767.f ? 32767 : (s1 <= -32768.f ? -32768 : int (s1));
   return ((unsigned int) i0 & 0xffffu) | ((unsigned int) i1 << 16);
 }
-template<bool MIX> __global__ void __launch_bounds__ (256)
-limit_encode_segments_kernel (const LimitEncodeSegment *segs, int BS)
+template<bool MIX> __device__ __forceinline__ void
+limit_encode_segment_body (const LimitEncodeSegment& s, int BS)
 {
-  const LimitEncodeSegment s = segs[blockIdx.y];
   const long long n = s.n_frames;
   const long long to_grid = (long long) (((16 - (reinterpret_cast<uintptr_t> (s.out) & 15)) & 15) / 4);
   const long long peel = to_grid < n ? to_grid : n;             // frames in front of the first 16-byte boundary of out
@@ -4605,6 +4758,19 @@ limit_encode_segments_kernel (const LimitEncodeSegment *segs, int BS)
         }
     }
 }
+template<bool MIX> __global__ void __launch_bounds__ (256)
+limit_encode_segments_kernel (const LimitEncodeSegment *segs, int BS)
+{
+  const LimitEncodeSegment s = segs[blockIdx.y];
+  limit_encode_segment_body<MIX> (s, BS);
+}
+// (a limiter block per segment: RateLimitEncodeSegment, kernels.hh)
+template<bool MIX> __global__ void __launch_bounds__ (256)
+limit_encode_segments_rates_kernel (const RateLimitEncodeSegment *segs)
+{
+  const RateLimitEncodeSegment r = segs[blockIdx.y];
+  limit_encode_segment_body<MIX> (r.s, r.limiter_block);
+}
 
 hipError_t
 launch_limit_encode_segments (hipStream_t st, const LimitEncodeSegment *segs_dev, int n_segs, long long max_frames, bool mix, int limiter_block)
@@ -4618,6 +4784,20 @@ launch_limit_encode_segments (hipStream_t st, const LimitEncodeSegment *segs_dev
     hipLaunchKernelGGL (limit_encode_segments_kernel<true>, grid, dim3 (256), 0, st, segs_dev, limiter_block);
   else
     hipLaunchKernelGGL (limit_encode_segments_kernel<false>, grid, dim3 (256), 0, st, segs_dev, limiter_block);
+  return hipGetLastError();
+}
+hipError_t
+launch_limit_encode_segments_rates (hipStream_t st, const RateLimitEncodeSegment *segs_dev, int n_segs, long long max_frames, bool mix, int min_limiter_block)
+{
+  if (n_segs <= 0 || max_frames <= 0)
+    return hipSuccess;
+  if (n_segs > 65535 || min_limiter_block < 4 * ENC_RUN)
+    return hipErrorInvalidValue;                               // a run may only straddle one block boundary
+  const dim3 grid (unsigned (std::max<long long> (1, (max_frames / 4 + ENC_RUN - 1) / ENC_RUN)), unsigned (n_segs));
+  if (mix)
+    hipLaunchKernelGGL (limit_encode_segments_rates_kernel<true>, grid, dim3 (256), 0, st, segs_dev);
+  else
+    hipLaunchKernelGGL (limit_encode_segments_rates_kernel<false>, grid, dim3 (256), 0, st, segs_dev);
   return hipGetLastError();
 }
 

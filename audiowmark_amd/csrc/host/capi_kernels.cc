@@ -3586,6 +3586,587 @@ awm_add_watermark_segments_keys_rate_s16_d (awm_ctx *ctx, const uint8_t *keys, s
                            n_channels, sample_rate);
 }
 
+/* ---- segments with a SAMPLE RATE EACH: awm_add_watermark_segments_rates_d and its three twins (include/awm_hip.h).
+ * One call, one upload, one chain of launches for a queue that is not sorted by rate.  The segments at another rate go through
+ * add_segments_rate_fused's stages with the rate-dependent values -- the resamplers' tables and geometry, the limiter block -- in the
+ * descriptors (kernels.hh RateResampleSlice ...), their batches are not split by rate; the segments at 44.1 kHz go through
+ * add_segments_fused's stages as a sub-batch of the same call (no identity resampler: (1e-20f + x) - 1e-20f is not x for every float).
+ * Both kinds read the same payload tables: K16p runs once per table group, K16t once per key, whatever the rates. ---- */
+static bool rates_all_equal (size_t n, const int *sample_rates);      // (with the `get` batches, below)
+
+struct RateTables
+{
+  const ResampleTable *down = nullptr, *up = nullptr;
+  int limiter_block = 0;
+};
+
+extern "C++" {
+template<class T> static int
+add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_tables, const uint8_t key[16], const std::vector<size_t>& segs,
+                          const std::vector<size_t>& payload_of, const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames,
+                          const T *const *pcm_in_d, T *const *out_d, const size_t *n_frames, const int *rates, SegmentKeys *mk = nullptr)
+{
+  constexpr bool S16 = std::is_same<T, int16_t>::value;
+  typedef typename std::conditional<S16, awmk::LimitEncodeSegment, awmk::SegmentCopy>::type Scatter;
+  constexpr size_t PER_LAUNCH = 4096, TABLE_GROUP = 1024;  // as in add_segments_fused
+  constexpr size_t STAGE_MAX_FLOATS = size_t (1) << 28;
+  const int C = 2;
+  const size_t FRAME = Params::frame_size, n_distinct = coded.size() / (2 * n_code);
+  const int use_limiter = !params().test_no_limiter;
+  const size_t block_frames = mark_block_frame_count();
+  const size_t table_stride = awmk::payload_table_stride (block_frames);
+  hipStream_t st = ctx->stream;
+
+  FrameModTemplate *tmpl = mk ? nullptr : ctx->get_frame_mod_template (capi_key (key));      // (a key per segment: SegmentKeys' templates)
+  if (!tmpl && !mk)
+    return AWM_ERR_HIP;
+
+  // the two kinds, each in the order of the tables
+  std::vector<size_t> at_rate, at_44;
+  for (size_t i = 0; i < segs.size(); i++)
+    (rates[segs[i]] == Params::mark_sample_rate ? at_44 : at_rate).push_back (i);
+  const size_t nr = at_rate.size(), nf = at_44.size();
+  auto group_of = [&] (size_t i) { return payload_of[i] / TABLE_GROUP; };
+  size_t max_total = 0, tab_total = 0;
+
+  // at another rate: the windows and the batches as in add_segments_rate_fused; a down slice is shared by the segments of a batch that
+  // agree in input, length, offset and rate
+  struct RSeg { SegmentWindow w; const RateTables *t; size_t down, x44_off, wm44_off, wm_off, max_off, tab_off; };
+  struct RBatch { size_t i0, i1, d0, d1, x44_floats, wm44_floats, wm_floats, max_n44, max_out, max_tab, max_len; long long frames1024; int min_block; };
+  std::vector<RSeg> rgeo (nr);
+  std::vector<RBatch> rbatches;
+  std::vector<size_t> down_owner;
+  std::map<std::tuple<const T *, size_t, size_t, int>, size_t> shared;
+  for (size_t k = 0; k < nr; k++)
+    {
+      RSeg& g = rgeo[k];
+      const size_t i = at_rate[k], s = segs[i];
+      g.t = &rate_tables.at (rates[s]);
+      if (int rc = segment_window (rates[s], zero_frames[s], n_frames[s], g.w))
+        return rc;
+      const size_t n44_floats = g.w.slice_frames * FRAME * C, wm_floats = ((g.w.pre + g.w.n) * C + 3) / 4 * 4;
+      const auto id = std::make_tuple (pcm_in_d[s], n_frames[s], zero_frames[s], rates[s]);
+      bool fresh = rbatches.empty() || k - rbatches.back().i0 >= PER_LAUNCH || group_of (i) != group_of (at_rate[rbatches.back().i0]);
+      if (!fresh)
+        {
+          const RBatch& b = rbatches.back();
+          const bool have = shared.count (id) > 0;
+          fresh = b.wm44_floats + n44_floats > WS_MAX_FLOATS || b.wm_floats + wm_floats > WS_MAX_FLOATS || (!have && b.x44_floats + n44_floats > WS_MAX_FLOATS);
+        }
+      if (fresh)
+        {
+          rbatches.push_back ({ k, k, down_owner.size(), down_owner.size(), 0, 0, 0, 0, 0, 0, 0, 0, g.t->limiter_block });
+          shared.clear();
+        }
+      RBatch& b = rbatches.back();
+      auto it = shared.find (id);
+      if (it == shared.end())
+        {
+          it = shared.emplace (id, k).first;
+          g.x44_off = b.x44_floats;
+          b.x44_floats += n44_floats;
+          down_owner.push_back (k);
+          b.d1 = down_owner.size();
+        }
+      else
+        g.x44_off = rgeo[it->second].x44_off;
+      g.wm44_off = b.wm44_floats;
+      b.wm44_floats += n44_floats;
+      g.wm_off = b.wm_floats;
+      b.wm_floats += wm_floats;
+      g.max_off = max_total;
+      g.tab_off = tab_total;
+      max_total += size_t (g.w.p.n_blocks);
+      tab_total += g.w.n_tab + 1;
+      b.i1 = k + 1;
+      b.max_n44 = std::max (b.max_n44, g.w.slice_frames * FRAME);
+      b.max_out = std::max (b.max_out, g.w.pre + g.w.n);
+      b.max_tab = std::max (b.max_tab, g.w.n_tab);
+      b.max_len = std::max (b.max_len, g.w.n);
+      b.frames1024 += (long long) g.w.slice_frames;
+      b.min_block = std::min (b.min_block, g.t->limiter_block);
+    }
+  size_t x44_max = 0, wm44_max = 0, wm_max = 0;
+  long long frames_max = 0;
+  for (const RBatch& b : rbatches)
+    {
+      x44_max = std::max (x44_max, b.x44_floats);
+      wm44_max = std::max (wm44_max, b.wm44_floats);
+      wm_max = std::max (wm_max, b.wm_floats);
+      frames_max = std::max (frames_max, b.frames1024);
+    }
+  const int L_rate = frames_per_span (ctx, frames_max);
+  const size_t n_down = down_owner.size();
+
+  // at 44.1 kHz: the geometry and the batches as in add_segments_fused
+  struct FSeg { size_t r, skipped, len, first_block, n_blocks, n_tab, max_off, tab_off, stage_off; };
+  struct FBatch { size_t i0, i1, g0, g1, stage_floats, max_len, max_tab; };
+  std::vector<FSeg> fgeo (nf);
+  std::vector<FBatch> fbatches;
+  size_t stage_max = 0, n_staged = 0;
+  long long total_frames1024 = 0;
+  for (size_t k = 0; k < nf; k++)
+    {
+      const size_t i = at_44[k], zf = zero_frames[segs[i]];
+      FSeg& g = fgeo[k];
+      g.r = zf % FRAME;
+      g.skipped = zf - g.r;
+      g.len = g.r + n_frames[segs[i]];
+      g.first_block = g.skipped / LIMITER_BLOCK;
+      g.n_blocks = (g.skipped + g.len) / LIMITER_BLOCK + 2 - g.first_block;
+      g.n_tab = awmk::limiter_tab_entries ((long long) g.len, (long long) g.skipped, LIMITER_BLOCK);
+      g.max_off = max_total;
+      g.tab_off = tab_total;
+      max_total += g.n_blocks;
+      tab_total += g.n_tab + 1;
+      total_frames1024 += (long long) ((g.len + FRAME - 1) / FRAME);
+      const bool stage = g.r || S16;
+      const size_t stage_floats = stage ? (g.len * 2 + 3) / 4 * 4 : 0;
+      if (fbatches.empty() || k - fbatches.back().i0 >= PER_LAUNCH || group_of (i) != group_of (at_44[fbatches.back().i0])
+          || (fbatches.back().stage_floats && fbatches.back().stage_floats + stage_floats > STAGE_MAX_FLOATS))
+        fbatches.push_back ({ k, k, n_staged, n_staged, 0, 0, 0 });
+      FBatch& b = fbatches.back();
+      g.stage_off = b.stage_floats;
+      b.stage_floats += stage_floats;
+      b.i1 = k + 1;
+      b.max_len = std::max (b.max_len, g.len);
+      b.max_tab = std::max (b.max_tab, g.n_tab);
+      if (stage)
+        b.g1 = ++n_staged;
+      stage_max = std::max (stage_max, b.stage_floats);
+    }
+  const int L_44 = frames_per_span (ctx, total_frames1024);
+
+  // one page-locked block, one upload: the kernel arguments of every stage of both kinds and the payloads' codes
+  const size_t off_rmix = n_down * sizeof (awmk::RateResampleSlice), off_up = off_rmix + nr * sizeof (awmk::AddMixArgs),
+               off_mm = off_up + nr * sizeof (awmk::RateResampleSlice), off_rlim = off_mm + nr * sizeof (awmk::RateMixSegment),
+               off_enc = off_rlim + nr * sizeof (awmk::RateLimiterClip),
+               off_fmix = off_enc + (S16 ? nr * sizeof (awmk::RateLimitEncodeSegment) : 0), off_flim = off_fmix + nf * sizeof (awmk::AddMixArgs),
+               off_gather = off_flim + nf * sizeof (awmk::LimiterClip), off_scatter = off_gather + n_staged * sizeof (awmk::SegmentCopy),
+               off_coded = off_scatter + n_staged * sizeof (Scatter), off_keys = (off_coded + coded.size() + 15) / 16 * 16;
+  if (mk)
+    if (int rc = mk->reserve (ctx, table_stride)) return rc;
+  const size_t arg_bytes = mk ? off_keys + mk->arg_bytes() : off_coded + coded.size();
+  if (int rc = ctx->ws_add_batch.reserve (arg_bytes)) return rc;
+  if (int rc = ctx->ws_keytab.reserve (std::min (n_distinct, TABLE_GROUP) * table_stride)) return rc;
+  if (nr)
+    {
+      if (int rc = ctx->ws_rate_a.reserve (x44_max * sizeof (float))) return rc;
+      if (int rc = ctx->ws_rate_b.reserve (wm44_max * sizeof (float))) return rc;
+      if (int rc = ctx->ws_rate_c.reserve (wm_max * sizeof (float))) return rc;
+    }
+  if (use_limiter)
+    {
+      if (int rc = ctx->ws_block_max.reserve (max_total * sizeof (float))) return rc;
+      if (int rc = ctx->ws_limit_tab.reserve (tab_total * sizeof (float2))) return rc;
+    }
+  if (stage_max)
+    {
+      if (int rc = ctx->ws_seg_in.reserve (stage_max * sizeof (float))) return rc;
+      if (int rc = ctx->ws_seg_out.reserve (stage_max * sizeof (float))) return rc;
+    }
+  if (ctx->ev_add_batch)
+    AWM_HIP_CHECK (hipEventSynchronize (ctx->ev_add_batch));            // (an earlier batch's staging has been copied)
+  else
+    AWM_HIP_CHECK (hipEventCreateWithFlags (&ctx->ev_add_batch, hipEventDisableTiming));
+  if (int rc = ctx->pin_add_batch.reserve (arg_bytes)) return rc;
+  char *h = ctx->pin_add_batch.as<char>(), *d = ctx->ws_add_batch.as<char>();
+  auto *h_down = reinterpret_cast<awmk::RateResampleSlice *> (h), *h_up = reinterpret_cast<awmk::RateResampleSlice *> (h + off_up);
+  auto *h_rmix = reinterpret_cast<awmk::AddMixArgs *> (h + off_rmix);
+  auto *h_mm = reinterpret_cast<awmk::RateMixSegment *> (h + off_mm);
+  auto *h_rlim = reinterpret_cast<awmk::RateLimiterClip *> (h + off_rlim);
+  auto *h_enc = reinterpret_cast<awmk::RateLimitEncodeSegment *> (h + off_enc);             // (16-bit only)
+  auto *h_fmix = reinterpret_cast<awmk::AddMixArgs *> (h + off_fmix);
+  auto *h_flim = reinterpret_cast<awmk::LimiterClip *> (h + off_flim);
+  auto *h_gather = reinterpret_cast<awmk::SegmentCopy *> (h + off_gather);
+  auto *h_scatter = reinterpret_cast<Scatter *> (h + off_scatter);
+  const auto *d_down = reinterpret_cast<const awmk::RateResampleSlice *> (d), *d_up = reinterpret_cast<const awmk::RateResampleSlice *> (d + off_up);
+  const auto *d_rmix = reinterpret_cast<const awmk::AddMixArgs *> (d + off_rmix);
+  const auto *d_mm = reinterpret_cast<const awmk::RateMixSegment *> (d + off_mm);
+  const auto *d_rlim = reinterpret_cast<const awmk::RateLimiterClip *> (d + off_rlim);
+  const auto *d_enc = reinterpret_cast<const awmk::RateLimitEncodeSegment *> (d + off_enc);
+  const auto *d_fmix = reinterpret_cast<const awmk::AddMixArgs *> (d + off_fmix);
+  const auto *d_flim = reinterpret_cast<const awmk::LimiterClip *> (d + off_flim);
+  const auto *d_gather = reinterpret_cast<const awmk::SegmentCopy *> (d + off_gather);
+  const auto *d_scatter = reinterpret_cast<const Scatter *> (d + off_scatter);
+  const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
+  std::memcpy (h + off_coded, coded.data(), coded.size());
+  if (mk)
+    mk->fill (h + off_keys, d + off_keys);
+  float *x44 = ctx->ws_rate_a.as<float>(), *wm44 = ctx->ws_rate_b.as<float>(), *wm = ctx->ws_rate_c.as<float>();
+  float *block_max = ctx->ws_block_max.as<float>();
+  float2 *tabs = ctx->ws_limit_tab.as<float2>();
+  auto table_of = [&] (size_t i) { return ctx->ws_keytab.as<int8_t>() + (payload_of[i] % TABLE_GROUP) * table_stride; };
+  auto rate_slice = [&] (const awmk::ResampleSlice& s, const ResampleTable& t) {
+    awmk::RateResampleSlice r { s, t.ctab.as<float>(), t.hl, t.np, t.step, 0, 0 };
+    awmk::resample_slice_geometry (r, C, true);
+    return r;
+  };
+  for (size_t q = 0; q < n_down; q++)
+    {
+      const RSeg& g = rgeo[down_owner[q]];
+      h_down[q] = rate_slice (window_down_slice (g.w, pcm_in_d[segs[at_rate[down_owner[q]]]], C, x44 + g.x44_off), *g.t->down);
+    }
+  for (size_t k = 0; k < nr; k++)
+    {
+      const RSeg& g = rgeo[k];
+      const size_t i = at_rate[k], s = segs[i];
+      const int lim_block = g.t->limiter_block;
+      h_rmix[k] = window_mix_args (g.w, x44 + g.x44_off, wm44 + g.wm44_off, C, table_of (i), params().water_delta, L_rate);
+      h_up[k] = rate_slice (window_up_slice (g.w, wm44 + g.wm44_off, C, wm + g.wm_off), *g.t->up);
+      float *mix_out = nullptr;                                   // (16-bit: no mix is stored; `orig` holds the address of the int16 values)
+      if constexpr (!S16)
+        mix_out = out_d[s];
+      h_mm[k] = { { reinterpret_cast<const float *> (pcm_in_d[s]), wm + g.wm_off, mix_out, (long long) g.w.n, (long long) g.w.pre, (long long) g.w.Z,
+                    use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr, (long long) g.w.p.first_block,
+                    (long long) g.w.p.n_blocks }, lim_block };
+      h_rlim[k] = { { mix_out, (long long) g.w.n, use_limiter ? block_max + g.max_off : nullptr, (long long) g.w.p.n_blocks,
+                      use_limiter ? tabs + g.tab_off : nullptr, (long long) g.w.n_tab, (long long) g.w.Z, (long long) g.w.p.first_block }, lim_block };
+      if constexpr (S16)
+        h_enc[k] = { { pcm_in_d[s], wm + g.wm_off + g.w.pre * C, out_d[s], (long long) g.w.n, (long long) g.w.Z,
+                       use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.w.Z / size_t (lim_block)) }, lim_block };
+    }
+  std::vector<long long> spans (nf);
+  size_t staged = 0;
+  for (size_t k = 0; k < nf; k++)
+    {
+      const FSeg& g = fgeo[k];
+      const size_t i = at_44[k], s = segs[i];
+      const float *in = ctx->ws_seg_in.as<float>() + g.stage_off;
+      float *out = ctx->ws_seg_out.as<float>() + g.stage_off;
+      if constexpr (!S16)
+        if (!g.r)
+          {
+            in = pcm_in_d[s];
+            out = out_d[s];
+          }
+      awmk::AddMixArgs a {};
+      a.pcm_in = in;
+      a.out = out;
+      a.n_frames = (long long) g.len;
+      a.n_channels = 2;
+      a.frame_mod = table_of (i);
+      fill_add_mix_common (a, params().water_delta);
+      a.first_frame = (long long) (g.skipped / FRAME);
+      a.block_max = use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr;
+      a.first_block = (long long) g.first_block;
+      a.n_blocks = (long long) g.n_blocks;
+      a.frames_per_span = L_44;
+      h_fmix[k] = a;
+      h_flim[k] = { out, (long long) g.len, block_max + g.max_off, (long long) g.n_blocks, tabs + g.tab_off, (long long) g.n_tab,
+                    (long long) g.skipped, (long long) g.first_block };
+      spans[k] = ((long long) ((g.len + FRAME - 1) / FRAME) + L_44 - 1) / L_44;
+      if (g.r || S16)
+        {
+          h_gather[staged] = { reinterpret_cast<const float *> (pcm_in_d[s]), ctx->ws_seg_in.as<float>() + g.stage_off, (long long) (n_frames[s] * 2),
+                               (long long) (g.r * 2) };
+          if constexpr (S16)
+            h_scatter[staged] = { nullptr, out + g.r * 2, out_d[s], (long long) n_frames[s], (long long) zero_frames[s],
+                                  use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.skipped / LIMITER_BLOCK) };
+          else
+            h_scatter[staged] = { out + g.r * 2, out_d[s], (long long) (n_frames[s] * 2), 0 };
+          staged++;
+        }
+    }
+  AWM_HIP_CHECK (hipMemcpyAsync (d, h, arg_bytes, hipMemcpyHostToDevice, st));
+  AWM_HIP_CHECK (hipEventRecord (ctx->ev_add_batch, st));
+
+  unsigned int ceiling_bits;
+  std::memcpy (&ceiling_bits, &LIMITER_CEILING, sizeof (ceiling_bits));
+  auto run_rate_batch = [&] (const RBatch& b) -> int {
+    const size_t nb = b.i1 - b.i0;
+    double down_values = 0, up_values = 0, n44_values = 0, out_values = 0;
+    long long max_spans = 0;
+    size_t lds_down = 0, lds_up = 0;
+    for (size_t q = b.d0; q < b.d1; q++)
+      {
+        down_values += double (h_down[q].s.n_in + h_down[q].s.n_out) * C;
+        lds_down = std::max (lds_down, awmk::resample_slice_lds_bytes (h_down[q]));
+      }
+    for (size_t k = b.i0; k < b.i1; k++)
+      {
+        up_values += double (h_up[k].s.n_in + h_up[k].s.n_out) * C;
+        lds_up = std::max (lds_up, awmk::resample_slice_lds_bytes (h_up[k]));
+        n44_values += double (rgeo[k].w.slice_frames * FRAME) * C;
+        out_values += double (rgeo[k].w.n) * C;
+        max_spans = std::max (max_spans, ((long long) rgeo[k].w.slice_frames + L_rate - 1) / L_rate);
+      }
+    {
+      ProfScope ps (ctx, PROF_RESAMPLE, down_values * 4.0, st);                     // every input and output sample once
+      if constexpr (S16)
+        AWM_HIP_CHECK (awmk::launch_resample_slices_rates_s16 (st, d_down + b.d0, int (b.d1 - b.d0), C, (long long) b.max_n44, true, lds_down));
+      else
+        AWM_HIP_CHECK (awmk::launch_resample_slices_rates (st, d_down + b.d0, int (b.d1 - b.d0), C, (long long) b.max_n44, true, lds_down));
+    }
+    if (use_limiter)
+      {
+        const size_t m0 = rgeo[b.i0].max_off, m1 = rgeo[b.i1 - 1].max_off + size_t (rgeo[b.i1 - 1].w.p.n_blocks);
+        AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (block_max + m0), ceiling_bits, m1 - m0));
+      }
+    {
+      ProfScope ps (ctx, PROF_ADD_MIX, n44_values * 8.0, st);
+      AWM_HIP_CHECK (awmk::launch_add_mix_batch (st, ctx->tabs, d_rmix + b.i0, int (nb), max_spans, int (block_frames), int (Params::frames_pad_start)));
+    }
+    {
+      ProfScope ps (ctx, PROF_RESAMPLE, up_values * 4.0, st);
+      AWM_HIP_CHECK (awmk::launch_resample_slices_rates (st, d_up + b.i0, int (nb), C, (long long) b.max_out, true, lds_up));
+    }
+    if constexpr (S16)
+      {
+        // the block maxima from the mix, the ramp tables, then the mix again: limited, encoded and stored as int16
+        if (use_limiter)
+          {
+            AWM_HIP_CHECK (awmk::launch_max_segments_rates_s16 (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, b.min_block));
+            AWM_HIP_CHECK (awmk::launch_limiter_table_batch_rates (st, d_rlim + b.i0, int (nb), LIMITER_CEILING, (long long) b.max_tab));
+          }
+        ProfScope ps (ctx, PROF_LIMIT_ENCODE_S16, out_values * 8.0, st);            // int16 and float in, int16 out
+        AWM_HIP_CHECK (awmk::launch_limit_encode_segments_rates (st, d_enc + b.i0, int (nb), (long long) b.max_len, true, b.min_block));
+      }
+    else
+      {
+        AWM_HIP_CHECK (awmk::launch_mix_max_segments_rates (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, b.min_block));
+        if (use_limiter)
+          {
+            ProfScope ps (ctx, PROF_LIMITER, out_values * 8.0, st);
+            AWM_HIP_CHECK (awmk::launch_limiter_batch_rates (st, d_rlim + b.i0, int (nb), (long long) b.max_len, C, b.min_block, LIMITER_CEILING,
+                                                             (long long) b.max_tab));
+          }
+      }
+    return 0;
+  };
+  auto run_44_batch = [&] (const FBatch& b) -> int {
+    const size_t nb = b.i1 - b.i0;
+    long long max_spans = 0;
+    double values = 0;
+    for (size_t k = b.i0; k < b.i1; k++)
+      {
+        max_spans = std::max (max_spans, spans[k]);
+        values += double (fgeo[k].len) * 2;
+      }
+    if constexpr (S16)
+      {
+        ProfScope ps (ctx, PROF_SEGMENT_GATHER_S16, values * 6.0, st);            // int16 in, float out
+        AWM_HIP_CHECK (awmk::launch_segment_gather_s16 (st, d_gather + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
+      }
+    else if (b.g1 > b.g0)
+      AWM_HIP_CHECK (awmk::launch_segment_copy (st, d_gather + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
+    if (use_limiter)
+      {
+        const size_t m0 = fgeo[b.i0].max_off, m1 = fgeo[b.i1 - 1].max_off + fgeo[b.i1 - 1].n_blocks;
+        AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (block_max + m0), ceiling_bits, m1 - m0));
+      }
+    {
+      ProfScope ps (ctx, PROF_ADD_MIX, values * 8.0, st);                          // read + write every sample once
+      AWM_HIP_CHECK (awmk::launch_add_mix_batch (st, ctx->tabs, d_fmix + b.i0, int (nb), max_spans, int (block_frames), int (Params::frames_pad_start)));
+    }
+    if constexpr (S16)
+      {
+        if (use_limiter)
+          AWM_HIP_CHECK (awmk::launch_limiter_table_batch (st, d_flim + b.i0, int (nb), (long long) b.max_len, LIMITER_BLOCK, LIMITER_CEILING, (long long) b.max_tab));
+        ProfScope ps (ctx, PROF_LIMIT_ENCODE_S16, values * 6.0, st);               // float in, int16 out
+        AWM_HIP_CHECK (awmk::launch_limit_encode_segments (st, d_scatter + b.g0, int (b.g1 - b.g0), (long long) b.max_len, false, LIMITER_BLOCK));
+      }
+    else
+      {
+        if (use_limiter)
+          {
+            ProfScope ps (ctx, PROF_LIMITER, values * 8.0, st);
+            AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_flim + b.i0, int (nb), (long long) b.max_len, 2, LIMITER_BLOCK, LIMITER_CEILING, (long long) b.max_tab));
+          }
+        if (b.g1 > b.g0)
+          AWM_HIP_CHECK (awmk::launch_segment_copy (st, d_scatter + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
+      }
+    return 0;
+  };
+
+  // table group by table group: its tables once, then its batches at another rate, then its batches at 44.1 kHz
+  size_t rb = 0, fb = 0, group_built = size_t (-1);
+  while (rb < rbatches.size() || fb < fbatches.size())
+    {
+      const size_t gr = rb < rbatches.size() ? group_of (at_rate[rbatches[rb].i0]) : size_t (-1);
+      const size_t gf = fb < fbatches.size() ? group_of (at_44[fbatches[fb].i0]) : size_t (-1);
+      const size_t group = std::min (gr, gf);
+      if (group != group_built)
+        {
+          awmk::PayloadTableArgs pa {};
+          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
+          pa.tmpl = mk ? ctx->ws_key_tmpl.as<short>() : tmpl->dev.as<short>();
+          if (mk)
+            {
+              if (int rc = mk->build (ctx, st, group * TABLE_GROUP + size_t (pa.n_payloads))) return rc;
+              pa.tmpl_of = mk->d_tmpl_of + group * TABLE_GROUP;
+              pa.tmpl_stride = (long long) table_stride;
+            }
+          pa.coded = d_coded + group * TABLE_GROUP * 2 * n_code;
+          pa.tables = ctx->ws_keytab.as<signed char>();
+          pa.table_stride = (long long) table_stride;
+          pa.half_entries = int (block_frames * Params::n_bands);
+          pa.n_code = int (n_code);
+          ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (pa.n_payloads) * table_stride, st);          // the tables out, once
+          AWM_HIP_CHECK (awmk::launch_payload_tables (st, pa));
+          group_built = group;
+        }
+      if (int rc = gr == group ? run_rate_batch (rbatches[rb++]) : run_44_batch (fbatches[fb++]))
+        return rc;
+    }
+  return 0;
+}
+
+/* the four entry points' body: T = float or int16_t, per_key: keys + 16 i is the key of segment i */
+template<class T> static int
+add_segments_rates (awm_ctx *ctx, const char *fn, const uint8_t *keys, bool per_key, size_t n_segments, const char *const *payload_hex,
+                    const size_t *zero_frames, const T *const *pcm_in_d, T *const *out_d, const size_t *n_frames, int n_channels, const int *sample_rates)
+{
+  constexpr bool S16 = std::is_same<T, int16_t>::value;
+  AWM_ENTER (ctx);
+  g_add_segments_fused_in_use = 0;
+  if (!n_segments)
+    return 0;
+  if (!sample_rates)
+    {
+      set_error (string_printf ("%s: sample_rates is null", fn));
+      return AWM_ERR_ARG;
+    }
+  std::map<int, RateTables> rate_tables;                     // the rates other than 44.1 kHz
+  for (size_t i = 0; i < n_segments; i++)
+    {
+      const int rate = sample_rates[i];
+      awm_segment_plan probe;
+      if (rate == Params::mark_sample_rate || rate_tables.count (rate))
+        continue;
+      if (awm_add_segment_plan (rate, 0, 0, &probe))
+        {
+          set_error (rate <= 0 ? string_printf ("%s: bad sample rate %d at index %zu", fn, rate, i)
+                               : string_printf ("%s: no fixed-ratio resampler between %d Hz and %d Hz at index %zu (zita's VResampler is not offered here)",
+                                                fn, rate, Params::mark_sample_rate, i));
+          return AWM_ERR_ARG;
+        }
+      rate_tables[rate].limiter_block = int (probe.limiter_block);
+    }
+  std::vector<size_t> payload_index;
+  std::vector<unsigned char> coded;
+  size_t n_code = 0;
+  if (int rc = segments_check (ctx, fn, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, payload_index, coded, n_code))
+    return rc;
+  for (size_t i = 0; i < n_segments; i++)
+    {
+      awm_segment_plan probe;
+      if (sample_rates[i] != Params::mark_sample_rate && awm_add_segment_plan (sample_rates[i], zero_frames[i], n_frames[i], &probe))
+        {
+          set_error (string_printf ("%s: zero_frames + n_frames of segment %zu is not below 2^40", fn, i));
+          return AWM_ERR_ARG;
+        }
+    }
+  for (auto& rt : rate_tables)
+    {
+      rt.second.down = ctx->get_resample_table (rt.first, Params::mark_sample_rate);
+      rt.second.up = ctx->get_resample_table (Params::mark_sample_rate, rt.first);
+      if (!rt.second.down || !rt.second.up)
+        return AWM_ERR_HIP;
+    }
+  if (per_key && segments_share_one_key (keys, n_segments))      // one key for all segments IS the one-key call
+    per_key = false;
+  // the fused path: stereo, the pointers aligned as the one-rate fused paths need them, at every other rate the floor of the batched
+  // limiter and windows that fit the workspaces
+  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2;
+  for (const auto& rt : rate_tables)
+    fused = fused && rt.second.limiter_block >= 8192;
+  for (size_t i = 0; i < n_segments && fused; i++)
+    if (n_frames[i])
+      {
+        if ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) | reinterpret_cast<uintptr_t> (out_d[i])) & (S16 ? 3 : 15))
+          fused = false;
+        else if (sample_rates[i] != Params::mark_sample_rate)
+          fused = segments_rate_fit_the_workspaces (1, zero_frames + i, n_frames + i, n_channels, sample_rates[i]);
+      }
+  if (!fused)
+    {
+      // segment by segment through the one-rate paths of one segment, each at its rate
+      for (size_t i = 0; i < n_segments; i++)
+        if (n_frames[i])
+          {
+            const uint8_t *key = per_key ? keys + 16 * i : keys;
+            const int rate = sample_rates[i];
+            const RateTables *rt = rate == Params::mark_sample_rate ? nullptr : &rate_tables.at (rate);
+            auto one = [&] (const float *in, float *out) {
+              return rt ? add_segment_rate (ctx, *rt->down, *rt->up, key, payload_hex[i], zero_frames[i], in, out, n_frames[i], n_channels, rate)
+                        : add_segment_stream (ctx, key, payload_hex[i], zero_frames[i], in, out, n_frames[i], n_channels);
+            };
+            if constexpr (S16)
+              {
+                // (the definition itself, as in add_segments_s16: decode, the float path of one segment, encode direct16)
+                const size_t n_values = n_frames[i] * size_t (n_channels);
+                if (int rc = ctx->ws_seg_in.reserve (n_values * sizeof (float))) return rc;
+                if (int rc = ctx->ws_seg_out.reserve (n_values * sizeof (float))) return rc;
+                float *f = ctx->ws_seg_in.as<float>(), *g = ctx->ws_seg_out.as<float>();
+                if (int rc = awm_pcm_decode_d (ctx, pcm_in_d[i], n_values, 16, 0, 0, f)) return rc;
+                if (int rc = one (f, g)) return rc;
+                if (int rc = awm_pcm_encode_d (ctx, g, n_values, 16, 0, 0, 1, out_d[i])) return rc;
+              }
+            else if (int rc = one (pcm_in_d[i], out_d[i]))
+              return rc;
+          }
+      return 0;
+    }
+  SegmentKeys mk;
+  std::vector<size_t> segs, table_of;
+  std::vector<unsigned char> coded_tables;
+  if (per_key)
+    segments_by_key_and_payload (n_segments, keys, n_frames, payload_index, coded, n_code, mk, segs, table_of, coded_tables);
+  else
+    segments_by_payload (n_segments, n_frames, payload_index, segs, table_of);
+  g_add_segments_fused_in_use = 1;
+  if (segs.empty())
+    return 0;
+  return add_segments_rates_fused (ctx, rate_tables, per_key ? nullptr : keys, segs, table_of, per_key ? coded_tables : coded, n_code, zero_frames,
+                                   pcm_in_d, out_d, n_frames, sample_rates, per_key ? &mk : nullptr);
+}
+} // extern "C++"
+
+int
+awm_add_watermark_segments_rates_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                    const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, const int *sample_rates)
+{
+  if (rates_all_equal (n_segments, sample_rates))          // IS the one-rate function (which hands 44.1 kHz on), before anything else happens
+    return awm_add_watermark_segments_rate_d (ctx, key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, sample_rates[0]);
+  return add_segments_rates (ctx, "awm_add_watermark_segments_rates_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                             n_channels, sample_rates);
+}
+
+int
+awm_add_watermark_segments_keys_rates_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                         const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, const int *sample_rates)
+{
+  if (rates_all_equal (n_segments, sample_rates))
+    return awm_add_watermark_segments_keys_rate_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, sample_rates[0]);
+  return add_segments_rates (ctx, "awm_add_watermark_segments_keys_rates_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                             n_channels, sample_rates);
+}
+
+// (16-bit: sample_rates may be null -- every segment at 44.1 kHz, like awm_get_watermark_batch_rates_s16_d)
+int
+awm_add_watermark_segments_rates_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                        const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames, int n_channels, const int *sample_rates)
+{
+  if (!sample_rates || rates_all_equal (n_segments, sample_rates))
+    return awm_add_watermark_segments_rate_s16_d (ctx, key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels,
+                                                  sample_rates ? sample_rates[0] : int (Params::mark_sample_rate));
+  return add_segments_rates (ctx, "awm_add_watermark_segments_rates_s16_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                             n_channels, sample_rates);
+}
+
+int
+awm_add_watermark_segments_keys_rates_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex,
+                                             const size_t *zero_frames, const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames,
+                                             int n_channels, const int *sample_rates)
+{
+  if (!sample_rates || rates_all_equal (n_segments, sample_rates))
+    return awm_add_watermark_segments_keys_rate_s16_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels,
+                                                       sample_rates ? sample_rates[0] : int (Params::mark_sample_rate));
+  return add_segments_rates (ctx, "awm_add_watermark_segments_keys_rates_s16_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d,
+                             n_frames, n_channels, sample_rates);
+}
+
 /* K16t alone (measurements, tests): the templates of n_keys keys built on the device, KEY_TMPL_LAUNCH per launch, and copied to the host,
  * n_keys x awmk::payload_table_stride (2226) entries -- they must equal awm_tab_frame_mod_template key by key, zeros behind.  out may be
  * NULL: the launches alone, on the context's stream (for timing) */

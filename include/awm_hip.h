@@ -391,6 +391,39 @@ int awm_add_watermark_segments_rate_s16_d (awm_ctx *ctx, const uint8_t key[16], 
 int awm_add_watermark_segments_keys_rate_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex,
                                                 const size_t *zero_frames, const int16_t *const *pcm_in_d, int16_t *const *out_d,
                                                 const size_t *n_frames, int n_channels, int sample_rate);
+/* The segment batches WITH A SAMPLE RATE PER SEGMENT: a request queue that is not sorted by rate in one call.  Each
+ * function is its _rate counterpart above with sample_rates (host, one rate per segment) in place of sample_rate.
+ * Definition: out_d[i] is bit for bit (16-bit: value for value) what the one-rate function of the same family writes for segment i alone
+ * at sample_rates[i]; the keys forms use keys + 16 i there.
+ * A call whose rates are all equal IS the one-rate function and forwards before anything else (all 44100: the 44.1 kHz function); one key
+ * for all segments of a keys form IS the one-key form.  sample_rates == NULL: the float forms refuse it when n_segments > 0 (AWM_ERR_ARG,
+ * like awm_get_watermark_batch_rates_d), the 16-bit forms take every segment at 44100 (like awm_get_watermark_batch_rates_s16_d).
+ * Rules: those of the one-rate functions -- AWM_ERR_ARG with nothing enqueued and nothing written, the index of the first offending segment
+ * in awm_last_error, for a sample_rates[i] <= 0, a rate without a fixed-ratio table in both directions, zero_frames[i] + n_frames[i] >= 2^40
+ * at that segment's rate, NULL pointers, the overlap sweep (16-bit: n C 2 bytes, odd addresses), a payload that does not parse, an armed SNR
+ * meter, keys == NULL.  n_segments == 0 returns 0, empty segments write nothing, the rate of an empty segment is still checked.
+ * The fused path takes stereo, n_segments >= 2, every pointer aligned as the one-rate fused paths need it (float 16-byte, 16-bit 4-byte),
+ * every rate other than 44100 at least 8192 Hz and with windows that fit a workspace, awm_debug_set_add_batched on.  It is one upload and one
+ * chain of launches: the batches are not split by rate -- K10w, the mix / maxima kernels, the batched limiter and the 16-bit encode pass
+ * read the resampler's geometry and the limiter block from each segment's descriptor --, segments share a down-resampled slice only if they
+ * agree in input, length, offset and rate, the segments at 44100 run the stages of the 44.1 kHz fused path as a sub-batch of the same call,
+ * and all of them read the same tables: K16p runs once per table group, K16t once per key, however many rates the call holds.  No workspace
+ * beyond those of the one-rate paths; awm_ctx_trim gives everything back.
+ * Everything else goes segment by segment through the one-rate path of one segment at that segment's rate;
+ * awm_debug_add_segments_fused_in_use () tells which path ran.
+ * Not offered: the command line, the file level, the tile stream, the awm_multi_* / sharded forms. */
+int awm_add_watermark_segments_rates_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
+                                        const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames,
+                                        int n_channels, const int *sample_rates);
+int awm_add_watermark_segments_keys_rates_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex,
+                                             const size_t *zero_frames, const float *const *pcm_in_d, float *const *out_d,
+                                             const size_t *n_frames, int n_channels, const int *sample_rates);
+int awm_add_watermark_segments_rates_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex,
+                                            const size_t *zero_frames, const int16_t *const *pcm_in_d, int16_t *const *out_d,
+                                            const size_t *n_frames, int n_channels, const int *sample_rates);
+int awm_add_watermark_segments_keys_rates_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex,
+                                                 const size_t *zero_frames, const int16_t *const *pcm_in_d, int16_t *const *out_d,
+                                                 const size_t *n_frames, int n_channels, const int *sample_rates);
 /* The window of one such segment (pure host arithmetic, no context, no device; the device path calls it per segment).  Frames and samples
  * are indices into the segment's stream: at 44.1 kHz for the frames (of 1024 samples) and the down_* samples, at sample_rate otherwise. */
 typedef struct
