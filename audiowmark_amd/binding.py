@@ -219,6 +219,10 @@ lib.awm_add_stream_create_at.argtypes = [_vp, _vp, C.c_char_p, C.c_int, C.c_size
 lib.awm_debug_sync_db_sliding_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, _vp]
 lib.awm_debug_sync_db_sliding_rows_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, C.c_longlong, C.c_longlong,
                                                  _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_longlong, _vp, C.c_longlong]
+lib.awm_debug_block_plane_ld.argtypes = [_vp]
+lib.awm_debug_block_db_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.c_uint32, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t,
+                                     _vp, _vp]
+lib.awm_debug_soft_bits_planes_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]
 lib.awm_get_watermark_file.argtypes = [_vp, _vp, C.c_char_p, C.POINTER(RawFormat), C.c_size_t, _vp]
 lib.awm_add_get_watermark_file.argtypes = [_vp, _vp, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(RawFormat), C.POINTER(RawFormat), C.c_size_t, _vp]
 lib.awm_add_stream_create.argtypes = [_vp, _vp, C.c_char_p, C.c_int, C.c_size_t, C.POINTER(_vp)]
@@ -1303,6 +1307,47 @@ class Context:
         _check(lib.awm_block_soft_bits_d(self._h, key_bytes(key), _dev_ptr(pcm), n, ch, _np(idx), len(idx), _np(out), _np(ok)),
                "awm_block_soft_bits_d")
         return out, ok
+
+    def block_plane_ld(self):
+        """row length of the block decoder's dB planes under the parameters in force"""
+        return _check(lib.awm_debug_block_plane_ld(self._h), "awm_debug_block_plane_ld")
+
+    def debug_block_db(self, key, pcm, indices, fill=0x7FC00000, slice_range=None, slice_frames=0, planes=None):
+        """awm_debug_block_db_d: K4b and K7 as block_soft_bits launches them -> (planes [blocks][channels][81][ld] float32 on the device
+        with the cells K4b left alone holding the bit pattern `fill`, soft [blocks][858], slot [blocks]: the row of planes / soft
+        of block i, -1 if it runs past the samples).  slice_range: int64 [n_slices][2] on the device, with slice_frames the padded-clip
+        mode.  planes: the caller's buffer instead of a fresh one."""
+        import torch
+        n, ch = _pcm_shape(pcm)
+        idx = np.ascontiguousarray(indices, np.uint64)
+        if planes is None:
+            planes = torch.empty((len(idx), ch, N_BANDS, self.block_plane_ld()), dtype=torch.float32, device=pcm.device)
+        assert planes.dtype == torch.float32 and planes.is_cuda and planes.is_contiguous()
+        assert slice_range is None or (slice_range.dtype == torch.int64 and slice_range.is_cuda and slice_range.is_contiguous() and slice_range.dim() == 2
+                                       and slice_range.shape[1] == 2)
+        soft = np.zeros((len(idx), SOFT_BITS), np.float32)
+        slot = np.zeros(len(idx), np.int32)
+        _check(lib.awm_debug_block_db_d(self._h, key_bytes(key), _dev_ptr(pcm), n, ch, _np(idx), len(idx), fill,
+                                        _dev_ptr(slice_range) if slice_range is not None else None,
+                                        slice_range.shape[0] if slice_range is not None else 0, slice_frames, _dev_ptr(planes), planes.numel(),
+                                        _np(soft), _np(slot)), "awm_debug_block_db_d")
+        return planes, soft, slot
+
+    def debug_soft_bits_planes(self, key, planes, n_blocks=None, channels=None, block_base=None, slice_range=None, range_index=None):
+        """awm_debug_soft_bits_planes_d: K7 alone on planes [blocks][channels][81][ld] float32 of the caller (device) -> soft [blocks][858];
+        block_base int64 [blocks], slice_range int64 [n_slices][2], range_index int32 [blocks] (device, all or none): the padded-clip mode"""
+        import torch
+        assert planes.dtype == torch.float32 and planes.is_cuda and planes.is_contiguous()
+        n_blocks = planes.shape[0] if n_blocks is None else n_blocks
+        channels = planes.shape[1] if channels is None else channels
+        for t, dtype in ((block_base, torch.int64), (slice_range, torch.int64), (range_index, torch.int32)):
+            assert t is None or (t.dtype == dtype and t.is_cuda and t.is_contiguous())
+        opt = lambda t: _dev_ptr(t) if t is not None else None
+        soft = np.zeros((max(n_blocks, 1), SOFT_BITS), np.float32)
+        _check(lib.awm_debug_soft_bits_planes_d(self._h, key_bytes(key), _dev_ptr(planes), planes.numel(), n_blocks, channels, opt(block_base),
+                                                opt(slice_range), opt(range_index), slice_range.shape[0] if slice_range is not None else 0,
+                                                _np(soft)), "awm_debug_soft_bits_planes_d")
+        return soft[:n_blocks]
 
     # conv_decode_soft
     def viterbi_decode(self, block_type, soft):

@@ -457,6 +457,9 @@ struct SoftBitsArgs
   const int       *range_index = nullptr;
 };
 hipError_t launch_soft_bits (hipStream_t st, const SoftBitsArgs& a);
+/* true if launch_soft_bits runs the kernel that takes the items in the padding's silence without a load (3+ channels at --frames-per-bit 3
+ * and awm_debug_set_soft_bits_generic take the one that loads every cell: K4b must not leave any unwritten then) */
+bool soft_bits_skips_silent_items (int n_channels, int frames_per_bit);
 
 /* K7b: everything between mix_decode and the Viterbi decoder, per decode job (reference wmget.cc:40-65 normalize_soft_bits,
  * wmcommon.cc:165-185 randomize_bit_order, wmget.cc:554-701 AB interleave / "all" average): the raw soft bits of the

@@ -4109,13 +4109,21 @@ soft_bits_wave_kernel (SoftBitsArgs a, int groups_per_block)
 int g_soft_bits_generic = 0;     // (debug toggle: the one-thread-per-bit kernel for every shape)
 extern "C" void awm_debug_set_soft_bits_generic (int on) { g_soft_bits_generic = on; }
 
+/* does launch_soft_bits take soft_bits_wave_kernel for this shape?  Only that kernel knows SoftBitsArgs::stream_range; soft_bits_kernel
+ * loads every cell of every item, so K4b has to write them all for it (SyncDbArgs::skip_unread_silent_tiles = 0) */
+bool
+soft_bits_skips_silent_items (int n_channels, int frames_per_bit)
+{
+  return !g_soft_bits_generic && frames_per_bit * n_channels * 30 <= SB_MAX_ITEMS;
+}
+
 hipError_t
 launch_soft_bits (hipStream_t st, const SoftBitsArgs& a)
 {
   if (a.n_blocks <= 0)
     return hipSuccess;
   const int n_bits = a.n_data_frames / a.frames_per_bit;
-  if (!g_soft_bits_generic && a.frames_per_bit * a.n_channels * 30 <= SB_MAX_ITEMS)
+  if (soft_bits_skips_silent_items (a.n_channels, a.frames_per_bit))
     {
       const int groups = (n_bits + SB_WAVES * SB_BPW - 1) / (SB_WAVES * SB_BPW);
       const long long rounds = (a.n_blocks + 7) / 8;                   // 8 blocks (one per XCD) at a time

@@ -2,6 +2,7 @@
 #include "context.hh"
 #include "syncfinder.hh"
 #include "wmget.hh"
+#include "wmdecode.hh"
 #include "wmspeed.hh"
 #include "utils.hh"
 #include "wmfile.hh"
@@ -1721,6 +1722,141 @@ awm_block_soft_bits_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, 
       else
         std::fill (out + i * n_bits, out + (i + 1) * n_bits, 0.f);
     }
+  return 0;
+}
+
+/* ---- debug views of the block decoder's dB pass and soft bits (K4b, K7): tests only ---- */
+namespace {
+
+constexpr size_t DEBUG_BLOCKS_MAX = 64;
+constexpr long long DEBUG_RANGE_MAX = 1LL << 40;
+
+/* the ranges of padded slices as the kernels may be given them: [n_slices][2] on the device, first < 0 (nothing but silence) or
+ * 0 <= first <= last <= max_value; one synchronisation */
+int
+debug_check_ranges (awm_ctx *ctx, const long long *slice_range_d, size_t n_slices, long long max_value, const char *&bad)
+{
+  std::vector<long long> r (2 * n_slices);
+  AWM_HIP_CHECK (hipMemcpyAsync (r.data(), slice_range_d, r.size() * sizeof (long long), hipMemcpyDeviceToHost, ctx->stream));
+  AWM_HIP_CHECK (hipStreamSynchronize (ctx->stream));
+  for (size_t s = 0; s < n_slices && !bad; s++)
+    if (r[2 * s] >= 0 && (r[2 * s] > r[2 * s + 1] || r[2 * s + 1] > max_value))
+      bad = "a slice's range is not first < 0 or 0 <= first <= last <= the values there are";
+  return 0;
+}
+
+}
+
+int
+awm_debug_block_plane_ld (awm_ctx *ctx)
+{
+  AWM_ENTER (ctx);
+  return int (block_plane_ld());
+}
+
+int
+awm_debug_block_db_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels, const uint64_t *index,
+                      size_t n_blocks, uint32_t fill, const long long *slice_range_d, size_t n_slices, size_t slice_frames,
+                      float *planes_out_d, size_t planes_values, float *soft_out, int *slot_out)
+{
+  AWM_ENTER (ctx);
+  const size_t block_values = size_t (std::max (n_channels, 0)) * Params::n_bands * size_t (block_plane_ld());
+  const size_t block_len = mark_block_frame_count() * Params::frame_size;
+  const char *bad = nullptr;
+  if (!pcm_d || !index || !planes_out_d || !soft_out || !slot_out)
+    bad = "null pointer";
+  else if (n_channels < 1 || n_channels > 3)
+    bad = "1, 2 or 3 channels";
+  else if (n_blocks < 1 || n_blocks > DEBUG_BLOCKS_MAX)
+    bad = "1 .. 64 blocks";
+  else if (n_frames > size_t (DEBUG_RANGE_MAX))
+    bad = "too many frames";
+  else if (planes_values / block_values < n_blocks)
+    bad = "planes_out_d holds fewer than n_blocks blocks";
+  else if ((slice_range_d != nullptr) != (slice_frames != 0) || (slice_range_d != nullptr) != (n_slices != 0))
+    bad = "slice_range_d, n_slices and slice_frames go together";
+  else if (slice_range_d && (slice_frames > n_frames || n_slices > n_frames / slice_frames))
+    bad = "the slices do not fit into the samples";
+  if (!bad && slice_range_d)
+    for (size_t i = 0; i < n_blocks && !bad; i++)
+      if (index[i] <= n_frames && n_frames - index[i] >= block_len && index[i] / slice_frames >= n_slices)      // (an accepted block)
+        bad = "a block starts behind the last slice";
+  if (!bad && slice_range_d)
+    if (int rc = debug_check_ranges (ctx, slice_range_d, n_slices, (long long) (n_frames * n_channels), bad))
+      return rc;
+  if (bad)
+    {
+      set_error (std::string ("awm_debug_block_db_d: ") + bad);
+      return AWM_ERR_ARG;
+    }
+  KeyTables *kt = ctx->get_key_tables (capi_key (key));
+  if (!kt)
+    return AWM_ERR_HIP;
+  const size_t n_bits = mark_data_frame_count() / params().frames_per_bit;
+  const std::vector<size_t> idx (index, index + n_blocks);
+  std::vector<int> slot_of;
+  std::vector<char> ok;
+  const BlockDbView view { fill, planes_out_d };
+  if (int rc = block_soft_bits_dev (ctx, ctx, kt, make_wav (pcm_d, n_frames, n_channels), idx, slot_of, ok, slice_range_d, slice_frames, &view))
+    return rc;
+  size_t n_slots = 0;
+  for (size_t i = 0; i < n_blocks; i++)
+    {
+      slot_out[i] = slot_of[i];
+      n_slots = std::max (n_slots, size_t (slot_of[i] + 1));
+    }
+  if (n_slots)
+    AWM_HIP_CHECK (hipMemcpyAsync (soft_out, ctx->ws_soft.ptr, n_slots * n_bits * sizeof (float), hipMemcpyDeviceToHost, ctx->stream));
+  AWM_HIP_CHECK (stream_wait (ctx->stream));
+  return 0;
+}
+
+int
+awm_debug_soft_bits_planes_d (awm_ctx *ctx, const uint8_t key[16], const float *planes_d, size_t planes_values, size_t n_blocks, int n_channels,
+                              const long long *block_base_d, const long long *slice_range_d, const int *range_index_d, size_t n_slices,
+                              float *soft_out)
+{
+  AWM_ENTER (ctx);
+  const size_t block_values = size_t (std::max (n_channels, 0)) * Params::n_bands * size_t (block_plane_ld());
+  const bool ranges = slice_range_d != nullptr;
+  const char *bad = nullptr;
+  if (!planes_d || !soft_out)
+    bad = "null pointer";
+  else if (n_channels < 1 || n_channels > 3)
+    bad = "1, 2 or 3 channels";
+  else if (n_blocks < 1 || n_blocks > DEBUG_BLOCKS_MAX)
+    bad = "1 .. 64 blocks";
+  else if (planes_values / block_values < n_blocks)
+    bad = "planes_d holds fewer than n_blocks blocks";
+  else if ((block_base_d != nullptr) != ranges || (range_index_d != nullptr) != ranges || (n_slices != 0) != ranges)
+    bad = "block_base_d, slice_range_d, range_index_d and n_slices go together";
+  if (!bad && ranges)
+    {
+      std::vector<long long> base (n_blocks);
+      std::vector<int> slice (n_blocks);
+      AWM_HIP_CHECK (hipMemcpyAsync (base.data(), block_base_d, n_blocks * sizeof (long long), hipMemcpyDeviceToHost, ctx->stream));
+      AWM_HIP_CHECK (hipMemcpyAsync (slice.data(), range_index_d, n_blocks * sizeof (int), hipMemcpyDeviceToHost, ctx->stream));
+      if (int rc = debug_check_ranges (ctx, slice_range_d, n_slices, DEBUG_RANGE_MAX * n_channels, bad))
+        return rc;
+      for (size_t i = 0; i < n_blocks && !bad; i++)
+        if (base[i] < 0 || base[i] > DEBUG_RANGE_MAX || slice[i] < 0 || size_t (slice[i]) >= n_slices)
+          bad = "a block's base or slice is out of range";
+    }
+  if (bad)
+    {
+      set_error (std::string ("awm_debug_soft_bits_planes_d: ") + bad);
+      return AWM_ERR_ARG;
+    }
+  KeyTables *kt = ctx->get_key_tables (capi_key (key));
+  if (!kt)
+    return AWM_ERR_HIP;
+  const size_t n_bits = mark_data_frame_count() / params().frames_per_bit;
+  if (int rc = ctx->ws_soft.reserve (n_blocks * n_bits * sizeof (float))) return rc;
+  const awmk::SoftBitsArgs sb = block_soft_args (kt, n_channels, planes_d, n_blocks, ctx->ws_soft.as<float>(), block_base_d, range_index_d,
+                                                 slice_range_d, ranges);
+  AWM_HIP_CHECK (awmk::launch_soft_bits (ctx->stream, sb));
+  AWM_HIP_CHECK (hipMemcpyAsync (soft_out, ctx->ws_soft.ptr, n_blocks * n_bits * sizeof (float), hipMemcpyDeviceToHost, ctx->stream));
+  AWM_HIP_CHECK (stream_wait (ctx->stream));
   return 0;
 }
 

@@ -38,8 +38,18 @@ struct DecodeJob
   bool   launched = false;
 };
 
+// a debug view of the block decoder's dB pass (awm_debug_block_db_d): the dB workspace is filled with the pattern before K4b runs and the
+// planes of the accepted blocks, [slot][C][81][block_plane_ld()], go to planes_out (device) after K7 has read them
+struct BlockDbView { unsigned int fill; float *planes_out; };
 int block_soft_bits_dev (awm_ctx *ctx, WorkLane *lane, KeyTables *kt, const DeviceWav& wav, const std::vector<size_t>& index,
-                         std::vector<int>& slot_of, std::vector<char>& ok, const long long *slice_range = nullptr, size_t slice_frames = 0);
+                         std::vector<int>& slot_of, std::vector<char>& ok, const long long *slice_range = nullptr, size_t slice_frames = 0,
+                         const BlockDbView *view = nullptr);
+// the launch arguments of K4b and K7 as block_soft_bits_dev sets them up (wmget.cc)
+long long block_plane_ld();
+awmk::SyncDbArgs block_db_args (const DeviceWav& wav, const long long *d_bases, const int *d_slice_of, size_t nb, float *planes,
+                                const long long *slice_range, size_t slice_frames);
+awmk::SoftBitsArgs block_soft_args (KeyTables *kt, int n_channels, const float *planes, size_t nb, float *out, const long long *d_bases,
+                                    const int *d_slice_of, const long long *slice_range, bool slices);
 // raw (optional): the rows the jobs' source slots index, instead of the lane's ws_soft
 int decode_launch (awm_ctx *ctx, WorkLane *lane, KeyTables *kt, DecodeJob& job, const float *raw = nullptr);
 // patterns_out (optional): the decoded patterns go there as (position in job.pending, bits, error) instead of into result_sets

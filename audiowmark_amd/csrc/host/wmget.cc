@@ -39,11 +39,85 @@ normalize_soft_bits (const std::vector<float>& soft_bits)
   return norm;
 }
 
+/* Launch arguments of K4b and K7 for `nb` blocks of `wav`: d_bases / d_slice_of are the device lists of the blocks' first samples and
+ * slices, planes is [nb][C][81][block_plane_ld()].  block_soft_bits_dev and the debug views (awm_debug_block_db_d,
+ * awm_debug_soft_bits_planes_d) call these two, so that what the views launch is what the product launches. */
+long long
+block_plane_ld()
+{
+  return (long long) ((mark_block_frame_count() + 63) & ~size_t (63));
+}
+
+awmk::SyncDbArgs
+block_db_args (const DeviceWav& wav, const long long *d_bases, const int *d_slice_of, size_t nb, float *planes, const long long *slice_range,
+               size_t slice_frames)
+{
+  const long long ld = block_plane_ld();
+  awmk::SyncDbArgs da {};
+  da.pcm = wav.data;
+  da.n_frames = wav.n_frames;
+  da.n_channels = wav.n_channels;
+  da.per_channel = 1;
+  da.stream_base = d_bases;
+  da.count0 = int (mark_block_frame_count());
+  da.n_streams = (long long) nb;
+  da.hop = Params::frame_size;
+  da.out = planes;
+  da.out_stream_stride = (long long) wav.n_channels * Params::n_bands * ld;
+  da.ld = ld;
+  da.have = nullptr;
+  da.first = 0;
+  da.last = (long long) wav.n_values();      // mix_decode uses plain run_fft: no silence skipping
+  if (slice_range && slice_frames)
+    {
+      da.stream_range = slice_range;
+      da.range_index = d_slice_of;
+      da.range_div = 1;
+      da.silent_frames_are_zero = 1;
+      // K7 gets the same ranges and does not read what is not written -- its wave kernel; the one-thread-per-bit kernel (3 channels at
+      // --frames-per-bit 3, awm_debug_set_soft_bits_generic) loads every cell: every tile is written for it
+      da.skip_unread_silent_tiles = awmk::soft_bits_skips_silent_items (wav.n_channels, params().frames_per_bit) ? 1 : 0;
+    }
+  da.tile_frames = 32;
+  return da;
+}
+
+awmk::SoftBitsArgs
+block_soft_args (KeyTables *kt, int n_channels, const float *planes, size_t nb, float *out, const long long *d_bases, const int *d_slice_of,
+                 const long long *slice_range, bool slices)
+{
+  const long long ld = block_plane_ld();
+  awmk::SoftBitsArgs sb {};
+  sb.db = planes;
+  sb.block_stride = (long long) n_channels * Params::n_bands * ld;
+  sb.ld = ld;
+  sb.n_channels = n_channels;
+  sb.mix_frame = kt->mix_frame.as<int16_t>();
+  sb.mix_up = kt->mix_up.as<uint8_t>();
+  sb.mix_down = kt->mix_down.as<uint8_t>();
+  sb.n_data_frames = mark_data_frame_count();
+  sb.frames_per_bit = params().frames_per_bit;
+  sb.block_frames = int (mark_block_frame_count());
+  sb.n_blocks = (long long) nb;
+  sb.out = out;
+  if (kt->slices && slices)
+    sb.block_slice = d_slice_of;                   // one key per clip: the mix table of the block's slice
+  if (slice_range && slices)
+    {
+      // blocks of padded slices: the items in the padding's silence are known without a load (kernels.hh SoftBitsArgs)
+      sb.block_base = d_bases;
+      sb.stream_range = slice_range;
+      sb.range_index = d_slice_of;
+    }
+  return sb;
+}
+
 /* FFTAnalyzer::fft_range (index, 2226 frames) + mix_decode for a batch of block starts; the soft bits stay on the device:
  * block i (if ok[i]) is slot[i] of ctx->ws_soft ([slots][858] floats) */
 int
 block_soft_bits_dev (awm_ctx *ctx, WorkLane *lane, KeyTables *kt, const DeviceWav& wav, const std::vector<size_t>& index,
-                     std::vector<int>& slot_of, std::vector<char>& ok, const long long *slice_range, size_t slice_frames)
+                     std::vector<int>& slot_of, std::vector<char>& ok, const long long *slice_range, size_t slice_frames,
+                     const BlockDbView *view)
 {
   // slice_range (a row of padded clips, kernels.hh launch_clip_stage): frames in the padding are not transformed, their dB values
   // are written directly (a frame of zeros transforms to exactly -96 dB per band)
@@ -63,8 +137,7 @@ block_soft_bits_dev (awm_ctx *ctx, WorkLane *lane, KeyTables *kt, const DeviceWa
   if (bases.empty())
     return 0;
   hipStream_t st = lane->stream;
-  const long long ld = (count + 63) & ~size_t (63);
-  const long long block_stride = (long long) C * Params::n_bands * ld;
+  const long long block_stride = (long long) C * Params::n_bands * block_plane_ld();
   const size_t max_batch = std::max<size_t> (1, (size_t (2) << 30) / (block_stride * sizeof (float)));
   if (int rc = lane->ws_soft.reserve (bases.size() * n_bits * sizeof (float))) return rc;
   const size_t idx_bytes = bases.size() * (sizeof (long long) + sizeof (int));
@@ -75,66 +148,29 @@ block_soft_bits_dev (awm_ctx *ctx, WorkLane *lane, KeyTables *kt, const DeviceWa
   for (size_t i = 0; i < bases.size(); i++)
     slice_of[i] = slice_frames ? int (size_t (bases[i]) / slice_frames) : 0;
   AWM_HIP_CHECK (hipMemcpyAsync (lane->ws_idx.ptr, lane->pin_blocks.ptr, idx_bytes, hipMemcpyHostToDevice, st));
-  const int *d_slice_of = reinterpret_cast<const int *> (lane->ws_idx.as<long long>() + bases.size());
+  const long long *d_bases = lane->ws_idx.as<long long>();
+  const int *d_slice_of = reinterpret_cast<const int *> (d_bases + bases.size());
+  const bool padded = slice_range && slice_frames;
   for (size_t b0 = 0; b0 < bases.size(); b0 += max_batch)
     {
       const size_t nb = std::min (max_batch, bases.size() - b0);
       if (int rc = lane->ws_block_db.reserve (nb * block_stride * sizeof (float))) return rc;
-      awmk::SyncDbArgs da {};
-      da.pcm = wav.data;
-      da.n_frames = wav.n_frames;
-      da.n_channels = C;
-      da.per_channel = 1;
-      da.stream_base = lane->ws_idx.as<long long>() + b0;
-      da.count0 = int (count);
-      da.n_streams = (long long) nb;
-      da.hop = Params::frame_size;
-      da.out = lane->ws_block_db.as<float>();
-      da.out_stream_stride = block_stride;
-      da.ld = ld;
-      da.have = nullptr;
-      da.first = 0;
-      da.last = (long long) wav.n_values();      // mix_decode uses plain run_fft: no silence skipping
-      if (slice_range && slice_frames)
-        {
-          da.stream_range = slice_range;
-          da.range_index = d_slice_of + b0;
-          da.range_div = 1;
-          da.silent_frames_are_zero = 1;
-          da.skip_unread_silent_tiles = 1;           // (K7 below gets the same ranges: it does not read what is not written)
-        }
-      da.tile_frames = 32;
+      float *planes = lane->ws_block_db.as<float>();
+      if (view)
+        AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (planes), view->fill, nb * block_stride));
+      const awmk::SyncDbArgs da = block_db_args (wav, d_bases + b0, d_slice_of + b0, nb, planes, slice_range, slice_frames);
       {
-        ProfScope ps (ctx, PROF_BLOCK_DB, ((slice_range && slice_frames) ? lane->prof_live_fraction : 1.0) * double (nb) * count * C * (4096.0 + 324.0), st);
+        ProfScope ps (ctx, PROF_BLOCK_DB, (padded ? lane->prof_live_fraction : 1.0) * double (nb) * count * C * (4096.0 + 324.0), st);
         AWM_HIP_CHECK (awmk::launch_sync_db (st, ctx->tabs, da));
       }
-
-      awmk::SoftBitsArgs sb {};
-      sb.db = lane->ws_block_db.as<float>();
-      sb.block_stride = block_stride;
-      sb.ld = ld;
-      sb.n_channels = C;
-      sb.mix_frame = kt->mix_frame.as<int16_t>();
-      sb.mix_up = kt->mix_up.as<uint8_t>();
-      sb.mix_down = kt->mix_down.as<uint8_t>();
-      sb.n_data_frames = mark_data_frame_count();
-      sb.frames_per_bit = params().frames_per_bit;
-      sb.block_frames = int (count);
-      sb.n_blocks = (long long) nb;
-      sb.out = lane->ws_soft.as<float>() + b0 * n_bits;
-      if (kt->slices && slice_frames)
-        sb.block_slice = d_slice_of + b0;              // one key per clip: the mix table of the block's slice
-      if (slice_range && slice_frames)
-        {
-          // blocks of padded slices: the items in the padding's silence are known without a load (kernels.hh SoftBitsArgs)
-          sb.block_base = lane->ws_idx.as<long long>() + b0;
-          sb.stream_range = slice_range;
-          sb.range_index = d_slice_of + b0;
-        }
+      const awmk::SoftBitsArgs sb = block_soft_args (kt, C, planes, nb, lane->ws_soft.as<float>() + b0 * n_bits, d_bases + b0, d_slice_of + b0,
+                                                     slice_range, slice_frames != 0);
       {
-        ProfScope ps (ctx, PROF_SOFT_BITS, ((slice_range && slice_frames) ? lane->prof_live_fraction : 1.0) * double (nb) * count * C * 324.0, st);
+        ProfScope ps (ctx, PROF_SOFT_BITS, (padded ? lane->prof_live_fraction : 1.0) * double (nb) * count * C * 324.0, st);
         AWM_HIP_CHECK (awmk::launch_soft_bits (st, sb));
       }
+      if (view)
+        AWM_HIP_CHECK (hipMemcpyAsync (view->planes_out + b0 * block_stride, planes, nb * block_stride * sizeof (float), hipMemcpyDeviceToDevice, st));
     }
   return 0;
 }

@@ -811,6 +811,28 @@ int  awm_debug_sync_db_sliding_rows_d (awm_ctx *ctx, const float *pcm_d, size_t 
                                        int tables_per_slice, int ld, float *out_d, float *tail_d, long long tail_stream_stride, char *have_d,
                                        long long have_stream_stride);
 void awm_debug_set_soft_bits_generic (int on); /* K7: one thread per soft bit for every shape (the fallback kernel) | four bits per wave */
+/* The block decoder's dB pass (K4b) and soft bits (K7) as awm_block_soft_bits_d launches them, with the dB planes made visible (tests only).
+ * The dB workspace is filled with the 32-bit pattern `fill` before K4b runs; the planes of the accepted blocks go to
+ * planes_out_d[slot][channel][band 0..80][ld] (device, planes_values floats, ld = awm_debug_block_plane_ld()), their soft bits to
+ * soft_out[slot][858] (host), slot_out[i] = the slot of block i or -1 (the block runs past the samples, as ok[i] = 0 of awm_block_soft_bits_d).
+ * slice_range_d (optional, device, [n_slices][2]) with slice_frames is the mode of a row of padded clips: block i belongs to slice
+ * index[i] / slice_frames, whose values that are not digital silence are [first, last) as absolute value indices (first < 0: none); frames
+ * outside get -96 dB without a transform, tiles K7 does not read are not written (where K7 is the one-thread-per-bit kernel, which loads
+ * every cell, all are), and K7 gets the same ranges.
+ * Arguments are checked on the host before anything is launched (at most one synchronisation): AWM_ERR_ARG for up to 3 channels, 1 .. 64
+ * blocks, a planes buffer too small for n_blocks blocks, slices that do not fit the samples, blocks behind the last slice, ranges outside
+ * 0 <= first <= last <= n_frames * n_channels. */
+int  awm_debug_block_plane_ld (awm_ctx *ctx);
+int  awm_debug_block_db_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels, const uint64_t *index,
+                           size_t n_blocks, uint32_t fill, const long long *slice_range_d, size_t n_slices, size_t slice_frames,
+                           float *planes_out_d, size_t planes_values, float *soft_out, int *slot_out);
+/* K7 alone on dB planes of the caller, planes_d[block][channel][81][ld] (device, planes_values floats): soft_out[block][858] (host).
+ * block_base_d [n_blocks], slice_range_d [n_slices][2] and range_index_d [n_blocks] (device, all three or none) are the padded-clip mode:
+ * block b starts at sample block_base_d[b] of a buffer whose slice range_index_d[b] has the range slice_range_d[..]; checked on the host
+ * like the arguments above (bases and ranges within 0 .. 2^40). */
+int  awm_debug_soft_bits_planes_d (awm_ctx *ctx, const uint8_t key[16], const float *planes_d, size_t planes_values, size_t n_blocks, int n_channels,
+                                   const long long *block_base_d, const long long *slice_range_d, const int *range_index_d, size_t n_slices,
+                                   float *soft_out);
 void awm_debug_set_scan_generic (int on);      /* K5w: 1 the approximate search takes launch_sync_scan_window's fallback, the generic K5 (scores identical) | 0 (default) the streaming kernel */
 int  awm_debug_scan_generic_launches (void);   /* K5w: how often launch_sync_scan_window has taken that fallback in this process, by the switch or by its own conditions */
 void awm_debug_set_chunk_stagger (int mode); /* get: phase offset between the chunk lanes -- 0 all chunks start together | 1 chunk i + 1 behind chunk i's
