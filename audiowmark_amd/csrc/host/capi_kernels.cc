@@ -2572,7 +2572,7 @@ add_segment_stream (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex
   return 0;
 }
 
-/* ---- segments with a KEY EACH (awm_add_watermark_segments_keys_d, below): what the two fused paths need beyond one key.  The tables are
+/* ---- segments with a KEY EACH (awm_add_watermark_segments_keys_d, below): what the fused path needs beyond one key.  The tables are
  * the distinct (key, payload) pairs, ordered by key; K16t (hip/keytab.hip) builds the templates of the keys a table group needs, at
  * most KEY_TMPL_LAUNCH per launch, into slot key mod KEY_TMPL_SLOTS of a workspace, and K16p reads table t's template through tmpl_of[t].
  * A group's keys are neighbours and no more than its tables, so within a group no two of them share a slot; a key whose template an
@@ -2662,230 +2662,6 @@ struct SegmentKeys
     return 0;
   }
 };
-
-/* the fused path: segs = the segments with samples, ordered by payload; payload_of[i] = index of segment i's payload among the distinct
- * ones; coded = their codes, [distinct][2 (A, B)][n_code] bytes.  With a key per segment (mk; key is not used): ordered by (key, payload),
- * and "payload" reads "(key, payload) pair" -- a table each, expanded from the template of its key.
- * T = int16_t (awm_add_watermark_segments_rate_s16_d): segments of signed 16-bit PCM.  EVERY segment is staged, the
- * r == 0 ones too -- the gather decodes on its way into ws_seg_in, K2 and the limiter's table run on the slices as for float --, and the
- * scatter is the limiter's apply pass with a 16-bit sink: it reads the un-limited mix from ws_seg_out behind the r samples, scales,
- * encodes and stores to out_d */
-extern "C++" {
-template<class T> static int
-add_segments_fused (awm_ctx *ctx, const uint8_t key[16], const std::vector<size_t>& segs, const std::vector<size_t>& payload_of,
-                    const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames, const T *const *pcm_in_d,
-                    T *const *out_d, const size_t *n_frames, SegmentKeys *mk = nullptr)
-{
-  constexpr bool S16 = std::is_same<T, int16_t>::value;
-  typedef typename std::conditional<S16, awmk::LimitEncodeSegment, awmk::SegmentCopy>::type Scatter;
-  constexpr size_t PER_LAUNCH = 4096;                      // (blockIdx.y <= 65535; a launch of 4096 clips fills the device many times over)
-  constexpr size_t TABLE_GROUP = 1024;                     // distinct payloads whose tables exist at a time (~370 MB at the default geometry)
-  constexpr size_t STAGE_MAX_FLOATS = size_t (1) << 28;    // staged samples per batch and direction (1 GiB): a batch that would need more is split
-  const size_t FRAME = Params::frame_size, n = segs.size(), n_distinct = coded.size() / (2 * n_code);
-  const int use_limiter = !params().test_no_limiter;
-  const size_t block_frames = mark_block_frame_count();
-  const size_t table_stride = awmk::payload_table_stride (block_frames);
-  hipStream_t st = ctx->stream;
-
-  FrameModTemplate *tmpl = mk ? nullptr : ctx->get_frame_mod_template (capi_key (key));      // (a key per segment: SegmentKeys' templates)
-  if (!tmpl && !mk)
-    return AWM_ERR_HIP;
-
-  // geometry of every segment and the batches: consecutive segments (in payload order) of one table group, at most PER_LAUNCH of them
-  struct Seg { size_t r, skipped, len, first_block, n_blocks, n_tab, max_off, tab_off, stage_off; };
-  struct Batch { size_t i0, i1, g0, g1, stage_floats, max_len, max_tab; };
-  std::vector<Seg> geo (n);
-  std::vector<Batch> batches;
-  size_t max_total = 0, tab_total = 0, stage_max = 0, n_staged = 0;
-  long long total_frames1024 = 0;
-  for (size_t i = 0; i < n; i++)
-    {
-      const size_t zf = zero_frames[segs[i]];
-      Seg& g = geo[i];
-      g.r = zf % FRAME;
-      g.skipped = zf - g.r;
-      g.len = g.r + n_frames[segs[i]];                     // the stream behind the whole frames of zeros: r zeros, then the segment
-      g.first_block = g.skipped / LIMITER_BLOCK;
-      g.n_blocks = (g.skipped + g.len) / LIMITER_BLOCK + 2 - g.first_block;
-      g.n_tab = awmk::limiter_tab_entries ((long long) g.len, (long long) g.skipped, LIMITER_BLOCK);
-      g.max_off = max_total;
-      g.tab_off = tab_total;
-      max_total += g.n_blocks;
-      tab_total += g.n_tab + 1;
-      total_frames1024 += (long long) ((g.len + FRAME - 1) / FRAME);
-      const bool stage = g.r || S16;
-      const size_t stage_floats = stage ? (g.len * 2 + 3) / 4 * 4 : 0;
-      if (batches.empty() || i - batches.back().i0 >= PER_LAUNCH || payload_of[i] / TABLE_GROUP != payload_of[batches.back().i0] / TABLE_GROUP
-          || (batches.back().stage_floats && batches.back().stage_floats + stage_floats > STAGE_MAX_FLOATS))
-        batches.push_back ({ i, i, n_staged, n_staged, 0, 0, 0 });
-      Batch& b = batches.back();
-      g.stage_off = b.stage_floats;
-      b.stage_floats += stage_floats;
-      b.i1 = i + 1;
-      b.max_len = std::max (b.max_len, g.len);
-      b.max_tab = std::max (b.max_tab, g.n_tab);
-      if (stage)
-        b.g1 = ++n_staged;
-      stage_max = std::max (stage_max, b.stage_floats);
-    }
-  const int L = frames_per_span (ctx, total_frames1024);
-
-  // one page-locked block, one upload: the segments' kernel arguments, the gather / scatter lists of the staged ones, the payloads' codes
-  const size_t off_lim = n * sizeof (awmk::AddMixArgs), off_gather = off_lim + n * sizeof (awmk::LimiterClip),
-               off_scatter = off_gather + n_staged * sizeof (awmk::SegmentCopy), off_coded = off_scatter + n_staged * sizeof (Scatter),
-               off_keys = (off_coded + coded.size() + 15) / 16 * 16;
-  if (mk)
-    if (int rc = mk->reserve (ctx, table_stride)) return rc;
-  const size_t arg_bytes = mk ? off_keys + mk->arg_bytes() : off_coded + coded.size();
-  if (int rc = ctx->ws_add_batch.reserve (arg_bytes)) return rc;
-  if (int rc = ctx->ws_keytab.reserve (std::min (n_distinct, TABLE_GROUP) * table_stride)) return rc;
-  if (use_limiter)
-    {
-      if (int rc = ctx->ws_block_max.reserve (max_total * sizeof (float))) return rc;
-      if (int rc = ctx->ws_limit_tab.reserve (tab_total * sizeof (float2))) return rc;
-    }
-  if (stage_max)
-    {
-      if (int rc = ctx->ws_seg_in.reserve (stage_max * sizeof (float))) return rc;
-      if (int rc = ctx->ws_seg_out.reserve (stage_max * sizeof (float))) return rc;
-    }
-  if (ctx->ev_add_batch)
-    AWM_HIP_CHECK (hipEventSynchronize (ctx->ev_add_batch));            // (an earlier batch's staging has been copied)
-  else
-    AWM_HIP_CHECK (hipEventCreateWithFlags (&ctx->ev_add_batch, hipEventDisableTiming));
-  if (int rc = ctx->pin_add_batch.reserve (arg_bytes)) return rc;
-  char *h = ctx->pin_add_batch.as<char>(), *d = ctx->ws_add_batch.as<char>();
-  auto *h_mix = reinterpret_cast<awmk::AddMixArgs *> (h);
-  auto *h_lim = reinterpret_cast<awmk::LimiterClip *> (h + off_lim);
-  auto *h_gather = reinterpret_cast<awmk::SegmentCopy *> (h + off_gather);
-  auto *h_scatter = reinterpret_cast<Scatter *> (h + off_scatter);
-  const auto *d_mix = reinterpret_cast<const awmk::AddMixArgs *> (d);
-  const auto *d_lim = reinterpret_cast<const awmk::LimiterClip *> (d + off_lim);
-  const auto *d_gather = reinterpret_cast<const awmk::SegmentCopy *> (d + off_gather);
-  const auto *d_scatter = reinterpret_cast<const Scatter *> (d + off_scatter);
-  const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
-  std::memcpy (h + off_coded, coded.data(), coded.size());
-  if (mk)
-    mk->fill (h + off_keys, d + off_keys);
-  float *block_max = ctx->ws_block_max.as<float>();
-  float2 *tabs = ctx->ws_limit_tab.as<float2>();
-  std::vector<long long> spans (n);
-  size_t staged = 0;
-  for (size_t i = 0; i < n; i++)
-    {
-      const Seg& g = geo[i];
-      const size_t s = segs[i];
-      const float *in = ctx->ws_seg_in.as<float>() + g.stage_off;
-      float *out = ctx->ws_seg_out.as<float>() + g.stage_off;
-      if constexpr (!S16)
-        if (!g.r)
-          {
-            in = pcm_in_d[s];
-            out = out_d[s];
-          }
-      awmk::AddMixArgs a {};
-      a.pcm_in = in;
-      a.out = out;
-      a.n_frames = (long long) g.len;
-      a.n_channels = 2;
-      a.frame_mod = ctx->ws_keytab.as<int8_t>() + (payload_of[i] % TABLE_GROUP) * table_stride;
-      fill_add_mix_common (a, params().water_delta);
-      a.first_frame = (long long) (g.skipped / FRAME);
-      a.block_max = use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr;
-      a.first_block = (long long) g.first_block;
-      a.n_blocks = (long long) g.n_blocks;
-      a.frames_per_span = L;
-      h_mix[i] = a;
-      h_lim[i] = { out, (long long) g.len, block_max + g.max_off, (long long) g.n_blocks, tabs + g.tab_off, (long long) g.n_tab,
-                   (long long) g.skipped, (long long) g.first_block };
-      spans[i] = ((long long) ((g.len + FRAME - 1) / FRAME) + L - 1) / L;
-      if (g.r || S16)
-        {
-          // (16-bit: `src` holds the address of the int16 values, launch_segment_gather_s16)
-          h_gather[staged] = { reinterpret_cast<const float *> (pcm_in_d[s]), ctx->ws_seg_in.as<float>() + g.stage_off, (long long) (n_frames[s] * 2),
-                               (long long) (g.r * 2) };
-          if constexpr (S16)
-            h_scatter[staged] = { nullptr, out + g.r * 2, out_d[s], (long long) n_frames[s], (long long) zero_frames[s],
-                                  use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.skipped / LIMITER_BLOCK) };
-          else
-            h_scatter[staged] = { out + g.r * 2, out_d[s], (long long) (n_frames[s] * 2), 0 };
-          staged++;
-        }
-    }
-  AWM_HIP_CHECK (hipMemcpyAsync (d, h, arg_bytes, hipMemcpyHostToDevice, st));
-  AWM_HIP_CHECK (hipEventRecord (ctx->ev_add_batch, st));
-
-  size_t group_built = size_t (-1);
-  for (const Batch& b : batches)
-    {
-      const size_t group = payload_of[b.i0] / TABLE_GROUP, nb = b.i1 - b.i0;
-      if (group != group_built)
-        {
-          awmk::PayloadTableArgs pa {};
-          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
-          pa.tmpl = mk ? ctx->ws_key_tmpl.as<short>() : tmpl->dev.as<short>();
-          if (mk)
-            {
-              if (int rc = mk->build (ctx, st, group * TABLE_GROUP + size_t (pa.n_payloads))) return rc;
-              pa.tmpl_of = mk->d_tmpl_of + group * TABLE_GROUP;
-              pa.tmpl_stride = (long long) table_stride;
-            }
-          pa.coded = d_coded + group * TABLE_GROUP * 2 * n_code;
-          pa.tables = ctx->ws_keytab.as<signed char>();
-          pa.table_stride = (long long) table_stride;
-          pa.half_entries = int (block_frames * Params::n_bands);
-          pa.n_code = int (n_code);
-          ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (pa.n_payloads) * table_stride, st);          // the tables out, once
-          AWM_HIP_CHECK (awmk::launch_payload_tables (st, pa));
-          group_built = group;
-        }
-      long long max_spans = 0;
-      double values = 0;
-      for (size_t i = b.i0; i < b.i1; i++)
-        {
-          max_spans = std::max (max_spans, spans[i]);
-          values += double (geo[i].len) * 2;
-        }
-      if constexpr (S16)
-        {
-          ProfScope ps (ctx, PROF_SEGMENT_GATHER_S16, values * 6.0, st);            // int16 in, float out
-          AWM_HIP_CHECK (awmk::launch_segment_gather_s16 (st, d_gather + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
-        }
-      else if (b.g1 > b.g0)
-        AWM_HIP_CHECK (awmk::launch_segment_copy (st, d_gather + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
-      if (use_limiter)
-        {
-          unsigned int bits;
-          std::memcpy (&bits, &LIMITER_CEILING, sizeof (bits));
-          const size_t m0 = geo[b.i0].max_off, m1 = geo[b.i1 - 1].max_off + geo[b.i1 - 1].n_blocks;
-          AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (block_max + m0), bits, m1 - m0));
-        }
-      {
-        ProfScope ps (ctx, PROF_ADD_MIX, values * 8.0, st);                          // read + write every sample once
-        AWM_HIP_CHECK (awmk::launch_add_mix_batch (st, ctx->tabs, d_mix + b.i0, int (nb), max_spans, int (block_frames), int (Params::frames_pad_start)));
-      }
-      if constexpr (S16)
-        {
-          // the ramp tables alone, then limit + encode from the staged mix to the caller's buffers
-          if (use_limiter)
-            AWM_HIP_CHECK (awmk::launch_limiter_table_batch (st, d_lim + b.i0, int (nb), (long long) b.max_len, LIMITER_BLOCK, LIMITER_CEILING, (long long) b.max_tab));
-          ProfScope ps (ctx, PROF_LIMIT_ENCODE_S16, values * 6.0, st);               // float in, int16 out
-          AWM_HIP_CHECK (awmk::launch_limit_encode_segments (st, d_scatter + b.g0, int (b.g1 - b.g0), (long long) b.max_len, false, LIMITER_BLOCK));
-        }
-      else
-        {
-          if (use_limiter)
-            {
-              ProfScope ps (ctx, PROF_LIMITER, values * 8.0, st);
-              AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_lim + b.i0, int (nb), (long long) b.max_len, 2, LIMITER_BLOCK, LIMITER_CEILING, (long long) b.max_tab));
-            }
-          if (b.g1 > b.g0)
-            AWM_HIP_CHECK (awmk::launch_segment_copy (st, d_scatter + b.g0, int (b.g1 - b.g0), (long long) b.max_len * 2));
-        }
-    }
-  return 0;
-}
-} // extern "C++"
 
 /* what both segment entry points check before anything is enqueued (fn: the entry point, for the messages), and the distinct payloads'
  * codes: payload_index[i] = index of segment i's payload among the distinct ones, coded = [distinct][2 (A, B)][n_code] bytes.  T: the sample
@@ -2998,40 +2774,6 @@ segments_by_payload (size_t n_segments, const size_t *n_frames, const std::vecto
   payload_of.resize (segs.size());
   for (size_t i = 0; i < segs.size(); i++)
     payload_of[i] = payload_index[segs[i]];
-}
-
-int
-awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
-                              const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels)
-{
-  AWM_ENTER (ctx);
-  g_add_segments_fused_in_use = 0;
-  if (!n_segments)
-    return 0;
-  std::vector<size_t> payload_index;
-  std::vector<unsigned char> coded;
-  size_t n_code = 0;
-  if (int rc = segments_check (ctx, "awm_add_watermark_segments_d", key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels,
-                               payload_index, coded, n_code))
-    return rc;
-  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2;
-  for (size_t i = 0; i < n_segments && fused; i++)
-    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) & 15) || (reinterpret_cast<uintptr_t> (out_d[i]) & 15)))
-      fused = false;
-  if (!fused)
-    {
-      for (size_t i = 0; i < n_segments; i++)
-        if (n_frames[i])
-          if (int rc = add_segment_stream (ctx, key, payload_hex[i], zero_frames[i], pcm_in_d[i], out_d[i], n_frames[i], n_channels))
-            return rc;
-      return 0;
-    }
-  std::vector<size_t> segs, payload_of;
-  segments_by_payload (n_segments, n_frames, payload_index, segs, payload_of);
-  g_add_segments_fused_in_use = 1;
-  if (segs.empty())
-    return 0;
-  return add_segments_fused (ctx, key, segs, payload_of, coded, n_code, zero_frames, pcm_in_d, out_d, n_frames);
 }
 
 /* ---- the same at another sample rate: awm_add_watermark_segments_rate_d (include/awm_hip.h).  add_full_rate's stages
@@ -3175,310 +2917,8 @@ segments_rate_fit_the_workspaces (size_t n_segments, const size_t *zero_frames, 
   return true;
 }
 
-/* the fused path (stereo): segs / payload_of / coded as for add_segments_fused.
- * T = int16_t (awm_add_watermark_segments_rate_s16_d): the down-resampler reads the int16 segments, K2 and the
- * up-resampler are as for float, the mix is computed twice and stored never -- once for the block maxima, once in the last pass, which
- * scales by the limiter's ramp, encodes and stores int16 to out_d.  No workspace beyond ws_rate_a / b / c */
-extern "C++" {
-template<class T> static int
-add_segments_rate_fused (awm_ctx *ctx, const ResampleTable& down, const ResampleTable& up, const uint8_t key[16], const std::vector<size_t>& segs,
-                         const std::vector<size_t>& payload_of, const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames,
-                         const T *const *pcm_in_d, T *const *out_d, const size_t *n_frames, int rate, SegmentKeys *mk = nullptr)
-{
-  constexpr bool S16 = std::is_same<T, int16_t>::value;
-  constexpr size_t PER_LAUNCH = 4096, TABLE_GROUP = 1024;  // as in add_segments_fused
-  const int C = 2;
-  const size_t FRAME = Params::frame_size, n = segs.size(), n_distinct = coded.size() / (2 * n_code);
-  const int use_limiter = !params().test_no_limiter;
-  const size_t block_frames = mark_block_frame_count();
-  const size_t table_stride = awmk::payload_table_stride (block_frames);
-  hipStream_t st = ctx->stream;
-
-  FrameModTemplate *tmpl = mk ? nullptr : ctx->get_frame_mod_template (capi_key (key));      // (a key per segment: SegmentKeys' templates)
-  if (!tmpl && !mk)
-    return AWM_ERR_HIP;
-
-  // the window of every segment and the batches: consecutive segments (in payload order) of one table group, at most PER_LAUNCH of them.
-  // Segments of a batch that agree in input, length and offset share one down-resampled slice
-  struct Seg { SegmentWindow w; size_t down, x44_off, wm44_off, wm_off, max_off, tab_off; };
-  struct Batch { size_t i0, i1, d0, d1, x44_floats, wm44_floats, wm_floats, max_n44, max_out, max_tab; long long frames1024; };
-  std::vector<Seg> geo (n);
-  std::vector<Batch> batches;
-  std::vector<size_t> down_owner;                          // (ordered) segment whose window a down slice is made for
-  std::map<std::tuple<const T *, size_t, size_t>, size_t> shared;
-  size_t max_total = 0, tab_total = 0;
-  int lim_block = 0;
-  for (size_t i = 0; i < n; i++)
-    {
-      Seg& g = geo[i];
-      const size_t s = segs[i];
-      if (int rc = segment_window (rate, zero_frames[s], n_frames[s], g.w))
-        return rc;
-      lim_block = int (g.w.p.limiter_block);
-      // (a segment that alone exceeds a workspace never gets here: segments_rate_fit_the_workspaces)
-      const size_t n44_floats = g.w.slice_frames * FRAME * C, wm_floats = ((g.w.pre + g.w.n) * C + 3) / 4 * 4;
-      const auto id = std::make_tuple (pcm_in_d[s], n_frames[s], zero_frames[s]);
-      bool fresh = batches.empty() || i - batches.back().i0 >= PER_LAUNCH || payload_of[i] / TABLE_GROUP != payload_of[batches.back().i0] / TABLE_GROUP;
-      if (!fresh)
-        {
-          const Batch& b = batches.back();
-          const bool have = shared.count (id) > 0;
-          fresh = b.wm44_floats + n44_floats > WS_MAX_FLOATS || b.wm_floats + wm_floats > WS_MAX_FLOATS || (!have && b.x44_floats + n44_floats > WS_MAX_FLOATS);
-        }
-      if (fresh)
-        {
-          batches.push_back ({ i, i, down_owner.size(), down_owner.size(), 0, 0, 0, 0, 0, 0, 0 });
-          shared.clear();
-        }
-      Batch& b = batches.back();
-      auto it = shared.find (id);
-      if (it == shared.end())
-        {
-          it = shared.emplace (id, i).first;
-          g.x44_off = b.x44_floats;
-          b.x44_floats += n44_floats;
-          down_owner.push_back (i);
-          b.d1 = down_owner.size();
-        }
-      else
-        g.x44_off = geo[it->second].x44_off;
-      g.wm44_off = b.wm44_floats;
-      b.wm44_floats += n44_floats;
-      g.wm_off = b.wm_floats;
-      b.wm_floats += wm_floats;
-      g.max_off = max_total;
-      g.tab_off = tab_total;
-      max_total += size_t (g.w.p.n_blocks);
-      tab_total += g.w.n_tab + 1;
-      b.i1 = i + 1;
-      b.max_n44 = std::max (b.max_n44, g.w.slice_frames * FRAME);
-      b.max_out = std::max (b.max_out, g.w.pre + g.w.n);
-      b.max_tab = std::max (b.max_tab, g.w.n_tab);
-      b.frames1024 += (long long) g.w.slice_frames;
-    }
-  size_t x44_max = 0, wm44_max = 0, wm_max = 0;
-  long long frames_max = 0;
-  for (const Batch& b : batches)
-    {
-      x44_max = std::max (x44_max, b.x44_floats);
-      wm44_max = std::max (wm44_max, b.wm44_floats);
-      wm_max = std::max (wm_max, b.wm_floats);
-      frames_max = std::max (frames_max, b.frames1024);
-    }
-  const int L = frames_per_span (ctx, frames_max);
-  const size_t n_down = down_owner.size();
-
-  // one page-locked block, one upload: the kernel arguments of every stage and the payloads' codes
-  const size_t off_mix = n_down * sizeof (awmk::ResampleSlice), off_up = off_mix + n * sizeof (awmk::AddMixArgs),
-               off_mm = off_up + n * sizeof (awmk::ResampleSlice), off_lim = off_mm + n * sizeof (awmk::MixSegment),
-               off_enc = off_lim + n * sizeof (awmk::LimiterClip), off_coded = off_enc + (S16 ? n * sizeof (awmk::LimitEncodeSegment) : 0),
-               off_keys = (off_coded + coded.size() + 15) / 16 * 16;
-  if (mk)
-    if (int rc = mk->reserve (ctx, table_stride)) return rc;
-  const size_t arg_bytes = mk ? off_keys + mk->arg_bytes() : off_coded + coded.size();
-  if (int rc = ctx->ws_add_batch.reserve (arg_bytes)) return rc;
-  if (int rc = ctx->ws_keytab.reserve (std::min (n_distinct, TABLE_GROUP) * table_stride)) return rc;
-  if (int rc = ctx->ws_rate_a.reserve (x44_max * sizeof (float))) return rc;
-  if (int rc = ctx->ws_rate_b.reserve (wm44_max * sizeof (float))) return rc;
-  if (int rc = ctx->ws_rate_c.reserve (wm_max * sizeof (float))) return rc;
-  if (use_limiter)
-    {
-      if (int rc = ctx->ws_block_max.reserve (max_total * sizeof (float))) return rc;
-      if (int rc = ctx->ws_limit_tab.reserve (tab_total * sizeof (float2))) return rc;
-    }
-  if (ctx->ev_add_batch)
-    AWM_HIP_CHECK (hipEventSynchronize (ctx->ev_add_batch));            // (an earlier batch's staging has been copied)
-  else
-    AWM_HIP_CHECK (hipEventCreateWithFlags (&ctx->ev_add_batch, hipEventDisableTiming));
-  if (int rc = ctx->pin_add_batch.reserve (arg_bytes)) return rc;
-  char *h = ctx->pin_add_batch.as<char>(), *d = ctx->ws_add_batch.as<char>();
-  auto *h_down = reinterpret_cast<awmk::ResampleSlice *> (h), *h_up = reinterpret_cast<awmk::ResampleSlice *> (h + off_up);
-  auto *h_mix = reinterpret_cast<awmk::AddMixArgs *> (h + off_mix);
-  auto *h_mm = reinterpret_cast<awmk::MixSegment *> (h + off_mm);
-  auto *h_lim = reinterpret_cast<awmk::LimiterClip *> (h + off_lim);
-  auto *h_enc = reinterpret_cast<awmk::LimitEncodeSegment *> (h + off_enc);                 // (16-bit only)
-  const auto *d_down = reinterpret_cast<const awmk::ResampleSlice *> (d), *d_up = reinterpret_cast<const awmk::ResampleSlice *> (d + off_up);
-  const auto *d_mix = reinterpret_cast<const awmk::AddMixArgs *> (d + off_mix);
-  const auto *d_mm = reinterpret_cast<const awmk::MixSegment *> (d + off_mm);
-  const auto *d_lim = reinterpret_cast<const awmk::LimiterClip *> (d + off_lim);
-  const auto *d_enc = reinterpret_cast<const awmk::LimitEncodeSegment *> (d + off_enc);
-  const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
-  std::memcpy (h + off_coded, coded.data(), coded.size());
-  if (mk)
-    mk->fill (h + off_keys, d + off_keys);
-  float *x44 = ctx->ws_rate_a.as<float>(), *wm44 = ctx->ws_rate_b.as<float>(), *wm = ctx->ws_rate_c.as<float>();
-  float *block_max = ctx->ws_block_max.as<float>();
-  float2 *tabs = ctx->ws_limit_tab.as<float2>();
-  for (size_t k = 0; k < n_down; k++)
-    {
-      const Seg& g = geo[down_owner[k]];
-      h_down[k] = window_down_slice (g.w, pcm_in_d[segs[down_owner[k]]], C, x44 + g.x44_off);
-    }
-  for (size_t i = 0; i < n; i++)
-    {
-      const Seg& g = geo[i];
-      const size_t s = segs[i];
-      const int8_t *table = ctx->ws_keytab.as<int8_t>() + (payload_of[i] % TABLE_GROUP) * table_stride;
-      h_mix[i] = window_mix_args (g.w, x44 + g.x44_off, wm44 + g.wm44_off, C, table, params().water_delta, L);
-      h_up[i] = window_up_slice (g.w, wm44 + g.wm44_off, C, wm + g.wm_off);
-      float *mix_out = nullptr;                                   // (16-bit: no mix is stored; `orig` holds the address of the int16 values)
-      if constexpr (!S16)
-        mix_out = out_d[s];
-      h_mm[i] = { reinterpret_cast<const float *> (pcm_in_d[s]), wm + g.wm_off, mix_out, (long long) g.w.n, (long long) g.w.pre, (long long) g.w.Z,
-                  use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr, (long long) g.w.p.first_block, (long long) g.w.p.n_blocks };
-      h_lim[i] = { mix_out, (long long) g.w.n, use_limiter ? block_max + g.max_off : nullptr, (long long) g.w.p.n_blocks,
-                   use_limiter ? tabs + g.tab_off : nullptr, (long long) g.w.n_tab, (long long) g.w.Z, (long long) g.w.p.first_block };
-      if constexpr (S16)
-        h_enc[i] = { pcm_in_d[s], wm + g.wm_off + g.w.pre * C, out_d[s], (long long) g.w.n, (long long) g.w.Z,
-                     use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.w.Z / size_t (g.w.p.limiter_block)) };
-    }
-  AWM_HIP_CHECK (hipMemcpyAsync (d, h, arg_bytes, hipMemcpyHostToDevice, st));
-  AWM_HIP_CHECK (hipEventRecord (ctx->ev_add_batch, st));
-
-  const awmk::ResampleArgs ra_down = resample_table_args (down, C), ra_up = resample_table_args (up, C);
-  size_t group_built = size_t (-1);
-  for (const Batch& b : batches)
-    {
-      const size_t group = payload_of[b.i0] / TABLE_GROUP, nb = b.i1 - b.i0;
-      if (group != group_built)
-        {
-          awmk::PayloadTableArgs pa {};
-          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
-          pa.tmpl = mk ? ctx->ws_key_tmpl.as<short>() : tmpl->dev.as<short>();
-          if (mk)
-            {
-              if (int rc = mk->build (ctx, st, group * TABLE_GROUP + size_t (pa.n_payloads))) return rc;
-              pa.tmpl_of = mk->d_tmpl_of + group * TABLE_GROUP;
-              pa.tmpl_stride = (long long) table_stride;
-            }
-          pa.coded = d_coded + group * TABLE_GROUP * 2 * n_code;
-          pa.tables = ctx->ws_keytab.as<signed char>();
-          pa.table_stride = (long long) table_stride;
-          pa.half_entries = int (block_frames * Params::n_bands);
-          pa.n_code = int (n_code);
-          ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (pa.n_payloads) * table_stride, st);          // the tables out, once
-          AWM_HIP_CHECK (awmk::launch_payload_tables (st, pa));
-          group_built = group;
-        }
-      double down_values = 0, up_values = 0, n44_values = 0, out_values = 0;
-      long long max_spans = 0;
-      for (size_t k = b.d0; k < b.d1; k++)
-        down_values += double (h_down[k].n_in + h_down[k].n_out) * C;
-      for (size_t i = b.i0; i < b.i1; i++)
-        {
-          up_values += double (h_up[i].n_in + h_up[i].n_out) * C;
-          n44_values += double (geo[i].w.slice_frames * FRAME) * C;
-          out_values += double (geo[i].w.n) * C;
-          max_spans = std::max (max_spans, ((long long) geo[i].w.slice_frames + L - 1) / L);
-        }
-      {
-        ProfScope ps (ctx, PROF_RESAMPLE, down_values * 4.0, st);                     // every input and output sample once
-        if constexpr (S16)
-          AWM_HIP_CHECK (awmk::launch_resample_slices_s16 (st, ra_down, d_down + b.d0, int (b.d1 - b.d0), (long long) b.max_n44, true));
-        else
-          AWM_HIP_CHECK (awmk::launch_resample_slices (st, ra_down, d_down + b.d0, int (b.d1 - b.d0), (long long) b.max_n44, true));
-      }
-      if (use_limiter)
-        {
-          unsigned int bits;
-          std::memcpy (&bits, &LIMITER_CEILING, sizeof (bits));
-          const size_t m0 = geo[b.i0].max_off, m1 = geo[b.i1 - 1].max_off + size_t (geo[b.i1 - 1].w.p.n_blocks);
-          AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (block_max + m0), bits, m1 - m0));
-        }
-      {
-        ProfScope ps (ctx, PROF_ADD_MIX, n44_values * 8.0, st);
-        AWM_HIP_CHECK (awmk::launch_add_mix_batch (st, ctx->tabs, d_mix + b.i0, int (nb), max_spans, int (block_frames), int (Params::frames_pad_start)));
-      }
-      {
-        ProfScope ps (ctx, PROF_RESAMPLE, up_values * 4.0, st);
-        AWM_HIP_CHECK (awmk::launch_resample_slices (st, ra_up, d_up + b.i0, int (nb), (long long) b.max_out, true));
-      }
-      size_t max_len = 0;
-      for (size_t i = b.i0; i < b.i1; i++)
-        max_len = std::max (max_len, geo[i].w.n);
-      if constexpr (S16)
-        {
-          // the block maxima from the mix, the ramp tables, then the mix again: limited, encoded and stored as int16
-          if (use_limiter)
-            {
-              AWM_HIP_CHECK (awmk::launch_max_segments_s16 (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, lim_block));
-              AWM_HIP_CHECK (awmk::launch_limiter_table_batch (st, d_lim + b.i0, int (nb), (long long) max_len, lim_block, LIMITER_CEILING, (long long) b.max_tab));
-            }
-          ProfScope ps (ctx, PROF_LIMIT_ENCODE_S16, out_values * 8.0, st);            // int16 and float in, int16 out
-          AWM_HIP_CHECK (awmk::launch_limit_encode_segments (st, d_enc + b.i0, int (nb), (long long) max_len, true, lim_block));
-        }
-      else
-        {
-          AWM_HIP_CHECK (awmk::launch_mix_max_segments (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, lim_block));
-          if (use_limiter)
-            {
-              ProfScope ps (ctx, PROF_LIMITER, out_values * 8.0, st);
-              AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_lim + b.i0, int (nb), (long long) max_len, C, lim_block, LIMITER_CEILING, (long long) b.max_tab));
-            }
-        }
-    }
-  return 0;
-}
-} // extern "C++"
-
-int
-awm_add_watermark_segments_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
-                                   const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
-{
-  if (sample_rate == Params::mark_sample_rate)
-    return awm_add_watermark_segments_d (ctx, key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels);
-  AWM_ENTER (ctx);
-  g_add_segments_fused_in_use = 0;
-  const char *fn = "awm_add_watermark_segments_rate_d";
-  awm_segment_plan probe;
-  if (awm_add_segment_plan (sample_rate, 0, 0, &probe))
-    {
-      set_error (sample_rate <= 0 ? string_printf ("%s: bad sample rate %d", fn, sample_rate)
-                                  : string_printf ("%s: no fixed-ratio resampler between %d Hz and %d Hz (zita's VResampler is not offered here)", fn,
-                                                   sample_rate, Params::mark_sample_rate));
-      return AWM_ERR_ARG;
-    }
-  if (!n_segments)
-    return 0;
-  std::vector<size_t> payload_index;
-  std::vector<unsigned char> coded;
-  size_t n_code = 0;
-  if (int rc = segments_check (ctx, fn, key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, payload_index, coded, n_code))
-    return rc;
-  for (size_t i = 0; i < n_segments; i++)
-    if (awm_add_segment_plan (sample_rate, zero_frames[i], n_frames[i], &probe))
-      {
-        set_error (string_printf ("%s: zero_frames + n_frames of segment %zu is not below 2^40", fn, i));
-        return AWM_ERR_ARG;
-      }
-  const ResampleTable *down = ctx->get_resample_table (sample_rate, Params::mark_sample_rate);
-  const ResampleTable *up = ctx->get_resample_table (Params::mark_sample_rate, sample_rate);
-  if (!down || !up)
-    return AWM_ERR_HIP;
-  // (the batched limiter needs blocks of at least four of its runs: launch_limiter_batch)
-  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2 && probe.limiter_block >= 8192
-               && segments_rate_fit_the_workspaces (n_segments, zero_frames, n_frames, n_channels, sample_rate);
-  for (size_t i = 0; i < n_segments && fused; i++)
-    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) & 15) || (reinterpret_cast<uintptr_t> (out_d[i]) & 15)))
-      fused = false;
-  if (!fused)
-    {
-      for (size_t i = 0; i < n_segments; i++)
-        if (n_frames[i])
-          if (int rc = add_segment_rate (ctx, *down, *up, key, payload_hex[i], zero_frames[i], pcm_in_d[i], out_d[i], n_frames[i], n_channels, sample_rate))
-            return rc;
-      return 0;
-    }
-  std::vector<size_t> segs, payload_of;
-  segments_by_payload (n_segments, n_frames, payload_index, segs, payload_of);
-  g_add_segments_fused_in_use = 1;
-  if (segs.empty())
-    return 0;
-  return add_segments_rate_fused (ctx, *down, *up, key, segs, payload_of, coded, n_code, zero_frames, pcm_in_d, out_d, n_frames, sample_rate);
-}
-
-/* ---- segments with a key each: awm_add_watermark_segments_keys_d / _rate_d (include/awm_hip.h).  The fused paths
- * above with one thing more per table: the template it is expanded from (SegmentKeys). ---- */
+/* ---- segments with a key each: awm_add_watermark_segments_keys_d / _rate_d (include/awm_hip.h).  The fused path
+ * below with one thing more per table: the template it is expanded from (SegmentKeys). ---- */
 static bool
 segments_share_one_key (const uint8_t *keys, size_t n_segments)
 {
@@ -3524,211 +2964,20 @@ segments_by_key_and_payload (size_t n_segments, const uint8_t *keys, const size_
     }
 }
 
-int
-awm_add_watermark_segments_keys_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
-                                   const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels)
-{
-  // one key for all segments IS the one-key function
-  if (ctx && keys && n_segments && segments_share_one_key (keys, n_segments))
-    return awm_add_watermark_segments_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels);
-  AWM_ENTER (ctx);
-  g_add_segments_fused_in_use = 0;
-  if (!n_segments)
-    return 0;
-  std::vector<size_t> payload_index;
-  std::vector<unsigned char> coded;
-  size_t n_code = 0;
-  if (int rc = segments_check (ctx, "awm_add_watermark_segments_keys_d", keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels,
-                               payload_index, coded, n_code))
-    return rc;
-  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2;
-  for (size_t i = 0; i < n_segments && fused; i++)
-    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) & 15) || (reinterpret_cast<uintptr_t> (out_d[i]) & 15)))
-      fused = false;
-  if (!fused)
-    {
-      for (size_t i = 0; i < n_segments; i++)
-        if (n_frames[i])
-          if (int rc = add_segment_stream (ctx, keys + 16 * i, payload_hex[i], zero_frames[i], pcm_in_d[i], out_d[i], n_frames[i], n_channels))
-            return rc;
-      return 0;
-    }
-  SegmentKeys mk;
-  std::vector<size_t> segs, table_of;
-  std::vector<unsigned char> coded_tables;
-  segments_by_key_and_payload (n_segments, keys, n_frames, payload_index, coded, n_code, mk, segs, table_of, coded_tables);
-  g_add_segments_fused_in_use = 1;
-  if (segs.empty())
-    return 0;
-  return add_segments_fused (ctx, nullptr, segs, table_of, coded_tables, n_code, zero_frames, pcm_in_d, out_d, n_frames, &mk);
-}
-
-int
-awm_add_watermark_segments_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
-                                        const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
-{
-  if (sample_rate == Params::mark_sample_rate)
-    return awm_add_watermark_segments_keys_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels);
-  if (ctx && keys && n_segments && segments_share_one_key (keys, n_segments))
-    return awm_add_watermark_segments_rate_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, sample_rate);
-  AWM_ENTER (ctx);
-  g_add_segments_fused_in_use = 0;
-  const char *fn = "awm_add_watermark_segments_keys_rate_d";
-  awm_segment_plan probe;
-  if (awm_add_segment_plan (sample_rate, 0, 0, &probe))
-    {
-      set_error (sample_rate <= 0 ? string_printf ("%s: bad sample rate %d", fn, sample_rate)
-                                  : string_printf ("%s: no fixed-ratio resampler between %d Hz and %d Hz (zita's VResampler is not offered here)", fn,
-                                                   sample_rate, Params::mark_sample_rate));
-      return AWM_ERR_ARG;
-    }
-  if (!n_segments)
-    return 0;
-  std::vector<size_t> payload_index;
-  std::vector<unsigned char> coded;
-  size_t n_code = 0;
-  if (int rc = segments_check (ctx, fn, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, payload_index, coded, n_code))
-    return rc;
-  for (size_t i = 0; i < n_segments; i++)
-    if (awm_add_segment_plan (sample_rate, zero_frames[i], n_frames[i], &probe))
-      {
-        set_error (string_printf ("%s: zero_frames + n_frames of segment %zu is not below 2^40", fn, i));
-        return AWM_ERR_ARG;
-      }
-  const ResampleTable *down = ctx->get_resample_table (sample_rate, Params::mark_sample_rate);
-  const ResampleTable *up = ctx->get_resample_table (Params::mark_sample_rate, sample_rate);
-  if (!down || !up)
-    return AWM_ERR_HIP;
-  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2 && probe.limiter_block >= 8192
-               && segments_rate_fit_the_workspaces (n_segments, zero_frames, n_frames, n_channels, sample_rate);
-  for (size_t i = 0; i < n_segments && fused; i++)
-    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) & 15) || (reinterpret_cast<uintptr_t> (out_d[i]) & 15)))
-      fused = false;
-  if (!fused)
-    {
-      for (size_t i = 0; i < n_segments; i++)
-        if (n_frames[i])
-          if (int rc = add_segment_rate (ctx, *down, *up, keys + 16 * i, payload_hex[i], zero_frames[i], pcm_in_d[i], out_d[i], n_frames[i], n_channels, sample_rate))
-            return rc;
-      return 0;
-    }
-  SegmentKeys mk;
-  std::vector<size_t> segs, table_of;
-  std::vector<unsigned char> coded_tables;
-  segments_by_key_and_payload (n_segments, keys, n_frames, payload_index, coded, n_code, mk, segs, table_of, coded_tables);
-  g_add_segments_fused_in_use = 1;
-  if (segs.empty())
-    return 0;
-  return add_segments_rate_fused (ctx, *down, *up, nullptr, segs, table_of, coded_tables, n_code, zero_frames, pcm_in_d, out_d, n_frames, sample_rate, &mk);
-}
-
-/* ---- segments of signed 16-bit PCM: awm_add_watermark_segments_rate_s16_d / _keys_rate_s16_d (include/awm_hip.h).
- * One body for both (per_key: keys + 16 i is the key of segment i) and for every rate.  The fused paths above with T = int16_t take stereo
- * batches whose pointers are 4-byte aligned; everything else goes segment by segment through the definition itself: awm_pcm_decode_d into
- * ws_seg_in, the float path of one segment into ws_seg_out, awm_pcm_encode_d (direct16) into the caller's buffer. ---- */
-static int
-add_segments_s16 (awm_ctx *ctx, const char *fn, const uint8_t *keys, bool per_key, size_t n_segments, const char *const *payload_hex,
-                  const size_t *zero_frames, const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
-{
-  AWM_ENTER (ctx);
-  g_add_segments_fused_in_use = 0;
-  const bool at_rate = sample_rate != Params::mark_sample_rate;
-  awm_segment_plan probe {};
-  if (at_rate && awm_add_segment_plan (sample_rate, 0, 0, &probe))
-    {
-      set_error (sample_rate <= 0 ? string_printf ("%s: bad sample rate %d", fn, sample_rate)
-                                  : string_printf ("%s: no fixed-ratio resampler between %d Hz and %d Hz (zita's VResampler is not offered here)", fn,
-                                                   sample_rate, Params::mark_sample_rate));
-      return AWM_ERR_ARG;
-    }
-  if (!n_segments)
-    return 0;
-  std::vector<size_t> payload_index;
-  std::vector<unsigned char> coded;
-  size_t n_code = 0;
-  if (int rc = segments_check (ctx, fn, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, payload_index, coded, n_code))
-    return rc;
-  const ResampleTable *down = nullptr, *up = nullptr;
-  if (at_rate)
-    {
-      for (size_t i = 0; i < n_segments; i++)
-        if (awm_add_segment_plan (sample_rate, zero_frames[i], n_frames[i], &probe))
-          {
-            set_error (string_printf ("%s: zero_frames + n_frames of segment %zu is not below 2^40", fn, i));
-            return AWM_ERR_ARG;
-          }
-      down = ctx->get_resample_table (sample_rate, Params::mark_sample_rate);
-      up = ctx->get_resample_table (Params::mark_sample_rate, sample_rate);
-      if (!down || !up)
-        return AWM_ERR_HIP;
-    }
-  if (per_key && segments_share_one_key (keys, n_segments))      // one key for all segments IS the one-key call
-    per_key = false;
-  // the fused paths: stereo, a stereo frame one load or store; at a rate the floor of the batched limiter and windows that fit the workspaces
-  bool fused = g_add_batched && n_channels == 2 && n_segments >= 2;
-  if (at_rate)
-    fused = fused && probe.limiter_block >= 8192 && segments_rate_fit_the_workspaces (n_segments, zero_frames, n_frames, n_channels, sample_rate);
-  for (size_t i = 0; i < n_segments && fused; i++)
-    if (n_frames[i] && ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) | reinterpret_cast<uintptr_t> (out_d[i])) & 3))
-      fused = false;
-  if (!fused)
-    {
-      for (size_t i = 0; i < n_segments; i++)
-        if (n_frames[i])
-          {
-            const size_t n_values = n_frames[i] * size_t (n_channels);
-            if (int rc = ctx->ws_seg_in.reserve (n_values * sizeof (float))) return rc;
-            if (int rc = ctx->ws_seg_out.reserve (n_values * sizeof (float))) return rc;
-            float *f = ctx->ws_seg_in.as<float>(), *g = ctx->ws_seg_out.as<float>();
-            const uint8_t *key = per_key ? keys + 16 * i : keys;
-            if (int rc = awm_pcm_decode_d (ctx, pcm_in_d[i], n_values, 16, 0, 0, f)) return rc;
-            if (int rc = at_rate ? add_segment_rate (ctx, *down, *up, key, payload_hex[i], zero_frames[i], f, g, n_frames[i], n_channels, sample_rate)
-                                 : add_segment_stream (ctx, key, payload_hex[i], zero_frames[i], f, g, n_frames[i], n_channels))
-              return rc;
-            if (int rc = awm_pcm_encode_d (ctx, g, n_values, 16, 0, 0, 1, out_d[i])) return rc;
-          }
-      return 0;
-    }
-  SegmentKeys mk;
-  std::vector<size_t> segs, table_of;
-  std::vector<unsigned char> coded_tables;
-  if (per_key)
-    segments_by_key_and_payload (n_segments, keys, n_frames, payload_index, coded, n_code, mk, segs, table_of, coded_tables);
-  else
-    segments_by_payload (n_segments, n_frames, payload_index, segs, table_of);
-  g_add_segments_fused_in_use = 1;
-  if (segs.empty())
-    return 0;
-  const std::vector<unsigned char>& codes = per_key ? coded_tables : coded;
-  if (at_rate)
-    return add_segments_rate_fused (ctx, *down, *up, per_key ? nullptr : keys, segs, table_of, codes, n_code, zero_frames, pcm_in_d, out_d, n_frames,
-                                    sample_rate, per_key ? &mk : nullptr);
-  return add_segments_fused (ctx, per_key ? nullptr : keys, segs, table_of, codes, n_code, zero_frames, pcm_in_d, out_d, n_frames, per_key ? &mk : nullptr);
-}
-
-int
-awm_add_watermark_segments_rate_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
-                                       const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
-{
-  return add_segments_s16 (ctx, "awm_add_watermark_segments_rate_s16_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
-                           n_channels, sample_rate);
-}
-
-int
-awm_add_watermark_segments_keys_rate_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
-                                            const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
-{
-  return add_segments_s16 (ctx, "awm_add_watermark_segments_keys_rate_s16_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
-                           n_channels, sample_rate);
-}
-
-/* ---- segments with a SAMPLE RATE EACH: awm_add_watermark_segments_rates_d and its three twins (include/awm_hip.h).
- * One call, one upload, one chain of launches for a queue that is not sorted by rate.  The segments at another rate go through
- * add_segments_rate_fused's stages with the rate-dependent values -- the resamplers' tables and geometry, the limiter block -- in the
- * descriptors (kernels.hh RateResampleSlice ...), their batches are not split by rate; the segments at 44.1 kHz go through
- * add_segments_fused's stages as a sub-batch of the same call (no identity resampler: (1e-20f + x) - 1e-20f is not x for every float).
- * Both kinds read the same payload tables: K16p runs once per table group, K16t once per key, whatever the rates. ---- */
+/* ---- THE SEGMENT BATCHES, all ten entry points: one key or a key each, float or signed 16-bit PCM, one sample rate for the call or one
+ * per segment (include/awm_hip.h; DESIGN.md sections 9.2, 9.3, 9.6, 9.7, 9.8).  One body (add_segments_any) checks, decides between the
+ * fused path and segment by segment, and orders the segments by their tables; one fused function (add_segments_fused) plans, uploads and
+ * runs the batches of the two KINDS of segment:
+ *   at 44.1 kHz     K2 mixes in place; a segment that begins r = zero_frames % 1024 samples into a frame is staged (above)
+ *   the window kind at another rate: add_full_rate's stages on the window of each segment (SegmentWindow)
+ * A call with a rate per segment has both kinds (no identity resampler for 44.1 kHz: (1e-20f + x) - 1e-20f is not x for every float); its
+ * window kind carries the rate-dependent values -- the resamplers' tables and geometry, the limiter block -- in the descriptors
+ * (kernels.hh RateResampleSlice ...) and takes the `_rates` launchers, so its batches are not split by rate.  A call at one rate takes the
+ * one-rate descriptors and launchers.  Both kinds read the same payload tables: K16p runs once per table group, K16t once per key. ---- */
 static bool rates_all_equal (size_t n, const int *sample_rates);      // (with the `get` batches, below)
+
+constexpr size_t SEGMENTS_PER_LAUNCH = 4096;               // (blockIdx.y <= 65535; a launch of 4096 clips fills the device many times over)
+constexpr size_t SEGMENT_TABLE_GROUP = 1024;               // distinct payloads whose tables exist at a time (~370 MB at the default geometry)
 
 struct RateTables
 {
@@ -3736,16 +2985,100 @@ struct RateTables
   int limiter_block = 0;
 };
 
+/* the kernel arguments of a fused call: arrays one behind the other, each on a 16-byte boundary, in the context's page-locked block and
+ * in its twin on the device.  take() while the sizes are known and nothing else, reserve() once, host() / dev() of what was taken,
+ * upload() once: one copy per call */
 extern "C++" {
-template<class T> static int
-add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_tables, const uint8_t key[16], const std::vector<size_t>& segs,
-                          const std::vector<size_t>& payload_of, const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames,
-                          const T *const *pcm_in_d, T *const *out_d, const size_t *n_frames, const int *rates, SegmentKeys *mk = nullptr)
+template<class D> struct SegmentArgArray { size_t off; };
+struct SegmentArgs
+{
+  size_t bytes = 0;
+  char  *h = nullptr, *d = nullptr;
+
+  template<class D> SegmentArgArray<D>
+  take (size_t n)
+  {
+    const SegmentArgArray<D> a { bytes };
+    bytes = (bytes + n * sizeof (D) + 15) / 16 * 16;
+    return a;
+  }
+  template<class D> D *host (SegmentArgArray<D> a) const { return reinterpret_cast<D *> (h + a.off); }
+  template<class D> const D *dev (SegmentArgArray<D> a) const { return reinterpret_cast<const D *> (d + a.off); }
+  int
+  reserve (awm_ctx *ctx)
+  {
+    if (int rc = ctx->ws_add_batch.reserve (bytes)) return rc;
+    if (ctx->ev_add_batch)
+      AWM_HIP_CHECK (hipEventSynchronize (ctx->ev_add_batch));          // (an earlier batch's staging has been copied)
+    else
+      AWM_HIP_CHECK (hipEventCreateWithFlags (&ctx->ev_add_batch, hipEventDisableTiming));
+    if (int rc = ctx->pin_add_batch.reserve (bytes)) return rc;
+    h = ctx->pin_add_batch.as<char>();
+    d = ctx->ws_add_batch.as<char>();
+    return 0;
+  }
+  int
+  upload (awm_ctx *ctx, hipStream_t st)
+  {
+    AWM_HIP_CHECK (hipMemcpyAsync (d, h, bytes, hipMemcpyHostToDevice, st));
+    AWM_HIP_CHECK (hipEventRecord (ctx->ev_add_batch, st));
+    return 0;
+  }
+};
+} // extern "C++"
+
+/* the tables of one group into ws_keytab (K16p, no table is built on the host): n_tables of them from `coded` on, expanded from the one
+ * key's template or, with a key per segment, from the templates of their keys, which are built first where they are missing (K16t) */
+static int
+segment_table_group (awm_ctx *ctx, hipStream_t st, const FrameModTemplate *tmpl, SegmentKeys *mk, size_t first_table, size_t n_tables,
+                     const unsigned char *coded_dev, size_t n_code)
+{
+  const size_t block_frames = mark_block_frame_count(), table_stride = awmk::payload_table_stride (block_frames);
+  awmk::PayloadTableArgs pa {};
+  pa.n_payloads = int (n_tables);
+  pa.tmpl = mk ? ctx->ws_key_tmpl.as<short>() : tmpl->dev.as<short>();
+  if (mk)
+    {
+      if (int rc = mk->build (ctx, st, first_table + n_tables)) return rc;
+      pa.tmpl_of = mk->d_tmpl_of + first_table;
+      pa.tmpl_stride = (long long) table_stride;
+    }
+  pa.coded = coded_dev + first_table * 2 * n_code;
+  pa.tables = ctx->ws_keytab.as<signed char>();
+  pa.table_stride = (long long) table_stride;
+  pa.half_entries = int (block_frames * Params::n_bands);
+  pa.n_code = int (n_code);
+  ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (pa.n_payloads) * table_stride, st);          // the tables out, once
+  AWM_HIP_CHECK (awmk::launch_payload_tables (st, pa));
+  return 0;
+}
+
+/* the fused path (stereo): segs = the segments with samples, ordered by payload; payload_of[i] = index of segment i's payload among the
+ * distinct ones; coded = their codes, [distinct][2 (A, B)][n_code] bytes.  With a key per segment (mk; key is not used): ordered by (key,
+ * payload), and "payload" reads "(key, payload) pair" -- a table each, expanded from the template of its key.
+ * MIXED: rates[s] is the rate of segment s (a call with a rate per segment); else rates[0] is the rate of all of them.
+ * T = int16_t: segments of signed 16-bit PCM.
+ *   at 44.1 kHz     EVERY segment is staged, the r == 0 ones too -- the gather decodes on its way into ws_seg_in, K2 and the limiter's table
+ *                   run on the slices as for float --, and the scatter is the limiter's apply pass with a 16-bit sink: it reads the
+ *                   un-limited mix from ws_seg_out behind the r samples, scales, encodes and stores to out_d
+ *   the window kind the down-resampler reads the int16 segments, K2 and the up-resampler are as for float, the mix is computed twice and
+ *                   stored never -- once for the block maxima, once in the last pass, which scales by the limiter's ramp, encodes and
+ *                   stores int16 to out_d.  No workspace beyond ws_rate_a / b / c */
+extern "C++" {
+template<class T, bool MIXED> static int
+add_segments_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_tables, const uint8_t key[16], const std::vector<size_t>& segs,
+                    const std::vector<size_t>& payload_of, const std::vector<unsigned char>& coded, size_t n_code, const size_t *zero_frames,
+                    const T *const *pcm_in_d, T *const *out_d, const size_t *n_frames, const int *rates, SegmentKeys *mk)
 {
   constexpr bool S16 = std::is_same<T, int16_t>::value;
   typedef typename std::conditional<S16, awmk::LimitEncodeSegment, awmk::SegmentCopy>::type Scatter;
-  constexpr size_t PER_LAUNCH = 4096, TABLE_GROUP = 1024;  // as in add_segments_fused
-  constexpr size_t STAGE_MAX_FLOATS = size_t (1) << 28;
+  // the window kind's descriptors: those of the one-rate launchers, in a mixed call each with its rate's values behind it
+  typedef typename std::conditional<MIXED, awmk::RateResampleSlice, awmk::ResampleSlice>::type WSlice;
+  typedef typename std::conditional<MIXED, awmk::RateMixSegment, awmk::MixSegment>::type WMix;
+  typedef typename std::conditional<MIXED, awmk::RateLimiterClip, awmk::LimiterClip>::type WLim;
+  typedef typename std::conditional<MIXED, awmk::RateLimitEncodeSegment, awmk::LimitEncodeSegment>::type WEnc;
+  constexpr size_t PER_LAUNCH = SEGMENTS_PER_LAUNCH, TABLE_GROUP = SEGMENT_TABLE_GROUP;
+  constexpr size_t STAGE_MAX_FLOATS = size_t (1) << 28;    // staged samples per batch and direction (1 GiB): a batch that would need more is split
   const int C = 2;
   const size_t FRAME = Params::frame_size, n_distinct = coded.size() / (2 * n_code);
   const int use_limiter = !params().test_no_limiter;
@@ -3758,30 +3091,33 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
     return AWM_ERR_HIP;
 
   // the two kinds, each in the order of the tables
+  auto rate_of = [&] (size_t s) { return rates[MIXED ? s : 0]; };
   std::vector<size_t> at_rate, at_44;
   for (size_t i = 0; i < segs.size(); i++)
-    (rates[segs[i]] == Params::mark_sample_rate ? at_44 : at_rate).push_back (i);
+    (rate_of (segs[i]) == Params::mark_sample_rate ? at_44 : at_rate).push_back (i);
   const size_t nr = at_rate.size(), nf = at_44.size();
   auto group_of = [&] (size_t i) { return payload_of[i] / TABLE_GROUP; };
-  size_t max_total = 0, tab_total = 0;
+  size_t max_total = 0, tab_total = 0;                     // block maxima and ramp table entries: the window kind's first, then 44.1 kHz
 
-  // at another rate: the windows and the batches as in add_segments_rate_fused; a down slice is shared by the segments of a batch that
-  // agree in input, length, offset and rate
+  // the window kind: the window of every segment and the batches: consecutive segments (in table order) of one table group, at most
+  // PER_LAUNCH of them, none of the three workspaces beyond WS_MAX_FLOATS.  Segments of a batch that agree in input, length, offset and
+  // rate share one down-resampled slice
   struct RSeg { SegmentWindow w; const RateTables *t; size_t down, x44_off, wm44_off, wm_off, max_off, tab_off; };
   struct RBatch { size_t i0, i1, d0, d1, x44_floats, wm44_floats, wm_floats, max_n44, max_out, max_tab, max_len; long long frames1024; int min_block; };
   std::vector<RSeg> rgeo (nr);
   std::vector<RBatch> rbatches;
-  std::vector<size_t> down_owner;
+  std::vector<size_t> down_owner;                          // segment (of this kind) whose window a down slice is made for
   std::map<std::tuple<const T *, size_t, size_t, int>, size_t> shared;
   for (size_t k = 0; k < nr; k++)
     {
       RSeg& g = rgeo[k];
       const size_t i = at_rate[k], s = segs[i];
-      g.t = &rate_tables.at (rates[s]);
-      if (int rc = segment_window (rates[s], zero_frames[s], n_frames[s], g.w))
+      g.t = MIXED ? &rate_tables.at (rate_of (s)) : &rate_tables.begin()->second;
+      if (int rc = segment_window (rate_of (s), zero_frames[s], n_frames[s], g.w))
         return rc;
+      // (a segment that alone exceeds a workspace never gets here: segments_rate_fit_the_workspaces)
       const size_t n44_floats = g.w.slice_frames * FRAME * C, wm_floats = ((g.w.pre + g.w.n) * C + 3) / 4 * 4;
-      const auto id = std::make_tuple (pcm_in_d[s], n_frames[s], zero_frames[s], rates[s]);
+      const auto id = std::make_tuple (pcm_in_d[s], n_frames[s], zero_frames[s], rate_of (s));
       bool fresh = rbatches.empty() || k - rbatches.back().i0 >= PER_LAUNCH || group_of (i) != group_of (at_rate[rbatches.back().i0]);
       if (!fresh)
         {
@@ -3834,7 +3170,8 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
   const int L_rate = frames_per_span (ctx, frames_max);
   const size_t n_down = down_owner.size();
 
-  // at 44.1 kHz: the geometry and the batches as in add_segments_fused
+  // at 44.1 kHz: the geometry of every segment and the batches: consecutive segments (in table order) of one table group, at most
+  // PER_LAUNCH of them, no more than STAGE_MAX_FLOATS staged
   struct FSeg { size_t r, skipped, len, first_block, n_blocks, n_tab, max_off, tab_off, stage_off; };
   struct FBatch { size_t i0, i1, g0, g1, stage_floats, max_len, max_tab; };
   std::vector<FSeg> fgeo (nf);
@@ -3847,7 +3184,7 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
       FSeg& g = fgeo[k];
       g.r = zf % FRAME;
       g.skipped = zf - g.r;
-      g.len = g.r + n_frames[segs[i]];
+      g.len = g.r + n_frames[segs[i]];                     // the stream behind the whole frames of zeros: r zeros, then the segment
       g.first_block = g.skipped / LIMITER_BLOCK;
       g.n_blocks = (g.skipped + g.len) / LIMITER_BLOCK + 2 - g.first_block;
       g.n_tab = awmk::limiter_tab_entries ((long long) g.len, (long long) g.skipped, LIMITER_BLOCK);
@@ -3873,17 +3210,22 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
     }
   const int L_44 = frames_per_span (ctx, total_frames1024);
 
-  // one page-locked block, one upload: the kernel arguments of every stage of both kinds and the payloads' codes
-  const size_t off_rmix = n_down * sizeof (awmk::RateResampleSlice), off_up = off_rmix + nr * sizeof (awmk::AddMixArgs),
-               off_mm = off_up + nr * sizeof (awmk::RateResampleSlice), off_rlim = off_mm + nr * sizeof (awmk::RateMixSegment),
-               off_enc = off_rlim + nr * sizeof (awmk::RateLimiterClip),
-               off_fmix = off_enc + (S16 ? nr * sizeof (awmk::RateLimitEncodeSegment) : 0), off_flim = off_fmix + nf * sizeof (awmk::AddMixArgs),
-               off_gather = off_flim + nf * sizeof (awmk::LimiterClip), off_scatter = off_gather + n_staged * sizeof (awmk::SegmentCopy),
-               off_coded = off_scatter + n_staged * sizeof (Scatter), off_keys = (off_coded + coded.size() + 15) / 16 * 16;
+  // one page-locked block, one upload: the kernel arguments of every stage of both kinds, the gather / scatter lists of the staged
+  // segments, the payloads' codes and what the keys' templates are built from
+  SegmentArgs args;
+  const auto a_down = args.take<WSlice> (n_down), a_up = args.take<WSlice> (nr);
+  const auto a_rmix = args.take<awmk::AddMixArgs> (nr);
+  const auto a_mm = args.take<WMix> (nr);
+  const auto a_rlim = args.take<WLim> (nr);
+  const auto a_enc = args.take<WEnc> (S16 ? nr : 0);
+  const auto a_fmix = args.take<awmk::AddMixArgs> (nf);
+  const auto a_flim = args.take<awmk::LimiterClip> (nf);
+  const auto a_gather = args.take<awmk::SegmentCopy> (n_staged);
+  const auto a_scatter = args.take<Scatter> (n_staged);
+  const auto a_coded = args.take<unsigned char> (coded.size());
   if (mk)
     if (int rc = mk->reserve (ctx, table_stride)) return rc;
-  const size_t arg_bytes = mk ? off_keys + mk->arg_bytes() : off_coded + coded.size();
-  if (int rc = ctx->ws_add_batch.reserve (arg_bytes)) return rc;
+  const auto a_keys = args.take<char> (mk ? mk->arg_bytes() : 0);
   if (int rc = ctx->ws_keytab.reserve (std::min (n_distinct, TABLE_GROUP) * table_stride)) return rc;
   if (nr)
     {
@@ -3901,42 +3243,47 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
       if (int rc = ctx->ws_seg_in.reserve (stage_max * sizeof (float))) return rc;
       if (int rc = ctx->ws_seg_out.reserve (stage_max * sizeof (float))) return rc;
     }
-  if (ctx->ev_add_batch)
-    AWM_HIP_CHECK (hipEventSynchronize (ctx->ev_add_batch));            // (an earlier batch's staging has been copied)
-  else
-    AWM_HIP_CHECK (hipEventCreateWithFlags (&ctx->ev_add_batch, hipEventDisableTiming));
-  if (int rc = ctx->pin_add_batch.reserve (arg_bytes)) return rc;
-  char *h = ctx->pin_add_batch.as<char>(), *d = ctx->ws_add_batch.as<char>();
-  auto *h_down = reinterpret_cast<awmk::RateResampleSlice *> (h), *h_up = reinterpret_cast<awmk::RateResampleSlice *> (h + off_up);
-  auto *h_rmix = reinterpret_cast<awmk::AddMixArgs *> (h + off_rmix);
-  auto *h_mm = reinterpret_cast<awmk::RateMixSegment *> (h + off_mm);
-  auto *h_rlim = reinterpret_cast<awmk::RateLimiterClip *> (h + off_rlim);
-  auto *h_enc = reinterpret_cast<awmk::RateLimitEncodeSegment *> (h + off_enc);             // (16-bit only)
-  auto *h_fmix = reinterpret_cast<awmk::AddMixArgs *> (h + off_fmix);
-  auto *h_flim = reinterpret_cast<awmk::LimiterClip *> (h + off_flim);
-  auto *h_gather = reinterpret_cast<awmk::SegmentCopy *> (h + off_gather);
-  auto *h_scatter = reinterpret_cast<Scatter *> (h + off_scatter);
-  const auto *d_down = reinterpret_cast<const awmk::RateResampleSlice *> (d), *d_up = reinterpret_cast<const awmk::RateResampleSlice *> (d + off_up);
-  const auto *d_rmix = reinterpret_cast<const awmk::AddMixArgs *> (d + off_rmix);
-  const auto *d_mm = reinterpret_cast<const awmk::RateMixSegment *> (d + off_mm);
-  const auto *d_rlim = reinterpret_cast<const awmk::RateLimiterClip *> (d + off_rlim);
-  const auto *d_enc = reinterpret_cast<const awmk::RateLimitEncodeSegment *> (d + off_enc);
-  const auto *d_fmix = reinterpret_cast<const awmk::AddMixArgs *> (d + off_fmix);
-  const auto *d_flim = reinterpret_cast<const awmk::LimiterClip *> (d + off_flim);
-  const auto *d_gather = reinterpret_cast<const awmk::SegmentCopy *> (d + off_gather);
-  const auto *d_scatter = reinterpret_cast<const Scatter *> (d + off_scatter);
-  const unsigned char *d_coded = reinterpret_cast<const unsigned char *> (d + off_coded);
-  std::memcpy (h + off_coded, coded.data(), coded.size());
+  if (int rc = args.reserve (ctx)) return rc;
+  WSlice *h_down = args.host (a_down), *h_up = args.host (a_up);
+  const WSlice *d_down = args.dev (a_down), *d_up = args.dev (a_up);
+  const awmk::AddMixArgs *d_rmix = args.dev (a_rmix), *d_fmix = args.dev (a_fmix);
+  const WMix *d_mm = args.dev (a_mm);
+  const WLim *d_rlim = args.dev (a_rlim);
+  const WEnc *d_enc = args.dev (a_enc);
+  const awmk::LimiterClip *d_flim = args.dev (a_flim);
+  const awmk::SegmentCopy *d_gather = args.dev (a_gather);
+  const Scatter *d_scatter = args.dev (a_scatter);
+  std::memcpy (args.host (a_coded), coded.data(), coded.size());
   if (mk)
-    mk->fill (h + off_keys, d + off_keys);
+    mk->fill (args.host (a_keys), args.dev (a_keys));
   float *x44 = ctx->ws_rate_a.as<float>(), *wm44 = ctx->ws_rate_b.as<float>(), *wm = ctx->ws_rate_c.as<float>();
   float *block_max = ctx->ws_block_max.as<float>();
   float2 *tabs = ctx->ws_limit_tab.as<float2>();
   auto table_of = [&] (size_t i) { return ctx->ws_keytab.as<int8_t>() + (payload_of[i] % TABLE_GROUP) * table_stride; };
-  auto rate_slice = [&] (const awmk::ResampleSlice& s, const ResampleTable& t) {
-    awmk::RateResampleSlice r { s, t.ctab.as<float>(), t.hl, t.np, t.step, 0, 0 };
-    awmk::resample_slice_geometry (r, C, true);
-    return r;
+
+  // the window kind's arguments.  A mixed call's slice has its resampler's table and the launch geometry at that rate behind it, its
+  // other descriptors the limiter block of their rate
+  auto rate_slice = [&] (const awmk::ResampleSlice& s, const ResampleTable& t) -> WSlice {
+    if constexpr (MIXED)
+      {
+        awmk::RateResampleSlice r { s, t.ctab.as<float>(), t.hl, t.np, t.step, 0, 0 };
+        awmk::resample_slice_geometry (r, C, true);
+        return r;
+      }
+    else
+      return s;
+  };
+  auto slice_of = [] (const WSlice& r) -> const awmk::ResampleSlice& {
+    if constexpr (MIXED)
+      return r.s;
+    else
+      return r;
+  };
+  auto at_block = [] (auto& slot, const auto& descriptor, int lim_block) {
+    if constexpr (MIXED)
+      slot = { descriptor, lim_block };
+    else
+      slot = descriptor;
   };
   for (size_t q = 0; q < n_down; q++)
     {
@@ -3948,20 +3295,26 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
       const RSeg& g = rgeo[k];
       const size_t i = at_rate[k], s = segs[i];
       const int lim_block = g.t->limiter_block;
-      h_rmix[k] = window_mix_args (g.w, x44 + g.x44_off, wm44 + g.wm44_off, C, table_of (i), params().water_delta, L_rate);
+      args.host (a_rmix)[k] = window_mix_args (g.w, x44 + g.x44_off, wm44 + g.wm44_off, C, table_of (i), params().water_delta, L_rate);
       h_up[k] = rate_slice (window_up_slice (g.w, wm44 + g.wm44_off, C, wm + g.wm_off), *g.t->up);
       float *mix_out = nullptr;                                   // (16-bit: no mix is stored; `orig` holds the address of the int16 values)
       if constexpr (!S16)
         mix_out = out_d[s];
-      h_mm[k] = { { reinterpret_cast<const float *> (pcm_in_d[s]), wm + g.wm_off, mix_out, (long long) g.w.n, (long long) g.w.pre, (long long) g.w.Z,
-                    use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr, (long long) g.w.p.first_block,
-                    (long long) g.w.p.n_blocks }, lim_block };
-      h_rlim[k] = { { mix_out, (long long) g.w.n, use_limiter ? block_max + g.max_off : nullptr, (long long) g.w.p.n_blocks,
-                      use_limiter ? tabs + g.tab_off : nullptr, (long long) g.w.n_tab, (long long) g.w.Z, (long long) g.w.p.first_block }, lim_block };
+      const awmk::MixSegment mm { reinterpret_cast<const float *> (pcm_in_d[s]), wm + g.wm_off, mix_out, (long long) g.w.n, (long long) g.w.pre,
+                                  (long long) g.w.Z, use_limiter ? reinterpret_cast<unsigned int *> (block_max + g.max_off) : nullptr,
+                                  (long long) g.w.p.first_block, (long long) g.w.p.n_blocks };
+      const awmk::LimiterClip lim { mix_out, (long long) g.w.n, use_limiter ? block_max + g.max_off : nullptr, (long long) g.w.p.n_blocks,
+                                    use_limiter ? tabs + g.tab_off : nullptr, (long long) g.w.n_tab, (long long) g.w.Z, (long long) g.w.p.first_block };
+      at_block (args.host (a_mm)[k], mm, lim_block);
+      at_block (args.host (a_rlim)[k], lim, lim_block);
       if constexpr (S16)
-        h_enc[k] = { { pcm_in_d[s], wm + g.wm_off + g.w.pre * C, out_d[s], (long long) g.w.n, (long long) g.w.Z,
-                       use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.w.Z / size_t (lim_block)) }, lim_block };
+        {
+          const awmk::LimitEncodeSegment enc { pcm_in_d[s], wm + g.wm_off + g.w.pre * C, out_d[s], (long long) g.w.n, (long long) g.w.Z,
+                                               use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.w.Z / size_t (lim_block)) };
+          at_block (args.host (a_enc)[k], enc, lim_block);
+        }
     }
+  // the arguments at 44.1 kHz
   std::vector<long long> spans (nf);
   size_t staged = 0;
   for (size_t k = 0; k < nf; k++)
@@ -3988,51 +3341,60 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
       a.first_block = (long long) g.first_block;
       a.n_blocks = (long long) g.n_blocks;
       a.frames_per_span = L_44;
-      h_fmix[k] = a;
-      h_flim[k] = { out, (long long) g.len, block_max + g.max_off, (long long) g.n_blocks, tabs + g.tab_off, (long long) g.n_tab,
-                    (long long) g.skipped, (long long) g.first_block };
+      args.host (a_fmix)[k] = a;
+      args.host (a_flim)[k] = { out, (long long) g.len, block_max + g.max_off, (long long) g.n_blocks, tabs + g.tab_off, (long long) g.n_tab,
+                                (long long) g.skipped, (long long) g.first_block };
       spans[k] = ((long long) ((g.len + FRAME - 1) / FRAME) + L_44 - 1) / L_44;
       if (g.r || S16)
         {
-          h_gather[staged] = { reinterpret_cast<const float *> (pcm_in_d[s]), ctx->ws_seg_in.as<float>() + g.stage_off, (long long) (n_frames[s] * 2),
-                               (long long) (g.r * 2) };
+          // (16-bit: `src` holds the address of the int16 values, launch_segment_gather_s16)
+          args.host (a_gather)[staged] = { reinterpret_cast<const float *> (pcm_in_d[s]), ctx->ws_seg_in.as<float>() + g.stage_off,
+                                           (long long) (n_frames[s] * 2), (long long) (g.r * 2) };
           if constexpr (S16)
-            h_scatter[staged] = { nullptr, out + g.r * 2, out_d[s], (long long) n_frames[s], (long long) zero_frames[s],
-                                  use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.skipped / LIMITER_BLOCK) };
+            args.host (a_scatter)[staged] = { nullptr, out + g.r * 2, out_d[s], (long long) n_frames[s], (long long) zero_frames[s],
+                                              use_limiter ? tabs + g.tab_off : nullptr, (long long) (g.skipped / LIMITER_BLOCK) };
           else
-            h_scatter[staged] = { out + g.r * 2, out_d[s], (long long) (n_frames[s] * 2), 0 };
+            args.host (a_scatter)[staged] = { out + g.r * 2, out_d[s], (long long) (n_frames[s] * 2), 0 };
           staged++;
         }
     }
-  AWM_HIP_CHECK (hipMemcpyAsync (d, h, arg_bytes, hipMemcpyHostToDevice, st));
-  AWM_HIP_CHECK (hipEventRecord (ctx->ev_add_batch, st));
+  if (int rc = args.upload (ctx, st)) return rc;
 
   unsigned int ceiling_bits;
   std::memcpy (&ceiling_bits, &LIMITER_CEILING, sizeof (ceiling_bits));
+  // one batch of the window kind: down, block maxima preset, K2 for the watermark alone, up, mix + maxima, limiter.  The `_rates`
+  // launchers read the tables and the limiter block from the descriptors and check min_block; the one-rate launchers are given them
   auto run_rate_batch = [&] (const RBatch& b) -> int {
     const size_t nb = b.i1 - b.i0;
     double down_values = 0, up_values = 0, n44_values = 0, out_values = 0;
     long long max_spans = 0;
-    size_t lds_down = 0, lds_up = 0;
+    size_t lds_down = 0, lds_up = 0;                       // (MIXED only)
     for (size_t q = b.d0; q < b.d1; q++)
       {
-        down_values += double (h_down[q].s.n_in + h_down[q].s.n_out) * C;
-        lds_down = std::max (lds_down, awmk::resample_slice_lds_bytes (h_down[q]));
+        down_values += double (slice_of (h_down[q]).n_in + slice_of (h_down[q]).n_out) * C;
+        if constexpr (MIXED)
+          lds_down = std::max (lds_down, awmk::resample_slice_lds_bytes (h_down[q]));
       }
     for (size_t k = b.i0; k < b.i1; k++)
       {
-        up_values += double (h_up[k].s.n_in + h_up[k].s.n_out) * C;
-        lds_up = std::max (lds_up, awmk::resample_slice_lds_bytes (h_up[k]));
+        up_values += double (slice_of (h_up[k]).n_in + slice_of (h_up[k]).n_out) * C;
+        if constexpr (MIXED)
+          lds_up = std::max (lds_up, awmk::resample_slice_lds_bytes (h_up[k]));
         n44_values += double (rgeo[k].w.slice_frames * FRAME) * C;
         out_values += double (rgeo[k].w.n) * C;
         max_spans = std::max (max_spans, ((long long) rgeo[k].w.slice_frames + L_rate - 1) / L_rate);
       }
+    const RateTables& t = *rgeo[b.i0].t;                   // (!MIXED: the call's one rate)
     {
       ProfScope ps (ctx, PROF_RESAMPLE, down_values * 4.0, st);                     // every input and output sample once
-      if constexpr (S16)
+      if constexpr (MIXED && S16)
         AWM_HIP_CHECK (awmk::launch_resample_slices_rates_s16 (st, d_down + b.d0, int (b.d1 - b.d0), C, (long long) b.max_n44, true, lds_down));
-      else
+      else if constexpr (MIXED)
         AWM_HIP_CHECK (awmk::launch_resample_slices_rates (st, d_down + b.d0, int (b.d1 - b.d0), C, (long long) b.max_n44, true, lds_down));
+      else if constexpr (S16)
+        AWM_HIP_CHECK (awmk::launch_resample_slices_s16 (st, resample_table_args (*t.down, C), d_down + b.d0, int (b.d1 - b.d0), (long long) b.max_n44, true));
+      else
+        AWM_HIP_CHECK (awmk::launch_resample_slices (st, resample_table_args (*t.down, C), d_down + b.d0, int (b.d1 - b.d0), (long long) b.max_n44, true));
     }
     if (use_limiter)
       {
@@ -4045,31 +3407,54 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
     }
     {
       ProfScope ps (ctx, PROF_RESAMPLE, up_values * 4.0, st);
-      AWM_HIP_CHECK (awmk::launch_resample_slices_rates (st, d_up + b.i0, int (nb), C, (long long) b.max_out, true, lds_up));
+      if constexpr (MIXED)
+        AWM_HIP_CHECK (awmk::launch_resample_slices_rates (st, d_up + b.i0, int (nb), C, (long long) b.max_out, true, lds_up));
+      else
+        AWM_HIP_CHECK (awmk::launch_resample_slices (st, resample_table_args (*t.up, C), d_up + b.i0, int (nb), (long long) b.max_out, true));
     }
     if constexpr (S16)
       {
         // the block maxima from the mix, the ramp tables, then the mix again: limited, encoded and stored as int16
         if (use_limiter)
           {
-            AWM_HIP_CHECK (awmk::launch_max_segments_rates_s16 (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, b.min_block));
-            AWM_HIP_CHECK (awmk::launch_limiter_table_batch_rates (st, d_rlim + b.i0, int (nb), LIMITER_CEILING, (long long) b.max_tab));
+            if constexpr (MIXED)
+              {
+                AWM_HIP_CHECK (awmk::launch_max_segments_rates_s16 (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, b.min_block));
+                AWM_HIP_CHECK (awmk::launch_limiter_table_batch_rates (st, d_rlim + b.i0, int (nb), LIMITER_CEILING, (long long) b.max_tab));
+              }
+            else
+              {
+                AWM_HIP_CHECK (awmk::launch_max_segments_s16 (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, t.limiter_block));
+                AWM_HIP_CHECK (awmk::launch_limiter_table_batch (st, d_rlim + b.i0, int (nb), (long long) b.max_len, t.limiter_block, LIMITER_CEILING,
+                                                                 (long long) b.max_tab));
+              }
           }
         ProfScope ps (ctx, PROF_LIMIT_ENCODE_S16, out_values * 8.0, st);            // int16 and float in, int16 out
-        AWM_HIP_CHECK (awmk::launch_limit_encode_segments_rates (st, d_enc + b.i0, int (nb), (long long) b.max_len, true, b.min_block));
+        if constexpr (MIXED)
+          AWM_HIP_CHECK (awmk::launch_limit_encode_segments_rates (st, d_enc + b.i0, int (nb), (long long) b.max_len, true, b.min_block));
+        else
+          AWM_HIP_CHECK (awmk::launch_limit_encode_segments (st, d_enc + b.i0, int (nb), (long long) b.max_len, true, t.limiter_block));
       }
     else
       {
-        AWM_HIP_CHECK (awmk::launch_mix_max_segments_rates (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, b.min_block));
+        if constexpr (MIXED)
+          AWM_HIP_CHECK (awmk::launch_mix_max_segments_rates (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, b.min_block));
+        else
+          AWM_HIP_CHECK (awmk::launch_mix_max_segments (st, d_mm + b.i0, int (nb), (long long) b.max_out, C, t.limiter_block));
         if (use_limiter)
           {
             ProfScope ps (ctx, PROF_LIMITER, out_values * 8.0, st);
-            AWM_HIP_CHECK (awmk::launch_limiter_batch_rates (st, d_rlim + b.i0, int (nb), (long long) b.max_len, C, b.min_block, LIMITER_CEILING,
-                                                             (long long) b.max_tab));
+            if constexpr (MIXED)
+              AWM_HIP_CHECK (awmk::launch_limiter_batch_rates (st, d_rlim + b.i0, int (nb), (long long) b.max_len, C, b.min_block, LIMITER_CEILING,
+                                                               (long long) b.max_tab));
+            else
+              AWM_HIP_CHECK (awmk::launch_limiter_batch (st, d_rlim + b.i0, int (nb), (long long) b.max_len, C, t.limiter_block, LIMITER_CEILING,
+                                                         (long long) b.max_tab));
           }
       }
     return 0;
   };
+  // one batch at 44.1 kHz: gather, block maxima preset, K2, limiter (16-bit: its tables, then limit + encode), scatter
   auto run_44_batch = [&] (const FBatch& b) -> int {
     const size_t nb = b.i1 - b.i0;
     long long max_spans = 0;
@@ -4097,6 +3482,7 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
     }
     if constexpr (S16)
       {
+        // the ramp tables alone, then limit + encode from the staged mix to the caller's buffers
         if (use_limiter)
           AWM_HIP_CHECK (awmk::launch_limiter_table_batch (st, d_flim + b.i0, int (nb), (long long) b.max_len, LIMITER_BLOCK, LIMITER_CEILING, (long long) b.max_tab));
         ProfScope ps (ctx, PROF_LIMIT_ENCODE_S16, values * 6.0, st);               // float in, int16 out
@@ -4115,7 +3501,7 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
     return 0;
   };
 
-  // table group by table group: its tables once, then its batches at another rate, then its batches at 44.1 kHz
+  // table group by table group: its tables once, then its batches of the window kind, then its batches at 44.1 kHz
   size_t rb = 0, fb = 0, group_built = size_t (-1);
   while (rb < rbatches.size() || fb < fbatches.size())
     {
@@ -4124,22 +3510,9 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
       const size_t group = std::min (gr, gf);
       if (group != group_built)
         {
-          awmk::PayloadTableArgs pa {};
-          pa.n_payloads = int (std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP));
-          pa.tmpl = mk ? ctx->ws_key_tmpl.as<short>() : tmpl->dev.as<short>();
-          if (mk)
-            {
-              if (int rc = mk->build (ctx, st, group * TABLE_GROUP + size_t (pa.n_payloads))) return rc;
-              pa.tmpl_of = mk->d_tmpl_of + group * TABLE_GROUP;
-              pa.tmpl_stride = (long long) table_stride;
-            }
-          pa.coded = d_coded + group * TABLE_GROUP * 2 * n_code;
-          pa.tables = ctx->ws_keytab.as<signed char>();
-          pa.table_stride = (long long) table_stride;
-          pa.half_entries = int (block_frames * Params::n_bands);
-          pa.n_code = int (n_code);
-          ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (pa.n_payloads) * table_stride, st);          // the tables out, once
-          AWM_HIP_CHECK (awmk::launch_payload_tables (st, pa));
+          if (int rc = segment_table_group (ctx, st, tmpl, mk, group * TABLE_GROUP, std::min (TABLE_GROUP, n_distinct - group * TABLE_GROUP),
+                                            args.dev (a_coded), n_code))
+            return rc;
           group_built = group;
         }
       if (int rc = gr == group ? run_rate_batch (rbatches[rb++]) : run_44_batch (fbatches[fb++]))
@@ -4148,37 +3521,49 @@ add_segments_rates_fused (awm_ctx *ctx, const std::map<int, RateTables>& rate_ta
   return 0;
 }
 
-/* the four entry points' body: T = float or int16_t, per_key: keys + 16 i is the key of segment i */
+/* the ten entry points' body.  T = float or int16_t; per_key: keys + 16 i is the key of segment i, else keys is the one key;
+ * per_segment: rates[i] is the rate of segment i, else rates[0] is the rate of the call.  What cannot take the fused path -- not stereo,
+ * one segment, a pointer off the grid (16 bytes; 16-bit: a stereo frame), a limiter block below the batched limiter's floor, a window
+ * beyond a workspace -- goes segment by segment, each at its rate; 16-bit through the definition itself: awm_pcm_decode_d into ws_seg_in,
+ * the float path of one segment into ws_seg_out, awm_pcm_encode_d (direct16) into the caller's buffer */
 template<class T> static int
-add_segments_rates (awm_ctx *ctx, const char *fn, const uint8_t *keys, bool per_key, size_t n_segments, const char *const *payload_hex,
-                    const size_t *zero_frames, const T *const *pcm_in_d, T *const *out_d, const size_t *n_frames, int n_channels, const int *sample_rates)
+add_segments_any (awm_ctx *ctx, const char *fn, const uint8_t *keys, bool per_key, size_t n_segments, const char *const *payload_hex,
+                  const size_t *zero_frames, const T *const *pcm_in_d, T *const *out_d, const size_t *n_frames, int n_channels, const int *rates,
+                  bool per_segment)
 {
   constexpr bool S16 = std::is_same<T, int16_t>::value;
   AWM_ENTER (ctx);
   g_add_segments_fused_in_use = 0;
-  if (!n_segments)
-    return 0;
-  if (!sample_rates)
+  if (per_segment)
     {
-      set_error (string_printf ("%s: sample_rates is null", fn));
-      return AWM_ERR_ARG;
+      if (!n_segments)
+        return 0;
+      if (!rates)
+        {
+          set_error (string_printf ("%s: sample_rates is null", fn));
+          return AWM_ERR_ARG;
+        }
     }
+  auto rate_of = [&] (size_t i) { return rates[per_segment ? i : 0]; };
   std::map<int, RateTables> rate_tables;                     // the rates other than 44.1 kHz
-  for (size_t i = 0; i < n_segments; i++)
+  for (size_t i = 0; i < (per_segment ? n_segments : 1); i++)
     {
-      const int rate = sample_rates[i];
+      const int rate = rate_of (i);
       awm_segment_plan probe;
       if (rate == Params::mark_sample_rate || rate_tables.count (rate))
         continue;
       if (awm_add_segment_plan (rate, 0, 0, &probe))
         {
-          set_error (rate <= 0 ? string_printf ("%s: bad sample rate %d at index %zu", fn, rate, i)
-                               : string_printf ("%s: no fixed-ratio resampler between %d Hz and %d Hz at index %zu (zita's VResampler is not offered here)",
-                                                fn, rate, Params::mark_sample_rate, i));
+          const std::string at = per_segment ? string_printf (" at index %zu", i) : std::string();
+          set_error (rate <= 0 ? string_printf ("%s: bad sample rate %d%s", fn, rate, at.c_str())
+                               : string_printf ("%s: no fixed-ratio resampler between %d Hz and %d Hz%s (zita's VResampler is not offered here)",
+                                                fn, rate, Params::mark_sample_rate, at.c_str()));
           return AWM_ERR_ARG;
         }
       rate_tables[rate].limiter_block = int (probe.limiter_block);
     }
+  if (!n_segments)
+    return 0;
   std::vector<size_t> payload_index;
   std::vector<unsigned char> coded;
   size_t n_code = 0;
@@ -4187,7 +3572,7 @@ add_segments_rates (awm_ctx *ctx, const char *fn, const uint8_t *keys, bool per_
   for (size_t i = 0; i < n_segments; i++)
     {
       awm_segment_plan probe;
-      if (sample_rates[i] != Params::mark_sample_rate && awm_add_segment_plan (sample_rates[i], zero_frames[i], n_frames[i], &probe))
+      if (rate_of (i) != Params::mark_sample_rate && awm_add_segment_plan (rate_of (i), zero_frames[i], n_frames[i], &probe))
         {
           set_error (string_printf ("%s: zero_frames + n_frames of segment %zu is not below 2^40", fn, i));
           return AWM_ERR_ARG;
@@ -4202,8 +3587,8 @@ add_segments_rates (awm_ctx *ctx, const char *fn, const uint8_t *keys, bool per_
     }
   if (per_key && segments_share_one_key (keys, n_segments))      // one key for all segments IS the one-key call
     per_key = false;
-  // the fused path: stereo, the pointers aligned as the one-rate fused paths need them, at every other rate the floor of the batched
-  // limiter and windows that fit the workspaces
+  // the fused path: stereo, the pointers on the grid, at every other rate the floor of the batched limiter (blocks of at least four of
+  // its runs: launch_limiter_batch) and windows that fit the workspaces
   bool fused = g_add_batched && n_channels == 2 && n_segments >= 2;
   for (const auto& rt : rate_tables)
     fused = fused && rt.second.limiter_block >= 8192;
@@ -4212,25 +3597,24 @@ add_segments_rates (awm_ctx *ctx, const char *fn, const uint8_t *keys, bool per_
       {
         if ((reinterpret_cast<uintptr_t> (pcm_in_d[i]) | reinterpret_cast<uintptr_t> (out_d[i])) & (S16 ? 3 : 15))
           fused = false;
-        else if (sample_rates[i] != Params::mark_sample_rate)
-          fused = segments_rate_fit_the_workspaces (1, zero_frames + i, n_frames + i, n_channels, sample_rates[i]);
+        else if (rate_of (i) != Params::mark_sample_rate)
+          fused = segments_rate_fit_the_workspaces (1, zero_frames + i, n_frames + i, n_channels, rate_of (i));
       }
   if (!fused)
     {
-      // segment by segment through the one-rate paths of one segment, each at its rate
+      const RateTables *one_rate = rate_tables.empty() ? nullptr : &rate_tables.begin()->second;
       for (size_t i = 0; i < n_segments; i++)
         if (n_frames[i])
           {
             const uint8_t *key = per_key ? keys + 16 * i : keys;
-            const int rate = sample_rates[i];
-            const RateTables *rt = rate == Params::mark_sample_rate ? nullptr : &rate_tables.at (rate);
+            const int rate = rate_of (i);
+            const RateTables *rt = rate == Params::mark_sample_rate ? nullptr : per_segment ? &rate_tables.at (rate) : one_rate;
             auto one = [&] (const float *in, float *out) {
               return rt ? add_segment_rate (ctx, *rt->down, *rt->up, key, payload_hex[i], zero_frames[i], in, out, n_frames[i], n_channels, rate)
                         : add_segment_stream (ctx, key, payload_hex[i], zero_frames[i], in, out, n_frames[i], n_channels);
             };
             if constexpr (S16)
               {
-                // (the definition itself, as in add_segments_s16: decode, the float path of one segment, encode direct16)
                 const size_t n_values = n_frames[i] * size_t (n_channels);
                 if (int rc = ctx->ws_seg_in.reserve (n_values * sizeof (float))) return rc;
                 if (int rc = ctx->ws_seg_out.reserve (n_values * sizeof (float))) return rc;
@@ -4254,19 +3638,80 @@ add_segments_rates (awm_ctx *ctx, const char *fn, const uint8_t *keys, bool per_
   g_add_segments_fused_in_use = 1;
   if (segs.empty())
     return 0;
-  return add_segments_rates_fused (ctx, rate_tables, per_key ? nullptr : keys, segs, table_of, per_key ? coded_tables : coded, n_code, zero_frames,
-                                   pcm_in_d, out_d, n_frames, sample_rates, per_key ? &mk : nullptr);
+  auto *fused_fn = per_segment ? add_segments_fused<T, true> : add_segments_fused<T, false>;
+  return fused_fn (ctx, rate_tables, per_key ? nullptr : keys, segs, table_of, per_key ? coded_tables : coded, n_code, zero_frames, pcm_in_d, out_d,
+                   n_frames, rates, per_key ? &mk : nullptr);
 }
 } // extern "C++"
+
+/* the entry points: which of them a call IS -- all rates equal: the one-rate function, 44.1 kHz: the function without a rate, one key for
+ * all: the one-key function -- is decided here, before anything else happens; the messages of a call carry that function's name */
+static const int RATE_44100 = Params::mark_sample_rate;
+
+int
+awm_add_watermark_segments_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                              const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels)
+{
+  return add_segments_any (ctx, "awm_add_watermark_segments_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels,
+                           &RATE_44100, false);
+}
+
+int
+awm_add_watermark_segments_rate_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                   const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_add_watermark_segments_d (ctx, key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels);
+  return add_segments_any (ctx, "awm_add_watermark_segments_rate_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, &sample_rate, false);
+}
+
+int
+awm_add_watermark_segments_keys_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                   const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels)
+{
+  if (ctx && keys && n_segments && segments_share_one_key (keys, n_segments))
+    return awm_add_watermark_segments_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels);
+  return add_segments_any (ctx, "awm_add_watermark_segments_keys_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, &RATE_44100, false);
+}
+
+int
+awm_add_watermark_segments_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                        const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_add_watermark_segments_keys_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels);
+  if (ctx && keys && n_segments && segments_share_one_key (keys, n_segments))
+    return awm_add_watermark_segments_rate_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, sample_rate);
+  return add_segments_any (ctx, "awm_add_watermark_segments_keys_rate_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, &sample_rate, false);
+}
+
+int
+awm_add_watermark_segments_rate_s16_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                       const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
+{
+  return add_segments_any (ctx, "awm_add_watermark_segments_rate_s16_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, &sample_rate, false);
+}
+
+int
+awm_add_watermark_segments_keys_rate_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
+                                            const int16_t *const *pcm_in_d, int16_t *const *out_d, const size_t *n_frames, int n_channels, int sample_rate)
+{
+  return add_segments_any (ctx, "awm_add_watermark_segments_keys_rate_s16_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, &sample_rate, false);
+}
 
 int
 awm_add_watermark_segments_rates_d (awm_ctx *ctx, const uint8_t key[16], size_t n_segments, const char *const *payload_hex, const size_t *zero_frames,
                                     const float *const *pcm_in_d, float *const *out_d, const size_t *n_frames, int n_channels, const int *sample_rates)
 {
-  if (rates_all_equal (n_segments, sample_rates))          // IS the one-rate function (which hands 44.1 kHz on), before anything else happens
+  if (rates_all_equal (n_segments, sample_rates))
     return awm_add_watermark_segments_rate_d (ctx, key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, sample_rates[0]);
-  return add_segments_rates (ctx, "awm_add_watermark_segments_rates_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
-                             n_channels, sample_rates);
+  return add_segments_any (ctx, "awm_add_watermark_segments_rates_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, sample_rates, true);
 }
 
 int
@@ -4275,8 +3720,8 @@ awm_add_watermark_segments_keys_rates_d (awm_ctx *ctx, const uint8_t *keys, size
 {
   if (rates_all_equal (n_segments, sample_rates))
     return awm_add_watermark_segments_keys_rate_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels, sample_rates[0]);
-  return add_segments_rates (ctx, "awm_add_watermark_segments_keys_rates_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
-                             n_channels, sample_rates);
+  return add_segments_any (ctx, "awm_add_watermark_segments_keys_rates_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, sample_rates, true);
 }
 
 // (16-bit: sample_rates may be null -- every segment at 44.1 kHz, like awm_get_watermark_batch_rates_s16_d)
@@ -4287,8 +3732,8 @@ awm_add_watermark_segments_rates_s16_d (awm_ctx *ctx, const uint8_t key[16], siz
   if (!sample_rates || rates_all_equal (n_segments, sample_rates))
     return awm_add_watermark_segments_rate_s16_d (ctx, key, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels,
                                                   sample_rates ? sample_rates[0] : int (Params::mark_sample_rate));
-  return add_segments_rates (ctx, "awm_add_watermark_segments_rates_s16_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
-                             n_channels, sample_rates);
+  return add_segments_any (ctx, "awm_add_watermark_segments_rates_s16_d", key, false, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames,
+                           n_channels, sample_rates, true);
 }
 
 int
@@ -4299,8 +3744,8 @@ awm_add_watermark_segments_keys_rates_s16_d (awm_ctx *ctx, const uint8_t *keys, 
   if (!sample_rates || rates_all_equal (n_segments, sample_rates))
     return awm_add_watermark_segments_keys_rate_s16_d (ctx, keys, n_segments, payload_hex, zero_frames, pcm_in_d, out_d, n_frames, n_channels,
                                                        sample_rates ? sample_rates[0] : int (Params::mark_sample_rate));
-  return add_segments_rates (ctx, "awm_add_watermark_segments_keys_rates_s16_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d,
-                             n_frames, n_channels, sample_rates);
+  return add_segments_any (ctx, "awm_add_watermark_segments_keys_rates_s16_d", keys, true, n_segments, payload_hex, zero_frames, pcm_in_d, out_d,
+                           n_frames, n_channels, sample_rates, true);
 }
 
 /* K16t alone (measurements, tests): the templates of n_keys keys built on the device, KEY_TMPL_LAUNCH per launch, and copied to the host,
