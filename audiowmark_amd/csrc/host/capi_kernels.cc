@@ -6,6 +6,7 @@
 #include "wmspeed.hh"
 #include "utils.hh"
 #include "wmfile.hh"
+#include "keytab_stage.hh"
 #include <sys/stat.h>
 #include <atomic>
 #include <future>
@@ -2367,6 +2368,47 @@ add_clips_batchable (awm_ctx *ctx, size_t n_clips, const float *const *pcm_in_d,
   return true;
 }
 
+/* lanes 0 .. n - 1 of the context, each with an ev_sync */
+static int
+lanes_with_sync (awm_ctx *ctx, int n, std::vector<WorkLane *>& lanes)
+{
+  lanes.clear();
+  for (int i = 0; i < n; i++)
+    {
+      WorkLane *l = ctx->lane (i);
+      if (!l)
+        {
+          set_error ("cannot create a work lane (stream)");
+          return AWM_ERR_HIP;
+        }
+      if (!l->ev_sync)
+        AWM_HIP_CHECK (hipEventCreateWithFlags (&l->ev_sync, hipEventDisableTiming));
+      lanes.push_back (l);
+    }
+  return 0;
+}
+
+/* the events of one call (no timing), destroyed with it */
+namespace {
+struct Events
+{
+  std::vector<hipEvent_t> ev;
+  Events() = default;
+  Events (const Events&) = delete;
+  Events& operator= (const Events&) = delete;
+  ~Events() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy (e); }
+  int
+  create (size_t n)
+  {
+    ev = std::vector<hipEvent_t> (n, nullptr);
+    for (hipEvent_t& e : ev)
+      AWM_HIP_CHECK (hipEventCreateWithFlags (&e, hipEventDisableTiming));
+    return 0;
+  }
+  hipEvent_t operator[] (size_t i) const { return ev[i]; }
+};
+}
+
 /* Batched arguments of a whole call: staged once (page-locked), copied once; groups then launch on slices of the device arrays. */
 struct AddBatchArgs
 {
@@ -2495,18 +2537,7 @@ awm_add_watermark_batch_d (awm_ctx *ctx, const uint8_t key[16], const char *payl
   constexpr int ADD_LANES = 8;
   const int n_lanes = int (std::min<size_t> (ADD_LANES, n_clips));
   std::vector<WorkLane *> lanes;
-  for (int i = 0; i < n_lanes; i++)
-    {
-      WorkLane *l = ctx->lane (i);
-      if (!l)
-        {
-          set_error ("cannot create a work lane (stream)");
-          return AWM_ERR_HIP;
-        }
-      if (!l->ev_sync)
-        AWM_HIP_CHECK (hipEventCreateWithFlags (&l->ev_sync, hipEventDisableTiming));
-      lanes.push_back (l);
-    }
+  if (int rc = lanes_with_sync (ctx, n_lanes, lanes)) return rc;
   if (n_lanes > 1)
     {
       AWM_HIP_CHECK (hipEventRecord (ctx->ev_sync, ctx->stream));
@@ -2584,7 +2615,7 @@ static bool
 key_templates_on_device_possible()
 {
   return params().mix && params().frames_per_bit == 2 && mark_block_frame_count() == 2226 && mark_sync_frame_count() == 510
-         && code_size (ConvBlockType::a, params().payload_size) == 858;
+         && code_size (ConvBlockType::a, params().payload_size) == KEYTAB_CODE_BITS;
 }
 
 struct SegmentKeys
@@ -2596,14 +2627,15 @@ struct SegmentKeys
   size_t     stride = 0;                       // entries of a template slot (awmk::payload_table_stride)
   size_t     built = 0;                        // keys 0 .. built - 1 have had their templates made
   const int *d_tmpl_of = nullptr;
-  const unsigned char *d_aux = nullptr;        // [S-box 256][key schedules: keys x 176]
+  const unsigned char *d_aux = nullptr;        // the keys' block without a payload's code (keytab_stage.hh)
+  KeytabAux  aux {};
 
   /* bytes behind the (16-byte aligned) end of the other arguments: tmpl_of, then what K16t reads */
-  size_t arg_bytes() const { return key_of_table.size() * sizeof (int) + (on_device ? 256 + 176 * keys.size() : 0); }
+  size_t arg_bytes() const { return key_of_table.size() * sizeof (int) + (on_device ? keytab_aux_layout (keys.size(), false).bytes : 0); }
   int
-  reserve (awm_ctx *ctx, size_t table_stride)
+  reserve (awm_ctx *ctx, size_t table_stride, bool device = g_key_tables_on_device && key_templates_on_device_possible())
   {
-    on_device = g_key_tables_on_device && key_templates_on_device_possible();
+    on_device = device;
     stride = table_stride;
     if (int rc = ctx->ws_key_tmpl.reserve (std::min (keys.size(), KEY_TMPL_SLOTS) * stride * sizeof (int16_t))) return rc;
     if (on_device)
@@ -2619,21 +2651,14 @@ struct SegmentKeys
     d_tmpl_of = reinterpret_cast<const int *> (d);
     if (!on_device)
       return;
-    unsigned char *aux = reinterpret_cast<unsigned char *> (h) + key_of_table.size() * sizeof (int);
-    std::memcpy (aux, Aes128::sbox(), 256);
-    for (size_t k = 0; k < keys.size(); k++)
-      {
-        Aes128 aes;
-        aes.set_key (keys[k].data());
-        std::memcpy (aux + 256 + 176 * k, aes.round_keys(), 176);
-      }
+    aux = keytab_aux_pack (reinterpret_cast<unsigned char *> (h) + key_of_table.size() * sizeof (int), keys.size(),
+                           [this] (size_t k) { return keys[k].data(); });
     d_aux = reinterpret_cast<const unsigned char *> (d) + key_of_table.size() * sizeof (int);
   }
-  /* the templates of the keys that the tables up to t1 - 1 need and that are not there yet (the groups come in order) */
+  /* the templates of the keys up to k1 - 1 that are not there yet (the groups come in order: k1 = 1 + the key of a group's last table) */
   int
-  build (awm_ctx *ctx, hipStream_t st, size_t t1)
+  build (awm_ctx *ctx, hipStream_t st, size_t k1)
   {
-    const size_t k1 = size_t (key_of_table[t1 - 1]) + 1;
     short *slots = ctx->ws_key_tmpl.as<short>();
     while (built < k1)
       {
@@ -2648,12 +2673,7 @@ struct SegmentKeys
             continue;
           }
         const size_t kn = std::min ({ KEY_TMPL_LAUNCH, k1 - built, KEY_TMPL_SLOTS - slot });
-        awmk::KeyTableArgs ka {};
-        ka.sbox = d_aux;
-        ka.round_keys = d_aux + 256 + 176 * built;
-        ka.scratch = ctx->ws_keytab_scratch.as<unsigned char>();
-        ka.scratch_slots = int (KEY_TMPL_LAUNCH);
-        ka.n_keys = (long long) kn;
+        const awmk::KeyTableArgs ka = keytab_args (d_aux, aux, built, kn, ctx->ws_keytab_scratch.as<unsigned char>(), KEY_TMPL_LAUNCH);
         const awmk::KeyTemplateOut out { slots + slot * stride, (long long) stride };
         ProfScope ps (ctx, PROF_KEY_TEMPLATE, double (kn) * stride * sizeof (int16_t), st);       // the templates out, once (721 KB per key)
         AWM_HIP_CHECK (awmk::launch_key_templates (st, ka, out));
@@ -2662,6 +2682,24 @@ struct SegmentKeys
     return 0;
   }
 };
+
+/* the conv code of one payload (its parsed bits) behind `coded`: 2 x n_code bytes 0 / 1, the A block's then the B block's */
+static int
+payload_code_append (const std::vector<int>& bits, size_t n_code, std::vector<unsigned char>& coded)
+{
+  for (ConvBlockType type : { ConvBlockType::a, ConvBlockType::b })
+    {
+      const std::vector<int> code = code_encode (type, bits);
+      if (code.size() != n_code)
+        {
+          set_error ("conv code of unexpected size");
+          return AWM_ERR_GENERIC;
+        }
+      for (int c : code)
+        coded.push_back ((unsigned char) (c & 1));
+    }
+  return 0;
+}
 
 /* what both segment entry points check before anything is enqueued (fn: the entry point, for the messages), and the distinct payloads'
  * codes: payload_index[i] = index of segment i's payload among the distinct ones, coded = [distinct][2 (A, B)][n_code] bytes.  T: the sample
@@ -2715,17 +2753,7 @@ segments_check (awm_ctx *ctx, const char *fn, const uint8_t key[16], size_t n_se
             }
           if (!n_frames[i])                                // (a segment without samples: its payload is checked, no table is made for it)
             continue;
-          for (int ab = 0; ab < 2; ab++)
-            {
-              const std::vector<int> code = code_encode (ab ? ConvBlockType::b : ConvBlockType::a, bits);
-              if (code.size() != n_code)
-                {
-                  set_error ("conv code of unexpected size");
-                  return AWM_ERR_GENERIC;
-                }
-              for (int c : code)
-                coded.push_back ((unsigned char) (c & 1));
-            }
+          if (int rc = payload_code_append (bits, n_code, coded)) return rc;
           it = distinct.emplace (payload_hex[i], distinct.size()).first;
         }
       payload_index[i] = it->second;
@@ -3039,7 +3067,7 @@ segment_table_group (awm_ctx *ctx, hipStream_t st, const FrameModTemplate *tmpl,
   pa.tmpl = mk ? ctx->ws_key_tmpl.as<short>() : tmpl->dev.as<short>();
   if (mk)
     {
-      if (int rc = mk->build (ctx, st, first_table + n_tables)) return rc;
+      if (int rc = mk->build (ctx, st, size_t (mk->key_of_table[first_table + n_tables - 1]) + 1)) return rc;
       pa.tmpl_of = mk->d_tmpl_of + first_table;
       pa.tmpl_stride = (long long) table_stride;
     }
@@ -3760,34 +3788,24 @@ awm_debug_key_templates_d (awm_ctx *ctx, const uint8_t *keys, size_t n_keys, int
       set_error ("awm_debug_key_templates_d: bad argument (keys; the default geometry: mix, two frames per bit, 128 payload bits)");
       return AWM_ERR_ARG;
     }
-  const size_t stride = awmk::payload_table_stride (mark_block_frame_count()), aux_bytes = 256 + KEY_TMPL_LAUNCH * 176;
-  if (int rc = ctx->ws_keytab_aux.reserve (aux_bytes)) return rc;
-  if (int rc = ctx->ws_key_tmpl.reserve (std::min (n_keys, KEY_TMPL_LAUNCH) * stride * sizeof (int16_t))) return rc;
-  if (int rc = ctx->ws_keytab_scratch.reserve (KEY_TMPL_LAUNCH * awmk::key_table_scratch_bytes())) return rc;
-  std::vector<unsigned char> aux (aux_bytes);
-  std::memcpy (aux.data(), Aes128::sbox(), 256);
+  const size_t stride = awmk::payload_table_stride (mark_block_frame_count());
+  if (int rc = ctx->ws_keytab_aux.reserve (keytab_aux_layout (KEY_TMPL_LAUNCH, false).bytes)) return rc;
+  std::vector<char> args;
   for (size_t g0 = 0; g0 < n_keys; g0 += KEY_TMPL_LAUNCH)
     {
+      // a launch window of keys through the segments' own staging and launch (no tables: tmpl_of stays empty)
       const size_t gn = std::min (KEY_TMPL_LAUNCH, n_keys - g0);
+      SegmentKeys mk;
       for (size_t i = 0; i < gn; i++)
         {
-          Aes128 aes;
-          aes.set_key (keys + 16 * (g0 + i));
-          std::memcpy (aux.data() + 256 + 176 * i, aes.round_keys(), 176);
+          mk.keys.emplace_back();
+          std::memcpy (mk.keys.back().data(), keys + 16 * (g0 + i), 16);
         }
-      unsigned char *d_aux = ctx->ws_keytab_aux.as<unsigned char>();
-      AWM_HIP_CHECK (hipMemcpyAsync (d_aux, aux.data(), aux_bytes, hipMemcpyHostToDevice, ctx->stream));
-      awmk::KeyTableArgs ka {};
-      ka.sbox = d_aux;
-      ka.round_keys = d_aux + 256;
-      ka.scratch = ctx->ws_keytab_scratch.as<unsigned char>();
-      ka.scratch_slots = int (KEY_TMPL_LAUNCH);
-      ka.n_keys = (long long) gn;
-      const awmk::KeyTemplateOut t { ctx->ws_key_tmpl.as<short>(), (long long) stride };
-      {
-        ProfScope ps (ctx, PROF_KEY_TEMPLATE, double (gn) * stride * sizeof (int16_t));
-        AWM_HIP_CHECK (awmk::launch_key_templates (ctx->stream, ka, t));
-      }
+      if (int rc = mk.reserve (ctx, stride, true)) return rc;
+      args.resize (mk.arg_bytes());
+      mk.fill (args.data(), ctx->ws_keytab_aux.as<char>());
+      AWM_HIP_CHECK (hipMemcpyAsync (ctx->ws_keytab_aux.ptr, args.data(), args.size(), hipMemcpyHostToDevice, ctx->stream));
+      if (int rc = mk.build (ctx, ctx->stream, gn)) return rc;
       if (out)
         AWM_HIP_CHECK (hipMemcpyAsync (out + g0 * stride, ctx->ws_key_tmpl.ptr, gn * stride * sizeof (int16_t), hipMemcpyDeviceToHost, ctx->stream));
       AWM_HIP_CHECK (stream_wait (ctx->stream));              // (the staging vector is refilled for the next launch)
@@ -3824,20 +3842,13 @@ awm_debug_key_payload_tables_d (awm_ctx *ctx, const uint8_t *keys, const char *c
           set_error (string_printf ("awm_debug_key_payload_tables_d: cannot parse the payload at index %zu", p));
           return AWM_ERR_ARG;
         }
-      for (int ab = 0; ab < 2; ab++)
-        for (int c : code_encode (ab ? ConvBlockType::b : ConvBlockType::a, bits))
-          coded.push_back ((unsigned char) (c & 1));
+      if (int rc = payload_code_append (bits, n_code, coded)) return rc;
       if (!t || std::memcmp (keys + 16 * p, keys + 16 * order[t - 1], 16))
         {
           mk.keys.emplace_back();
           std::memcpy (mk.keys.back().data(), keys + 16 * p, 16);
         }
       mk.key_of_table.push_back (int (mk.keys.size() - 1));
-    }
-  if (coded.size() != n * 2 * n_code)
-    {
-      set_error ("conv code of unexpected size");
-      return AWM_ERR_GENERIC;
     }
   if (int rc = mk.reserve (ctx, table_stride)) return rc;
   const size_t off_keys = (coded.size() + 15) / 16 * 16;
@@ -3847,21 +3858,7 @@ awm_debug_key_payload_tables_d (awm_ctx *ctx, const uint8_t *keys, const char *c
   if (int rc = ctx->ws_keytab_aux.reserve (args.size())) return rc;
   mk.fill (args.data() + off_keys, ctx->ws_keytab_aux.as<char>() + off_keys);
   if (int rc = upload_sync (ctx->ws_keytab_aux, args.data(), args.size(), ctx->stream)) return rc;
-  if (int rc = mk.build (ctx, ctx->stream, n)) return rc;
-  awmk::PayloadTableArgs pa {};
-  pa.tmpl = ctx->ws_key_tmpl.as<short>();
-  pa.tmpl_of = mk.d_tmpl_of;
-  pa.tmpl_stride = (long long) table_stride;
-  pa.coded = ctx->ws_keytab_aux.as<unsigned char>();
-  pa.tables = ctx->ws_keytab.as<signed char>();
-  pa.table_stride = (long long) table_stride;
-  pa.half_entries = int (block_frames * Params::n_bands);
-  pa.n_code = int (n_code);
-  pa.n_payloads = int (n);
-  {
-    ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (n) * table_stride);
-    AWM_HIP_CHECK (awmk::launch_payload_tables (ctx->stream, pa));
-  }
+  if (int rc = segment_table_group (ctx, ctx->stream, nullptr, &mk, 0, n, ctx->ws_keytab_aux.as<unsigned char>(), n_code)) return rc;
   for (size_t t = 0; t < n; t++)
     AWM_HIP_CHECK (hipMemcpyAsync (tables_out + order[t] * table_bytes, ctx->ws_keytab.as<int8_t>() + t * table_stride, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
   AWM_HIP_CHECK (stream_wait (ctx->stream));
@@ -3891,32 +3888,14 @@ awm_debug_payload_tables_d (awm_ctx *ctx, const uint8_t key[16], const char *con
           set_error (string_printf ("awm_debug_payload_tables_d: cannot parse the payload at index %zu", p));
           return AWM_ERR_ARG;
         }
-      for (int ab = 0; ab < 2; ab++)
-        for (int c : code_encode (ab ? ConvBlockType::b : ConvBlockType::a, bits))
-          coded.push_back ((unsigned char) (c & 1));
-    }
-  if (coded.size() != n_payloads * 2 * n_code)
-    {
-      set_error ("conv code of unexpected size");
-      return AWM_ERR_GENERIC;
+      if (int rc = payload_code_append (bits, n_code, coded)) return rc;
     }
   FrameModTemplate *tmpl = ctx->get_frame_mod_template (capi_key (key));
   if (!tmpl)
     return AWM_ERR_HIP;
   if (int rc = ctx->ws_keytab.reserve (n_payloads * table_stride)) return rc;
   if (int rc = upload_sync (ctx->ws_keytab_aux, coded.data(), coded.size(), ctx->stream)) return rc;
-  awmk::PayloadTableArgs pa {};
-  pa.tmpl = tmpl->dev.as<short>();
-  pa.coded = ctx->ws_keytab_aux.as<unsigned char>();
-  pa.tables = ctx->ws_keytab.as<signed char>();
-  pa.table_stride = (long long) table_stride;
-  pa.half_entries = int (block_frames * Params::n_bands);
-  pa.n_code = int (n_code);
-  pa.n_payloads = int (n_payloads);
-  {
-    ProfScope ps (ctx, PROF_PAYLOAD_TAB, double (n_payloads) * table_stride);
-    AWM_HIP_CHECK (awmk::launch_payload_tables (ctx->stream, pa));
-  }
+  if (int rc = segment_table_group (ctx, ctx->stream, tmpl, nullptr, 0, n_payloads, ctx->ws_keytab_aux.as<unsigned char>(), n_code)) return rc;
   if (tables_out)
     {
       AWM_HIP_CHECK (hipMemcpy2DAsync (tables_out, table_bytes, ctx->ws_keytab.ptr, table_stride, table_bytes, n_payloads, hipMemcpyDeviceToHost, ctx->stream));
@@ -3932,52 +3911,60 @@ awm_debug_payload_tables_d (awm_ctx *ctx, const uint8_t key[16], const char *con
  * 0: on host threads */
 extern "C" void awm_debug_set_key_tables_on_device (int on) { g_key_tables_on_device = on; }
 
-/* awm_add_watermark_batch_keys_d with the tables built by K16: groups of GROUP keys (one workgroup = one compute unit per key), two
- * table areas in turn -- the tables of group g + 1 are built (on a lane of their own) while the clips of group g are watermarked on the
- * add lanes; what the host contributes per key is the AES key schedule (176 bytes). */
+constexpr size_t KEY_TABLE_LAUNCH = 256;       // keys per launch of K16: one workgroup = one compute unit per key
+
+/* K16's block for the keys of a batch of clips with one payload (keytab_stage.hh): one page-locked block (pin_keytab), one upload to
+ * ws_keytab_aux on st.  The block is the context's: the caller waits for the upload before it returns */
+static int
+clip_keys_aux_upload (awm_ctx *ctx, hipStream_t st, const uint8_t *keys, size_t n_keys, const std::vector<int>& bits, KeytabAux& aux)
+{
+  std::vector<unsigned char> coded;
+  if (int rc = payload_code_append (bits, KEYTAB_CODE_BITS, coded)) return rc;
+  const size_t aux_bytes = keytab_aux_layout (n_keys, true).bytes;
+  if (int rc = ctx->pin_keytab.reserve (aux_bytes)) return rc;
+  if (int rc = ctx->ws_keytab_aux.reserve (aux_bytes)) return rc;
+  aux = keytab_aux_pack (ctx->pin_keytab.as<unsigned char>(), n_keys, keys, coded.data());
+  AWM_HIP_CHECK (hipMemcpyAsync (ctx->ws_keytab_aux.ptr, ctx->pin_keytab.ptr, aux_bytes, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+/* K16 for keys first_key .. first_key + n_keys - 1 of the block in ws_keytab_aux, KEY_TABLE_LAUNCH per launch on st (the launches of a
+ * stream share ws_keytab_scratch): their tables from `tables` on, one behind the other */
+static int
+key_tables_run (awm_ctx *ctx, hipStream_t st, const KeytabAux& aux, size_t first_key, size_t n_keys, int8_t *tables)
+{
+  const size_t table_bytes = awmk::key_table_bytes();
+  for (size_t g0 = 0; g0 < n_keys; g0 += KEY_TABLE_LAUNCH)
+    {
+      const size_t gn = std::min (KEY_TABLE_LAUNCH, n_keys - g0);
+      awmk::KeyTableArgs ka = keytab_args (ctx->ws_keytab_aux.as<unsigned char>(), aux, first_key + g0, gn,
+                                           ctx->ws_keytab_scratch.as<unsigned char>(), KEY_TABLE_LAUNCH);
+      ka.tables = reinterpret_cast<signed char *> (tables + g0 * table_bytes);
+      ProfScope ps (ctx, PROF_KEYTAB, double (gn) * table_bytes, st);                  // the table out, once (360 KB per key)
+      AWM_HIP_CHECK (awmk::launch_frame_mod_tables (st, ka));
+    }
+  return 0;
+}
+
 /* Batched clips with a key per clip, everything on the context's stream: FIRST the tables of (up to 4096) keys, 256 per launch of K16, THEN the
  * clips in one launch per stage.  K16 holds 116 KB of LDS on every compute unit it runs on: beside it K2 runs one workgroup per unit
  * instead of four, and the first group's tables are waited for in any case -- building the next group's tables WHILE a group is
- * watermarked (the loop below, awm_debug_set_add_batched (1)) cost more than it hid once the clips of a group took 3 ms instead of 8. */
+ * watermarked (add_batch_keys_device_tables below, awm_debug_set_add_batched (1)) cost more than it hid once the clips of a group took 3 ms instead of 8. */
 static int
 add_batch_keys_tables_first (awm_ctx *ctx, const uint8_t *keys, const std::vector<int>& bits, size_t n_clips, const float *const *pcm_in_d,
                              float *const *out_d, const size_t *n_frames)
 {
-  constexpr size_t GROUP = 256, SUPER = 4096;
+  constexpr size_t SUPER = 4096;
   const size_t table_bytes = awmk::key_table_bytes();
   const int use_limiter = !params().test_no_limiter;
   hipStream_t st = ctx->stream;
-  // one page-locked block, one upload: [S-box 256][conv code of the payload, A then B: 2 x 858][key schedules: n x 176]
-  const size_t aux_bytes = 256 + 2 * 858 + n_clips * 176;
-  if (int rc = ctx->pin_keytab.reserve (aux_bytes)) return rc;
-  if (int rc = ctx->ws_keytab_aux.reserve (aux_bytes)) return rc;
   if (int rc = ctx->ws_keytab.reserve (std::min (n_clips, SUPER) * table_bytes)) return rc;
-  if (int rc = ctx->ws_keytab_scratch.reserve (GROUP * awmk::key_table_scratch_bytes())) return rc;
-  unsigned char *aux = ctx->pin_keytab.as<unsigned char>();
-  std::memcpy (aux, Aes128::sbox(), 256);
-  for (int ab = 0; ab < 2; ab++)
-    {
-      const std::vector<int> coded = code_encode (ab ? ConvBlockType::b : ConvBlockType::a, bits);
-      if (coded.size() != 858)
-        {
-          set_error ("conv code of unexpected size");
-          return AWM_ERR_GENERIC;
-        }
-      for (size_t i = 0; i < coded.size(); i++)
-        aux[256 + 858 * ab + i] = (unsigned char) (coded[i] & 1);
-    }
-  for (size_t i = 0; i < n_clips; i++)
-    {
-      Aes128 aes;
-      aes.set_key (keys + 16 * i);
-      std::memcpy (aux + 256 + 2 * 858 + 176 * i, aes.round_keys(), 176);
-    }
-  unsigned char *d_aux = ctx->ws_keytab_aux.as<unsigned char>();
-  AWM_HIP_CHECK (hipMemcpyAsync (d_aux, aux, aux_bytes, hipMemcpyHostToDevice, st));
-  hipEvent_t ev_aux = nullptr;
-  struct Event { hipEvent_t& e; ~Event() { if (e) (void) hipEventDestroy (e); } } event { ev_aux };
-  AWM_HIP_CHECK (hipEventCreateWithFlags (&ev_aux, hipEventDisableTiming));
-  AWM_HIP_CHECK (hipEventRecord (ev_aux, st));
+  if (int rc = ctx->ws_keytab_scratch.reserve (KEY_TABLE_LAUNCH * awmk::key_table_scratch_bytes())) return rc;
+  KeytabAux aux;
+  if (int rc = clip_keys_aux_upload (ctx, st, keys, n_clips, bits, aux)) return rc;
+  Events ev_aux;
+  if (int rc = ev_aux.create (1)) return rc;
+  AWM_HIP_CHECK (hipEventRecord (ev_aux[0], st));
   std::vector<const int8_t *> tables (n_clips);
   for (size_t i = 0; i < n_clips; i++)
     tables[i] = ctx->ws_keytab.as<int8_t>() + (i % SUPER) * table_bytes;
@@ -3987,33 +3974,24 @@ add_batch_keys_tables_first (awm_ctx *ctx, const uint8_t *keys, const std::vecto
   for (size_t s0 = 0; s0 < n_clips; s0 += SUPER)
     {
       const size_t sn = std::min (SUPER, n_clips - s0);
-      for (size_t g0 = s0; g0 < s0 + sn; g0 += GROUP)
-        {
-          const size_t gn = std::min (GROUP, s0 + sn - g0);
-          awmk::KeyTableArgs ka {};
-          ka.sbox = d_aux;
-          ka.coded = d_aux + 256;
-          ka.round_keys = d_aux + 256 + 2 * 858 + 176 * g0;
-          ka.scratch = ctx->ws_keytab_scratch.as<unsigned char>();
-          ka.scratch_slots = int (GROUP);
-          ka.tables = reinterpret_cast<signed char *> (ctx->ws_keytab.as<int8_t>() + (g0 - s0) * table_bytes);
-          ka.n_keys = (long long) gn;
-          ProfScope ps (ctx, PROF_KEYTAB, double (gn) * table_bytes, st);              // the table out, once (360 KB per key)
-          AWM_HIP_CHECK (awmk::launch_frame_mod_tables (st, ka));
-        }
+      if (int rc = key_tables_run (ctx, st, aux, s0, sn, ctx->ws_keytab.as<int8_t>()))
+        return rc;
       if (int rc = add_batch_run (ctx, st, batch, s0, sn, use_limiter))
         return rc;
     }
   // (the staging block is the context's: its upload has to be through before the next call refills it)
-  AWM_HIP_CHECK (hipEventSynchronize (ev_aux));
+  AWM_HIP_CHECK (hipEventSynchronize (ev_aux[0]));
   return 0;
 }
 
+/* awm_add_watermark_batch_keys_d with the tables built by K16: groups of GROUP keys (one workgroup = one compute unit per key), two
+ * table areas in turn -- the tables of group g + 1 are built (on a lane of their own) while the clips of group g are watermarked on the
+ * add lanes; what the host contributes per key is the AES key schedule (176 bytes). */
 static int
 add_batch_keys_device_tables (awm_ctx *ctx, const uint8_t *keys, const std::vector<int>& bits, size_t n_clips, const float *const *pcm_in_d,
                               float *const *out_d, const size_t *n_frames, int n_channels)
 {
-  constexpr size_t GROUP = 256;
+  constexpr size_t GROUP = KEY_TABLE_LAUNCH;               // (a group's tables are one launch)
   constexpr int ADD_LANES = 8;
   const size_t table_bytes = awmk::key_table_bytes();
   // a group of clips in one launch per stage on the context's stream (add_clips_batched above), or clip by clip on eight lanes
@@ -4022,59 +4000,17 @@ add_batch_keys_device_tables (awm_ctx *ctx, const uint8_t *keys, const std::vect
     return add_batch_keys_tables_first (ctx, keys, bits, n_clips, pcm_in_d, out_d, n_frames);
   const int use_limiter = !params().test_no_limiter;
   const int n_lanes = batched ? 1 : int (std::min<size_t> (ADD_LANES, n_clips));
-  std::vector<WorkLane *> lanes;
-  for (int i = 0; i <= n_lanes; i++)                       // lanes 0 .. n_lanes - 1 watermark, lane n_lanes builds tables
-    {
-      WorkLane *l = ctx->lane (i);
-      if (!l)
-        {
-          set_error ("cannot create a work lane (stream)");
-          return AWM_ERR_HIP;
-        }
-      if (!l->ev_sync)
-        AWM_HIP_CHECK (hipEventCreateWithFlags (&l->ev_sync, hipEventDisableTiming));
-      lanes.push_back (l);
-    }
+  std::vector<WorkLane *> lanes;                           // lanes 0 .. n_lanes - 1 watermark, lane n_lanes builds tables
+  if (int rc = lanes_with_sync (ctx, n_lanes + 1, lanes)) return rc;
   hipStream_t table_stream = lanes[n_lanes]->stream;
-  // one page-locked block, one upload: [S-box 256][conv code of the payload, A then B: 2 x 858][key schedules: n x 176]
-  const size_t aux_bytes = 256 + 2 * 858 + n_clips * 176;
-  if (int rc = ctx->pin_keytab.reserve (aux_bytes)) return rc;
-  if (int rc = ctx->ws_keytab_aux.reserve (aux_bytes)) return rc;
   if (int rc = ctx->ws_keytab.reserve (2 * GROUP * table_bytes)) return rc;
-  if (int rc = ctx->ws_keytab_scratch.reserve (GROUP * awmk::key_table_scratch_bytes())) return rc;
-  unsigned char *aux = ctx->pin_keytab.as<unsigned char>();
-  std::memcpy (aux, Aes128::sbox(), 256);
-  for (int ab = 0; ab < 2; ab++)
-    {
-      const std::vector<int> coded = code_encode (ab ? ConvBlockType::b : ConvBlockType::a, bits);
-      if (coded.size() != 858)
-        {
-          set_error ("conv code of unexpected size");
-          return AWM_ERR_GENERIC;
-        }
-      for (size_t i = 0; i < coded.size(); i++)
-        aux[256 + 858 * ab + i] = (unsigned char) (coded[i] & 1);
-    }
-  for (size_t i = 0; i < n_clips; i++)
-    {
-      Aes128 aes;
-      aes.set_key (keys + 16 * i);
-      std::memcpy (aux + 256 + 2 * 858 + 176 * i, aes.round_keys(), 176);
-    }
-  unsigned char *d_aux = ctx->ws_keytab_aux.as<unsigned char>();
-  AWM_HIP_CHECK (hipMemcpyAsync (d_aux, aux, aux_bytes, hipMemcpyHostToDevice, ctx->stream));
-  hipEvent_t ev_aux = nullptr, ev_tab[2] = { nullptr, nullptr };
-  std::vector<hipEvent_t> lane_done (2 * size_t (n_lanes), nullptr);
-  struct Events
-  {
-    hipEvent_t& a; hipEvent_t (&t)[2]; std::vector<hipEvent_t>& d;
-    ~Events() { if (a) (void) hipEventDestroy (a); for (hipEvent_t e : t) if (e) (void) hipEventDestroy (e); for (hipEvent_t e : d) if (e) (void) hipEventDestroy (e); }
-  } events { ev_aux, ev_tab, lane_done };
-  AWM_HIP_CHECK (hipEventCreateWithFlags (&ev_aux, hipEventDisableTiming));
-  for (auto& e : ev_tab)
-    AWM_HIP_CHECK (hipEventCreateWithFlags (&e, hipEventDisableTiming));
-  for (auto& e : lane_done)
-    AWM_HIP_CHECK (hipEventCreateWithFlags (&e, hipEventDisableTiming));
+  if (int rc = ctx->ws_keytab_scratch.reserve (KEY_TABLE_LAUNCH * awmk::key_table_scratch_bytes())) return rc;
+  KeytabAux aux;
+  if (int rc = clip_keys_aux_upload (ctx, ctx->stream, keys, n_clips, bits, aux)) return rc;
+  Events ev_aux, ev_tab, lane_done;                        // lane_done: [half][lane], the lane is through the clips of that half
+  if (int rc = ev_aux.create (1)) return rc;
+  if (int rc = ev_tab.create (2)) return rc;
+  if (int rc = lane_done.create (2 * size_t (n_lanes))) return rc;
   AddBatchArgs batch;
   if (batched)
     {
@@ -4085,10 +4021,10 @@ add_batch_keys_device_tables (awm_ctx *ctx, const uint8_t *keys, const std::vect
       if (int rc = add_batch_stage (ctx, ctx->stream, n_clips, pcm_in_d, out_d, n_frames, tables, use_limiter, batch))
         return rc;
     }
-  AWM_HIP_CHECK (hipEventRecord (ev_aux, ctx->stream));    // (also orders everything behind the clips' producers on the context's stream)
-  AWM_HIP_CHECK (hipStreamWaitEvent (table_stream, ev_aux, 0));
+  AWM_HIP_CHECK (hipEventRecord (ev_aux[0], ctx->stream)); // (also orders everything behind the clips' producers on the context's stream)
+  AWM_HIP_CHECK (hipStreamWaitEvent (table_stream, ev_aux[0], 0));
   for (int i = 1; i < n_lanes; i++)
-    AWM_HIP_CHECK (hipStreamWaitEvent (lanes[i]->stream, ev_aux, 0));
+    AWM_HIP_CHECK (hipStreamWaitEvent (lanes[i]->stream, ev_aux[0], 0));
   int rc = 0;
   for (size_t g0 = 0, gi = 0; g0 < n_clips && !rc; g0 += GROUP, gi++)
     {
@@ -4098,16 +4034,8 @@ add_batch_keys_device_tables (awm_ctx *ctx, const uint8_t *keys, const std::vect
       if (gi >= 2)                                          // the clips of group gi - 2 (same table area) are through on every lane
         for (int i = 0; i < n_lanes; i++)
           AWM_HIP_CHECK (hipStreamWaitEvent (table_stream, lane_done[size_t (half) * n_lanes + i], 0));
-      awmk::KeyTableArgs ka {};
-      ka.sbox = d_aux;
-      ka.coded = d_aux + 256;
-      ka.round_keys = d_aux + 256 + 2 * 858 + 176 * g0;
-      ka.scratch = ctx->ws_keytab_scratch.as<unsigned char>();
-      ka.scratch_slots = int (GROUP);
-      ka.tables = reinterpret_cast<signed char *> (dev);
-      ka.n_keys = (long long) gn;
-      ProfScope ps (ctx, PROF_KEYTAB, double (gn) * table_bytes, table_stream);          // the table out, once (360 KB per key)
-      AWM_HIP_CHECK (awmk::launch_frame_mod_tables (table_stream, ka));
+      if (int rc_tab = key_tables_run (ctx, table_stream, aux, g0, gn, dev))
+        return rc_tab;
       AWM_HIP_CHECK (hipEventRecord (ev_tab[half], table_stream));
       for (int i = 0; i < n_lanes; i++)
         AWM_HIP_CHECK (hipStreamWaitEvent (lanes[i]->stream, ev_tab[half], 0));
@@ -4127,7 +4055,7 @@ add_batch_keys_device_tables (awm_ctx *ctx, const uint8_t *keys, const std::vect
   AWM_HIP_CHECK (hipEventRecord (lanes[n_lanes]->ev_sync, table_stream));
   AWM_HIP_CHECK (hipStreamWaitEvent (ctx->stream, lanes[n_lanes]->ev_sync, 0));
   // (the staging block is the context's: its upload has to be through before the next call refills it)
-  AWM_HIP_CHECK (hipEventSynchronize (ev_aux));
+  AWM_HIP_CHECK (hipEventSynchronize (ev_aux[0]));
   return rc;
 }
 
@@ -4137,47 +4065,23 @@ awm_debug_frame_mod_tables_d (awm_ctx *ctx, const uint8_t *keys, size_t n_keys, 
 {
   AWM_ENTER (ctx);
   const std::vector<int> bits = parse_payload (payload_hex ? payload_hex : "");
-  if (bits.empty() || !keys || !tables_out || !params().mix || code_size (ConvBlockType::a, params().payload_size) != 858)
+  if (bits.empty() || !keys || !tables_out || !params().mix || code_size (ConvBlockType::a, params().payload_size) != KEYTAB_CODE_BITS)
     {
       set_error ("awm_debug_frame_mod_tables_d: bad argument");
       return AWM_ERR_ARG;
     }
-  constexpr size_t GROUP = 256;
+  // a launch of keys at a time through the staging and the launches of the clip batches, into one table area
   const size_t table_bytes = awmk::key_table_bytes();
-  const size_t aux_bytes = 256 + 2 * 858 + GROUP * 176;
-  if (int rc = ctx->ws_keytab_aux.reserve (aux_bytes)) return rc;
-  if (int rc = ctx->ws_keytab.reserve (GROUP * table_bytes)) return rc;
-  if (int rc = ctx->ws_keytab_scratch.reserve (GROUP * awmk::key_table_scratch_bytes())) return rc;
-  std::vector<unsigned char> aux (aux_bytes);
-  std::memcpy (aux.data(), Aes128::sbox(), 256);
-  for (int ab = 0; ab < 2; ab++)
+  if (int rc = ctx->ws_keytab.reserve (KEY_TABLE_LAUNCH * table_bytes)) return rc;
+  if (int rc = ctx->ws_keytab_scratch.reserve (KEY_TABLE_LAUNCH * awmk::key_table_scratch_bytes())) return rc;
+  for (size_t g0 = 0; g0 < n_keys; g0 += KEY_TABLE_LAUNCH)
     {
-      const std::vector<int> coded = code_encode (ab ? ConvBlockType::b : ConvBlockType::a, bits);
-      for (size_t i = 0; i < 858 && i < coded.size(); i++)
-        aux[256 + 858 * ab + i] = (unsigned char) (coded[i] & 1);
-    }
-  for (size_t g0 = 0; g0 < n_keys; g0 += GROUP)
-    {
-      const size_t gn = std::min (GROUP, n_keys - g0);
-      for (size_t i = 0; i < gn; i++)
-        {
-          Aes128 aes;
-          aes.set_key (keys + 16 * (g0 + i));
-          std::memcpy (aux.data() + 256 + 2 * 858 + 176 * i, aes.round_keys(), 176);
-        }
-      unsigned char *d_aux = ctx->ws_keytab_aux.as<unsigned char>();
-      AWM_HIP_CHECK (hipMemcpyAsync (d_aux, aux.data(), aux_bytes, hipMemcpyHostToDevice, ctx->stream));
-      awmk::KeyTableArgs ka {};
-      ka.sbox = d_aux;
-      ka.coded = d_aux + 256;
-      ka.round_keys = d_aux + 256 + 2 * 858;
-      ka.scratch = ctx->ws_keytab_scratch.as<unsigned char>();
-      ka.scratch_slots = int (GROUP);
-      ka.tables = ctx->ws_keytab.as<signed char>();
-      ka.n_keys = (long long) gn;
-      AWM_HIP_CHECK (awmk::launch_frame_mod_tables (ctx->stream, ka));
+      const size_t gn = std::min (KEY_TABLE_LAUNCH, n_keys - g0);
+      KeytabAux aux;
+      if (int rc = clip_keys_aux_upload (ctx, ctx->stream, keys + 16 * g0, gn, bits, aux)) return rc;
+      if (int rc = key_tables_run (ctx, ctx->stream, aux, 0, gn, ctx->ws_keytab.as<int8_t>())) return rc;
       AWM_HIP_CHECK (hipMemcpyAsync (tables_out + g0 * table_bytes, ctx->ws_keytab.ptr, gn * table_bytes, hipMemcpyDeviceToHost, ctx->stream));
-      AWM_HIP_CHECK (stream_wait (ctx->stream));
+      AWM_HIP_CHECK (stream_wait (ctx->stream));              // (the staging block and the table area are refilled for the next launch)
     }
   return 0;
 }
@@ -4207,7 +4111,7 @@ awm_add_watermark_batch_keys_d (awm_ctx *ctx, const uint8_t *keys, const char *p
     }
   const size_t table_bytes = 2 * mark_block_frame_count() * Params::n_bands;
   if (g_key_tables_on_device && params().mix && table_bytes == awmk::key_table_bytes()
-      && code_size (ConvBlockType::a, params().payload_size) == 858 && n_clips)
+      && code_size (ConvBlockType::a, params().payload_size) == KEYTAB_CODE_BITS && n_clips)
     return add_batch_keys_device_tables (ctx, keys, bits, n_clips, pcm_in_d, out_d, n_frames, n_channels);
   // The host path (--linear, or the device path switched off): a key's table costs about a millisecond of one host core and is 360 KB; the device needs 25 us per clip.  So the tables are built
   // for SUPER clips at a time on up to 64 host threads, straight into one half of a page-locked staging block (the workers copy,
@@ -4222,18 +4126,7 @@ awm_add_watermark_batch_keys_d (awm_ctx *ctx, const uint8_t *keys, const char *p
   if (int rc = ctx->pin_keytab.reserve (2 * SUPER * table_bytes)) return rc;
   const int n_lanes = int (std::min<size_t> (ADD_LANES, std::max<size_t> (1, n_clips)));
   std::vector<WorkLane *> lanes;
-  for (int i = 0; i < n_lanes; i++)
-    {
-      WorkLane *l = ctx->lane (i);
-      if (!l)
-        {
-          set_error ("cannot create a work lane (stream)");
-          return AWM_ERR_HIP;
-        }
-      if (!l->ev_sync)
-        AWM_HIP_CHECK (hipEventCreateWithFlags (&l->ev_sync, hipEventDisableTiming));
-      lanes.push_back (l);
-    }
+  if (int rc = lanes_with_sync (ctx, n_lanes, lanes)) return rc;
   const std::vector<Key> key_list = key_list_from (keys, int (n_clips));
   ParamValues *const pv = &params();
   char *const pin_base = ctx->pin_keytab.as<char>();
@@ -4262,14 +4155,9 @@ awm_add_watermark_batch_keys_d (awm_ctx *ctx, const uint8_t *keys, const char *p
       t.join();
     return good;
   };
-  hipEvent_t ev_up[2] = { nullptr, nullptr };
-  struct EvGuard { hipEvent_t (&ev)[2]; ~EvGuard() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy (e); } } guard { ev_up };
-  for (auto& e : ev_up)
-    AWM_HIP_CHECK (hipEventCreateWithFlags (&e, hipEventDisableTiming));
-  std::vector<hipEvent_t> lane_done (2 * size_t (n_lanes), nullptr);                    // [half][lane]: the lane is through the clips of that half
-  struct DoneGuard { std::vector<hipEvent_t>& ev; ~DoneGuard() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy (e); } } done_guard { lane_done };
-  for (auto& e : lane_done)
-    AWM_HIP_CHECK (hipEventCreateWithFlags (&e, hipEventDisableTiming));
+  Events ev_up, lane_done;                                 // lane_done: [half][lane], the lane is through the clips of that half
+  if (int rc = ev_up.create (2)) return rc;
+  if (int rc = lane_done.create (2 * size_t (n_lanes))) return rc;
   int rc = 0, last_half = -1;
   std::future<bool> next_built;
   struct FutureGuard { std::future<bool>& f; ~FutureGuard() { if (f.valid()) f.wait(); } } future_guard { next_built };     // (the task writes into the staging block)

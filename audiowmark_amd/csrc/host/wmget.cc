@@ -1,6 +1,7 @@
 #include "wmget.hh"
 #include "wmdecode.hh"
 #include "wmspeed.hh"
+#include "keytab_stage.hh"
 #include <atomic>
 #include <future>
 #include <chrono>
@@ -1576,7 +1577,7 @@ struct DeviceGroupTables
   size_t      cap = G;                   // keys per table area: a group (two areas in turn), or ALL keys of a call (one area)
   int         areas = 2;
   size_t      off_chain = 0, off_perm = 0, off_pos = 0, off_mf = 0, off_mu = 0, off_md = 0, off_ord = 0, off_rf = 0, off_want = 0, half_bytes = 0, pin_half = 0;
-  size_t aux_bytes() const { return 256 + cap * 176; }
+  size_t aux_bytes() const { return keytab_aux_layout (cap, false).bytes; }
   size_t want_bytes() const { return cap * NW * sizeof (int); }
 
   static bool
@@ -1632,26 +1633,15 @@ struct DeviceGroupTables
   launch (const std::vector<Key>& keys, int half)
   {
     unsigned char *aux = lane->pin_keytab.as<unsigned char>() + size_t (half) * pin_half;
-    std::memcpy (aux, Aes128::sbox(), 256);
-    for (size_t i = 0; i < keys.size(); i++)
-      {
-        Aes128 aes;
-        aes.set_key (keys[i].aes_key());
-        std::memcpy (aux + 256 + 176 * i, aes.round_keys(), 176);
-      }
+    const KeytabAux lay = keytab_aux_pack (aux, keys.size(), [&keys] (size_t i) { return keys[i].aes_key(); });
     unsigned char *d_aux = lane->ws_keytab_aux.as<unsigned char>() + size_t (half) * align256 (aux_bytes());
-    AWM_HIP_CHECK (hipMemcpyAsync (d_aux, aux, 256 + 176 * keys.size(), hipMemcpyHostToDevice, table_stream));
+    AWM_HIP_CHECK (hipMemcpyAsync (d_aux, aux, lay.bytes, hipMemcpyHostToDevice, table_stream));
     char *d = lane->ws_keytab.as<char>() + size_t (half) * half_bytes;
     // (one workgroup = one compute unit per key: LAUNCH keys per launch, the launches of a stream one after the other share the scratch)
     for (size_t k0 = 0; k0 < keys.size(); k0 += LAUNCH)
       {
         const size_t kn = std::min (LAUNCH, keys.size() - k0);
-        awmk::KeyTableArgs ka {};
-        ka.sbox = d_aux;
-        ka.round_keys = d_aux + 256 + 176 * k0;
-        ka.scratch = lane->ws_keytab_scratch.as<unsigned char>();
-        ka.scratch_slots = int (std::min (cap, LAUNCH));
-        ka.n_keys = (long long) kn;
+        const awmk::KeyTableArgs ka = keytab_args (d_aux, lay, k0, kn, lane->ws_keytab_scratch.as<unsigned char>(), std::min (cap, LAUNCH));
         awmk::ClipKeyTableOut o {};
         o.chains = reinterpret_cast<unsigned int *> (d + off_chain) + k0 * N_CHAIN;
         o.perm = reinterpret_cast<int *> (d + off_perm) + k0 * NW;

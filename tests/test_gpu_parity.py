@@ -598,6 +598,22 @@ def test_key_tables_on_the_device(gpu):
     assert all(gpu.torch.equal(a, b) for a, b in zip(host_side, device_side))
 
 
+def test_add_batch_keys_reuses_its_table_area_behind_4096_clips(gpu):
+    """awm_add_watermark_batch_keys_d in its default mode builds the tables of 4096 keys, watermarks their clips and begins again in the
+    same table area: clip 4096 reads slot 0.  4097 clips of one frame with a key each; the clips at the edges of the first launch of K16
+    (0, 255, 256) and of the table area (4095, 4096) equal one call per clip bit for bit."""
+    t = gpu.torch
+    n = 4097
+    x = gpu.dev(noise(3100, n * 1024, 2))
+    out = t.zeros_like(x)
+    keys = [gpu.awm.test_key(1 + i) for i in range(n)]
+    clips = [x[1024 * i:1024 * (i + 1)] for i in range(n)]
+    marked = gpu.ctx.add_watermark_batch_keys(keys, PAY1, clips, outs=[out[1024 * i:1024 * (i + 1)] for i in range(n)])
+    for i in (0, 255, 256, 4095, 4096):
+        assert t.equal(marked[i], gpu.ctx.add_watermark(keys[i], PAY1, clips[i])), i
+    assert not t.equal(marked[4096], clips[4096])
+
+
 def test_get_key_tables_on_the_device(gpu):
     """K16g (hip/keytab.hip): the tables `get` needs per key of a clip batch -- K5w's sync chains and row frames, the want list, K4s's
     gathered layout (perm, pos), the mix entries in shuffled order, the inverse bit order -- built on the device, group by group as the
