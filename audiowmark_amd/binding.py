@@ -258,6 +258,7 @@ lib.awm_resample_ratio_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c
 lib.awm_detect_speed_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp]
 lib.awm_speed_clip_location_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_int, _vp]
 lib.awm_speed_mags_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_size_t, _vp]
+lib.awm_var_resample_table.argtypes = [C.c_double, _vp, C.c_size_t, C.POINTER(C.c_int)]
 lib.awm_speed_scan_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
                                  _vp, C.c_int, C.c_size_t, _vp, _vp]
 
@@ -560,6 +561,17 @@ def tab_window(n=1024):
 def tab_synth_window():
     out = np.zeros(3072, np.float32)
     lib.awm_tab_synth_window(_np(out))
+    return out
+
+
+def var_resample_table(ratio):
+    """awm_var_resample_table: the coefficient table resample_ratio uses for `ratio`, [257][hl] float32 (pure host)."""
+    hl = C.c_int(0)
+    n = lib.awm_var_resample_table(float(ratio), None, 0, C.byref(hl))
+    _check(n, "awm_var_resample_table")
+    out = np.zeros((257, hl.value), np.float32)
+    assert n == out.size
+    _check(lib.awm_var_resample_table(float(ratio), _np(out), out.size, C.byref(hl)), "awm_var_resample_table")
     return out
 
 

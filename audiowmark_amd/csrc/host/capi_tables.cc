@@ -319,6 +319,23 @@ awm_speed_clip_candidates (const uint8_t key[16], const float *hashed_values, si
   return 0;
 }
 
+int
+awm_var_resample_table (double ratio, float *out, size_t max_floats, int *hl_out)
+{
+  int hl = 0;
+  const std::vector<float> tab = var_resample_table (ratio, &hl);
+  if (tab.empty())
+    {
+      set_error (string_printf ("failed to setup vresampler with ratio=%f", ratio));
+      return AWM_ERR_ARG;
+    }
+  if (hl_out)
+    *hl_out = hl;
+  if (out)
+    std::copy (tab.begin(), tab.begin() + std::min (tab.size(), max_floats), out);
+  return int (tab.size());
+}
+
 void
 awm_set_params (double water_delta, int mix, int frames_per_bit, int test_no_limiter,
                 double sync_threshold2, int n_best, double chunk_size_min)

@@ -409,6 +409,16 @@ var_resample_geometry (double ratio)
   return g;
 }
 
+std::vector<float>
+var_resample_table (double ratio, int *hl)
+{
+  const VarGeometry vg = var_geometry (ratio);
+  if (!vg.ok)
+    return {};
+  *hl = int (vg.hl);
+  return zita_table (vg.frel, vg.hl, 256);
+}
+
 int
 resample_var_device (awm_ctx *ctx, WorkLane *lane, const float *in_d, size_t n_in, int n_channels, double ratio, float *out_d, size_t n_out)
 {

@@ -93,6 +93,8 @@ struct VarResampleGeometry
   size_t stream_frames (size_t n_in) const { return size_t (((static_cast<unsigned __int128> (n_in) << shift) + mant - 1) / mant); }
 };
 VarResampleGeometry var_resample_geometry (double ratio);
+/* the dense coefficient table of that setup, 257 rows of hl floats (what get_var_tables pads and uploads); empty if the ratio is refused */
+std::vector<float> var_resample_table (double ratio, int *hl);
 /* n_out output frames of the VResampler stream for n_in input frames (zero extended) */
 int resample_var_device (awm_ctx *ctx, WorkLane *lane, const float *in_d, size_t n_in, int n_channels, double ratio, float *out_d, size_t n_out);
 

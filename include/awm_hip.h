@@ -740,7 +740,8 @@ int awm_ctx_set_helpers (awm_ctx *ctx, awm_ctx *const *helpers, int n_helpers);
  * wmcommon.hh:49-52); patterns found on the stretched stream carry the speed in awm_pattern.speed.
  * The stretch is zita-resampler's VResampler (resample.cc:96-125), restated like the fixed-ratio Resampler: bit parity
  * with the library is unpinned.  On the device the resampler's phase comes from the exact product instead of zita's
- * accumulated double (differs by its accumulated rounding only), so stretched PCM agrees to ~1e-7, not bit for bit. */
+ * accumulated double (differs by its accumulated rounding only): stretched PCM is bit-exact against the exact-phase restatement
+ * (tests/_speed.py var_resample32 on awm_var_resample_table) and agrees to ~1e-7 with zita's accumulated phase. */
 void awm_set_speed_params (int detect_speed, int detect_speed_patient, double try_speed, double test_speed);
 /* resample_ratio_truncate (resample.cc:96-119): frames the call produces / the call itself (out_d: n_out_frames frames) */
 size_t awm_resample_ratio_frames (size_t n_frames, int n_channels, int rate, double ratio, double max_in_seconds);
@@ -769,6 +770,10 @@ int    awm_speed_select_n_best (double *speed, double *quality, int count, int n
 double awm_speed_smooth_best (const double *speed, const double *quality, int count, double step, double distance);
 size_t awm_speed_clip_positions (const uint8_t key[16], size_t n_values, size_t max_out, uint64_t *positions);
 int    awm_speed_clip_candidates (const uint8_t key[16], const float *hashed_values, size_t n, int candidates, double *locations);
+/* the coefficient table awm_resample_ratio_d uses for `ratio` (VResampler::setup (ratio, nchan, 16): 257 phases x hl taps, dense, row
+ * major, before the padding of the device copy): returns its size 257 * *hl in floats and copies min (size, max_floats) of them to out
+ * (out may be null); < 0 if the ratio is refused (ratio < 1 / 16 or > 256) */
+int    awm_var_resample_table (double ratio, float *out, size_t max_floats, int *hl);
 
 /* A / B hooks for measurements (tools/gpu_variants.py): the previous formulation of two kernels stays selectable so that a change can be
  * timed against it in one process, on the same data, with the same clocks.  Results are bit-identical either way (tests).
