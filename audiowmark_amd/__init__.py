@@ -15,7 +15,8 @@ from .binding import (AwmError, Context, Pattern, lib, library_path, tab_up_down
                       PATTERN_DTYPE, set_add_payloads_fused, add_payloads_fused_in_use, ADD_PAYLOADS_TILE, set_payloads_file_tile,
                       set_add_payloads_rate_fused, add_payloads_rate_fused_in_use,
                       frame_mod_template, add_segments_fused_in_use, add_segment_plan, add_stream_rate_plan, get_batch_rates_plan, N_BANDS, BLOCK_FRAMES,
-                      add_watermark_segments_s16, add_watermark_segments_keys_s16)
+                      add_watermark_segments_s16, add_watermark_segments_keys_s16,
+                      set_speed_batch_bytes, speed_batch_bytes, set_speed_batch, speed_batch_plan, speed_batch_launches)
 from . import binding
 
 __all__ = ["AwmError", "Context", "Pattern", "lib", "library_path", "tab_up_down", "tab_bit_pos", "tab_mix_entries",
@@ -24,4 +25,5 @@ __all__ = ["AwmError", "Context", "Pattern", "lib", "library_path", "tab_up_down
            "PATTERN_DTYPE", "set_add_payloads_fused", "add_payloads_fused_in_use", "ADD_PAYLOADS_TILE", "set_payloads_file_tile", "binding",
            "set_add_payloads_rate_fused", "add_payloads_rate_fused_in_use",
            "frame_mod_template", "add_segments_fused_in_use", "add_segment_plan", "add_stream_rate_plan", "get_batch_rates_plan",
-           "N_BANDS", "BLOCK_FRAMES", "add_watermark_segments_s16", "add_watermark_segments_keys_s16"]
+           "N_BANDS", "BLOCK_FRAMES", "add_watermark_segments_s16", "add_watermark_segments_keys_s16",
+           "set_speed_batch_bytes", "speed_batch_bytes", "set_speed_batch", "speed_batch_plan", "speed_batch_launches"]

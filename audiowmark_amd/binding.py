@@ -256,6 +256,18 @@ lib.awm_resample_ratio_frames.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_doub
 lib.awm_resample_ratio_frames.restype = C.c_size_t
 lib.awm_resample_ratio_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, _vp, C.c_size_t]
 lib.awm_detect_speed_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp]
+lib.awm_detect_speed_batch_d.argtypes = [_vp, _vp, C.c_int, C.c_size_t, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
+lib.awm_debug_set_speed_batch_bytes.argtypes = [C.c_size_t]
+lib.awm_debug_set_speed_batch_bytes.restype = None
+lib.awm_debug_speed_batch_bytes.argtypes = []
+lib.awm_debug_speed_batch_bytes.restype = C.c_size_t
+lib.awm_debug_set_speed_batch.argtypes = [C.c_int]
+lib.awm_debug_set_speed_batch.restype = None
+lib.awm_speed_batch_plan.argtypes = [C.c_size_t, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t, _vp, _vp]
+lib.awm_debug_speed_batch_launches.argtypes = [_vp, _vp, _vp, _vp]
+lib.awm_debug_speed_batch_launches.restype = None
+lib.awm_debug_speed_scan_batch_d.argtypes = [_vp, _vp, C.c_int, C.c_size_t, _vp, _vp, C.c_int, C.c_int, _vp, C.c_double, C.c_double, C.c_int, C.c_int,
+                                             _vp, _vp, C.c_size_t, _vp, _vp, _vp]
 lib.awm_speed_clip_location_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_int, _vp]
 lib.awm_speed_mags_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_size_t, _vp]
 lib.awm_var_resample_table.argtypes = [C.c_double, _vp, C.c_size_t, C.POINTER(C.c_int)]
@@ -333,6 +345,38 @@ def set_params(water_delta=0.01, mix=True, frames_per_bit=2, test_no_limiter=Fal
 def set_speed_params(detect_speed=False, patient=False, try_speed=-1.0, test_speed=-1.0):
     """--detect-speed / --detect-speed-patient / --try-speed / --test-speed of `get` (reference wmcommon.hh:49-52)."""
     lib.awm_set_speed_params(int(detect_speed), int(patient), float(try_speed), float(test_speed))
+
+
+def set_speed_batch_bytes(n_bytes=0):
+    """awm_debug_set_speed_batch_bytes: scratch budget of a sub-group of the batched speed search (0: the default)"""
+    lib.awm_debug_set_speed_batch_bytes(int(n_bytes))
+
+
+def speed_batch_bytes():
+    """awm_debug_speed_batch_bytes: the scratch budget of a sub-group in force"""
+    return int(lib.awm_debug_speed_batch_bytes())
+
+
+def set_speed_batch(mode=0):
+    """awm_debug_set_speed_batch, the clip batches under a speed parameter: 0 (the default) every clip over the lanes with the one-clip
+    search; 1 the searches of the short clips as a batch; 2 one clip after the other on the context's lane (the measurement's baseline)"""
+    lib.awm_debug_set_speed_batch(int(mode))
+
+
+def speed_batch_plan(n_frames, n_channels=2, rate=44100, patient=False, budget_bytes=0):
+    """awm_speed_batch_plan (no GPU needed): (sub-group of every clip, -1 = under 0.25 s; bytes of every sub-group's first pass)"""
+    n = len(n_frames)
+    frames = (C.c_size_t * max(n, 1))(*[int(f) for f in n_frames])
+    group, nbytes = (C.c_int * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    g = _check(lib.awm_speed_batch_plan(n, frames, n_channels, rate, int(patient), int(budget_bytes), group, nbytes), "awm_speed_batch_plan")
+    return [int(group[i]) for i in range(n)], [int(nbytes[i]) for i in range(g)]
+
+
+def speed_batch_launches():
+    """awm_debug_speed_batch_launches: launches of the batch forms of (K12, K13, K14, K15) in this process so far"""
+    k = [C.c_int(0) for _ in range(4)]
+    lib.awm_debug_speed_batch_launches(*[C.byref(x) for x in k])
+    return tuple(x.value for x in k)
 
 
 def plan_chunks(n_frames):
@@ -1198,6 +1242,50 @@ class Context:
         if rc < 0:
             _check(rc, "awm_detect_speed_d")
         return (speed.value if rc else None), speed.value, quality.value
+
+    @staticmethod
+    def _speed_batch_args(key_or_keys, clips):
+        per_clip = isinstance(key_or_keys, (list, tuple))
+        if per_clip:
+            assert len(key_or_keys) == len(clips)
+            keys = b"".join(key_bytes(k) for k in key_or_keys)
+        else:
+            keys = key_bytes(key_or_keys)
+        shapes = [_pcm_shape(c) for c in clips]
+        ch = shapes[0][1]
+        assert all(s[1] == ch for s in shapes)
+        ptrs = (C.c_void_p * len(clips))(*[_dev_ptr(c) if c.numel() else None for c in clips])
+        frames = (C.c_size_t * len(clips))(*[s[0] for s in shapes])
+        return keys, int(per_clip), ptrs, frames, ch
+
+    def detect_speed_batch(self, key_or_keys, clips, patient=False, rate=44100):
+        """awm_detect_speed_batch_d: detect_speed for many resident clips (one key, or a list with a key per clip) with the passes of the
+        search in lockstep -> one (speed to try or None, best speed, best quality) per clip, equal to detect_speed on that clip; a
+        clip on which detect_speed raises has its negative error code in place of the first element."""
+        if not clips:
+            return []
+        keys, per_clip, ptrs, frames, ch = self._speed_batch_args(key_or_keys, clips)
+        n = len(clips)
+        speed, quality, use = np.zeros(n), np.zeros(n), np.zeros(n, np.int32)
+        _check(lib.awm_detect_speed_batch_d(self._h, keys, per_clip, n, ptrs, frames, ch, rate, int(patient), _np(speed), _np(quality), _np(use)),
+               "awm_detect_speed_batch_d")
+        return [((int(use[i]) if use[i] < 0 else float(speed[i]) if use[i] else None), float(speed[i]), float(quality[i])) for i in range(n)]
+
+    def speed_scan_batch(self, key_or_keys, clips, clip_locations, seconds, step, n_steps, n_center_steps, speeds, rate=44100):
+        """awm_debug_speed_scan_batch_d: speed_scan for many clips in one launch per kernel; speeds[i] = the list of clip i -> one
+        (speeds, qualities) per clip"""
+        keys, per_clip, ptrs, frames, ch = self._speed_batch_args(key_or_keys, clips)
+        n = len(clips)
+        loc = np.ascontiguousarray(clip_locations, np.float64)
+        counts = np.array([len(s) for s in speeds], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(s, np.float64) for s in speeds]) if n else [], np.float64)
+        cap = max(int(counts.max()) * (2 * n_center_steps + 1) * (2 * n_steps + 1), 1)
+        o_s, o_q, n_out = np.zeros((n, cap)), np.zeros((n, cap)), np.zeros(n, np.int32)
+        _check(lib.awm_debug_speed_scan_batch_d(self._h, keys, per_clip, n, ptrs, frames, ch, rate, _np(loc), seconds, step, n_steps, n_center_steps,
+                                                _np(flat), _np(counts), cap, _np(o_s), _np(o_q), _np(n_out)), "awm_debug_speed_scan_batch_d")
+        for c in n_out:
+            _check(int(c), "awm_debug_speed_scan_batch_d (a clip)")
+        return [(o_s[i, :n_out[i]].copy(), o_q[i, :n_out[i]].copy()) for i in range(n)]
 
     def speed_clip_location(self, key, pcm, seconds, candidates=5, rate=44100):
         n, ch = _pcm_shape(pcm)

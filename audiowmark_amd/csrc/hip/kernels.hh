@@ -671,6 +671,15 @@ struct SpeedCenterDev
   long long          n_out;        // output frames
   int                rows;         // K13 / K14: STFT rows of the half-rate clip
 };
+/* batch forms of K12 - K14 (..._batch_kernel): an entry of the launch is a (clip, centre) pair; entry e has centers[e] (n_in, n_out and rows
+ * of its clip) and entries[e]: what the one-clip launch holds once in its arguments */
+struct SpeedEntryDev
+{
+  const float         *in;           // K12: the clip
+  const unsigned int  *cols;         // K13: column table of the clip's key
+  const int           *col_frame;    // K14
+  const unsigned char *col_first;    // K14
+};
 /* K12: VResampler (resample.cc:96-125); blockIdx.y = centre, outputs at out + centre * out_stride */
 struct VarResampleArgs
 {
@@ -683,7 +692,9 @@ struct VarResampleArgs
   double                max_step;      // largest advance of the input window per output among the centres, in frames (mant / 2^shift); 0: unknown
   int                   lds_floats;    // set by the launcher
 };
-hipError_t launch_resample_var (hipStream_t st, const VarResampleArgs& a, long long max_n_out, int n_centers);
+/* entries != nullptr: the batch form (a.in unused); entries_aligned: every clip of the launch is on an 8 byte address */
+hipError_t launch_resample_var (hipStream_t st, const VarResampleArgs& a, long long max_n_out, int n_centers,
+                                const SpeedEntryDev *entries = nullptr, bool entries_aligned = false);
 
 /* K13: SpeedSync::prepare_mags (wmspeed.cc:204-268) */
 struct SpeedMagsArgs
@@ -697,7 +708,8 @@ struct SpeedMagsArgs
   float2               *mags;          // [centre][510][ld] (umag, dmag)
   long long             mags_center_stride, ld;
 };
-hipError_t launch_speed_mags (hipStream_t st, const DevTables& t, const SpeedMagsArgs& a, int max_rows, int n_centers);
+hipError_t launch_speed_mags (hipStream_t st, const DevTables& t, const SpeedMagsArgs& a, int max_rows, int n_centers,
+                              const SpeedEntryDev *entries = nullptr /* batch form: a.cols unused */);
 
 /* K14: SpeedSync::compare (wmspeed.cc:270-395) */
 struct SpeedItemDev { int center; double rel_speed_inv, q16_scale; };
@@ -715,11 +727,17 @@ struct SpeedCompareArgs
   unsigned long long   *best;          // [items] bits of the best quality (zero initialised)
   int                   fold_groups = 0, n_ranges = 0;   // set by the launcher: groups of speeds folded into blockIdx.x (see launch_speed_compare)
 };
-hipError_t launch_speed_compare (hipStream_t st, const SpeedCompareArgs& a, int n_items);
+hipError_t launch_speed_compare (hipStream_t st, const SpeedCompareArgs& a, int n_items,
+                                 const SpeedEntryDev *entries = nullptr /* batch form: a.col_frame, a.col_first unused */);
 
 /* K15 */
 constexpr int ENERGY_PARTS = 256;
 hipError_t launch_gather_values (hipStream_t st, const float *in, const unsigned long long *pos, long long n, float *out);
 hipError_t launch_energy (hipStream_t st, const float *in, const long long *range /* [n][2] value index begin, end */, int n_ranges,
                           double *out /* [n][ENERGY_PARTS] */);
+/* batch forms: positions / values of clip c at [first, first + n) of pos / out; a range carries its clip's base pointer */
+struct GatherClipDev  { const float *in; long long first, n; };
+struct EnergyRangeDev { const float *in; long long begin, end; };
+hipError_t launch_gather_values_batch (hipStream_t st, const GatherClipDev *clips, int n_clips, long long max_n, const unsigned long long *pos, float *out);
+hipError_t launch_energy_batch (hipStream_t st, const EnergyRangeDev *range, int n_ranges, double *out /* [n][ENERGY_PARTS] */);
 }

@@ -12,6 +12,7 @@
 #include "kernels.hh"
 #include "awm_fft.hip.h"
 #include <algorithm>
+#include <atomic>
 
 namespace awmk {
 
@@ -141,58 +142,29 @@ constexpr int RV_MAX_SPAN = 4096;         // input frames of a staged window (32
 template<int CT> __global__ void __launch_bounds__ (256)
 resample_var_kernel (VarResampleArgs a, int tiles_per_wg, int in_span)
 {
-  extern __shared__ float s_tab[];                           // lds_floats: sized for the largest table of the launch (occupancy); then the window
-  const SpeedCenterDev cd = a.centers[blockIdx.y];
-  if ((long long) blockIdx.x * tiles_per_wg * RV_TILE >= cd.n_out)
-    return;
-  const int stride = cd.stride, n_tab = 257 * stride;
-  const bool in_lds = n_tab <= a.lds_floats;
-  const bool staged = CT == 2 && in_lds && in_span > 0;
-  float2 *s_in = reinterpret_cast<float2 *> (s_tab + ((a.lds_floats + 1) & ~1));
-  if (in_lds)
-    for (int i = threadIdx.x; i < n_tab; i += blockDim.x)
-      s_tab[i] = cd.ctab[i];
-  float *out = a.out + blockIdx.y * a.out_stride;
-  for (int t = 0; t < tiles_per_wg; t++)
-    {
-      const long long tile0 = ((long long) blockIdx.x * tiles_per_wg + t) * RV_TILE;
-      if (tile0 >= cd.n_out)
-        break;                                                                 // (uniform)
-      long long first0 = 0;
-      if (staged)
-        {
-          first0 = var_phase (cd, tile0).first;                                // window starts do not decrease with m
-          if (t)
-            __syncthreads();                                                   // the previous tile's windows have been read
-          const float2 *in2 = reinterpret_cast<const float2 *> (a.in);
-          for (int i = threadIdx.x; i < in_span; i += 256)
-            {
-              const long long j = first0 + i;
-              s_in[i] = (j >= 0 && j < cd.n_in) ? in2[j] : make_float2 (0.f, 0.f);
-            }
-        }
-      if (in_lds && (staged || t == 0))
-        __syncthreads();
-      for (int q = 0; q < RV_TILE / 256; q++)
-        {
-          const long long m = tile0 + q * 256 + threadIdx.x;
-          if (m >= cd.n_out)
-            break;
-          if (staged)
-            {
-              const VarPhase v = var_phase (cd, m);
-              const long long rel = v.first - first0;
-              if (rel >= 0 && rel + 2 * cd.hl <= in_span)                      // (always, by the launcher's bound; kept as a guard)
-                var_output_staged (cd, s_tab, stride, v, s_in + rel, m, out);
-              else
-                var_output<CT> (cd, s_tab, stride, a.in, a.n_channels, m, out);
-            }
-          else if (in_lds)                                       // two copies of the loop: ds_read vs global_load addressing
-            var_output<CT> (cd, s_tab, stride, a.in, a.n_channels, m, out);
-          else
-            var_output<CT> (cd, cd.ctab, stride, a.in, a.n_channels, m, out);
-        }
-    }
+#define RV_IN a.in
+#include "speed_resample_var_body.inc"
+#undef RV_IN
+}
+
+/* batch form: blockIdx.y = (clip, centre) pair; the pair's clip comes from entries[blockIdx.y], its n_in from its SpeedCenterDev as before */
+template<int CT> __global__ void __launch_bounds__ (256)
+resample_var_batch_kernel (VarResampleArgs a, int tiles_per_wg, int in_span, const SpeedEntryDev *entries)
+{
+  const float *const in_b = entries[blockIdx.y].in;
+#define RV_IN in_b
+#include "speed_resample_var_body.inc"
+#undef RV_IN
+}
+
+std::atomic<int> g_speed_batch_launches[4];                  // K12, K13, K14, K15 in their batch forms
+extern "C" void
+awm_debug_speed_batch_launches (int *k12, int *k13, int *k14, int *k15)
+{
+  int *out[4] = { k12, k13, k14, k15 };
+  for (int i = 0; i < 4; i++)
+    if (out[i])
+      *out[i] = g_speed_batch_launches[i].load();
 }
 
 /* (measurement knob) bit 0: the stereo input window of a tile through LDS | bit 1: a workgroup keeps its table for several tiles.
@@ -204,7 +176,7 @@ int g_resample_var_mode = 2;
 extern "C" void awm_debug_set_resample_var_mode (int mode) { g_resample_var_mode = mode; }
 
 hipError_t
-launch_resample_var (hipStream_t st, const VarResampleArgs& args, long long max_n_out, int n_centers)
+launch_resample_var (hipStream_t st, const VarResampleArgs& args, long long max_n_out, int n_centers, const SpeedEntryDev *entries, bool entries_aligned)
 {
   if (max_n_out <= 0 || n_centers <= 0)
     return hipSuccess;
@@ -216,14 +188,24 @@ launch_resample_var (hipStream_t st, const VarResampleArgs& args, long long max_
   const long long n_tiles = (max_n_out + RV_TILE - 1) / RV_TILE;
   const int tiles_per_wg = (g_resample_var_mode & 2) ? int (std::min<long long> (16, std::max<long long> (1, n_tiles * n_centers / 4096))) : 1;   // >= 4096 workgroups first
   const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg), unsigned (n_centers));
-  const bool aligned = (reinterpret_cast<uintptr_t> (a.in) & 7) == 0 && (reinterpret_cast<uintptr_t> (a.out) & 7) == 0 && (a.out_stride & 1) == 0;
+  // (batch form: the caller has looked at every clip of the launch; one clip on a 4 byte address sends the whole launch through <0>)
+  const bool in_aligned = entries ? entries_aligned : (reinterpret_cast<uintptr_t> (a.in) & 7) == 0;
+  const bool aligned = in_aligned && (reinterpret_cast<uintptr_t> (a.out) & 7) == 0 && (a.out_stride & 1) == 0;
   // input frames the outputs of a tile read: the window start moves by floor ((RV_TILE - 1) * max_step) + 1 at most (+ 1: var_phase's
   // round-up case), plus one window (2 hl <= 2 max_stride)
   const long long span = (long long) ((RV_TILE - 1) * a.max_step) + 3 + 2LL * a.max_stride;
   const bool stage = (g_resample_var_mode & 1) && a.n_channels == 2 && aligned && a.lds_floats > 0 && a.max_step > 0 && span <= RV_MAX_SPAN;
   const int in_span = stage ? int (span) : 0;
   const size_t lds_bytes = size_t ((a.lds_floats + 1) & ~1) * sizeof (float) + size_t (in_span) * sizeof (float2);
-  if (a.n_channels == 2 && aligned)
+  if (entries)
+    {
+      g_speed_batch_launches[0]++;
+      if (a.n_channels == 2 && aligned)
+        hipLaunchKernelGGL (resample_var_batch_kernel<2>, grid, dim3 (256), lds_bytes, st, a, tiles_per_wg, in_span, entries);
+      else
+        hipLaunchKernelGGL (resample_var_batch_kernel<0>, grid, dim3 (256), lds_bytes, st, a, tiles_per_wg, in_span, entries);
+    }
+  else if (a.n_channels == 2 && aligned)
     hipLaunchKernelGGL (resample_var_kernel<2>, grid, dim3 (256), lds_bytes, st, a, tiles_per_wg, in_span);
   else
     hipLaunchKernelGGL (resample_var_kernel<0>, grid, dim3 (256), lds_bytes, st, a, tiles_per_wg, in_span);
@@ -248,106 +230,31 @@ typedef const unsigned int __attribute__ ((address_space (4))) *const_uint_ptr;
 __global__ void __launch_bounds__ (256)
 speed_mags_kernel (DevTables t, SpeedMagsArgs a)
 {
-  __shared__ float2 s_tw[512];
-  __shared__ float  s_win[512];
-  __shared__ float2 s_x[4][XBUF_ELEMS];
-  __shared__ float  s_db[SPEED_TILE * SPEED_NB];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const SpeedCenterDev cd = a.centers[blockIdx.y];
-  const int row0 = blockIdx.x * SPEED_TILE;
-  if (row0 >= cd.rows)
-    return;
-  fft512_load_twiddles (t.tw512, s_tw);
-  for (int i = threadIdx.x; i < 512; i += blockDim.x)
-    s_win[i] = a.window512[i];
-  __syncthreads();
+#define SM_COLS a.cols
+#include "speed_mags_body.inc"
+#undef SM_COLS
+}
 
-  const int C = a.n_channels;
-  const float *sub = a.sub + blockIdx.y * a.sub_stride;
-  float2 *xbuf = s_x[wave];
-  for (int r = wave; r < SPEED_TILE; r += 4)
-    {
-      const int row = row0 + r;
-      if (row >= cd.rows)
-        break;
-      const long long pos = (long long) row * 128;
-      float acc0 = 0.f, acc1 = 0.f;                            // bands 20 + lane, 84 + lane
-      for (int c0 = 0; c0 < C; c0 += 2)
-        {
-          const bool two = c0 + 1 < C;
-          float2 z[8];
-          bool nz0 = false, nz1 = false;
-#pragma unroll
-          for (int j = 0; j < 8; j++)
-            {
-              const int n = lane + 64 * j;
-              const float x0 = sub[(pos + n) * C + c0];
-              const float x1 = two ? sub[(pos + n) * C + c0 + 1] : 0.f;
-              nz0 |= x0 != 0.f;
-              nz1 |= x1 != 0.f;
-              z[j] = make_float2 (__fmul_rn (x0, s_win[n]), __fmul_rn (x1, s_win[n]));
-            }
-          const bool live0 = __any (nz0), live1 = __any (nz1);
-          fft512_forward (z, xbuf, s_tw, lane);
-          xbuf[0 * 64 + lane] = z[0];
-          xbuf[1 * 64 + lane] = z[1];
-          xbuf[6 * 64 + lane] = z[6];
-          xbuf[7 * 64 + lane] = z[7];
-          wave_sync();
-#pragma unroll
-          for (int part = 0; part < 2; part++)
-            {
-              const int k = SPEED_MIN_BAND + 64 * part + lane;
-              if (k <= 100)
-                {
-                  const float2 zk = xbuf[zpos (k)], zm = xbuf[zpos (512 - k)];
-                  const float2 xa = make_float2 (0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-                  const float2 xb = make_float2 (0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-                  float v = part ? acc1 : acc0;
-                  v = __fadd_rn (v, live0 ? db_from_complex (xa) : -96.f);
-                  if (two)
-                    v = __fadd_rn (v, live1 ? db_from_complex (xb) : -96.f);
-                  if (part)
-                    acc1 = v;
-                  else
-                    acc0 = v;
-                }
-            }
-          wave_sync();
-        }
-      s_db[r * SPEED_NB + lane] = acc0;
-      if (lane < SPEED_NB - 64)
-        s_db[r * SPEED_NB + 64 + lane] = acc1;
-    }
-  __syncthreads();
-
-  float2 *mags = a.mags + blockIdx.y * a.mags_center_stride;
-  const float *db = s_db + lane * SPEED_NB;                    // this lane's row of the tile
-  const bool store = row0 + lane < cd.rows;
-  const_uint_ptr cols = (const_uint_ptr) a.cols;
-  for (int col = __builtin_amdgcn_readfirstlane (wave); col < SPEED_COLS; col += 4)
-    {
-      unsigned int cw[15];
-#pragma unroll
-      for (int i = 0; i < 15; i++)
-        cw[i] = cols[col * 16 + i];
-      float u = 0.f, d = 0.f;
-#pragma unroll
-      for (int i = 0; i < 30; i++)
-        u = __fadd_rn (u, db[(cw[i >> 2] >> (8 * (i & 3))) & 0xff]);
-#pragma unroll
-      for (int i = 30; i < 60; i++)
-        d = __fadd_rn (d, db[(cw[i >> 2] >> (8 * (i & 3))) & 0xff]);
-      if (store)
-        mags[(long long) col * a.ld + row0 + lane] = make_float2 (u, d);
-    }
+/* batch form: blockIdx.y = (clip, centre) pair with the column table of its clip's key; sub and mags keep one stride per launch */
+__global__ void __launch_bounds__ (256)
+speed_mags_batch_kernel (DevTables t, SpeedMagsArgs a, const SpeedEntryDev *entries)
+{
+#define SM_COLS entries[blockIdx.y].cols
+#include "speed_mags_body.inc"
+#undef SM_COLS
 }
 
 hipError_t
-launch_speed_mags (hipStream_t st, const DevTables& t, const SpeedMagsArgs& a, int max_rows, int n_centers)
+launch_speed_mags (hipStream_t st, const DevTables& t, const SpeedMagsArgs& a, int max_rows, int n_centers, const SpeedEntryDev *entries)
 {
   if (max_rows <= 0 || n_centers <= 0)
     return hipSuccess;
+  if (entries)
+    {
+      g_speed_batch_launches[1]++;
+      hipLaunchKernelGGL (speed_mags_batch_kernel, dim3 (unsigned ((max_rows + SPEED_TILE - 1) / SPEED_TILE), unsigned (n_centers)), dim3 (256), 0, st, t, a, entries);
+      return hipGetLastError();
+    }
   hipLaunchKernelGGL (speed_mags_kernel, dim3 (unsigned ((max_rows + SPEED_TILE - 1) / SPEED_TILE), unsigned (n_centers)), dim3 (256), 0, st, t, a);
   return hipGetLastError();
 }
@@ -366,9 +273,18 @@ launch_speed_mags (hipStream_t st, const DevTables& t, const SpeedMagsArgs& a, i
  * gathers of a column hit the same cache lines, so the matrix is read from HBM once per NS speeds.  (One workgroup per
  * (speed, state range) read 11.7 GB for 1 GB of matrices in the first pass and ran at HBM speed: 1.56 ms.)
  * ------------------------------------------------------------------------------------------------------------------ */
-template<int NS> __global__ void __launch_bounds__ (256)
-speed_compare_kernel (SpeedCompareArgs a)
+template<int NS, bool BATCH> __device__ __forceinline__ void
+speed_compare_body (SpeedCompareArgs a, const SpeedEntryDev *entries)
 {
+  const int *col_frame_b = nullptr;
+  const unsigned char *col_first_b = nullptr;
+  if constexpr (BATCH)
+    {
+      col_frame_b = entries[blockIdx.y].col_frame;
+      col_first_b = entries[blockIdx.y].col_first;
+    }
+  const auto col_frame = [&] { if constexpr (BATCH) return col_frame_b; else return a.col_frame; };
+  const auto col_first = [&] { if constexpr (BATCH) return col_first_b; else return a.col_first; };
   constexpr int BIT_COLS = 3 * 85;                             // columns of one sync bit in the three blocks
   __shared__ int2   s_fo[NS][BIT_COLS];                        // frame offsets in Q16 (whole rows x 8, fraction) of the current bit
   __shared__ double s_best[NS][4];
@@ -435,7 +351,7 @@ speed_compare_kernel (SpeedCompareArgs a)
         {
           const int k = e / BIT_COLS, c = e - k * BIT_COLS;
           const int block = c / 85, j = c - block * 85;
-          const int steps = (block * a.frames_per_block + a.col_frame[bit * a.rows_per_bit + j]) * a.steps_per_frame;
+          const int steps = (block * a.frames_per_block + col_frame()[bit * a.rows_per_bit + j]) * a.steps_per_frame;
           double v = steps * items[k < ns ? k : 0].rel_speed_inv;
           v = v + 0.5;
           v = v * 65536.0;
@@ -453,7 +369,7 @@ speed_compare_kernel (SpeedCompareArgs a)
         }
       if (active)
         {
-          const unsigned char *first = a.col_first + bit * (a.frames_per_block + 2);
+          const unsigned char *first = col_first() + bit * (a.frames_per_block + 2);
           const float2 *mc = mags + (long long) bit * a.rows_per_bit * a.ld;
           for (int block = 0; block < 3; block++)
             {
@@ -552,6 +468,19 @@ speed_compare_kernel (SpeedCompareArgs a)
     }
 }
 
+template<int NS> __global__ void __launch_bounds__ (256)
+speed_compare_kernel (SpeedCompareArgs a)
+{
+  speed_compare_body<NS, false> (a, nullptr);
+}
+
+/* batch form: blockIdx.y = (clip, centre) pair over all clips of the launch, with the frame tables of its clip's key */
+template<int NS> __global__ void __launch_bounds__ (256)
+speed_compare_batch_kernel (SpeedCompareArgs a, const SpeedEntryDev *entries)
+{
+  speed_compare_body<NS, true> (a, entries);
+}
+
 // (A / B, tools/gpu_speed_compare_ab.py, round 6: 1 = all 11 relative speeds of a centre in one thread -- the matrix gathered once, but 179
 // registers = two waves per SIMD for a kernel that lives on the latency of its gathers: 0.482 against 0.447 ms per launch; off)
 int g_speed_compare_wide = 0;
@@ -561,13 +490,24 @@ extern "C" void awm_debug_set_speed_compare_wide (int on) { g_speed_compare_wide
 int g_speed_compare_fold = 1;
 extern "C" void awm_debug_set_speed_compare_fold (int on) { g_speed_compare_fold = on; }
 
+template<int NS> static void
+compare_launch (dim3 grid, hipStream_t st, const SpeedCompareArgs& a, const SpeedEntryDev *entries)
+{
+  if (entries)
+    hipLaunchKernelGGL (speed_compare_batch_kernel<NS>, grid, dim3 (256), 0, st, a, entries);
+  else
+    hipLaunchKernelGGL (speed_compare_kernel<NS>, grid, dim3 (256), 0, st, a);
+}
+
 hipError_t
-launch_speed_compare (hipStream_t st, const SpeedCompareArgs& a, int n_items)
+launch_speed_compare (hipStream_t st, const SpeedCompareArgs& a, int n_items, const SpeedEntryDev *entries)
 {
   if (n_items <= 0 || a.n_centers <= 0 || a.items_per_center <= 0)
     return hipSuccess;
   if (a.rows_per_bit != 85 || n_items != a.n_centers * a.items_per_center)
     return hipErrorInvalidValue;
+  if (entries)
+    g_speed_batch_launches[2]++;
   const unsigned ranges = unsigned ((a.pad_start + 255) / 256);
   const int per = a.items_per_center;
   // six speeds per thread where that still leaves enough workgroups to fill the chip (the first pass: 57 centres x 11 or 23
@@ -577,18 +517,18 @@ launch_speed_compare (hipStream_t st, const SpeedCompareArgs& a, int n_items)
   // matrix is then gathered once instead of once per group of six (round 5's counters: 2.18 GB fetched per launch for 1.0 GB of
   // matrices, the two groups of a centre run on different XCDs)
   if (g_speed_compare_wide && per > 6 && per <= 12 && (long long) ranges * a.n_centers >= 1024)
-    hipLaunchKernelGGL (speed_compare_kernel<12>, dim3 (ranges, unsigned (a.n_centers), 1), dim3 (256), 0, st, a);
+    compare_launch<12> (dim3 (ranges, unsigned (a.n_centers), 1), st, a, entries);
   else if ((long long) ranges * a.n_centers * groups6 >= 1024 && g_speed_compare_fold && groups6 > 1)
     {
       SpeedCompareArgs f = a;
       f.fold_groups = int (groups6);
       f.n_ranges = int (ranges);
-      hipLaunchKernelGGL (speed_compare_kernel<6>, dim3 ((ranges + 7) / 8 * 8 * groups6, unsigned (a.n_centers), 1), dim3 (256), 0, st, f);
+      compare_launch<6> (dim3 ((ranges + 7) / 8 * 8 * groups6, unsigned (a.n_centers), 1), st, f, entries);
     }
   else if ((long long) ranges * a.n_centers * groups6 >= 1024)
-    hipLaunchKernelGGL (speed_compare_kernel<6>, dim3 (ranges, unsigned (a.n_centers), groups6), dim3 (256), 0, st, a);
+    compare_launch<6> (dim3 (ranges, unsigned (a.n_centers), groups6), st, a, entries);
   else
-    hipLaunchKernelGGL (speed_compare_kernel<1>, dim3 (ranges, unsigned (a.n_centers), unsigned (per)), dim3 (256), 0, st, a);
+    compare_launch<1> (dim3 (ranges, unsigned (a.n_centers), unsigned (per)), st, a, entries);
   return hipGetLastError();
 }
 
@@ -615,11 +555,54 @@ launch_gather_values (hipStream_t st, const float *in, const unsigned long long 
   return hipGetLastError();
 }
 
+/* batch form: blockIdx.y = clip; its positions and values are pos / out [first, first + n) */
+__global__ void __launch_bounds__ (256)
+gather_values_batch_kernel (const GatherClipDev *clips, const unsigned long long *pos, float *out)
+{
+  const GatherClipDev c = clips[blockIdx.y];
+  const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < c.n)
+    out[c.first + i] = c.in[pos[c.first + i]];
+}
+
+hipError_t
+launch_gather_values_batch (hipStream_t st, const GatherClipDev *clips, int n_clips, long long max_n, const unsigned long long *pos, float *out)
+{
+  if (n_clips <= 0 || max_n <= 0)
+    return hipSuccess;
+  g_speed_batch_launches[3]++;
+  hipLaunchKernelGGL (gather_values_batch_kernel, dim3 (unsigned ((max_n + 255) / 256), unsigned (n_clips)), dim3 (256), 0, st, clips, pos, out);
+  return hipGetLastError();
+}
+
 __global__ void __launch_bounds__ (256)
 energy_kernel (const float *in, const long long *range, double *out)
 {
   __shared__ double s_part[4];
   const long long begin = range[2 * blockIdx.y], end = range[2 * blockIdx.y + 1];
+  double e = 0;
+  for (long long i = begin + (long long) blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (long long) gridDim.x * blockDim.x)
+    {
+      const float s = in[i];
+      e += double (__fmul_rn (s, s));
+    }
+  for (int o = 32; o > 0; o >>= 1)
+    e += __shfl_xor (e, o);
+  if ((threadIdx.x & 63) == 0)
+    s_part[threadIdx.x >> 6] = e;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    out[blockIdx.y * gridDim.x + blockIdx.x] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+}
+
+/* batch form: blockIdx.y = candidate range of any clip, with that clip's base pointer; the same ENERGY_PARTS partial sums per range, in
+ * the same order (the loop is energy_kernel's, restated: as one shared function the one-clip kernel took other scalar registers) */
+__global__ void __launch_bounds__ (256)
+energy_batch_kernel (const EnergyRangeDev *range, double *out)
+{
+  __shared__ double s_part[4];
+  const float *in = range[blockIdx.y].in;
+  const long long begin = range[blockIdx.y].begin, end = range[blockIdx.y].end;
   double e = 0;
   for (long long i = begin + (long long) blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (long long) gridDim.x * blockDim.x)
     {
@@ -642,6 +625,16 @@ launch_energy (hipStream_t st, const float *in, const long long *range, int n_ra
   if (n_ranges <= 0)
     return hipSuccess;
   hipLaunchKernelGGL (energy_kernel, dim3 (ENERGY_PARTS, unsigned (n_ranges)), dim3 (256), 0, st, in, range, out);
+  return hipGetLastError();
+}
+
+hipError_t
+launch_energy_batch (hipStream_t st, const EnergyRangeDev *range, int n_ranges, double *out)
+{
+  if (n_ranges <= 0)
+    return hipSuccess;
+  g_speed_batch_launches[3]++;
+  hipLaunchKernelGGL (energy_batch_kernel, dim3 (ENERGY_PARTS, unsigned (n_ranges)), dim3 (256), 0, st, range, out);
   return hipGetLastError();
 }
 

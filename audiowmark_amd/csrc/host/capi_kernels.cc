@@ -5084,4 +5084,125 @@ awm_detect_speed_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, siz
   return results.empty() ? 0 : 1;
 }
 
+/* ---- batches of clips ---- */
+namespace {
+// the checks the batch entry points share: AWM_ERR_ARG before anything is enqueued or written
+int
+speed_batch_args (const char *what, const uint8_t *keys, size_t n_clips, const float *const *pcm_d, const size_t *n_frames, int n_channels, int rate)
+{
+  bool bad = n_channels < 1 || rate <= 0 || (n_clips && (!keys || !pcm_d || !n_frames));
+  for (size_t i = 0; i < n_clips && !bad; i++)
+    bad = !pcm_d[i] && n_frames[i] > 0;
+  if (bad)
+    {
+      set_error (std::string (what) + ": bad argument");
+      return AWM_ERR_ARG;
+    }
+  return 0;
+}
+}
+
+void
+awm_debug_set_speed_batch_bytes (size_t bytes)
+{
+  speed_batch_set_bytes (bytes);
+}
+
+size_t
+awm_debug_speed_batch_bytes (void)
+{
+  return speed_batch_bytes();
+}
+
+int
+awm_speed_batch_plan (size_t n_clips, const size_t *n_frames, int n_channels, int rate, int patient, size_t budget_bytes, int *group_of_clip,
+                      size_t *bytes_of_group)
+{
+  if (n_channels < 1 || rate <= 0 || (n_clips && (!n_frames || !group_of_clip)))
+    {
+      set_error ("awm_speed_batch_plan: bad argument");
+      return AWM_ERR_ARG;
+    }
+  std::vector<int> group;
+  std::vector<size_t> bytes;
+  const int n = speed_batch_plan (std::vector<size_t> (n_frames, n_frames + n_clips), std::vector<int> (n_clips, rate), n_channels, patient != 0,
+                                  budget_bytes ? budget_bytes : speed_batch_bytes(), group, bytes);
+  std::copy (group.begin(), group.end(), group_of_clip);
+  if (bytes_of_group)
+    std::copy (bytes.begin(), bytes.end(), bytes_of_group);
+  return n;
+}
+
+int
+awm_detect_speed_batch_d (awm_ctx *ctx, const uint8_t *keys, int key_per_clip, size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
+                          int n_channels, int rate, int patient, double *speed_out, double *quality_out, int *use_out)
+{
+  AWM_ENTER (ctx);
+  if (int rc = speed_batch_args ("awm_detect_speed_batch_d", keys, n_clips, pcm_d, n_frames, n_channels, rate))
+    return rc;
+  if (!n_clips)
+    return 0;
+  std::vector<SpeedBatchClip> clips;
+  for (size_t i = 0; i < n_clips; i++)
+    clips.push_back ({ capi_key (keys + (key_per_clip ? 16 * i : 0)), make_wav_rate (pcm_d[i], n_frames[i], n_channels, rate) });
+  const bool old_patient = params().detect_speed_patient;
+  params().detect_speed_patient = patient != 0;
+  std::vector<SpeedBatchResult> results;
+  const int rc = detect_speed_batch (ctx, ctx, clips, results);
+  params().detect_speed_patient = old_patient;
+  if (rc)
+    return rc;
+  for (size_t i = 0; i < n_clips; i++)
+    {
+      if (speed_out)
+        speed_out[i] = results[i].speed;
+      if (quality_out)
+        quality_out[i] = results[i].quality;
+      if (use_out)
+        use_out[i] = results[i].rc ? results[i].rc : results[i].use ? 1 : 0;
+    }
+  return 0;
+}
+
+int
+awm_debug_speed_scan_batch_d (awm_ctx *ctx, const uint8_t *keys, int key_per_clip, size_t n_clips, const float *const *pcm_d, const size_t *n_frames,
+                              int n_channels, int rate, const double *clip_locations, double seconds, double step, int n_steps, int n_center_steps,
+                              const double *speeds, const int *n_speeds, size_t max_out_per_clip, double *out_speed, double *out_quality, int *n_out)
+{
+  AWM_ENTER (ctx);
+  if (int rc = speed_batch_args ("awm_debug_speed_scan_batch_d", keys, n_clips, pcm_d, n_frames, n_channels, rate))
+    return rc;
+  if (n_clips && (!clip_locations || !speeds || !n_speeds || !n_out || (max_out_per_clip && (!out_speed || !out_quality))))
+    {
+      set_error ("awm_debug_speed_scan_batch_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  std::vector<SpeedBatchItem> items (n_clips);
+  std::vector<SpeedBatchItem *> batch;
+  size_t at = 0;
+  for (size_t i = 0; i < n_clips; i++)
+    {
+      items[i].key = capi_key (keys + (key_per_clip ? 16 * i : 0));
+      items[i].wav = make_wav_rate (pcm_d[i], n_frames[i], n_channels, rate);
+      items[i].clip_location = clip_locations[i];
+      items[i].speeds.assign (speeds + at, speeds + at + std::max (n_speeds[i], 0));
+      at += std::max (n_speeds[i], 0);
+      batch.push_back (&items[i]);
+    }
+  if (int rc = speed_scan_batch (ctx, ctx, batch, { seconds, step, n_steps, n_center_steps }))
+    return rc;
+  for (size_t i = 0; i < n_clips; i++)
+    {
+      std::vector<SpeedScore>& scores = items[i].scores;
+      std::sort (scores.begin(), scores.end(), [] (const SpeedScore& a, const SpeedScore& b) { return a.speed < b.speed; });
+      for (size_t k = 0; k < scores.size() && k < max_out_per_clip; k++)
+        {
+          out_speed[i * max_out_per_clip + k] = scores[k].speed;
+          out_quality[i * max_out_per_clip + k] = scores[k].quality;
+        }
+      n_out[i] = items[i].rc ? items[i].rc : int (scores.size());
+    }
+  return 0;
+}
+
 } // extern "C"

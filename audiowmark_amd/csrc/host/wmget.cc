@@ -3,6 +3,7 @@
 #include "wmspeed.hh"
 #include "keytab_stage.hh"
 #include <atomic>
+#include <functional>
 #include <future>
 #include <chrono>
 #include <memory>
@@ -1139,6 +1140,28 @@ clip_decoder_run (awm_ctx *ctx, WorkLane *lane, bool spread, const std::vector<K
 
 } // namespace
 
+/* one result of the speed part: the stream stretched back to speed 1 on the lane, block and clip decoder on the copy */
+static int
+decode_stretched (awm_ctx *ctx, WorkLane *home, bool spread, ResultSet& result_set, const DetectSpeedResult& sr, const DeviceWav& wav, bool first_chunk)
+{
+  // resample_ratio (wav, speed, mark_sample_rate * speed)
+  size_t n_out = 0;
+  DevBuffer& stretched = speed_stretch_buffer (home);
+  if (int rc = resample_ratio_device (ctx, home, wav, sr.speed, -1, stretched, &n_out))
+    return rc;
+  DeviceWav sw;
+  sw.data = stretched.as<float>();
+  sw.n_frames = n_out;
+  sw.n_channels = wav.n_channels;
+  sw.sample_rate = int (Params::mark_sample_rate * sr.speed);
+  if (int rc = block_decoder_run (ctx, home, spread, { sr.key }, sw, { ChunkRange { 0, sw.n_frames, 0.0 } }, { &result_set }, sr.speed, nullptr))
+    return rc;
+  if (first_chunk)
+    if (int rc = clip_decoder_run (ctx, home, spread, { sr.key }, sw, result_set, sr.speed))
+      return rc;
+  return 0;
+}
+
 /* The speed part of decode() (reference wmget.cc:886-927): "we always (unconditionally) try to decode the watermark on the
  * original wav data; if detected speed is somewhat different than 1.0, we also try to decode stretched data; we report all
  * normal and speed results we get".  Runs before the normal decoders of the chunk, like in the reference. */
@@ -1160,23 +1183,8 @@ decode_speed (awm_ctx *ctx, WorkLane *home, bool spread, ResultSet& result_set, 
         speed_results.push_back ({ key, params().try_speed });
     }
   for (const auto& sr : speed_results)
-    {
-      // resample_ratio (wav, speed, mark_sample_rate * speed)
-      size_t n_out = 0;
-      DevBuffer& stretched = speed_stretch_buffer (home);
-      if (int rc = resample_ratio_device (ctx, home, wav, sr.speed, -1, stretched, &n_out))
-        return rc;
-      DeviceWav sw;
-      sw.data = stretched.as<float>();
-      sw.n_frames = n_out;
-      sw.n_channels = wav.n_channels;
-      sw.sample_rate = int (Params::mark_sample_rate * sr.speed);
-      if (int rc = block_decoder_run (ctx, home, spread, { sr.key }, sw, { ChunkRange { 0, sw.n_frames, 0.0 } }, { &result_set }, sr.speed, nullptr))
-        return rc;
-      if (first_chunk)
-        if (int rc = clip_decoder_run (ctx, home, spread, { sr.key }, sw, result_set, sr.speed))
-          return rc;
-    }
+    if (int rc = decode_stretched (ctx, home, spread, result_set, sr, wav, first_chunk))
+      return rc;
   return 0;
 }
 
@@ -1453,6 +1461,14 @@ extern "C" void awm_debug_clip_key_timing (double out[3]) { for (int i = 0; i < 
  * 208 / 211 ms with 2 / 3 / 4 / 6; tools/gpu_clip_keys_ab.py) */
 static int g_staged_threads = 0;
 extern "C" void awm_debug_set_staged_threads (int n) { g_staged_threads = n < 0 ? 0 : (n > 8 ? 8 : n); }
+
+/* (A / B, tools/gpu_get_batch_speed.py) under a speed parameter: 0 every clip over the lanes with the one-clip search | 1 the searches of
+ * the short clips as a batch (detect_speed_batch), their stretched decodes over the lanes, the plain decode in their groups | 2 (the tool's
+ * baseline only) every clip after the other on the context's lane, as it was before.  Measured (profiles/get_batch_speed, stereo clips of
+ * 30 s, --detect-speed, a tenth off speed): 64 clips 193 / 275 / 378 ms, 1024 clips 3.07 / 2.98 / 6.02 s for 0 / 1 / 2: a batch of one group
+ * has one lane searching in mode 1, and with four groups side by side mode 1 leads by 2 - 3 %.  Default 0. */
+static int g_speed_batch = 0;
+extern "C" void awm_debug_set_speed_batch (int mode) { g_speed_batch = mode < 0 || mode > 2 ? 0 : mode; }
 
 bool
 clip_is_short (size_t n_frames)
@@ -1860,11 +1876,22 @@ awm_debug_clip_slice_values (int n_channels)
   return n_channels < 1 ? 0 : 3 * (mark_block_frame_count() + 5) * Params::frame_size * size_t (n_channels);
 }
 
+/* The groups under a speed parameter (awm_debug_set_speed_batch (1)), per clip of the call: what the speed search of the groups found
+ * (search: run it, detect_speed_batch on the clips as stage 0 left them in their slices) and the plain patterns of the clip, unmerged --
+ * the caller puts the stretched stream's patterns in front of them (get_watermark_batch_device) */
+struct ClipSpeedPart
+{
+  bool                                        search = false;
+  std::vector<std::vector<DetectSpeedResult>> found;
+  std::vector<ResultSet>                      plain;
+};
+
 /* clip_keys (may be null): one key per clip -- clip i is searched and decoded with (*clip_keys)[i] alone (key_list is not used then) */
 static int
 clip_batch_staged (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_list, const std::vector<DeviceWav>& clips, const std::vector<size_t>& which,
                    std::vector<ResultSet>& result_sets, const std::vector<Key> *clip_keys = nullptr, WorkLane *table_lane = nullptr,
-                   const DeviceGroupTables *all_tables = nullptr, const std::vector<int> *slot_of_clip = nullptr, const ClipRates *rates = nullptr)
+                   const DeviceGroupTables *all_tables = nullptr, const std::vector<int> *slot_of_clip = nullptr, const ClipRates *rates = nullptr,
+                   ClipSpeedPart *speed = nullptr)
 {
   const size_t count = mark_block_frame_count();
   const int n_bits_a = int (mark_data_frame_count() / params().frames_per_bit);
@@ -1926,6 +1953,39 @@ clip_batch_staged (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_lis
       if (int rc = clip_stage0_launch (ctx, lane, clips, which.data() + g0, gn, rates, lane->ws_clip.as<float>(), slice_values, s0)) return rc;
       long long *const d_range = s0.d_range;
       const long long margin_values = s0.margin_values;
+      if (speed && speed->search)
+        {
+          // the speed search of the group's clips, sub-groups in lockstep on this lane: after stage 0 a clip lies contiguous inside its
+          // slice as float PCM at 44.1 kHz whatever it was (another fixed-ratio rate, 16-bit) -- no further copy or decode per clip
+          std::vector<SpeedBatchClip> batch;
+          std::vector<size_t> clip_of;
+          for (size_t i = 0; i < gn; i++)
+            {
+              DeviceWav w;
+              w.data = lane->ws_clip.as<float>() + i * slice_values + s0.pad_start[i];
+              w.n_frames = size_t (s0.n_values[i]) / C;
+              w.n_channels = C;
+              w.sample_rate = int (Params::mark_sample_rate);
+              for (const Key& key : (clip_keys ? std::vector<Key> { (*clip_keys)[which[g0 + i]] } : key_list))
+                {
+                  batch.push_back ({ key, w });
+                  clip_of.push_back (which[g0 + i]);
+                }
+            }
+          std::vector<SpeedBatchResult> found;
+          if (int rc = detect_speed_batch (ctx, lane, batch, found))
+            return rc;
+          for (size_t b = 0; b < batch.size(); b++)
+            {
+              if (found[b].rc)                         // (the one-clip get of this clip fails with this error)
+                {
+                  set_error (found[b].error);
+                  return found[b].rc;
+                }
+              if (found[b].use)
+                speed->found[clip_of[b]].push_back ({ batch[b].key, found[b].speed });
+            }
+        }
       DeviceWav group;
       group.data = lane->ws_clip.as<float>();
       group.n_frames = gn * slice_frames;
@@ -2066,6 +2126,12 @@ clip_batch_staged (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_lis
       g0 += gn;
     }
   drain.ok = true;
+  if (speed)
+    {
+      for (size_t j = 0; j < which.size(); j++)
+        speed->plain[which[j]] = chunk_sets[j];
+      return 0;
+    }
   for (size_t j = 0; j < which.size(); j++)
     {
       ResultSet& rs = result_sets[which[j]];                        // as get_watermark_device: one chunk at offset 0, merge, sort
@@ -2089,8 +2155,10 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
   auto keys_of = [&] (size_t i) { return clip_keys ? std::vector<Key> { (*clip_keys)[i] } : key_list; };
   // one clip on one lane: at another rate its 44.1 kHz copy goes into the lane's workspace first
   // (a 16-bit clip that goes this way is decoded into the lane's workspace first: one launch, the exact conversion of the file level)
-  auto get_one = [&] (WorkLane *lane, bool spread, size_t i) {
+  // (`empty`: a clip without a frame at 44.1 kHz has no patterns)
+  auto stage_one = [&] (WorkLane *lane, size_t i, DeviceWav& wav44, bool& empty) {
     DeviceWav clip = clips[i];
+    empty = false;
     if (clip.pcm16 && clip.n_values())
       {
         if (int rc = lane->ws_pcm.reserve (std::max<size_t> (16, clip.n_values() * sizeof (float)))) return rc;
@@ -2099,33 +2167,128 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
         clip.data = lane->ws_pcm.as<float>();
       }
     clip.pcm16 = nullptr;
+    wav44 = clip;
     if (!rates)
-      return get_watermark_on (ctx, lane, spread, keys_of (i), clip, result_sets[i]);
+      return 0;
     if (!rates->n44[i])
-      return 0;                                      // an empty clip: no patterns
+      {
+        empty = true;
+        return 0;
+      }
+    return resample_to_mark_rate (ctx, lane, *rates, i, clip, wav44);
+  };
+  auto get_one = [&] (WorkLane *lane, bool spread, size_t i) {
     DeviceWav wav44;
-    if (int rc = resample_to_mark_rate (ctx, lane, *rates, i, clip, wav44))
+    bool empty = false;
+    if (int rc = stage_one (lane, i, wav44, empty))
       return rc;
-    return get_watermark_on (ctx, lane, spread, keys_of (i), wav44, result_sets[i]);
+    return empty ? 0 : get_watermark_on (ctx, lane, spread, keys_of (i), wav44, result_sets[i]);
   };
   result_sets.clear();
   result_sets.resize (clips.size());
   if (clips.empty())
     return 0;
+  /* jobs over the work lanes in parallel, one job per lane and host thread at a time */
+  auto over_lanes = [&] (size_t n_jobs, const std::function<int (WorkLane *, size_t)>& job) {
+    if (!n_jobs)
+      return 0;
+    const int n_workers = std::max (1, std::min<int> ({ n_threads > 0 ? n_threads : MAX_LANES, MAX_LANES, int (n_jobs) }));
+    std::vector<WorkLane *> lanes;
+    for (int i = 0; i < n_workers; i++)
+      {
+        WorkLane *l = ctx->lane (i);
+        if (!l)
+          {
+            set_error ("cannot create a work lane (stream)");
+            return int (AWM_ERR_HIP);
+          }
+        lanes.push_back (l);
+      }
+    if (!clip_keys)
+      for (const Key& key : key_list)
+        if (!ctx->get_key_tables (key))               // built once, before the workers start
+          return int (AWM_ERR_HIP);
+    // the clips may still be in flight on the context's stream
+    if (!ctx->ev_sync)
+      AWM_HIP_CHECK (hipEventCreateWithFlags (&ctx->ev_sync, hipEventDisableTiming));
+    AWM_HIP_CHECK (hipEventRecord (ctx->ev_sync, ctx->stream));
+    for (size_t i = 1; i < lanes.size(); i++)
+      AWM_HIP_CHECK (hipStreamWaitEvent (lanes[i]->stream, ctx->ev_sync, 0));
+    std::atomic<size_t> next { lanes.size() };
+    std::vector<int> rc (lanes.size(), 0);
+    std::vector<std::string> err (lanes.size());
+    ParamValues *const pv = &params();
+    auto worker = [&] (size_t li) {
+      ParamsBind bind (pv);
+      const bool was_blocking = wait_blocking();
+      wait_blocking() = lanes.size() > 1;
+      struct Restore { bool v; ~Restore() { wait_blocking() = v; } } restore { was_blocking };
+      if (hipSetDevice (ctx->device) != hipSuccess)
+        {
+          rc[li] = AWM_ERR_HIP;
+          err[li] = "hipSetDevice failed in a batch worker";
+          return;
+        }
+      // the first job of every lane is dealt (job li to lane li), the rest is pulled: a call of no more clips than lanes -- the few long
+      // clips or VResampler rates of a batch of short clips -- grows the same lanes' workspaces every time it is repeated
+      for (size_t t = li; t < n_jobs; t = next.fetch_add (1))
+        if (int r = job (lanes[li], t))
+          {
+            rc[li] = r;
+            err[li] = last_error();
+            next.store (n_jobs);                   // stop the other workers
+            break;
+          }
+    };
+    std::vector<std::thread> threads;
+    for (size_t li = 1; li < lanes.size(); li++)
+      threads.emplace_back (worker, li);
+    worker (0);
+    for (auto& t : threads)
+      t.join();
+    for (size_t li = 0; li < lanes.size(); li++)
+      if (rc[li])
+        {
+          set_error (err[li]);
+          return rc[li];
+        }
+    return 0;
+  };
   // short clips: staged over the lanes from this thread; everything else: one clip per lane and host thread
   std::vector<size_t> staged, threaded;
-  if (params().detect_speed || params().detect_speed_patient || params().try_speed > 0)
+  // (at another rate a clip is short by its 44.1 kHz length, and the groups take only what stage 0 resamples or copies: the fixed-ratio
+  // rates and 44.1 kHz.  The groups fill in call order whatever the rates of their clips)
+  for (size_t i = 0; i < clips.size(); i++)
+    ((rates ? rates->groupable (i) && clip_is_short (rates->n44[i]) : clip_is_short (clips[i])) ? staged : threaded).push_back (i);
+  /* Under a speed parameter (decode_speed) every clip goes over the lanes in parallel with the one-clip search (get_one), each lane with
+   * its own search scratch and stretch buffer.  With awm_debug_set_speed_batch (1) the short clips keep their groups: after stage 0 the
+   * speed search of a group's clips runs as detect_speed_batch on the slices (sub-groups in lockstep), then the plain search and decode of
+   * the group as always; the stretched decodes of the clips with a speed are collected and run over the lanes in parallel afterwards, and
+   * their patterns go in front of the clip's plain ones, the reference's order.  That way measured slower than the lanes
+   * (g_speed_batch above), so it is not the default. */
+  const bool speed_on = params().detect_speed || params().detect_speed_patient || params().try_speed > 0;
+  ClipSpeedPart speed_part;
+  ClipSpeedPart *speed_ptr = nullptr;
+  if (speed_on && g_speed_batch == 2)
     {
-      // the speed search and the stretched copy of a clip live in per-context buffers: one clip after the other
       for (size_t i = 0; i < clips.size(); i++)
         if (int rc = get_one (ctx, true, i))
           return rc;
       return 0;
     }
-  // (at another rate a clip is short by its 44.1 kHz length, and the groups take only what stage 0 resamples or copies: the fixed-ratio
-  // rates and 44.1 kHz.  The groups fill in call order whatever the rates of their clips)
-  for (size_t i = 0; i < clips.size(); i++)
-    ((rates ? rates->groupable (i) && clip_is_short (rates->n44[i]) : clip_is_short (clips[i])) ? staged : threaded).push_back (i);
+  if (speed_on && g_speed_batch == 1)
+    {
+      speed_part.search = params().detect_speed || params().detect_speed_patient;
+      speed_part.found.resize (clips.size());
+      speed_part.plain.resize (clips.size());
+      speed_ptr = &speed_part;
+    }
+  else if (speed_on)
+    {
+      threaded.insert (threaded.end(), staged.begin(), staged.end());
+      staged.clear();
+      std::sort (threaded.begin(), threaded.end());
+    }
   if (!staged.empty())
     {
       if (!ctx->ev_sync)
@@ -2191,11 +2354,11 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
         workers.emplace_back ([&, t] {
           ParamsBind bind (pv);
           (void) hipSetDevice (ctx->device);
-          rcs[t] = clip_batch_staged (ctx, staged_lanes[t], key_list, clips, share[t], result_sets, clip_keys, table_lanes[t], all_ptr, &slot_of_clip, rates);
+          rcs[t] = clip_batch_staged (ctx, staged_lanes[t], key_list, clips, share[t], result_sets, clip_keys, table_lanes[t], all_ptr, &slot_of_clip, rates, speed_ptr);
           if (rcs[t])
             messages[t] = last_error();
         });
-      rcs[0] = clip_batch_staged (ctx, staged_lanes[0], key_list, clips, share[0], result_sets, clip_keys, table_lanes[0], all_ptr, &slot_of_clip, rates);
+      rcs[0] = clip_batch_staged (ctx, staged_lanes[0], key_list, clips, share[0], result_sets, clip_keys, table_lanes[0], all_ptr, &slot_of_clip, rates, speed_ptr);
       for (auto& w : workers)
         w.join();
       for (int t = 0; t < n_staged_threads; t++)
@@ -2206,72 +2369,42 @@ get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, cons
             return rcs[t];
           }
     }
-  if (threaded.empty())
-    return 0;
-  n_threads = std::max (1, std::min<int> ({ n_threads > 0 ? n_threads : MAX_LANES, MAX_LANES, int (threaded.size()) }));
-  std::vector<WorkLane *> lanes;
-  for (int i = 0; i < n_threads; i++)
+  if (speed_ptr)
     {
-      WorkLane *l = ctx->lane (i);
-      if (!l)
+      // the stretched decodes: the clips for which the search returned a speed, or every clip with --try-speed; staged as get_one stages a
+      // clip, then what decode_speed runs for one result; a clip's results in key order on one lane
+      std::vector<size_t> jobs;
+      for (size_t i : staged)
         {
-          set_error ("cannot create a work lane (stream)");
-          return AWM_ERR_HIP;
+          if (!speed_part.search && (rates ? rates->n44[i] : clips[i].n_frames))       // (an empty clip has no chunk: decode() never sees it)
+            for (const Key& key : keys_of (i))
+              speed_part.found[i].push_back ({ key, params().try_speed });
+          if (!speed_part.found[i].empty())
+            jobs.push_back (i);
         }
-      lanes.push_back (l);
+      std::vector<ResultSet> speed_sets (clips.size());
+      if (int rc = over_lanes (jobs.size(), [&] (WorkLane *lane, size_t j) {
+            const size_t i = jobs[j];
+            DeviceWav wav44;
+            bool empty = false;
+            if (int rc = stage_one (lane, i, wav44, empty))
+              return rc;
+            for (const DetectSpeedResult& sr : speed_part.found[i])
+              if (int rc = decode_stretched (ctx, lane, false, speed_sets[i], sr, wav44, true))
+                return rc;
+            return 0;
+          }))
+        return rc;
+      for (size_t i : staged)
+        {
+          ResultSet chunk = speed_part.plain[i];                        // as get_watermark_device: one chunk at offset 0, merge, sort
+          chunk.patterns.insert (chunk.patterns.begin(), speed_sets[i].patterns.begin(), speed_sets[i].patterns.end());
+          chunk.apply_time_offset (0.0);
+          result_sets[i].merge (chunk);
+          result_sets[i].sort (keys_of (i));
+        }
     }
-  if (!clip_keys)
-    for (const Key& key : key_list)
-      if (!ctx->get_key_tables (key))               // built once, before the workers start
-        return AWM_ERR_HIP;
-  // the clips may still be in flight on the context's stream
-  if (!ctx->ev_sync)
-    AWM_HIP_CHECK (hipEventCreateWithFlags (&ctx->ev_sync, hipEventDisableTiming));
-  AWM_HIP_CHECK (hipEventRecord (ctx->ev_sync, ctx->stream));
-  for (size_t i = 1; i < lanes.size(); i++)
-    AWM_HIP_CHECK (hipStreamWaitEvent (lanes[i]->stream, ctx->ev_sync, 0));
-  std::atomic<size_t> next { lanes.size() };
-  std::vector<int> rc (lanes.size(), 0);
-  std::vector<std::string> err (lanes.size());
-  ParamValues *const pv = &params();
-  auto worker = [&] (size_t li) {
-    ParamsBind bind (pv);
-    const bool was_blocking = wait_blocking();
-    wait_blocking() = lanes.size() > 1;
-    struct Restore { bool v; ~Restore() { wait_blocking() = v; } } restore { was_blocking };
-    if (hipSetDevice (ctx->device) != hipSuccess)
-      {
-        rc[li] = AWM_ERR_HIP;
-        err[li] = "hipSetDevice failed in a batch worker";
-        return;
-      }
-    // the first clip of every lane is dealt (clip li to lane li), the rest is pulled: a call of no more clips than lanes -- the few long
-    // clips or VResampler rates of a batch of short clips -- grows the same lanes' workspaces every time it is repeated
-    for (size_t t = li; t < threaded.size(); t = next.fetch_add (1))
-      {
-        const size_t i = threaded[t];
-        if (int r = get_one (lanes[li], false, i))
-          {
-            rc[li] = r;
-            err[li] = last_error();
-            next.store (threaded.size());          // stop the other workers
-            break;
-          }
-      }
-  };
-  std::vector<std::thread> threads;
-  for (size_t li = 1; li < lanes.size(); li++)
-    threads.emplace_back (worker, li);
-  worker (0);
-  for (auto& t : threads)
-    t.join();
-  for (size_t li = 0; li < lanes.size(); li++)
-    if (rc[li])
-      {
-        set_error (err[li]);
-        return rc[li];
-      }
-  return 0;
+  return over_lanes (threaded.size(), [&] (WorkLane *lane, size_t t) { return get_one (lane, false, threaded[t]); });
 }
 
 /* (awm_debug_clip_stage_d) stage 0 of ONE group alone, into the caller's buffer on the context's stream */

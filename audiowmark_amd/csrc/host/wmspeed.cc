@@ -3,8 +3,10 @@
 #include "wmcommon.hh"
 #include "utils.hh"
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <thread>
 
 namespace awm {
@@ -290,6 +292,41 @@ speed_clip_range (double location, const DeviceWav& wav, double clip_seconds, si
 
 struct ScanCenter { double speed; VarResampleTable *table; long long n_in, n_out; int rows; };
 
+/* resample_ratio_truncate (clip, center / 2, mark_sample_rate / 2, seconds / center) and the STFT rows of its output */
+void
+center_geometry (const DeviceWav& clip, double seconds, ScanCenter& c)
+{
+  const int C = clip.n_channels, N = Params::frame_size / 2, hop = Params::sync_search_step / 2;
+  size_t in_frames = clip.n_frames;
+  const double max_in_seconds = seconds / c.speed;
+  if (max_in_seconds > 0)
+    in_frames = std::min<size_t> (in_frames * C, C * lrint (clip.sample_rate * max_in_seconds)) / C;
+  c.n_in = (long long) in_frames;
+  c.n_out = lrint (in_frames * (c.speed / 2));             // "we downsample the audio by factor 2 to improve performance"
+  c.rows = c.n_out > N ? int ((c.n_out - N - 1) / hop + 1) : 0;          // pos + N < n_out, pos = 0, hop, ...
+}
+
+/* the three passes of run_search (reference wmspeed.cc:622-681) */
+struct SearchPlan
+{
+  SpeedScanParams scan1, scan2, scan3;
+  size_t n_best;
+};
+SearchPlan
+search_plan (bool patient)
+{
+  // first pass: grid over 0.8 .. 1.25; second: improve the n best; third: fast refinement around the best
+  SearchPlan p;
+  p.scan1 = patient ? SpeedScanParams { 50, 1.00035, 11, 28 } : SpeedScanParams { 25, 1.0007, 5, 28 };
+  p.scan2 = patient ? SpeedScanParams { 50, 1.000175, 1, 0 } : SpeedScanParams { 50, 1.00035, 1, 0 };
+  p.scan3 = SpeedScanParams { 50, 1.00005, 40, 0 };
+  p.n_best = patient ? 15 : 5;
+  return p;
+}
+constexpr double scan3_smooth_distance = 20;
+constexpr double speed_sync_threshold = 0.4;
+constexpr int    clip_candidates = 5;
+
 /* resample + STFT + column sums of all centres of a pass; leaves the matrices in ws->mags */
 int
 prepare_mags (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& clip, double seconds, std::vector<ScanCenter>& centers,
@@ -304,11 +341,10 @@ prepare_mags (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& cli
   const int C = clip.n_channels;
   std::vector<double> ratios;
   for (auto& c : centers)
-    ratios.push_back (c.speed / 2);                        // "we downsample the audio by factor 2 to improve performance"
+    ratios.push_back (c.speed / 2);
   std::vector<VarResampleTable *> tables;
   if (int rc = get_var_tables (ctx, ratios, tables))
     return rc;
-  const int N = Params::frame_size / 2, hop = Params::sync_search_step / 2;
   long long max_out = 0;
   int max_rows = 0;
   std::vector<awmk::SpeedCenterDev> cds;
@@ -316,14 +352,7 @@ prepare_mags (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& cli
     {
       ScanCenter& c = centers[i];
       c.table = tables[i];
-      // resample_ratio_truncate (clip, center / 2, mark_sample_rate / 2, seconds / center)
-      size_t in_frames = clip.n_frames;
-      const double max_in_seconds = seconds / c.speed;
-      if (max_in_seconds > 0)
-        in_frames = std::min<size_t> (in_frames * C, C * lrint (clip.sample_rate * max_in_seconds)) / C;
-      c.n_in = (long long) in_frames;
-      c.n_out = lrint (in_frames * ratios[i]);
-      c.rows = c.n_out > N ? int ((c.n_out - N - 1) / hop + 1) : 0;        // pos + N < n_out, pos = 0, hop, ...
+      center_geometry (clip, seconds, c);
       awmk::SpeedCenterDev cd = center_dev (c.table, ratios[i], c.n_in, c.n_out);
       cd.rows = c.rows;
       cds.push_back (cd);
@@ -726,15 +755,9 @@ detect_speed (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_list, co
   const double in_seconds = double (wav.n_frames) / wav.sample_rate;
   if (in_seconds < 0.25)
     return 0;
-  const bool patient = params().detect_speed_patient;
-  // first pass: grid over 0.8 .. 1.25; second: improve the n best; third: fast refinement around the best
-  const SpeedScanParams scan1 = patient ? SpeedScanParams { 50, 1.00035, 11, 28 } : SpeedScanParams { 25, 1.0007, 5, 28 };
-  const SpeedScanParams scan2 = patient ? SpeedScanParams { 50, 1.000175, 1, 0 } : SpeedScanParams { 50, 1.00035, 1, 0 };
-  const SpeedScanParams scan3 { 50, 1.00005, 40, 0 };
-  const double scan3_smooth_distance = 20;
-  const double speed_sync_threshold = 0.4;
-  const size_t n_best = patient ? 15 : 5;
-  const int clip_candidates = 5;
+  const SearchPlan plan = search_plan (params().detect_speed_patient);
+  const SpeedScanParams &scan1 = plan.scan1, &scan2 = plan.scan2, &scan3 = plan.scan3;
+  const size_t n_best = plan.n_best;
   for (const Key& key : key_list)
     {
       double clip_location = 0;
@@ -775,6 +798,466 @@ detect_speed (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_list, co
           if (best_speed < 0.9999 || best_speed > 1.0001)
             results.push_back ({ key, best_speed });
         }
+    }
+  return 0;
+}
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Batches: the same passes for several clips in lockstep.  An entry of a launch is a (clip, centre) pair: entry e has its
+ * SpeedCenterDev (n_in, n_out, rows of its clip at that centre) and a SpeedEntryDev (the clip's pointer, the tables of its
+ * key); sub and mags keep one stride per launch, the largest any entry needs.  Descriptors of a pass travel in one copy,
+ * its scores come back in one copy behind one synchronisation.
+ * ------------------------------------------------------------------------------------------------------------------ */
+namespace {
+
+std::atomic<size_t> g_speed_batch_bytes { SPEED_BATCH_BYTES };
+
+size_t
+align16 (size_t n)
+{
+  return (n + 15) & ~size_t (15);
+}
+
+/* bytes of sub + mags the first pass needs per centre of this clip, as launch strides (the largest centre of the clip) */
+void
+scan1_strides (size_t n_frames, int n_channels, int rate, const SpeedScanParams& sp, long long *sub_stride, long long *ld)
+{
+  DeviceWav wav {};
+  wav.n_frames = n_frames;
+  wav.n_channels = n_channels;
+  wav.sample_rate = rate;
+  size_t start_point, end_point;
+  speed_clip_range (0, wav, sp.seconds * 1.3, &start_point, &end_point);
+  DeviceWav clip = wav;
+  clip.n_frames = end_point - start_point;
+  long long max_out = 0;
+  int max_rows = 0;
+  for (int c = -sp.n_center_steps; c <= sp.n_center_steps; c++)
+    {
+      ScanCenter sc { std::pow (sp.step, c * (sp.n_steps * 2 + 1)), nullptr, 0, 0, 0 };
+      center_geometry (clip, sp.seconds, sc);
+      max_out = std::max (max_out, sc.n_out);
+      max_rows = std::max (max_rows, sc.rows);
+    }
+  *sub_stride = (max_out * n_channels + 3) / 4 * 4;
+  *ld = (max_rows + 15) / 16 * 16;
+}
+
+} // namespace
+
+void
+speed_batch_set_bytes (size_t bytes)
+{
+  g_speed_batch_bytes = bytes ? bytes : SPEED_BATCH_BYTES;
+}
+
+size_t
+speed_batch_bytes()
+{
+  return g_speed_batch_bytes;
+}
+
+int
+speed_batch_plan (const std::vector<size_t>& n_frames, const std::vector<int>& rates, int n_channels, bool patient, size_t budget,
+                  std::vector<int>& group_of_clip, std::vector<size_t>& bytes_of_group)
+{
+  const SpeedScanParams sp = search_plan (patient).scan1;
+  const size_t centers = size_t (2 * sp.n_center_steps + 1);
+  group_of_clip.assign (n_frames.size(), -1);
+  bytes_of_group.clear();
+  size_t members = 0;
+  long long sub_stride = 0, ld = 0;                        // of the open sub-group
+  for (size_t i = 0; i < n_frames.size(); i++)
+    {
+      if (rates[i] <= 0 || double (n_frames[i]) / rates[i] < 0.25)
+        continue;                                          // takes no part in the search
+      long long s = 0, l = 0;
+      scan1_strides (n_frames[i], n_channels, rates[i], sp, &s, &l);
+      const auto bytes = [&] (size_t n, long long ss, long long ll) { return n * centers * (size_t (ss) * sizeof (float) + size_t (510) * ll * sizeof (float2)); };
+      const long long s_with = std::max (s, sub_stride), l_with = std::max (l, ld);
+      if (members && (bytes (members + 1, s_with, l_with) > budget || members + 1 > SPEED_BATCH_MAX_CLIPS))
+        {
+          members = 0;                                     // the clip opens the next sub-group (a sub-group holds one clip at least)
+          sub_stride = ld = 0;
+        }
+      if (!members)
+        bytes_of_group.push_back (0);
+      members++;
+      sub_stride = std::max (s, sub_stride);
+      ld = std::max (l, ld);
+      group_of_clip[i] = int (bytes_of_group.size()) - 1;
+      bytes_of_group.back() = bytes (members, sub_stride, ld);
+    }
+  return int (bytes_of_group.size());
+}
+
+int
+speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, double seconds, int candidates)
+{
+  (void) ctx;
+  SpeedScratch *ws = speed_scratch (lane);
+  hipStream_t st = lane->stream;
+  if (batch.empty())
+    return 0;
+  /* get_clip_locations (reference wmspeed.cc:533-553) of every clip: positions side by side, one gather */
+  std::vector<unsigned long long> pos;
+  std::vector<awmk::GatherClipDev> gather;
+  std::vector<Random> rngs;
+  long long max_n = 0;
+  for (SpeedBatchItem *item : batch)
+    {
+      rngs.emplace_back (item->key, 0, Random::Stream::speed_clip);
+      Random& rng = rngs.back();
+      const size_t first = pos.size(), n_values = item->wav.n_values();
+      for (size_t p = 0; p < n_values; p += rng() % 1000)
+        pos.push_back (p);
+      gather.push_back ({ item->wav.data, (long long) first, (long long) (pos.size() - first) });
+      max_n = std::max (max_n, gather.back().n);
+    }
+  const size_t pos_bytes = align16 (pos.size() * sizeof (unsigned long long)), gather_bytes = gather.size() * sizeof (awmk::GatherClipDev);
+  const size_t val_bytes = pos.size() * sizeof (float);
+  const size_t n_ranges = batch.size() * size_t (candidates);
+  const size_t range_bytes = n_ranges * sizeof (awmk::EnergyRangeDev), e_bytes = n_ranges * awmk::ENERGY_PARTS * sizeof (double);
+  if (int rc = ws->gather_pos.reserve (pos_bytes + gather_bytes))
+    return rc;
+  if (int rc = ws->gather_out.reserve (std::max<size_t> (val_bytes, 16)))
+    return rc;
+  if (int rc = ws->ranges.reserve (range_bytes))
+    return rc;
+  if (int rc = ws->energy.reserve (e_bytes))
+    return rc;
+  if (int rc = ws->pin.reserve (std::max<size_t> (std::max (pos_bytes + gather_bytes + val_bytes, range_bytes + e_bytes), 1 << 16)))
+    return rc;
+  char *pin = ws->pin.as<char>();
+  std::memcpy (pin, pos.data(), pos.size() * sizeof (unsigned long long));
+  std::memcpy (pin + pos_bytes, gather.data(), gather_bytes);
+  AWM_HIP_CHECK (hipMemcpyAsync (ws->gather_pos.ptr, pin, pos_bytes + gather_bytes, hipMemcpyHostToDevice, st));
+  AWM_HIP_CHECK (awmk::launch_gather_values_batch (st, reinterpret_cast<const awmk::GatherClipDev *> (ws->gather_pos.as<char>() + pos_bytes), int (gather.size()),
+                                                   max_n, ws->gather_pos.as<unsigned long long>(), ws->gather_out.as<float>()));
+  const float *values = reinterpret_cast<const float *> (pin + pos_bytes + gather_bytes);
+  AWM_HIP_CHECK (hipMemcpyAsync (pin + pos_bytes + gather_bytes, ws->gather_out.ptr, val_bytes, hipMemcpyDeviceToHost, st));
+  AWM_HIP_CHECK (hipStreamSynchronize (st));
+  std::vector<double> locations;                           // [clip][candidate]
+  std::vector<awmk::EnergyRangeDev> ranges;
+  for (size_t b = 0; b < batch.size(); b++)
+    {
+      const DeviceWav& wav = batch[b]->wav;
+      unsigned char hash[20];
+      sha1 (values + gather[b].first, size_t (gather[b].n) * sizeof (float), hash);          // Random::seed_from_hash (reference random.cc:184-190)
+      uint64_t seed = 0;
+      for (int i = 0; i < 8; i++)
+        seed = (seed << 8) | hash[i];
+      rngs[b].seed (seed, Random::Stream::speed_clip);
+      for (int c = 0; c < candidates; c++)
+        {
+          locations.push_back (rngs[b].random_double());
+          size_t start_point, end_point;
+          speed_clip_range (locations.back(), wav, seconds, &start_point, &end_point);
+          ranges.push_back ({ wav.data, (long long) (start_point * wav.n_channels), (long long) (end_point * wav.n_channels) });
+        }
+    }
+  /* get_best_clip_location (reference wmspeed.cc:555-577): the candidate with the highest energy, per clip */
+  std::memcpy (pin, ranges.data(), range_bytes);
+  AWM_HIP_CHECK (hipMemcpyAsync (ws->ranges.ptr, pin, range_bytes, hipMemcpyHostToDevice, st));
+  AWM_HIP_CHECK (awmk::launch_energy_batch (st, ws->ranges.as<awmk::EnergyRangeDev>(), int (n_ranges), ws->energy.as<double>()));
+  AWM_HIP_CHECK (hipMemcpyAsync (pin + range_bytes, ws->energy.ptr, e_bytes, hipMemcpyDeviceToHost, st));
+  AWM_HIP_CHECK (hipStreamSynchronize (st));
+  const double *parts = reinterpret_cast<const double *> (pin + range_bytes);
+  for (size_t b = 0; b < batch.size(); b++)
+    {
+      double clip_location = 0, best_energy = 0;
+      for (int c = 0; c < candidates; c++)
+        {
+          double energy = 0;
+          for (int k = 0; k < awmk::ENERGY_PARTS; k++)
+            energy += parts[(b * candidates + c) * awmk::ENERGY_PARTS + k];
+          if (energy > best_energy)
+            {
+              best_energy = energy;
+              clip_location = locations[b * candidates + c];
+            }
+        }
+      batch[b]->clip_location = clip_location;
+    }
+  return 0;
+}
+
+int
+speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, const SpeedScanParams& sp)
+{
+  SpeedScratch *ws = speed_scratch (lane);
+  if (int rc = ensure_window (ctx))
+    return rc;
+  struct Part { SpeedBatchItem *item; DeviceWav clip; SpeedKeyTables *skt; size_t first, count; };
+  std::vector<Part> parts;
+  std::vector<ScanCenter> centers;                         // of all clips, clip after clip
+  std::vector<double> ratios;
+  int C = 0;
+  for (SpeedBatchItem *item : batch)
+    {
+      item->scores.clear();
+      if (item->rc || item->speeds.empty())
+        continue;
+      Part part { item, item->wav, nullptr, centers.size(), 0 };
+      for (double speed : item->speeds)
+        for (int c = -sp.n_center_steps; c <= sp.n_center_steps && !item->rc; c++)
+          {
+            const double center = speed * std::pow (sp.step, c * (sp.n_steps * 2 + 1));
+            if (!var_geometry (center / 2).ok)             // (the one-clip search fails here as well, in get_var_tables: the clip drops out, the others go on)
+              {
+                item->error = string_printf ("failed to setup vresampler with ratio=%f", center / 2);   // (not set_error: the call goes on)
+                item->rc = AWM_ERR_ARG;
+              }
+            centers.push_back ({ center, nullptr, 0, 0, 0 });
+          }
+      if (item->rc)
+        {
+          centers.resize (part.first);
+          continue;
+        }
+      if (C && item->wav.n_channels != C)
+        {
+          set_error ("speed_scan_batch: the clips of a launch have one channel count");
+          return AWM_ERR_ARG;
+        }
+      C = item->wav.n_channels;
+      /* SpeedSearch::get_jobs (reference wmspeed.cc:461-492) */
+      size_t start_point, end_point;
+      speed_clip_range (item->clip_location, item->wav, sp.seconds * 1.3, &start_point, &end_point);
+      part.clip.data = item->wav.data + start_point * C;
+      part.clip.n_frames = end_point - start_point;
+      part.count = centers.size() - part.first;
+      part.skt = get_speed_key_tables (ctx, item->key);    // (never evicted: alive for the launches below)
+      if (!part.skt)
+        return AWM_ERR_HIP;
+      parts.push_back (part);
+    }
+  if (centers.empty())
+    return 0;
+  if (centers.size() > SPEED_BATCH_MAX_ENTRIES)
+    {
+      set_error ("speed_scan_batch: too many (clip, centre) pairs for one launch");
+      return AWM_ERR_ARG;
+    }
+  // every ratio once (the first pass has the same 57 for every clip): the lookup below runs under the context's table lock
+  std::vector<double> unique_ratios;
+  std::vector<size_t> table_of;
+  {
+    std::map<double, size_t> seen;
+    for (const auto& c : centers)
+      {
+        ratios.push_back (c.speed / 2);
+        const auto it = seen.emplace (ratios.back(), unique_ratios.size());
+        if (it.second)
+          unique_ratios.push_back (ratios.back());
+        table_of.push_back (it.first->second);
+      }
+  }
+  std::vector<VarResampleTable *> unique_tables, tables;
+  if (int rc = get_var_tables (ctx, unique_ratios, unique_tables))
+    return rc;
+  for (size_t t : table_of)
+    tables.push_back (unique_tables[t]);
+  const int per = 2 * sp.n_steps + 1;
+  std::vector<awmk::SpeedCenterDev> cds;
+  std::vector<awmk::SpeedEntryDev> entries;
+  std::vector<awmk::SpeedItemDev> items;
+  std::vector<double> item_speed;
+  long long max_out = 0;
+  int max_rows = 0;
+  bool aligned = true;
+  awmk::VarResampleArgs ra {};
+  double var_bytes = 0, mags_bytes = 0, compare_bytes = 0;
+  for (const Part& part : parts)
+    {
+      aligned = aligned && (reinterpret_cast<uintptr_t> (part.clip.data) & 7) == 0;
+      for (size_t i = part.first; i < part.first + part.count; i++)
+        {
+          ScanCenter& c = centers[i];
+          c.table = tables[i];
+          center_geometry (part.clip, sp.seconds, c);
+          awmk::SpeedCenterDev cd = center_dev (c.table, ratios[i], c.n_in, c.n_out);
+          cd.rows = c.rows;
+          cds.push_back (cd);
+          entries.push_back ({ part.clip.data, part.skt->cols.as<unsigned int>(), part.skt->col_frame.as<int>(), part.skt->col_first.as<unsigned char>() });
+          max_out = std::max (max_out, c.n_out);
+          max_rows = std::max (max_rows, c.rows);
+          ra.max_stride = std::max (ra.max_stride, cd.stride);
+          ra.max_step = std::max (ra.max_step, std::ldexp (double (cd.mant), -cd.shift));
+          var_bytes += double (c.n_in + c.n_out) * C * 4.0;
+          mags_bytes += double (c.n_out) * C * 4.0 + double (c.rows) * 510 * 8.0;
+          compare_bytes += double (c.rows) * 510 * 8.0 + per * 8.0;
+          /* SpeedSync::get_jobs (reference wmspeed.cc:172-192) */
+          for (int p = -sp.n_steps; p <= sp.n_steps; p++)
+            {
+              const double center = c.speed;
+              const double relative_speed = std::pow (sp.step, p) * center / center;
+              awmk::SpeedItemDev it {};
+              it.center = int (i);
+              it.rel_speed_inv = 1 / relative_speed;
+              it.q16_scale = (1 << 16) / relative_speed;
+              items.push_back (it);
+              item_speed.push_back (relative_speed * center);
+            }
+        }
+    }
+  const long long ld = (max_rows + 15) / 16 * 16;
+  const long long sub_stride = (max_out * C + 3) / 4 * 4;
+  const long long center_stride = 510 * ld;
+  const size_t n = centers.size();
+  const size_t cds_bytes = align16 (n * sizeof (awmk::SpeedCenterDev)), entries_bytes = align16 (n * sizeof (awmk::SpeedEntryDev));
+  const size_t items_bytes = align16 (items.size() * sizeof (awmk::SpeedItemDev)), best_bytes = items.size() * sizeof (unsigned long long);
+  const size_t blob_bytes = cds_bytes + entries_bytes + items_bytes;
+  if (int rc = ws->sub.reserve (std::max<size_t> (size_t (sub_stride) * n * sizeof (float), 16)))
+    return rc;
+  if (int rc = ws->mags.reserve (std::max<size_t> (size_t (center_stride) * n * sizeof (float2), 16)))
+    return rc;
+  if (int rc = ws->centers.reserve (blob_bytes))
+    return rc;
+  if (int rc = ws->best.reserve (best_bytes))
+    return rc;
+  if (int rc = ws->pin.reserve (std::max<size_t> (blob_bytes + best_bytes, 1 << 16)))
+    return rc;
+  hipStream_t st = lane->stream;
+  char *pin = ws->pin.as<char>(), *dev = ws->centers.as<char>();
+  std::memcpy (pin, cds.data(), n * sizeof (awmk::SpeedCenterDev));
+  std::memcpy (pin + cds_bytes, entries.data(), n * sizeof (awmk::SpeedEntryDev));
+  std::memcpy (pin + cds_bytes + entries_bytes, items.data(), items.size() * sizeof (awmk::SpeedItemDev));
+  AWM_HIP_CHECK (hipMemcpyAsync (dev, pin, blob_bytes, hipMemcpyHostToDevice, st));
+  AWM_HIP_CHECK (hipMemsetAsync (ws->best.ptr, 0, best_bytes, st));
+  const awmk::SpeedCenterDev *cds_d = reinterpret_cast<const awmk::SpeedCenterDev *> (dev);
+  const awmk::SpeedEntryDev *entries_d = reinterpret_cast<const awmk::SpeedEntryDev *> (dev + cds_bytes);
+  ra.n_channels = C;
+  ra.centers = cds_d;
+  ra.out = ws->sub.as<float>();
+  ra.out_stride = sub_stride;
+  {
+    ProfScope ps (ctx, PROF_RESAMPLE_VAR, var_bytes, st);
+    AWM_HIP_CHECK (awmk::launch_resample_var (st, ra, max_out, int (n), entries_d, aligned));
+  }
+  awmk::SpeedMagsArgs ma {};
+  ma.sub = ws->sub.as<float>();
+  ma.sub_stride = sub_stride;
+  ma.n_channels = C;
+  ma.centers = cds_d;
+  ma.window512 = workspace (ctx)->window512.as<float>();
+  ma.mags = ws->mags.as<float2>();
+  ma.mags_center_stride = center_stride;
+  ma.ld = ld;
+  {
+    ProfScope ps (ctx, PROF_SPEED_MAGS, mags_bytes, st);
+    AWM_HIP_CHECK (awmk::launch_speed_mags (st, ctx->tabs, ma, max_rows, int (n), entries_d));
+  }
+  const int steps_per_frame = Params::frame_size / Params::sync_search_step;
+  const int frames_per_block = int (mark_block_frame_count());
+  awmk::SpeedCompareArgs ca {};
+  ca.mags = ws->mags.as<float2>();
+  ca.mags_center_stride = center_stride;
+  ca.ld = ld;
+  ca.centers = cds_d;
+  ca.items = reinterpret_cast<const awmk::SpeedItemDev *> (dev + cds_bytes + entries_bytes);
+  ca.n_centers = int (n);
+  ca.items_per_center = per;
+  ca.frames_per_block = frames_per_block;
+  ca.steps_per_frame = steps_per_frame;
+  ca.pad_start = frames_per_block * steps_per_frame + steps_per_frame;
+  ca.rows_per_bit = Params::sync_frames_per_bit;
+  ca.min_delta = std::min (params().water_delta, 0.080);
+  ca.best = ws->best.as<unsigned long long>();
+  {
+    ProfScope ps (ctx, PROF_SPEED_COMPARE, compare_bytes, st);
+    AWM_HIP_CHECK (awmk::launch_speed_compare (st, ca, int (items.size()), entries_d));
+  }
+  AWM_HIP_CHECK (hipMemcpyAsync (pin + blob_bytes, ws->best.ptr, best_bytes, hipMemcpyDeviceToHost, st));
+  AWM_HIP_CHECK (hipStreamSynchronize (st));
+  const double *best = reinterpret_cast<const double *> (pin + blob_bytes);
+  for (const Part& part : parts)
+    for (size_t i = part.first * per; i < (part.first + part.count) * per; i++)
+      {
+        SpeedScore sc;
+        if (best[i] > 0)
+          {
+            sc.quality = best[i];
+            sc.speed = item_speed[i];
+          }
+        part.item->scores.push_back (sc);
+      }
+  return 0;
+}
+
+int
+detect_speed_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchClip>& clips, std::vector<SpeedBatchResult>& results)
+{
+  results.assign (clips.size(), SpeedBatchResult());
+  if (clips.empty())
+    return 0;
+  const SearchPlan plan = search_plan (params().detect_speed_patient);
+  std::vector<size_t> n_frames;
+  std::vector<int> rates, group;
+  std::vector<size_t> group_bytes;
+  for (const auto& c : clips)
+    {
+      if (c.wav.n_channels != clips[0].wav.n_channels)
+        {
+          set_error ("detect_speed_batch: the clips of a batch have one channel count");
+          return AWM_ERR_ARG;
+        }
+      n_frames.push_back (c.wav.n_frames);
+      rates.push_back (c.wav.sample_rate);
+    }
+  /* "our algorithm won't work at all for very short input files": such a clip is in no sub-group */
+  const int n_groups = speed_batch_plan (n_frames, rates, clips[0].wav.n_channels, params().detect_speed_patient, speed_batch_bytes(), group, group_bytes);
+  std::vector<SpeedBatchItem> items (clips.size());
+  for (int g = 0; g < n_groups; g++)
+    {
+      std::vector<SpeedBatchItem *> batch;
+      for (size_t i = 0; i < clips.size(); i++)
+        if (group[i] == g)
+          {
+            items[i].key = clips[i].key;
+            items[i].wav = clips[i].wav;
+            batch.push_back (&items[i]);
+          }
+      if (int rc = speed_clip_location_batch (ctx, lane, batch, plan.scan1.seconds, clip_candidates))
+        return rc;
+      for (SpeedBatchItem *item : batch)
+        item->speeds = { 1.0 };
+      if (int rc = speed_scan_batch (ctx, lane, batch, plan.scan1))
+        return rc;
+      for (SpeedBatchItem *item : batch)
+        {
+          select_n_best_scores (item->scores, plan.n_best);
+          item->speeds.clear();
+          for (const auto& s : item->scores)
+            item->speeds.push_back (s.speed);
+        }
+      if (int rc = speed_scan_batch (ctx, lane, batch, plan.scan2))
+        return rc;
+      for (SpeedBatchItem *item : batch)
+        {
+          select_n_best_scores (item->scores, 1);
+          item->speeds.clear();
+          if (!item->scores.empty())                       // (empty: the clip takes no part in the last pass, its result stays 0 / 0)
+            item->speeds.push_back (item->scores[0].speed);
+        }
+      if (int rc = speed_scan_batch (ctx, lane, batch, plan.scan3))
+        return rc;
+      for (size_t i = 0; i < clips.size(); i++)
+        if (group[i] == g)
+          {
+            const SpeedBatchItem& item = items[i];
+            SpeedBatchResult& r = results[i];
+            r.rc = item.rc;
+            r.error = item.error;
+            if (item.rc || item.speeds.empty())
+              continue;
+            r.searched = true;
+            r.speed = score_smooth_find_best (item.scores, 1 - plan.scan3.step, scan3_smooth_distance);
+            for (const auto& s : item.scores)
+              r.quality = std::max (r.quality, s.quality);
+            // "speeds closer to 1.0 than this usually work without stretching before decode"
+            r.use = r.quality > speed_sync_threshold && (r.speed < 0.9999 || r.speed > 1.0001);
+          }
     }
   return 0;
 }

@@ -6,6 +6,7 @@
 // kernels per pass (hip/speed.hip); the host keeps the reference's control flow between the passes.
 #pragma once
 #include <memory>
+#include <string>
 #include <vector>
 #include "context.hh"
 #include "random.hh"
@@ -126,5 +127,50 @@ double score_smooth_find_best (const std::vector<SpeedScore>& scores, double ste
  * with print_results (the caller prints them: several chunks may be searching at the same time). */
 int detect_speed (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_list, const DeviceWav& wav, std::string *report,
                   std::vector<DetectSpeedResult>& results, double *best_speed = nullptr, double *best_quality = nullptr);
+
+/* ---- batches of clips: the passes of detect_speed in lockstep, one launch per kernel and pass for a sub-group of clips ---- */
+/* sub + mags of the first pass that a sub-group may ask for (one 30 s stereo clip: 1.25 GB non-patient); a sub-group holds one clip
+ * at least.  awm_debug_set_speed_batch_bytes.  Measured (profiles/get_batch_speed, the clip batches with awm_debug_set_speed_batch (1)):
+ * 64 clips 294 / 284 / 275 ms at 4 / 12 / 32 GiB, 1024 clips no difference beyond the spread; larger budgets were not measured.  The
+ * scratch is per lane and grow-only: what a search grew it to stays until awm_ctx_trim */
+constexpr size_t SPEED_BATCH_BYTES = size_t (32) << 30;
+constexpr size_t SPEED_BATCH_MAX_CLIPS = 512;               // per sub-group: 57 centres each stay below
+constexpr size_t SPEED_BATCH_MAX_ENTRIES = 65535;           // ... the (clip, centre) pairs of one launch (blockIdx.y)
+void   speed_batch_set_bytes (size_t bytes);                // 0: the default
+size_t speed_batch_bytes();
+
+struct SpeedBatchClip
+{
+  Key       key;
+  DeviceWav wav;
+};
+struct SpeedBatchResult
+{
+  int    rc = 0;            // < 0: the search of this clip failed where the one-clip search fails (digital silence: a speed the resampler refuses)
+  bool   searched = false;  // best speed and quality are those of a finished search
+  bool   use = false;       // decode at `speed` (detect_speed would return { key, speed })
+  double speed = 0, quality = 0;
+  std::string error;        // rc < 0: the error text
+};
+/* one clip of a batch pass: clip location and speeds in, scores out (speed_scan's order); rc as in SpeedBatchResult */
+struct SpeedBatchItem
+{
+  Key                     key;
+  DeviceWav               wav;
+  double                  clip_location = 0;
+  std::vector<double>     speeds;
+  std::vector<SpeedScore> scores;
+  int                     rc = 0;
+  std::string             error;
+};
+/* which sub-group every clip of a batch search is in (-1: under 0.25 s, no search) and what each sub-group's first pass asks for;
+ * clips stay in order, a sub-group is closed by the first clip with which it would pass `budget`.  Pure host. */
+int speed_batch_plan (const std::vector<size_t>& n_frames, const std::vector<int>& rates, int n_channels, bool patient, size_t budget,
+                      std::vector<int>& group_of_clip, std::vector<size_t>& bytes_of_group);
+/* speed_clip_location / speed_scan for every clip of `batch` (one channel count), results equal to the one-clip calls bit for bit */
+int speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, double seconds, int candidates);
+int speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, const SpeedScanParams& scan_params);
+/* detect_speed (params().detect_speed_patient) for clips with a key each, sub-group after sub-group */
+int detect_speed_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchClip>& clips, std::vector<SpeedBatchResult>& results);
 
 } // namespace awm

@@ -547,7 +547,8 @@ int awm_get_watermark_batch_keys_rate_d (awm_ctx *ctx, const uint8_t *keys, size
  * call order WHATEVER THEIR RATES; stage 0 of a group whose clips do not share one rate is the same launcher (every clip resampled with its own
  * rate's table, or copied, straight into its padded slice: one launch per form present in the group, not per clip or rate), a group that
  * happens to share one rate runs as in the one-rate call.  Long clips, VResampler rates and 44.1 kHz long clips go over the work lanes, each
- * resampled with its own rate into its lane's grow-only workspace first; so does every clip while a speed parameter is set.  A call
+ * resampled with its own rate into its lane's grow-only workspace first; so does every clip while a speed parameter is set (one clip
+ * per lane and host thread, in parallel, each with the one-clip speed search; awm_debug_set_speed_batch).  A call
  * whose rates are all equal IS the one-rate function above (44100: the 44.1 kHz function).
  * Refusals, AWM_ERR_ARG with nothing enqueued and n_out / out untouched, awm_last_error names the index of the first offending clip:
  * sample_rates NULL with n_clips > 0, a sample_rates[i] <= 0, a ratio that neither zita class takes (awm_resample_frames gives 0 for a
@@ -761,6 +762,44 @@ int awm_speed_mags_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, s
 int awm_speed_scan_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels, int rate,
                       double clip_location, double seconds, double step, int n_steps, int n_center_steps,
                       const double *speeds, int n_speeds, size_t max_out, double *out_speed, double *out_quality);
+
+/* detect_speed for a batch of clips, the batch of awm_detect_speed_d: clip i with keys (16 bytes) or keys + 16 i (key_per_clip != 0).
+ * The passes of the search run in lockstep for sub-groups of clips -- one launch per kernel and pass, one synchronisation between
+ * passes for the whole sub-group (the batch forms of K12 - K15, speed.hip) -- and every clip's result is bit for bit that of the
+ * one-clip call: use_out[i] = 1 / 0 as awm_detect_speed_d returns them, speed_out[i] / quality_out[i] its speed and quality; a clip
+ * under 0.25 s has 0, 0, 0.  A clip on which the one-clip call fails (digital silence: AWM_ERR_ARG, "failed to setup vresampler")
+ * has that error code in use_out[i] and 0, 0; the other clips are not affected and the call returns 0.  The clips are read where
+ * they lie and need 4 byte alignment only.  AWM_ERR_ARG with nothing enqueued and the outputs untouched: a null pcm_d[i] with
+ * n_frames[i] > 0, n_channels < 1, rate <= 0.  n_clips == 0 returns 0.
+ * A sub-group is as many clips, in order, as fit a byte budget for the first pass's scratch (sub + mags, about 1.25 GB per 30 s
+ * stereo clip); awm_debug_set_speed_batch_bytes changes it (0: the default), awm_speed_batch_plan (pure host) returns the number of
+ * sub-groups and writes every clip's sub-group (-1: under 0.25 s) and every sub-group's bytes (n_clips entries at most; may be null);
+ * budget_bytes 0: the current setting.  Memory: the default budget is 32 GiB, the largest of three measured values (4 / 12 / 32 GiB;
+ * larger ones were not measured, the times were still falling).  The scratch is per lane and grow-only: one call with 27 or more
+ * stereo clips of 30 s grows the lane's scratch to about 32 GiB, and it stays until awm_ctx_trim; a caller short of memory sets a
+ * smaller budget first (a sub-group of one clip asks for 1.25 GB).  awm_debug_speed_batch_launches: launches of the batch kernels so far (K15: gather + energy). */
+int  awm_detect_speed_batch_d (awm_ctx *ctx, const uint8_t *keys, int key_per_clip, size_t n_clips, const float *const *pcm_d,
+                               const size_t *n_frames, int n_channels, int rate, int patient, double *speed_out, double *quality_out,
+                               int *use_out);
+void awm_debug_set_speed_batch_bytes (size_t bytes);
+size_t awm_debug_speed_batch_bytes (void);             /* the budget in force */
+int  awm_speed_batch_plan (size_t n_clips, const size_t *n_frames, int n_channels, int rate, int patient, size_t budget_bytes,
+                           int *group_of_clip, size_t *bytes_of_group);
+void awm_debug_speed_batch_launches (int *k12, int *k13, int *k14, int *k15);
+/* (A / B) how the batches of clips (awm_get_watermark_batch_d and its forms) work under a speed parameter.  0, the default: every clip
+ * over the work lanes in parallel with the one-clip search.  1: the short clips keep their groups (float or 16-bit, 44.1 kHz or another
+ * fixed-ratio rate); after stage 0 of a group the speed search of its clips runs as a batch on the slices (awm_detect_speed_batch_d's
+ * way, on the group's lane, whose search scratch grows to the byte budget), the stretched decodes of the clips with a speed run over the
+ * lanes afterwards; measured slower than 0 (profiles/get_batch_speed).  2: one clip after the other on the context's own lane (what the batches did before; kept for
+ * tools/gpu_get_batch_speed.py).  The results are the same in all three. */
+void awm_debug_set_speed_batch (int mode);
+/* the batch of awm_speed_scan_d: ONE pass over several clips in one launch per kernel, clip i with its own clip location and its
+ * own n_speeds[i] speeds (`speeds`: all lists back to back); scores of clip i sorted by speed at out_*[i * max_out_per_clip ...],
+ * n_out[i] their number (or the clip's error code) */
+int  awm_debug_speed_scan_batch_d (awm_ctx *ctx, const uint8_t *keys, int key_per_clip, size_t n_clips, const float *const *pcm_d,
+                                   const size_t *n_frames, int n_channels, int rate, const double *clip_locations, double seconds,
+                                   double step, int n_steps, int n_center_steps, const double *speeds, const int *n_speeds,
+                                   size_t max_out_per_clip, double *out_speed, double *out_quality, int *n_out);
 
 /* host side pieces of the search (pure host, no GPU): select_n_best_scores (wmspeed.cc:494-531; in place, returns the new
  * count), score_smooth_find_best (:397-428), and the two halves of get_clip_locations (:533-553): the sample positions that
