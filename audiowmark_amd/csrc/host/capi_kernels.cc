@@ -5045,6 +5045,20 @@ awm_speed_mags_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_
   return rows;
 }
 
+namespace {
+// the scores of a pass as the scan entry points give them out: sorted by speed, up to max_out of them
+void
+write_scores_by_speed (std::vector<SpeedScore>& scores, size_t max_out, double *out_speed, double *out_quality)
+{
+  std::sort (scores.begin(), scores.end(), [] (const SpeedScore& a, const SpeedScore& b) { return a.speed < b.speed; });
+  for (size_t i = 0; i < scores.size() && i < max_out; i++)
+    {
+      out_speed[i] = scores[i].speed;
+      out_quality[i] = scores[i].quality;
+    }
+}
+}
+
 int
 awm_speed_scan_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels, int rate,
                   double clip_location, double seconds, double step, int n_steps, int n_center_steps,
@@ -5055,12 +5069,7 @@ awm_speed_scan_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_
   if (int rc = speed_scan (ctx, ctx, capi_key (key), make_wav_rate (pcm_d, n_frames, n_channels, rate), clip_location,
                            { seconds, step, n_steps, n_center_steps }, std::vector<double> (speeds, speeds + n_speeds), scores))
     return rc;
-  std::sort (scores.begin(), scores.end(), [] (const SpeedScore& a, const SpeedScore& b) { return a.speed < b.speed; });
-  for (size_t i = 0; i < scores.size() && i < max_out; i++)
-    {
-      out_speed[i] = scores[i].speed;
-      out_quality[i] = scores[i].quality;
-    }
+  write_scores_by_speed (scores, max_out, out_speed, out_quality);
   return int (scores.size());
 }
 
@@ -5193,14 +5202,8 @@ awm_debug_speed_scan_batch_d (awm_ctx *ctx, const uint8_t *keys, int key_per_cli
     return rc;
   for (size_t i = 0; i < n_clips; i++)
     {
-      std::vector<SpeedScore>& scores = items[i].scores;
-      std::sort (scores.begin(), scores.end(), [] (const SpeedScore& a, const SpeedScore& b) { return a.speed < b.speed; });
-      for (size_t k = 0; k < scores.size() && k < max_out_per_clip; k++)
-        {
-          out_speed[i * max_out_per_clip + k] = scores[k].speed;
-          out_quality[i * max_out_per_clip + k] = scores[k].quality;
-        }
-      n_out[i] = items[i].rc ? items[i].rc : int (scores.size());
+      write_scores_by_speed (items[i].scores, max_out_per_clip, out_speed + i * max_out_per_clip, out_quality + i * max_out_per_clip);
+      n_out[i] = items[i].rc ? items[i].rc : int (items[i].scores.size());
     }
   return 0;
 }

@@ -30,7 +30,7 @@ SpeedWorkspace::release()
 void
 SpeedScratch::release()
 {
-  for (DevBuffer *b : { &sub, &mags, &centers, &items, &best, &gather_pos, &gather_out, &ranges, &energy, &stretched })
+  for (DevBuffer *b : { &sub, &mags, &centers, &best, &gather_pos, &gather_out, &ranges, &energy, &stretched })
     b->release();
   pin.release();
 }
@@ -203,15 +203,13 @@ awmk::SpeedCenterDev
 center_dev (const VarResampleTable *vt, double ratio, long long n_in, long long n_out)
 {
   awmk::SpeedCenterDev cd {};
-  const double step = 256 / ratio;
-  int e = 0;
-  const double f = std::frexp (step, &e);                  // step = f * 2^e, 0.5 <= f < 1
+  const VarResampleGeometry g = var_resample_geometry (ratio);     // (ok: the ratio has a table)
   cd.ctab = vt->ctab;
   cd.hl = vt->hl;
   cd.stride = vt->hl | 1;
-  cd.mant = (unsigned long long) std::ldexp (f, 53);       // step = mant * 2^(e - 53)
-  cd.shift = 61 - e;                                       // m * step / 256 = (m * mant) >> shift
-  cd.frac_scale = std::ldexp (1.0, e - 53);
+  cd.mant = g.mant;
+  cd.shift = g.shift;
+  cd.frac_scale = std::ldexp (1.0, 8 - g.shift);           // step = mant * 2^(e - 53), e - 53 = 8 - shift
   cd.n_in = n_in;
   cd.n_out = n_out;
   cd.rows = 0;
@@ -327,92 +325,45 @@ constexpr double scan3_smooth_distance = 20;
 constexpr double speed_sync_threshold = 0.4;
 constexpr int    clip_candidates = 5;
 
-/* resample + STFT + column sums of all centres of a pass; leaves the matrices in ws->mags */
-int
-prepare_mags (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& clip, double seconds, std::vector<ScanCenter>& centers,
-              long long *ld_out, long long *center_stride_out)
+/* "our algorithm won't work at all for very short input files" */
+bool
+long_enough_to_search (size_t n_frames, int rate)
 {
-  SpeedScratch *ws = speed_scratch (lane);
-  SpeedKeyTables *skt = get_speed_key_tables (ctx, key);
-  if (!skt)
-    return AWM_ERR_HIP;
-  if (int rc = ensure_window (ctx))
-    return rc;
-  const int C = clip.n_channels;
-  std::vector<double> ratios;
-  for (auto& c : centers)
-    ratios.push_back (c.speed / 2);
-  std::vector<VarResampleTable *> tables;
-  if (int rc = get_var_tables (ctx, ratios, tables))
-    return rc;
-  long long max_out = 0;
-  int max_rows = 0;
-  std::vector<awmk::SpeedCenterDev> cds;
-  for (size_t i = 0; i < centers.size(); i++)
-    {
-      ScanCenter& c = centers[i];
-      c.table = tables[i];
-      center_geometry (clip, seconds, c);
-      awmk::SpeedCenterDev cd = center_dev (c.table, ratios[i], c.n_in, c.n_out);
-      cd.rows = c.rows;
-      cds.push_back (cd);
-      max_out = std::max (max_out, c.n_out);
-      max_rows = std::max (max_rows, c.rows);
-    }
-  const long long ld = (max_rows + 15) / 16 * 16;
-  const long long sub_stride = (max_out * C + 3) / 4 * 4;
-  const long long center_stride = 510 * ld;
-  if (int rc = ws->sub.reserve (std::max<size_t> (size_t (sub_stride) * centers.size() * sizeof (float), 16)))
-    return rc;
-  if (int rc = ws->mags.reserve (std::max<size_t> (size_t (center_stride) * centers.size() * sizeof (float2), 16)))
-    return rc;
-  if (int rc = ws->centers.reserve (cds.size() * sizeof (awmk::SpeedCenterDev)))
-    return rc;
-  if (int rc = ws->pin.reserve (std::max<size_t> (cds.size() * sizeof (awmk::SpeedCenterDev), 1 << 16)))
-    return rc;
-  hipStream_t st = lane->stream;
-  std::memcpy (ws->pin.ptr, cds.data(), cds.size() * sizeof (awmk::SpeedCenterDev));
-  AWM_HIP_CHECK (hipMemcpyAsync (ws->centers.ptr, ws->pin.ptr, cds.size() * sizeof (awmk::SpeedCenterDev), hipMemcpyHostToDevice, st));
-  awmk::VarResampleArgs ra {};
-  ra.in = clip.data;
-  ra.n_channels = C;
-  ra.centers = ws->centers.as<awmk::SpeedCenterDev>();
-  ra.out = ws->sub.as<float>();
-  ra.out_stride = sub_stride;
-  for (const auto& cd : cds)
-    {
-      ra.max_stride = std::max (ra.max_stride, cd.stride);
-      ra.max_step = std::max (ra.max_step, std::ldexp (double (cd.mant), -cd.shift));
-    }
-  double var_bytes = 0, mags_bytes = 0;
-  for (const auto& c : centers)
-    {
-      var_bytes += double (c.n_in + c.n_out) * C * 4.0;                   // K12: the clip in, the resampled clip out, per centre speed
-      mags_bytes += double (c.n_out) * C * 4.0 + double (c.rows) * 510 * 8.0;   // K13: the resampled clip once, { umag, dmag } per row and sync frame out
-    }
-  {
-    ProfScope ps (ctx, PROF_RESAMPLE_VAR, var_bytes, st);
-    AWM_HIP_CHECK (awmk::launch_resample_var (st, ra, max_out, int (centers.size())));
-  }
-  awmk::SpeedMagsArgs ma {};
-  ma.sub = ws->sub.as<float>();
-  ma.sub_stride = sub_stride;
-  ma.n_channels = C;
-  ma.centers = ra.centers;
-  ma.window512 = workspace (ctx)->window512.as<float>();        // (built by ensure_window above; never replaced)
-  ma.cols = skt->cols.as<unsigned int>();
-  ma.mags = ws->mags.as<float2>();
-  ma.mags_center_stride = center_stride;
-  ma.ld = ld;
-  {
-    ProfScope ps (ctx, PROF_SPEED_MAGS, mags_bytes, st);
-    AWM_HIP_CHECK (awmk::launch_speed_mags (st, ctx->tabs, ma, max_rows, int (centers.size())));
-  }
-  AWM_HIP_CHECK (hipStreamSynchronize (st));               // the pinned staging area is reused by the caller
-  *ld_out = ld;
-  *center_stride_out = center_stride;
-  return 0;
+  return rate > 0 && double (n_frames) / rate >= 0.25;
 }
+
+/* the part of the input a pass reads (SpeedSearch::get_jobs, reference wmspeed.cc:461-492): "speed is between 0.8 and 1.25, so we
+ * use a clip seconds factor of 1.3 to provide enough samples" */
+DeviceWav
+scan_clip (const DeviceWav& wav, double clip_location, const SpeedScanParams& sp)
+{
+  size_t start_point, end_point;
+  speed_clip_range (clip_location, wav, sp.seconds * 1.3, &start_point, &end_point);
+  DeviceWav clip = wav;
+  clip.data = wav.data + start_point * wav.n_channels;
+  clip.n_frames = end_point - start_point;
+  return clip;
+}
+
+/* the centres of a pass around `speed`, -n_center_steps .. n_center_steps */
+void
+append_centers (const SpeedScanParams& sp, double speed, std::vector<ScanCenter>& centers)
+{
+  for (int c = -sp.n_center_steps; c <= sp.n_center_steps; c++)
+    centers.push_back ({ speed * std::pow (sp.step, c * (sp.n_steps * 2 + 1)), nullptr, 0, 0, 0 });
+}
+
+/* sub and mags keep one stride per launch, the largest any of its centres needs (the pass reserves them, the planner counts them) */
+struct PassStrides
+{
+  long long max_out = 0;
+  int       max_rows = 0;
+  void      add (const ScanCenter& c)    { max_out = std::max (max_out, c.n_out); max_rows = std::max (max_rows, c.rows); }
+  void      add (const PassStrides& s)   { max_out = std::max (max_out, s.max_out); max_rows = std::max (max_rows, s.max_rows); }
+  long long sub_stride (int C) const     { return (max_out * C + 3) / 4 * 4; }
+  long long ld() const                   { return (max_rows + 15) / 16 * 16; }
+  long long center_stride() const        { return 510 * ld(); }
+};
 
 } // namespace
 
@@ -430,11 +381,11 @@ var_resample_geometry (double ratio)
   if (!vg.ok)
     return g;
   int e = 0;
-  const double f = std::frexp (vg.step, &e);
+  const double f = std::frexp (vg.step, &e);               // step = f * 2^e, 0.5 <= f < 1
   g.ok = true;
   g.hl = int (vg.hl);
-  g.mant = (unsigned long long) std::ldexp (f, 53);
-  g.shift = 61 - e;
+  g.mant = (unsigned long long) std::ldexp (f, 53);        // step = mant * 2^(e - 53)
+  g.shift = 61 - e;                                        // m * step / 256 = (m * mant) >> shift
   return g;
 }
 
@@ -499,206 +450,6 @@ resample_ratio_device (awm_ctx *ctx, WorkLane *lane, const DeviceWav& wav, doubl
   return resample_var_device (ctx, lane, wav.data, in_frames, C, ratio, out.as<float>(), size_t (n_out));
 }
 
-int
-speed_clip_location (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& wav, double seconds, int candidates, double *location)
-{
-  (void) ctx;
-  SpeedScratch *ws = speed_scratch (lane);
-  hipStream_t st = lane->stream;
-  /* get_clip_locations (reference wmspeed.cc:533-553): hash a sparse subset of the samples */
-  Random rng (key, 0, Random::Stream::speed_clip);
-  std::vector<unsigned long long> pos;
-  const size_t n_values = wav.n_values();
-  pos.reserve (n_values / 400 + 16);
-  for (size_t p = 0; p < n_values; p += rng() % 1000)
-    pos.push_back (p);
-  const size_t pos_bytes = pos.size() * sizeof (unsigned long long), val_bytes = pos.size() * sizeof (float);
-  if (int rc = ws->gather_pos.reserve (std::max<size_t> (pos_bytes, 16)))
-    return rc;
-  if (int rc = ws->gather_out.reserve (std::max<size_t> (val_bytes, 16)))
-    return rc;
-  if (int rc = ws->pin.reserve (std::max<size_t> (std::max (pos_bytes, val_bytes), 1 << 16)))
-    return rc;
-  std::memcpy (ws->pin.ptr, pos.data(), pos_bytes);
-  AWM_HIP_CHECK (hipMemcpyAsync (ws->gather_pos.ptr, ws->pin.ptr, pos_bytes, hipMemcpyHostToDevice, st));
-  AWM_HIP_CHECK (awmk::launch_gather_values (st, wav.data, ws->gather_pos.as<unsigned long long>(), (long long) pos.size(), ws->gather_out.as<float>()));
-  AWM_HIP_CHECK (hipStreamSynchronize (st));               // the staging area changes direction
-  AWM_HIP_CHECK (hipMemcpyAsync (ws->pin.ptr, ws->gather_out.ptr, val_bytes, hipMemcpyDeviceToHost, st));
-  AWM_HIP_CHECK (hipStreamSynchronize (st));
-  unsigned char hash[20];
-  sha1 (ws->pin.ptr, val_bytes, hash);                     // Random::seed_from_hash (reference random.cc:184-190)
-  uint64_t seed = 0;
-  for (int i = 0; i < 8; i++)
-    seed = (seed << 8) | hash[i];
-  rng.seed (seed, Random::Stream::speed_clip);
-  std::vector<double> locations;
-  for (int c = 0; c < candidates; c++)
-    locations.push_back (rng.random_double());
-
-  /* get_best_clip_location (reference wmspeed.cc:555-577): the candidate with the highest energy */
-  std::vector<long long> ranges;
-  for (double loc : locations)
-    {
-      size_t start_point, end_point;
-      speed_clip_range (loc, wav, seconds, &start_point, &end_point);
-      ranges.push_back ((long long) (start_point * wav.n_channels));
-      ranges.push_back ((long long) (end_point * wav.n_channels));
-    }
-  const size_t e_bytes = size_t (candidates) * awmk::ENERGY_PARTS * sizeof (double);
-  if (int rc = ws->ranges.reserve (ranges.size() * sizeof (long long)))
-    return rc;
-  if (int rc = ws->energy.reserve (e_bytes))
-    return rc;
-  std::memcpy (ws->pin.ptr, ranges.data(), ranges.size() * sizeof (long long));
-  AWM_HIP_CHECK (hipMemcpyAsync (ws->ranges.ptr, ws->pin.ptr, ranges.size() * sizeof (long long), hipMemcpyHostToDevice, st));
-  AWM_HIP_CHECK (awmk::launch_energy (st, wav.data, ws->ranges.as<long long>(), candidates, ws->energy.as<double>()));
-  AWM_HIP_CHECK (hipStreamSynchronize (st));
-  AWM_HIP_CHECK (hipMemcpyAsync (ws->pin.ptr, ws->energy.ptr, e_bytes, hipMemcpyDeviceToHost, st));
-  AWM_HIP_CHECK (hipStreamSynchronize (st));
-  const double *parts = ws->pin.as<double>();
-  double clip_location = 0, best_energy = 0;
-  for (int c = 0; c < candidates; c++)
-    {
-      double energy = 0;
-      for (int k = 0; k < awmk::ENERGY_PARTS; k++)
-        energy += parts[c * awmk::ENERGY_PARTS + k];
-      if (energy > best_energy)
-        {
-          best_energy = energy;
-          clip_location = locations[c];
-        }
-    }
-  *location = clip_location;
-  return 0;
-}
-
-int
-speed_scan (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& wav, double clip_location, const SpeedScanParams& sp,
-            const std::vector<double>& speeds, std::vector<SpeedScore>& scores)
-{
-  SpeedScratch *ws = speed_scratch (lane);
-  scores.clear();
-  /* SpeedSearch::get_jobs (reference wmspeed.cc:461-492): "speed is between 0.8 and 1.25, so we use a clip seconds
-   * factor of 1.3 to provide enough samples" */
-  size_t start_point, end_point;
-  speed_clip_range (clip_location, wav, sp.seconds * 1.3, &start_point, &end_point);
-  DeviceWav clip = wav;
-  clip.data = wav.data + start_point * wav.n_channels;
-  clip.n_frames = end_point - start_point;
-  std::vector<ScanCenter> centers;
-  for (double speed : speeds)
-    for (int c = -sp.n_center_steps; c <= sp.n_center_steps; c++)
-      centers.push_back ({ speed * std::pow (sp.step, c * (sp.n_steps * 2 + 1)), nullptr, 0, 0, 0 });
-  if (centers.empty())
-    return 0;
-  long long ld = 0, center_stride = 0;
-  if (int rc = prepare_mags (ctx, lane, key, clip, sp.seconds, centers, &ld, &center_stride))
-    return rc;
-  SpeedKeyTables *skt = get_speed_key_tables (ctx, key);
-  /* SpeedSync::get_jobs (reference wmspeed.cc:172-192): relative speeds step^p, p = -n_steps .. n_steps, per centre */
-  std::vector<awmk::SpeedItemDev> items;
-  std::vector<double> item_speed;
-  for (size_t ci = 0; ci < centers.size(); ci++)
-    for (int p = -sp.n_steps; p <= sp.n_steps; p++)
-      {
-        const double center = centers[ci].speed;
-        const double relative_speed = std::pow (sp.step, p) * center / center;
-        awmk::SpeedItemDev it {};
-        it.center = int (ci);
-        it.rel_speed_inv = 1 / relative_speed;
-        it.q16_scale = (1 << 16) / relative_speed;
-        items.push_back (it);
-        item_speed.push_back (relative_speed * center);
-      }
-  const size_t items_bytes = items.size() * sizeof (awmk::SpeedItemDev), best_bytes = items.size() * sizeof (unsigned long long);
-  if (int rc = ws->items.reserve (items_bytes))
-    return rc;
-  if (int rc = ws->best.reserve (best_bytes))
-    return rc;
-  if (int rc = ws->pin.reserve (std::max<size_t> (std::max (items_bytes, best_bytes), 1 << 16)))
-    return rc;
-  hipStream_t st = lane->stream;
-  std::memcpy (ws->pin.ptr, items.data(), items_bytes);
-  AWM_HIP_CHECK (hipMemcpyAsync (ws->items.ptr, ws->pin.ptr, items_bytes, hipMemcpyHostToDevice, st));
-  AWM_HIP_CHECK (hipMemsetAsync (ws->best.ptr, 0, best_bytes, st));
-  const int steps_per_frame = Params::frame_size / Params::sync_search_step;
-  const int frames_per_block = int (mark_block_frame_count());
-  awmk::SpeedCompareArgs ca {};
-  ca.mags = ws->mags.as<float2>();
-  ca.mags_center_stride = center_stride;
-  ca.ld = ld;
-  ca.centers = ws->centers.as<awmk::SpeedCenterDev>();
-  ca.items = ws->items.as<awmk::SpeedItemDev>();
-  ca.n_centers = int (centers.size());
-  ca.items_per_center = 2 * sp.n_steps + 1;
-  ca.col_frame = skt->col_frame.as<int>();
-  ca.col_first = skt->col_first.as<unsigned char>();
-  ca.frames_per_block = frames_per_block;
-  ca.steps_per_frame = steps_per_frame;
-  ca.pad_start = frames_per_block * steps_per_frame + steps_per_frame;      // "a bit of overlap to handle boundaries"
-  ca.rows_per_bit = Params::sync_frames_per_bit;
-  ca.min_delta = std::min (params().water_delta, 0.080);
-  ca.best = ws->best.as<unsigned long long>();
-  {
-    // K14: every centre's { umag, dmag } matrix once (its 2 n_steps + 1 relative speeds share it) + one best score per item
-    double bytes = double (items.size()) * 8.0;
-    for (const auto& c : centers)
-      bytes += double (c.rows) * 510 * 8.0;
-    ProfScope ps (ctx, PROF_SPEED_COMPARE, bytes, st);
-    AWM_HIP_CHECK (awmk::launch_speed_compare (st, ca, int (items.size())));
-  }
-  AWM_HIP_CHECK (hipStreamSynchronize (st));
-  AWM_HIP_CHECK (hipMemcpyAsync (ws->pin.ptr, ws->best.ptr, best_bytes, hipMemcpyDeviceToHost, st));
-  AWM_HIP_CHECK (hipStreamSynchronize (st));
-  const double *best = ws->pin.as<double>();
-  for (size_t i = 0; i < items.size(); i++)
-    {
-      SpeedScore sc;                                       // "Score best_score": stays { 0, 0 } unless a state has quality > 0
-      if (best[i] > 0)
-        {
-          sc.quality = best[i];
-          sc.speed = item_speed[i];
-        }
-      scores.push_back (sc);
-    }
-  return 0;
-}
-
-int
-speed_mags (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& wav, double clip_location, double center, double seconds,
-            std::vector<float>& out, int *rows)
-{
-  SpeedScratch *ws = speed_scratch (lane);
-  size_t start_point, end_point;
-  speed_clip_range (clip_location, wav, seconds * 1.3, &start_point, &end_point);
-  DeviceWav clip = wav;
-  clip.data = wav.data + start_point * wav.n_channels;
-  clip.n_frames = end_point - start_point;
-  std::vector<ScanCenter> centers { { center, nullptr, 0, 0, 0 } };
-  long long ld = 0, center_stride = 0;
-  if (int rc = prepare_mags (ctx, lane, key, clip, seconds, centers, &ld, &center_stride))
-    return rc;
-  KeyTables *kt = ctx->get_key_tables (key);
-  const SyncTable& stab = kt->sync[0].host;
-  std::vector<float2> m (size_t (510) * ld);
-  AWM_HIP_CHECK (hipMemcpy (m.data(), ws->mags.ptr, m.size() * sizeof (float2), hipMemcpyDeviceToHost));
-  // back to the reference's column order (all 510 sync frames sorted by frame)
-  std::vector<int> order (510);
-  for (int i = 0; i < 510; i++)
-    order[i] = i;
-  std::sort (order.begin(), order.end(), [&] (int a, int b) { return stab.frame[a] < stab.frame[b]; });
-  *rows = centers[0].rows;
-  out.assign (size_t (*rows) * 510 * 2, 0.f);
-  for (int r = 0; r < *rows; r++)
-    for (int c = 0; c < 510; c++)
-      {
-        const float2 v = m[size_t (order[c]) * ld + r];
-        out[(size_t (r) * 510 + c) * 2] = v.x;
-        out[(size_t (r) * 510 + c) * 2 + 1] = v.y;
-      }
-  return 0;
-}
-
 void
 select_n_best_scores (std::vector<SpeedScore>& scores, size_t n)
 {
@@ -746,67 +497,13 @@ score_smooth_find_best (const std::vector<SpeedScore>& in_scores, double step, d
   return best_speed;
 }
 
-int
-detect_speed (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_list, const DeviceWav& wav, std::string *report,
-              std::vector<DetectSpeedResult>& results, double *best_speed_out, double *best_quality_out)
-{
-  results.clear();
-  /* "our algorithm won't work at all for very short input files" */
-  const double in_seconds = double (wav.n_frames) / wav.sample_rate;
-  if (in_seconds < 0.25)
-    return 0;
-  const SearchPlan plan = search_plan (params().detect_speed_patient);
-  const SpeedScanParams &scan1 = plan.scan1, &scan2 = plan.scan2, &scan3 = plan.scan3;
-  const size_t n_best = plan.n_best;
-  for (const Key& key : key_list)
-    {
-      double clip_location = 0;
-      if (int rc = speed_clip_location (ctx, lane, key, wav, scan1.seconds, clip_candidates, &clip_location))
-        return rc;
-      std::vector<SpeedScore> scores;
-      if (int rc = speed_scan (ctx, lane, key, wav, clip_location, scan1, { 1.0 }, scores))
-        return rc;
-      select_n_best_scores (scores, n_best);
-      std::vector<double> speeds;
-      for (const auto& s : scores)
-        speeds.push_back (s.speed);
-      if (int rc = speed_scan (ctx, lane, key, wav, clip_location, scan2, speeds, scores))
-        return rc;
-      select_n_best_scores (scores, 1);
-      if (scores.empty())
-        continue;
-      if (int rc = speed_scan (ctx, lane, key, wav, clip_location, scan3, { scores[0].speed }, scores))
-        return rc;
-      const double best_speed = score_smooth_find_best (scores, 1 - scan3.step, scan3_smooth_distance);
-      double best_quality = 0;
-      for (const auto& s : scores)
-        best_quality = std::max (best_quality, s.quality);
-      if (report)
-        {
-          double delta = -1;
-          if (params().test_speed > 0)
-            delta = 100 * std::fabs (best_speed - params().test_speed) / params().test_speed;
-          *report += string_printf ("detect_speed %f %f %.4f\n", best_speed, best_quality, delta);
-        }
-      if (best_speed_out)
-        *best_speed_out = best_speed;
-      if (best_quality_out)
-        *best_quality_out = best_quality;
-      if (best_quality > speed_sync_threshold)
-        {
-          // "speeds closer to 1.0 than this usually work without stretching before decode"
-          if (best_speed < 0.9999 || best_speed > 1.0001)
-            results.push_back ({ key, best_speed });
-        }
-    }
-  return 0;
-}
-
 /* ------------------------------------------------------------------------------------------------------------------
- * Batches: the same passes for several clips in lockstep.  An entry of a launch is a (clip, centre) pair: entry e has its
- * SpeedCenterDev (n_in, n_out, rows of its clip at that centre) and a SpeedEntryDev (the clip's pointer, the tables of its
- * key); sub and mags keep one stride per launch, the largest any entry needs.  Descriptors of a pass travel in one copy,
- * its scores come back in one copy behind one synchronisation.
+ * The search: clip location, three passes and the decisions between them, for one clip (SpeedForm::ONE_CLIP) or for
+ * several clips in lockstep (SpeedForm::BATCH).  An entry of a launch is a (clip, centre) pair: entry e has its
+ * SpeedCenterDev (n_in, n_out, rows of its clip at that centre) and, in the batch form, a SpeedEntryDev (the clip's
+ * pointer, the tables of its key); sub and mags keep one stride per launch, the largest any entry needs.  Descriptors
+ * of a pass travel in one copy, its scores come back in one copy behind one synchronisation.  The form selects the
+ * kernels (the launchers take the entries or nullptr), nothing else.
  * ------------------------------------------------------------------------------------------------------------------ */
 namespace {
 
@@ -818,29 +515,24 @@ align16 (size_t n)
   return (n + 15) & ~size_t (15);
 }
 
-/* bytes of sub + mags the first pass needs per centre of this clip, as launch strides (the largest centre of the clip) */
-void
-scan1_strides (size_t n_frames, int n_channels, int rate, const SpeedScanParams& sp, long long *sub_stride, long long *ld)
+/* what the first pass asks for per centre of this clip (the clip's length at location 0) */
+PassStrides
+scan1_strides (size_t n_frames, int n_channels, int rate, const SpeedScanParams& sp)
 {
   DeviceWav wav {};
   wav.n_frames = n_frames;
   wav.n_channels = n_channels;
   wav.sample_rate = rate;
-  size_t start_point, end_point;
-  speed_clip_range (0, wav, sp.seconds * 1.3, &start_point, &end_point);
-  DeviceWav clip = wav;
-  clip.n_frames = end_point - start_point;
-  long long max_out = 0;
-  int max_rows = 0;
-  for (int c = -sp.n_center_steps; c <= sp.n_center_steps; c++)
+  const DeviceWav clip = scan_clip (wav, 0, sp);
+  std::vector<ScanCenter> centers;
+  append_centers (sp, 1.0, centers);
+  PassStrides strides;
+  for (ScanCenter& c : centers)
     {
-      ScanCenter sc { std::pow (sp.step, c * (sp.n_steps * 2 + 1)), nullptr, 0, 0, 0 };
-      center_geometry (clip, sp.seconds, sc);
-      max_out = std::max (max_out, sc.n_out);
-      max_rows = std::max (max_rows, sc.rows);
+      center_geometry (clip, sp.seconds, c);
+      strides.add (c);
     }
-  *sub_stride = (max_out * n_channels + 3) / 4 * 4;
-  *ld = (max_rows + 15) / 16 * 16;
+  return strides;
 }
 
 } // namespace
@@ -866,40 +558,47 @@ speed_batch_plan (const std::vector<size_t>& n_frames, const std::vector<int>& r
   group_of_clip.assign (n_frames.size(), -1);
   bytes_of_group.clear();
   size_t members = 0;
-  long long sub_stride = 0, ld = 0;                        // of the open sub-group
+  PassStrides open;                                        // of the open sub-group
+  const auto bytes = [&] (size_t n, const PassStrides& s) {
+    return n * centers * (size_t (s.sub_stride (n_channels)) * sizeof (float) + size_t (s.center_stride()) * sizeof (float2));
+  };
   for (size_t i = 0; i < n_frames.size(); i++)
     {
-      if (rates[i] <= 0 || double (n_frames[i]) / rates[i] < 0.25)
+      if (!long_enough_to_search (n_frames[i], rates[i]))
         continue;                                          // takes no part in the search
-      long long s = 0, l = 0;
-      scan1_strides (n_frames[i], n_channels, rates[i], sp, &s, &l);
-      const auto bytes = [&] (size_t n, long long ss, long long ll) { return n * centers * (size_t (ss) * sizeof (float) + size_t (510) * ll * sizeof (float2)); };
-      const long long s_with = std::max (s, sub_stride), l_with = std::max (l, ld);
-      if (members && (bytes (members + 1, s_with, l_with) > budget || members + 1 > SPEED_BATCH_MAX_CLIPS))
+      const PassStrides own = scan1_strides (n_frames[i], n_channels, rates[i], sp);
+      PassStrides with = open;
+      with.add (own);
+      if (members && (bytes (members + 1, with) > budget || members + 1 > SPEED_BATCH_MAX_CLIPS))
         {
           members = 0;                                     // the clip opens the next sub-group (a sub-group holds one clip at least)
-          sub_stride = ld = 0;
+          open = PassStrides();
         }
       if (!members)
         bytes_of_group.push_back (0);
       members++;
-      sub_stride = std::max (s, sub_stride);
-      ld = std::max (l, ld);
+      open.add (own);
       group_of_clip[i] = int (bytes_of_group.size()) - 1;
-      bytes_of_group.back() = bytes (members, sub_stride, ld);
+      bytes_of_group.back() = bytes (members, open);
     }
   return int (bytes_of_group.size());
 }
 
 int
-speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, double seconds, int candidates)
+speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, double seconds, int candidates, SpeedForm form)
 {
   (void) ctx;
   SpeedScratch *ws = speed_scratch (lane);
   hipStream_t st = lane->stream;
   if (batch.empty())
     return 0;
-  /* get_clip_locations (reference wmspeed.cc:533-553) of every clip: positions side by side, one gather */
+  const bool one_clip = form == SpeedForm::ONE_CLIP;       // K15 without descriptors per clip: positions and [n][2] ranges only
+  if (one_clip && batch.size() != 1)
+    {
+      set_error ("speed_clip_location_batch: the one-clip form takes one clip");
+      return AWM_ERR_ARG;
+    }
+  /* get_clip_locations (reference wmspeed.cc:533-553) of every clip: hash a sparse subset of the samples; positions side by side, one gather */
   std::vector<unsigned long long> pos;
   std::vector<awmk::GatherClipDev> gather;
   std::vector<Random> rngs;
@@ -914,11 +613,12 @@ speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<Speed
       gather.push_back ({ item->wav.data, (long long) first, (long long) (pos.size() - first) });
       max_n = std::max (max_n, gather.back().n);
     }
-  const size_t pos_bytes = align16 (pos.size() * sizeof (unsigned long long)), gather_bytes = gather.size() * sizeof (awmk::GatherClipDev);
+  const size_t pos_bytes = align16 (pos.size() * sizeof (unsigned long long)), gather_bytes = one_clip ? 0 : gather.size() * sizeof (awmk::GatherClipDev);
   const size_t val_bytes = pos.size() * sizeof (float);
   const size_t n_ranges = batch.size() * size_t (candidates);
-  const size_t range_bytes = n_ranges * sizeof (awmk::EnergyRangeDev), e_bytes = n_ranges * awmk::ENERGY_PARTS * sizeof (double);
-  if (int rc = ws->gather_pos.reserve (pos_bytes + gather_bytes))
+  const size_t range_bytes = n_ranges * (one_clip ? 2 * sizeof (long long) : sizeof (awmk::EnergyRangeDev));
+  const size_t e_bytes = n_ranges * awmk::ENERGY_PARTS * sizeof (double);
+  if (int rc = ws->gather_pos.reserve (std::max<size_t> (pos_bytes + gather_bytes, 16)))
     return rc;
   if (int rc = ws->gather_out.reserve (std::max<size_t> (val_bytes, 16)))
     return rc;
@@ -926,14 +626,18 @@ speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<Speed
     return rc;
   if (int rc = ws->energy.reserve (e_bytes))
     return rc;
+  // the staging area holds what goes up and what comes down side by side: no synchronisation between the directions
   if (int rc = ws->pin.reserve (std::max<size_t> (std::max (pos_bytes + gather_bytes + val_bytes, range_bytes + e_bytes), 1 << 16)))
     return rc;
   char *pin = ws->pin.as<char>();
   std::memcpy (pin, pos.data(), pos.size() * sizeof (unsigned long long));
   std::memcpy (pin + pos_bytes, gather.data(), gather_bytes);
   AWM_HIP_CHECK (hipMemcpyAsync (ws->gather_pos.ptr, pin, pos_bytes + gather_bytes, hipMemcpyHostToDevice, st));
-  AWM_HIP_CHECK (awmk::launch_gather_values_batch (st, reinterpret_cast<const awmk::GatherClipDev *> (ws->gather_pos.as<char>() + pos_bytes), int (gather.size()),
-                                                   max_n, ws->gather_pos.as<unsigned long long>(), ws->gather_out.as<float>()));
+  if (one_clip)
+    AWM_HIP_CHECK (awmk::launch_gather_values (st, gather[0].in, ws->gather_pos.as<unsigned long long>(), gather[0].n, ws->gather_out.as<float>()));
+  else
+    AWM_HIP_CHECK (awmk::launch_gather_values_batch (st, reinterpret_cast<const awmk::GatherClipDev *> (ws->gather_pos.as<char>() + pos_bytes), int (gather.size()),
+                                                     max_n, ws->gather_pos.as<unsigned long long>(), ws->gather_out.as<float>()));
   const float *values = reinterpret_cast<const float *> (pin + pos_bytes + gather_bytes);
   AWM_HIP_CHECK (hipMemcpyAsync (pin + pos_bytes + gather_bytes, ws->gather_out.ptr, val_bytes, hipMemcpyDeviceToHost, st));
   AWM_HIP_CHECK (hipStreamSynchronize (st));
@@ -957,9 +661,19 @@ speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<Speed
         }
     }
   /* get_best_clip_location (reference wmspeed.cc:555-577): the candidate with the highest energy, per clip */
-  std::memcpy (pin, ranges.data(), range_bytes);
+  if (one_clip)
+    for (size_t k = 0; k < n_ranges; k++)
+      {
+        reinterpret_cast<long long *> (pin)[2 * k] = ranges[k].begin;
+        reinterpret_cast<long long *> (pin)[2 * k + 1] = ranges[k].end;
+      }
+  else
+    std::memcpy (pin, ranges.data(), range_bytes);
   AWM_HIP_CHECK (hipMemcpyAsync (ws->ranges.ptr, pin, range_bytes, hipMemcpyHostToDevice, st));
-  AWM_HIP_CHECK (awmk::launch_energy_batch (st, ws->ranges.as<awmk::EnergyRangeDev>(), int (n_ranges), ws->energy.as<double>()));
+  if (one_clip)
+    AWM_HIP_CHECK (awmk::launch_energy (st, gather[0].in, ws->ranges.as<long long>(), int (n_ranges), ws->energy.as<double>()));
+  else
+    AWM_HIP_CHECK (awmk::launch_energy_batch (st, ws->ranges.as<awmk::EnergyRangeDev>(), int (n_ranges), ws->energy.as<double>()));
   AWM_HIP_CHECK (hipMemcpyAsync (pin + range_bytes, ws->energy.ptr, e_bytes, hipMemcpyDeviceToHost, st));
   AWM_HIP_CHECK (hipStreamSynchronize (st));
   const double *parts = reinterpret_cast<const double *> (pin + range_bytes);
@@ -983,11 +697,30 @@ speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<Speed
 }
 
 int
-speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, const SpeedScanParams& sp)
+speed_clip_location (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& wav, double seconds, int candidates, double *location)
+{
+  SpeedBatchItem item;
+  item.key = key;
+  item.wav = wav;
+  if (int rc = speed_clip_location_batch (ctx, lane, { &item }, seconds, candidates, SpeedForm::ONE_CLIP))
+    return rc;
+  *location = item.clip_location;
+  return 0;
+}
+
+int
+speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, const SpeedScanParams& sp, SpeedForm form,
+                  SpeedMagsView *mags_view)
 {
   SpeedScratch *ws = speed_scratch (lane);
   if (int rc = ensure_window (ctx))
     return rc;
+  const bool one_clip = form == SpeedForm::ONE_CLIP;
+  if (one_clip && batch.size() != 1)
+    {
+      set_error ("speed_scan_batch: the one-clip form takes one clip");
+      return AWM_ERR_ARG;
+    }
   struct Part { SpeedBatchItem *item; DeviceWav clip; SpeedKeyTables *skt; size_t first, count; };
   std::vector<Part> parts;
   std::vector<ScanCenter> centers;                         // of all clips, clip after clip
@@ -1000,15 +733,12 @@ speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem
         continue;
       Part part { item, item->wav, nullptr, centers.size(), 0 };
       for (double speed : item->speeds)
-        for (int c = -sp.n_center_steps; c <= sp.n_center_steps && !item->rc; c++)
+        append_centers (sp, speed, centers);
+      for (size_t i = part.first; i < centers.size() && !item->rc; i++)
+        if (!var_geometry (centers[i].speed / 2).ok)       // the clip drops out, the others go on (not set_error: the call goes on)
           {
-            const double center = speed * std::pow (sp.step, c * (sp.n_steps * 2 + 1));
-            if (!var_geometry (center / 2).ok)             // (the one-clip search fails here as well, in get_var_tables: the clip drops out, the others go on)
-              {
-                item->error = string_printf ("failed to setup vresampler with ratio=%f", center / 2);   // (not set_error: the call goes on)
-                item->rc = AWM_ERR_ARG;
-              }
-            centers.push_back ({ center, nullptr, 0, 0, 0 });
+            item->error = string_printf ("failed to setup vresampler with ratio=%f", centers[i].speed / 2);
+            item->rc = AWM_ERR_ARG;
           }
       if (item->rc)
         {
@@ -1021,11 +751,7 @@ speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem
           return AWM_ERR_ARG;
         }
       C = item->wav.n_channels;
-      /* SpeedSearch::get_jobs (reference wmspeed.cc:461-492) */
-      size_t start_point, end_point;
-      speed_clip_range (item->clip_location, item->wav, sp.seconds * 1.3, &start_point, &end_point);
-      part.clip.data = item->wav.data + start_point * C;
-      part.clip.n_frames = end_point - start_point;
+      part.clip = scan_clip (item->wav, item->clip_location, sp);
       part.count = centers.size() - part.first;
       part.skt = get_speed_key_tables (ctx, item->key);    // (never evicted: alive for the launches below)
       if (!part.skt)
@@ -1063,8 +789,7 @@ speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem
   std::vector<awmk::SpeedEntryDev> entries;
   std::vector<awmk::SpeedItemDev> items;
   std::vector<double> item_speed;
-  long long max_out = 0;
-  int max_rows = 0;
+  PassStrides strides;
   bool aligned = true;
   awmk::VarResampleArgs ra {};
   double var_bytes = 0, mags_bytes = 0, compare_bytes = 0;
@@ -1080,14 +805,14 @@ speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem
           cd.rows = c.rows;
           cds.push_back (cd);
           entries.push_back ({ part.clip.data, part.skt->cols.as<unsigned int>(), part.skt->col_frame.as<int>(), part.skt->col_first.as<unsigned char>() });
-          max_out = std::max (max_out, c.n_out);
-          max_rows = std::max (max_rows, c.rows);
+          strides.add (c);
           ra.max_stride = std::max (ra.max_stride, cd.stride);
           ra.max_step = std::max (ra.max_step, std::ldexp (double (cd.mant), -cd.shift));
-          var_bytes += double (c.n_in + c.n_out) * C * 4.0;
-          mags_bytes += double (c.n_out) * C * 4.0 + double (c.rows) * 510 * 8.0;
+          var_bytes += double (c.n_in + c.n_out) * C * 4.0;                   // K12: the clip in, the resampled clip out, per centre speed
+          mags_bytes += double (c.n_out) * C * 4.0 + double (c.rows) * 510 * 8.0;   // K13: the resampled clip once, { umag, dmag } per row and sync frame out
+          // K14: every centre's { umag, dmag } matrix once (its 2 n_steps + 1 relative speeds share it) + one best score per item
           compare_bytes += double (c.rows) * 510 * 8.0 + per * 8.0;
-          /* SpeedSync::get_jobs (reference wmspeed.cc:172-192) */
+          /* SpeedSync::get_jobs (reference wmspeed.cc:172-192): relative speeds step^p, p = -n_steps .. n_steps, per centre */
           for (int p = -sp.n_steps; p <= sp.n_steps; p++)
             {
               const double center = c.speed;
@@ -1101,11 +826,10 @@ speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem
             }
         }
     }
-  const long long ld = (max_rows + 15) / 16 * 16;
-  const long long sub_stride = (max_out * C + 3) / 4 * 4;
-  const long long center_stride = 510 * ld;
+  const long long ld = strides.ld(), sub_stride = strides.sub_stride (C), center_stride = strides.center_stride();
   const size_t n = centers.size();
-  const size_t cds_bytes = align16 (n * sizeof (awmk::SpeedCenterDev)), entries_bytes = align16 (n * sizeof (awmk::SpeedEntryDev));
+  // one blob of descriptors: centres, entries (batch form only), items
+  const size_t cds_bytes = align16 (n * sizeof (awmk::SpeedCenterDev)), entries_bytes = one_clip ? 0 : align16 (n * sizeof (awmk::SpeedEntryDev));
   const size_t items_bytes = align16 (items.size() * sizeof (awmk::SpeedItemDev)), best_bytes = items.size() * sizeof (unsigned long long);
   const size_t blob_bytes = cds_bytes + entries_bytes + items_bytes;
   if (int rc = ws->sub.reserve (std::max<size_t> (size_t (sub_stride) * n * sizeof (float), 16)))
@@ -1121,33 +845,45 @@ speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem
   hipStream_t st = lane->stream;
   char *pin = ws->pin.as<char>(), *dev = ws->centers.as<char>();
   std::memcpy (pin, cds.data(), n * sizeof (awmk::SpeedCenterDev));
-  std::memcpy (pin + cds_bytes, entries.data(), n * sizeof (awmk::SpeedEntryDev));
+  if (!one_clip)
+    std::memcpy (pin + cds_bytes, entries.data(), n * sizeof (awmk::SpeedEntryDev));
   std::memcpy (pin + cds_bytes + entries_bytes, items.data(), items.size() * sizeof (awmk::SpeedItemDev));
   AWM_HIP_CHECK (hipMemcpyAsync (dev, pin, blob_bytes, hipMemcpyHostToDevice, st));
-  AWM_HIP_CHECK (hipMemsetAsync (ws->best.ptr, 0, best_bytes, st));
   const awmk::SpeedCenterDev *cds_d = reinterpret_cast<const awmk::SpeedCenterDev *> (dev);
-  const awmk::SpeedEntryDev *entries_d = reinterpret_cast<const awmk::SpeedEntryDev *> (dev + cds_bytes);
+  // The form: with entries the launchers take the batch kernels, with nullptr the one-clip kernels, which read the clip and the key's
+  // tables from the args (those of the one part; the batch kernels do not look at them)
+  const awmk::SpeedEntryDev *entries_d = one_clip ? nullptr : reinterpret_cast<const awmk::SpeedEntryDev *> (dev + cds_bytes);
+  ra.in = entries[0].in;
   ra.n_channels = C;
   ra.centers = cds_d;
   ra.out = ws->sub.as<float>();
   ra.out_stride = sub_stride;
   {
     ProfScope ps (ctx, PROF_RESAMPLE_VAR, var_bytes, st);
-    AWM_HIP_CHECK (awmk::launch_resample_var (st, ra, max_out, int (n), entries_d, aligned));
+    AWM_HIP_CHECK (awmk::launch_resample_var (st, ra, strides.max_out, int (n), entries_d, aligned));
   }
   awmk::SpeedMagsArgs ma {};
   ma.sub = ws->sub.as<float>();
   ma.sub_stride = sub_stride;
   ma.n_channels = C;
   ma.centers = cds_d;
-  ma.window512 = workspace (ctx)->window512.as<float>();
+  ma.window512 = workspace (ctx)->window512.as<float>();        // (built by ensure_window above; never replaced)
+  ma.cols = entries[0].cols;
   ma.mags = ws->mags.as<float2>();
   ma.mags_center_stride = center_stride;
   ma.ld = ld;
   {
     ProfScope ps (ctx, PROF_SPEED_MAGS, mags_bytes, st);
-    AWM_HIP_CHECK (awmk::launch_speed_mags (st, ctx->tabs, ma, max_rows, int (n), entries_d));
+    AWM_HIP_CHECK (awmk::launch_speed_mags (st, ctx->tabs, ma, strides.max_rows, int (n), entries_d));
   }
+  if (mags_view)                                           // the test view of the matrices: no comparison
+    {
+      AWM_HIP_CHECK (hipStreamSynchronize (st));
+      mags_view->ld = ld;
+      mags_view->rows = centers[0].rows;
+      return 0;
+    }
+  AWM_HIP_CHECK (hipMemsetAsync (ws->best.ptr, 0, best_bytes, st));
   const int steps_per_frame = Params::frame_size / Params::sync_search_step;
   const int frames_per_block = int (mark_block_frame_count());
   awmk::SpeedCompareArgs ca {};
@@ -1158,9 +894,11 @@ speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem
   ca.items = reinterpret_cast<const awmk::SpeedItemDev *> (dev + cds_bytes + entries_bytes);
   ca.n_centers = int (n);
   ca.items_per_center = per;
+  ca.col_frame = entries[0].col_frame;
+  ca.col_first = entries[0].col_first;
   ca.frames_per_block = frames_per_block;
   ca.steps_per_frame = steps_per_frame;
-  ca.pad_start = frames_per_block * steps_per_frame + steps_per_frame;
+  ca.pad_start = frames_per_block * steps_per_frame + steps_per_frame;      // "a bit of overlap to handle boundaries"
   ca.rows_per_bit = Params::sync_frames_per_bit;
   ca.min_delta = std::min (params().water_delta, 0.080);
   ca.best = ws->best.as<unsigned long long>();
@@ -1174,7 +912,7 @@ speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem
   for (const Part& part : parts)
     for (size_t i = part.first * per; i < (part.first + part.count) * per; i++)
       {
-        SpeedScore sc;
+        SpeedScore sc;                                     // "Score best_score": stays { 0, 0 } unless a state has quality > 0
         if (best[i] > 0)
           {
             sc.quality = best[i];
@@ -1186,12 +924,156 @@ speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem
 }
 
 int
+speed_scan (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& wav, double clip_location, const SpeedScanParams& sp,
+            const std::vector<double>& speeds, std::vector<SpeedScore>& scores, SpeedMagsView *mags_view)
+{
+  SpeedBatchItem item;
+  item.key = key;
+  item.wav = wav;
+  item.clip_location = clip_location;
+  item.speeds = speeds;
+  if (int rc = speed_scan_batch (ctx, lane, { &item }, sp, SpeedForm::ONE_CLIP, mags_view))
+    return rc;
+  if (item.rc)
+    {
+      set_error (item.error);
+      return item.rc;
+    }
+  scores = item.scores;
+  return 0;
+}
+
+int
+speed_mags (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& wav, double clip_location, double center, double seconds,
+            std::vector<float>& out, int *rows)
+{
+  SpeedScratch *ws = speed_scratch (lane);
+  std::vector<SpeedScore> scores;
+  SpeedMagsView view;
+  if (int rc = speed_scan (ctx, lane, key, wav, clip_location, { seconds, 1.0, 0, 0 }, { center }, scores, &view))   // (the centre itself: step^0)
+    return rc;
+  const long long ld = view.ld;
+  KeyTables *kt = ctx->get_key_tables (key);
+  const SyncTable& stab = kt->sync[0].host;
+  std::vector<float2> m (size_t (510) * ld);
+  AWM_HIP_CHECK (hipMemcpy (m.data(), ws->mags.ptr, m.size() * sizeof (float2), hipMemcpyDeviceToHost));
+  // back to the reference's column order (all 510 sync frames sorted by frame)
+  std::vector<int> order (510);
+  for (int i = 0; i < 510; i++)
+    order[i] = i;
+  std::sort (order.begin(), order.end(), [&] (int a, int b) { return stab.frame[a] < stab.frame[b]; });
+  *rows = view.rows;
+  out.assign (size_t (*rows) * 510 * 2, 0.f);
+  for (int r = 0; r < *rows; r++)
+    for (int c = 0; c < 510; c++)
+      {
+        const float2 v = m[size_t (order[c]) * ld + r];
+        out[(size_t (r) * 510 + c) * 2] = v.x;
+        out[(size_t (r) * 510 + c) * 2 + 1] = v.y;
+      }
+  return 0;
+}
+
+namespace {
+
+/* run_search (reference wmspeed.cc:622-781) for the clips of `batch` in lockstep: clip location, scan 1, the n best, scan 2, the best,
+ * scan 3, smoothing and thresholds.  A clip whose scores run empty or whose search fails drops out, the others go on. */
+int
+speed_search (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, const SearchPlan& plan, SpeedForm form,
+              std::vector<SpeedBatchResult>& results)
+{
+  results.assign (batch.size(), SpeedBatchResult());
+  if (int rc = speed_clip_location_batch (ctx, lane, batch, plan.scan1.seconds, clip_candidates, form))
+    return rc;
+  for (SpeedBatchItem *item : batch)
+    item->speeds = { 1.0 };
+  if (int rc = speed_scan_batch (ctx, lane, batch, plan.scan1, form))
+    return rc;
+  for (SpeedBatchItem *item : batch)
+    {
+      select_n_best_scores (item->scores, plan.n_best);
+      item->speeds.clear();
+      for (const auto& s : item->scores)
+        item->speeds.push_back (s.speed);
+    }
+  if (int rc = speed_scan_batch (ctx, lane, batch, plan.scan2, form))
+    return rc;
+  for (SpeedBatchItem *item : batch)
+    {
+      select_n_best_scores (item->scores, 1);
+      item->speeds.clear();
+      if (!item->scores.empty())                           // (empty: the clip takes no part in the last pass, it stays unsearched)
+        item->speeds.push_back (item->scores[0].speed);
+    }
+  if (int rc = speed_scan_batch (ctx, lane, batch, plan.scan3, form))
+    return rc;
+  for (size_t b = 0; b < batch.size(); b++)
+    {
+      const SpeedBatchItem& item = *batch[b];
+      SpeedBatchResult& r = results[b];
+      r.rc = item.rc;
+      r.error = item.error;
+      if (item.rc || item.speeds.empty())
+        continue;
+      r.searched = true;
+      r.speed = score_smooth_find_best (item.scores, 1 - plan.scan3.step, scan3_smooth_distance);
+      for (const auto& s : item.scores)
+        r.quality = std::max (r.quality, s.quality);
+      // "speeds closer to 1.0 than this usually work without stretching before decode"
+      r.use = r.quality > speed_sync_threshold && (r.speed < 0.9999 || r.speed > 1.0001);
+    }
+  return 0;
+}
+
+} // namespace
+
+int
+detect_speed (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_list, const DeviceWav& wav, std::string *report,
+              std::vector<DetectSpeedResult>& results, double *best_speed_out, double *best_quality_out)
+{
+  results.clear();
+  if (!long_enough_to_search (wav.n_frames, wav.sample_rate))
+    return 0;
+  const SearchPlan plan = search_plan (params().detect_speed_patient);
+  for (const Key& key : key_list)                          // key after key, each a search of one clip
+    {
+      SpeedBatchItem item;
+      item.key = key;
+      item.wav = wav;
+      std::vector<SpeedBatchResult> found;
+      if (int rc = speed_search (ctx, lane, { &item }, plan, SpeedForm::ONE_CLIP, found))
+        return rc;
+      const SpeedBatchResult& r = found[0];
+      if (r.rc)
+        {
+          set_error (r.error);
+          return r.rc;
+        }
+      if (!r.searched)
+        continue;
+      if (report)
+        {
+          double delta = -1;
+          if (params().test_speed > 0)
+            delta = 100 * std::fabs (r.speed - params().test_speed) / params().test_speed;
+          *report += string_printf ("detect_speed %f %f %.4f\n", r.speed, r.quality, delta);
+        }
+      if (best_speed_out)
+        *best_speed_out = r.speed;
+      if (best_quality_out)
+        *best_quality_out = r.quality;
+      if (r.use)
+        results.push_back ({ key, r.speed });
+    }
+  return 0;
+}
+
+int
 detect_speed_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchClip>& clips, std::vector<SpeedBatchResult>& results)
 {
   results.assign (clips.size(), SpeedBatchResult());
   if (clips.empty())
     return 0;
-  const SearchPlan plan = search_plan (params().detect_speed_patient);
   std::vector<size_t> n_frames;
   std::vector<int> rates, group;
   std::vector<size_t> group_bytes;
@@ -1205,59 +1087,27 @@ detect_speed_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchCl
       n_frames.push_back (c.wav.n_frames);
       rates.push_back (c.wav.sample_rate);
     }
-  /* "our algorithm won't work at all for very short input files": such a clip is in no sub-group */
+  /* a clip too short to search is in no sub-group */
   const int n_groups = speed_batch_plan (n_frames, rates, clips[0].wav.n_channels, params().detect_speed_patient, speed_batch_bytes(), group, group_bytes);
+  const SearchPlan plan = search_plan (params().detect_speed_patient);
   std::vector<SpeedBatchItem> items (clips.size());
   for (int g = 0; g < n_groups; g++)
     {
       std::vector<SpeedBatchItem *> batch;
+      std::vector<size_t> clip_of;
       for (size_t i = 0; i < clips.size(); i++)
         if (group[i] == g)
           {
             items[i].key = clips[i].key;
             items[i].wav = clips[i].wav;
             batch.push_back (&items[i]);
+            clip_of.push_back (i);
           }
-      if (int rc = speed_clip_location_batch (ctx, lane, batch, plan.scan1.seconds, clip_candidates))
+      std::vector<SpeedBatchResult> found;
+      if (int rc = speed_search (ctx, lane, batch, plan, SpeedForm::BATCH, found))
         return rc;
-      for (SpeedBatchItem *item : batch)
-        item->speeds = { 1.0 };
-      if (int rc = speed_scan_batch (ctx, lane, batch, plan.scan1))
-        return rc;
-      for (SpeedBatchItem *item : batch)
-        {
-          select_n_best_scores (item->scores, plan.n_best);
-          item->speeds.clear();
-          for (const auto& s : item->scores)
-            item->speeds.push_back (s.speed);
-        }
-      if (int rc = speed_scan_batch (ctx, lane, batch, plan.scan2))
-        return rc;
-      for (SpeedBatchItem *item : batch)
-        {
-          select_n_best_scores (item->scores, 1);
-          item->speeds.clear();
-          if (!item->scores.empty())                       // (empty: the clip takes no part in the last pass, its result stays 0 / 0)
-            item->speeds.push_back (item->scores[0].speed);
-        }
-      if (int rc = speed_scan_batch (ctx, lane, batch, plan.scan3))
-        return rc;
-      for (size_t i = 0; i < clips.size(); i++)
-        if (group[i] == g)
-          {
-            const SpeedBatchItem& item = items[i];
-            SpeedBatchResult& r = results[i];
-            r.rc = item.rc;
-            r.error = item.error;
-            if (item.rc || item.speeds.empty())
-              continue;
-            r.searched = true;
-            r.speed = score_smooth_find_best (item.scores, 1 - plan.scan3.step, scan3_smooth_distance);
-            for (const auto& s : item.scores)
-              r.quality = std::max (r.quality, s.quality);
-            // "speeds closer to 1.0 than this usually work without stretching before decode"
-            r.use = r.quality > speed_sync_threshold && (r.speed < 0.9999 || r.speed > 1.0001);
-          }
+      for (size_t b = 0; b < batch.size(); b++)
+        results[clip_of[b]] = found[b];
     }
   return 0;
 }

@@ -3,7 +3,8 @@
 //   detect_speed (key_list, wav, print_results) -> one { key, speed } per key whose best speed passes the thresholds
 //   resample_ratio / resample_ratio_truncate
 // The searches themselves (SpeedSync::prepare_mags / compare for every centre and relative speed of a pass) are three
-// kernels per pass (hip/speed.hip); the host keeps the reference's control flow between the passes.
+// kernels per pass (hip/speed.hip); the host keeps the reference's control flow between the passes.  That host code exists once,
+// for a vector of clips (SpeedBatchItem): the one-clip entry points run it with one item in SpeedForm::ONE_CLIP.
 #pragma once
 #include <memory>
 #include <string>
@@ -74,7 +75,7 @@ struct SpeedWorkspace
 /* buffers of ONE speed search / stretch: per work lane, so that the chunks of a stream can run their searches side by side */
 struct SpeedScratch
 {
-  DevBuffer    sub, mags, centers, items, best, gather_pos, gather_out, ranges, energy, stretched;
+  DevBuffer    sub, mags, centers, best, gather_pos, gather_out, ranges, energy, stretched;
   PinnedBuffer pin;
   void release();
 };
@@ -107,13 +108,27 @@ int resample_ratio_device (awm_ctx *ctx, WorkLane *lane, const DeviceWav& wav, d
 /* the lane's buffer for a chunk stretched to the detected speed (decode() keeps one at a time) */
 DevBuffer& speed_stretch_buffer (WorkLane *lane);
 
-/* get_best_clip_location (reference wmspeed.cc:533-577) */
+/* Which kernels a search runs.  The caller says it, the batch size does not: a sub-group of one clip is still a batch. */
+enum class SpeedForm
+{
+  ONE_CLIP,   // exactly one clip: the one-clip kernels (the launchers get entries = nullptr, no descriptors per clip are uploaded)
+  BATCH       // the batch kernels, a SpeedEntryDev / GatherClipDev / EnergyRangeDev per entry
+};
+/* speed_scan_batch stopped after K13 (speed_mags): leading dimension of the matrices in SpeedScratch::mags, rows of the first centre */
+struct SpeedMagsView
+{
+  long long ld = 0;
+  int       rows = 0;
+};
+
+/* get_best_clip_location (reference wmspeed.cc:533-577): speed_clip_location_batch with one clip */
 int speed_clip_location (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& wav, double seconds, int candidates, double *location);
 
 /* one pass of run_search for one key (reference wmspeed.cc:461-492, 683-719): scores of every centre x relative speed,
- * in the order centres (speeds x -n_center_steps..n_center_steps) x steps -n_steps..n_steps */
+ * in the order centres (speeds x -n_center_steps..n_center_steps) x steps -n_steps..n_steps.  speed_scan_batch with one clip; a speed
+ * the resampler refuses is an error of the call */
 int speed_scan (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& wav, double clip_location, const SpeedScanParams& scan_params,
-                const std::vector<double>& speeds, std::vector<SpeedScore>& scores);
+                const std::vector<double>& speeds, std::vector<SpeedScore>& scores, SpeedMagsView *mags_view = nullptr);
 
 /* magnitude matrix of one centre speed (tests): rows x 510 x (umag, dmag), columns in the reference's order (sorted by frame) */
 int speed_mags (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& wav, double clip_location, double center, double seconds,
@@ -122,13 +137,14 @@ int speed_mags (awm_ctx *ctx, WorkLane *lane, const Key& key, const DeviceWav& w
 void   select_n_best_scores (std::vector<SpeedScore>& scores, size_t n);                          // reference wmspeed.cc:494-531
 double score_smooth_find_best (const std::vector<SpeedScore>& scores, double step, double distance); // reference wmspeed.cc:397-428
 
-/* detect_speed (reference wmspeed.cc:622-781) on a lane.  best_speed / best_quality (optional) receive the last key's values
+/* detect_speed (reference wmspeed.cc:622-781) on a lane: the keys one after the other, each a search of one clip in the one-clip form.
+ * best_speed / best_quality (optional) receive the last key's values
  * whether or not they pass the thresholds.  `report` (optional) receives the "detect_speed ..." lines the reference prints
  * with print_results (the caller prints them: several chunks may be searching at the same time). */
 int detect_speed (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_list, const DeviceWav& wav, std::string *report,
                   std::vector<DetectSpeedResult>& results, double *best_speed = nullptr, double *best_quality = nullptr);
 
-/* ---- batches of clips: the passes of detect_speed in lockstep, one launch per kernel and pass for a sub-group of clips ---- */
+/* ---- the search itself, for clips in lockstep: one launch per kernel and pass for all clips of a call ---- */
 /* sub + mags of the first pass that a sub-group may ask for (one 30 s stereo clip: 1.25 GB non-patient); a sub-group holds one clip
  * at least.  awm_debug_set_speed_batch_bytes.  Measured (profiles/get_batch_speed, the clip batches with awm_debug_set_speed_batch (1)):
  * 64 clips 294 / 284 / 275 ms at 4 / 12 / 32 GiB, 1024 clips no difference beyond the spread; larger budgets were not measured.  The
@@ -152,7 +168,7 @@ struct SpeedBatchResult
   double speed = 0, quality = 0;
   std::string error;        // rc < 0: the error text
 };
-/* one clip of a batch pass: clip location and speeds in, scores out (speed_scan's order); rc as in SpeedBatchResult */
+/* one clip of a pass: clip location and speeds in, scores out (speed_scan's order); rc as in SpeedBatchResult */
 struct SpeedBatchItem
 {
   Key                     key;
@@ -167,10 +183,14 @@ struct SpeedBatchItem
  * clips stay in order, a sub-group is closed by the first clip with which it would pass `budget`.  Pure host. */
 int speed_batch_plan (const std::vector<size_t>& n_frames, const std::vector<int>& rates, int n_channels, bool patient, size_t budget,
                       std::vector<int>& group_of_clip, std::vector<size_t>& bytes_of_group);
-/* speed_clip_location / speed_scan for every clip of `batch` (one channel count), results equal to the one-clip calls bit for bit */
-int speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, double seconds, int candidates);
-int speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, const SpeedScanParams& scan_params);
-/* detect_speed (params().detect_speed_patient) for clips with a key each, sub-group after sub-group */
+/* Clip location and one pass for every clip of `batch` (one channel count): the only bodies, whatever the form.  Per call one copy of all
+ * descriptors through the pinned buffer, the launches, one copy back behind one synchronisation (the clip location: two of each).  Both
+ * forms give a clip the same location and scores bit for bit.  mags_view: stop after K13 and leave the matrices in the scratch. */
+int speed_clip_location_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, double seconds, int candidates,
+                               SpeedForm form = SpeedForm::BATCH);
+int speed_scan_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchItem *>& batch, const SpeedScanParams& scan_params,
+                      SpeedForm form = SpeedForm::BATCH, SpeedMagsView *mags_view = nullptr);
+/* detect_speed (params().detect_speed_patient) for clips with a key each, sub-group after sub-group in the batch form */
 int detect_speed_batch (awm_ctx *ctx, WorkLane *lane, const std::vector<SpeedBatchClip>& clips, std::vector<SpeedBatchResult>& results);
 
 } // namespace awm

@@ -4,6 +4,7 @@ the C ABI against the oracle and the golden vectors of the compiled reference (t
 Tolerances: the detected speed is a float result of a search over float scores -- it has to agree within 2e-6 (two steps of
 the final smoothing grid, wmspeed.cc:407); scores within 1e-4, magnitudes within 1e-2 dB-sum units (values ~2000); stretched
 PCM within 1e-6; everything that is decoded from the stretched stream (payload bits, sync positions, pattern types) exactly."""
+import contextlib
 import hashlib
 import json
 import os
@@ -42,6 +43,14 @@ def gpu():
     ctx.close()
 
 
+@contextlib.contextmanager
+def one_clip_forms_only(gpu):
+    """the one-clip entry points never launch a batch form of K12 - K15 (awm.speed_batch_launches counts those)"""
+    before = gpu.awm.speed_batch_launches()
+    yield
+    assert gpu.awm.speed_batch_launches() == before
+
+
 @pytest.fixture(scope="module")
 def golden():
     with open(os.path.join(HERE, "golden", "speed_v1.json")) as f:
@@ -71,7 +80,8 @@ def replayed(golden, marked):
 @pytest.mark.parametrize("ratio,ch", [(1 / 0.9764, 2), (1 / 1.01, 2), (0.49, 1), (0.8, 3), (1.25, 2), (2.5, 1)])
 def test_resample_ratio_matches_restated_zita(gpu, ratio, ch):
     x = np.random.default_rng(int(ratio * 1000)).uniform(-1, 1, (200000 + ch, ch)).astype(np.float32)
-    got = gpu.ctx.resample_ratio(gpu.dev(x, ch), ratio).cpu().numpy()
+    with one_clip_forms_only(gpu):
+        got = gpu.ctx.resample_ratio(gpu.dev(x, ch), ratio).cpu().numpy()
     want = orc.resample_ratio(x, ch, ratio).reshape(-1, ch)
     assert got.shape == want.shape
     assert np.abs(got - want).max() <= 1e-6
@@ -86,8 +96,9 @@ def test_clip_location_and_magnitudes(gpu, golden, replayed):
         case = golden["cases"][speed]
         z = replayed[speed]
         zd = gpu.dev(z)
-        assert gpu.ctx.speed_clip_location(KEY, zd, 25.0) == case["clip_location_25"]
-        mags = gpu.ctx.speed_mags(KEY, zd, case["clip_location_25"], 0.98, 25.0)
+        with one_clip_forms_only(gpu):
+            assert gpu.ctx.speed_clip_location(KEY, zd, 25.0) == case["clip_location_25"]
+            mags = gpu.ctx.speed_mags(KEY, zd, case["clip_location_25"], 0.98, 25.0)
         assert mags.shape[0] == case["mags_rows"]
         for r, col, u, d in case["mags_samples"]:
             assert abs(float(mags[r, col, 0]) - u) < 1e-2 and abs(float(mags[r, col, 1]) - d) < 1e-2
@@ -97,7 +108,8 @@ def test_clip_location_and_magnitudes(gpu, golden, replayed):
 
 def test_scan_pass(gpu, golden, replayed):
     case = golden["cases"]["0.9764"]
-    s, q = gpu.ctx.speed_scan(KEY, gpu.dev(replayed["0.9764"]), case["clip_location_25"], 25.0, 1.0007, 5, 2, [0.98])
+    with one_clip_forms_only(gpu):
+        s, q = gpu.ctx.speed_scan(KEY, gpu.dev(replayed["0.9764"]), case["clip_location_25"], 25.0, 1.0007, 5, 2, [0.98])
     assert s.tolist() == case["scan_speed"]
     assert np.abs(q - np.array(case["scan_quality"])).max() < 1e-4
     assert abs(s[q.argmax()] - 0.9764) < 1e-3
@@ -106,7 +118,8 @@ def test_scan_pass(gpu, golden, replayed):
 @pytest.mark.parametrize("patient", [False, True])
 def test_detect_speed(gpu, golden, replayed, patient):
     for speed, case in golden["cases"].items():
-        use, best, quality = gpu.ctx.detect_speed(KEY, gpu.dev(replayed[speed]), patient)
+        with one_clip_forms_only(gpu):
+            use, best, quality = gpu.ctx.detect_speed(KEY, gpu.dev(replayed[speed]), patient)
         want = case["detect_patient" if patient else "detect"]
         if want is None:
             assert use is None                           # replay speed 1: nothing to correct (|speed - 1| < 1e-4)
@@ -122,8 +135,9 @@ def test_decode_with_detect_speed(gpu, golden, replayed):
         want = golden["cases"][speed]["decode_detect_speed"]
         gpu.awm.set_speed_params(detect_speed=True)
         try:
-            got = gpu.ctx.decode_chunk(KEY, gpu.dev(replayed[speed]), True)
-            got_all = gpu.ctx.get_watermark(KEY, gpu.dev(replayed[speed]))
+            with one_clip_forms_only(gpu):
+                got = gpu.ctx.decode_chunk(KEY, gpu.dev(replayed[speed]), True)
+                got_all = gpu.ctx.get_watermark(KEY, gpu.dev(replayed[speed]))
         finally:
             gpu.awm.set_speed_params()
         assert [(p["sync_index"], p["type"], p["block_type"], p["bits"]) for p in got] == \
@@ -133,6 +147,29 @@ def test_decode_with_detect_speed(gpu, golden, replayed):
             assert abs(g["sync_quality"] - w["sync_quality"]) < 1e-4
         hits = [p for p in got_all if p["bits"] == golden["payload"]]
         assert hits and (speed == "1") == all(p["speed"] == 1 for p in hits)
+
+
+def test_key_list_is_searched_key_after_key(gpu, golden, replayed):
+    """detect_speed with a key list (wmspeed.cc:622-781 runs per key): three one-clip searches, each key with its own outcome -- the
+    key that marked the clip is decoded at the detected speed, a key whose quality stays under the threshold (before and after it in
+    the list) is decoded plain, and every key's patterns are those of a call with that key alone"""
+    k_other, k_other2 = bytes(range(1, 17)), bytes([7] * 16)
+    keys = [k_other, KEY, k_other2]
+    zd = gpu.dev(replayed["0.9764"])
+    gpu.awm.set_speed_params(detect_speed=True)
+    try:
+        with one_clip_forms_only(gpu):
+            pats = gpu.ctx.get_watermark_keys(keys, zd)
+            alone = [gpu.ctx.get_watermark(k, zd) for k in keys]
+    finally:
+        gpu.awm.set_speed_params()
+    order = lambda ps: sorted(ps, key=lambda p: sorted(p.items()))
+    for i, want in enumerate(alone):
+        got = [{k: v for k, v in p.items() if k != "key_index"} for p in pats if p["key_index"] == i]
+        assert order(got) == order(want), i
+    assert any(p["bits"] == golden["payload"] and abs(p["speed"] - 0.9764) <= 3e-4 for p in alone[1])
+    for i in (0, 2):
+        assert all(p["speed"] == 1 for p in alone[i]), i
 
 
 def test_try_speed(gpu, golden, replayed):

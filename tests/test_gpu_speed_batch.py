@@ -215,7 +215,10 @@ def test_clip_on_a_four_byte_address_between_sentinels(gpu, clips, single):
 
 
 def scan_loop(gpu, keys, dev, locs, params, speeds):
-    return [gpu.ctx.speed_scan(k, d, loc, *params, s) for k, d, loc, s in zip(keys, dev, locs, speeds)]
+    before = gpu.awm.speed_batch_launches()
+    scans = [gpu.ctx.speed_scan(k, d, loc, *params, s) for k, d, loc, s in zip(keys, dev, locs, speeds)]
+    assert gpu.awm.speed_batch_launches() == before    # the one-clip forms
+    return scans
 
 
 def assert_scans_equal(got, want):
@@ -231,9 +234,10 @@ def test_scan_batch_equals_per_clip_scans(gpu, clips, dev_clips):
     81 relative speeds per clip (folded in the batch, one speed per thread in the one-clip call)"""
     order = [0, 3, 4]
     dev = [dev_clips[i] for i in order]
+    before = gpu.awm.speed_batch_launches()
     locs25 = [gpu.ctx.speed_clip_location(k, d, 25.0) for k, d in zip(KEYS, dev)]
     assert len(set(locs25)) == 3
-    before = gpu.awm.speed_batch_launches()
+    assert gpu.awm.speed_batch_launches() == before    # the one-clip gather and energy kernels
     got = gpu.ctx.speed_scan_batch(KEYS, dev, locs25, *SCAN1, [[1.0]] * 3)
     assert tuple(a - b for a, b in zip(gpu.awm.speed_batch_launches(), before)) == (1, 1, 1, 0)
     assert_scans_equal(got, scan_loop(gpu, KEYS, dev, locs25, SCAN1, [[1.0]] * 3))
