@@ -301,6 +301,14 @@ lib.awm_ctx_snr_begin.argtypes = [_vp]
 lib.awm_ctx_snr_end.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
 lib.awm_get_watermark_keys_d.argtypes = [_vp, _vp, C.c_int, _vp, C.c_size_t, C.c_int, C.c_size_t, _vp, _vp]
 lib.awm_get_watermark_keys_file.argtypes = [_vp, _vp, C.c_int, C.c_char_p, C.POINTER(RawFormat), C.c_size_t, _vp, _vp]
+# whole streams resident as signed 16-bit PCM: the twins' argument lists
+lib.awm_get_watermark_s16_d.argtypes = lib.awm_get_watermark_d.argtypes
+lib.awm_get_watermark_keys_s16_d.argtypes = lib.awm_get_watermark_keys_d.argtypes
+lib.awm_get_watermark_rate_s16_d.argtypes = lib.awm_get_watermark_rate_d.argtypes
+lib.awm_sync_fft_s16_d.argtypes = lib.awm_sync_fft_d.argtypes
+lib.awm_sync_search_s16_d.argtypes = lib.awm_sync_search_d.argtypes
+lib.awm_block_soft_bits_s16_d.argtypes = lib.awm_block_soft_bits_d.argtypes
+lib.awm_debug_sync_db_sliding_rows_s16_d.argtypes = lib.awm_debug_sync_db_sliding_rows_d.argtypes
 
 
 def set_global_params(**kw):
@@ -1655,6 +1663,88 @@ class Context:
         _check(lib.awm_debug_clip_stage_rates_s16_d(self._h, len(clips), ptrs, frames, ch, rates, _dev_ptr(out), _np(ranges)),
                "awm_debug_clip_stage_rates_s16_d")
         return out, ranges
+
+    # ---- whole streams resident as signed 16-bit PCM (awm_get_watermark_s16_d and its twins) ----
+    @staticmethod
+    def _s16_shape(pcm16):
+        """(n_frames, n_channels) of an interleaved torch.int16 CUDA tensor shaped [frames, channels] or [frames]; a view at any even
+        address is fine as long as it is contiguous"""
+        import torch
+        assert pcm16.dtype == torch.int16 and pcm16.is_cuda and pcm16.is_contiguous()
+        return (pcm16.shape[0], 1) if pcm16.dim() == 1 else (pcm16.shape[0], pcm16.shape[1])
+
+    def get_watermark_s16(self, key, pcm16, sample_rate=44100):
+        """awm_get_watermark_s16_d / awm_get_watermark_rate_s16_d: get_watermark on a torch.int16 stream as it is -- the result is that of
+        get_watermark (pcm_decode of the same bytes, sample_rate), and no float copy of the stream is made"""
+        n, ch = self._s16_shape(pcm16)
+        ptr = C.c_void_p(pcm16.data_ptr())
+        if sample_rate != 44100:
+            return self._patterns(lib.awm_get_watermark_rate_s16_d, "awm_get_watermark_rate_s16_d", self._h, key_bytes(key), ptr, n, ch, sample_rate)
+        return self._patterns(lib.awm_get_watermark_s16_d, "awm_get_watermark_s16_d", self._h, key_bytes(key), ptr, n, ch)
+
+    def get_watermark_keys_s16(self, keys, pcm16):
+        """awm_get_watermark_keys_s16_d: get_watermark_keys on a torch.int16 stream"""
+        n, ch = self._s16_shape(pcm16)
+        return self._patterns_keys(lib.awm_get_watermark_keys_s16_d, "awm_get_watermark_keys_s16_d", keys, C.c_void_p(pcm16.data_ptr()), n, ch)
+
+    def sync_fft_s16(self, pcm16, index, frame_count, want_frames=None, first=0, last=None, out=None):
+        """awm_sync_fft_s16_d: sync_fft on a torch.int16 stream"""
+        import torch
+        n, ch = self._s16_shape(pcm16)
+        if last is None:
+            last = n * ch
+        if out is None:
+            db = torch.zeros((frame_count, N_BANDS), dtype=torch.float32, device=pcm16.device)
+            have = torch.zeros(frame_count, dtype=torch.int8, device=pcm16.device)
+        else:
+            db = _out_tensor(out[0], (frame_count, N_BANDS), torch.float32, pcm16.device, "sync_fft_s16 (db)")
+            have = _out_tensor(out[1], (frame_count,), torch.int8, pcm16.device, "sync_fft_s16 (have)")
+        want = np.ascontiguousarray(want_frames, np.int8) if want_frames is not None else None
+        _check(lib.awm_sync_fft_s16_d(self._h, C.c_void_p(pcm16.data_ptr()), n, ch, index, frame_count, _np(want) if want is not None else None,
+                                      first, last, _dev_ptr(db), _dev_ptr(have)), "awm_sync_fft_s16_d")
+        return db, have
+
+    def sync_search_s16(self, key, pcm16, clip_mode=False, max_out=4096):
+        """awm_sync_search_s16_d: sync_search on a torch.int16 stream"""
+        n, ch = self._s16_shape(pcm16)
+        while True:
+            idx = np.zeros(max_out, np.uint64)
+            q = np.zeros(max_out, np.float64)
+            bt = np.zeros(max_out, np.int32)
+            cnt = _check(lib.awm_sync_search_s16_d(self._h, key_bytes(key), C.c_void_p(pcm16.data_ptr()), n, ch, int(clip_mode), max_out, _np(idx),
+                                                   _np(q), _np(bt)), "awm_sync_search_s16_d")
+            if cnt <= max_out:
+                return idx[:cnt], q[:cnt], bt[:cnt]
+            max_out = cnt
+
+    def block_soft_bits_s16(self, key, pcm16, indices):
+        """awm_block_soft_bits_s16_d: block_soft_bits on a torch.int16 stream"""
+        n, ch = self._s16_shape(pcm16)
+        idx = np.ascontiguousarray(indices, np.uint64)
+        out = np.zeros((len(idx), SOFT_BITS), np.float32)
+        ok = np.zeros(len(idx), np.int32)
+        _check(lib.awm_block_soft_bits_s16_d(self._h, key_bytes(key), C.c_void_p(pcm16.data_ptr()), n, ch, _np(idx), len(idx), _np(out), _np(ok)),
+               "awm_block_soft_bits_s16_d")
+        return out, ok
+
+    def sync_db_sliding_rows_s16(self, pcm16, n_frames, bases, counts, count0, rows_per_plane, row_perm, band_pos, first, last, out, have,
+                                 tail=None, stream_range=None, range_index=None, range_div=1, tables_per_slice=0):
+        """awm_debug_sync_db_sliding_rows_s16_d: sync_db_sliding_rows on a torch.int16 stream (the default forms only)"""
+        import torch
+        n, ch = self._s16_shape(pcm16)
+        assert 0 <= n_frames <= n
+        want = ((bases, torch.int64, 1), (counts, torch.int32, 1), (row_perm, torch.int32, 0), (band_pos, torch.uint8, 0), (out, torch.float32, 3),
+                (have, torch.int8, 2), (tail, torch.float32, 2), (stream_range, torch.int64, 2), (range_index, torch.int32, 1))
+        for t, dtype, dim in want:
+            assert t is None or (t.dtype == dtype and t.is_cuda and t.is_contiguous() and (not dim or t.dim() == dim))
+        assert bases.numel() == counts.numel() and out.shape[1] == 60 and out.shape[0] == have.shape[0] and (tail is None or tail.shape[0] == out.shape[0])
+        opt = lambda t: _dev_ptr(t) if t is not None else None
+        _check(lib.awm_debug_sync_db_sliding_rows_s16_d(self._h, C.c_void_p(pcm16.data_ptr()), n_frames, ch, _dev_ptr(bases), _dev_ptr(counts),
+                                                        bases.numel(), count0, rows_per_plane, _dev_ptr(row_perm), _dev_ptr(band_pos), first, last,
+                                                        opt(stream_range), opt(range_index), range_div, tables_per_slice, out.shape[2],
+                                                        _dev_ptr(out), opt(tail), tail.shape[1] if tail is not None else 0, _dev_ptr(have),
+                                                        have.shape[1]), "awm_debug_sync_db_sliding_rows_s16_d")
+        self.synchronize()
 
     def decode_chunks(self, key, pcm, chunks, first_is_stream_start, max_out=8192):
         """decode() of several chunks [(first_frame, n_frames), ...] of one resident buffer; returns one pattern list per

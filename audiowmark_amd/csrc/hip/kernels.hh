@@ -342,6 +342,20 @@ hipError_t launch_sync_db_sliding (hipStream_t st, const DevTables& t, const Syn
 /* does the form of K4s in force (awm_debug_set_refine_form) write rows of 64 fine offsets + SyncDbArgs::tail for streams of this many channels? */
 bool sliding_rows_have_tail (int n_channels);
 
+/* WHOLE STREAMS OF SIGNED 16-BIT PCM (awm_get_watermark_s16_d and its twins): K4, K4b, K4s, the silence scan and the fixed-ratio resampler
+ * instantiated for PcmS16.  The args are the float launchers' -- SyncDbArgs::pcm / ResampleArgs::in hold the ADDRESS of the int16 values,
+ * interleaved, little-endian, any even address (odd: hipErrorInvalidValue) -- and every output is bit for bit what the float launcher
+ * writes for the decoded stream, float (v) * (1 / 32768) (launch_pcm_decode): a value is converted once, where it leaves global memory,
+ * and nothing behind the load differs.  Stereo frames that are 4-byte aligned are loaded whole; a stereo stream on an address that is
+ * only 2-byte aligned and mono streams off a 4-byte boundary take 2-byte loads.  Nothing outside the stream's values is read.
+ * launch_sync_db_sliding_s16 has the DEFAULT forms only (stereo: form 4 with gathered rows, band_pos set; mono: sync_db_sliding_kernel<1>):
+ * hipErrorInvalidValue while awm_debug_set_refine_form selects another one (sliding_s16_form_ok). */
+hipError_t launch_sync_db_s16 (hipStream_t st, const DevTables& t, const SyncDbArgs& a);
+hipError_t launch_sync_db_sliding_s16 (hipStream_t st, const DevTables& t, const SyncDbArgs& a);
+bool sliding_s16_form_ok();
+hipError_t launch_nonzero_range_s16 (hipStream_t st, const int16_t *data, long long n_values, unsigned long long *result);
+hipError_t launch_resample_s16 (hipStream_t st, const ResampleArgs& a);
+
 /* K5: sync_decode (syncfinder.cc:116-153) for many candidates.
  * value(cand, row, band) = db[plane(cand) + row * row_stride + band * band_stride + lane(cand)],
  * have(cand, row)        = have[hplane(cand) + row * have_row_stride + lane(cand)]

@@ -1410,6 +1410,95 @@ struct PcmS16
   static __device__ __forceinline__ float2 conv2 (short2 v) { return make_float2 (conv (v.x), conv (v.y)); }
 };
 
+/* fetch_stereo / fetch_channel (top of this file) for a stream of SIGNED 16-BIT values -- whole streams straight from 16-bit PCM, kernels.hh
+ * launch_sync_db_s16: `pcm` holds the ADDRESS of the int16 values, any even address.  A lane owns the same samples as in the float
+ * forms, two adjacent frames.  Stereo: one 8-byte load where the pair is 8-byte aligned, two 4-byte loads (a frame each) where the
+ * frames are 4-byte aligned, four 2-byte loads on an address that is only 2-byte aligned; mono: one 4-byte load where the pair is
+ * 4-byte aligned, two 2-byte loads otherwise.  Every form reads the frame's values and nothing else, and decodes each as PcmS16 does. */
+__device__ __forceinline__ void
+fetch_stereo_s16 (const short *pcm, long long idx, int avail, int lane, float (&l)[16], float (&r)[16])
+{
+  const short *p = pcm + idx * 2;
+  const unsigned int align = (unsigned int) reinterpret_cast<uintptr_t> (p);
+  if (avail >= 1024 && (align & 7) == 0)
+    {
+      typedef short v4s __attribute__ ((ext_vector_type (4)));
+      const v4s *p4 = reinterpret_cast<const v4s *> (p);
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const v4s v = p4[lane + 64 * j];
+          l[2 * j] = PcmS16::conv (v.x); r[2 * j] = PcmS16::conv (v.y); l[2 * j + 1] = PcmS16::conv (v.z); r[2 * j + 1] = PcmS16::conv (v.w);
+        }
+    }
+  else if (avail >= 1024 && (align & 3) == 0)
+    {
+      const short2 *p2 = reinterpret_cast<const short2 *> (p);
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const float2 a = PcmS16::conv2 (p2[2 * (lane + 64 * j)]), b = PcmS16::conv2 (p2[2 * (lane + 64 * j) + 1]);
+          l[2 * j] = a.x; r[2 * j] = a.y; l[2 * j + 1] = b.x; r[2 * j + 1] = b.y;
+        }
+    }
+  else
+    {
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const int x = 2 * (lane + 64 * j);
+          l[2 * j]     = x < avail     ? PcmS16::conv (p[2 * x])     : 0.f;
+          r[2 * j]     = x < avail     ? PcmS16::conv (p[2 * x + 1]) : 0.f;
+          l[2 * j + 1] = x + 1 < avail ? PcmS16::conv (p[2 * x + 2]) : 0.f;
+          r[2 * j + 1] = x + 1 < avail ? PcmS16::conv (p[2 * x + 3]) : 0.f;
+        }
+    }
+}
+
+__device__ __forceinline__ void
+fetch_channel_s16 (const short *pcm, long long idx, int avail, int C, int ch, int lane, float (&v)[16])
+{
+  const short *p = pcm + idx * C + ch;
+  if (C == 1 && avail >= 1024 && ((reinterpret_cast<uintptr_t> (p) & 3) == 0))
+    {
+      const short2 *p2 = reinterpret_cast<const short2 *> (p);
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const float2 a = PcmS16::conv2 (p2[lane + 64 * j]);
+          v[2 * j] = a.x; v[2 * j + 1] = a.y;
+        }
+    }
+  else
+    {
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const int x = 2 * (lane + 64 * j);
+          v[2 * j]     = x < avail     ? PcmS16::conv (p[(long long) x * C])       : 0.f;
+          v[2 * j + 1] = x + 1 < avail ? PcmS16::conv (p[(long long) (x + 1) * C]) : 0.f;
+        }
+    }
+}
+
+/* the fetch of a kernel templated over what its stream's values are: PcmF32 is the float form itself */
+template<class In> __device__ __forceinline__ void
+fetch_stereo_in (const float *pcm, long long idx, int avail, int lane, float (&l)[16], float (&r)[16])
+{
+  if constexpr (std::is_same<In, PcmS16>::value)
+    fetch_stereo_s16 (reinterpret_cast<const short *> (pcm), idx, avail, lane, l, r);
+  else
+    fetch_stereo (pcm, idx, avail, lane, l, r);
+}
+template<class In> __device__ __forceinline__ void
+fetch_channel_in (const float *pcm, long long idx, int avail, int C, int ch, int lane, float (&v)[16])
+{
+  if constexpr (std::is_same<In, PcmS16>::value)
+    fetch_channel_s16 (reinterpret_cast<const short *> (pcm), idx, avail, C, ch, lane, v);
+  else
+    fetch_channel (pcm, idx, avail, C, ch, lane, v);
+}
+
 /* stereo, input window of the tile staged in LDS (zero extended): s_in[0] is input frame first0; same products and sums as below */
 template<class Sink> __device__ __forceinline__ void
 resample_output_staged (const ResampleArgs& a, const float *tab, int stride, long long m, const float2 *s_in, unsigned int t_rel, Sink& sink)
@@ -1502,7 +1591,7 @@ resample_output (const ResampleArgs& a, const float *tab, int stride, long long 
  * 32 bits. */
 /* A workgroup keeps its table for `tiles_per_wg` consecutive tiles: staging the table took as long as the taps of one tile
  * (a dozen dependent global loads per thread for 4 outputs per thread). */
-template<int CT> __global__ void __launch_bounds__ (256)
+template<int CT, class In = PcmF32> __global__ void __launch_bounds__ (256)
 resample_kernel (ResampleArgs a, int lds_floats, int in_span, int tiles_per_wg)
 {
   extern __shared__ float s_tab[];                           // lds_floats (launcher): the table, or nothing if it is too large; then the window
@@ -1532,11 +1621,11 @@ resample_kernel (ResampleArgs a, int lds_floats, int in_span, int tiles_per_wg)
         {
           if (t)
             __syncthreads();                                                   // the previous tile's windows have been read
-          const float2 *in2 = reinterpret_cast<const float2 *> (a.in);
+          const typename In::frame2 *in2 = reinterpret_cast<const typename In::frame2 *> (a.in);
           for (int i = threadIdx.x; i < in_span; i += 256)
             {
               const long long j = first0 + i;
-              s_in[i] = (j >= 0 && j < a.n_in) ? in2[j] : make_float2 (0.f, 0.f);
+              s_in[i] = (j >= 0 && j < a.n_in) ? In::conv2 (in2[j]) : make_float2 (0.f, 0.f);
             }
         }
       if (in_lds && (staged || t == 0))
@@ -1549,9 +1638,9 @@ resample_kernel (ResampleArgs a, int lds_floats, int in_span, int tiles_per_wg)
           if (staged)
             resample_output_staged (a, s_tab, stride, m, s_in, r0 + (unsigned int) (q * 256 + threadIdx.x) * (unsigned int) a.step, sink);
           else if (in_lds)
-            resample_output<CT> (a, s_tab, stride, m, sink);
+            resample_output<CT, In> (a, s_tab, stride, m, sink);
           else
-            resample_output<CT> (a, a.ctab, a.hl, m, sink);
+            resample_output<CT, In> (a, a.ctab, a.hl, m, sink);
         }
     }
 }
@@ -1637,40 +1726,41 @@ resample_phase_body (const float *ctab, const float *in, long long n_in, long lo
     }
 }
 
-template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
+template<int NP, int STEP, int HL, int R, int J, class In = PcmF32> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
 resample_phase_kernel (ResampleArgs a, int tiles_per_wg)
 {
   ResampleStore sink { a.out };
-  resample_phase_body<NP, STEP, HL, R, J> (a.ctab, a.in, a.n_in, a.n_out, tiles_per_wg, sink);
+  resample_phase_body<NP, STEP, HL, R, J, false, In> (a.ctab, a.in, a.n_in, a.n_out, tiles_per_wg, sink);
 }
 
 /* (measurement knob) 1 (default): the phase-per-thread kernel for stereo 48 <-> 44.1 kHz | 0: the generic kernel for every ratio */
 int g_resample_phase = 1;
 extern "C" void awm_debug_set_resample_phase (int on) { g_resample_phase = on; }
 
-template<int NP, int STEP, int HL> static hipError_t
+template<int NP, int STEP, int HL, class In> static hipError_t
 launch_resample_phase (hipStream_t st, const ResampleArgs& a)
 {
   constexpr int R = 2, J = 8;
   const long long n_tiles = (a.n_out + R * J * NP - 1) / (R * J * NP);
   const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles / 4096)));     // >= 4096 workgroups first
   const dim3 grid (unsigned ((n_tiles + tiles_per_wg - 1) / tiles_per_wg));
-  hipLaunchKernelGGL ((resample_phase_kernel<NP, STEP, HL, R, J>), grid, dim3 (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64), 0, st, a, tiles_per_wg);
+  hipLaunchKernelGGL ((resample_phase_kernel<NP, STEP, HL, R, J, In>), grid, dim3 (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64), 0, st, a, tiles_per_wg);
   return hipGetLastError();
 }
 
-hipError_t
-launch_resample (hipStream_t st, const ResampleArgs& a)
+template<class In> static hipError_t
+launch_resample_any (hipStream_t st, const ResampleArgs& a)
 {
   if (a.n_out <= 0)
     return hipSuccess;
-  const bool aligned = (reinterpret_cast<uintptr_t> (a.in) & 7) == 0 && (reinterpret_cast<uintptr_t> (a.out) & 7) == 0;
+  // (a stereo frame is one load: 8 bytes of float, 4 bytes of 16-bit values)
+  const bool aligned = (reinterpret_cast<uintptr_t> (a.in) & (sizeof (typename In::frame2) - 1)) == 0 && (reinterpret_cast<uintptr_t> (a.out) & 7) == 0;
   if (g_resample_phase && a.n_channels == 2 && aligned)
     {
       if (a.np == 147 && a.step == 160 && a.hl == 18)
-        return launch_resample_phase<147, 160, 18> (st, a);
+        return launch_resample_phase<147, 160, 18, In> (st, a);
       if (a.np == 160 && a.step == 147 && a.hl == 16)
-        return launch_resample_phase<160, 147, 16> (st, a);
+        return launch_resample_phase<160, 147, 16, In> (st, a);
     }
   const long long n_tiles = (a.n_out + RS_TILE - 1) / RS_TILE;
   const int tiles_per_wg = int (std::min<long long> (8, std::max<long long> (1, n_tiles / 4096)));     // >= 4096 workgroups first
@@ -1684,10 +1774,24 @@ launch_resample (hipStream_t st, const ResampleArgs& a)
   const int in_span = stage ? int (span) : 0;
   const size_t lds_bytes = size_t ((lds_floats + 1) & ~1) * sizeof (float) + size_t (in_span) * sizeof (float2);
   if (a.n_channels == 2 && aligned)
-    hipLaunchKernelGGL (resample_kernel<2>, grid, dim3 (256), lds_bytes, st, a, lds_floats, in_span, tiles_per_wg);
+    hipLaunchKernelGGL ((resample_kernel<2, In>), grid, dim3 (256), lds_bytes, st, a, lds_floats, in_span, tiles_per_wg);
   else
-    hipLaunchKernelGGL (resample_kernel<0>, grid, dim3 (256), lds_bytes, st, a, lds_floats, in_span, tiles_per_wg);
+    hipLaunchKernelGGL ((resample_kernel<0, In>), grid, dim3 (256), lds_bytes, st, a, lds_floats, in_span, tiles_per_wg);
   return hipGetLastError();
+}
+
+hipError_t
+launch_resample (hipStream_t st, const ResampleArgs& a)
+{
+  return launch_resample_any<PcmF32> (st, a);
+}
+
+hipError_t
+launch_resample_s16 (hipStream_t st, const ResampleArgs& a)
+{
+  if (reinterpret_cast<uintptr_t> (a.in) & 1)
+    return hipErrorInvalidValue;
+  return launch_resample_any<PcmS16> (st, a);
 }
 
 template<int NP, int STEP, int HL, int R, int J> __global__ void __launch_bounds__ (((STEP > NP ? STEP : NP) * R + 63) / 64 * 64)
@@ -2344,7 +2448,7 @@ sync_stream_range (const SyncDbArgs& a, long long stream, long long& first, long
 
 // TLD: row length of the output tile in LDS (frames per tile + 1).  33 keeps a workgroup at 38 KB so that FOUR of them
 // (16 waves) fit on a CU; the full 73 is only needed by the table-driven refinement fallback (72 fine offsets).
-template<int CV, bool SPLIT, int TLD> __global__ void __launch_bounds__ (64 * WAVES)
+template<int CV, bool SPLIT, int TLD, class In = PcmF32> __global__ void __launch_bounds__ (64 * WAVES)
 sync_db_kernel (DevTables t, SyncDbArgs a)
 {
   constexpr int TILE_LD = TLD, TILE_MAX = TLD - 1, SPLIT_COLS = TILE_MAX / 2;
@@ -2422,7 +2526,7 @@ sync_db_kernel (DevTables t, SyncDbArgs a)
           if (CV == 2)
             {
               float in[2][16];
-              fetch_stereo (a.pcm, idx, 1024, lane, in[0], in[1]);
+              fetch_stereo_in<In> (a.pcm, idx, 1024, lane, in[0], in[1]);
               float2 za[8], zb[8];
               window_pack (in[0], s_win, lane, za);
               window_pack (in[1], s_win, lane, zb);
@@ -2471,7 +2575,7 @@ sync_db_kernel (DevTables t, SyncDbArgs a)
               for (int c = c_begin; c < c_end; c++)
                 {
                   float in[16];
-                  fetch_channel (a.pcm, idx, 1024, C, c, lane, in);
+                  fetch_channel_in<In> (a.pcm, idx, 1024, C, c, lane, in);
                   float2 z[8];
                   window_pack (in, s_win, lane, z);
                   fft512_forward (z, xbuf, s_tw, lane);
@@ -2557,8 +2661,8 @@ sync_db_kernel (DevTables t, SyncDbArgs a)
       a.have[stream * a.have_stream_stride + tile0 + i] = s_have[i];
 }
 
-hipError_t
-launch_sync_db (hipStream_t st, const DevTables& t, const SyncDbArgs& a)
+template<class In> static hipError_t
+launch_sync_db_any (hipStream_t st, const DevTables& t, const SyncDbArgs& a)
 {
   if (a.n_streams <= 0 || a.tile_frames <= 0 || a.tile_frames > 72)
     return a.n_streams <= 0 ? hipSuccess : hipErrorInvalidValue;
@@ -2582,7 +2686,7 @@ launch_sync_db (hipStream_t st, const DevTables& t, const SyncDbArgs& a)
           b.stream_count = a.stream_count ? a.stream_count + done : nullptr;
           b.out = a.out + done * a.out_stream_stride;
           b.have = a.have ? a.have + done * a.have_stream_stride : nullptr;
-          hipError_t e = launch_sync_db (st, t, b);
+          hipError_t e = launch_sync_db_any<In> (st, t, b);
           if (e != hipSuccess)
             return e;
           done += n;
@@ -2595,7 +2699,7 @@ launch_sync_db (hipStream_t st, const DevTables& t, const SyncDbArgs& a)
       SyncDbArgs b = a;
       b.tile_frames = 16;                                        // two planes of 16 frames side by side in a 33-column tile
       const unsigned split_tiles = unsigned ((max_count + b.tile_frames - 1) / b.tile_frames);
-      hipLaunchKernelGGL ((sync_db_kernel<2, true, 33>), dim3 (split_tiles, unsigned (a.n_streams), 1), dim3 (64 * WAVES), 0, st, t, b);
+      hipLaunchKernelGGL ((sync_db_kernel<2, true, 33, In>), dim3 (split_tiles, unsigned (a.n_streams), 1), dim3 (64 * WAVES), 0, st, t, b);
       return hipGetLastError();
     }
   const unsigned planes = a.per_channel ? unsigned (a.n_channels) : 1u;
@@ -2609,18 +2713,32 @@ launch_sync_db (hipStream_t st, const DevTables& t, const SyncDbArgs& a)
   if (a.n_channels == 2 && !a.per_channel)
     {
       if (small)
-        hipLaunchKernelGGL ((sync_db_kernel<2, false, 33>), grid, dim3 (64 * WAVES), 0, st, t, b);
+        hipLaunchKernelGGL ((sync_db_kernel<2, false, 33, In>), grid, dim3 (64 * WAVES), 0, st, t, b);
       else
-        hipLaunchKernelGGL ((sync_db_kernel<2, false, 73>), grid, dim3 (64 * WAVES), 0, st, t, b);
+        hipLaunchKernelGGL ((sync_db_kernel<2, false, 73, In>), grid, dim3 (64 * WAVES), 0, st, t, b);
     }
   else
     {
       if (small)
-        hipLaunchKernelGGL ((sync_db_kernel<1, false, 33>), grid, dim3 (64 * WAVES), 0, st, t, b);
+        hipLaunchKernelGGL ((sync_db_kernel<1, false, 33, In>), grid, dim3 (64 * WAVES), 0, st, t, b);
       else
-        hipLaunchKernelGGL ((sync_db_kernel<1, false, 73>), grid, dim3 (64 * WAVES), 0, st, t, b);
+        hipLaunchKernelGGL ((sync_db_kernel<1, false, 73, In>), grid, dim3 (64 * WAVES), 0, st, t, b);
     }
   return hipGetLastError();
+}
+
+hipError_t
+launch_sync_db (hipStream_t st, const DevTables& t, const SyncDbArgs& a)
+{
+  return launch_sync_db_any<PcmF32> (st, t, a);
+}
+
+hipError_t
+launch_sync_db_s16 (hipStream_t st, const DevTables& t, const SyncDbArgs& a)
+{
+  if (reinterpret_cast<uintptr_t> (a.pcm) & 1)
+    return hipErrorInvalidValue;
+  return launch_sync_db_any<PcmS16> (st, t, a);
 }
 
 /* ==========================================================================================
@@ -2673,7 +2791,7 @@ uniform_global (const float *p)
 
 // STATUS: <1> is the product path for MONO streams; <2> ("form 0", round 2) only runs behind awm_debug_set_refine_form (0) as one of the
 // three kernels test_refinement_kernel_forms holds against each other bit for bit -- stereo streams take sync_db_sliding4_kernel.
-template<int CV> __global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (3, 3)))
+template<int CV, class In = PcmF32> __global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (3, 3)))
 sync_db_sliding_kernel (DevTables t, SyncDbArgs a)
 {
   constexpr int SCRATCH_FLOATS = XBUF_ELEMS * 4 > NB * SL_TILE ? XBUF_ELEMS * 4 : NB * SL_TILE;
@@ -2738,7 +2856,7 @@ sync_db_sliding_kernel (DevTables t, SyncDbArgs a)
       {
         // one channel at a time (16 samples per lane live instead of 32: the double transform below needs the registers)
         float in[16];
-        fetch_channel (a.pcm, base, 1024, CV, c, lane, in);
+        fetch_channel_in<In> (a.pcm, base, 1024, CV, c, lane, in);
         int cnt = 0;
 #pragma unroll
         for (int j = 0; j < 16; j++)
@@ -2784,6 +2902,7 @@ sync_db_sliding_kernel (DevTables t, SyncDbArgs a)
   // them back as broadcasts: no global load is ever waited for inside the step loop.
   constexpr int FPL = 2 * CV;                                     // floats per lane and block
   float f_in[FPL], f_out[FPL];
+  const typename In::value *pcm_in = reinterpret_cast<const typename In::value *> (a.pcm);      // (PcmS16: the values' address)
   auto fetch_block = [&] (int q) {
     const long long s0 = base + 128LL * q;
 #pragma unroll
@@ -2792,8 +2911,8 @@ sync_db_sliding_kernel (DevTables t, SyncDbArgs a)
         const int e = lane * FPL + i;                             // (transition * 8 + j) * C + c
         const int trans = SL_TILE * q + e / (8 * C);
         const bool need = trans + 1 < count;
-        f_in[i] = need ? a.pcm[(s0 + 1024) * C + e] : 0.f;
-        f_out[i] = trans < count ? a.pcm[s0 * C + e] : 0.f;       // the first 8 samples of the window of step `trans`
+        f_in[i] = need ? In::conv (pcm_in[(s0 + 1024) * C + e]) : 0.f;
+        f_out[i] = trans < count ? In::conv (pcm_in[s0 * C + e]) : 0.f;       // the first 8 samples of the window of step `trans`
       }
   };
   auto publish_block = [&] () {
@@ -3207,7 +3326,7 @@ template<int ROWS, int DELTA_BYTES> struct S4Lds
   static constexpr int BYTES     = TOTAL > XBUF_ELEMS * 16 ? TOTAL : XBUF_ELEMS * 16;   // the first transform's exchange tile lies over it all
 };
 
-template<bool U32, int ROWS> __device__ __forceinline__ void
+template<bool U32, int ROWS, class In = PcmF32> __device__ __forceinline__ void
 sync_db_sliding4_body (const DevTables& t, const SyncDbArgs& a)
 {
   constexpr int CV = 2, LPC = 28;
@@ -3253,7 +3372,7 @@ sync_db_sliding4_body (const DevTables& t, const SyncDbArgs& a)
   int nz0 = 0, nz1 = 0;                                        // non-zero samples of the current window, per channel (wave uniform)
   {
     float in[CV][16];
-    fetch_stereo (a.pcm, base, 1024, lane, in[0], in[1]);
+    fetch_stereo_in<In> (a.pcm, base, 1024, lane, in[0], in[1]);
     // (at four waves per SIMD -- the float form -- there is no room for the 56 registers of the two twiddle sets: read per channel)
     double2 tw1[U32 ? 1 : 7], tw2[U32 ? 1 : 7], ws[3];
     if constexpr (!U32)
@@ -3357,16 +3476,49 @@ sync_db_sliding4_body (const DevTables& t, const SyncDbArgs& a)
     // beyond the stream read a valid place instead and publish_block drops what they got.
     if (SL_TILE * q >= count)
       return;
-    const global_float *p_out = uniform_global (a.pcm + (base + 128LL * q) * CV);
     const int trans = SL_TILE * q + (lane >> 2);                  // lane * FPL + i = (transition * 8 + j) * C + c
     const unsigned at_out = trans < count ? unsigned (lane * FPL) : 0u;
     const unsigned at_in = trans + 1 < count ? unsigned (lane * FPL + 1024 * CV) : at_out;
-#pragma unroll
-    for (int i = 0; i < FPL; i += 2)
+    if constexpr (std::is_same<In, PcmS16>::value)
       {
-        const v2f vo = *(const global_v2f *) (p_out + at_out + i), vi = *(const global_v2f *) (p_out + at_in + i);
-        f_out[i] = vo.x; f_out[i + 1] = vo.y;                     // the first 8 samples of the window of step `trans`
-        f_in[i] = vi.x;  f_in[i + 1] = vi.y;
+        // 16-bit values: the same scalar base and lane offsets, counted in values of 2 bytes.  A lane's two frames are two 4-byte
+        // loads where the stream's frames are 4-byte aligned (wave uniform: the base is), four 2-byte loads otherwise
+        typedef __attribute__ ((address_space (1))) short global_short;
+        typedef short v2s __attribute__ ((ext_vector_type (2)));
+        typedef __attribute__ ((address_space (1))) v2s global_v2s;
+        const unsigned long long addr = (unsigned long long) wave_uniform ((long long) (unsigned long long) (reinterpret_cast<const short *> (a.pcm) + (base + 128LL * q) * CV));
+        const global_short *p_out = (const global_short *) addr;
+        if ((addr & 3) == 0)
+          {
+#pragma unroll
+            for (int i = 0; i < FPL; i += 2)
+              {
+                const v2s vo = *(const global_v2s *) (p_out + at_out + i), vi = *(const global_v2s *) (p_out + at_in + i);
+                f_out[i] = PcmS16::conv (vo.x); f_out[i + 1] = PcmS16::conv (vo.y);
+                f_in[i] = PcmS16::conv (vi.x);  f_in[i + 1] = PcmS16::conv (vi.y);
+              }
+          }
+        else
+          {
+#pragma unroll
+            for (int i = 0; i < FPL; i++)
+              {
+                const short vo = p_out[at_out + i], vi = p_out[at_in + i];
+                f_out[i] = PcmS16::conv (vo);
+                f_in[i] = PcmS16::conv (vi);
+              }
+          }
+      }
+    else
+      {
+        const global_float *p_out = uniform_global (a.pcm + (base + 128LL * q) * CV);
+#pragma unroll
+        for (int i = 0; i < FPL; i += 2)
+          {
+            const v2f vo = *(const global_v2f *) (p_out + at_out + i), vi = *(const global_v2f *) (p_out + at_in + i);
+            f_out[i] = vo.x; f_out[i + 1] = vo.y;                     // the first 8 samples of the window of step `trans`
+            f_in[i] = vi.x;  f_in[i + 1] = vi.y;
+          }
       }
   };
   // per block of 16 offsets, one bit per offset at bit 4 * offset: the window carries no weighted non-zero sample (-96 dB exactly,
@@ -3614,6 +3766,12 @@ sync_db_sliding4f_bands_kernel (DevTables t, SyncDbArgs a)
 {
   sync_db_sliding4_body<true, NB> (t, a);
 }
+// the default form on a stream of signed 16-bit values (launch_sync_db_sliding_s16): gathered rows, as the refinement launches it
+__global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (3, 3)))
+sync_db_sliding4_s16_kernel (DevTables t, SyncDbArgs a)
+{
+  sync_db_sliding4_body<false, 60, PcmS16> (t, a);
+}
 
 /* which form of K4s runs for stereo streams (awm_debug_set_refine_form; the result of 0, 3 and 4 is the same to the last bit):
  *   0  sync_db_sliding_kernel<2>    two bins of both channels per lane (42 lanes)
@@ -3653,6 +3811,25 @@ launch_sync_db_sliding (hipStream_t st, const DevTables& t, const SyncDbArgs& a)
     hipLaunchKernelGGL (sync_db_sliding_kernel<2>, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a);
   else
     hipLaunchKernelGGL (sync_db_sliding_kernel<1>, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a);
+  return hipGetLastError();
+}
+
+bool sliding_s16_form_ok() { return g_refine_form == 4; }
+
+hipError_t
+launch_sync_db_sliding_s16 (hipStream_t st, const DevTables& t, const SyncDbArgs& a)
+{
+  if (a.n_streams <= 0 || a.count0 <= 0)
+    return hipSuccess;
+  // only the default forms, in the layout the refinement uses: stereo gathered rows (band_pos), mono as it is
+  if (a.hop != 8 || a.count0 > 65 || a.per_channel || (a.n_channels != 1 && a.n_channels != 2) || !sliding_s16_form_ok()
+      || (a.n_channels == 2 && !a.band_pos) || (reinterpret_cast<uintptr_t> (a.pcm) & 1))
+    return hipErrorInvalidValue;
+  const unsigned grid = unsigned ((a.n_streams + WAVES - 1) / WAVES);
+  if (a.n_channels == 2)
+    hipLaunchKernelGGL (sync_db_sliding4_s16_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a);
+  else
+    hipLaunchKernelGGL ((sync_db_sliding_kernel<1, PcmS16>), dim3 (grid), dim3 (64 * WAVES), 0, st, t, a);
   return hipGetLastError();
 }
 
@@ -4141,13 +4318,13 @@ launch_soft_bits (hipStream_t st, const SoftBitsArgs& a)
 }
 
 /* scan_silence (reference syncfinder.cc:155-169) */
-__global__ void __launch_bounds__ (256)
-nonzero_range_kernel (const float *data, long long n_values, unsigned long long *result)
+template<class In = PcmF32> __global__ void __launch_bounds__ (256)
+nonzero_range_kernel (const typename In::value *data, long long n_values, unsigned long long *result)
 {
   const long long stride = (long long) gridDim.x * blockDim.x;
   unsigned long long first = ~0ULL, last = 0;
   for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n_values; i += stride)
-    if (data[i] != 0.f)
+    if (data[i] != 0)                                  // (PcmS16: the decoded value is zero exactly where the integer is)
       {
         if ((unsigned long long) i < first) first = i;
         if ((unsigned long long) i + 1 > last) last = i + 1;
@@ -4299,8 +4476,8 @@ launch_soft_prep (hipStream_t st, const SoftPrepArgs& a)
   return hipGetLastError();
 }
 
-hipError_t
-launch_nonzero_range (hipStream_t st, const float *data, long long n_values, unsigned long long *result)
+template<class In> static hipError_t
+launch_nonzero_range_any (hipStream_t st, const typename In::value *data, long long n_values, unsigned long long *result)
 {
   // result[0] = min index of a non-zero value (all ones if there is none), result[1] = max index + 1 (no host copy: async)
   hipError_t e = hipMemsetAsync (result, 0xff, sizeof (unsigned long long), st);
@@ -4308,8 +4485,20 @@ launch_nonzero_range (hipStream_t st, const float *data, long long n_values, uns
     e = hipMemsetAsync (result + 1, 0, sizeof (unsigned long long), st);
   if (e != hipSuccess || n_values <= 0)
     return e;
-  hipLaunchKernelGGL (nonzero_range_kernel, dim3 (1024), dim3 (256), 0, st, data, n_values, result);
+  hipLaunchKernelGGL (nonzero_range_kernel<In>, dim3 (1024), dim3 (256), 0, st, data, n_values, result);
   return hipGetLastError();
+}
+
+hipError_t
+launch_nonzero_range (hipStream_t st, const float *data, long long n_values, unsigned long long *result)
+{
+  return launch_nonzero_range_any<PcmF32> (st, data, n_values, result);
+}
+
+hipError_t
+launch_nonzero_range_s16 (hipStream_t st, const int16_t *data, long long n_values, unsigned long long *result)
+{
+  return launch_nonzero_range_any<PcmS16> (st, reinterpret_cast<const short *> (data), n_values, result);
 }
 
 /* the non-silent range a workgroup of WAVES waves found in its part of a slice -- first = smallest absolute index of a non-zero value

@@ -1496,14 +1496,14 @@ awm_debug_sync_db_sliding_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, 
   return 0;
 }
 
-int
-awm_debug_sync_db_sliding_rows_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channels, const long long *base_d, const int *count_d,
-                                  size_t n_streams, int count0, int rows_per_plane, const int *row_perm_d, const unsigned char *band_pos_d,
-                                  long long first, long long last, const long long *stream_range_d, const int *range_index_d, int range_div,
-                                  int tables_per_slice, int ld, float *out_d, float *tail_d, long long tail_stream_stride, char *have_d,
-                                  long long have_stream_stride)
+/* the body of awm_debug_sync_db_sliding_rows_d and of its 16-bit twin (s16: pcm_d holds the address of int16 values) */
+static int
+sliding_rows_body (awm_ctx *ctx, const char *who, const void *pcm_d, bool s16, size_t n_frames, int n_channels, const long long *base_d, const int *count_d,
+                   size_t n_streams, int count0, int rows_per_plane, const int *row_perm_d, const unsigned char *band_pos_d,
+                   long long first, long long last, const long long *stream_range_d, const int *range_index_d, int range_div,
+                   int tables_per_slice, int ld, float *out_d, float *tail_d, long long tail_stream_stride, char *have_d,
+                   long long have_stream_stride)
 {
-  AWM_ENTER (ctx);
   const char *bad = nullptr;
   if (!pcm_d || !base_d || !count_d || !row_perm_d || !band_pos_d || !out_d || !have_d)
     bad = "null pointer";
@@ -1535,12 +1535,12 @@ awm_debug_sync_db_sliding_rows_d (awm_ctx *ctx, const float *pcm_d, size_t n_fra
     }
   if (bad)
     {
-      set_error (std::string ("awm_debug_sync_db_sliding_rows_d: ") + bad);
+      set_error (std::string (who) + ": " + bad);
       return AWM_ERR_ARG;
     }
   // (the fields and their order: SyncFinder's refinement, syncfinder.cc "K4s: sliding DFT over the fine offsets")
   awmk::SyncDbArgs da {};
-  da.pcm = pcm_d;
+  da.pcm = static_cast<const float *> (pcm_d);
   da.n_frames = (long long) n_frames;
   da.n_channels = n_channels;
   da.per_channel = 0;
@@ -1569,18 +1569,82 @@ awm_debug_sync_db_sliding_rows_d (awm_ctx *ctx, const float *pcm_d, size_t n_fra
       da.tables_per_slice = tables_per_slice;
     }
   da.tile_frames = ld;
-  AWM_HIP_CHECK (awmk::launch_sync_db_sliding (ctx->stream, ctx->tabs, da));
+  if (s16)
+    AWM_HIP_CHECK (awmk::launch_sync_db_sliding_s16 (ctx->stream, ctx->tabs, da));
+  else
+    AWM_HIP_CHECK (awmk::launch_sync_db_sliding (ctx->stream, ctx->tabs, da));
   return 0;
 }
 
 int
-awm_sync_fft_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channels, size_t index, size_t frame_count,
-                const char *want_frames, size_t first, size_t last, float *db_out_d, char *have_out_d)
+awm_debug_sync_db_sliding_rows_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channels, const long long *base_d, const int *count_d,
+                                  size_t n_streams, int count0, int rows_per_plane, const int *row_perm_d, const unsigned char *band_pos_d,
+                                  long long first, long long last, const long long *stream_range_d, const int *range_index_d, int range_div,
+                                  int tables_per_slice, int ld, float *out_d, float *tail_d, long long tail_stream_stride, char *have_d,
+                                  long long have_stream_stride)
 {
   AWM_ENTER (ctx);
+  return sliding_rows_body (ctx, "awm_debug_sync_db_sliding_rows_d", pcm_d, false, n_frames, n_channels, base_d, count_d, n_streams, count0, rows_per_plane,
+                            row_perm_d, band_pos_d, first, last, stream_range_d, range_index_d, range_div, tables_per_slice, ld, out_d, tail_d,
+                            tail_stream_stride, have_d, have_stream_stride);
+}
+
+/* The refusals that every entry point for a whole stream of 16-bit PCM adds to its float twin's: AWM_ERR_ARG, nothing enqueued.  The odd
+ * address and the missing stream first; then the form of K4s, of which only the default has a 16-bit instantiation */
+static int
+check_stream_s16 (const char *who, const int16_t *pcm_d, size_t n_frames, int n_channels)
+{
+  const char *bad = nullptr;
+  if (reinterpret_cast<uintptr_t> (pcm_d) & 1)
+    bad = "pcm_d is not 2-byte aligned";
+  else if (!pcm_d && n_frames)
+    bad = "pcm_d is null";
+  else if (n_channels < 1)
+    bad = "n_channels < 1";
+  else if (!awmk::sliding_s16_form_ok())
+    bad = "16-bit streams run the default form of the refinement only (awm_debug_set_refine_form)";
+  if (!bad)
+    return 0;
+  set_error (std::string (who) + ": " + bad);
+  return AWM_ERR_ARG;
+}
+
+static DeviceWav
+make_wav_s16 (const int16_t *pcm_d, size_t n_frames, int n_channels, int rate = Params::mark_sample_rate)
+{
+  DeviceWav w = make_wav_rate (nullptr, n_frames, n_channels, rate);
+  w.pcm16 = n_frames ? pcm_d : nullptr;
+  return w;
+}
+
+int
+awm_debug_sync_db_sliding_rows_s16_d (awm_ctx *ctx, const int16_t *pcm_d, size_t n_frames, int n_channels, const long long *base_d, const int *count_d,
+                                      size_t n_streams, int count0, int rows_per_plane, const int *row_perm_d, const unsigned char *band_pos_d,
+                                      long long first, long long last, const long long *stream_range_d, const int *range_index_d, int range_div,
+                                      int tables_per_slice, int ld, float *out_d, float *tail_d, long long tail_stream_stride, char *have_d,
+                                      long long have_stream_stride)
+{
+  AWM_ENTER (ctx);
+  if (int rc = check_stream_s16 ("awm_debug_sync_db_sliding_rows_s16_d", pcm_d, n_frames, n_channels))
+    return rc;
+  return sliding_rows_body (ctx, "awm_debug_sync_db_sliding_rows_s16_d", pcm_d, true, n_frames, n_channels, base_d, count_d, n_streams, count0,
+                            rows_per_plane, row_perm_d, band_pos_d, first, last, stream_range_d, range_index_d, range_div, tables_per_slice, ld, out_d,
+                            tail_d, tail_stream_stride, have_d, have_stream_stride);
+}
+
+/* the body of awm_sync_fft_d and of its 16-bit twin */
+static int
+sync_fft_body (awm_ctx *ctx, const char *who, const DeviceWav& wav, size_t index, size_t frame_count,
+               const char *want_frames, size_t first, size_t last, float *db_out_d, char *have_out_d)
+{
+  const size_t n_frames = wav.n_frames;
+  const int n_channels = wav.n_channels;
+  auto launch_db = [&] (hipStream_t s, const awmk::SyncDbArgs& args) {
+    return wav.s16() ? awmk::launch_sync_db_s16 (s, ctx->tabs, args) : awmk::launch_sync_db (s, ctx->tabs, args);
+  };
   if (n_frames < index + frame_count * Params::frame_size)
     {
-      set_error ("awm_sync_fft_d: read past end");       // the reference returns empty vectors here
+      set_error (std::string (who) + ": read past end");       // the reference returns empty vectors here
       return AWM_ERR_ARG;
     }
   if (!frame_count)
@@ -1593,7 +1657,7 @@ awm_sync_fft_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channel
   std::vector<long long> bases;
   std::vector<int> counts;
   awmk::SyncDbArgs da {};
-  da.pcm = pcm_d;
+  da.pcm = wav.pcm_arg();
   da.n_frames = (long long) n_frames;
   da.n_channels = n_channels;
   da.per_channel = 0;
@@ -1614,7 +1678,7 @@ awm_sync_fft_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channel
       da.n_streams = 1;
       da.out_stream_stride = 0;
       da.have_stream_stride = 0;
-      AWM_HIP_CHECK (awmk::launch_sync_db (st, ctx->tabs, da));
+      AWM_HIP_CHECK (launch_db (st, da));
     }
   else
     {
@@ -1645,7 +1709,7 @@ awm_sync_fft_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channel
               run.have = da.have + f;
               run.out_stream_stride = 0;
               run.have_stream_stride = 0;
-              AWM_HIP_CHECK (awmk::launch_sync_db (st, ctx->tabs, run));
+              AWM_HIP_CHECK (launch_db (st, run));
               f = g;
             }
         }
@@ -1659,14 +1723,31 @@ awm_sync_fft_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channel
 }
 
 int
-awm_sync_search_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels, int clip_mode,
-                   size_t max_out, uint64_t *index, double *quality, int *block_type)
+awm_sync_fft_d (awm_ctx *ctx, const float *pcm_d, size_t n_frames, int n_channels, size_t index, size_t frame_count,
+                const char *want_frames, size_t first, size_t last, float *db_out_d, char *have_out_d)
 {
   AWM_ENTER (ctx);
+  return sync_fft_body (ctx, "awm_sync_fft_d", make_wav (pcm_d, n_frames, n_channels), index, frame_count, want_frames, first, last, db_out_d, have_out_d);
+}
+
+int
+awm_sync_fft_s16_d (awm_ctx *ctx, const int16_t *pcm_d, size_t n_frames, int n_channels, size_t index, size_t frame_count,
+                    const char *want_frames, size_t first, size_t last, float *db_out_d, char *have_out_d)
+{
+  AWM_ENTER (ctx);
+  if (int rc = check_stream_s16 ("awm_sync_fft_s16_d", pcm_d, n_frames, n_channels))
+    return rc;
+  return sync_fft_body (ctx, "awm_sync_fft_s16_d", make_wav_s16 (pcm_d, n_frames, n_channels), index, frame_count, want_frames, first, last, db_out_d,
+                        have_out_d);
+}
+
+static int
+sync_search_body (awm_ctx *ctx, const uint8_t key[16], const DeviceWav& wav, int clip_mode, size_t max_out, uint64_t *index, double *quality,
+                  int *block_type)
+{
   SyncFinder sf (ctx);
   std::vector<SyncFinder::Score> scores;
-  if (int rc = sf.search (capi_key (key), make_wav (pcm_d, n_frames, n_channels),
-                          clip_mode ? SyncFinder::Mode::CLIP : SyncFinder::Mode::BLOCK, scores))
+  if (int rc = sf.search (capi_key (key), wav, clip_mode ? SyncFinder::Mode::CLIP : SyncFinder::Mode::BLOCK, scores))
     return rc;
   for (size_t i = 0; i < scores.size() && i < max_out; i++)
     {
@@ -1675,6 +1756,24 @@ awm_sync_search_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size
       block_type[i] = int (scores[i].block_type);
     }
   return int (scores.size());
+}
+
+int
+awm_sync_search_s16_d (awm_ctx *ctx, const uint8_t key[16], const int16_t *pcm_d, size_t n_frames, int n_channels, int clip_mode,
+                       size_t max_out, uint64_t *index, double *quality, int *block_type)
+{
+  AWM_ENTER (ctx);
+  if (int rc = check_stream_s16 ("awm_sync_search_s16_d", pcm_d, n_frames, n_channels))
+    return rc;
+  return sync_search_body (ctx, key, make_wav_s16 (pcm_d, n_frames, n_channels), clip_mode, max_out, index, quality, block_type);
+}
+
+int
+awm_sync_search_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels, int clip_mode,
+                   size_t max_out, uint64_t *index, double *quality, int *block_type)
+{
+  AWM_ENTER (ctx);
+  return sync_search_body (ctx, key, make_wav (pcm_d, n_frames, n_channels), clip_mode, max_out, index, quality, block_type);
 }
 
 long
@@ -1701,18 +1800,16 @@ awm_search_approx_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, si
   return long (scores.size());
 }
 
-int
-awm_block_soft_bits_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels,
-                       const uint64_t *index, size_t n_blocks, float *out, int *ok)
+static int
+block_soft_bits_body (awm_ctx *ctx, const uint8_t key[16], const DeviceWav& wav, const uint64_t *index, size_t n_blocks, float *out, int *ok)
 {
-  AWM_ENTER (ctx);
   KeyTables *kt = ctx->get_key_tables (capi_key (key));
   if (!kt)
     return AWM_ERR_HIP;
   std::vector<size_t> idx (index, index + n_blocks);
   std::vector<std::vector<float>> raw;
   std::vector<char> okv;
-  if (int rc = block_soft_bits (ctx, kt, make_wav (pcm_d, n_frames, n_channels), idx, raw, okv))
+  if (int rc = block_soft_bits (ctx, kt, wav, idx, raw, okv))
     return rc;
   const size_t n_bits = mark_data_frame_count() / params().frames_per_bit;
   for (size_t i = 0; i < n_blocks; i++)
@@ -1724,6 +1821,24 @@ awm_block_soft_bits_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, 
         std::fill (out + i * n_bits, out + (i + 1) * n_bits, 0.f);
     }
   return 0;
+}
+
+int
+awm_block_soft_bits_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames, int n_channels,
+                       const uint64_t *index, size_t n_blocks, float *out, int *ok)
+{
+  AWM_ENTER (ctx);
+  return block_soft_bits_body (ctx, key, make_wav (pcm_d, n_frames, n_channels), index, n_blocks, out, ok);
+}
+
+int
+awm_block_soft_bits_s16_d (awm_ctx *ctx, const uint8_t key[16], const int16_t *pcm_d, size_t n_frames, int n_channels,
+                           const uint64_t *index, size_t n_blocks, float *out, int *ok)
+{
+  AWM_ENTER (ctx);
+  if (int rc = check_stream_s16 ("awm_block_soft_bits_s16_d", pcm_d, n_frames, n_channels))
+    return rc;
+  return block_soft_bits_body (ctx, key, make_wav_s16 (pcm_d, n_frames, n_channels), index, n_blocks, out, ok);
 }
 
 /* ---- debug views of the block decoder's dB pass and soft bits (K4b, K7): tests only ---- */
@@ -4236,6 +4351,40 @@ awm_get_watermark_keys_d (awm_ctx *ctx, const uint8_t *keys, int n_keys, const f
   return fill_patterns_keys (rs, list, max_out, out, key_of_pattern);
 }
 
+int
+awm_get_watermark_s16_d (awm_ctx *ctx, const uint8_t key[16], const int16_t *pcm_d, size_t n_frames, int n_channels,
+                         size_t max_out, awm_pattern *out)
+{
+  AWM_ENTER (ctx);
+  if (int rc = check_stream_s16 ("awm_get_watermark_s16_d", pcm_d, n_frames, n_channels))
+    return rc;
+  ResultSet rs;
+  if (int rc = get_watermark_device (ctx, { capi_key (key) }, make_wav_s16 (pcm_d, n_frames, n_channels), rs))
+    return rc;
+  for (size_t i = 0; i < rs.patterns.size() && i < max_out; i++)
+    fill_pattern (rs.patterns[i], out[i]);
+  return int (rs.patterns.size());
+}
+
+int
+awm_get_watermark_keys_s16_d (awm_ctx *ctx, const uint8_t *keys, int n_keys, const int16_t *pcm_d, size_t n_frames, int n_channels,
+                              size_t max_out, awm_pattern *out, int *key_of_pattern)
+{
+  AWM_ENTER (ctx);
+  if (n_keys < 0 || (n_keys && !keys) || (max_out && !out))
+    {
+      set_error ("awm_get_watermark_keys_s16_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  if (int rc = check_stream_s16 ("awm_get_watermark_keys_s16_d", pcm_d, n_frames, n_channels))
+    return rc;
+  const std::vector<Key> list = key_list_from (keys, n_keys);
+  ResultSet rs;
+  if (int rc = get_watermark_device (ctx, list, make_wav_s16 (pcm_d, n_frames, n_channels), rs))
+    return rc;
+  return fill_patterns_keys (rs, list, max_out, out, key_of_pattern);
+}
+
 /* The tail of every batch entry point: the key list -- `key` for all clips, or (keys set) one key per clip --, the batch and its patterns.
  * rates (may be null): the clips are at other rates than 44.1 kHz */
 static int
@@ -4418,6 +4567,35 @@ awm_get_watermark_rate_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_
     return rc;
   DeviceWav wav44;
   if (int rc = resample_to_mark_rate (ctx, ctx, rates, 0, make_wav_rate (pcm_d, n_frames, n_channels, sample_rate), wav44))
+    return rc;
+  ResultSet rs;
+  if (int rc = get_watermark_device (ctx, { capi_key (key) }, wav44, rs))
+    return rc;
+  for (size_t i = 0; i < rs.patterns.size() && i < max_out; i++)
+    fill_pattern (rs.patterns[i], out[i]);
+  return int (rs.patterns.size());
+}
+
+int
+awm_get_watermark_rate_s16_d (awm_ctx *ctx, const uint8_t key[16], const int16_t *pcm_d, size_t n_frames, int n_channels,
+                              int sample_rate, size_t max_out, awm_pattern *out)
+{
+  if (sample_rate == Params::mark_sample_rate)
+    return awm_get_watermark_s16_d (ctx, key, pcm_d, n_frames, n_channels, max_out, out);
+  AWM_ENTER (ctx);
+  if (max_out && !out)
+    {
+      set_error ("awm_get_watermark_rate_s16_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  if (int rc = check_stream_s16 ("awm_get_watermark_rate_s16_d", pcm_d, n_frames, n_channels))
+    return rc;
+  ClipRates rates;
+  if (int rc = clip_rates_each (ctx, &sample_rate, 1, &n_frames, rates))
+    return rc;
+  // (the 44.1 kHz copy on the lane is float: from here on the call is the float call's)
+  DeviceWav wav44;
+  if (int rc = resample_to_mark_rate (ctx, ctx, rates, 0, make_wav_s16 (pcm_d, n_frames, n_channels, sample_rate), wav44))
     return rc;
   ResultSet rs;
   if (int rc = get_watermark_device (ctx, { capi_key (key) }, wav44, rs))

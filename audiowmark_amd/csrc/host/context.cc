@@ -601,7 +601,8 @@ static const char *prof_names[awm::PROF_COUNT] = {
   "add_mix_multi_kernel", "payload_table_kernel",
   "resample_mix_multi_kernel", "clip_resample_pad_kernel", "key_template_kernel", "clip_stage_mixed_kernel",
   "clip_pad_s16_kernel", "clip_resample_pad_s16_kernel", "clip_stage_mixed_s16_kernel",
-  "pcm_decode_kernel", "pcm_encode_kernel", "segment_gather_s16_kernel", "limit_encode_s16_kernel"
+  "pcm_decode_kernel", "pcm_encode_kernel", "segment_gather_s16_kernel", "limit_encode_s16_kernel",
+  "sync_db_s16_kernel(approx)", "sync_db_s16_kernel(refine)", "sync_db_s16_kernel(block)", "resample_s16_kernel"
 };
 
 extern "C" {

@@ -233,7 +233,8 @@ enum ProfId { PROF_ADD_MIX, PROF_LIMITER, PROF_SYNC_DB, PROF_SYNC_SCAN, PROF_LOC
               PROF_RESAMPLE, PROF_RESAMPLE_VAR, PROF_SPEED_MAGS, PROF_SPEED_COMPARE, PROF_KEYTAB, PROF_ADD_MIX_MULTI, PROF_PAYLOAD_TAB,
               PROF_RESAMPLE_MIX, PROF_CLIP_RESAMPLE, PROF_KEY_TEMPLATE, PROF_CLIP_STAGE_MIXED,
               PROF_CLIP_PAD_S16, PROF_CLIP_RESAMPLE_S16, PROF_CLIP_STAGE_MIXED_S16,
-              PROF_PCM_DECODE, PROF_PCM_ENCODE, PROF_SEGMENT_GATHER_S16, PROF_LIMIT_ENCODE_S16, PROF_COUNT };
+              PROF_PCM_DECODE, PROF_PCM_ENCODE, PROF_SEGMENT_GATHER_S16, PROF_LIMIT_ENCODE_S16,
+              PROF_SYNC_DB_S16, PROF_REFINE_DB_S16, PROF_BLOCK_DB_S16, PROF_RESAMPLE_S16, PROF_COUNT };
 struct ProfPending { int id; hipEvent_t start, stop; };
 }
 

@@ -36,7 +36,10 @@ SyncFinder::prepare_launch (const DeviceWav& wav, Mode mode, size_t scan_lo, siz
   auto *res = m_lane->ws_misc.as<unsigned long long>();
   scan_hi = std::min (scan_hi, wav.n_values());
   scan_lo = std::min (scan_lo, scan_hi);
-  AWM_HIP_CHECK (awmk::launch_nonzero_range (m_lane->stream, wav.data + scan_lo, (long long) (scan_hi - scan_lo), res));
+  if (wav.s16())
+    AWM_HIP_CHECK (awmk::launch_nonzero_range_s16 (m_lane->stream, wav.pcm16 + scan_lo, (long long) (scan_hi - scan_lo), res));
+  else
+    AWM_HIP_CHECK (awmk::launch_nonzero_range (m_lane->stream, wav.data + scan_lo, (long long) (scan_hi - scan_lo), res));
   AWM_HIP_CHECK (hipMemcpyAsync (m_lane->pin_small.ptr, res, 2 * sizeof (unsigned long long), hipMemcpyDeviceToHost, m_lane->stream));
   m_prepare_values = wav.n_values();
   m_prepare_lo = scan_lo;
@@ -113,7 +116,7 @@ SyncFinder::approx_device (KeyTables *kt, const DeviceWav& wav, Mode mode, long 
   if (int rc = m_lane->ws_mean.reserve (size_t (n_shifts) * S * sizeof (double))) return rc;
 
   awmk::SyncDbArgs da {};
-  da.pcm = wav.data;
+  da.pcm = wav.pcm_arg();
   da.n_frames = wav.n_frames;
   da.n_channels = wav.n_channels;
   da.per_channel = 0;
@@ -133,8 +136,13 @@ SyncFinder::approx_device (KeyTables *kt, const DeviceWav& wav, Mode mode, long 
   if (!db_ready)                                     // (else: another key of the same `get` left these matrices in the workspace)
     {
       // algorithmic bytes: the samples ONCE (the four shifts of a tile read the same samples; they share one XCD's L2) + one dB row per frame and shift
-      ProfScope ps (m_ctx, PROF_SYNC_DB, double (n_db) * 4096.0 * wav.n_channels + double (n_shifts) * n_db * 324.0, st);
-      AWM_HIP_CHECK (awmk::launch_sync_db (st, m_ctx->tabs, da));
+      // (a 16-bit stream: 2 bytes per sample, the kernels instantiated for PcmS16 under a scope of their own)
+      ProfScope ps (m_ctx, wav.s16() ? PROF_SYNC_DB_S16 : PROF_SYNC_DB,
+                    double (n_db) * (wav.s16() ? 2048.0 : 4096.0) * wav.n_channels + double (n_shifts) * n_db * 324.0, st);
+      if (wav.s16())
+        AWM_HIP_CHECK (awmk::launch_sync_db_s16 (st, m_ctx->tabs, da));
+      else
+        AWM_HIP_CHECK (awmk::launch_sync_db (st, m_ctx->tabs, da));
     }
   if (after_db_event)
     AWM_HIP_CHECK (hipEventRecord (after_db_event, st));
@@ -560,7 +568,7 @@ SyncFinder::refine_batch_launch (KeyTables *kt, const DeviceWav& wav, Mode mode,
   if (max_count > 0)
     {
       awmk::SyncDbArgs da {};
-      da.pcm = wav.data;
+      da.pcm = wav.pcm_arg();
       da.n_frames = wav.n_frames;
       da.n_channels = wav.n_channels;
       da.per_channel = 0;
@@ -593,8 +601,12 @@ SyncFinder::refine_batch_launch (KeyTables *kt, const DeviceWav& wav, Mode mode,
         }
       da.tile_frames = TP;
       {
-        ProfScope ps (m_ctx, PROF_REFINE_DB, (slices ? m_lane->prof_live_fraction : 1.0) * db_bytes, st);
-        if (gathered)
+        ProfScope ps (m_ctx, wav.s16() ? PROF_REFINE_DB_S16 : PROF_REFINE_DB, (slices ? m_lane->prof_live_fraction : 1.0) * db_bytes, st);
+        if (wav.s16() && gathered)
+          AWM_HIP_CHECK (awmk::launch_sync_db_sliding_s16 (st, m_ctx->tabs, da));   // (the default forms only: the entry points refuse the others)
+        else if (wav.s16())
+          AWM_HIP_CHECK (awmk::launch_sync_db_s16 (st, m_ctx->tabs, da));
+        else if (gathered)
           AWM_HIP_CHECK (awmk::launch_sync_db_sliding (st, m_ctx->tabs, da));       // K4s: sliding DFT over the fine offsets
         else
           AWM_HIP_CHECK (awmk::launch_sync_db (st, m_ctx->tabs, da));               // K4: one FFT per fine offset

@@ -14,10 +14,27 @@ struct DeviceWav
   size_t       n_frames = 0;      // samples per channel
   int          n_channels = 0;
   int          sample_rate = 44100;
-  // a clip of a batch that the caller holds as signed 16-bit PCM (wmget.hh get_watermark_batch_device): its values, `data` is null.
-  // Stage 0 of the groups reads them as they are; every other consumer is given a float DeviceWav
+  // Material that the caller holds as signed 16-bit PCM: its values, `data` is null.  A clip of a batch (wmget.hh
+  // get_watermark_batch_device): stage 0 of the groups reads it as it is, a long clip is decoded on its lane first.  A whole stream
+  // (get_watermark_device, awm_get_watermark_s16_d): SyncFinder (silence scan, K4, K4s), the block decoder's dB pass (K4b) and the
+  // fixed-ratio resampler read it as it is (kernels.hh launch_sync_db_s16), the ClipDecoder's padded copies are 16-bit too; the speed
+  // part and the VResampler are given a float copy of the chunk they work on (wmget.cc lane_float_copy)
   const int16_t *pcm16 = nullptr;
   size_t n_values() const { return n_frames * n_channels; }
+  bool   s16() const { return pcm16 != nullptr; }
+  // what SyncDbArgs::pcm / ResampleArgs::in take: the float values, or the ADDRESS of the 16-bit ones
+  const float *pcm_arg() const { return pcm16 ? reinterpret_cast<const float *> (pcm16) : data; }
+  // frames [first_frame, first_frame + n) of this material
+  DeviceWav view (size_t first_frame, size_t n) const
+  {
+    DeviceWav v = *this;
+    if (pcm16)
+      v.pcm16 = pcm16 + first_frame * n_channels;
+    else
+      v.data = data + first_frame * n_channels;
+    v.n_frames = n;
+    return v;
+  }
 };
 
 class SyncFinder

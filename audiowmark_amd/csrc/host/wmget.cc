@@ -56,7 +56,7 @@ block_db_args (const DeviceWav& wav, const long long *d_bases, const int *d_slic
 {
   const long long ld = block_plane_ld();
   awmk::SyncDbArgs da {};
-  da.pcm = wav.data;
+  da.pcm = wav.pcm_arg();                     // (a 16-bit stream: the caller launches launch_sync_db_s16)
   da.n_frames = wav.n_frames;
   da.n_channels = wav.n_channels;
   da.per_channel = 1;
@@ -162,8 +162,12 @@ block_soft_bits_dev (awm_ctx *ctx, WorkLane *lane, KeyTables *kt, const DeviceWa
         AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (planes), view->fill, nb * block_stride));
       const awmk::SyncDbArgs da = block_db_args (wav, d_bases + b0, d_slice_of + b0, nb, planes, slice_range, slice_frames);
       {
-        ProfScope ps (ctx, PROF_BLOCK_DB, (padded ? lane->prof_live_fraction : 1.0) * double (nb) * count * C * (4096.0 + 324.0), st);
-        AWM_HIP_CHECK (awmk::launch_sync_db (st, ctx->tabs, da));
+        ProfScope ps (ctx, wav.s16() ? PROF_BLOCK_DB_S16 : PROF_BLOCK_DB,
+                      (padded ? lane->prof_live_fraction : 1.0) * double (nb) * count * C * ((wav.s16() ? 2048.0 : 4096.0) + 324.0), st);
+        if (wav.s16())
+          AWM_HIP_CHECK (awmk::launch_sync_db_s16 (st, ctx->tabs, da));
+        else
+          AWM_HIP_CHECK (awmk::launch_sync_db (st, ctx->tabs, da));
       }
       const awmk::SoftBitsArgs sb = block_soft_args (kt, C, planes, nb, lane->ws_soft.as<float>() + b0 * n_bits, d_bases + b0, d_slice_of + b0,
                                                      slice_range, slice_frames != 0);
@@ -720,10 +724,7 @@ block_decoder_run (awm_ctx *ctx, WorkLane *home, bool spread, const std::vector<
     }
   } drain { lanes };
   auto chunk_wav = [&] (size_t c) {
-    DeviceWav cw = stream;
-    cw.data = stream.data + chunks[c].first_frame * stream.n_channels;
-    cw.n_frames = chunks[c].n_frames;
-    return cw;
+    return stream.view (chunks[c].first_frame, chunks[c].n_frames);
   };
   /* Every chunk walks through: approximate search -> (candidate list on the host) -> refinement -> (sync positions on the
    * host) -> block dB, soft bits, Viterbi -> (bits on the host), key after key (the approximate dB matrices of a chunk are
@@ -1072,13 +1073,26 @@ clip_run_block (awm_ctx *ctx, WorkLane *lane, const std::vector<Key>& key_list, 
   const size_t total = pad_start + (last_sample - first_sample) + pad_end;
   if (int rc = lane->ws_clip.reserve (total * sizeof (float)))
     return rc;
-  float *ext = lane->ws_clip.as<float>();
   hipStream_t st = lane->stream;
-  AWM_HIP_CHECK (hipMemsetAsync (ext, 0, pad_start * sizeof (float), st));
-  AWM_HIP_CHECK (hipMemcpyAsync (ext + pad_start, wav.data + first_sample, (last_sample - first_sample) * sizeof (float), hipMemcpyDeviceToDevice, st));
-  AWM_HIP_CHECK (hipMemsetAsync (ext + pad_start + (last_sample - first_sample), 0, pad_end * sizeof (float), st));
   DeviceWav l_wav;
-  l_wav.data = ext;
+  if (wav.s16())
+    {
+      // a 16-bit stream: the padded copy is 16-bit as well (zero is zero in both formats), in the same workspace, and the search and the
+      // block decoder read it with the 16-bit kernels as they read the stream
+      int16_t *ext = lane->ws_clip.as<int16_t>();
+      AWM_HIP_CHECK (hipMemsetAsync (ext, 0, pad_start * sizeof (int16_t), st));
+      AWM_HIP_CHECK (hipMemcpyAsync (ext + pad_start, wav.pcm16 + first_sample, (last_sample - first_sample) * sizeof (int16_t), hipMemcpyDeviceToDevice, st));
+      AWM_HIP_CHECK (hipMemsetAsync (ext + pad_start + (last_sample - first_sample), 0, pad_end * sizeof (int16_t), st));
+      l_wav.pcm16 = ext;
+    }
+  else
+    {
+      float *ext = lane->ws_clip.as<float>();
+      AWM_HIP_CHECK (hipMemsetAsync (ext, 0, pad_start * sizeof (float), st));
+      AWM_HIP_CHECK (hipMemcpyAsync (ext + pad_start, wav.data + first_sample, (last_sample - first_sample) * sizeof (float), hipMemcpyDeviceToDevice, st));
+      AWM_HIP_CHECK (hipMemsetAsync (ext + pad_start + (last_sample - first_sample), 0, pad_end * sizeof (float), st));
+      l_wav.data = ext;
+    }
   l_wav.n_frames = total / C;
   l_wav.n_channels = wav.n_channels;
   l_wav.sample_rate = wav.sample_rate;
@@ -1140,6 +1154,26 @@ clip_decoder_run (awm_ctx *ctx, WorkLane *lane, bool spread, const std::vector<K
 
 } // namespace
 
+/* A 16-bit chunk (or a stream that the VResampler converts) for the consumers that have no 16-bit form -- the speed search (K12, K15),
+ * the stretch, the VResampler: decoded into the lane's grow-only float workspace, the exact conversion of awm_pcm_decode_d, one launch
+ * under the decode's scope.  Bounded by the chunk the lane works on.  A float `in` is passed through. */
+int
+lane_float_copy (awm_ctx *ctx, WorkLane *lane, const DeviceWav& in, DeviceWav& out)
+{
+  out = in;
+  if (!in.s16())
+    return 0;
+  if (int rc = lane->ws_pcm.reserve (std::max<size_t> (16, in.n_values() * sizeof (float)))) return rc;
+  {
+    ProfScope ps (ctx, PROF_PCM_DECODE, double (in.n_values()) * 6.0, lane->stream);
+    AWM_HIP_CHECK (awmk::launch_pcm_decode (lane->stream, reinterpret_cast<const unsigned char *> (in.pcm16), lane->ws_pcm.as<float>(),
+                                            (long long) in.n_values(), awmk::PcmFormatDev { 2, 0, 0, 0 }));
+  }
+  out.data = lane->ws_pcm.as<float>();
+  out.pcm16 = nullptr;
+  return 0;
+}
+
 /* one result of the speed part: the stream stretched back to speed 1 on the lane, block and clip decoder on the copy */
 static int
 decode_stretched (awm_ctx *ctx, WorkLane *home, bool spread, ResultSet& result_set, const DetectSpeedResult& sr, const DeviceWav& wav, bool first_chunk)
@@ -1166,11 +1200,15 @@ decode_stretched (awm_ctx *ctx, WorkLane *home, bool spread, ResultSet& result_s
  * original wav data; if detected speed is somewhat different than 1.0, we also try to decode stretched data; we report all
  * normal and speed results we get".  Runs before the normal decoders of the chunk, like in the reference. */
 static int
-decode_speed (awm_ctx *ctx, WorkLane *home, bool spread, ResultSet& result_set, const std::vector<Key>& key_list, const DeviceWav& wav,
+decode_speed (awm_ctx *ctx, WorkLane *home, bool spread, ResultSet& result_set, const std::vector<Key>& key_list, const DeviceWav& chunk,
               bool first_chunk, std::string *report)
 {
   if (!(params().detect_speed || params().detect_speed_patient || params().try_speed > 0))
     return 0;
+  // (a 16-bit chunk: K12 / K15 and the stretch have no 16-bit form, they get the chunk's float copy on the lane)
+  DeviceWav wav;
+  if (int rc = lane_float_copy (ctx, home, chunk, wav))
+    return rc;
   std::vector<DetectSpeedResult> speed_results;
   if (params().detect_speed || params().detect_speed_patient)
     {
@@ -1333,9 +1371,7 @@ decode_chunks_on (awm_ctx *ctx, WorkLane *home, bool spread, const std::vector<K
       std::vector<int> rcs (chunks.size(), 0);
       std::vector<std::string> messages (chunks.size());
       auto run_chunk = [&] (size_t c, WorkLane *lane) {
-        DeviceWav cw = wav;
-        cw.data = wav.data + chunks[c].first_frame * wav.n_channels;
-        cw.n_frames = chunks[c].n_frames;
+        const DeviceWav cw = wav.view (chunks[c].first_frame, chunks[c].n_frames);
         rcs[c] = decode_speed (ctx, lane, false, chunk_sets[c], key_list, cw, c == 0 && first_is_stream_start,
                                speed_print_results ? &reports[c] : nullptr);
         if (rcs[c])
@@ -1391,9 +1427,7 @@ decode_chunks_on (awm_ctx *ctx, WorkLane *home, bool spread, const std::vector<K
   if (!chunks.empty() && first_is_stream_start)
     {
       // ClipDecoder only looks at the first chunk of the stream (reference wmget.cc:932-936)
-      DeviceWav cw = wav;
-      cw.data = wav.data + chunks[0].first_frame * wav.n_channels;
-      cw.n_frames = chunks[0].n_frames;
+      const DeviceWav cw = wav.view (chunks[0].first_frame, chunks[0].n_frames);
       if (int rc = clip_decoder_run (ctx, home, spread, key_list, cw, chunk_sets[0], 1))
         return rc;
       chunk_sets[0].set_debug_sync (debug_sync);
@@ -1792,10 +1826,15 @@ resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, siz
   out.n_frames = n44;
   out.n_channels = C;
   out.sample_rate = Params::mark_sample_rate;
+  out.pcm16 = nullptr;
   if (!table)
-    return resample_var_device (ctx, lane, in.data, in.n_frames, C, double (Params::mark_sample_rate) / rates.sample_rate[i], lane->ws_rate.as<float>(), n44);
+    {
+      DeviceWav fin;
+      if (int rc = lane_float_copy (ctx, lane, in, fin)) return rc;
+      return resample_var_device (ctx, lane, fin.data, in.n_frames, C, double (Params::mark_sample_rate) / rates.sample_rate[i], lane->ws_rate.as<float>(), n44);
+    }
   awmk::ResampleArgs ra {};
-  ra.in = in.data;
+  ra.in = in.pcm_arg();
   ra.n_in = (long long) in.n_frames;
   ra.n_channels = C;
   ra.ctab = table->ctab.as<float>();
@@ -1804,6 +1843,12 @@ resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, siz
   ra.step = table->step;
   ra.out = lane->ws_rate.as<float>();
   ra.n_out = (long long) n44;
+  if (in.s16())
+    {
+      ProfScope ps (ctx, PROF_RESAMPLE_S16, (double (in.n_frames) * 2.0 + double (n44) * 4.0) * C, lane->stream);
+      AWM_HIP_CHECK (awmk::launch_resample_s16 (lane->stream, ra));
+      return 0;
+    }
   ProfScope ps (ctx, PROF_RESAMPLE, double (in.n_frames + n44) * C * 4.0, lane->stream);      // every input and output sample once
   AWM_HIP_CHECK (awmk::launch_resample (lane->stream, ra));
   return 0;

@@ -78,7 +78,11 @@ int get_watermark_batch_device (awm_ctx *ctx, const std::vector<Key>& key_list, 
 int clip_stage_device (awm_ctx *ctx, const std::vector<DeviceWav>& clips, const ClipRates *rates, float *slices, long long *range_out);
 // the 44.1 kHz copy of clip i of `rates` (n44[i] frames) in the lane's own grow-only workspace, on the lane's stream: what the decoders are
 // given.  A clip at 44.1 kHz is handed on as it is
+// (`in` 16-bit, awm_get_watermark_rate_s16_d: the fixed-ratio resampler reads the 16-bit values, kernels.hh launch_resample_s16, under a
+// scope of its own; the VResampler is given the lane's float copy, lane_float_copy)
 int resample_to_mark_rate (awm_ctx *ctx, WorkLane *lane, const ClipRates& rates, size_t i, const DeviceWav& in, DeviceWav& out);
+// a 16-bit `in` decoded into the lane's grow-only float workspace (WorkLane::ws_pcm) on the lane's stream; a float `in` as it is
+int lane_float_copy (awm_ctx *ctx, WorkLane *lane, const DeviceWav& in, DeviceWav& out);
 
 // soft bits of whole blocks (fft_range + mix_decode), raw mix order
 int block_soft_bits (awm_ctx *ctx, KeyTables *kt, const DeviceWav& wav, const std::vector<size_t>& index,

@@ -592,6 +592,47 @@ int awm_get_watermark_batch_rates_s16_d (awm_ctx *ctx, const uint8_t key[16], si
 int awm_get_watermark_batch_keys_rates_s16_d (awm_ctx *ctx, const uint8_t *keys, size_t n_clips, const int16_t *const *pcm_d,
                                               const size_t *n_frames, int n_channels, const int *sample_rates, int n_threads,
                                               size_t max_out_per_clip, awm_pattern *out, int *n_out);
+/* WHOLE STREAMS resident as SIGNED 16-BIT PCM (little-endian, interleaved; an hour or eight of programme as a decoder, a capture card or
+ * a WAV file delivers it): `get` without a float copy of the stream -- half the memory the float call's caller holds, and no decode pass.
+ * pcm_d = n_frames frames of n_channels int16 values (device pointer).
+ * Definition: with f = what awm_pcm_decode_d (ctx, pcm_d, n_frames * n_channels, 16, 0, 0, f) writes -- float (v) * (1 / 32768), exact --
+ * every call below returns, field for field and bit for bit, what its float twin (the same name without _s16) returns for f.
+ * Paths: the kernels that read PCM on the long-stream path -- the dB kernels of the approximate search (K4), of the refinement (K4s) and
+ * of the block decoder (K4b), and the silence scan of CLIP mode -- are instantiated for 16-bit input: a value is converted once, where
+ * it leaves global memory, and nothing behind the load differs.  Chunks and lanes are views of pcm_d.  The ClipDecoder's two padded copies
+ * (a block + 5 frames each) stay 16-bit, in the workspace the float call uses for them, and are read by the same kernels.  With default
+ * parameters the call launches no decode of the stream or of a chunk, reserves no float PCM workspace and launches none of the float dB
+ * kernels, for any stream length, chunk count and key count (scopes sync_db_s16_kernel(approx / refine / block), resample_s16_kernel).
+ * Exceptions, both bounded by what one lane works on and both given back by awm_ctx_trim: while detect_speed, detect_speed_patient or
+ * try_speed is set, a lane decodes the CHUNK it runs the speed part on into its grow-only float workspace (the speed search and the
+ * stretch have no 16-bit form; the un-stretched decoders of that chunk still read the 16-bit values); and awm_get_watermark_rate_s16_d at
+ * a rate that only the VResampler takes decodes the stream on its lane first.  At a rate the fixed-ratio resampler takes, the resampler
+ * -- the form the float call launches -- reads the 16-bit values and writes the lane's 44.1 kHz float copy as in the float call; at 44100
+ * the call is awm_get_watermark_s16_d.
+ * Alignment: any even address.  A stereo stream whose frames are 4-byte aligned loads whole frames (8 bytes per lane where a lane's two
+ * frames are 8-byte aligned); a stereo stream on an address that is only 2-byte aligned, and mono samples off a 4-byte boundary, take
+ * 2-byte loads with the same bits.  Nothing outside the stream's values is read.
+ * Refusals, AWM_ERR_ARG with nothing enqueued and the outputs untouched: an odd pcm_d; NULL with n_frames > 0; n_channels < 1; whatever
+ * the float twin refuses; and any call while awm_debug_set_refine_form selects a form other than the default (4) -- only the default
+ * forms of K4s have 16-bit instantiations.  n_frames == 0 behaves like the float twin.
+ * Not offered: the file level and the command line, which convert their files' formats themselves (keeping a 16-bit WAV's bytes as the
+ * resident stream is the obvious follow-up); awm_decode_chunk*_d, awm_add_get_watermark_d, the sharded and awm_multi_* forms; other
+ * sample formats; the `add` side for whole streams; the speed search (K12, K15) on 16-bit input; the clip batches have forms of their
+ * own above, whose long clips keep their present path. */
+int awm_get_watermark_s16_d (awm_ctx *ctx, const uint8_t key[16], const int16_t *pcm_d, size_t n_frames, int n_channels,
+                             size_t max_out, awm_pattern *out);
+int awm_get_watermark_keys_s16_d (awm_ctx *ctx, const uint8_t *keys, int n_keys, const int16_t *pcm_d, size_t n_frames, int n_channels,
+                                  size_t max_out, awm_pattern *out, int *key_of_pattern);
+int awm_get_watermark_rate_s16_d (awm_ctx *ctx, const uint8_t key[16], const int16_t *pcm_d, size_t n_frames, int n_channels,
+                                  int sample_rate, size_t max_out, awm_pattern *out);
+/* ... and the kernel level on such a stream: the twins of awm_sync_fft_d (K4), awm_sync_search_d (K4, K4s, the scans, the silence scan;
+ * BLOCK and CLIP mode) and awm_block_soft_bits_d (K4b, K7).  Same definition, alignment, refusals and "not offered" as above. */
+int awm_sync_fft_s16_d (awm_ctx *ctx, const int16_t *pcm_d, size_t n_frames, int n_channels, size_t index, size_t frame_count,
+                        const char *want_frames, size_t first, size_t last, float *db_out_d, char *have_out_d);
+int awm_sync_search_s16_d (awm_ctx *ctx, const uint8_t key[16], const int16_t *pcm_d, size_t n_frames, int n_channels, int clip_mode,
+                           size_t max_out, uint64_t *index, double *quality, int *block_type);
+int awm_block_soft_bits_s16_d (awm_ctx *ctx, const uint8_t key[16], const int16_t *pcm_d, size_t n_frames, int n_channels,
+                               const uint64_t *index, size_t n_blocks, float *out, int *ok);
 /* decode() of one chunk only (wmget.cc:886-939) -- the unit `get` is sharded by */
 int awm_decode_chunk_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d, size_t n_frames,
                         int n_channels, int first_chunk, size_t max_out, awm_pattern *out);
@@ -854,6 +895,17 @@ int  awm_debug_sync_db_sliding_rows_d (awm_ctx *ctx, const float *pcm_d, size_t 
                                        long long first, long long last, const long long *stream_range_d, const int *range_index_d, int range_div,
                                        int tables_per_slice, int ld, float *out_d, float *tail_d, long long tail_stream_stride, char *have_d,
                                        long long have_stream_stride);
+/* ... on a stream of SIGNED 16-BIT PCM (awm_get_watermark_s16_d above): K4s in the product's gathered layout, instantiated for 16-bit
+ * input.  Definition: every cell, have flag and untouched cell is bit for bit what awm_debug_sync_db_sliding_rows_d writes for the decoded
+ * stream.  Paths: stereo the default form (4, rows of 64 + tail), mono sync_db_sliding_kernel<1>; the wave-uniform base and one 32-bit
+ * lane offset of the float kernel are kept.  Alignment: any even address; stereo frames that are 4-byte aligned are loaded whole, a base
+ * that is only 2-byte aligned takes 2-byte loads.  Refusals: those of the float call, an odd pcm_d, and a form other than the default
+ * (awm_debug_set_refine_form): AWM_ERR_ARG, nothing enqueued.  Not offered: the other forms, awm_debug_sync_db_sliding_d's bands layout. */
+int  awm_debug_sync_db_sliding_rows_s16_d (awm_ctx *ctx, const int16_t *pcm_d, size_t n_frames, int n_channels, const long long *base_d,
+                                           const int *count_d, size_t n_streams, int count0, int rows_per_plane, const int *row_perm_d,
+                                           const unsigned char *band_pos_d, long long first, long long last, const long long *stream_range_d,
+                                           const int *range_index_d, int range_div, int tables_per_slice, int ld, float *out_d, float *tail_d,
+                                           long long tail_stream_stride, char *have_d, long long have_stream_stride);
 void awm_debug_set_soft_bits_generic (int on); /* K7: one thread per soft bit for every shape (the fallback kernel) | four bits per wave */
 /* The block decoder's dB pass (K4b) and soft bits (K7) as awm_block_soft_bits_d launches them, with the dB planes made visible (tests only).
  * The dB workspace is filled with the 32-bit pattern `fill` before K4b runs; the planes of the accepted blocks go to
