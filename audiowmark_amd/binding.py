@@ -309,6 +309,14 @@ lib.awm_sync_fft_s16_d.argtypes = lib.awm_sync_fft_d.argtypes
 lib.awm_sync_search_s16_d.argtypes = lib.awm_sync_search_d.argtypes
 lib.awm_block_soft_bits_s16_d.argtypes = lib.awm_block_soft_bits_d.argtypes
 lib.awm_debug_sync_db_sliding_rows_s16_d.argtypes = lib.awm_debug_sync_db_sliding_rows_d.argtypes
+# whole streams from and to signed 16-bit PCM (`add`, and "watermark, then verify")
+lib.awm_add_mix_s16_d.argtypes = lib.awm_add_mix_d.argtypes
+lib.awm_add_limit_s16_d.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, _vp, C.c_size_t, C.c_size_t]
+lib.awm_add_watermark_s16_d.argtypes = lib.awm_add_watermark_d.argtypes
+lib.awm_add_get_watermark_s16_d.argtypes = lib.awm_add_get_watermark_d.argtypes
+lib.awm_debug_add_s16_fused_in_use.argtypes = []
+lib.awm_debug_lane_add_mix_bytes.argtypes = [_vp]
+lib.awm_debug_lane_add_mix_bytes.restype = C.c_size_t
 
 
 def set_global_params(**kw):
@@ -1681,6 +1689,47 @@ class Context:
         if sample_rate != 44100:
             return self._patterns(lib.awm_get_watermark_rate_s16_d, "awm_get_watermark_rate_s16_d", self._h, key_bytes(key), ptr, n, ch, sample_rate)
         return self._patterns(lib.awm_get_watermark_s16_d, "awm_get_watermark_s16_d", self._h, key_bytes(key), ptr, n, ch)
+
+    # ---- whole streams from and to signed 16-bit PCM (awm_add_watermark_s16_d and its twins) ----
+    def add_watermark_s16(self, key, payload_hex, pcm16, out=None, sample_rate=44100):
+        """awm_add_watermark_s16_d: add_watermark on a torch.int16 stream as it is, into a torch.int16 `out` (None: a fresh tensor; `out` may
+        BE pcm16) -- value for value pcm_encode (direct16) of add_watermark (pcm_decode of the same bytes); returns `out`"""
+        import torch
+        n, ch = self._s16_shape(pcm16)
+        if out is None:
+            out = torch.empty_like(pcm16)
+        assert self._s16_shape(out) == (n, ch)
+        _check(lib.awm_add_watermark_s16_d(self._h, key_bytes(key), payload_hex.encode(), C.c_void_p(pcm16.data_ptr()),
+                                           C.c_void_p(out.data_ptr()), n, ch, sample_rate), "awm_add_watermark_s16_d")
+        return out
+
+    def add_get_watermark_s16(self, key, payload_hex, pcm16, out, sample_rate=44100):
+        """awm_add_get_watermark_s16_d: add_watermark_s16 into `out`, then get_watermark_s16 of `out`, as one call; returns the pattern
+        list -- the results of the two separate calls"""
+        n, ch = self._s16_shape(pcm16)
+        assert self._s16_shape(out) == (n, ch)
+        return self._patterns(lib.awm_add_get_watermark_s16_d, "awm_add_get_watermark_s16_d", self._h, key_bytes(key), payload_hex.encode(),
+                              C.c_void_p(pcm16.data_ptr()), C.c_void_p(out.data_ptr()), n, ch, sample_rate)
+
+    def add_mix_s16(self, pcm16, out, frame_mod, water_delta, first_frame, halo_before, halo_after, block_max, first_block=0):
+        """awm_add_mix_s16_d: add_mix on a torch.int16 span (and torch.int16 halos) -- `out` (float32) and block_max are bit for bit those of
+        add_mix on the decoded span and halos"""
+        n, ch = self._s16_shape(pcm16)
+        fm = np.ascontiguousarray(frame_mod, np.int8)
+        _check(lib.awm_add_mix_s16_d(self._h, C.c_void_p(pcm16.data_ptr()), _dev_ptr(out), n, ch, _np(fm), water_delta, first_frame,
+                                     C.c_void_p(halo_before.data_ptr()) if halo_before is not None else None,
+                                     C.c_void_p(halo_after.data_ptr()) if halo_after is not None else None,
+                                     _dev_ptr(block_max) if block_max is not None else None, first_block,
+                                     block_max.numel() if block_max is not None else 0), "awm_add_mix_s16_d")
+
+    def add_limit_s16(self, mix, out, first_sample, block_max, first_block=0):
+        """awm_add_limit_s16_d: the limiter's ramp over the float mix (block_max None: no ramp), encoded into the torch.int16 `out` -- value
+        for value pcm_encode (direct16) of what add_limit leaves in a copy of `mix`; `mix` is not modified"""
+        n, ch = _pcm_shape(mix)
+        assert self._s16_shape(out) == (n, ch)
+        _check(lib.awm_add_limit_s16_d(self._h, _dev_ptr(mix), C.c_void_p(out.data_ptr()), n, ch, first_sample,
+                                       _dev_ptr(block_max) if block_max is not None else None, first_block,
+                                       block_max.numel() if block_max is not None else 0), "awm_add_limit_s16_d")
 
     def get_watermark_keys_s16(self, keys, pcm16):
         """awm_get_watermark_keys_s16_d: get_watermark_keys on a torch.int16 stream"""

@@ -356,6 +356,26 @@ bool sliding_s16_form_ok();
 hipError_t launch_nonzero_range_s16 (hipStream_t st, const int16_t *data, long long n_values, unsigned long long *result);
 hipError_t launch_resample_s16 (hipStream_t st, const ResampleArgs& a);
 
+/* WHOLE STREAMS FROM AND TO SIGNED 16-BIT PCM (awm_add_watermark_s16_d).
+ * launch_add_mix_s16: K2 instantiated for PcmS16, the span form included.  AddMixArgs::pcm_in, halo_before and halo_after hold the ADDRESS
+ * of int16 values (interleaved, any even address; odd: hipErrorInvalidValue), converted where they leave global memory; out and block_max
+ * are bit for bit what launch_add_mix writes for the decoded stream and the decoded halos.
+ * launch_limit_encode: the last pass, launch_limiter's arguments plus the int16 sink.  out[v] is the direct16 rule of launch_pcm_encode
+ * (v * 32768, saturated at 32767 / -32768, truncated) of what launch_limiter leaves of mix[v]; mix is not modified and nothing outside
+ * out[0 .. n_frames * n_channels) is written.  block_max null: no ramp.  Stereo on a 4-byte aligned sink (mix 8-byte aligned): groups of
+ * four frames, one 16-byte store each (limit_encode_segment_body); mono: groups of eight values; every other channel count, a stereo sink
+ * that is only 2-byte aligned, limiter blocks below 2048 and a missing table workspace: a value per thread with launch_limiter's generic
+ * arithmetic.  No run is skipped where its ramp is (1, 0).  orig (stereo vector form only, else hipErrorInvalidValue): the address of
+ * int16 frames, 4-byte aligned; the value is mix[v] + the decoded orig[v] (launch_max_segment_s16's add), and a frame of orig is read for the
+ * last time by the thread that stores the same frame of out, so out may BE orig.
+ * launch_max_segment_s16: launch_max_segments_s16 for one segment, arguments by value. */
+hipError_t launch_add_mix_s16 (hipStream_t st, const DevTables& t, const AddMixArgs& a);
+hipError_t launch_limit_encode (hipStream_t st, const float *mix, short *out, long long n_frames, int n_channels, long long first_sample,
+                                const float *block_max, long long first_block, long long n_blocks, int limiter_block, float ceiling,
+                                float2 *scale_tab = nullptr, size_t scale_tab_entries = 0, const void *orig = nullptr);
+hipError_t launch_max_segment_s16 (hipStream_t st, const MixSegment& seg, int n_channels, int limiter_block);
+hipError_t launch_power_sums_s16 (hipStream_t st, const int16_t *orig, const float *mixed, long long n_values, double *acc);   // launch_power_sums, the input decoded as it is read
+
 /* K5: sync_decode (syncfinder.cc:116-153) for many candidates.
  * value(cand, row, band) = db[plane(cand) + row * row_stride + band * band_stride + lane(cand)],
  * have(cand, row)        = have[hplane(cand) + row * have_row_stride + lane(cand)]

@@ -115,6 +115,115 @@ fetch_channel (const float *pcm, long long idx, int avail, int C, int ch, int la
     }
 }
 
+/* What a kernel READS (K2 on 16-bit streams, the dB kernels and the resampler's taps straight from 16-bit PCM): the type of a value and of
+ * a stereo frame in global memory, and the conversion to the float the kernel works on.  PcmF32, the default of every template below: the
+ * values as they are.  PcmS16: signed 16 bit, the exact decode of pcm_decode_s16le_kernel, float (v) * (1 / 32768) with one rounded
+ * product; a stereo frame is one 4-byte load.  A value is converted once, where it leaves global memory -- on its way into the LDS
+ * window (which stays float2) or, in the unstaged taps and the copy, as it is read -- and nothing behind the load differs. */
+struct PcmF32
+{
+  typedef float  value;
+  typedef float2 frame2;
+  static __device__ __forceinline__ float  conv (float v) { return v; }
+  static __device__ __forceinline__ float2 conv2 (float2 v) { return v; }
+};
+struct PcmS16
+{
+  typedef short  value;
+  typedef short2 frame2;
+  static __device__ __forceinline__ float  conv (short v) { return __fmul_rn (float (v), 1.0f / 32768.0f); }
+  static __device__ __forceinline__ float2 conv2 (short2 v) { return make_float2 (conv (v.x), conv (v.y)); }
+};
+
+/* fetch_stereo / fetch_channel for a stream of SIGNED 16-BIT values -- whole streams straight from 16-bit PCM, kernels.hh
+ * launch_add_mix_s16 and launch_sync_db_s16: `pcm` holds the ADDRESS of the int16 values, any even address.  A lane owns the same samples
+ * as in the float forms, two adjacent frames.  Stereo: one 8-byte load where the pair is 8-byte aligned, two 4-byte loads (a frame each)
+ * where the frames are 4-byte aligned, four 2-byte loads on an address that is only 2-byte aligned; mono: one 4-byte load where the pair is
+ * 4-byte aligned, two 2-byte loads otherwise.  Every form reads the frame's values and nothing else, and decodes each as PcmS16 does. */
+__device__ __forceinline__ void
+fetch_stereo_s16 (const short *pcm, long long idx, int avail, int lane, float (&l)[16], float (&r)[16])
+{
+  const short *p = pcm + idx * 2;
+  const unsigned int align = (unsigned int) reinterpret_cast<uintptr_t> (p);
+  if (avail >= 1024 && (align & 7) == 0)
+    {
+      typedef short v4s __attribute__ ((ext_vector_type (4)));
+      const v4s *p4 = reinterpret_cast<const v4s *> (p);
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const v4s v = p4[lane + 64 * j];
+          l[2 * j] = PcmS16::conv (v.x); r[2 * j] = PcmS16::conv (v.y); l[2 * j + 1] = PcmS16::conv (v.z); r[2 * j + 1] = PcmS16::conv (v.w);
+        }
+    }
+  else if (avail >= 1024 && (align & 3) == 0)
+    {
+      const short2 *p2 = reinterpret_cast<const short2 *> (p);
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const float2 a = PcmS16::conv2 (p2[2 * (lane + 64 * j)]), b = PcmS16::conv2 (p2[2 * (lane + 64 * j) + 1]);
+          l[2 * j] = a.x; r[2 * j] = a.y; l[2 * j + 1] = b.x; r[2 * j + 1] = b.y;
+        }
+    }
+  else
+    {
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const int x = 2 * (lane + 64 * j);
+          l[2 * j]     = x < avail     ? PcmS16::conv (p[2 * x])     : 0.f;
+          r[2 * j]     = x < avail     ? PcmS16::conv (p[2 * x + 1]) : 0.f;
+          l[2 * j + 1] = x + 1 < avail ? PcmS16::conv (p[2 * x + 2]) : 0.f;
+          r[2 * j + 1] = x + 1 < avail ? PcmS16::conv (p[2 * x + 3]) : 0.f;
+        }
+    }
+}
+
+__device__ __forceinline__ void
+fetch_channel_s16 (const short *pcm, long long idx, int avail, int C, int ch, int lane, float (&v)[16])
+{
+  const short *p = pcm + idx * C + ch;
+  if (C == 1 && avail >= 1024 && ((reinterpret_cast<uintptr_t> (p) & 3) == 0))
+    {
+      const short2 *p2 = reinterpret_cast<const short2 *> (p);
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const float2 a = PcmS16::conv2 (p2[lane + 64 * j]);
+          v[2 * j] = a.x; v[2 * j + 1] = a.y;
+        }
+    }
+  else
+    {
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        {
+          const int x = 2 * (lane + 64 * j);
+          v[2 * j]     = x < avail     ? PcmS16::conv (p[(long long) x * C])       : 0.f;
+          v[2 * j + 1] = x + 1 < avail ? PcmS16::conv (p[(long long) (x + 1) * C]) : 0.f;
+        }
+    }
+}
+
+/* the fetch of a kernel templated over what its stream's values are: PcmF32 is the float form itself */
+template<class In> __device__ __forceinline__ void
+fetch_stereo_in (const float *pcm, long long idx, int avail, int lane, float (&l)[16], float (&r)[16])
+{
+  if constexpr (std::is_same<In, PcmS16>::value)
+    fetch_stereo_s16 (reinterpret_cast<const short *> (pcm), idx, avail, lane, l, r);
+  else
+    fetch_stereo (pcm, idx, avail, lane, l, r);
+}
+template<class In> __device__ __forceinline__ void
+fetch_channel_in (const float *pcm, long long idx, int avail, int C, int ch, int lane, float (&v)[16])
+{
+  if constexpr (std::is_same<In, PcmS16>::value)
+    fetch_channel_s16 (reinterpret_cast<const short *> (pcm), idx, avail, C, ch, lane, v);
+  else
+    fetch_channel (pcm, idx, avail, C, ch, lane, v);
+}
+
 // window + pack: frame[x] = sample * window[x] (float multiply, reference wmcommon.cc:106-110)
 __device__ __forceinline__ void
 window_pack (const float (&v)[16], const float *s_win, int lane, float2 (&z)[8])
@@ -610,7 +719,8 @@ span_partition (long long n_frames, int C, int L, int wave, long long& F, long l
 
 // where frame m comes from (halo before / the launch's samples / halo after) and how much of it exists.  Without HALO frames -1 and F are
 // silence.  The pointer is only good where avail > 0
-template<bool HALO> __device__ __forceinline__ const float *
+// In: what the stream's values are; PcmS16: the pointers hold the addresses of int16 values, and the frame's address is counted in them
+template<bool HALO, class In = PcmF32> __device__ __forceinline__ const float *
 frame_source (const float *pcm_in, long long n_frames, int C, long long F, long long m, const float *halo_before, const float *halo_after, int& avail)
 {
   if constexpr (HALO)
@@ -626,10 +736,10 @@ frame_source (const float *pcm_in, long long n_frames, int C, long long F, long 
       const long long left = n_frames - m * 1024;
       avail = left < 1024 ? int (left) : 1024;
     }
-  return pcm_in + m * 1024 * C;
+  return reinterpret_cast<const float *> (reinterpret_cast<const typename In::value *> (pcm_in) + m * 1024 * C);
 }
 
-template<int CV, bool OPAQUE, bool PAIR = false> __device__ __forceinline__ void
+template<int CV, bool OPAQUE, bool PAIR = false, class In = PcmF32> __device__ __forceinline__ void
 add_mix_body (const DevTables& t, const AddMixArgs& a, long long frame_number0, int block_frames)
 {
   __shared__ float2 s_tw[512];
@@ -676,15 +786,15 @@ add_mix_body (const DevTables& t, const AddMixArgs& a, long long frame_number0, 
           asm volatile ("" : "+v" (lane));
         }
       int avail;
-      const float *src = frame_source<true> (a.pcm_in, a.n_frames, C, F, m, a.halo_before, a.halo_after, avail);
+      const float *src = frame_source<true, In> (a.pcm_in, a.n_frames, C, F, m, a.halo_before, a.halo_after, avail);
       float in[CV][16];
       float2 d[CV][8];
       if (avail > 0)
         {
           if constexpr (CV == 2)
-            fetch_stereo (src, 0, avail, lane, in[0], in[1]);
+            fetch_stereo_in<In> (src, 0, avail, lane, in[0], in[1]);
           else
-            fetch_channel (src, 0, avail, C, ch0, lane, in[0]);
+            fetch_channel_in<In> (src, 0, avail, C, ch0, lane, in[0]);
           const long long g = a.first_frame + m;                       // frame index in the whole stream
           const long long row = (frame_number0 + g) % total_rows;      // reference wmadd.cc:326-344
           const int8_t *mod_row = a.frame_mod + row * NB;
@@ -740,22 +850,22 @@ add_mix_body (const DevTables& t, const AddMixArgs& a, long long frame_number0, 
     }
 }
 
-template<int CV> __global__ void __launch_bounds__ (64 * WAVES)
+template<int CV, class In = PcmF32> __global__ void __launch_bounds__ (64 * WAVES)
 add_mix_kernel (DevTables t, AddMixArgs a, long long frame_number0, int block_frames)
 {
-  add_mix_body<CV, false> (t, a, frame_number0, block_frames);
+  add_mix_body<CV, false, false, In> (t, a, frame_number0, block_frames);
 }
 // stereo: four waves per SIMD (122 registers, 39 KB of LDS per workgroup: four workgroups per CU)
-template<int CV> __global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
+template<int CV, class In = PcmF32> __global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
 add_mix_kernel_w4 (DevTables t, AddMixArgs a, long long frame_number0, int block_frames)
 {
-  add_mix_body<CV, true> (t, a, frame_number0, block_frames);
+  add_mix_body<CV, true, false, In> (t, a, frame_number0, block_frames);
 }
 // the same with the two channels' transforms pipelined over the wave's one exchange tile (frame_delta2)
-__global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
+template<class In = PcmF32> __global__ void __launch_bounds__ (64 * WAVES) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
 add_mix_pair_kernel (DevTables t, AddMixArgs a, long long frame_number0, int block_frames)
 {
-  add_mix_body<2, true, true> (t, a, frame_number0, block_frames);
+  add_mix_body<2, true, true, In> (t, a, frame_number0, block_frames);
 }
 /* a batch of clips in ONE launch (stereo): blockIdx.y = clip, its arguments from an array on the device (uniform: scalar loads); the grid's
  * x extent covers the clip with the most spans, the others' surplus workgroups return at once */
@@ -769,8 +879,10 @@ int add_mix_waves_per_simd() { return 4; }
 int g_fft_pair = 1;              // (debug toggle: stereo add with frame_delta2)
 extern "C" void awm_debug_set_fft_pair (int on) { g_fft_pair = on; }
 
-hipError_t
-launch_add_mix (hipStream_t st, const DevTables& t, const AddMixArgs& a)
+/* In: what pcm_in and the halos hold (PcmS16, launch_add_mix_s16: the addresses of int16 values, converted where they leave global memory;
+ * everything behind the fetch is the same code) */
+template<class In> static hipError_t
+launch_add_mix_any (hipStream_t st, const DevTables& t, const AddMixArgs& a)
 {
   if (a.n_frames <= 0)
     return hipSuccess;
@@ -783,12 +895,20 @@ launch_add_mix (hipStream_t st, const DevTables& t, const AddMixArgs& a)
   const long long frame_number0 = 2LL * block_frames - a.frames_pad_start;       // reference wmadd.cc:293-294
   // stereo: both channels in one wave, four waves per SIMD (122 registers; three waves + prefetch of the next frame: 3 - 5 % slower)
   if (stereo && g_fft_pair)
-    hipLaunchKernelGGL (add_mix_pair_kernel, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
+    hipLaunchKernelGGL (add_mix_pair_kernel<In>, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
   else if (stereo)
-    hipLaunchKernelGGL (add_mix_kernel_w4<2>, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
+    hipLaunchKernelGGL ((add_mix_kernel_w4<2, In>), dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
   else
-    hipLaunchKernelGGL (add_mix_kernel<1>, dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
+    hipLaunchKernelGGL ((add_mix_kernel<1, In>), dim3 (grid), dim3 (64 * WAVES), 0, st, t, a, frame_number0, block_frames);
   return hipGetLastError();
+}
+hipError_t launch_add_mix (hipStream_t st, const DevTables& t, const AddMixArgs& a) { return launch_add_mix_any<PcmF32> (st, t, a); }
+hipError_t
+launch_add_mix_s16 (hipStream_t st, const DevTables& t, const AddMixArgs& a)
+{
+  if ((reinterpret_cast<uintptr_t> (a.pcm_in) | reinterpret_cast<uintptr_t> (a.halo_before) | reinterpret_cast<uintptr_t> (a.halo_after)) & 1)
+    return hipErrorInvalidValue;
+  return launch_add_mix_any<PcmS16> (st, t, a);
 }
 
 hipError_t
@@ -1390,114 +1510,8 @@ struct ResampleStore
   __device__ __forceinline__ void put2 (long long k, float2 v) { reinterpret_cast<float2 *> (out)[k] = v; }
 };
 
-/* What the taps READ (stage 0 of the clip groups straight from 16-bit PCM, kernels.hh launch_clip_stage_s16): the type of a value and of
- * a stereo frame in global memory, and the conversion to the float the taps work on.  PcmF32, the default of every template below: the
- * values as they are.  PcmS16: signed 16 bit, the exact decode of pcm_decode_s16le_kernel, float (v) * (1 / 32768) with one rounded
- * product; a stereo frame is one 4-byte load.  A value is converted once, where it leaves global memory -- on its way into the LDS
- * window (which stays float2) or, in the unstaged taps and the copy, as it is read -- and nothing behind the load differs. */
-struct PcmF32
-{
-  typedef float  value;
-  typedef float2 frame2;
-  static __device__ __forceinline__ float  conv (float v) { return v; }
-  static __device__ __forceinline__ float2 conv2 (float2 v) { return v; }
-};
-struct PcmS16
-{
-  typedef short  value;
-  typedef short2 frame2;
-  static __device__ __forceinline__ float  conv (short v) { return __fmul_rn (float (v), 1.0f / 32768.0f); }
-  static __device__ __forceinline__ float2 conv2 (short2 v) { return make_float2 (conv (v.x), conv (v.y)); }
-};
-
-/* fetch_stereo / fetch_channel (top of this file) for a stream of SIGNED 16-BIT values -- whole streams straight from 16-bit PCM, kernels.hh
- * launch_sync_db_s16: `pcm` holds the ADDRESS of the int16 values, any even address.  A lane owns the same samples as in the float
- * forms, two adjacent frames.  Stereo: one 8-byte load where the pair is 8-byte aligned, two 4-byte loads (a frame each) where the
- * frames are 4-byte aligned, four 2-byte loads on an address that is only 2-byte aligned; mono: one 4-byte load where the pair is
- * 4-byte aligned, two 2-byte loads otherwise.  Every form reads the frame's values and nothing else, and decodes each as PcmS16 does. */
-__device__ __forceinline__ void
-fetch_stereo_s16 (const short *pcm, long long idx, int avail, int lane, float (&l)[16], float (&r)[16])
-{
-  const short *p = pcm + idx * 2;
-  const unsigned int align = (unsigned int) reinterpret_cast<uintptr_t> (p);
-  if (avail >= 1024 && (align & 7) == 0)
-    {
-      typedef short v4s __attribute__ ((ext_vector_type (4)));
-      const v4s *p4 = reinterpret_cast<const v4s *> (p);
-#pragma unroll
-      for (int j = 0; j < 8; j++)
-        {
-          const v4s v = p4[lane + 64 * j];
-          l[2 * j] = PcmS16::conv (v.x); r[2 * j] = PcmS16::conv (v.y); l[2 * j + 1] = PcmS16::conv (v.z); r[2 * j + 1] = PcmS16::conv (v.w);
-        }
-    }
-  else if (avail >= 1024 && (align & 3) == 0)
-    {
-      const short2 *p2 = reinterpret_cast<const short2 *> (p);
-#pragma unroll
-      for (int j = 0; j < 8; j++)
-        {
-          const float2 a = PcmS16::conv2 (p2[2 * (lane + 64 * j)]), b = PcmS16::conv2 (p2[2 * (lane + 64 * j) + 1]);
-          l[2 * j] = a.x; r[2 * j] = a.y; l[2 * j + 1] = b.x; r[2 * j + 1] = b.y;
-        }
-    }
-  else
-    {
-#pragma unroll
-      for (int j = 0; j < 8; j++)
-        {
-          const int x = 2 * (lane + 64 * j);
-          l[2 * j]     = x < avail     ? PcmS16::conv (p[2 * x])     : 0.f;
-          r[2 * j]     = x < avail     ? PcmS16::conv (p[2 * x + 1]) : 0.f;
-          l[2 * j + 1] = x + 1 < avail ? PcmS16::conv (p[2 * x + 2]) : 0.f;
-          r[2 * j + 1] = x + 1 < avail ? PcmS16::conv (p[2 * x + 3]) : 0.f;
-        }
-    }
-}
-
-__device__ __forceinline__ void
-fetch_channel_s16 (const short *pcm, long long idx, int avail, int C, int ch, int lane, float (&v)[16])
-{
-  const short *p = pcm + idx * C + ch;
-  if (C == 1 && avail >= 1024 && ((reinterpret_cast<uintptr_t> (p) & 3) == 0))
-    {
-      const short2 *p2 = reinterpret_cast<const short2 *> (p);
-#pragma unroll
-      for (int j = 0; j < 8; j++)
-        {
-          const float2 a = PcmS16::conv2 (p2[lane + 64 * j]);
-          v[2 * j] = a.x; v[2 * j + 1] = a.y;
-        }
-    }
-  else
-    {
-#pragma unroll
-      for (int j = 0; j < 8; j++)
-        {
-          const int x = 2 * (lane + 64 * j);
-          v[2 * j]     = x < avail     ? PcmS16::conv (p[(long long) x * C])       : 0.f;
-          v[2 * j + 1] = x + 1 < avail ? PcmS16::conv (p[(long long) (x + 1) * C]) : 0.f;
-        }
-    }
-}
-
-/* the fetch of a kernel templated over what its stream's values are: PcmF32 is the float form itself */
-template<class In> __device__ __forceinline__ void
-fetch_stereo_in (const float *pcm, long long idx, int avail, int lane, float (&l)[16], float (&r)[16])
-{
-  if constexpr (std::is_same<In, PcmS16>::value)
-    fetch_stereo_s16 (reinterpret_cast<const short *> (pcm), idx, avail, lane, l, r);
-  else
-    fetch_stereo (pcm, idx, avail, lane, l, r);
-}
-template<class In> __device__ __forceinline__ void
-fetch_channel_in (const float *pcm, long long idx, int avail, int C, int ch, int lane, float (&v)[16])
-{
-  if constexpr (std::is_same<In, PcmS16>::value)
-    fetch_channel_s16 (reinterpret_cast<const short *> (pcm), idx, avail, C, ch, lane, v);
-  else
-    fetch_channel (pcm, idx, avail, C, ch, lane, v);
-}
+/* (What the taps READ -- PcmF32, the default of every template below, or PcmS16 -- is defined with the sample fetches at the top of this
+ * file: K2 reads 16-bit streams too.) */
 
 /* stereo, input window of the tile staged in LDS (zero extended): s_in[0] is input frame first0; same products and sums as below */
 template<class Sink> __device__ __forceinline__ void
@@ -2159,14 +2173,14 @@ constexpr int MIX_RUN = 2048;            // values per thread group run: 256 thr
 
 /* `add --snr` (reference wmadd.cc:553-563): power of the input and of (mix - input) BEFORE the limiter, in double like the
  * reference's loop; acc[0] += sum (mix - orig)^2, acc[1] += sum orig^2 */
-__global__ void __launch_bounds__ (256)
-power_sums_kernel (const float *orig, const float *mixed, long long n_values, double *acc)
+template<class In> __device__ __forceinline__ void
+power_sums_body (const typename In::value *orig, const float *mixed, long long n_values, double *acc)
 {
   __shared__ double s_d[4], s_s[4];
   double d2 = 0, s2 = 0;
   for (long long i = (long long) blockIdx.x * 256 + threadIdx.x; i < n_values; i += (long long) gridDim.x * 256)
     {
-      const double o = orig[i], d = double (mixed[i]) - o;
+      const double o = In::conv (orig[i]), d = double (mixed[i]) - o;
       d2 += d * d;
       s2 += o * o;
     }
@@ -2188,6 +2202,17 @@ power_sums_kernel (const float *orig, const float *mixed, long long n_values, do
       atomicAdd (acc + 1, s_s[0] + s_s[1] + s_s[2] + s_s[3]);
     }
 }
+__global__ void __launch_bounds__ (256)
+power_sums_kernel (const float *orig, const float *mixed, long long n_values, double *acc)
+{
+  power_sums_body<PcmF32> (orig, mixed, n_values, acc);
+}
+// (the input as signed 16-bit PCM, decoded as it is read: K2 on 16-bit streams)
+__global__ void __launch_bounds__ (256)
+power_sums_s16_kernel (const short *orig, const float *mixed, long long n_values, double *acc)
+{
+  power_sums_body<PcmS16> (orig, mixed, n_values, acc);
+}
 
 hipError_t
 launch_power_sums (hipStream_t st, const float *orig, const float *mixed, long long n_values, double *acc)
@@ -2196,6 +2221,16 @@ launch_power_sums (hipStream_t st, const float *orig, const float *mixed, long l
     return hipSuccess;
   const long long blocks = (n_values + 256 * 16 - 1) / (256 * 16);
   hipLaunchKernelGGL (power_sums_kernel, dim3 (unsigned (blocks < 4096 ? blocks : 4096)), dim3 (256), 0, st, orig, mixed, n_values, acc);
+  return hipGetLastError();
+}
+hipError_t
+launch_power_sums_s16 (hipStream_t st, const int16_t *orig, const float *mixed, long long n_values, double *acc)
+{
+  if (n_values <= 0)
+    return hipSuccess;
+  const long long blocks = (n_values + 256 * 16 - 1) / (256 * 16);
+  hipLaunchKernelGGL (power_sums_s16_kernel, dim3 (unsigned (blocks < 4096 ? blocks : 4096)), dim3 (256), 0, st, reinterpret_cast<const short *> (orig),
+                      mixed, n_values, acc);
   return hipGetLastError();
 }
 
@@ -2392,6 +2427,24 @@ launch_mix_max_segment (hipStream_t st, const MixSegment& seg, int n_channels, i
   if (n_channels < 1 || seg.pre < 0 || seg.first_sample < seg.pre || (long long) limiter_block * n_channels < MIX_RUN)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL (mix_max_segment_kernel, dim3 (unsigned ((n_values + MIX_RUN - 1) / MIX_RUN)), dim3 (256), 0, st, seg, n_channels, limiter_block);
+  return hipGetLastError();
+}
+// (one 16-bit segment, the maxima alone, arguments by value: the whole stream at another rate, awm_add_watermark_s16_d)
+__global__ void __launch_bounds__ (256)
+max_segment_s16_kernel (MixSegment s, int C, int BS)
+{
+  mix_max_segment_body<PcmS16, false> (s, C, BS);
+}
+hipError_t
+launch_max_segment_s16 (hipStream_t st, const MixSegment& seg, int n_channels, int limiter_block)
+{
+  const long long n_values = (seg.pre + seg.n_frames) * n_channels;
+  if (n_values <= 0)
+    return hipSuccess;
+  if (n_channels < 1 || seg.pre < 0 || seg.first_sample < seg.pre || (long long) limiter_block * n_channels < MIX_RUN
+      || (reinterpret_cast<uintptr_t> (seg.orig) & 1))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL (max_segment_s16_kernel, dim3 (unsigned ((n_values + MIX_RUN - 1) / MIX_RUN)), dim3 (256), 0, st, seg, n_channels, limiter_block);
   return hipGetLastError();
 }
 
@@ -4995,6 +5048,138 @@ launch_limit_encode_segments_rates (hipStream_t st, const RateLimitEncodeSegment
     hipLaunchKernelGGL (limit_encode_segments_rates_kernel<true>, grid, dim3 (256), 0, st, segs_dev);
   else
     hipLaunchKernelGGL (limit_encode_segments_rates_kernel<false>, grid, dim3 (256), 0, st, segs_dev);
+  return hipGetLastError();
+}
+
+/* kernels.hh launch_limit_encode: the last pass of a WHOLE STREAM from and to 16-bit PCM, arguments by value.  Stereo on a 4-byte aligned
+ * sink is the segments' body (groups of four frames).  Unlike limiter_apply_run no run is skipped where its entries are (1, 0): the values
+ * still have to be encoded. */
+template<bool MIX> __global__ void __launch_bounds__ (256)
+limit_encode_kernel (LimitEncodeSegment s, int BS)
+{
+  limit_encode_segment_body<MIX> (s, BS);
+}
+__device__ __forceinline__ int
+encode_direct16_value (float v, float scale)
+{
+  const float s = __fmul_rn (__fmul_rn (v, scale), 32768.f);
+  return s >= 32767.f ? 32767 : (s <= -32768.f ? -32768 : int (s));
+}
+/* mono: a thread owns a group of eight values, one 16-byte store, from the first 16-byte boundary of `out`; the up to seven values in front
+ * and behind are single values of workgroup 0.  A workgroup owns 256 groups, 2048 values: at most two table entries. */
+__global__ void __launch_bounds__ (256)
+limit_encode_mono_kernel (LimitEncodeSegment s, int BS)
+{
+  const long long n = s.n_frames;
+  const long long to_grid = (long long) (((16 - (reinterpret_cast<uintptr_t> (s.out) & 15)) & 15) / 2);
+  const long long peel = to_grid < n ? to_grid : n;
+  const long long n_groups = (n - peel) / 8;
+  const long long base = (long long) blockIdx.x * 256;
+  if (base < n_groups)
+    {
+      const long long gs0 = s.first_sample + peel + 8 * base;
+      float2 t0 = make_float2 (1.f, 0.f), t1 = t0;
+      int i0 = 0;
+      if (s.tab)
+        {
+          const long long b0 = gs0 / BS;                      // uniform: once per workgroup
+          i0 = int (gs0 - b0 * BS);
+          const float2 *tb = s.tab + (b0 - s.tab_first_block);
+          t0 = tb[0];
+          t1 = tb[1];
+        }
+      auto scale = [&] (int i) -> float {
+        const bool next = i >= BS;
+        const float2 t = next ? t1 : t0;
+        return __fadd_rn (t.x, __fmul_rn (float (next ? i - BS : i), t.y));
+      };
+      const long long q = base + threadIdx.x;
+      if (q < n_groups)
+        {
+          const float *src = s.wm + peel + 8 * q;
+          float v[8];
+#pragma unroll
+          for (int k = 0; k < 8; k++)
+            v[k] = src[k];
+          const int i = i0 + 8 * int (threadIdx.x);
+          unsigned int w[4];
+#pragma unroll
+          for (int k = 0; k < 4; k++)
+            w[k] = ((unsigned int) encode_direct16_value (v[2 * k], scale (i + 2 * k)) & 0xffffu)
+                 | ((unsigned int) encode_direct16_value (v[2 * k + 1], scale (i + 2 * k + 1)) << 16);
+          reinterpret_cast<uint4 *> (s.out + peel)[q] = make_uint4 (w[0], w[1], w[2], w[3]);
+        }
+    }
+  if (blockIdx.x == 0)
+    {
+      const long long f = threadIdx.x < peel ? threadIdx.x : peel + 8 * n_groups + (threadIdx.x - peel);
+      if (f < n)
+        {
+          float sc = 1.f;
+          if (s.tab)
+            {
+              const long long gs = s.first_sample + f, b = gs / BS;
+              const float2 t = s.tab[b - s.tab_first_block];
+              sc = __fadd_rn (t.x, __fmul_rn (float (int (gs - b * BS)), t.y));
+            }
+          s.out[f] = short (encode_direct16_value (s.wm[f], sc));
+        }
+    }
+}
+// every other channel count, sinks that are only 2-byte aligned, short limiter blocks: a value per thread, limiter_scale's arithmetic
+__global__ void __launch_bounds__ (256)
+limit_encode_values_kernel (const float *mix, short *out, long long n_frames, int C, long long first_sample, const float *block_max,
+                            long long first_block, long long n_blocks, int BS, float ceiling)
+{
+  const long long n_values = n_frames * C;
+  const long long stride = (long long) gridDim.x * blockDim.x;
+  for (long long v = (long long) blockIdx.x * blockDim.x + threadIdx.x; v < n_values; v += stride)
+    {
+      const float sc = block_max ? limiter_scale (first_sample + v / C, block_max, first_block, n_blocks, BS, ceiling) : 1.f;
+      out[v] = short (encode_direct16_value (mix[v], sc));
+    }
+}
+
+hipError_t
+launch_limit_encode (hipStream_t st, const float *mix, short *out, long long n_frames, int n_channels, long long first_sample,
+                     const float *block_max, long long first_block, long long n_blocks, int limiter_block, float ceiling,
+                     float2 *scale_tab, size_t scale_tab_entries, const void *orig)
+{
+  if (n_frames <= 0 || n_channels < 1)
+    return hipSuccess;
+  if (!mix || !out || (reinterpret_cast<uintptr_t> (out) & 1) || (reinterpret_cast<uintptr_t> (mix) & 3) || limiter_block < 1)
+    return hipErrorInvalidValue;
+  const size_t need = limiter_tab_entries (n_frames, first_sample, limiter_block);
+  const uintptr_t out_a = reinterpret_cast<uintptr_t> (out), mix_a = reinterpret_cast<uintptr_t> (mix), orig_a = reinterpret_cast<uintptr_t> (orig);
+  const bool tab_ok = !block_max || (scale_tab && scale_tab_entries >= need);
+  const bool vec = tab_ok && limiter_block >= 4 * ENC_RUN
+                && ((n_channels == 2 && (out_a & 3) == 0 && (mix_a & 7) == 0 && (orig_a & 3) == 0) || (n_channels == 1 && !orig));
+  if (!vec)
+    {
+      if (orig)
+        return hipErrorInvalidValue;                            // (the mix computed again: the stereo form only)
+      long long blocks = (n_frames * n_channels + 255) / 256;
+      if (blocks > 256 * 32)
+        blocks = 256 * 32;
+      hipLaunchKernelGGL (limit_encode_values_kernel, dim3 (unsigned (blocks)), dim3 (256), 0, st, mix, out, n_frames, n_channels, first_sample,
+                          block_max, first_block, n_blocks, limiter_block, ceiling);
+      return hipGetLastError();
+    }
+  const long long tab_first = first_sample / limiter_block;
+  if (block_max)
+    hipLaunchKernelGGL (limiter_table_kernel, dim3 (unsigned ((need + 255) / 256)), dim3 (256), 0, st, scale_tab, tab_first, (long long) need,
+                        block_max, first_block, n_blocks, limiter_block, ceiling);
+  const LimitEncodeSegment s { orig, mix, out, n_frames, first_sample, block_max ? scale_tab : nullptr, tab_first };
+  if (n_channels == 1)
+    hipLaunchKernelGGL (limit_encode_mono_kernel, dim3 (unsigned (std::max<long long> (1, (n_frames / 8 + 255) / 256))), dim3 (256), 0, st, s, limiter_block);
+  else
+    {
+      const dim3 grid (unsigned (std::max<long long> (1, (n_frames / 4 + ENC_RUN - 1) / ENC_RUN)));
+      if (orig)
+        hipLaunchKernelGGL (limit_encode_kernel<true>, grid, dim3 (256), 0, st, s, limiter_block);
+      else
+        hipLaunchKernelGGL (limit_encode_kernel<false>, grid, dim3 (256), 0, st, s, limiter_block);
+    }
   return hipGetLastError();
 }
 

@@ -218,8 +218,9 @@ static int
 add_mix_impl (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
               const int8_t *frame_mod_dev, double water_delta, size_t first_frame,
               const float *halo_before_d, const float *halo_after_d, float *block_max_d, size_t first_block, size_t n_blocks,
-              WorkLane *lane = nullptr, int delta_only = 0)
+              WorkLane *lane = nullptr, int delta_only = 0, bool s16 = false)
 {
+  // (s16: pcm_in_d and the halos hold the addresses of int16 values, K2 instantiated for 16-bit input; counted under the float K2's scope)
   hipStream_t st = lane ? lane->stream : ctx->stream;
   awmk::AddMixArgs a {};
   a.pcm_in = pcm_in_d;
@@ -237,10 +238,13 @@ add_mix_impl (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames
   a.frames_per_span = frames_per_span (ctx, (long long) (n_frames + 1023) / 1024);
   a.delta_only = delta_only;
   {
-    ProfScope ps (ctx, PROF_ADD_MIX, double (n_frames) * n_channels * 8.0, st);     // read + write every sample once
-    AWM_HIP_CHECK (awmk::launch_add_mix (st, ctx->tabs, a));
+    ProfScope ps (ctx, PROF_ADD_MIX, double (n_frames) * n_channels * (s16 ? 6.0 : 8.0), st);     // read + write every sample once
+    AWM_HIP_CHECK (s16 ? awmk::launch_add_mix_s16 (st, ctx->tabs, a) : awmk::launch_add_mix (st, ctx->tabs, a));
   }
-  if (ctx->snr_on)                    // add --snr: the mix before the limiter (reference wmadd.cc:553-563)
+  if (ctx->snr_on && s16)
+    AWM_HIP_CHECK (awmk::launch_power_sums_s16 (st, reinterpret_cast<const int16_t *> (pcm_in_d), out_d, (long long) (n_frames * n_channels),
+                                                ctx->ws_snr.as<double>()));
+  else if (ctx->snr_on)               // add --snr: the mix before the limiter (reference wmadd.cc:553-563)
     AWM_HIP_CHECK (awmk::launch_power_sums (st, pcm_in_d, out_d, (long long) (n_frames * n_channels), ctx->ws_snr.as<double>()));
   return 0;
 }
@@ -322,6 +326,78 @@ awm_add_limit_d (awm_ctx *ctx, float *out_d, size_t n_frames, int n_channels, si
   return 0;
 }
 
+/* The two halves on signed 16-bit PCM (include/awm_hip.h): K2 instantiated for 16-bit input, and the last pass -- ramp, encode, store -- of
+ * a whole stream.  Refusals before anything is enqueued. */
+int
+awm_add_mix_s16_d (awm_ctx *ctx, const int16_t *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
+                   const int8_t *frame_mod, double water_delta, size_t first_frame,
+                   const int16_t *halo_before_d, const int16_t *halo_after_d,
+                   float *block_max_d, size_t first_block, size_t n_blocks)
+{
+  AWM_ENTER (ctx);
+  const char *bad = nullptr;
+  if (n_channels < 1)
+    bad = "n_channels < 1";
+  else if ((reinterpret_cast<uintptr_t> (pcm_in_d) | reinterpret_cast<uintptr_t> (halo_before_d) | reinterpret_cast<uintptr_t> (halo_after_d)) & 1)
+    bad = "an int16 pointer is not 2-byte aligned";
+  else if (!frame_mod || (n_frames && (!pcm_in_d || !out_d)))
+    bad = "null pointer";
+  if (bad)
+    {
+      set_error (std::string ("awm_add_mix_s16_d: ") + bad);
+      return AWM_ERR_ARG;
+    }
+  if (!n_frames)
+    return 0;
+  const size_t table_bytes = 2 * mark_block_frame_count() * Params::n_bands;
+  if (int rc = ctx->ws_misc.reserve (table_bytes)) return rc;
+  AWM_HIP_CHECK (hipMemcpyAsync (ctx->ws_misc.ptr, frame_mod, table_bytes, hipMemcpyHostToDevice, ctx->stream));
+  return add_mix_impl (ctx, reinterpret_cast<const float *> (pcm_in_d), out_d, n_frames, n_channels, ctx->ws_misc.as<int8_t>(), water_delta, first_frame,
+                       reinterpret_cast<const float *> (halo_before_d), reinterpret_cast<const float *> (halo_after_d), block_max_d, first_block,
+                       n_blocks, nullptr, 0, /* s16 */ true);
+}
+
+/* one pass of the last pass on a lane: the table entries of its own blocks, then ramp + encode + store (counted under limit_encode_s16_kernel) */
+static int
+limit_encode_pass (awm_ctx *ctx, WorkLane *lane, const float *mix_d, int16_t *out_d, size_t n_frames, int n_channels, size_t first_sample,
+                   const float *block_max_d, size_t first_block, size_t n_blocks, int limiter_block, const int16_t *orig_d = nullptr)
+{
+  float2 *tab = nullptr;
+  size_t tab_entries = 0;
+  if (block_max_d)
+    {
+      tab_entries = awmk::limiter_tab_entries ((long long) n_frames, (long long) first_sample, limiter_block);
+      if (int rc = lane->ws_limit_tab.reserve ((tab_entries + 1) * sizeof (float2))) return rc;
+      tab = lane->ws_limit_tab.as<float2>();
+    }
+  ProfScope ps (ctx, PROF_LIMIT_ENCODE_S16, double (n_frames) * n_channels * (orig_d ? 8.0 : 6.0), lane->stream);
+  AWM_HIP_CHECK (awmk::launch_limit_encode (lane->stream, mix_d, out_d, (long long) n_frames, n_channels, (long long) first_sample, block_max_d,
+                                            (long long) first_block, (long long) n_blocks, limiter_block, LIMITER_CEILING, tab, tab_entries, orig_d));
+  return 0;
+}
+
+int
+awm_add_limit_s16_d (awm_ctx *ctx, const float *mix_d, int16_t *out_d, size_t n_frames, int n_channels, size_t first_sample,
+                     const float *block_max_d, size_t first_block, size_t n_blocks)
+{
+  AWM_ENTER (ctx);
+  const char *bad = nullptr;
+  if (n_channels < 1)
+    bad = "n_channels < 1";
+  else if (reinterpret_cast<uintptr_t> (out_d) & 1)
+    bad = "out_d is not 2-byte aligned";
+  else if (n_frames && (!mix_d || !out_d))
+    bad = "null pointer";
+  if (bad)
+    {
+      set_error (std::string ("awm_add_limit_s16_d: ") + bad);
+      return AWM_ERR_ARG;
+    }
+  if (!n_frames)
+    return 0;
+  return limit_encode_pass (ctx, ctx, mix_d, out_d, n_frames, n_channels, first_sample, block_max_d, first_block, n_blocks, LIMITER_BLOCK);
+}
+
 /* (measurement knob, tools/gpu_add_slabs.py) `add` in slabs of this many MB of output: the fused add of slab s, then the limiter for
  * everything whose look-ahead second is complete -- so that the limiter re-reads what the add has just written while it may still
  * be in the 256 MB memory-side cache.  0 (default): one add over the whole stream, then one limiter pass.  DESIGN.md section 3 has
@@ -338,6 +414,83 @@ add_buffers_overlap (const float *in, const float *out, size_t n_values)
 {
   const uintptr_t a = reinterpret_cast<uintptr_t> (in), b = reinterpret_cast<uintptr_t> (out), bytes = n_values * sizeof (float);
   return a < b + bytes && b < a + bytes;
+}
+
+/* where the passes of the last stage of a whole-stream `add` end: with marks (awm_add_get_watermark_d and its 16-bit twin) one pass per
+ * range of `get`'s chunk ends, rounded up to whole limiter blocks, else one pass */
+static std::vector<size_t>
+last_pass_ends (size_t n_frames, int n_channels, bool per_chunk)
+{
+  std::vector<size_t> ends;
+  if (per_chunk)
+    for (const ChunkRange& c : plan_chunks (n_frames, n_channels))
+      {
+        size_t e = std::min (n_frames, (c.first_frame + c.n_frames + LIMITER_BLOCK - 1) / LIMITER_BLOCK * size_t (LIMITER_BLOCK));
+        if (e < n_frames && n_frames - e < size_t (LIMITER_BLOCK))          // (no sliver of a last pass)
+          e = n_frames;
+        if (ends.empty() || e > ends.back())
+          ends.push_back (e);
+      }
+  if (ends.empty() || ends.back() != n_frames)
+    ends.push_back (n_frames);
+  return ends;
+}
+
+/* add_full from and to 16-bit PCM (awm_add_watermark_s16_d at 44.1 kHz), every channel count and any even address: K2 reads the int16
+ * values and writes the un-limited float mix into the lane's grow-only workspace, the last pass -- ramp, encode, store -- runs per range
+ * and leaves an event behind each when marks are armed.  out_d may be pcm_in_d: K2 has consumed the input before the first pass stores.
+ * No decode and no encode launch; the slab switch of add_full does not apply. */
+static int
+add_full_s16 (awm_ctx *ctx, const int16_t *pcm_in_d, int16_t *out_d, size_t n_frames, int n_channels,
+              const int8_t *frame_mod_dev, double water_delta, int use_limiter, WorkLane *lane = nullptr, ReadyMarks *marks = nullptr)
+{
+  if (!lane)
+    lane = ctx;
+  if (marks)
+    {
+      marks->disarm();
+      marks->base = out_d;
+      marks->n_frames = n_frames;
+    }
+  hipStream_t st = lane->stream;
+  float *block_max = nullptr;
+  const size_t n_blocks = n_frames / LIMITER_BLOCK + 2;
+  if (use_limiter)
+    {
+      if (int rc = lane->ws_block_max.reserve (n_blocks * sizeof (float))) return rc;
+      block_max = lane->ws_block_max.as<float>();
+      unsigned int bits;
+      std::memcpy (&bits, &LIMITER_CEILING, sizeof (bits));
+      AWM_HIP_CHECK (awmk::launch_fill_u32 (st, reinterpret_cast<unsigned int *> (block_max), bits, n_blocks));
+    }
+  if (int rc = lane->ws_add_mix.reserve (n_frames * n_channels * sizeof (float))) return rc;
+  float *mix = lane->ws_add_mix.as<float>();
+  if (int rc = add_mix_impl (ctx, reinterpret_cast<const float *> (pcm_in_d), mix, n_frames, n_channels, frame_mod_dev, water_delta, 0, nullptr, nullptr,
+                             block_max, 0, n_blocks, lane, 0, /* s16 */ true))
+    return rc;
+  size_t done = 0;
+  for (size_t e : last_pass_ends (n_frames, n_channels, marks != nullptr))
+    {
+      // (the passes share the lane's ramp table: they run in stream order, a pass rebuilds the entries of its own blocks)
+      if (int rc = limit_encode_pass (ctx, lane, mix + done * n_channels, out_d + done * n_channels, e - done, n_channels, done, block_max, 0, n_blocks,
+                                      LIMITER_BLOCK))
+        return rc;
+      done = e;
+      if (marks)
+        {
+          hipEvent_t ev = marks->next_event();
+          if (!ev)
+            {
+              set_error ("cannot create an event");
+              return AWM_ERR_HIP;
+            }
+          AWM_HIP_CHECK (hipEventRecord (ev, st));
+          marks->marks.push_back ({ e, ev });
+        }
+    }
+  if (marks)
+    marks->armed = true;
+  return 0;
 }
 
 /* whole stream on one lane (stream + block maxima + limiter table of that lane; the context itself is lane 0) */
@@ -401,18 +554,7 @@ add_full (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames, in
     return rc;
   // With marks (awm_add_get_watermark_d) the limiter runs in one pass per range of `get`'s chunk ends (every block maximum is known
   // after the mix: a pass needs nothing from the passes after it) and leaves an event behind each: the chunk that ends there may start.
-  std::vector<size_t> ends;
-  if (marks)
-    for (const ChunkRange& c : plan_chunks (n_frames, n_channels))
-      {
-        size_t e = std::min (n_frames, (c.first_frame + c.n_frames + LIMITER_BLOCK - 1) / LIMITER_BLOCK * size_t (LIMITER_BLOCK));
-        if (e < n_frames && n_frames - e < size_t (LIMITER_BLOCK))          // (no sliver of a last pass)
-          e = n_frames;
-        if (ends.empty() || e > ends.back())
-          ends.push_back (e);
-      }
-  if (ends.empty() || ends.back() != n_frames)
-    ends.push_back (n_frames);
+  const std::vector<size_t> ends = last_pass_ends (n_frames, n_channels, marks != nullptr);
   if (use_limiter)
     {
       const size_t tab_entries = awmk::limiter_tab_entries ((long long) n_frames, 0, LIMITER_BLOCK);
@@ -2424,6 +2566,186 @@ awm_add_get_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payloa
   for (size_t i = 0; i < rs.patterns.size() && i < max_out; i++)
     fill_pattern (rs.patterns[i], out[i]);
   return int (rs.patterns.size());
+}
+
+/* WHOLE STREAMS FROM AND TO 16-BIT PCM (include/awm_hip.h awm_add_watermark_s16_d). */
+static int g_add_s16_fused_in_use = 0;
+extern "C" int awm_debug_add_s16_fused_in_use (void) { return g_add_s16_fused_in_use; }
+
+/* the refusals of both pipeline calls, before anything is enqueued */
+static int
+check_add_s16 (awm_ctx *ctx, const char *who, const int16_t *pcm_in_d, const int16_t *out_d, size_t n_frames, int n_channels, int sample_rate)
+{
+  const uintptr_t a = reinterpret_cast<uintptr_t> (pcm_in_d), b = reinterpret_cast<uintptr_t> (out_d);
+  const char *bad = nullptr;
+  if (n_channels < 1)
+    bad = "n_channels < 1";
+  else if ((a | b) & 1)
+    bad = "an int16 pointer is not 2-byte aligned";
+  else if (n_frames && (!pcm_in_d || !out_d))
+    bad = "null pointer";
+  else if (sample_rate <= 0)
+    bad = "bad sample rate";
+  else
+    {
+      const uintptr_t bytes = n_frames * size_t (n_channels) * sizeof (int16_t);
+      if (a != b && a < b + bytes && b < a + bytes)
+        bad = "the output overlaps the input partially (out_d == pcm_in_d exactly is allowed)";
+    }
+  if (bad)
+    {
+      set_error (std::string (who) + ": " + bad);
+      return AWM_ERR_ARG;
+    }
+  if (sample_rate != Params::mark_sample_rate
+      && (!rate_converter (ctx, sample_rate, Params::mark_sample_rate).ok() || !rate_converter (ctx, Params::mark_sample_rate, sample_rate).ok()))
+    return AWM_ERR_ARG;                                         // (rate_converter has set the message)
+  return 0;
+}
+
+/* add_full_rate from and to 16-bit PCM: stereo, 4-byte aligned pointers, fixed-ratio tables both ways.  Kernels that exist, composed: the
+ * down-resampler reads the int16 values, K2 writes the watermark signal alone, the up-resampler brings it to the rate; the block maxima
+ * come from decode (in) + wm with nothing stored, and the last pass computes that sum again, applies the ramp, encodes and stores.  A frame
+ * of the input is read for the last time by the thread that stores the same frame of the output: out_d may be pcm_in_d. */
+static int
+add_full_rate_s16 (awm_ctx *ctx, const int16_t *pcm_in_d, int16_t *out_d, size_t n_frames, const int8_t *frame_mod_dev, double water_delta,
+                   int use_limiter, int rate, const RateConverter& down, const RateConverter& up)
+{
+  const int C = 2;
+  const size_t last44 = up.window_start (n_frames - 1) + size_t (up.hl()) + 1;     // (add_full_rate's geometry)
+  const size_t F = last44 / Params::frame_size + 1;
+  const size_t n44 = (F + 1) * Params::frame_size;
+  if (int rc = ctx->ws_rate_a.reserve (n44 * C * sizeof (float))) return rc;
+  if (int rc = ctx->ws_rate_b.reserve (n44 * C * sizeof (float))) return rc;
+  if (int rc = ctx->ws_rate_c.reserve (n_frames * C * sizeof (float))) return rc;
+  float *x44 = ctx->ws_rate_a.as<float>(), *wm44 = ctx->ws_rate_b.as<float>(), *wm = ctx->ws_rate_c.as<float>();
+  {
+    awmk::ResampleArgs ra = resample_table_args (*down.fixed, C);
+    ra.in = reinterpret_cast<const float *> (pcm_in_d);
+    ra.n_in = (long long) n_frames;
+    ra.out = x44;
+    ra.n_out = (long long) n44;
+    ProfScope ps (ctx, PROF_RESAMPLE_S16, double (n_frames) * C * 2.0 + double (n44) * C * 4.0);
+    AWM_HIP_CHECK (awmk::launch_resample_s16 (ctx->stream, ra));
+  }
+  {
+    awmk::AddMixArgs a {};
+    a.pcm_in = x44;
+    a.out = wm44;
+    a.n_frames = (long long) n44;
+    a.n_channels = C;
+    a.frame_mod = frame_mod_dev;
+    fill_add_mix_common (a, water_delta);
+    a.frames_per_span = frames_per_span (ctx, (long long) (F + 1));
+    a.delta_only = 1;
+    ProfScope ps (ctx, PROF_ADD_MIX, double (n44) * C * 8.0);
+    AWM_HIP_CHECK (awmk::launch_add_mix (ctx->stream, ctx->tabs, a));
+  }
+  if (int rc = resample_device (ctx, up, wm44, F * Params::frame_size, C, wm, n_frames)) return rc;
+  const int lim_block = int (size_t (rate) * size_t (Params::limiter_block_size_ms) / 1000);
+  const size_t n_blocks = n_frames / lim_block + 2;
+  float *block_max = nullptr;
+  if (use_limiter)
+    {
+      if (int rc = ctx->ws_block_max.reserve (n_blocks * sizeof (float))) return rc;
+      block_max = ctx->ws_block_max.as<float>();
+      if (int rc = awm_add_init_block_max_d (ctx, block_max, n_blocks)) return rc;
+      const awmk::MixSegment seg { reinterpret_cast<const float *> (pcm_in_d), wm, nullptr, (long long) n_frames, 0, 0,
+                                   reinterpret_cast<unsigned int *> (block_max), 0, (long long) n_blocks };
+      AWM_HIP_CHECK (awmk::launch_max_segment_s16 (ctx->stream, seg, C, lim_block));
+    }
+  return limit_encode_pass (ctx, ctx, wm, out_d, n_frames, C, 0, block_max, 0, n_blocks, lim_block, pcm_in_d);
+}
+
+/* the definition, on the context's stream: decode into a float workspace, the float call into a second one, encode into out_d */
+static int
+add_s16_by_definition (awm_ctx *ctx, const int16_t *pcm_in_d, int16_t *out_d, size_t n_frames, int n_channels, const int8_t *frame_mod_dev,
+                       int sample_rate, ReadyMarks *marks = nullptr)
+{
+  const size_t n_values = n_frames * size_t (n_channels);
+  if (int rc = ctx->ws_pcm.reserve (n_values * sizeof (float))) return rc;
+  if (int rc = ctx->ws_add_mix.reserve (n_values * sizeof (float))) return rc;
+  float *f = ctx->ws_pcm.as<float>(), *g = ctx->ws_add_mix.as<float>();
+  {
+    ProfScope ps (ctx, PROF_PCM_DECODE, double (n_values) * 6.0);
+    AWM_HIP_CHECK (awmk::launch_pcm_decode (ctx->stream, reinterpret_cast<const unsigned char *> (pcm_in_d), f, (long long) n_values,
+                                            awmk::PcmFormatDev { 2, 0, 0, 0 }));
+  }
+  const int rc = sample_rate != Params::mark_sample_rate
+               ? add_full_rate (ctx, f, g, n_frames, n_channels, frame_mod_dev, params().water_delta, !params().test_no_limiter, sample_rate)
+               : add_full (ctx, f, g, n_frames, n_channels, frame_mod_dev, params().water_delta, !params().test_no_limiter);
+  if (rc)
+    return rc;
+  ProfScope ps (ctx, PROF_PCM_ENCODE, double (n_values) * 6.0);
+  AWM_HIP_CHECK (awmk::launch_pcm_encode (ctx->stream, g, reinterpret_cast<unsigned char *> (out_d), (long long) n_values,
+                                          awmk::PcmFormatDev { 2, 0, 0, 1 }));
+  return 0;
+}
+
+/* both pipeline calls behind their checks; marks: awm_add_get_watermark_s16_d at 44.1 kHz (armed by the fused path only) */
+static int
+add_watermark_s16 (awm_ctx *ctx, FrameModTable *fm, const int16_t *pcm_in_d, int16_t *out_d, size_t n_frames, int n_channels, int sample_rate,
+                   ReadyMarks *marks)
+{
+  g_add_s16_fused_in_use = 0;
+  if (!n_frames)
+    return 0;
+  const int8_t *table = fm->dev.as<int8_t>();
+  const int use_limiter = !params().test_no_limiter;
+  if (sample_rate == Params::mark_sample_rate)
+    {
+      g_add_s16_fused_in_use = 1;
+      return add_full_s16 (ctx, pcm_in_d, out_d, n_frames, n_channels, table, params().water_delta, use_limiter, nullptr, marks);
+    }
+  const RateConverter down = rate_converter (ctx, sample_rate, Params::mark_sample_rate);
+  const RateConverter up = rate_converter (ctx, Params::mark_sample_rate, sample_rate);
+  const int lim_block = int (size_t (sample_rate) * size_t (Params::limiter_block_size_ms) / 1000);
+  const bool aligned = ((reinterpret_cast<uintptr_t> (pcm_in_d) | reinterpret_cast<uintptr_t> (out_d)) & 3) == 0;
+  if (down.fixed && up.fixed && n_channels == 2 && aligned && lim_block >= 8192 && !ctx->snr_on)
+    {
+      g_add_s16_fused_in_use = 1;
+      return add_full_rate_s16 (ctx, pcm_in_d, out_d, n_frames, table, params().water_delta, use_limiter, sample_rate, down, up);
+    }
+  return add_s16_by_definition (ctx, pcm_in_d, out_d, n_frames, n_channels, table, sample_rate);
+}
+
+int
+awm_add_watermark_s16_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, const int16_t *pcm_in_d, int16_t *out_d,
+                         size_t n_frames, int n_channels, int sample_rate)
+{
+  AWM_ENTER (ctx);
+  if (int rc = check_add_s16 (ctx, "awm_add_watermark_s16_d", pcm_in_d, out_d, n_frames, n_channels, sample_rate))
+    return rc;
+  FrameModTable *fm = ctx->get_frame_mod (capi_key (key), payload_hex ? payload_hex : "");
+  if (!fm)
+    return AWM_ERR_ARG;
+  return add_watermark_s16 (ctx, fm, pcm_in_d, out_d, n_frames, n_channels, sample_rate, nullptr);
+}
+
+int
+awm_add_get_watermark_s16_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, const int16_t *pcm_in_d, int16_t *out_d,
+                             size_t n_frames, int n_channels, int sample_rate, size_t max_out, awm_pattern *out)
+{
+  AWM_ENTER (ctx);
+  if (max_out && !out)
+    {
+      set_error ("awm_add_get_watermark_s16_d: bad argument");
+      return AWM_ERR_ARG;
+    }
+  if (int rc = check_add_s16 (ctx, "awm_add_get_watermark_s16_d", pcm_in_d, out_d, n_frames, n_channels, sample_rate))
+    return rc;
+  if (int rc = check_stream_s16 ("awm_add_get_watermark_s16_d", out_d, n_frames, n_channels))       // (what the `get` half would refuse)
+    return rc;
+  FrameModTable *fm = ctx->get_frame_mod (capi_key (key), payload_hex ? payload_hex : "");
+  if (!fm)
+    return AWM_ERR_ARG;
+  // the hand-over of awm_add_get_watermark_d: `get` starts a chunk once the last pass has passed the chunk's end
+  const bool hand_over = sample_rate == Params::mark_sample_rate && n_frames > 0;
+  int rc = add_watermark_s16 (ctx, fm, pcm_in_d, out_d, n_frames, n_channels, sample_rate, hand_over ? &ctx->ready : nullptr);
+  if (!rc)
+    rc = awm_get_watermark_rate_s16_d (ctx, key, out_d, n_frames, n_channels, sample_rate, max_out, out);
+  ctx->ready.disarm();
+  return rc;
 }
 
 /* add_watermark for many independent inputs with one key and payload (BASELINE config 5: a batch of short clips).  A 30 s clip

@@ -188,7 +188,7 @@ struct FileStaging
 // the fused entry point arms them: two separate calls cannot know what the caller queued on the stream in between.
 struct ReadyMarks
 {
-  const float *base = nullptr;           // the output buffer the marks belong to
+  const void  *base = nullptr;           // the output buffer the marks belong to (float values, or the int16 values of awm_add_get_watermark_s16_d)
   size_t       n_frames = 0;
   bool         armed = false;
   std::vector<std::pair<size_t, hipEvent_t>> marks;    // (samples per channel that are final, event) in stream order
@@ -251,7 +251,8 @@ struct WorkLane
             ws_viterbi, ws_viterbi_in, ws_viterbi_bits, ws_viterbi_err, ws_viterbi_sync, ws_block_max, ws_clip, ws_idx, ws_limit_tab, ws_jobs, ws_group, ws_keytab, ws_keytab_aux, ws_keytab_scratch;
   DevBuffer ws_rate;                                       // `get` of material at another rate (wmget.cc resample_to_mark_rate): the 44.1 kHz copy of the clip this lane works on
   DevBuffer ws_pcm;                                        // `get` of a batch of 16-bit clips (wmget.cc decode_clip_on_lane): the float copy of the clip this lane works on -- long clips, VResampler rates, speed search; the groups never use it
-  DevBuffer ws_shard_edge, ws_shard_tail, ws_shard_q;      // multi-GPU protocol (wmshard.cc): edge frames, stitched tail buffer, score blocks
+  DevBuffer ws_add_mix;                                    // `add` of a whole stream from and to 16-bit PCM (capi_kernels.cc add_full_s16): the un-limited float mix between K2 and the last pass; through the definition, the float result (ws_pcm: the decoded input)
+  DevBuffer ws_shard_edge, ws_shard_tail, ws_shard_q;     // multi-GPU protocol (wmshard.cc): edge frames, stitched tail buffer, score blocks
   // host staging (two refinement slots: see SyncFinder::SearchJob)
   PinnedBuffer pin_refine_in[2], pin_refine_q[2], pin_peaks, pin_blocks, pin_jobs, pin_bits, pin_small, pin_group, pin_shard, pin_shard_up, pin_keytab;
   hipEvent_t   ev_refine[2] = { nullptr, nullptr };

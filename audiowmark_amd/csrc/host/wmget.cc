@@ -666,7 +666,7 @@ block_decoder_run (awm_ctx *ctx, WorkLane *home, bool spread, const std::vector<
   // The file level `get` (host/wmfile.cc) arms LIVE marks: a loader thread is still bringing the stream in (its copies and sample decodes
   // on the copy stream, a mark behind every tile) while this function starts the chunks: every lane, the context's own included, waits for
   // the mark that covers its chunk -- on the host first, until the loader has recorded it.
-  ReadyMarks *marks = (spread && lane_base == 0 && lanes.size() > 1 && ctx->ready.armed && ctx->ready.base == stream.data
+  ReadyMarks *marks = (spread && lane_base == 0 && lanes.size() > 1 && ctx->ready.armed && ctx->ready.base == static_cast<const void *> (stream.pcm_arg())
                        && ctx->ready.n_frames == stream.n_frames && (ctx->ready.live || !ctx->ready.marks.empty())) ? &ctx->ready : nullptr;
   if (marks && !marks->live)
     std::rotate (lanes.begin(), lanes.begin() + 1, lanes.end());

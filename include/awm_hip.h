@@ -133,6 +133,22 @@ int awm_add_mix_d (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_f
                    float *block_max_d /* may be NULL: no limiter */, size_t first_block, size_t n_blocks);
 int awm_add_limit_d (awm_ctx *ctx, float *out_d, size_t n_frames, int n_channels, size_t first_sample,
                      const float *block_max_d, size_t first_block, size_t n_blocks);
+/* The two halves on SIGNED 16-BIT PCM (whole streams from and to 16-bit PCM: awm_add_watermark_s16_d below).
+ * awm_add_mix_s16_d is K2 instantiated for 16-bit input, span form included: pcm_in_d and the halos are int16 values (little-endian,
+ * interleaved, any even address), converted where they leave global memory; out_d (float) and block_max_d are bit for bit what
+ * awm_add_mix_d writes for the stream and the halos decoded by awm_pcm_decode_d (float (v) * (1 / 32768)).  The rules are awm_add_mix_d's:
+ * the span starts on a frame boundary, a NULL block_max_d means no limiter, the maxima are pre-initialised with awm_add_init_block_max_d.
+ * awm_add_limit_s16_d is the last pass: out_d (int16) is value for value what awm_pcm_encode_d (..., 16, 0, 0, direct16 = 1, out_d) writes
+ * for what awm_add_limit_d leaves in a copy of mix_d -- ramp, v * 32768, saturated at 32767 and -32768, truncated, in one pass.  mix_d is
+ * not modified, nothing outside [out_d, out_d + n C) is written; block_max_d NULL: no ramp.  Stereo on a 4-byte aligned out_d stores
+ * groups of four frames (16 bytes), mono groups of eight values, everything else a value per thread.
+ * AWM_ERR_ARG with nothing enqueued: a NULL pointer with n_frames > 0, n_channels < 1, an int16 pointer at an odd address. */
+int awm_add_mix_s16_d (awm_ctx *ctx, const int16_t *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
+                       const int8_t *frame_mod, double water_delta, size_t first_frame,
+                       const int16_t *halo_before_d, const int16_t *halo_after_d,
+                       float *block_max_d /* may be NULL: no limiter */, size_t first_block, size_t n_blocks);
+int awm_add_limit_s16_d (awm_ctx *ctx, const float *mix_d, int16_t *out_d, size_t n_frames, int n_channels, size_t first_sample,
+                         const float *block_max_d /* NULL: no ramp */, size_t first_block, size_t n_blocks);
 int awm_add_d (awm_ctx *ctx, const float *pcm_in_d, float *out_d, size_t n_frames, int n_channels,
                const int8_t *frame_mod, double water_delta, int use_limiter);
 /* awm_add_mix_d for ONE span and n_payloads tables: out_d[p] (and, with a limiter, block_max_d[p]) receive what awm_add_mix_d writes
@@ -503,6 +519,35 @@ int awm_get_watermark_d (awm_ctx *ctx, const uint8_t key[16], const float *pcm_d
  * cannot: the caller may have queued other work on the buffer in between).  Returns the pattern count or an error code. */
 int awm_add_get_watermark_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, const float *pcm_in_d, float *out_d,
                              size_t n_frames, int n_channels, int sample_rate, size_t max_out, awm_pattern *out);
+/* WHOLE STREAMS FROM AND TO SIGNED 16-BIT PCM (little-endian, interleaved): `add`, and "watermark, then verify", on the 16-bit original
+ * (DESIGN.md section 9.10).  pcm_in_d = n_frames frames of n_channels int16 values, out_d the same (device pointers).
+ * Definition: with f = what awm_pcm_decode_d (ctx, pcm_in_d, n C, 16, 0, 0, f) writes -- float (v) * (1 / 32768), exact -- and g = what
+ * awm_add_watermark_d writes for f, awm_add_watermark_s16_d writes to out_d, value for value, what awm_pcm_encode_d (ctx, g, n C, 16, 0, 0,
+ * 1, out_d) writes: v * 32768, saturated at 32767 and -32768, truncated (the reference's native rule, rawconverter.cc:197-198).
+ * awm_add_get_watermark_s16_d writes the same out_d and returns what awm_get_watermark_rate_s16_d returns on it, field for field; at
+ * 44.1 kHz with the hand-over of awm_add_get_watermark_d: `get` starts a chunk once the last pass has passed the chunk's end.
+ * The context's parameters apply as for awm_add_watermark_d (test_no_limiter, water_delta, frames_per_bit, the SNR meter).
+ * Paths.  At 44.1 kHz, every channel count and any even address: K2 reads the int16 values itself (converted where they leave global
+ * memory) and writes the un-limited float mix into a grow-only workspace of the context (n C 4 bytes, given back by awm_ctx_trim); one
+ * last pass applies the limiter's ramp, encodes and stores int16 -- two passes, 12 bytes per value, no decode and no encode launch.
+ * At a rate the fixed-ratio resampler takes both ways (48, 32, 96, 22.05, 88.2 kHz ...), stereo with both pointers 4-byte aligned and a
+ * limiter block of at least 8192 samples: the down-resampler reads the int16 values, K2 writes the watermark signal alone, the
+ * up-resampler brings it to the rate, the block maxima come from decode (in) + wm without a stored mix, and the last pass computes that
+ * sum again, applies the ramp, encodes and stores.  Everything else (mono or three channels at a rate, 2-byte-only addresses at a rate,
+ * rates that only the VResampler takes such as 44101, a call at a rate while the SNR meter is armed) goes through the definition on the context's
+ * stream: decode into a float workspace, awm_add_watermark_d into a second one, encode into out_d; awm_ctx_trim gives both back.
+ * awm_debug_add_s16_fused_in_use () tells which path ran.
+ * out_d == pcm_in_d exactly is allowed: at 44.1 kHz the input has been consumed before the first int16 is stored; at a rate a frame of
+ * the input is read for the last time by the thread that overwrites it.  n_frames == 0 returns 0 and writes nothing.
+ * AWM_ERR_ARG with nothing enqueued and the outputs untouched: a NULL pointer with n_frames > 0, n_channels < 1, an int16 pointer at an
+ * odd address, a payload that does not parse, a rate that neither zita class takes, an output that overlaps the input partially, and
+ * (awm_add_get_watermark_s16_d) max_out > 0 with out == NULL.
+ * Not offered from 16-bit input: many payloads (awm_add_watermark_payloads_d), the clip batches (awm_add_watermark_batch*_d), the tile
+ * stream, the file level and the command line, the sharded and awm_multi_* forms, other sample formats. */
+int awm_add_watermark_s16_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, const int16_t *pcm_in_d, int16_t *out_d,
+                             size_t n_frames, int n_channels, int sample_rate);
+int awm_add_get_watermark_s16_d (awm_ctx *ctx, const uint8_t key[16], const char *payload_hex, const int16_t *pcm_in_d, int16_t *out_d,
+                                 size_t n_frames, int n_channels, int sample_rate, size_t max_out, awm_pattern *out);
 /* The reference's get_watermark takes a LIST of keys (wmcommon.hh:228, `--key a --key b`, tests/key-test.sh:13-37): the file is
  * read once, the approximate dB matrices of a chunk / of a padded clip are computed once and shared by the keys
  * (syncfinder.cc:171-256), patterns are sorted by time with the key list order breaking ties (wmget.cc:288-316).
@@ -616,9 +661,9 @@ int awm_get_watermark_batch_keys_rates_s16_d (awm_ctx *ctx, const uint8_t *keys,
  * the float twin refuses; and any call while awm_debug_set_refine_form selects a form other than the default (4) -- only the default
  * forms of K4s have 16-bit instantiations.  n_frames == 0 behaves like the float twin.
  * Not offered: the file level and the command line, which convert their files' formats themselves (keeping a 16-bit WAV's bytes as the
- * resident stream is the obvious follow-up); awm_decode_chunk*_d, awm_add_get_watermark_d, the sharded and awm_multi_* forms; other
- * sample formats; the `add` side for whole streams; the speed search (K12, K15) on 16-bit input; the clip batches have forms of their
- * own above, whose long clips keep their present path. */
+ * resident stream is the obvious follow-up); awm_decode_chunk*_d, the sharded and awm_multi_* forms; other sample formats; the speed
+ * search (K12, K15) on 16-bit input; the clip batches have forms of their own above, whose long clips keep their present path.  The `add`
+ * side for whole streams and "watermark, then verify": awm_add_watermark_s16_d and awm_add_get_watermark_s16_d. */
 int awm_get_watermark_s16_d (awm_ctx *ctx, const uint8_t key[16], const int16_t *pcm_d, size_t n_frames, int n_channels,
                              size_t max_out, awm_pattern *out);
 int awm_get_watermark_keys_s16_d (awm_ctx *ctx, const uint8_t *keys, int n_keys, const int16_t *pcm_d, size_t n_frames, int n_channels,
@@ -968,6 +1013,7 @@ void awm_debug_set_add_payloads_rate_fused (int mode);  /* awm_add_watermark_pay
                                                          * down-resample + K2m, then K10 and K11 per output | 0 a loop over the single-payload path (as awm_debug_set_add_payloads_fused (0) at every rate) */
 int  awm_debug_add_payloads_rate_fused_in_use (void);   /* which of these the last awm_add_watermark_payloads_d took: 2 | 1 (also: not stereo, another fixed ratio than 44.1 -> 48 kHz, a pointer
                                                          * that is only 4-byte aligned) | 0 (also: 44.1 kHz, one payload, a VResampler rate, workspaces that could not be reserved) */
+int  awm_debug_add_s16_fused_in_use (void);       /* 1 if the last awm_add_watermark_s16_d / awm_add_get_watermark_s16_d ran without a decode and an encode of the stream, 0 if it went through the definition */
 int  awm_debug_add_segments_fused_in_use (void);  /* 1 if the last awm_add_watermark_segments_d / _rate_d / _keys_d / _keys_rate_d took the fused path (one launch per stage), 0: segment by segment */
 int  awm_debug_payload_tables_d (awm_ctx *ctx, const uint8_t key[16], const char *const *payload_hex, size_t n_payloads, int8_t *tables_out);
 /* K16t alone: the templates of n_keys keys (16 bytes each) built on the device, 256 keys per launch, copied to out: n_keys x 360624 int16
@@ -1004,6 +1050,8 @@ void awm_debug_clip_form_launches (long out[3]); /* clip batches: stage 0 kernel
                                             * profiling scopes count a group's stage 0 as one launch whatever its forms) */
 size_t awm_debug_lane_pcm_bytes (awm_ctx *ctx); /* bytes the context's lanes hold as float copies of 16-bit clips (long clips, VResampler rates, speed search): 0 after
                                             * awm_ctx_trim and for as long as the 16-bit batches see short clips only */
+size_t awm_debug_lane_add_mix_bytes (awm_ctx *ctx); /* bytes the context's lanes hold as the float mix of awm_add_watermark_s16_d (through the definition: its float result;
+                                            * the decoded input counts under awm_debug_lane_pcm_bytes): 0 after awm_ctx_trim */
 void awm_debug_set_clip_pad_margin (int frames); /* clip batches: frames of zeros written on either side of a clip (default and minimum 2048; one slice = 6693 frames
                                             * or more: whole slices, the A side of the measurement in tools/gpu_clip_margin_ab.py) */
 void awm_debug_set_staged_threads (int n);  /* clip batches: host threads (= lanes) working on groups of clips; 0 = default (4; 2 with a key per clip only where the
